@@ -3,7 +3,7 @@
 SED hot-path benchmark (contract: see the task's bench.py section).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--summation coherent]
-                    [--shard auto|k|frames]
+                    [--shard auto|k|frames] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one synthetic trajectory already resident in HBM:
 phase table -> k-projection (split-precision f16 MFMA from the group's cached split planes,
@@ -67,6 +67,7 @@ FLOP_PER_UNIT = 12                # 3 components x (re, im) x FMA per (k, t, ato
 K1_UNITS_PER_S = 4.3e13           # slope of the planes kernel's time over the k-count
 HBM_BOUND_K1_BPS = 6.2e12         # trajectory bytes per second of its HBM-bound small-K variant
 XGMI_LINK_BPS = 64e9              # one direction of one xGMI link
+DUMP_BUDGET_BYTES = 48 << 20      # --dump-outputs: bytes of array data written in all (the limit is 64 MB)
 
 
 def parse_args(argv=None):
@@ -99,7 +100,12 @@ def parse_args(argv=None):
     ap.add_argument("--stub-engine", action="store_true",
                     help="TEST ONLY: run the orchestration (spawn, rendezvous, sharding, host exchange, JSON) with an "
                          "engine that computes nothing; the line is marked and carries no measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result of the last one as DIR/<name>.npy (float32; rank 0)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # --------------------------------------------------------------------------- self-launch
@@ -416,6 +422,8 @@ def main():
     first_step_s = time.perf_counter() - t0
     oneoff = engine.oneoff_stats()                               # plan build, magnitude pass, plane build
     elapsed, stages_by_rank, (k1_n, k1_ms) = measure(args.steps, max(0, args.warmup - 1))
+    if args.dump_outputs and group.has_result:
+        dump_outputs(Path(args.dump_outputs), engine, T, K, intensity_out)
     _, k_cnt = group.ranges(K, T)
     real = not args.stub_engine
 
@@ -720,6 +728,31 @@ def main():
     exchange.barrier()
     group.close()
     engine.close()
+
+
+def dump_outputs(out_dir: Path, engine, T: int, K: int, intensity_out: bool):
+    """--dump-outputs: what the last timed step left on the device, fetched the way a caller of that
+    path receives it (finalize transposes the slab again; the slab itself is not recomputed): `sed`
+    (T,K,3) complex64 and `intensity` (T,K) float32, or the (T,K) float32 `sed` of an intensity
+    result.  Complex values are written as float32 (..., 2) = (real, imag).  Above DUMP_BUDGET_BYTES a
+    fixed seeded sample of frequency rows is written, the same rows in every file; `rows.npy` holds
+    their indices (float64)."""
+    import numpy as np
+    if intensity_out:
+        arrays = {"sed": engine.finalize(T, K, True)}
+    else:
+        sed, inten = engine.finalize(T, K, False, with_intensity=True)
+        arrays = {"sed": sed, "intensity": inten}
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    n_rows = max(1, min(T, DUMP_BUDGET_BYTES // row_bytes))
+    rows = np.arange(T) if n_rows == T else np.sort(np.random.default_rng(0).choice(T, n_rows, replace=False))
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "rows.npy", rows.astype(np.float64))
+    for name, a in arrays.items():
+        s = np.ascontiguousarray(a[rows])
+        if np.iscomplexobj(s):
+            s = s.view(np.float32).reshape(s.shape + (2,))
+        np.save(out_dir / f"{name}.npy", s)
 
 
 def first_call_probe(engine):
