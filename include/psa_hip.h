@@ -126,6 +126,21 @@ int         psa_set_k1(psa_ctx* ctx, int selector);     /* PSA_K1_* */
  *                             per 128 rows and stage instead of 40).  Same arithmetic; the float32 fold
  *                             comes every 10 stages instead of every 8. */
 #define PSA_OPT_K1_WIDE         7
+/*   PSA_OPT_K1_LOWRANK    [1] k-lists on one line (k-paths) are projected as 64 node rows of exact phases
+ *                             (the 128-row planes kernel), one float16 product of the difference to the
+ *                             reference's float32 phases with the hi plane (k1_planes_diff.hip) and a
+ *                             combine; planned per group on the host (api_lowrank.hip), else the dense
+ *                             kernels.  Environment PSA_K1_LOWRANK=0/1 sets it at context creation.
+ *   PSA_OPT_K1_LOWRANK_MIN_K [256] shortest whole k-list (K_total) the route serves.  Environment
+ *                             PSA_K1_LOWRANK_MIN_K.
+ *   PSA_OPT_K1_LOWRANK_MIN_LOCAL [128] shortest part of such a list one projection launch serves (the
+ *                             D pass works in 512-row blocks: a 128-vector part is a half-empty one).
+ *                             A list split over calls of one process keeps the route for every part of
+ *                             >= 128; psa_amd.dist sets 256 on the ranks of a k-sharded run, where a
+ *                             128-vector shard is faster on the dense kernels. */
+#define PSA_OPT_K1_LOWRANK      8
+#define PSA_OPT_K1_LOWRANK_MIN_K 9
+#define PSA_OPT_K1_LOWRANK_MIN_LOCAL 10
 int         psa_set_option(psa_ctx* ctx, int option, int64_t value);
 /* device name / CU count / HBM bytes of the context's GPU */
 int         psa_device_info(psa_ctx* ctx, char* name, int name_len,
@@ -238,6 +253,13 @@ int psa_k_pairs(const float* k_vectors, int64_t K, int32_t* kmap /* K */,
  * and conjugated where bit 31 is set. */
 int psa_sed_set_kmap(psa_ctx* ctx, const int32_t* kmap, int64_t K_out);
 
+/* The low-rank plan of a k-list for one atom group (api_lowrank.hip) as a host-only service for tests:
+ * *ok = 1 when the route serves; geo[12] = u (3), k0 (3), x_c, h_x, interval width, interval id, bound on
+ * |D|, scale of D; kappa[64] the nodes, C[K * 64 * 2] the complex64 combine matrix (either may be null).
+ * No context, no GPU. */
+int psa_lowrank_plan(const float* k_vectors, int64_t K, const float* mean_pos_all, int64_t N, const int32_t* idx,
+                     int64_t n_g, int32_t* ok, double* geo, double* kappa, float* C);
+
 /* One (k, omega) bin: S[c] = FFT_t(q)[i_w] / T for ONE k-vector and one atom group, as 3
  * complex64 -- what iSED consumes of a group's spectrum (sed_calculator.py:483, :494-499: only
  * sed[i_w, i_k, :] of the full path spectrum is used).  One pass over the trajectory and one DFT
@@ -267,6 +289,8 @@ int psa_last_timings(psa_ctx* ctx, double* ms /* [8] */);
 /* number of projection-kernel launches and their summed duration (HIP events on
  * the context's stream) since the last call of this function */
 int psa_k1_stats(psa_ctx* ctx, int64_t* launches, double* total_ms);
+/* projection launches of the context's life that took the low-rank route for k-paths (PSA_OPT_K1_LOWRANK) */
+int psa_k1_lowrank_launches(psa_ctx* ctx, int64_t* launches);
 /* host wall clock (ms) of work that is done once and then cached, summed since the last call:
  * [0] rocFFT plan builds (run-time compiled per (T, batch))  [1] largest-magnitude passes
  * [2] split-plane builds  [3] trajectory uploads (psa_data_upload / psa_sed_project_upload) */

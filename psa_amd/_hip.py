@@ -24,6 +24,9 @@ K1_AUTO, K1_WAVE, K1_MFMA32, K1_SPLIT_BF16 = 0, 1, 2, 3
 OPT_PLANES, OPT_PLANES_BUDGET, OPT_PLANES_EAGER, OPT_PLANES_MIN_K, OPT_FOLD_PAIRS, OPT_FFT_PRIME = 0, 1, 2, 3, 4, 5
 OPT_K1_LOADER_WAVES = 6
 OPT_K1_WIDE = 7
+OPT_K1_LOWRANK = 8
+OPT_K1_LOWRANK_MIN_K = 9
+OPT_K1_LOWRANK_MIN_LOCAL = 10
 KMAP_MIRROR = 0x80000000
 ABI_VERSION = 3
 UNIQUE_ID_BYTES = 128
@@ -64,6 +67,8 @@ SIGNATURES = {
     "psa_sed_calculate": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p, _i64p,
                                     C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, _f32p, C.c_size_t]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
+    "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double), _f32p]),
     "psa_sed_set_kmap": (C.c_int, [_ctx, _i32p, C.c_int64]),
     "psa_sed_single_bin": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, _i32p, C.c_int64, C.c_int32, C.c_int64, _f32p]),
     "psa_slab_read": (C.c_int, [_ctx, C.c_int64, C.c_int64, C.c_void_p]),
@@ -72,6 +77,7 @@ SIGNATURES = {
     "psa_result_chiral_phase": (C.c_int, [_ctx, C.c_int, C.c_int, _f32p, C.c_size_t]),
     "psa_last_timings": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
     "psa_k1_stats": (C.c_int, [_ctx, _i64p, C.POINTER(C.c_double)]),
+    "psa_k1_lowrank_launches": (C.c_int, [_ctx, _i64p]),
     "psa_oneoff_stats": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
     "psa_debug_phase_table": (C.c_int, [_ctx, _f32p, _f32p, C.c_int64, _i32p, C.c_int64,
                                         C.c_int64, C.c_void_p]),
@@ -160,6 +166,27 @@ def k_pairs(k_vectors):
     _check(load_library().psa_k_pairs(_f32(kv), K, kmap.ctypes.data_as(_i32p), uidx.ctypes.data_as(_i32p), C.byref(n)),
            "psa_k_pairs")
     return kmap.view(np.uint32), uidx[:n.value].copy()
+
+
+def lowrank_plan(k_vectors, mean_pos_all, idx=None):
+    """The low-rank plan of a k-list for one atom group (psa_lowrank_plan; host only): None when the list stays on
+    the dense kernels, else a dict with u, k0, x_c, h_x, width, interval, d_bound, dscale, kappa (64,) and
+    C (K, 64) complex64."""
+    kv = _as_f32(k_vectors, (3,))
+    mean = _as_f32(mean_pos_all, (3,))
+    K, N = kv.shape[0], mean.shape[0]
+    ix = None if idx is None else np.ascontiguousarray(idx, np.int32)
+    n_g = N if ix is None else ix.size
+    ok, geo = C.c_int32(0), np.zeros(12, np.float64)
+    kappa, cm = np.zeros(64, np.float64), np.zeros((K, 64), np.complex64)
+    dp = C.POINTER(C.c_double)
+    _check(load_library().psa_lowrank_plan(_f32(kv), K, _f32(mean), N, None if ix is None else ix.ctypes.data_as(_i32p), n_g,
+                                           C.byref(ok), geo.ctypes.data_as(dp), kappa.ctypes.data_as(dp),
+                                           cm.ctypes.data_as(_f32p)), "psa_lowrank_plan")
+    if not ok.value:
+        return None
+    return {"u": geo[0:3].copy(), "k0": geo[3:6].copy(), "x_c": geo[6], "h_x": geo[7], "width": geo[8],
+            "interval": int(geo[9]), "d_bound": geo[10], "dscale": geo[11], "kappa": kappa, "C": cm}
 
 
 def host_mean_frames(x: np.ndarray, threads: int = 0) -> np.ndarray:
@@ -597,6 +624,12 @@ class Engine:
         n, ms = C.c_int64(0), C.c_double(0.0)
         _check(self._lib.psa_k1_stats(self._h, C.byref(n), C.byref(ms)), "psa_k1_stats")
         return n.value, ms.value
+
+    def lowrank_launches(self) -> int:
+        """Projection launches so far that took the low-rank route for k-paths (PSA_OPT_K1_LOWRANK)."""
+        n = C.c_int64(0)
+        _check(self._lib.psa_k1_lowrank_launches(self._h, C.byref(n)), "psa_k1_lowrank_launches")
+        return n.value
 
     # -- diagnostics -----------------------------------------------------------------
     def debug_phase_table(self, mean_pos_all, k_vectors, idx=None) -> np.ndarray:

@@ -232,6 +232,9 @@ int psa_create(int device, psa_ctx** out) {
     psa_ctx* c = new psa_ctx();
     c->device = device;
     c->compute_units = prop.multiProcessorCount;
+    // A/B switches of the low-rank route, read once here (psa_set_option overrides them)
+    if (const char* v = std::getenv("PSA_K1_LOWRANK")) c->opt_k1_lowrank = std::atoi(v) != 0;
+    if (const char* v = std::getenv("PSA_K1_LOWRANK_MIN_K")) c->opt_k1_lowrank_min_k = std::max(1, std::atoi(v));
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
@@ -321,6 +324,21 @@ int psa_set_option(psa_ctx* c, int option, int64_t value) {
         case PSA_OPT_FFT_PRIME: c->opt_fft_prime = value != 0; return PSA_OK;
         case PSA_OPT_K1_LOADER_WAVES: c->opt_k1_loader_waves = value != 0; return PSA_OK;
         case PSA_OPT_K1_WIDE: c->opt_k1_wide = value != 0; return PSA_OK;
+        case PSA_OPT_K1_LOWRANK:
+            c->opt_k1_lowrank = value != 0;
+            if (!c->opt_k1_lowrank) {
+                PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+                for (psa::DevBuf* b : {&c->d_lr_diff, &c->d_lr_qn, &c->d_lr_C, &c->d_lr_f64}) b->release();
+            }
+            return PSA_OK;
+        case PSA_OPT_K1_LOWRANK_MIN_LOCAL:
+            PSA_REQUIRE(value >= 1, "PSA_OPT_K1_LOWRANK_MIN_LOCAL must be >= 1");
+            c->opt_k1_lowrank_min_local = value;
+            return PSA_OK;
+        case PSA_OPT_K1_LOWRANK_MIN_K:
+            PSA_REQUIRE(value >= 1, "PSA_OPT_K1_LOWRANK_MIN_K must be >= 1");
+            c->opt_k1_lowrank_min_k = value;
+            return PSA_OK;
     }
     set_error("unknown option %d", option);
     return PSA_EINVAL;
@@ -360,6 +378,13 @@ int psa_oneoff_stats(psa_ctx* c, double* ms) {
         ms[i] = c->oneoff_ms[i];
         c->oneoff_ms[i] = 0.0;
     }
+    return PSA_OK;
+}
+
+int psa_k1_lowrank_launches(psa_ctx* c, int64_t* launches) {
+    PSA_TRY(enter(c));
+    PSA_REQUIRE(launches != nullptr, "null argument");
+    *launches = c->lowrank_launches;
     return PSA_OK;
 }
 

@@ -7,6 +7,7 @@
 #pragma once
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -86,6 +87,22 @@ int    group_source(psa_ctx* c, int* slot_io, bool* disp_io, const float* mean_h
                     int64_t n_g, int64_t K, PlaneSet** ps);
 void   fold_pairs(const float* k, int64_t K, std::vector<int32_t>* kmap, std::vector<int32_t>* unique_idx);
 int    install_kmap(psa_ctx* c, const std::vector<int32_t>& kmap);
+// api_lowrank.hip: the plan of the low-rank route for k-paths (ok = false: the list stays on the dense kernels; why)
+struct LowRankPlan {
+    bool                ok = false;
+    const char*         why = "";
+    double              u[3] = {0, 0, 0}, k0[3] = {0, 0, 0};   // the line: k0 + kappa u
+    double              x_c = 0, h_x = 0, width = 0;          // the group's centre / half-width along u; node interval width
+    int64_t             interval = 0;                         // node interval [interval * width, + width)
+    double              kappa[LOWRANK_NODES] = {};            // the nodes
+    double              d_bound = 0;                          // bound on |P_ref - P_line|
+    float               dscale = 0.f;                         // power of two the D image carries
+    std::vector<double> kline;                                // (K, 3) the k-vectors projected on the line
+    std::vector<float>  C;                                    // (K, 64) complex64 combine matrix
+};
+int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, const int32_t* h_idx, int64_t n_g, LowRankPlan* p);
+int prepare_lowrank(psa_ctx* c, int slot, const float* k_host, int64_t nk, int64_t K_total, const float* mean_all,
+                    const int32_t* h_idx, const PlaneSet* ps, ProjGeom* g);
 int    begin_result(psa_ctx* c, int64_t T, int64_t K_total, int64_t k_offset, bool intensity, char** rows, size_t* row_bytes);
 
 }  // namespace psa

@@ -1,0 +1,235 @@
+// Low-rank route for k-paths: the host plan (the device half is k1_planes_diff.hip).
+//
+// All vectors of a k-path lie on one line, k_j = k0 + kappa_j u.  With x_a = u.r_a,
+//     exp(i k_j.r_a) = exp(i kappa_j x_c) * sum_l L_l(kappa_j) W[l, a],   W[l, a] = exp(i k0.r_a) exp(i kappa_l (x_a - x_c)),
+// where kappa_l are 64 Chebyshev nodes of an interval of kappa and L_l their Lagrange polynomials: Chebyshev
+// interpolation of exp(i kappa (x - x_c)) over an interval of half-width h_k, |x - x_c| <= h_x, is exact to fp64
+// rounding with 64 nodes while h_k h_x <= 30.  C[j, l] = exp(i kappa_j x_c) L_l(kappa_j).
+// What the line does not carry goes to D = P_ref - exp(i k~_j.r) (k~_j: k_j projected on the line), bounded by
+//     |D| <= 2^-22 sum_i max|k_i| max|r_i|   (float32 rounding of the reference's phase argument)
+//          + max_j |k_j - k~_j| max_a |r_a|  (the vectors off the line)
+//          + 2^-20                           (sincosf against fp64 sincos)
+// and accepted when the bound is at most 2^-13: D times the hi plane alone then misses at most 2^-25 of |v| per term.
+//
+// The plan is ROW-DETERMINISTIC for the lists it serves: u, k0, the node interval and hence the nodes and each row
+// of C depend on the line and the atom group, not on which part of the path a launch holds, so a list split over
+// calls projects every row with the same arithmetic.  That needs a line the float32 k-vectors determine EXACTLY:
+// any quantity estimated from them carries their rounding (~1e-7 relative) and lands on different grid points for
+// different sub-lists.  So the route serves lines through Gamma (k0 = 0) along a small-integer (lattice) direction
+// such as [110] -- u is then snapped exactly and kappa_j = k_j.u is a function of k_j alone -- and lists that lie
+// on one side of Gamma: node intervals tile kappa >= 0 as [n w, (n+1) w) and kappa <= 0 as (-(n+1) w, -n w], with
+// a width w fixed by the group's x-range, and every kappa of a launch must fall in one of them.  Everything else
+// (paths off Gamma, non-lattice directions, lists crossing Gamma or longer than one interval) stays on the dense
+// kernels.  A list that crosses Gamma declines as a whole while a part of it on one side may take the route, so
+// for such lists splitting can move rows by the ~1e-7 that separates the two routes.
+#include "api_internal.h"
+
+namespace psa {
+
+namespace {
+constexpr double LR_OMEGA = 30.0;                 // half-width product h_k h_x of a node interval
+constexpr double LR_D_MAX = 1.0 / 8192.0;         // 2^-13
+}  // namespace
+
+int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, const int32_t* h_idx, int64_t n_g, LowRankPlan* p) {
+    *p = LowRankPlan{};
+    auto fail = [&](const char* why) {
+        p->why = why;
+        return PSA_OK;
+    };
+    if (K < 2) return fail("fewer than two k-vectors");
+    if (n_g < 1) return fail("empty group");
+    for (int64_t i = 0; i < 3 * K; ++i)
+        if (!std::isfinite(k[i])) return fail("k-vector not finite");
+    // ---- direction: the vector farthest from the first one
+    double  p0[3] = {k[0], k[1], k[2]}, far = 0.0;
+    int64_t jf = 0;
+    for (int64_t j = 1; j < K; ++j) {
+        double d2 = 0.0;
+        for (int i = 0; i < 3; ++i) d2 += ((double)k[3 * j + i] - p0[i]) * ((double)k[3 * j + i] - p0[i]);
+        if (d2 > far) {
+            far = d2;
+            jf = j;
+        }
+    }
+    if (!(far > 0.0)) return fail("all k-vectors equal");
+    double u[3], nu = std::sqrt(far);
+    for (int i = 0; i < 3; ++i) u[i] = ((double)k[3 * jf + i] - p0[i]) / nu;
+    {   // canonical sign: the largest component positive
+        int im = 0;
+        for (int i = 1; i < 3; ++i)
+            if (std::fabs(u[i]) > std::fabs(u[im])) im = i;
+        if (u[im] < 0)
+            for (double& v : u) v = -v;
+    }
+    bool snapped = false;          // (a direction that is not within 1e-6 of a small-integer one is declined below)
+    for (int n = 1; n <= 12 && !snapped; ++n) {    // small-integer direction: u = m / |m| with |m_i| <= n
+        double m[3], mn = 0.0, dev = 0.0;
+        const double s = n / std::max({std::fabs(u[0]), std::fabs(u[1]), std::fabs(u[2])});
+        for (int i = 0; i < 3; ++i) {
+            m[i] = std::nearbyint(u[i] * s);
+            mn += m[i] * m[i];
+        }
+        mn = std::sqrt(mn);
+        for (int i = 0; i < 3; ++i) dev = std::max(dev, std::fabs(m[i] / mn - u[i]));
+        if (dev < 1e-6) {
+            for (int i = 0; i < 3; ++i) u[i] = m[i] / mn + 0.0;
+            snapped = true;
+        }
+    }
+    if (!snapped) return fail("direction not a lattice direction");
+    // ---- the line must pass through Gamma: then k0 = 0 exactly.  The distance of the line from Gamma is
+    // estimated from the point of the list farthest from it (float32 rounding: ~1e-7 of |k|)
+    {
+        double kmax2 = 0.0, off2 = 0.0;
+        for (int64_t j = 0; j < K; ++j) {
+            double kj[3], d = 0.0, n2 = 0.0;
+            for (int i = 0; i < 3; ++i) {
+                kj[i] = k[3 * j + i];
+                d += kj[i] * u[i];
+                n2 += kj[i] * kj[i];
+            }
+            double o2 = 0.0;
+            for (int i = 0; i < 3; ++i) o2 += (kj[i] - d * u[i]) * (kj[i] - d * u[i]);
+            kmax2 = std::max(kmax2, n2);
+            off2 = std::max(off2, o2);
+        }
+        if (!(std::sqrt(off2) <= 1e-5 * std::sqrt(kmax2))) return fail("line does not pass through Gamma");
+    }
+    for (int i = 0; i < 3; ++i) p->u[i] = u[i];
+    // ---- the group's atoms along u
+    double xmin = INFINITY, xmax = -INFINITY, rmax = 0.0, rabs[3] = {0, 0, 0};
+    for (int64_t a = 0; a < n_g; ++a) {
+        const int64_t src = h_idx ? h_idx[a] : a;
+        if (src < 0 || src >= N) return fail("index outside the trajectory");
+        const float* r = mean_all + 3 * src;
+        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2])) return fail("mean position not finite");
+        const double x = u[0] * r[0] + u[1] * r[1] + u[2] * r[2];
+        xmin = std::min(xmin, x);
+        xmax = std::max(xmax, x);
+        rmax = std::max(rmax, std::sqrt((double)r[0] * r[0] + (double)r[1] * r[1] + (double)r[2] * r[2]));
+        for (int i = 0; i < 3; ++i) rabs[i] = std::max(rabs[i], (double)std::fabs(r[i]));
+    }
+    p->x_c = 0.5 * (xmin + xmax);
+    p->h_x = std::max(0.5 * (xmax - xmin), 1e-12);
+    p->width = 2.0 * LR_OMEGA / p->h_x;
+    // ---- kappa, the line's vectors, the off-line residual
+    p->kline.resize((size_t)3 * K);
+    std::vector<double> kap((size_t)K);
+    double              off = 0.0, kabs[3] = {0, 0, 0};
+    for (int64_t j = 0; j < K; ++j) {
+        double kj[3], kk = 0.0;
+        for (int i = 0; i < 3; ++i) {
+            kj[i] = k[3 * j + i];
+            kk += (kj[i] - p->k0[i]) * u[i];
+            kabs[i] = std::max(kabs[i], std::fabs(kj[i]));
+        }
+        kap[(size_t)j] = kk;
+        double e2 = 0.0;
+        for (int i = 0; i < 3; ++i) {
+            p->kline[3 * j + i] = p->k0[i] + kk * u[i];
+            e2 += (kj[i] - p->kline[3 * j + i]) * (kj[i] - p->kline[3 * j + i]);
+        }
+        off = std::max(off, std::sqrt(e2));
+    }
+    p->d_bound = 0x1p-22 * (kabs[0] * rabs[0] + kabs[1] * rabs[1] + kabs[2] * rabs[2]) + off * rmax + 0x1p-20;
+    if (!(p->d_bound <= LR_D_MAX)) return fail("k-vectors not on one line (or phases too large)");
+    // ---- one node interval holds every kappa: [n w, (n + 1) w] on the side kappa >= 0, [-(n + 1) w, -n w] on the
+    // other (kappa = 0, Gamma itself, belongs to interval 0 of either side)
+    bool pos = true, neg = true;
+    for (int64_t j = 0; j < K; ++j) {
+        pos = pos && kap[(size_t)j] >= 0.0;
+        neg = neg && kap[(size_t)j] <= 0.0;
+    }
+    if (!pos && !neg) return fail("k-list crosses Gamma");
+    const bool   side = pos;                                              // all kappa >= 0 (both only if all are 0)
+    const double n0 = std::floor(std::fabs(kap[0]) / p->width);
+    for (int64_t j = 0; j < K; ++j)
+        if (std::floor(std::fabs(kap[(size_t)j]) / p->width) != n0) return fail("k-path longer than one node interval");
+    p->interval = side ? (int64_t)n0 : -(int64_t)n0 - 1;
+    const double mid = (p->interval + 0.5) * p->width, half = 0.5 * p->width;
+    double       bw[LOWRANK_NODES];
+    for (int l = 0; l < LOWRANK_NODES; ++l) {
+        const double th = M_PI * (2 * l + 1) / (2.0 * LOWRANK_NODES);
+        p->kappa[l] = mid + half * std::cos(th);
+        bw[l] = ((l & 1) ? -1.0 : 1.0) * std::sin(th);           // barycentric weights of Chebyshev points of the first kind
+    }
+    // ---- C[j, l] = exp(i kappa_j x_c) L_l(kappa_j), complex64
+    p->C.assign((size_t)K * LOWRANK_NODES * 2, 0.f);
+    for (int64_t j = 0; j < K; ++j) {
+        const double kj = kap[(size_t)j];
+        double       L[LOWRANK_NODES], den = 0.0;
+        int          hit = -1;
+        for (int l = 0; l < LOWRANK_NODES; ++l)
+            if (kj == p->kappa[l]) hit = l;
+        if (hit >= 0) {
+            for (int l = 0; l < LOWRANK_NODES; ++l) L[l] = l == hit;
+        } else {
+            for (int l = 0; l < LOWRANK_NODES; ++l) {
+                L[l] = bw[l] / (kj - p->kappa[l]);
+                den += L[l];
+            }
+            for (double& v : L) v /= den;
+        }
+        const double cr = std::cos(kj * p->x_c), ci = std::sin(kj * p->x_c);
+        for (int l = 0; l < LOWRANK_NODES; ++l) {
+            p->C[((size_t)j * LOWRANK_NODES + l) * 2 + 0] = (float)(cr * L[l]);
+            p->C[((size_t)j * LOWRANK_NODES + l) * 2 + 1] = (float)(ci * L[l]);
+        }
+    }
+    // ---- scale of D: the bound lands at or below 2^14 (float16 maximum 65504)
+    p->dscale = std::ldexp(1.0f, 14 - (int)std::ceil(std::log2(p->d_bound)));
+    p->ok = true;
+    return PSA_OK;
+}
+
+// Decide the route of one projection launch (a group's planes, nk k-vectors of a list of K_total) and, when the
+// low-rank route serves, upload what it needs: fp64 [k0 (3), u (3), x_c, kappa (64), kline (nk x 3)] and C.
+// The decision depends on the list, the group and the options only -- never on how the list is split over
+// calls -- as long as every part keeps PSA_OPT_K1_LOWRANK_MIN_LOCAL vectors (default 128: a 512-row D block at
+// least half full).
+int prepare_lowrank(psa_ctx* c, int slot, const float* k_host, int64_t nk, int64_t K_total, const float* mean_all,
+                    const int32_t* h_idx, const PlaneSet* ps, ProjGeom* g) {
+    g->lowrank = false;
+    if (!c->opt_k1_lowrank || g->split != 4 || !ps || K_total < c->opt_k1_lowrank_min_k || nk < c->opt_k1_lowrank_min_local)
+        return PSA_OK;
+    LowRankPlan p;
+    PSA_TRY(plan_lowrank(k_host, nk, mean_all, c->slot[slot].N, h_idx, g->n_g, &p));
+    if (!p.ok) return PSA_OK;
+    std::vector<double> f64((size_t)7 + LOWRANK_NODES + 3 * (size_t)nk);
+    std::memcpy(f64.data(), p.k0, 3 * sizeof(double));
+    std::memcpy(f64.data() + 3, p.u, 3 * sizeof(double));
+    f64[6] = p.x_c;
+    std::memcpy(f64.data() + 7, p.kappa, sizeof(p.kappa));
+    std::memcpy(f64.data() + 7 + LOWRANK_NODES, p.kline.data(), p.kline.size() * sizeof(double));
+    PSA_TRY(upload(c, c->d_lr_f64, f64.data(), f64.size() * sizeof(double)));
+    PSA_TRY(upload(c, c->d_lr_C, p.C.data(), p.C.size() * sizeof(float)));
+    PSA_TRY(c->d_lr_qn.reserve((size_t)LOWRANK_NODES * 3 * (size_t)c->slot[slot].T * sizeof(float2)));
+    g->lowrank = true;
+    g->dscale = p.dscale;
+    g->M_pad_d = (int)((2 * nk + 511) / 512 * 512);
+    return PSA_OK;
+}
+
+}  // namespace psa
+
+using namespace psa;
+
+extern "C" {
+
+int psa_lowrank_plan(const float* k_vectors, int64_t K, const float* mean_pos_all, int64_t N, const int32_t* idx, int64_t n_g,
+                     int32_t* ok, double* geo, double* kappa, float* C) {
+    PSA_REQUIRE(K >= 0 && K < (1ll << 29) && N >= 1 && n_g >= 0 && n_g <= (idx ? (int64_t)1 << 30 : N) && ok && geo &&
+                    (K == 0 || k_vectors) && mean_pos_all,
+                "bad argument");
+    LowRankPlan p;
+    PSA_TRY(plan_lowrank(k_vectors, K, mean_pos_all, N, idx, n_g, &p));
+    *ok = p.ok;
+    const double g[12] = {p.u[0], p.u[1], p.u[2], p.k0[0], p.k0[1], p.k0[2], p.x_c, p.h_x, p.width, (double)p.interval, p.d_bound, p.dscale};
+    std::memcpy(geo, g, sizeof(g));
+    if (p.ok && kappa) std::memcpy(kappa, p.kappa, sizeof(p.kappa));
+    if (p.ok && C) std::memcpy(C, p.C.data(), p.C.size() * sizeof(float));
+    return PSA_OK;
+}
+
+}  // extern "C"

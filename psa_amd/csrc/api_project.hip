@@ -258,6 +258,14 @@ int make_geom(psa_ctx* c, int slot, int64_t K_local, int64_t n_g, const int* d_i
 int prepare_phase(psa_ctx* c, const int* d_idx, const ProjGeom& g, bool disp, int64_t k_first) {
     const float* d_kvec = c->d_kvec.as<float>() + 3 * k_first;         // the launch's k-vectors within the uploaded list
     const bool f16 = g.split == 2 || g.split == 4, bf16 = g.split == 3;
+    if (g.lowrank) {      // the D image and the node table (the plan's fp64 inputs were uploaded by prepare_lowrank)
+        PSA_TRY(c->d_lr_diff.reserve(pd16_table_bytes(g.M_pad_d, g.A_pad)));
+        PSA_TRY(c->d_phase.reserve(pf16_table_bytes(128, g.A_pad)));
+        StageTimer    st(c, PSA_T_PHASE);
+        const double* f64 = c->d_lr_f64.as<double>();
+        return launch_lowrank_tables(c, d_kvec, f64 + 7 + LOWRANK_NODES, f64, f64 + 7, c->d_mean_all.as<float>(), d_idx,
+                                     c->d_lr_diff.ptr, c->d_phase.ptr, g, g.M_pad_d, g.dscale);
+    }
     PSA_TRY(c->d_phase.reserve(f16    ? pf16_table_bytes(g.M_pad, g.A_pad)
                                : bf16 ? pb_table_bytes(g.M_pad, g.A_pad)
                                       : p_table_floats(g.M_pad, g.A_pad) * sizeof(float)));
@@ -308,6 +316,21 @@ static int launch_projection_once(psa_ctx* c, int slot, const int* d_idx, ProjGe
         const _Float16* pl = ps->buf.as<_Float16>() + (size_t)fg0 * (size_t)(ps->A_pad / K1_BA) * PL_STAGE_ELEMS;
         // PSA_OPT_K1_LOADER_WAVES [1]: 128-row M blocks go to the loader-wavefront form of the kernel
         // (k1_planes_lw.hip; 2-3 % faster than the eight-wavefront form on every shape, round 3); 0 = never
+        if (g.lowrank) {
+            // node rows (the 128-row planes kernel on the node table in d_phase) -> d_lr_qn; D pass -> q; q += C Qn
+            ProjGeom gn = g;
+            gn.K = LOWRANK_NODES;
+            gn.m_blk = gn.M_pad = 2 * LOWRANK_NODES;
+            gn.q_stride = t_count;
+            PSA_REQUIRE(c->d_lr_qn.cap >= (size_t)LOWRANK_NODES * 3 * t_count * sizeof(float2), "node projections not reserved");
+            PSA_TRY(launch_k1_planes_lw(c, pl, c->d_phase.ptr, c->d_lr_qn.as<float2>(), gn, ps->n_fg - fg0));
+            ProjGeom gd = g;
+            gd.M_pad = g.M_pad_d;
+            PSA_TRY(launch_k1_planes_diff(c, pl, c->d_lr_diff.ptr, d_q, gd, ps->n_fg - fg0, g.dscale));
+            PSA_TRY(launch_lowrank_combine(c, c->d_lr_qn.as<float2>(), c->d_lr_C.as<float2>(), d_q, g, t_count));
+            ++c->lowrank_launches;
+            return PSA_OK;
+        }
         if (g.m_blk == 256) return launch_k1_planes_wide(c, pl, c->d_phase.ptr, d_q, g, ps->n_fg - fg0);
         if (g.m_blk == 128 && c->opt_k1_loader_waves) return launch_k1_planes_lw(c, pl, c->d_phase.ptr, d_q, g, ps->n_fg - fg0);
         return launch_k1_planes(c, pl, c->d_phase.ptr, d_q, g, ps->n_fg - fg0);
@@ -416,6 +439,7 @@ int project_groups(psa_ctx* c, const ProjectArgs& a, int slot_in, bool disp_in, 
             const int64_t nk = std::min(kb, a.K_local - k0);
             ProjGeom      g;
             PSA_TRY(make_geom(c, slot, nk, n_g, d_idx, h_idx, disp, ps, 0, &g));
+            PSA_TRY(prepare_lowrank(c, slot, a.k_vectors + 3 * k0, nk, a.K_total, a.mean_pos_all, h_idx, ps, &g));
             PSA_TRY(prepare_phase(c, d_idx, g, disp, k0));
             PSA_TRY(launch_projection(c, slot, d_idx, g, disp, ps, d_q + (size_t)k0 * 3 * (size_t)T, T, 0, T));
         }

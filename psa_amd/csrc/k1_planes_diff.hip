@@ -1,0 +1,357 @@
+// K1 low-rank route for k-paths (planned on the host in api_lowrank.hip): the device half.
+//
+// A k-path lies on one line, k_j = k0 + kappa_j u, so its phase matrix is, to fp64 rounding, 64 node rows
+// combined per k-vector: exp(i k_j.r) = sum_l C[j,l] W[l,.] (Chebyshev interpolation in kappa).  The reference
+// rounds the phase argument in float32, which the node rows do not; the difference D = P_ref - P_line is
+// small (|D| <= 2^-13, checked by the plan) and goes through ONE float16 product with the hi plane.  So
+//     q = C (W v) + D v_hi
+// = a 128-row "2 x f16" launch of the existing planes kernel (node_table_kernel -> k1_planes_lw.hip), the D pass
+// below (one MFMA per row tile and component instead of three, hi plane only), and lowrank_combine_kernel.
+//
+// D pass: 512-ROW x 64-frame workgroup tile.  Eight wavefronts, two per SIMD; wavefront w = 4 h + f owns rows
+// [256 h, +256) x frames [16 f, +16) x 3 components = 48 accumulator tiles (192 registers), the stage's three B
+// fragments (12) and a four-deep ring of A fragments read two row tiles ahead (16).  No float32 fold sums: the D
+// part is ~1e-5 of the signal, so the float16-MFMA chain's truncation over all stages (<= n_stage * 2^-24 of it)
+// stays far below float32 rounding of the total.
+// A stage is 44 one-KiB units: 12 plane units (unit 4 c + j = hi piece of component c, frame group j) and 32 D
+// units (unit 12 + 2 mt + h = row tile mt of row half h).  The units live in a ring of 160 units of LDS: stage s,
+// unit u at (44 s + u) mod 160; positions repeat every 40 stages, so the main loop is unrolled 40 times and every
+// LDS address is a constant.  Entering stage s (stage s-1's units are free) waves 0-3 issue the units 28..43 of
+// stage s+2 and 0..27 of stage s+3 (the 160 - 3 x 44 = 28 spare units) -- eleven LDS-DMA instructions each,
+// their SIMD partners none (the issuing wavefront is held per instruction, its partner multiplies meanwhile:
+// PSA_K1W_SOLO of k1_planes_wide.hip).  The barrier that ends stage s is preceded by vmcnt(7): all of stages s+1
+// and s+2 have landed, so a stage reads the next one's fragments while it multiplies.
+// Per stage and CU: 44 KiB of LDS-DMA (11 per 128 rows; the 256-row kernel needs 28), 384 MFMAs.
+#include <utility>
+
+#include "k1_f16.h"
+
+namespace psa {
+
+namespace {
+constexpr int D_M_BLK = 512, D_T_BLK = 64, D_MT = 16, D_PERIOD = 40;
+constexpr int D_STAGE_UNITS = 44, D_RING_UNITS = 160, D_EARLY = D_RING_UNITS - 3 * D_STAGE_UNITS;   // 28
+constexpr int D_STAGE_BYTES = D_M_BLK * K1_BA * 2;                                               // 32 KiB of D per stage
+constexpr int D_V_GROUP_BYTES = PL_STAGE_ELEMS * 2;                                              // 6 KiB
+static_assert(D_EARLY == 28 && D_RING_UNITS % 4 == 0 && D_STAGE_UNITS % 4 == 0, "ring arithmetic");
+constexpr unsigned d_unit_off(int s40, int unit) { return (unsigned)((D_STAGE_UNITS * (s40 % D_PERIOD) + unit) % D_RING_UNITS) * 1024u; }
+
+// one LDS-DMA instruction: uniform 64-bit base + per-lane offset -> LDS at wbase + OFF (+ lane * 16)
+template <unsigned OFF, bool NT>
+__device__ __forceinline__ void d_dma(const void* sbase, unsigned voff, unsigned wbase) {
+    if constexpr (NT)
+        asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(voff), "s"(sbase), "s"(wbase), "n"(OFF) : "memory", "scc");
+    else
+        asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(wbase), "n"(OFF) : "memory", "scc");
+}
+}  // namespace
+
+// element (row m, atom a) of the D image: [M block of 512][atom stage][unit 2 mt + h][16 rows][32 atoms] (float16), the
+// 16-byte slots of a row swizzled as in the phase-table image (pf16_tile_index)
+__host__ __device__ inline size_t pd16_index(int m, int a, int n_stage) {
+    const int row = m % D_M_BLK, rt = row >> 4, v = 2 * (rt & 15) + (rt >> 4), r = row & 15, al = a % K1_BA;
+    return (((size_t)(m / D_M_BLK) * n_stage + a / K1_BA) * 32 + v) * (16 * K1_BA) + (size_t)r * K1_BA +
+           (size_t)((((al >> 3) ^ pl_swizzle(r)) << 3) + (al & 7));
+}
+// (+ 4 stages of padding: the D pass fetches up to three stages past an M block's end and never reads them)
+size_t pd16_table_bytes(int M_pad, int A_pad) { return ((size_t)M_pad * A_pad + 4 * (size_t)D_M_BLK * K1_BA) * 2; }
+
+template <bool NT_V>
+__global__ void __launch_bounds__(512, 2)
+k1_planes_diff_kernel(const _Float16* __restrict__ planes, const _Float16* __restrict__ Db, float2* __restrict__ Q, int64_t T,
+                      int64_t q_stride, int n_fg, int n_stage, int K, int n_mblk, int n_tblk, float qscale) {
+    using PR = F16x2;
+    using E8 = PR::v8;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[D_RING_UNITS * 1024];
+    const unsigned lds0 = (unsigned)(size_t)(lds_u8*)smem;
+
+    // XCD-aware block map (k1_planes.hip)
+    const int b = blockIdx.x;
+    const int r8 = b >> 3;
+    const int mb = r8 % n_mblk;
+    const int tb = (r8 / n_mblk) * 8 + (b & 7);
+    if (tb >= n_tblk) return;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wh = w >> 2, wf = w & 3;
+    const int r16 = lane & 15, q = lane >> 4;
+
+    // ---- waves 0-3: eleven source streams, instruction i = unit w + 4 i of every stage ----------------------
+    // i = 0..2: hi piece of component i of frame group w; i = 3..10: D unit w + 4 (i - 3)
+    const unsigned char* src[11];
+    {
+        int fg = tb * 4 + (w & 3);                                      // frame group (past the end: the last one, never stored)
+        if (fg >= n_fg) fg = n_fg - 1;
+        const unsigned char* pl0 = reinterpret_cast<const unsigned char*>(planes) + (size_t)fg * n_stage * D_V_GROUP_BYTES;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) src[i] = pl0 + 1024 * (2 * i);      // (component i, piece 0) = block 2 i of the 6
+        const unsigned char* d0 = reinterpret_cast<const unsigned char*>(Db) + (size_t)mb * n_stage * D_STAGE_BYTES;
+#pragma unroll
+        for (int i = 3; i < 11; ++i) src[i] = d0 + 1024 * ((w & 3) + 4 * (i - 3));
+    }
+    const unsigned dma_voff = 16 * lane;
+    const unsigned wbase = lds0 + 1024 * (w & 3);                       // unit 4 i + w: 1024 w past unit 4 i (no wrap: 44 s + 4 i is a multiple of 4)
+    using std::integral_constant;
+    auto dma = [&](auto s40_c, auto i_c) __attribute__((always_inline)) {
+        constexpr int      S40 = decltype(s40_c)::value, I = decltype(i_c)::value;
+        constexpr unsigned OFF = d_unit_off(S40, 4 * I);
+        if constexpr (I < 3) {
+            d_dma<OFF, NT_V>(src[I], dma_voff, wbase);
+            src[I] += D_V_GROUP_BYTES;
+        } else {
+            d_dma<OFF, false>(src[I], dma_voff, wbase);
+            src[I] += D_STAGE_BYTES;
+        }
+    };
+    auto dma_range = [&]<int S40, int... Is>(integral_constant<int, S40>, std::integer_sequence<int, Is...>) __attribute__((always_inline)) {
+        (dma(integral_constant<int, S40>{}, integral_constant<int, Is>{}), ...);
+    };
+    // units 0..27 of a stage are instructions 0..6, units 28..43 instructions 7..10
+    auto dma_late = [&](auto s40_c) __attribute__((always_inline)) {
+        dma_range(s40_c, std::integer_sequence<int, 7, 8, 9, 10>{});
+    };
+    auto dma_early = [&](auto s40_c) __attribute__((always_inline)) {
+        dma_range(s40_c, std::make_integer_sequence<int, 7>{});
+    };
+
+    // ---- fragment reads: every unit is 16 rows (frames) x 64 bytes, lane (r16, q) takes 16 bytes ----------
+    const unsigned lane_off = lds0 + r16 * (K1_BA * 2) + ((q ^ pl_swizzle(r16)) << 4);
+    unsigned       lane_a[3], lane_b[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        lane_a[i] = lane_off + 1024 * wh + 65536 * i;                 // D unit 12 + 2 mt + h: 1024 h past unit 12 + 2 mt (even)
+        lane_b[i] = lane_off + 1024 * wf + 65536 * i;                 // plane unit 4 c + f
+        asm volatile("" : "+v"(lane_a[i]), "+v"(lane_b[i]));
+    }
+    auto lds_frag = [&](const unsigned (&base)[3], unsigned off) __attribute__((always_inline)) {
+        return *reinterpret_cast<lds_cv8*>((const lds_u8*)(size_t)(base[off >> 16] + (off & 0xFFFFu)));
+    };
+    E8    a[4];                                    // A fragments of row tiles mt .. mt+3 (mod 4), read two ahead
+    E8    bf[3];                                   // hi B fragments of the stage in work
+    f32x4 acc[D_MT][3];
+    auto  read_a = [&](auto s40_c, auto mt_c) __attribute__((always_inline)) {
+        constexpr int S40 = decltype(s40_c)::value, MTI = decltype(mt_c)::value;
+        a[MTI & 3] = lds_frag(lane_a, d_unit_off(S40, 12 + 2 * MTI));
+    };
+    auto read_b = [&](auto s40_c, auto c_c) __attribute__((always_inline)) {
+        constexpr int S40 = decltype(s40_c)::value, CC = decltype(c_c)::value;
+        bf[CC] = lds_frag(lane_b, d_unit_off(S40, 4 * CC));
+    };
+#pragma unroll
+    for (int mt = 0; mt < D_MT; ++mt)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[mt][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // ---- prologue: stages 0 and 1 whole, units 0..27 of stage 2 ------------------------------------------
+    using I0 = integral_constant<int, 0>;
+    using I1 = integral_constant<int, 1>;
+    using I2 = integral_constant<int, 2>;
+    if (wh == 0) {
+        dma_early(I0{});
+        dma_late(I0{});
+        dma_early(I1{});
+        dma_late(I1{});
+        dma_early(I2{});
+    }
+    asm volatile("s_waitcnt vmcnt(7)\n\ts_barrier" ::: "memory");      // stages 0 and 1 landed
+    read_b(I0{}, I0{});
+    read_b(I0{}, I1{});
+    read_b(I0{}, I2{});
+    read_a(I0{}, I0{});
+    read_a(I0{}, I1{});
+
+    int  left = n_stage;                                               // stages to go when the period began
+    auto stage = [&](auto s40_c) __attribute__((always_inline)) {
+        constexpr int S40 = decltype(s40_c)::value;
+        if (left <= S40) return;                                       // past the group's last stage
+        using SN = integral_constant<int, (S40 + 1) % D_PERIOD>;
+        using SNN = integral_constant<int, (S40 + 2) % D_PERIOD>;
+        using S3 = integral_constant<int, (S40 + 3) % D_PERIOD>;
+        if (wh == 0) {                                                 // stage s-1's units are free
+            dma_late(SNN{});
+            dma_early(S3{});
+        }
+        auto tile = [&](auto mt_c) __attribute__((always_inline)) {
+            constexpr int MTI = decltype(mt_c)::value;
+            if constexpr (MTI + 2 < D_MT)
+                read_a(s40_c, integral_constant<int, MTI + 2>{});
+            else
+                read_a(SN{}, integral_constant<int, MTI + 2 - D_MT>{});
+            auto comp = [&](auto c_c) __attribute__((always_inline)) {
+                constexpr int CC = decltype(c_c)::value;
+                acc[MTI][CC] = PR::mma(a[MTI & 3], bf[CC], acc[MTI][CC]);
+                if constexpr (MTI == D_MT - 1) read_b(SN{}, c_c);      // behind the component's last use in this stage
+            };
+            comp(I0{});
+            comp(I1{});
+            comp(I2{});
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        [&]<int... Ms>(std::integer_sequence<int, Ms...>) __attribute__((always_inline)) { (tile(integral_constant<int, Ms>{}), ...); }(
+            std::make_integer_sequence<int, D_MT>{});
+        // what this stage read from its own units has been consumed above; reads in flight come from stage s+1
+        asm volatile("s_waitcnt vmcnt(7)\n\ts_barrier" ::: "memory");     // stages s+1 and s+2 landed
+    };
+    for (; left > 0; left -= D_PERIOD)
+        [&]<int... Ss>(std::integer_sequence<int, Ss...>) __attribute__((always_inline)) { (stage(integral_constant<int, Ss>{}), ...); }(
+            std::make_integer_sequence<int, D_PERIOD>{});
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // nothing in flight when LDS is handed on
+
+    // ---- epilogue (k1_planes.hip): register j of lane (r16, q) is row 4q + j, column r16 of its 16x16 tile ----
+    const int     lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int     r16_e = lane_e & 15, q_e = lane_e >> 4;
+    const int     m0 = mb * D_M_BLK + wh * (D_M_BLK / 2);
+    const int64_t t = (int64_t)tb * D_T_BLK + wf * 16 + r16_e;
+    if (t < T) {
+#pragma unroll
+        for (int mt = 0; mt < D_MT; ++mt) {
+#pragma unroll
+            for (int pr = 0; pr < 2; ++pr) {
+                const int k = (m0 + mt * 16 + 4 * q_e + 2 * pr) >> 1;
+                if (k < K) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        Q[((int64_t)k * 3 + c) * q_stride + t] = make_float2(acc[mt][c][2 * pr] * qscale, acc[mt][c][2 * pr + 1] * qscale);
+                }
+            }
+        }
+    }
+}
+
+// d_planes: the group's planes from its first frame group on; d_diff: the D image (pd16_index), g.M_pad rows; dscale: the
+// power of two the image was multiplied by
+int launch_k1_planes_diff(psa_ctx* c, const void* d_planes, const void* d_diff, float2* d_q, const ProjGeom& g, int64_t n_fg, float dscale) {
+    PSA_REQUIRE(g.M_pad % D_M_BLK == 0 && g.M_pad >= 2 * g.K && g.M_pad > 0, "D pass: 512-row M blocks only");
+    PSA_REQUIRE(g.A_pad % K1_BA == 0 && g.A_pad > 0, "D pass needs the atom axis padded to %d", K1_BA);
+    PSA_REQUIRE(g.vscale > 0.f && dscale > 0.f && n_fg * 16 >= g.T, "planes do not cover the launch");
+    const int     n_mblk = g.M_pad / D_M_BLK;
+    const int64_t n_tblk = (g.T + D_T_BLK - 1) / D_T_BLK;
+    const int64_t grid = ((n_tblk + 7) / 8) * 8 * n_mblk;
+    PSA_REQUIRE(grid < (1ll << 31) && n_tblk < (1ll << 29) && n_fg < (1ll << 31), "projection grid too large");
+    const float qscale = 1.f / (g.vscale * dscale);                      // powers of two: exact
+    if (n_mblk == 1)
+        hipLaunchKernelGGL((k1_planes_diff_kernel<true>), dim3((unsigned)grid), dim3(512), 0, c->stream, (const _Float16*)d_planes,
+                           (const _Float16*)d_diff, d_q, g.T, g.q_stride, (int)n_fg, g.A_pad / K1_BA, g.K, n_mblk, (int)n_tblk, qscale);
+    else
+        hipLaunchKernelGGL((k1_planes_diff_kernel<false>), dim3((unsigned)grid), dim3(512), 0, c->stream, (const _Float16*)d_planes,
+                           (const _Float16*)d_diff, d_q, g.T, g.q_stride, (int)n_fg, g.A_pad / K1_BA, g.K, n_mblk, (int)n_tblk, qscale);
+    PSA_HIP_CHECK(hipGetLastError());
+    return PSA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Tables
+// ---------------------------------------------------------------------------------------------
+// D[j, a] = (P_ref - P_line) * dscale, one float16 piece.  P_ref exactly as phase_table_f16_kernel (k1_pair.hip)
+// computes it -- the same float32 FMA chain and sincosf, under the same compiler flags --, P_line from the k-vector
+// projected on the plan's line, kline[3 j..], in fp64.  Rows past 2K and atoms past n_g are zero.
+__global__ void __launch_bounds__(256)
+diff_table_kernel(const float* __restrict__ kvec, const double* __restrict__ kline, const float* __restrict__ mean_all,
+                  const int* __restrict__ idx, _Float16* __restrict__ Db, int K, int n_g, int A_pad, float dscale) {
+    const int a = blockIdx.y * 256 + threadIdx.x;
+    const int k = blockIdx.x;
+    if (a >= A_pad) return;
+    float d[2] = {0.f, 0.f};
+    if (k < K && a < n_g) {
+        const int   src = idx ? idx[a] : a;
+        const float rx = mean_all[3 * (size_t)src + 0], ry = mean_all[3 * (size_t)src + 1], rz = mean_all[3 * (size_t)src + 2];
+        const float kx = kvec[3 * k + 0], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
+        const float arg = __fmaf_rn(kz, rz, __fmaf_rn(ky, ry, __fmul_rn(kx, rx)));
+        float       cs[2];
+        sincosf(arg, &cs[1], &cs[0]);
+        const double th = kline[3 * k + 0] * (double)rx + kline[3 * k + 1] * (double)ry + kline[3 * k + 2] * (double)rz;
+        double       se, ce;
+        sincos(th, &se, &ce);
+        d[0] = (float)(((double)cs[0] - ce) * (double)dscale);
+        d[1] = (float)(((double)cs[1] - se) * (double)dscale);
+    }
+    const int n_stage = A_pad / K1_BA;
+    Db[pd16_index(2 * k, a, n_stage)] = (_Float16)d[0];
+    Db[pd16_index(2 * k + 1, a, n_stage)] = (_Float16)d[1];
+}
+
+// Node rows W[l, a] = exp(i k0.r_a) exp(i kappa_l (u.r_a - x_c)), fp64 argument and sincos, in the two-piece phase-table
+// image of one 128-row M block (pf16_tile_index): what k1_planes_lw.hip projects as 64 k-vectors.
+// geo = {k0 (3), u (3), x_c}; kappa: the 64 nodes
+__global__ void __launch_bounds__(256)
+node_table_kernel(const double* __restrict__ geo, const double* __restrict__ kappa, const float* __restrict__ mean_all,
+                  const int* __restrict__ idx, _Float16* __restrict__ Pb, int n_g, int A_pad) {
+    const int a = blockIdx.y * 256 + threadIdx.x;
+    const int l = blockIdx.x;
+    if (a >= A_pad) return;
+    double cs[2] = {0.0, 0.0};
+    if (a < n_g) {
+        const int    src = idx ? idx[a] : a;
+        const double rx = mean_all[3 * (size_t)src + 0], ry = mean_all[3 * (size_t)src + 1], rz = mean_all[3 * (size_t)src + 2];
+        const double th = (geo[0] * rx + geo[1] * ry + geo[2] * rz) + kappa[l] * ((geo[3] * rx + geo[4] * ry + geo[5] * rz) - geo[6]);
+        sincos(th, &cs[1], &cs[0]);
+    }
+    const int n_stage = A_pad / K1_BA;
+#pragma unroll
+    for (int ri = 0; ri < 2; ++ri) {
+        const double   x = cs[ri] * (double)F16x2::P_SCALE;
+        const _Float16 lead = (_Float16)(float)x;
+        Pb[pf16_tile_index(0, 2 * l + ri, a, 128, n_stage)] = lead;
+        Pb[pf16_tile_index(1, 2 * l + ri, a, 128, n_stage)] = (_Float16)(float)(x - (double)lead);
+    }
+}
+
+int launch_lowrank_tables(psa_ctx* c, const float* d_kvec, const double* d_kline, const double* d_geo, const double* d_kappa,
+                          const float* d_mean_all, const int* d_idx, void* d_diff, void* d_nodes, const ProjGeom& g, int M_pad_d,
+                          float dscale) {
+    PSA_REQUIRE(M_pad_d % D_M_BLK == 0 && M_pad_d >= 2 * g.K && g.A_pad % K1_BA == 0, "bad low-rank table geometry");
+    hipLaunchKernelGGL(diff_table_kernel, dim3(M_pad_d / 2, (g.A_pad + 255) / 256), dim3(256), 0, c->stream, d_kvec, d_kline, d_mean_all,
+                       d_idx, (_Float16*)d_diff, g.K, g.n_g, g.A_pad, dscale);
+    PSA_HIP_CHECK(hipGetLastError());
+    PSA_HIP_CHECK(hipMemsetAsync((char*)d_diff + (size_t)M_pad_d * g.A_pad * 2, 0, pd16_table_bytes(M_pad_d, g.A_pad) - (size_t)M_pad_d * g.A_pad * 2,
+                                 c->stream));
+    hipLaunchKernelGGL(node_table_kernel, dim3(LOWRANK_NODES, (g.A_pad + 255) / 256), dim3(256), 0, c->stream, d_geo, d_kappa, d_mean_all,
+                       d_idx, (_Float16*)d_nodes, g.n_g, g.A_pad);
+    PSA_HIP_CHECK(hipGetLastError());
+    return PSA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// q[j, c, t] += sum_l C[j, l] Qn[l, c, t]: float32, l in order (the result of a row does not depend on the
+// other rows of the launch).  A thread holds the 64 node values of one (c, t) and walks JB rows; C is uniform
+// across the block (scalar loads).
+// ---------------------------------------------------------------------------------------------
+constexpr int COMBINE_JB = 64;
+__global__ void __launch_bounds__(256)
+lowrank_combine_kernel(const float2* __restrict__ Qn, const float2* __restrict__ Cm, float2* __restrict__ q, int64_t T,
+                       int64_t q_stride, int64_t qn_stride, int K) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int     c = blockIdx.y;
+    const int     j0 = blockIdx.z * COMBINE_JB;
+    if (t >= T) return;
+    float2 v[LOWRANK_NODES];
+#pragma unroll
+    for (int l = 0; l < LOWRANK_NODES; ++l) v[l] = Qn[((int64_t)l * 3 + c) * qn_stride + t];
+    const int j1 = j0 + COMBINE_JB < K ? j0 + COMBINE_JB : K;
+    for (int j = j0; j < j1; ++j) {
+        const float2* cj = Cm + (size_t)j * LOWRANK_NODES;
+        float         sr = 0.f, si = 0.f;
+#pragma unroll
+        for (int l = 0; l < LOWRANK_NODES; ++l) {
+            const float2 w = cj[l];
+            sr = __fmaf_rn(w.x, v[l].x, sr);
+            sr = __fmaf_rn(-w.y, v[l].y, sr);
+            si = __fmaf_rn(w.x, v[l].y, si);
+            si = __fmaf_rn(w.y, v[l].x, si);
+        }
+        float2& o = q[((int64_t)j * 3 + c) * q_stride + t];
+        o = make_float2(o.x + sr, o.y + si);
+    }
+}
+
+int launch_lowrank_combine(psa_ctx* c, const float2* d_qn, const float2* d_C, float2* d_q, const ProjGeom& g, int64_t qn_stride) {
+    const int64_t nb = (g.T + 255) / 256;
+    PSA_REQUIRE(nb < (1ll << 31) && g.K > 0, "combine grid too large");
+    hipLaunchKernelGGL(lowrank_combine_kernel, dim3((unsigned)nb, 3, (unsigned)((g.K + COMBINE_JB - 1) / COMBINE_JB)), dim3(256), 0,
+                       c->stream, d_qn, d_C, d_q, g.T, g.q_stride, qn_stride, g.K);
+    PSA_HIP_CHECK(hipGetLastError());
+    return PSA_OK;
+}
+
+}  // namespace psa

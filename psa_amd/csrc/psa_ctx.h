@@ -110,6 +110,7 @@ struct TimingState {
 // P' (phase table) lives in HBM as the LDS tile images the projection kernel DMAs in:
 //   [M block][atom stage][row in block][K1_PROW floats: 32 atoms + 4 pad]
 constexpr int K1_BA   = 32;   // atoms per LDS stage
+constexpr int LOWRANK_NODES = 64;   // node rows of the low-rank route for k-paths (api_lowrank.hip)
 constexpr int K1_VROW = 96;   // floats per staged V row (32 atoms x 3 components)
 constexpr int K1_PROW = 36;   // floats per staged P' row (odd number of 16-byte slots)
 
@@ -132,6 +133,9 @@ struct ProjGeom {
     int     split = 0;    // 0: float32 kernels; 2: "2 x f16" kernel (k1_pair.hip); 3: "3 x bf16" (k1_split.hip);
                           // 4: "2 x f16" from the group's cached split planes (k1_planes.hip)
     float   vscale = 0.f; // split == 2: power of two applied to d (from the slot's largest magnitude)
+    bool    lowrank = false;  // split == 4 through the low-rank route for k-paths (api_lowrank.hip, k1_planes_diff.hip)
+    int     M_pad_d = 0;      // lowrank: rows of the D image (2K rounded up to 512)
+    float   dscale = 0.f;     // lowrank: power of two the D image carries
 };
 
 // A group's data as cached split planes (k1_f16.h plane_index): built from one generation of one
@@ -231,6 +235,12 @@ struct psa_ctx {
     int64_t      opt_fft_prime = 1;
     int64_t      opt_k1_wide = 1;               // PSA_OPT_K1_WIDE: 256-row M blocks (k1_planes_wide.hip) where the k-list fills them (k1_planes_block_rows)
     int64_t      opt_k1_loader_waves = 1;       // PSA_OPT_K1_LOADER_WAVES: 128-row M blocks through k1_planes_lw.hip
+    int64_t      opt_k1_lowrank = 1;            // PSA_OPT_K1_LOWRANK: k-paths through the node rows + D pass (api_lowrank.hip)
+    int64_t      opt_k1_lowrank_min_k = 256;    // PSA_OPT_K1_LOWRANK_MIN_K: shortest whole k-list it serves
+    int64_t      opt_k1_lowrank_min_local = 128; // PSA_OPT_K1_LOWRANK_MIN_LOCAL: shortest part of it one launch serves
+    int64_t      lowrank_launches = 0;          // projection launches that took the route (psa_k1_lowrank_launches)
+    // its D image, node projections, C, fp64 inputs (the node table goes into d_phase); released when the route is switched off
+    psa::DevBuf  d_lr_diff, d_lr_qn, d_lr_C, d_lr_f64;
 
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
@@ -296,6 +306,15 @@ int    launch_k1_planes_lw(psa_ctx* c, const void* d_planes, const void* d_phase
 // --- k1_planes_wide.hip (256-row M blocks: k-lists of more than 64 vectors under PSA_OPT_K1_WIDE)
 int    launch_k1_planes_wide(psa_ctx* c, const void* d_planes, const void* d_phase, float2* d_q, const ProjGeom& g,
                              int64_t n_fg);
+
+// --- k1_planes_diff.hip (low-rank route for k-paths: tables, D pass, combine; planned in api_lowrank.hip)
+size_t pd16_table_bytes(int M_pad, int A_pad);
+int    launch_lowrank_tables(psa_ctx* c, const float* d_kvec, const double* d_kline, const double* d_geo, const double* d_kappa,
+                             const float* d_mean_all, const int* d_idx, void* d_diff, void* d_nodes, const ProjGeom& g, int M_pad_d,
+                             float dscale);
+int    launch_k1_planes_diff(psa_ctx* c, const void* d_planes, const void* d_diff, float2* d_q, const ProjGeom& g, int64_t n_fg,
+                             float dscale);
+int    launch_lowrank_combine(psa_ctx* c, const float2* d_qn, const float2* d_C, float2* d_q, const ProjGeom& g, int64_t qn_stride);
 
 // --- k2_epilogue.hip
 int launch_dft_bin(psa_ctx* c, const float2* d_q, int64_t T, int64_t bin, float2* d_out3);

@@ -340,6 +340,10 @@ class KShardGroup:
             # a frame-sharded slot holds T/n frames while the FFT runs over all T: the plan primed from
             # the slot's own length (PSA_OPT_FFT_PRIME) would be compiled for nothing
             engine.set_option(_hip.OPT_FFT_PRIME, 0)
+        if self.nranks > 1 and hasattr(engine, "set_option"):
+            # every rank decides alike: shards under 256 k-vectors stay on the dense kernels, where a half-empty
+            # 512-row block of the low-rank route's difference pass does not pay
+            engine.set_option(_hip.OPT_K1_LOWRANK_MIN_LOCAL, 256)
         if self.nranks > 1:
             # the host driver of this pool supports dmabuf IPC only: without this RCCL's peer-memory
             # exchange fails with "hipIpcGetMemHandle: invalid argument".  `_hip.load_library` sets it

@@ -1,0 +1,157 @@
+"""The host plan of the low-rank route for k-paths (api_lowrank.hip, psa_lowrank_plan): which lists it serves, that
+its combine matrix times the node exponentials gives the line's phases, that its bound on D holds, and that it does
+not depend on how a path is split.  No GPU: the plan is host code, the D-pass kernel is checked by its resources."""
+import re
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+SRC = ROOT / "psa_amd" / "csrc"
+
+
+def _path(cfg):
+    from psa_amd import synth
+    from psa_amd.core.sed_calculator import SEDCalculator
+    from psa_amd.core.trajectory import Trajectory
+    spec, req = synth.baseline_spec(cfg)
+    r0, types, box = synth.lattice(spec.cells)
+    stub = np.zeros((1, spec.n_atoms, 3), np.float32)
+    calc = SEDCalculator(Trajectory(stub, stub, types, np.zeros(1, np.float32), box, np.diag(box).copy(),
+                                    np.zeros(3, np.float32), spec.dt_ps), *spec.cells)
+    if req["kind"] != "path":
+        return r0, None, calc
+    _, vecs = calc.get_k_path(req["direction"], req["bz_coverage"], req["n_k"])
+    return r0, np.asarray(vecs, np.float32), calc
+
+
+def _check_plan(p, vecs, r0, n_atoms=4096):
+    r = r0[np.linspace(0, len(r0) - 1, n_atoms).astype(int)].astype(np.float64)
+    x = r @ p["u"]
+    W = np.exp(1j * (r @ p["k0"]))[None, :] * np.exp(1j * np.outer(p["kappa"], x - p["x_c"]))      # (64, A)
+    kap = (vecs.astype(np.float64) - p["k0"]) @ p["u"]
+    kline = p["k0"][None, :] + kap[:, None] * p["u"][None, :]
+    exact = np.exp(1j * (kline @ r.T))
+    got = p["C"].astype(np.complex128) @ W
+    # C is stored as complex64: 2^-24 per entry, summed over 64 nodes with a Lebesgue constant of a few
+    assert np.max(np.abs(got - exact)) < 1e-6
+    # in fp64 (C rebuilt from the nodes) the interpolation itself is exact to 1e-10
+    bw = (-1.0) ** np.arange(64) * np.sin(np.pi * (2 * np.arange(64) + 1) / 128)
+    L = bw[None, :] / (kap[:, None] - p["kappa"][None, :])
+    L /= L.sum(axis=1, keepdims=True)
+    got64 = (np.exp(1j * kap * p["x_c"])[:, None] * L) @ W
+    assert np.max(np.abs(got64 - exact)) < 1e-10
+    # the reference's float32 phases stay within the bound of the line's
+    rf = r.astype(np.float32)
+    k32 = vecs.astype(np.float32)
+    arg = np.float32(k32[:, None, 2] * rf[None, :, 2] + (k32[:, None, 1] * rf[None, :, 1] + k32[:, None, 0] * rf[None, :, 0]))
+    assert np.max(np.abs(np.exp(1j * arg.astype(np.float64)) - exact)) <= p["d_bound"]
+    assert p["d_bound"] <= 2.0 ** -13 and p["d_bound"] * p["dscale"] <= 2.0 ** 14
+
+
+@pytest.mark.parametrize("cfg", ["C1", "C2", "C3", "C5"])
+def test_paths_get_a_plan(cfg):
+    from psa_amd import _hip
+    r0, vecs, _ = _path(cfg)
+    p = _hip.lowrank_plan(vecs, r0)
+    assert p is not None and p["interval"] == 0
+    _check_plan(p, vecs, r0)
+
+
+def test_golden_large_phase_path():
+    """A path whose phases reach far (the large-phase golden cases' regime): positions pushed out by 100."""
+    from psa_amd import _hip
+    r0, vecs, _ = _path("C2")
+    r = (r0[:8192] + np.float32(100.0)).astype(np.float32)
+    p = _hip.lowrank_plan(vecs, r)
+    if p is not None:
+        _check_plan(p, vecs, r)
+
+
+def test_grids_offline_and_nan_fall_back():
+    from psa_amd import _hip
+    r0, vecs, calc = _path("C3")
+    rng = np.random.default_rng(3)
+    assert _hip.lowrank_plan(rng.normal(size=(64, 3)).astype(np.float32), r0) is None              # off the line
+    bent = vecs.copy()
+    bent[len(bent) // 2:, 2] += np.float32(0.01)
+    assert _hip.lowrank_plan(bent, r0) is None
+    bad = vecs.copy()
+    bad[5, 0] = np.nan
+    assert _hip.lowrank_plan(bad, r0) is None
+    bad_r = r0.copy()
+    bad_r[7, 1] = np.inf
+    assert _hip.lowrank_plan(vecs, bad_r) is None
+    g = np.stack(np.meshgrid(np.linspace(-1, 1, 8), np.linspace(-1, 1, 8), [0.0], indexing="ij"), -1).reshape(-1, 3)
+    assert _hip.lowrank_plan(g.astype(np.float32), r0) is None                                     # a grid (C4's kind)
+    assert _hip.lowrank_plan(vecs[:1], r0) is None
+
+
+def test_lines_it_declines():
+    """Lines the float32 k-vectors do not determine exactly -- off Gamma, or along a direction that is not a lattice
+    direction -- and lists that cross Gamma stay on the dense kernels (their plan would depend on the sub-list)."""
+    from psa_amd import _hip
+    r0, vecs, _ = _path("C3")
+    shifted = vecs + np.float32([0.0123, 0.0456, 0.0789])
+    assert _hip.lowrank_plan(shifted, r0) is None
+    assert _hip.lowrank_plan(shifted[128:], r0) is None
+    t = np.linspace(0.0, 0.8, 200)[:, None]
+    odd = (t * np.array([1.0, 0.3127, 0.0713]) / np.linalg.norm([1.0, 0.3127, 0.0713])).astype(np.float32)
+    assert _hip.lowrank_plan(odd, r0) is None
+    crossing = np.concatenate([-vecs[:0:-1], vecs])
+    assert _hip.lowrank_plan(crossing, r0) is None
+
+
+@pytest.mark.parametrize("sign", [1, -1])
+def test_sub_lists_get_the_same_plan(sign):
+    """Halves, thirds, an inner slice -- of the path and of its mirror image (Gamma towards -[110]): the same u, k0,
+    interval, nodes and, row by row, the same C, bit for bit."""
+    from psa_amd import _hip
+    r0, vecs, _ = _path("C3")
+    vecs = (sign * vecs).astype(np.float32)
+    whole = _hip.lowrank_plan(vecs, r0)
+    assert whole is not None and whole["interval"] == (0 if sign > 0 else -1)
+    _check_plan(whole, vecs, r0)
+    for lo, hi in [(0, 128), (128, 256), (0, 96), (96, 200), (200, 256), (37, 219)]:
+        p = _hip.lowrank_plan(vecs[lo:hi], r0)
+        assert p is not None
+        for key in ("u", "k0", "kappa"):
+            assert np.array_equal(p[key], whole[key]), key
+        for key in ("x_c", "h_x", "width", "interval"):
+            assert p[key] == whole[key], key
+        assert np.array_equal(p["C"].view(np.uint32), whole["C"][lo:hi].view(np.uint32))
+
+
+def test_index_list_group():
+    from psa_amd import _hip
+    r0, vecs, _ = _path("C3")
+    idx = np.arange(0, len(r0), 2, dtype=np.int32)
+    p = _hip.lowrank_plan(vecs, r0, idx)
+    assert p is not None
+    _check_plan(p, vecs, r0[idx])
+
+
+def test_diff_kernel_uses_no_scratch(tmp_path):
+    """The D pass waits for its LDS-DMA with a counted vmcnt: no scratch, no spill (tests/test_kernel_resources.py)."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not Path(hipcc).exists():
+        pytest.skip("no hipcc")
+    line = next(ln for ln in (SRC / "Makefile").read_text().splitlines() if ln.startswith("CXXFLAGS"))
+    cont = (SRC / "Makefile").read_text().split(line)[1].splitlines()[1]
+    flags = [f.replace("$(ARCH)", "gfx950").replace("$(ROOT)", str(ROOT))
+             for f in (line.split(":=")[1].rstrip("\\") + " " + cont).split() if not f.startswith("-W")]
+    res = subprocess.run([hipcc, *flags, "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
+                          str(SRC / "k1_planes_diff.hip"), "-o", str(tmp_path / "k.s")], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", res.stderr)]
+    spills = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", res.stderr)]
+    assert scratch and all(s == 0 for s in scratch), res.stderr[-1500:]
+    assert all(s == 0 for s in spills), spills
+    asm = (tmp_path / "k.s").read_text()
+    assert "scratch_" not in asm
+    # two instantiations x 40 unrolled stages x 16 row tiles x 3 components
+    assert asm.count("v_mfma_f32_16x16x32_f16") == 2 * 40 * 48
