@@ -3,16 +3,20 @@
 SED hot-path benchmark (contract: see the task's bench.py section).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--summation coherent]
-                    [--shard auto|k|frames] [--dump-outputs DIR]
+                    [--shard auto|k|frames] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one synthetic trajectory already resident in HBM:
 phase table -> k-projection (split-precision f16 MFMA from the group's cached split planes,
 fp32-equivalent) -> batched rocFFT over time -> scale / |.|^2 epilogue -> (N > 1: exchange, see
 below) -> transpose to the reference's (T,K,3) layout + SED.intensity, result left on the device.
 Default workload is the configuration BASELINE.json's target is quoted on (C3: 32768 atoms x 65536
-steps x 256 k-points, [110] path, basis types [1,2]); it fits one MI355X.  The same JSON line
-carries `end_to_end` (the public `SEDCalculator.calculate` on the resident trajectory, result as a
-host ndarray) and `variants` (the other summation mode: the two basis types as separate groups).
+steps x 256 k-points, [110] path, basis types [1,2]); it fits one MI355X.  A plain run sets up,
+warms up, times the steps, writes --dump-outputs and prints the line: the headline, `roofline`
+(from the timed launches), `stages_ms_per_step` and `first_step`.  With --full the same JSON line
+also carries `end_to_end` (the public `SEDCalculator.calculate` on the resident trajectory, result
+as a host ndarray), `variants` (the other summation mode: the two basis types as separate groups),
+`shards`, `first_call` and `cpu_baseline` (N = 1), and N > 1 checks the gathered result against a
+one-GPU recomputation.
 
 N > 1: one process per GPU.  `python bench.py --gpus N` starts the N ranks itself (children of
 this process, before anything touches HIP); under a launcher that already exported WORLD_SIZE
@@ -90,12 +94,17 @@ def parse_args(argv=None):
                          "bf16x3 = 3xbf16 split-precision MFMA, mfma32 = exact-fp32 MFMA")
     ap.add_argument("--even-split", action="store_true",
                     help="N > 1, mode k: give every rank the same number of k-points instead of the root-heavy split")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check more than the headline figure: end_to_end, variants, shards, first_call, "
+                         "cpu_baseline and (N > 1) the gathered result against a one-GPU recomputation; the --no-* "
+                         "options below leave parts of it out")
     ap.add_argument("--no-check", action="store_true",
-                    help="N > 1: skip the comparison of the gathered result with a one-GPU recomputation on rank 0")
+                    help="with --full, N > 1: skip the comparison of the gathered result with a one-GPU recomputation on rank 0")
     ap.add_argument("--check", action="store_true", help="N = 1: no effect (kept for old command lines)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip end_to_end, variants, shards, first_call (kernel experiments)")
-    ap.add_argument("--no-first-call", action="store_true", help="skip the first_call probe (writes a 1.6 GB file)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip end_to_end, variants, shards, first_call (kernel experiments)")
+    ap.add_argument("--no-first-call", action="store_true", help="with --full: skip the first_call probe (writes a 1.6 GB file)")
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames in the CPU-baseline sample (0 = auto)")
     ap.add_argument("--stub-engine", action="store_true",
                     help="TEST ONLY: run the orchestration (spawn, rendezvous, sharding, host exchange, JSON) with an "
@@ -427,9 +436,9 @@ def main():
     _, k_cnt = group.ranges(K, T)
     real = not args.stub_engine
 
-    # N > 1: the gathered result against a one-GPU recomputation on rank 0 (default on)
+    # N > 1, --full: the gathered result against a one-GPU recomputation on rank 0
     shard_check = None
-    if world > 1 and not args.no_check and real:
+    if args.full and world > 1 and not args.no_check and real:
         gathered = None
         if group.has_result:
             gathered = engine.finalize(T, K, True) if intensity_out else engine.result_intensity(T, K)
@@ -447,7 +456,7 @@ def main():
 
     # ------------------------------------------------------------------ variants (collective)
     variants = {}
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras
     v_steps = max(3, args.steps // 2)
 
     def variant(n_units, seconds, by_rank, k1, what, **more):
@@ -697,7 +706,7 @@ def main():
                 out["first_call"] = first_call_probe(engine)
             except Exception as err:                    # noqa: BLE001
                 out["first_call"] = {"error": f"{type(err).__name__}: {err}"}
-        if not args.no_cpu_baseline and real:
+        if args.full and not args.no_cpu_baseline and real:
             n_frames = args.cpu_frames or int(min(T, max(64, 2 ** int(np.log2(1.0e11 / (n_sum_atoms * K))))))
             call_kw = dict(kw, summation_mode=args.summation)
             n_units, times, vel, ref_int, mean_sample = cpu_baseline(spec, tables, r0, types, vecs, call_kw, n_frames)

@@ -25,7 +25,7 @@ def _run(*extra, env=None):
 
 @pytest.mark.parametrize("shard, n", [("k", 2), ("frames", 2), ("auto", 3)])
 def test_bench_spawns_its_ranks_and_prints_one_line(shard, n):
-    res = _run("--gpus", str(n), "--shard", shard)
+    res = _run("--gpus", str(n), "--shard", shard, "--full")
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, res.stdout
@@ -54,6 +54,28 @@ def test_bench_spawns_its_ranks_and_prints_one_line(shard, n):
     else:
         sk = out["variants"]["shard_k"]
         assert sk["shard_mode"] == "k" and sum(sk["k_points_per_rank"]) == 32 and len(sk["k_points_per_rank"]) == n
+
+
+# what only --full measures or checks; a plain run's line has none of it
+FULL_ONLY = {"end_to_end", "variants", "shards", "first_call", "cpu_baseline", "shard_check_max_rel"}
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_a_plain_run_leaves_the_rest_to_full(n):
+    """Without --full the line holds the headline figure and what the timed steps measured themselves
+    (roofline, stages, first step); --full adds the other measurements to the same line."""
+    lines = {}
+    for opt in ((), ("--full",)):
+        res = _run("--gpus", str(n), *opt)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines[opt] = json.loads(res.stdout.strip())
+    plain, full = lines[()], lines[("--full",)]
+    assert not FULL_ONLY & set(plain)
+    assert {"roofline", "stages_ms_per_step", "first_step"} <= set(plain)
+    assert "end_to_end" in full and ("variants" in full) == (n > 1)      # (C1 has one atom group: no other summation mode)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "config"):
+        assert plain[key] == full[key], key
+    assert plain["ms_per_step"] >= 0 and full["ms_per_step"] >= 0
 
 
 def test_bench_runs_as_one_rank_under_a_launcher():

@@ -1,6 +1,6 @@
 #!/bin/bash
 # The round's profiling passes (GPU box): rocprofv3 kernel statistics of the timed workload and of the
-# default command, then the PMC passes of the projection kernel at K = 256 / 64 / 32.
+# full command (bench.py --full), then the PMC passes of the projection kernel at K = 256 / 64 / 32.
 #   tools/profile_round.sh r3        -> gpurun_out/prof_r3*, gpurun_out/pmc_r3*.json ; then tools/make_profiles.py r3
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -10,6 +10,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/gpurun_out/prof_$
   > "$ROOT/gpurun_out/prof_${tag}_bench.json" 2> "$ROOT/gpurun_out/prof_${tag}.err"
 echo "stats pass 1 done"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/gpurun_out/prof_${tag}_default" -- python3 "$ROOT/bench.py" \
+  --full \
   > "$ROOT/gpurun_out/prof_${tag}_default_bench.json" 2> "$ROOT/gpurun_out/prof_${tag}_default.err"
 echo "stats pass 2 done"
 "$ROOT/tools/pmc_k1.sh" $tag > /dev/null
