@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PSA_HIP_ABI_VERSION 3
+#define PSA_HIP_ABI_VERSION 4
 
 /* error codes */
 #define PSA_OK          0
@@ -178,6 +178,19 @@ int psa_mean_positions(psa_ctx* ctx, int slot, float* mean_host /* (N,3) */);
  * frames like NumPy's -- bit-identical to np.mean(x, axis=0, dtype=np.float32), one pass at memory
  * bandwidth.  No context, no GPU. */
 int psa_host_mean_frames(const float* x /* (T, cols) */, int64_t T, int64_t cols, float* mean_out, int threads);
+
+/* Per-atom weights (mass-weighted or charge-weighted SED): from this call on, every projection on the
+ * context -- psa_sed_project, _project_upload, _calculate, _fs_project, _single_bin and the psa_debug_*
+ * projections -- computes
+ *     q[k,c,t] = sum_a  w[idx[a]] * d[t, idx[a], c] * P[k,a]
+ * (the phase still from the unweighted mean positions; FFT, /T, |.|^2, group sums, pair folding and the
+ * chiral phase unchanged) until it is cleared with w = NULL.  w: N finite float32 values, copied to the
+ * device during the call; a non-finite entry is PSA_EINVAL, and so is a projection whose slot holds a
+ * different number of atoms.  The weight enters the phase table, never the data: the resident arrays,
+ * their split planes and the plane cache are untouched.  The float16 tables hold w * 2^-e, 2^e the
+ * smallest power of two >= max|w|, and the launch multiplies 2^e back exactly.  With no weights set every
+ * result is bit for bit what it is without this call. */
+int psa_set_atom_weights(psa_ctx* ctx, const float* w /* N, or NULL to clear */, int64_t N);
 
 /* ---- the hot path -------------------------------------------------------
  * psa_sed_project: for each of the G atom groups, for the K_local k-vectors given,

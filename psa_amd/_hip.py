@@ -28,7 +28,7 @@ OPT_K1_LOWRANK = 8
 OPT_K1_LOWRANK_MIN_K = 9
 OPT_K1_LOWRANK_MIN_LOCAL = 10
 KMAP_MIRROR = 0x80000000
-ABI_VERSION = 3
+ABI_VERSION = 4
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -59,6 +59,7 @@ SIGNATURES = {
                                           _f32p, _f32p, _f32p, _f32p]),
     "psa_mean_positions": (C.c_int, [_ctx, C.c_int, _f32p]),
     "psa_host_mean_frames": (C.c_int, [_f32p, C.c_int64, C.c_int64, _f32p, C.c_int]),
+    "psa_set_atom_weights": (C.c_int, [_ctx, _f32p, C.c_int64]),
     "psa_sed_project": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, C.c_int64, C.c_int64,
                                   _i32p, _i64p, C.c_int32, C.c_int32]),
     "psa_sed_project_upload": (C.c_int, [_ctx, C.c_int, _f32p, C.c_int64, C.c_int64, _f32p, _f32p, C.c_int64,
@@ -478,6 +479,19 @@ class Engine:
         return out
 
     # -- the hot path ----------------------------------------------------------------
+    def set_atom_weights(self, weights: Optional[np.ndarray]):
+        """Per-atom weights of every later projection on this context (psa_set_atom_weights): q = sum_a w_a d_a
+        exp(i k.r_a).  None clears them.  The resident arrays and their split planes are not touched."""
+        if weights is None:
+            _check(self._lib.psa_set_atom_weights(self._h, None, 0), "psa_set_atom_weights")
+            return
+        w = np.ascontiguousarray(weights, np.float32)
+        if w.ndim != 1 or w.size == 0:
+            raise ValueError(f"atom weights must be a non-empty (N,) array, got shape {w.shape}")
+        if not np.all(np.isfinite(w)):
+            raise ValueError("atom weights must be finite")
+        _check(self._lib.psa_set_atom_weights(self._h, _f32(w), w.shape[0]), "psa_set_atom_weights")
+
     def project(self, slot, mean_pos_all, k_vectors, groups=None, flags=0,
                 K_total=None, k_offset=0):
         mean = _as_f32(mean_pos_all, (3,))

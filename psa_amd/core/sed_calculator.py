@@ -32,6 +32,7 @@ import numpy as np
 from .. import _hip
 from ..io.writer import out_to_qdump
 from ..utils.helpers import parse_direction
+from ..weights import check_atom_weights
 from .sed import SED
 from .trajectory import Trajectory
 
@@ -154,10 +155,11 @@ class SEDCalculator:
         return [np.asarray(g) for g in groups]
 
     def _run_device(self, k_vectors: np.ndarray, groups, intensity: bool, mean_pos_all,
-                    fetch: bool = True):
+                    fetch: bool = True, atom_weights: Optional[np.ndarray] = None):
         """(result, sum_c |result|^2 or None): the second array accompanies a complex result -- it is
         what `SED.intensity` returns (core/sed.py:22-24), produced on the device in the pass that
-        writes the result."""
+        writes the result.  `atom_weights` (validated (N,) float32, or None) are set on the engine for
+        this calculation only; a sharded run needs nothing more, as every rank makes this same call."""
         slot, data, flags = self._data_slot()
         if intensity:
             flags |= _hip.F_INTENSITY
@@ -166,17 +168,23 @@ class SEDCalculator:
         with eng.lock:                       # project + finalize must not interleave across threads
             K = len(k_vectors)
             T = self.traj.n_frames
-            if self._shard is not None and self._shard.nranks > 1:
-                out = self._shard.run(slot, data, mean_pos_all, k_vectors, groups, flags, T, fetch, with_intensity=want)
-            elif not eng.is_resident(slot, data):
-                # first call on this array: upload and project, overlapped
-                eng.project_upload(slot, data, mean_pos_all, k_vectors, groups, flags)
-                out = eng.finalize(T, K, intensity, fetch, with_intensity=want)
-            elif fetch:                      # one library call; long complex results leave block by block
-                out = eng.calculate(slot, mean_pos_all, k_vectors, groups, flags, with_intensity=want)
-            else:
-                eng.project(slot, mean_pos_all, k_vectors, groups, flags)
-                out = eng.finalize(T, K, intensity, False, with_intensity=want)
+            if atom_weights is not None:     # (only then: an engine without weights never hears of them)
+                eng.set_atom_weights(atom_weights)
+            try:
+                if self._shard is not None and self._shard.nranks > 1:
+                    out = self._shard.run(slot, data, mean_pos_all, k_vectors, groups, flags, T, fetch, with_intensity=want)
+                elif not eng.is_resident(slot, data):
+                    # first call on this array: upload and project, overlapped
+                    eng.project_upload(slot, data, mean_pos_all, k_vectors, groups, flags)
+                    out = eng.finalize(T, K, intensity, fetch, with_intensity=want)
+                elif fetch:                  # one library call; long complex results leave block by block
+                    out = eng.calculate(slot, mean_pos_all, k_vectors, groups, flags, with_intensity=want)
+                else:
+                    eng.project(slot, mean_pos_all, k_vectors, groups, flags)
+                    out = eng.finalize(T, K, intensity, False, with_intensity=want)
+            finally:
+                if atom_weights is not None:  # no later calculation (iSED included) sees them
+                    eng.set_atom_weights(None)
         if want:
             return out if out is not None else (None, None)
         return out, None
@@ -308,7 +316,7 @@ class SEDCalculator:
                   basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None,
                   summation_mode: str = 'coherent',
                   k_grid_shape: Optional[Tuple[int, int]] = None,
-                  k_chunk_size: int = 500) -> SED:
+                  k_chunk_size: int = 500, *, atom_weights: Optional[np.ndarray] = None) -> SED:
         """SED of the trajectory at the given k-vectors (reference :182-336).
 
         coherent (or a single group): `sed` is (T,K,3) complex64; incoherent with several
@@ -316,9 +324,16 @@ class SEDCalculator:
         compatibility; the GPU handles all k-points in one pass over the trajectory
         instead of re-gathering it per chunk (:287-290), which the reference itself only
         matches to ~8e-7.
+
+        `atom_weights` (keyword only; not in the reference): (N,) real finite weights, one per atom of
+        the trajectory.  Every group's projection becomes sum_a w_a d[t,a,c] exp(i k.r_a), the phase
+        still from the unweighted mean positions; the rest is unchanged.  With w_a = sqrt(m_a)
+        (`psa_amd.mass_weights`) and one group per basis type, the incoherent sum is the mass-weighted
+        SED sum_b m_b |...|^2.  None: the unweighted result, bit for bit.
         """
         if summation_mode not in _MODES:
             raise ValueError(f"summation_mode must be 'coherent' or 'incoherent', got {summation_mode}")
+        weights = None if atom_weights is None else check_atom_weights(atom_weights, self.traj.n_atoms)
         n_t, n_atoms = self.traj.n_frames, self.traj.n_atoms
         if n_t == 0 or n_atoms == 0:
             logger.warning("Cannot calculate SED: 0 frames or 0 atoms.")
@@ -339,10 +354,10 @@ class SEDCalculator:
             # several coherent groups act as their sorted union (:297-298)
             members = np.unique(np.concatenate(groups)).astype(int) if len(groups) > 1 else groups[0]
             data, inten = self._run_device(np.asarray(k_vectors_3d), self._device_groups([members]), False,
-                                           mean_pos_all)
+                                           mean_pos_all, atom_weights=weights)
         else:
             data, inten = self._run_device(np.asarray(k_vectors_3d), self._device_groups(groups), True,
-                                           mean_pos_all)
+                                           mean_pos_all, atom_weights=weights)
         sed = SED(data, freqs, k_points_mags, k_vectors_3d, k_grid_shape=k_grid_shape,
                   is_complex=is_complex, phase=None)
         if inten is not None and isinstance(data, np.ndarray):
@@ -406,8 +421,9 @@ class SEDCalculator:
                             basis_atom_types=None, summation_mode: str = 'coherent',
                             basis_atom_indices=None, lat_param: Optional[float] = None,
                             chiral: bool = False, chiral_axis: str = 'z',
-                            k_chunk_size: int = 500) -> SED:
-        """k-path dispersion in one call (README.md:100-106; psa_gui.py:947-999)."""
+                            k_chunk_size: int = 500, *, atom_weights: Optional[np.ndarray] = None) -> SED:
+        """k-path dispersion in one call (README.md:100-106; psa_gui.py:947-999).  `atom_weights`: as for
+        `calculate`."""
         if chiral and summation_mode != 'coherent':
             logger.info("Chirality calculation selected, forcing coherent summation mode.")
             summation_mode = 'coherent'
@@ -417,22 +433,23 @@ class SEDCalculator:
         with self.engine.lock:
             sed = self.calculate(k_mags, k_vecs, basis_atom_indices=basis_atom_indices,
                                  basis_atom_types=basis_atom_types, summation_mode=summation_mode,
-                                 k_chunk_size=k_chunk_size)
+                                 k_chunk_size=k_chunk_size, atom_weights=atom_weights)
             return self._finish(sed, chiral, chiral_axis)
 
     def calculate_chiral_sed(self, direction, bz_coverage: float = 1.0, n_k: int = 100,
-                             chiral_axis: str = 'z', **kwargs) -> SED:
-        """README.md:117-122: a k-path SED with the chiral phase attached."""
+                             chiral_axis: str = 'z', *, atom_weights: Optional[np.ndarray] = None, **kwargs) -> SED:
+        """README.md:117-122: a k-path SED with the chiral phase attached.  `atom_weights`: as for
+        `calculate`."""
         return self.calculate_kpath_sed(direction, bz_coverage, n_k, chiral=True,
-                                        chiral_axis=chiral_axis, **kwargs)
+                                        chiral_axis=chiral_axis, atom_weights=atom_weights, **kwargs)
 
     def calculate_kgrid_sed(self, plane: str = 'xy', k_ranges=(-1.0, 1.0, -1.0, 1.0),
                             n_kx: int = 20, n_ky: int = 20, k_fixed: float = 0.0,
                             basis_atom_types=None, summation_mode: str = 'coherent',
                             basis_atom_indices=None, chiral: bool = False, chiral_axis: str = 'z',
-                            k_chunk_size: int = 500) -> SED:
+                            k_chunk_size: int = 500, *, atom_weights: Optional[np.ndarray] = None) -> SED:
         """2-D k-grid SED in one call (README.md:135-140; psa_gui.py:2135-2191).
-        `k_ranges` = (first_min, first_max, second_min, second_max)."""
+        `k_ranges` = (first_min, first_max, second_min, second_max).  `atom_weights`: as for `calculate`."""
         if chiral and summation_mode != 'coherent':
             logger.info("Chirality calculation selected for K-Grid, forcing coherent summation mode.")
             summation_mode = 'coherent'
@@ -441,7 +458,7 @@ class SEDCalculator:
         with self.engine.lock:
             sed = self.calculate(k_mags, k_vecs, basis_atom_indices=basis_atom_indices,
                                  basis_atom_types=basis_atom_types, summation_mode=summation_mode,
-                                 k_grid_shape=shape, k_chunk_size=k_chunk_size)
+                                 k_grid_shape=shape, k_chunk_size=k_chunk_size, atom_weights=atom_weights)
             return self._finish(sed, chiral, chiral_axis)
 
     # ------------------------------------------------------------------ iSED

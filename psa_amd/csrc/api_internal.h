@@ -103,6 +103,8 @@ struct LowRankPlan {
 int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, const int32_t* h_idx, int64_t n_g, LowRankPlan* p);
 int prepare_lowrank(psa_ctx* c, int slot, const float* k_host, int64_t nk, int64_t K_total, const float* mean_all,
                     const int32_t* h_idx, const PlaneSet* ps, ProjGeom* g);
+int    check_weights(psa_ctx* c, int64_t N);            // the context's atom weights fit a slot of N atoms
+void   set_geom_weights(const psa_ctx* c, ProjGeom* g);  // ... and go into a launch's geometry
 int    begin_result(psa_ctx* c, int64_t T, int64_t K_total, int64_t k_offset, bool intensity, char** rows, size_t* row_bytes);
 
 }  // namespace psa

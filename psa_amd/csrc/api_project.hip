@@ -204,11 +204,24 @@ int get_planes(psa_ctx* c, int slot, const int* d_idx, const int32_t* h_idx, int
     return PSA_OK;
 }
 
+// Per-atom weights (psa_set_atom_weights) of a projection over a slot of N atoms: none set, or N of them
+int check_weights(psa_ctx* c, int64_t N) {
+    PSA_REQUIRE(c->weights_N == 0 || c->weights_N == N, "atom weights were set for %lld atoms, the trajectory has %lld",
+                (long long)c->weights_N, (long long)N);
+    return PSA_OK;
+}
+
+void set_geom_weights(const psa_ctx* c, ProjGeom* g) {
+    g->weights = c->weights_N ? c->d_weights.as<float>() : nullptr;
+    g->wscale = c->weights_N ? c->weights_scale : 1.f;
+}
+
 // h_idx: the group's index list on the host (nullptr: all atoms in order); ps: its split planes, if any
 // force: 0 = the product rule; 3 = "3 x bf16" wherever it can serve (needs no scale: the streaming
 // upload projects frames before the whole array has been seen); -1 = the float32 kernel
 int make_geom(psa_ctx* c, int slot, int64_t K_local, int64_t n_g, const int* d_idx, const int32_t* h_idx,
               bool disp, const PlaneSet* ps, int force, ProjGeom* g) {
+    set_geom_weights(c, g);
     g->T = c->slot[slot].T;
     g->q_stride = g->T;
     g->N_tot = c->slot[slot].N;
@@ -462,6 +475,34 @@ using namespace psa;
 
 extern "C" {
 
+int psa_set_atom_weights(psa_ctx* c, const float* w, int64_t N) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    if (w == nullptr) {
+        c->weights_N = 0;
+        c->weights_scale = 1.f;
+        return PSA_OK;
+    }
+    PSA_REQUIRE(N >= 1 && N < (1ll << 31), "bad atom count %lld", (long long)N);
+    float wmax = 0.f;
+    for (int64_t a = 0; a < N; ++a) {
+        PSA_REQUIRE(std::isfinite(w[a]), "atom weight %lld is not finite", (long long)a);
+        wmax = std::max(wmax, std::fabs(w[a]));
+    }
+    // 2^e: the smallest power of two >= max|w| (all zero: 1), kept inside the float range
+    int e = 0;
+    if (wmax > 0.f) {
+        const float m = std::frexp(wmax, &e);        // wmax = m 2^e, m in [0.5, 1)
+        if (m == 0.5f) --e;
+        e = std::min(127, std::max(-126, e));
+    }
+    c->weights_N = 0;                                  // (no weights if the copy fails)
+    PSA_TRY(upload(c, c->d_weights, w, (size_t)N * sizeof(float)));
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));   // the caller's array is only read during the call
+    c->weights_N = N;
+    c->weights_scale = std::ldexp(1.f, e);
+    return PSA_OK;
+}
 
 int psa_sed_project(psa_ctx* c, int slot, const float* mean_pos_all, const float* k_vectors,
                     int64_t K_local, int64_t K_total, int64_t k_offset, const int32_t* group_idx,
@@ -474,6 +515,7 @@ int psa_sed_project(psa_ctx* c, int slot, const float* mean_pos_all, const float
     const bool    intensity = (flags & PSA_F_INTENSITY) != 0;
     bool          disp = (flags & PSA_F_DISPLACEMENTS) != 0;
     PSA_TRY(check_project_args(c, a, N));
+    PSA_TRY(check_weights(c, N));
     // the whole list on this device: k-vectors whose negation (or twin) is in the list are not projected
     std::vector<float>   uniq_k;
     std::vector<int32_t> kmap;
@@ -522,6 +564,7 @@ int psa_sed_project_upload(psa_ctx* c, int slot, const float* host, int64_t T, i
     PSA_REQUIRE(slot >= 0 && slot < PSA_NUM_SLOTS, "bad data slot %d", slot);
     PSA_REQUIRE(T > 0 && N > 0, "empty trajectory (T=%lld, N=%lld)", (long long)T, (long long)N);
     PSA_TRY(check_project_args(c, a, N));
+    PSA_TRY(check_weights(c, N));
     PSA_TRY(data_alloc_locked(c, slot, T, N));
     c->slot[slot].valid = false;
     const bool intensity = (flags & PSA_F_INTENSITY) != 0;
@@ -764,6 +807,7 @@ static int calculate_pipelined(psa_ctx* c, const ProjectArgs& a_in, void* out_ho
     const int64_t T = c->slot[slot].T, N = c->slot[slot].N;
     bool          disp = (a.flags & PSA_F_DISPLACEMENTS) != 0;
     PSA_TRY(check_project_args(c, a, N));
+    PSA_TRY(check_weights(c, N));
     std::vector<float>   uniq_k;
     std::vector<int32_t> kmap;
     const bool           folded = fold_k_list(c, a.k_vectors, K_out, &uniq_k, &kmap);
@@ -954,6 +998,7 @@ int psa_sed_single_bin(psa_ctx* c, int slot, const float* mean_pos_all, const fl
     const int64_t T = c->slot[slot].T, N = c->slot[slot].N;
     PSA_REQUIRE(mean_pos_all && k_vector && out_c64x3, "null argument");
     PSA_REQUIRE(i_w >= 0 && i_w < T, "frequency bin %lld outside [0,%lld)", (long long)i_w, (long long)T);
+    PSA_TRY(check_weights(c, N));
     if (idx) {
         PSA_REQUIRE(n_g >= 0, "negative group size");
         for (int64_t i = 0; i < n_g; ++i)
@@ -1086,7 +1131,9 @@ int psa_debug_phase_table(psa_ctx* c, const float* mean_pos_all, const float* k_
             PSA_REQUIRE(idx[i] >= 0 && idx[i] < N, "Atom indices in basis out of bounds.");
     else
         PSA_REQUIRE(n_g == N, "identity group must cover all atoms");
+    PSA_TRY(check_weights(c, N));
     ProjGeom g;
+    set_geom_weights(c, &g);
     g.n_g = (int)n_g;
     g.A_pad = (int)((n_g + 31) / 32 * 32);
     g.K = (int)K;
@@ -1124,6 +1171,7 @@ static int debug_project(psa_ctx* c, int slot, const float* mean_pos_all, const 
             PSA_REQUIRE(idx[i] >= 0 && idx[i] < N, "Atom indices in basis out of bounds.");
     else
         PSA_REQUIRE(n_g == N, "identity group must cover all atoms");
+    PSA_TRY(check_weights(c, N));
     PSA_TRY(upload(c, c->d_kvec, k_vectors, (size_t)K * 3 * sizeof(float)));
     PSA_TRY(upload(c, c->d_mean_all, mean_pos_all, (size_t)N * 3 * sizeof(float)));
     if (idx) PSA_TRY(upload(c, c->d_idx, idx, (size_t)n_g * sizeof(int32_t)));

@@ -131,6 +131,7 @@ int psa_sed_fs_project(psa_ctx* c, int slot, const float* mean_pos_all, const fl
     } else {
         n_g = N;
     }
+    PSA_TRY(check_weights(c, N));
     char*  rows = nullptr;
     size_t row_bytes = 0;
     PSA_TRY(begin_result(c, T_total, K_total, k_offset, intensity, &rows, &row_bytes));

@@ -317,10 +317,13 @@ k1_pair_kernel(const float* __restrict__ V, const _Float16* __restrict__ Pb, con
 // ---------------------------------------------------------------------------------------------
 // Phase table in split form: two float16 planes in the tile image the kernel reads.
 // Same float32 argument / sincos as phase_table_kernel (kernels_misc.hip); only the storage differs.
+// Per-atom weights w (may be null) enter as w * wnorm, wnorm = 2^-e with 2^e >= max|w|: |P'| stays <= 1 before
+// P_SCALE, inside the float16 range, and the launch multiplies 2^e back into qscale (powers of two: exact).
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 phase_table_f16_kernel(const float* __restrict__ kvec, const float* __restrict__ mean_all, const int* __restrict__ idx,
-                       _Float16* __restrict__ Pb, int K, int n_g, int A_pad, int M_pad, int m_blk) {
+                       const float* __restrict__ w, float wnorm, _Float16* __restrict__ Pb, int K, int n_g, int A_pad,
+                       int M_pad, int m_blk) {
     const int a = blockIdx.y * 256 + threadIdx.x;
     const int k = blockIdx.x;
     if (a >= A_pad || 2 * k >= M_pad) return;
@@ -332,6 +335,11 @@ phase_table_f16_kernel(const float* __restrict__ kvec, const float* __restrict__
         const float kx = kvec[3 * k + 0], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
         const float arg = __fmaf_rn(kz, rz, __fmaf_rn(ky, ry, __fmul_rn(kx, rx)));
         sincosf(arg, &cs[1], &cs[0]);
+        if (w) {
+            const float wa = w[src] * wnorm;
+            cs[0] *= wa;
+            cs[1] *= wa;
+        }
     }
     const int n_stage = A_pad / K1_BA;
 #pragma unroll
@@ -352,8 +360,8 @@ size_t pf16_table_bytes(int M_pad, int A_pad) { return (size_t)M_pad * A_pad * 2
 int launch_phase_table_f16(psa_ctx* c, const float* d_kvec, const float* d_mean_all, const int* d_idx, void* d_phase,
                            const ProjGeom& g) {
     dim3 grid(g.M_pad / 2, (g.A_pad + 255) / 256);
-    hipLaunchKernelGGL(phase_table_f16_kernel, grid, dim3(256), 0, c->stream, d_kvec, d_mean_all, d_idx, (_Float16*)d_phase,
-                       g.K, g.n_g, g.A_pad, g.M_pad, g.m_blk);
+    hipLaunchKernelGGL(phase_table_f16_kernel, grid, dim3(256), 0, c->stream, d_kvec, d_mean_all, d_idx, g.weights,
+                       1.f / g.wscale, (_Float16*)d_phase, g.K, g.n_g, g.A_pad, g.M_pad, g.m_blk);
     PSA_HIP_CHECK(hipGetLastError());
     if (g.m_blk == 256)
         PSA_HIP_CHECK(hipMemsetAsync((char*)d_phase + (size_t)g.M_pad * g.A_pad * 2 * F16x2::NP, 0, PF16_PAD_BYTES, c->stream));
@@ -393,7 +401,7 @@ static int launch_pair_variant(psa_ctx* c, const float* d_v, const void* d_phase
     const int64_t n_tblk = (g.T + C::T_BLK - 1) / C::T_BLK;
     const int64_t grid = ((n_tblk + 7) / 8) * 8 * n_mblk;
     PSA_REQUIRE(grid < (1ll << 31) && n_tblk < (1ll << 31), "projection grid too large");
-    const float qscale = 1.f / (g.vscale * F16x2::P_SCALE);           // powers of two: exact
+    const float qscale = 1.f / (g.vscale * F16x2::P_SCALE) * g.wscale;   // powers of two: exact
     hipLaunchKernelGGL((k1_pair_kernel<MT16, GATHER>), dim3((unsigned)grid), dim3(512), 0, c->stream, d_v,
                        (const _Float16*)d_phase, d_idx, d_q, g.T, g.q_stride, g.N_tot, g.n_g, g.A_pad / K1_BA, g.K, n_mblk, (int)n_tblk,
                        g.vscale, qscale);

@@ -550,7 +550,7 @@ static int launch_planes_variant(psa_ctx* c, const void* d_planes, const void* d
     const int64_t n_tblk = (g.T + C::T_BLK - 1) / C::T_BLK;
     const int64_t grid = ((n_tblk + 7) / 8) * 8 * n_mblk;
     PSA_REQUIRE(grid < (1ll << 31) && n_tblk < (1ll << 29) && n_fg < (1ll << 31), "projection grid too large");
-    const float qscale = 1.f / (g.vscale * F16x2::P_SCALE);           // powers of two: exact
+    const float qscale = 1.f / (g.vscale * F16x2::P_SCALE) * g.wscale;   // powers of two: exact (wscale: psa_ctx.h)
     if (n_mblk == 1)
         hipLaunchKernelGGL((k1_planes_kernel<MT16, RING, true>), dim3((unsigned)grid), dim3(512), 0, c->stream,
                            (const _Float16*)d_planes, (const _Float16*)d_phase, d_q, g.T, g.q_stride, (int)n_fg,

@@ -229,7 +229,7 @@ int launch_k1_planes_diff(psa_ctx* c, const void* d_planes, const void* d_diff, 
     const int64_t n_tblk = (g.T + D_T_BLK - 1) / D_T_BLK;
     const int64_t grid = ((n_tblk + 7) / 8) * 8 * n_mblk;
     PSA_REQUIRE(grid < (1ll << 31) && n_tblk < (1ll << 29) && n_fg < (1ll << 31), "projection grid too large");
-    const float qscale = 1.f / (g.vscale * dscale);                      // powers of two: exact
+    const float qscale = 1.f / (g.vscale * dscale) * g.wscale;           // powers of two: exact (wscale: psa_ctx.h)
     if (n_mblk == 1)
         hipLaunchKernelGGL((k1_planes_diff_kernel<true>), dim3((unsigned)grid), dim3(512), 0, c->stream, (const _Float16*)d_planes,
                            (const _Float16*)d_diff, d_q, g.T, g.q_stride, (int)n_fg, g.A_pad / K1_BA, g.K, n_mblk, (int)n_tblk, qscale);
@@ -246,9 +246,12 @@ int launch_k1_planes_diff(psa_ctx* c, const void* d_planes, const void* d_diff, 
 // D[j, a] = (P_ref - P_line) * dscale, one float16 piece.  P_ref exactly as phase_table_f16_kernel (k1_pair.hip)
 // computes it -- the same float32 FMA chain and sincosf, under the same compiler flags --, P_line from the k-vector
 // projected on the plan's line, kline[3 j..], in fp64.  Rows past 2K and atoms past n_g are zero.
+// Per-atom weights w (may be null): the route is linear per atom column, so D and the node rows both carry the same
+// w * wnorm (phase_table_f16_kernel, k1_pair.hip): |w wnorm| <= 1 keeps |D| under the plan's bound and dscale valid.
 __global__ void __launch_bounds__(256)
 diff_table_kernel(const float* __restrict__ kvec, const double* __restrict__ kline, const float* __restrict__ mean_all,
-                  const int* __restrict__ idx, _Float16* __restrict__ Db, int K, int n_g, int A_pad, float dscale) {
+                  const int* __restrict__ idx, const float* __restrict__ w, float wnorm, _Float16* __restrict__ Db, int K,
+                  int n_g, int A_pad, float dscale) {
     const int a = blockIdx.y * 256 + threadIdx.x;
     const int k = blockIdx.x;
     if (a >= A_pad) return;
@@ -263,8 +266,9 @@ diff_table_kernel(const float* __restrict__ kvec, const double* __restrict__ kli
         const double th = kline[3 * k + 0] * (double)rx + kline[3 * k + 1] * (double)ry + kline[3 * k + 2] * (double)rz;
         double       se, ce;
         sincos(th, &se, &ce);
-        d[0] = (float)(((double)cs[0] - ce) * (double)dscale);
-        d[1] = (float)(((double)cs[1] - se) * (double)dscale);
+        const double wa = w ? (double)(w[src] * wnorm) : 1.0;
+        d[0] = (float)(((double)cs[0] - ce) * (double)dscale * wa);
+        d[1] = (float)(((double)cs[1] - se) * (double)dscale * wa);
     }
     const int n_stage = A_pad / K1_BA;
     Db[pd16_index(2 * k, a, n_stage)] = (_Float16)d[0];
@@ -276,7 +280,8 @@ diff_table_kernel(const float* __restrict__ kvec, const double* __restrict__ kli
 // geo = {k0 (3), u (3), x_c}; kappa: the 64 nodes
 __global__ void __launch_bounds__(256)
 node_table_kernel(const double* __restrict__ geo, const double* __restrict__ kappa, const float* __restrict__ mean_all,
-                  const int* __restrict__ idx, _Float16* __restrict__ Pb, int n_g, int A_pad) {
+                  const int* __restrict__ idx, const float* __restrict__ w, float wnorm, _Float16* __restrict__ Pb, int n_g,
+                  int A_pad) {
     const int a = blockIdx.y * 256 + threadIdx.x;
     const int l = blockIdx.x;
     if (a >= A_pad) return;
@@ -286,6 +291,11 @@ node_table_kernel(const double* __restrict__ geo, const double* __restrict__ kap
         const double rx = mean_all[3 * (size_t)src + 0], ry = mean_all[3 * (size_t)src + 1], rz = mean_all[3 * (size_t)src + 2];
         const double th = (geo[0] * rx + geo[1] * ry + geo[2] * rz) + kappa[l] * ((geo[3] * rx + geo[4] * ry + geo[5] * rz) - geo[6]);
         sincos(th, &cs[1], &cs[0]);
+        if (w) {
+            const double wa = (double)(w[src] * wnorm);
+            cs[0] *= wa;
+            cs[1] *= wa;
+        }
     }
     const int n_stage = A_pad / K1_BA;
 #pragma unroll
@@ -302,12 +312,12 @@ int launch_lowrank_tables(psa_ctx* c, const float* d_kvec, const double* d_kline
                           float dscale) {
     PSA_REQUIRE(M_pad_d % D_M_BLK == 0 && M_pad_d >= 2 * g.K && g.A_pad % K1_BA == 0, "bad low-rank table geometry");
     hipLaunchKernelGGL(diff_table_kernel, dim3(M_pad_d / 2, (g.A_pad + 255) / 256), dim3(256), 0, c->stream, d_kvec, d_kline, d_mean_all,
-                       d_idx, (_Float16*)d_diff, g.K, g.n_g, g.A_pad, dscale);
+                       d_idx, g.weights, 1.f / g.wscale, (_Float16*)d_diff, g.K, g.n_g, g.A_pad, dscale);
     PSA_HIP_CHECK(hipGetLastError());
     PSA_HIP_CHECK(hipMemsetAsync((char*)d_diff + (size_t)M_pad_d * g.A_pad * 2, 0, pd16_table_bytes(M_pad_d, g.A_pad) - (size_t)M_pad_d * g.A_pad * 2,
                                  c->stream));
     hipLaunchKernelGGL(node_table_kernel, dim3(LOWRANK_NODES, (g.A_pad + 255) / 256), dim3(256), 0, c->stream, d_geo, d_kappa, d_mean_all,
-                       d_idx, (_Float16*)d_nodes, g.n_g, g.A_pad);
+                       d_idx, g.weights, 1.f / g.wscale, (_Float16*)d_nodes, g.n_g, g.A_pad);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;
 }

@@ -345,7 +345,7 @@ int launch_k1_planes_wide(psa_ctx* c, const void* d_planes, const void* d_phase,
     const int64_t n_tblk = (g.T + W_T_BLK - 1) / W_T_BLK;
     const int64_t grid = ((n_tblk + 7) / 8) * 8 * n_mblk;
     PSA_REQUIRE(grid < (1ll << 31) && n_tblk < (1ll << 29) && n_fg < (1ll << 31), "projection grid too large");
-    const float qscale = 1.f / (g.vscale * F16x2::P_SCALE);           // powers of two: exact
+    const float qscale = 1.f / (g.vscale * F16x2::P_SCALE) * g.wscale;   // powers of two: exact (wscale: psa_ctx.h)
     if (!c->d_zeros.ptr) {
         PSA_TRY(c->d_zeros.reserve(1024));
         PSA_HIP_CHECK(hipMemsetAsync(c->d_zeros.ptr, 0, 1024, c->stream));

@@ -458,7 +458,8 @@ k1_split_kernel(const float* __restrict__ V, const __bf16* __restrict__ Pb, cons
 
 // ---------------------------------------------------------------------------------------------
 // Phase table in split form: three bf16 planes in the tile image above.
-// Same float32 argument / sincos as phase_table_kernel (kernels_misc.hip); only the storage differs.
+// Same float32 argument / sincos and per-atom weight as phase_table_kernel (kernels_misc.hip); only the storage
+// differs (bf16 has the float32 exponent range: the weight needs no scaling).
 // ---------------------------------------------------------------------------------------------
 __host__ __device__ inline size_t pb_tile_index(int piece, int m, int a, int m_blk, int n_stage) {
     const int    row = m % m_blk, al = a % K1_BA;
@@ -469,8 +470,8 @@ __host__ __device__ inline size_t pb_tile_index(int piece, int m, int a, int m_b
 
 __global__ void __launch_bounds__(256)
 phase_table_split_kernel(const float* __restrict__ kvec, const float* __restrict__ mean_all,
-                         const int* __restrict__ idx, __bf16* __restrict__ Pb, int K, int n_g,
-                         int A_pad, int M_pad, int m_blk) {
+                         const int* __restrict__ idx, const float* __restrict__ w, __bf16* __restrict__ Pb, int K,
+                         int n_g, int A_pad, int M_pad, int m_blk) {
     const int a = blockIdx.y * 256 + threadIdx.x;
     const int k = blockIdx.x;
     if (a >= A_pad || 2 * k >= M_pad) return;
@@ -482,6 +483,10 @@ phase_table_split_kernel(const float* __restrict__ kvec, const float* __restrict
         const float kx = kvec[3 * k + 0], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
         const float arg = __fmaf_rn(kz, rz, __fmaf_rn(ky, ry, __fmul_rn(kx, rx)));
         sincosf(arg, &cs[1], &cs[0]);
+        if (w) {
+            cs[0] *= w[src];
+            cs[1] *= w[src];
+        }
     }
     const int n_stage = A_pad / K1_BA;
 #pragma unroll
@@ -503,7 +508,7 @@ size_t pb_table_bytes(int M_pad, int A_pad) { return (size_t)M_pad * A_pad * 6; 
 int launch_phase_table_split(psa_ctx* c, const float* d_kvec, const float* d_mean_all, const int* d_idx,
                              void* d_phase, const ProjGeom& g) {
     dim3 grid(g.M_pad / 2, (g.A_pad + 255) / 256);
-    hipLaunchKernelGGL(phase_table_split_kernel, grid, dim3(256), 0, c->stream, d_kvec, d_mean_all, d_idx,
+    hipLaunchKernelGGL(phase_table_split_kernel, grid, dim3(256), 0, c->stream, d_kvec, d_mean_all, d_idx, g.weights,
                        (__bf16*)d_phase, g.K, g.n_g, g.A_pad, g.M_pad, g.m_blk);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;

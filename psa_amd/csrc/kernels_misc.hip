@@ -17,10 +17,12 @@ namespace psa {
 // Layout written: the LDS tile images of the projection kernel (p_tile_index in psa_ctx.h):
 // row m = 2k holds cos, m = 2k+1 holds sin; everything outside (K, n_g) is zero so the
 // tile kernel needs no bounds checks on P' (the 4 pad floats per row are never read).
+// w (may be null): per-atom weights (psa_set_atom_weights), P[k,a] = w[idx[a]] exp(i k.r_a) -- the
+// projection is linear per atom, so the weight rides on the phase and the data stay as they are.
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 phase_table_kernel(const float* __restrict__ kvec, const float* __restrict__ mean_all,
-                   const int* __restrict__ idx, float* __restrict__ P,
+                   const int* __restrict__ idx, const float* __restrict__ w, float* __restrict__ P,
                    int K, int n_g, int A_pad, int M_pad, int m_blk) {
     const int a = blockIdx.y * 256 + threadIdx.x;      // grid.x runs over k (can be > 65535)
     const int k = blockIdx.x;
@@ -34,6 +36,10 @@ phase_table_kernel(const float* __restrict__ kvec, const float* __restrict__ mea
         const float kx = kvec[3 * k + 0], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
         const float arg = __fmaf_rn(kz, rz, __fmaf_rn(ky, ry, __fmul_rn(kx, rx)));
         sincosf(arg, &s, &c);
+        if (w) {
+            c *= w[src];
+            s *= w[src];
+        }
     }
     const int n_stage = A_pad / K1_BA;
     P[p_tile_index(2 * k, a, m_blk, n_stage)]     = c;
@@ -43,7 +49,7 @@ phase_table_kernel(const float* __restrict__ kvec, const float* __restrict__ mea
 int launch_phase_table(psa_ctx* c, const float* d_kvec, const float* d_mean_all, const int* d_idx,
                        float* d_phase, const ProjGeom& g) {
     dim3 grid(g.M_pad / 2, (g.A_pad + 255) / 256);
-    hipLaunchKernelGGL(phase_table_kernel, grid, dim3(256), 0, c->stream, d_kvec, d_mean_all, d_idx,
+    hipLaunchKernelGGL(phase_table_kernel, grid, dim3(256), 0, c->stream, d_kvec, d_mean_all, d_idx, g.weights,
                        d_phase, g.K, g.n_g, g.A_pad, g.M_pad, g.m_blk);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;

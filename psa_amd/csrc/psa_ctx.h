@@ -136,6 +136,11 @@ struct ProjGeom {
     bool    lowrank = false;  // split == 4 through the low-rank route for k-paths (api_lowrank.hip, k1_planes_diff.hip)
     int     M_pad_d = 0;      // lowrank: rows of the D image (2K rounded up to 512)
     float   dscale = 0.f;     // lowrank: power of two the D image carries
+    // per-atom weights (psa_set_atom_weights), folded into the phase table: (N_tot) float32 on the device, indexed like
+    // the mean positions; nullptr = none.  The float16 tables hold w 2^-e and their launches multiply qscale by
+    // wscale = 2^e (the float32 and bf16 tables hold w itself)
+    const float* weights = nullptr;
+    float        wscale = 1.f;
 };
 
 // A group's data as cached split planes (k1_f16.h plane_index): built from one generation of one
@@ -241,6 +246,12 @@ struct psa_ctx {
     int64_t      lowrank_launches = 0;          // projection launches that took the route (psa_k1_lowrank_launches)
     // its D image, node projections, C, fp64 inputs (the node table goes into d_phase); released when the route is switched off
     psa::DevBuf  d_lr_diff, d_lr_qn, d_lr_C, d_lr_f64;
+
+    // per-atom weights of every projection (psa_set_atom_weights): d_weights holds weights_N values, none when 0;
+    // weights_scale = 2^e, the smallest power of two >= their largest magnitude
+    psa::DevBuf  d_weights;
+    int64_t      weights_N = 0;
+    float        weights_scale = 1.f;
 
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
