@@ -235,6 +235,7 @@ int psa_create(int device, psa_ctx** out) {
     // A/B switches of the low-rank route, read once here (psa_set_option overrides them)
     if (const char* v = std::getenv("PSA_K1_LOWRANK")) c->opt_k1_lowrank = std::atoi(v) != 0;
     if (const char* v = std::getenv("PSA_K1_LOWRANK_MIN_K")) c->opt_k1_lowrank_min_k = std::max(1, std::atoi(v));
+    if (const char* v = std::getenv("PSA_K1_COMBINE")) c->k1_combine_arm = std::atoi(v) != 0;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;

@@ -340,7 +340,10 @@ static int launch_projection_once(psa_ctx* c, int slot, const int* d_idx, ProjGe
             ProjGeom gd = g;
             gd.M_pad = g.M_pad_d;
             PSA_TRY(launch_k1_planes_diff(c, pl, c->d_lr_diff.ptr, d_q, gd, ps->n_fg - fg0, g.dscale));
-            PSA_TRY(launch_lowrank_combine(c, c->d_lr_qn.as<float2>(), c->d_lr_C.as<float2>(), d_q, g, t_count));
+            if (c->k1_combine_arm == 0)
+                PSA_TRY(launch_lowrank_combine(c, c->d_lr_qn.as<float2>(), c->d_lr_C.as<float2>(), d_q, g, t_count));
+            else
+                PSA_TRY(launch_lowrank_combine_v(c, c->d_lr_qn.as<float2>(), c->d_lr_C.as<float2>(), d_q, g, t_count));
             ++c->lowrank_launches;
             return PSA_OK;
         }

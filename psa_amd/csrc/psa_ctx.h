@@ -244,6 +244,7 @@ struct psa_ctx {
     int64_t      opt_k1_lowrank_min_k = 256;    // PSA_OPT_K1_LOWRANK_MIN_K: shortest whole k-list it serves
     int64_t      opt_k1_lowrank_min_local = 128; // PSA_OPT_K1_LOWRANK_MIN_LOCAL: shortest part of it one launch serves
     int64_t      lowrank_launches = 0;          // projection launches that took the route (psa_k1_lowrank_launches)
+    int          k1_combine_arm = 1;            // PSA_K1_COMBINE (environment, psa_create): 1 lowrank_combine.hip, 0 the scalar combine
     // its D image, node projections, C, fp64 inputs (the node table goes into d_phase); released when the route is switched off
     psa::DevBuf  d_lr_diff, d_lr_qn, d_lr_C, d_lr_f64;
 
@@ -326,6 +327,9 @@ int    launch_lowrank_tables(psa_ctx* c, const float* d_kvec, const double* d_kl
 int    launch_k1_planes_diff(psa_ctx* c, const void* d_planes, const void* d_diff, float2* d_q, const ProjGeom& g, int64_t n_fg,
                              float dscale);
 int    launch_lowrank_combine(psa_ctx* c, const float2* d_qn, const float2* d_C, float2* d_q, const ProjGeom& g, int64_t qn_stride);
+
+// --- lowrank_combine.hip (the packed combine; the arm: psa_ctx::k1_combine_arm)
+int    launch_lowrank_combine_v(psa_ctx* c, const float2* d_qn, const float2* d_C, float2* d_q, const ProjGeom& g, int64_t qn_stride);
 
 // --- k2_epilogue.hip
 int launch_dft_bin(psa_ctx* c, const float2* d_q, int64_t T, int64_t bin, float2* d_out3);
