@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from lowrank_cases import D_LIMIT, DIRECTIONS, LIMITS, geometry, mass_weights
 
 SRC = ROOT / "psa_amd" / "csrc"
 
@@ -155,3 +156,51 @@ def test_diff_kernel_uses_no_scratch(tmp_path):
     assert "scratch_" not in asm
     # two instantiations x 40 unrolled stages x 16 row tiles x 3 components
     assert asm.count("v_mfma_f32_16x16x32_f16") == 2 * 40 * 48
+
+
+# ---- the geometries of the GPU envelope (tests/test_gpu_lowrank_envelope.py): the premises it rests on ------------
+@pytest.mark.parametrize("name", DIRECTIONS + LIMITS + ["plain_100"])
+def test_envelope_geometries(name):
+    """Each geometry gets its node interval, and the plan's interpolation and bound on D hold."""
+    from psa_amd import _hip
+    k, r, interval = geometry(name)
+    p = _hip.lowrank_plan(k, r)
+    assert p is not None and p["interval"] == interval, name
+    _check_plan(p, k, r)
+    if name in LIMITS:
+        assert D_LIMIT[0] <= p["d_bound"] <= D_LIMIT[1], p["d_bound"]     # D at its limit: really there
+
+
+def test_envelope_weighted_limit_keeps_its_plan():
+    """Per-atom weights do not enter the plan: the weighted case runs on the shifted geometry's plan and bound."""
+    from psa_amd import _hip
+    k, r, _ = geometry("limit_shift")
+    w = mass_weights(len(r), 4)
+    assert 1.0 <= w.min() and w.max() <= 240.0 and w.max() / w.min() > 200
+    p = _hip.lowrank_plan(k, r)
+    assert D_LIMIT[0] <= p["d_bound"] <= D_LIMIT[1]
+
+
+@pytest.mark.parametrize("group", ["one_atom", "slab", "whole"])
+def test_envelope_groups_have_finite_normalised_rows(group):
+    """The incoherent case's groups: one atom (h_x clamped to 1e-12, an interval 6e13 wide), a 2 A slab across u and
+    the whole box get different plans, each with finite rows of C whose Lagrange weights sum to one."""
+    from psa_amd import _hip
+    k, r, _ = geometry("plain_100")
+    x_u = r[:, 0]
+    idx = {"one_atom": np.array([int(np.argmin(x_u))], np.int32),
+           "slab": np.flatnonzero((x_u > 5.0) & (x_u < 7.0)).astype(np.int32),
+           "whole": None}[group]
+    p = _hip.lowrank_plan(k, r, idx)
+    assert p is not None and p["interval"] == 0
+    whole = _hip.lowrank_plan(k, r)
+    if group != "whole":
+        assert p["x_c"] != whole["x_c"] and p["width"] != whole["width"]
+    if group == "one_atom":
+        assert p["h_x"] == 1e-12 and p["width"] == pytest.approx(6e13)
+    C = p["C"].astype(np.complex128)
+    assert np.all(np.isfinite(C))
+    # C[j, l] = exp(i kappa_j x_c) L_l(kappa_j): the row sums are unit phases
+    kap = k.astype(np.float64) @ p["u"]
+    np.testing.assert_allclose(C.sum(axis=1), np.exp(1j * kap * p["x_c"]), rtol=0, atol=1e-5)
+    _check_plan(p, k, r if idx is None else r[idx])
