@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PSA_HIP_ABI_VERSION 4
+#define PSA_HIP_ABI_VERSION 5
 
 /* error codes */
 #define PSA_OK          0
@@ -192,6 +192,27 @@ int psa_host_mean_frames(const float* x /* (T, cols) */, int64_t T, int64_t cols
  * result is bit for bit what it is without this call. */
 int psa_set_atom_weights(psa_ctx* ctx, const float* w /* N, or NULL to clear */, int64_t N);
 
+/* Segment-averaged (Welch) intensity spectra.  For segment length L, hop H (1 <= H, 2 <= L <= T) and a real window
+ * w of length L:
+ *     n_seg      = 1 + (T - L) / H              (integer division; frames after the last segment are not used)
+ *     U          = (1/L) sum_tau w[tau]^2        (float64 on the host; must be > 0)
+ *     F_s[k,c,o] = (1/L) sum_tau w[tau] q[k,c,s H + tau] exp(-2 pi i o tau / L)
+ *     I[o,k]     = 1/(n_seg U) sum_s sum_c |F_s[k,c,o]|^2,  summed over the atom groups like PSA_F_INTENSITY
+ * No detrending; frequencies are np.fft.fftfreq(L, dt), two-sided, in FFT order.  With w = 1, L = T (one segment)
+ * I is the PSA_F_INTENSITY result bit for bit; with w = 1 and H = L, sum_o I is the mean power of the frames used.
+ * From this call on, until it is cleared with L = 0, psa_sed_project, _project_upload and _calculate produce I:
+ * the projection is unchanged; after it the windowed segments are gathered (in blocks of k rows, so that the extra
+ * device memory never exceeds the q buffer), transformed by a batched length-L FFT and reduced into the slab.
+ *   - they require PSA_F_INTENSITY, and L <= T of the slot projected (PSA_EINVAL otherwise);
+ *   - psa_sed_finalize returns (L,K) float32 (out_bytes = 4 L K); psa_slab_read / psa_slab_write rows are (nrows, L)
+ *     float32; folded +-k pairs are mirrored as usual: I(-k)[o] = I(k)[(L - o) mod L];
+ *   - the frame-sharded entry points (psa_sed_fs_*) refuse with PSA_EINVAL;
+ *   - psa_sed_single_bin (iSED) and the psa_debug_* projections ignore the setting;
+ *   - set before an upload, the FFT primer builds the plan of length L instead of T.
+ * window: L finite float32 values, copied during the call.  hop < 1, L < 2, a non-finite window or U = 0 is
+ * PSA_EINVAL (the previous setting is then kept). */
+int psa_set_segments(psa_ctx* ctx, int64_t L, int64_t hop, const float* window /* L, copied; L = 0 clears */);
+
 /* ---- the hot path -------------------------------------------------------
  * psa_sed_project: for each of the G atom groups, for the K_local k-vectors given,
  *     P[k,a]   = exp(i * (k . mean_pos[idx[a]]))            float32 FMA chain + sincos
@@ -282,7 +303,7 @@ int psa_sed_single_bin(psa_ctx* ctx, int slot, const float* mean_pos_all, const 
                        float* out_c64x3 /* 6 floats */);
 
 /* Raw access to rows [row0, row0+nrows) of the k-major slab (complex64 (nrows,3,T) or float32
- * (nrows,T), whichever the last psa_sed_project produced): lets a host transport stand in for
+ * (nrows,T), whichever the last psa_sed_project produced; (nrows,L) float32 under psa_set_segments): lets a host transport stand in for
  * psa_sed_gather when no RCCL communicator can be formed, and serves checkpointing. */
 int psa_slab_read(psa_ctx* ctx, int64_t row0, int64_t nrows, void* host);
 int psa_slab_write(psa_ctx* ctx, int64_t row0, int64_t nrows, const void* host);

@@ -28,7 +28,7 @@ OPT_K1_LOWRANK = 8
 OPT_K1_LOWRANK_MIN_K = 9
 OPT_K1_LOWRANK_MIN_LOCAL = 10
 KMAP_MIRROR = 0x80000000
-ABI_VERSION = 4
+ABI_VERSION = 5
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -60,6 +60,7 @@ SIGNATURES = {
     "psa_mean_positions": (C.c_int, [_ctx, C.c_int, _f32p]),
     "psa_host_mean_frames": (C.c_int, [_f32p, C.c_int64, C.c_int64, _f32p, C.c_int]),
     "psa_set_atom_weights": (C.c_int, [_ctx, _f32p, C.c_int64]),
+    "psa_set_segments": (C.c_int, [_ctx, C.c_int64, C.c_int64, _f32p]),
     "psa_sed_project": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, C.c_int64, C.c_int64,
                                   _i32p, _i64p, C.c_int32, C.c_int32]),
     "psa_sed_project_upload": (C.c_int, [_ctx, C.c_int, _f32p, C.c_int64, C.c_int64, _f32p, _f32p, C.c_int64,
@@ -328,6 +329,7 @@ class Engine:
         self.lock = threading.RLock()
         self.rank, self.nranks = 0, 1
         self.result_serial = 0       # bumped by every call that replaces the result resident on the device
+        self.segment_length = 0      # L of the Welch segments set on the context (set_segments); 0 = none
 
     # -- lifecycle -------------------------------------------------------------------
     def close(self):
@@ -492,6 +494,17 @@ class Engine:
             raise ValueError("atom weights must be finite")
         _check(self._lib.psa_set_atom_weights(self._h, _f32(w), w.shape[0]), "psa_set_atom_weights")
 
+    def set_segments(self, segments):
+        """Welch segments of every later intensity projection on this context (psa_set_segments): a
+        `psa_amd.Segments`, or None to clear them.  While they are set, results are (L, K) float32."""
+        if segments is None:
+            _check(self._lib.psa_set_segments(self._h, 0, 0, None), "psa_set_segments")
+            self.segment_length = 0
+            return
+        w = np.ascontiguousarray(segments.window_array(), np.float32)
+        _check(self._lib.psa_set_segments(self._h, segments.length, segments.hop, _f32(w)), "psa_set_segments")
+        self.segment_length = segments.length
+
     def project(self, slot, mean_pos_all, k_vectors, groups=None, flags=0,
                 K_total=None, k_offset=0):
         mean = _as_f32(mean_pos_all, (3,))
@@ -552,6 +565,7 @@ class Engine:
         with_intensity (complex results): returns (sed, sum_c |sed|^2), the second array computed on the
         device in the pass that writes the first."""
         T, _ = self.shape(slot)
+        T = self.segment_length or T                 # frequency bins of the result: L under set_segments
         mean = _as_f32(mean_pos_all, (3,))
         kv = _as_f32(k_vectors, (3,))
         idx, off, G = pack_groups(groups)

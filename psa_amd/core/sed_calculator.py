@@ -31,6 +31,7 @@ import numpy as np
 
 from .. import _hip
 from ..io.writer import out_to_qdump
+from ..segments import Segments
 from ..utils.helpers import parse_direction
 from ..weights import check_atom_weights
 from .sed import SED
@@ -155,11 +156,14 @@ class SEDCalculator:
         return [np.asarray(g) for g in groups]
 
     def _run_device(self, k_vectors: np.ndarray, groups, intensity: bool, mean_pos_all,
-                    fetch: bool = True, atom_weights: Optional[np.ndarray] = None):
+                    fetch: bool = True, atom_weights: Optional[np.ndarray] = None,
+                    segments: Optional[Segments] = None):
         """(result, sum_c |result|^2 or None): the second array accompanies a complex result -- it is
         what `SED.intensity` returns (core/sed.py:22-24), produced on the device in the pass that
         writes the result.  `atom_weights` (validated (N,) float32, or None) are set on the engine for
-        this calculation only; a sharded run needs nothing more, as every rank makes this same call."""
+        this calculation only; a sharded run needs nothing more, as every rank makes this same call.
+        `segments` (validated against T, intensity only; not on sharded runs) likewise: the result is then
+        the (L, K) float32 segment-averaged intensity."""
         slot, data, flags = self._data_slot()
         if intensity:
             flags |= _hip.F_INTENSITY
@@ -167,10 +171,12 @@ class SEDCalculator:
         eng = self.engine
         with eng.lock:                       # project + finalize must not interleave across threads
             K = len(k_vectors)
-            T = self.traj.n_frames
+            T = self.traj.n_frames if segments is None else segments.length
             if atom_weights is not None:     # (only then: an engine without weights never hears of them)
                 eng.set_atom_weights(atom_weights)
             try:
+                if segments is not None:     # (inside the try: cleared whatever happens)
+                    eng.set_segments(segments)
                 if self._shard is not None and self._shard.nranks > 1:
                     out = self._shard.run(slot, data, mean_pos_all, k_vectors, groups, flags, T, fetch, with_intensity=want)
                 elif not eng.is_resident(slot, data):
@@ -185,6 +191,8 @@ class SEDCalculator:
             finally:
                 if atom_weights is not None:  # no later calculation (iSED included) sees them
                     eng.set_atom_weights(None)
+                if segments is not None:
+                    eng.set_segments(None)
         if want:
             return out if out is not None else (None, None)
         return out, None
@@ -316,7 +324,8 @@ class SEDCalculator:
                   basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None,
                   summation_mode: str = 'coherent',
                   k_grid_shape: Optional[Tuple[int, int]] = None,
-                  k_chunk_size: int = 500, *, atom_weights: Optional[np.ndarray] = None) -> SED:
+                  k_chunk_size: int = 500, *, atom_weights: Optional[np.ndarray] = None,
+                  segments: Optional[Segments] = None) -> SED:
         """SED of the trajectory at the given k-vectors (reference :182-336).
 
         coherent (or a single group): `sed` is (T,K,3) complex64; incoherent with several
@@ -330,21 +339,43 @@ class SEDCalculator:
         still from the unweighted mean positions; the rest is unchanged.  With w_a = sqrt(m_a)
         (`psa_amd.mass_weights`) and one group per basis type, the incoherent sum is the mass-weighted
         SED sum_b m_b |...|^2.  None: the unweighted result, bit for bit.
+
+        `segments` (keyword only; not in the reference): a `psa_amd.Segments` -- the segment-averaged (Welch)
+        intensity instead (psa_amd/segments.py): `sed` is (L,K) float32, `freqs` np.fft.fftfreq(L, dt_ps),
+        `is_complex` False, in either mode (coherent: the groups' union as one group; incoherent: summed over the
+        groups).  A sharded calculator refuses it (NotImplementedError).  None: the full-length result.
         """
         if summation_mode not in _MODES:
             raise ValueError(f"summation_mode must be 'coherent' or 'incoherent', got {summation_mode}")
         weights = None if atom_weights is None else check_atom_weights(atom_weights, self.traj.n_atoms)
+        if segments is not None:
+            if not isinstance(segments, Segments):
+                raise TypeError(f"segments must be a psa_amd.Segments, got {type(segments).__name__}")
+            if self._shard is not None and self._shard.nranks > 1:
+                raise NotImplementedError("segment-averaged spectra are not available on a sharded calculator")
         n_t, n_atoms = self.traj.n_frames, self.traj.n_atoms
         if n_t == 0 or n_atoms == 0:
             logger.warning("Cannot calculate SED: 0 frames or 0 atoms.")
             return SED(np.array([], dtype=np.complex64).reshape(0, 0, 3), np.array([], dtype=np.float32),
                        k_points_mags, k_vectors_3d, k_grid_shape=k_grid_shape, is_complex=True, phase=None)
 
+        if segments is not None:
+            segments.count(n_t)                          # ValueError if L > T
         mean_pos_all = self._mean_positions()
         freqs = np.fft.fftfreq(n_t, d=self.dt_ps)
         groups = self._resolve_groups(basis_atom_indices, basis_atom_types, summation_mode)
         is_complex = summation_mode == "coherent" or len(groups) <= 1
         n_k = len(k_vectors_3d)
+
+        if segments is not None:
+            # the (one) coherent group is projected like an incoherent one of a single group: an intensity
+            if is_complex and len(groups) > 1:
+                groups = [np.unique(np.concatenate(groups)).astype(int)]
+            data = np.zeros((segments.length, 0), np.float32) if n_k == 0 else self._run_device(
+                np.asarray(k_vectors_3d), self._device_groups(groups), True, mean_pos_all, atom_weights=weights,
+                segments=segments)[0]
+            return SED(data, np.fft.fftfreq(segments.length, d=self.dt_ps), k_points_mags, k_vectors_3d,
+                       k_grid_shape=k_grid_shape, is_complex=False, phase=None)
 
         if n_k == 0:
             logger.warning("k_vectors_3d is empty. Returning SED object with empty SED data.")
@@ -421,9 +452,12 @@ class SEDCalculator:
                             basis_atom_types=None, summation_mode: str = 'coherent',
                             basis_atom_indices=None, lat_param: Optional[float] = None,
                             chiral: bool = False, chiral_axis: str = 'z',
-                            k_chunk_size: int = 500, *, atom_weights: Optional[np.ndarray] = None) -> SED:
-        """k-path dispersion in one call (README.md:100-106; psa_gui.py:947-999).  `atom_weights`: as for
-        `calculate`."""
+                            k_chunk_size: int = 500, *, atom_weights: Optional[np.ndarray] = None,
+                            segments: Optional[Segments] = None) -> SED:
+        """k-path dispersion in one call (README.md:100-106; psa_gui.py:947-999).  `atom_weights`, `segments`:
+        as for `calculate` (segments and `chiral` exclude each other: the phase needs complex amplitudes)."""
+        if chiral and segments is not None:
+            raise ValueError("chiral=True needs complex amplitudes; segment-averaged spectra are intensities")
         if chiral and summation_mode != 'coherent':
             logger.info("Chirality calculation selected, forcing coherent summation mode.")
             summation_mode = 'coherent'
@@ -433,7 +467,7 @@ class SEDCalculator:
         with self.engine.lock:
             sed = self.calculate(k_mags, k_vecs, basis_atom_indices=basis_atom_indices,
                                  basis_atom_types=basis_atom_types, summation_mode=summation_mode,
-                                 k_chunk_size=k_chunk_size, atom_weights=atom_weights)
+                                 k_chunk_size=k_chunk_size, atom_weights=atom_weights, segments=segments)
             return self._finish(sed, chiral, chiral_axis)
 
     def calculate_chiral_sed(self, direction, bz_coverage: float = 1.0, n_k: int = 100,
@@ -447,9 +481,13 @@ class SEDCalculator:
                             n_kx: int = 20, n_ky: int = 20, k_fixed: float = 0.0,
                             basis_atom_types=None, summation_mode: str = 'coherent',
                             basis_atom_indices=None, chiral: bool = False, chiral_axis: str = 'z',
-                            k_chunk_size: int = 500, *, atom_weights: Optional[np.ndarray] = None) -> SED:
+                            k_chunk_size: int = 500, *, atom_weights: Optional[np.ndarray] = None,
+                            segments: Optional[Segments] = None) -> SED:
         """2-D k-grid SED in one call (README.md:135-140; psa_gui.py:2135-2191).
-        `k_ranges` = (first_min, first_max, second_min, second_max).  `atom_weights`: as for `calculate`."""
+        `k_ranges` = (first_min, first_max, second_min, second_max).  `atom_weights`, `segments`: as for
+        `calculate` (segments and `chiral` exclude each other)."""
+        if chiral and segments is not None:
+            raise ValueError("chiral=True needs complex amplitudes; segment-averaged spectra are intensities")
         if chiral and summation_mode != 'coherent':
             logger.info("Chirality calculation selected for K-Grid, forcing coherent summation mode.")
             summation_mode = 'coherent'
@@ -458,7 +496,8 @@ class SEDCalculator:
         with self.engine.lock:
             sed = self.calculate(k_mags, k_vecs, basis_atom_indices=basis_atom_indices,
                                  basis_atom_types=basis_atom_types, summation_mode=summation_mode,
-                                 k_grid_shape=shape, k_chunk_size=k_chunk_size, atom_weights=atom_weights)
+                                 k_grid_shape=shape, k_chunk_size=k_chunk_size, atom_weights=atom_weights,
+                                 segments=segments)
             return self._finish(sed, chiral, chiral_axis)
 
     # ------------------------------------------------------------------ iSED

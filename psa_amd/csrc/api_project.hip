@@ -429,7 +429,62 @@ int upload_project_inputs(psa_ctx* c, const ProjectArgs& a, int64_t N) {
     return PSA_OK;
 }
 
-// groups [g_first, G) on the resident slot: project, FFT, epilogue
+// ---- Welch segments (psa_set_segments) --------------------------------------------------------------------------------
+// A projection over T frames while segments are set: intensity only, L <= T
+int check_segments(psa_ctx* c, int64_t T, int32_t flags) {
+    if (c->seg_L == 0) return PSA_OK;
+    PSA_REQUIRE(flags & PSA_F_INTENSITY, "segment-averaged spectra are intensities: PSA_F_INTENSITY is required while segments are set");
+    PSA_REQUIRE(c->seg_L <= T, "segment length %lld exceeds the trajectory's %lld frames", (long long)c->seg_L, (long long)T);
+    return PSA_OK;
+}
+
+// frequency bins of a result over T frames: L while segments are set
+static int64_t result_frames(const psa_ctx* c, int64_t T) { return c->seg_L ? c->seg_L : T; }
+
+// Blocks of the segment stage: nk k-vectors x ns segments, so that the segment buffer (3 L complex64 per k-vector and
+// segment) never holds more than the q buffer (K_local,3,T).  L <= T: at least K_local (k, segment) units fit.
+static void segment_blocks(const psa_ctx* c, int64_t T, int64_t K_local, int64_t* nk, int64_t* ns) {
+    const int64_t n_seg = 1 + (T - c->seg_L) / c->seg_hop;
+    const int64_t units = std::max<int64_t>(1, K_local * T / c->seg_L);
+    if (units >= n_seg) {
+        *ns = n_seg;
+        *nk = std::max<int64_t>(1, std::min(K_local, units / n_seg));
+    } else {
+        *ns = units;
+        *nk = 1;
+    }
+}
+
+// In place of the length-T FFT and intensity_accumulate: q (K_local,3,T) of one group -> windowed segments -> batched
+// length-L FFT -> inv_norm sum_s sum_c |F/L|^2 into the slab rows (K_local, L); first: the call's first group
+static int segment_stage(psa_ctx* c, const float2* d_q, int64_t T, int64_t K_local, float* rows, bool first) {
+    const int64_t L = c->seg_L, H = c->seg_hop, n_seg = 1 + (T - L) / H;
+    int64_t       nk = 0, ns = 0;
+    segment_blocks(c, T, K_local, &nk, &ns);
+    const float inv_norm = (float)(1.0 / ((double)n_seg * c->seg_U));   // exactly 1 for w = 1, one segment
+    PSA_TRY(c->d_seg.reserve((size_t)nk * 3 * (size_t)ns * (size_t)L * sizeof(float2)));
+    float2* d_seg = c->d_seg.as<float2>();
+    for (int64_t k0 = 0; k0 < K_local; k0 += nk) {
+        const int64_t bk = std::min(nk, K_local - k0);
+        for (int64_t s0 = 0; s0 < n_seg; s0 += ns) {
+            const int64_t bs = std::min(ns, n_seg - s0);
+            {
+                StageTimer st(c, PSA_T_EPILOGUE);
+                PSA_TRY(launch_segment_window(c, d_q + (size_t)k0 * 3 * (size_t)T, c->d_seg_window.as<float>(), d_seg, T, L, H, s0,
+                                              bs, bk));
+            }
+            {
+                StageTimer st(c, PSA_T_FFT);
+                PSA_TRY(run_fft(c, d_seg, L, 3 * bk * bs));
+            }
+            StageTimer st(c, PSA_T_EPILOGUE);
+            PSA_TRY(launch_segment_power(c, d_seg, rows + (size_t)k0 * (size_t)L, L, bs, bk, inv_norm, first && s0 == 0));
+        }
+    }
+    return PSA_OK;
+}
+
+// groups [g_first, G) on the resident slot: project, FFT, epilogue (or the segment stage)
 int project_groups(psa_ctx* c, const ProjectArgs& a, int slot_in, bool disp_in, int g_first, bool* first, char* rows,
                    float2* d_q) {
     const int64_t T = c->slot[slot_in].T, N = c->slot[slot_in].N;
@@ -459,13 +514,17 @@ int project_groups(psa_ctx* c, const ProjectArgs& a, int slot_in, bool disp_in, 
             PSA_TRY(prepare_phase(c, d_idx, g, disp, k0));
             PSA_TRY(launch_projection(c, slot, d_idx, g, disp, ps, d_q + (size_t)k0 * 3 * (size_t)T, T, 0, T));
         }
-        {
-            StageTimer st(c, PSA_T_FFT);
-            PSA_TRY(run_fft(c, d_q, T, 3 * a.K_local));
-        }
-        if (intensity) {
-            StageTimer st(c, PSA_T_EPILOGUE);
-            PSA_TRY(launch_intensity_accumulate(c, d_q, (float*)rows, T, a.K_local, *first));
+        if (c->seg_L) {
+            PSA_TRY(segment_stage(c, d_q, T, a.K_local, (float*)rows, *first));
+        } else {
+            {
+                StageTimer st(c, PSA_T_FFT);
+                PSA_TRY(run_fft(c, d_q, T, 3 * a.K_local));
+            }
+            if (intensity) {
+                StageTimer st(c, PSA_T_EPILOGUE);
+                PSA_TRY(launch_intensity_accumulate(c, d_q, (float*)rows, T, a.K_local, *first));
+            }
         }
         *first = false;
     }
@@ -507,6 +566,33 @@ int psa_set_atom_weights(psa_ctx* c, const float* w, int64_t N) {
     return PSA_OK;
 }
 
+int psa_set_segments(psa_ctx* c, int64_t L, int64_t hop, const float* window) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    if (L == 0) {
+        c->seg_L = c->seg_hop = 0;
+        c->seg_U = 0.0;
+        return PSA_OK;
+    }
+    PSA_REQUIRE(L >= 2 && L < (1ll << 31), "bad segment length %lld", (long long)L);
+    PSA_REQUIRE(hop >= 1, "segment hop %lld < 1", (long long)hop);
+    PSA_REQUIRE(window != nullptr, "null window");
+    double u = 0.0;
+    for (int64_t t = 0; t < L; ++t) {
+        PSA_REQUIRE(std::isfinite(window[t]), "window value %lld is not finite", (long long)t);
+        u += (double)window[t] * (double)window[t];
+    }
+    u /= (double)L;
+    PSA_REQUIRE(u > 0.0, "the window is zero everywhere (U = 0)");
+    c->seg_L = 0;                                      // (no segments if the copy fails)
+    PSA_TRY(upload(c, c->d_seg_window, window, (size_t)L * sizeof(float)));
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));   // the caller's array is only read during the call
+    c->seg_L = L;
+    c->seg_hop = hop;
+    c->seg_U = u;
+    return PSA_OK;
+}
+
 int psa_sed_project(psa_ctx* c, int slot, const float* mean_pos_all, const float* k_vectors,
                     int64_t K_local, int64_t K_total, int64_t k_offset, const int32_t* group_idx,
                     const int64_t* group_off, int32_t G, int32_t flags) {
@@ -519,6 +605,7 @@ int psa_sed_project(psa_ctx* c, int slot, const float* mean_pos_all, const float
     bool          disp = (flags & PSA_F_DISPLACEMENTS) != 0;
     PSA_TRY(check_project_args(c, a, N));
     PSA_TRY(check_weights(c, N));
+    PSA_TRY(check_segments(c, T, flags));
     // the whole list on this device: k-vectors whose negation (or twin) is in the list are not projected
     std::vector<float>   uniq_k;
     std::vector<int32_t> kmap;
@@ -529,7 +616,7 @@ int psa_sed_project(psa_ctx* c, int slot, const float* mean_pos_all, const float
     }
     char*  rows = nullptr;
     size_t row_bytes = 0;
-    PSA_TRY(begin_result(c, T, K_total, k_offset, intensity, &rows, &row_bytes));
+    PSA_TRY(begin_result(c, result_frames(c, T), K_total, k_offset, intensity, &rows, &row_bytes));
     if (folded) PSA_TRY(install_kmap(c, kmap));
     if (K_local == 0) return PSA_OK;
     PSA_TRY(upload_project_inputs(c, a, N));
@@ -568,13 +655,14 @@ int psa_sed_project_upload(psa_ctx* c, int slot, const float* host, int64_t T, i
     PSA_REQUIRE(T > 0 && N > 0, "empty trajectory (T=%lld, N=%lld)", (long long)T, (long long)N);
     PSA_TRY(check_project_args(c, a, N));
     PSA_TRY(check_weights(c, N));
+    PSA_TRY(check_segments(c, T, flags));
     PSA_TRY(data_alloc_locked(c, slot, T, N));
     c->slot[slot].valid = false;
     const bool intensity = (flags & PSA_F_INTENSITY) != 0;
     const bool disp = (flags & PSA_F_DISPLACEMENTS) != 0;
     char*      rows = nullptr;
     size_t     row_bytes = 0;
-    PSA_TRY(begin_result(c, T, K, 0, intensity, &rows, &row_bytes));
+    PSA_TRY(begin_result(c, result_frames(c, T), K, 0, intensity, &rows, &row_bytes));
     if (folded) PSA_TRY(install_kmap(c, kmap));
     PSA_TRY(upload_project_inputs(c, a, N));
     float2* d_q = intensity ? nullptr : (float2*)rows;
@@ -582,13 +670,21 @@ int psa_sed_project_upload(psa_ctx* c, int slot, const float* host, int64_t T, i
         PSA_TRY(c->d_qwork.reserve((size_t)K * 3 * T * sizeof(float2)));
         d_q = c->d_qwork.as<float2>();
     }
-    // the rocFFT plan (run-time compiled on first use of a length) is built beside the upload
+    // the rocFFT plan (run-time compiled on first use of a length) is built beside the upload -- with segments set,
+    // the plan of the segment stage's first block
+    int64_t fft_len = T, fft_batch = 3 * K;
+    if (c->seg_L) {
+        int64_t nk = 0, ns = 0;
+        segment_blocks(c, T, K, &nk, &ns);
+        fft_len = c->seg_L;
+        fft_batch = 3 * nk * ns;
+    }
     int         plan_rc = PSA_OK;
     std::string plan_err;
     std::thread planner([&] {
         (void)hipSetDevice(c->device);
         FftPlan* p = nullptr;
-        plan_rc = get_plan(c, T, 3 * K, &p);
+        plan_rc = get_plan(c, fft_len, fft_batch, &p);
         if (plan_rc != PSA_OK) plan_err = g_error;
     });
     struct JoinOnExit {                                           // no path leaves with the thread running
@@ -644,13 +740,17 @@ int psa_sed_project_upload(psa_ctx* c, int slot, const float* host, int64_t T, i
                                  c->stream));
     bool first = true;
     if (g0 < G) {
-        {
-            StageTimer st(c, PSA_T_FFT);
-            PSA_TRY(run_fft(c, d_q, T, 3 * K));
-        }
-        if (intensity) {
-            StageTimer st(c, PSA_T_EPILOGUE);
-            PSA_TRY(launch_intensity_accumulate(c, d_q, (float*)rows, T, K, true));
+        if (c->seg_L) {
+            PSA_TRY(segment_stage(c, d_q, T, K, (float*)rows, true));
+        } else {
+            {
+                StageTimer st(c, PSA_T_FFT);
+                PSA_TRY(run_fft(c, d_q, T, 3 * K));
+            }
+            if (intensity) {
+                StageTimer st(c, PSA_T_EPILOGUE);
+                PSA_TRY(launch_intensity_accumulate(c, d_q, (float*)rows, T, K, true));
+            }
         }
         first = false;
         // remaining groups on the now resident array, by the ordinary rule
@@ -811,6 +911,7 @@ static int calculate_pipelined(psa_ctx* c, const ProjectArgs& a_in, void* out_ho
     bool          disp = (a.flags & PSA_F_DISPLACEMENTS) != 0;
     PSA_TRY(check_project_args(c, a, N));
     PSA_TRY(check_weights(c, N));
+    PSA_TRY(check_segments(c, T, a.flags));                       // (a complex result: refused while segments are set)
     std::vector<float>   uniq_k;
     std::vector<int32_t> kmap;
     const bool           folded = fold_k_list(c, a.k_vectors, K_out, &uniq_k, &kmap);

@@ -94,7 +94,14 @@ float2* fs_my_rows(psa_ctx* c) {
     return c->fs_intensity ? c->d_qrows.as<float2>() : c->d_slab.as<float2>() + (size_t)c->fs_rows_k0 * 3 * c->fs_T_total;
 }
 
+// the frame-sharded entry points do not take Welch segments (psa_set_segments)
+int fs_no_segments(psa_ctx* c) {
+    PSA_REQUIRE(c->seg_L == 0, "frame-sharded projections do not take segments: clear them with psa_set_segments(ctx, 0, 0, NULL)");
+    return PSA_OK;
+}
+
 int fs_check(psa_ctx* c) {
+    PSA_TRY(fs_no_segments(c));
     if (c->fs_T_total <= 0) {
         set_error("no frame-sharded projection in flight: call psa_sed_fs_project first");
         return PSA_ESTATE;
@@ -116,6 +123,7 @@ int psa_sed_fs_project(psa_ctx* c, int slot, const float* mean_pos_all, const fl
                        const int32_t* idx, int64_t n_g, int32_t flags, int64_t T_total, int64_t k_offset, int64_t k_count) {
     PSA_TRY(enter(c));
     Guard guard(c);
+    PSA_TRY(fs_no_segments(c));
     PSA_TRY(check_slot(c, slot));
     const int64_t T_local = c->slot[slot].T, N = c->slot[slot].N;
     const bool    intensity = (flags & PSA_F_INTENSITY) != 0;

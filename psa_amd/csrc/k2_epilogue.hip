@@ -5,6 +5,8 @@
 //   scale_transpose_c64   S[k,c,w]/T -> out[w,k,c]      ref: sed_calculator.py:83-84, 311
 //   intensity_accumulate  I[k,w] (+)= sum_c |S[k,c,w]/T|^2          ref: :325
 //   transpose_f32         I[k,w] -> out[w,k]                         ref: :327
+//   segment_window        seg[k,c,s,tau] = w[tau] q[k,c,s H + tau]  Welch segments (no counterpart in the reference)
+//   segment_power         I[k,w] (+)= inv_norm sum_s sum_c |F_s[k,c,w]/L|^2
 //   result_intensity      sum_c |out[w,k,c]|^2                       ref: core/sed.py:22-24
 //   result_chiral_c       folded phase difference of two components  ref: :344-350
 //   dft_bin               one frequency bin of FFT_t(q)/T                 ref: :83-84 as used by :494-499
@@ -124,6 +126,74 @@ int launch_intensity_accumulate(psa_ctx* c, const float2* d_q, float* d_slab_row
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(intensity_accumulate_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream,
                        d_q, d_slab_rows, T, K_local, first_group ? 1 : 0);
+    PSA_HIP_CHECK(hipGetLastError());
+    return PSA_OK;
+}
+
+// Welch segments (psa_set_segments; the definition is in psa_hip.h).  One block of the segment stage covers rows
+// [k0, k0 + nk) of q (K,3,T) -- the caller passes q from row k0 on -- and segments [s0, s0 + ns), into the segment
+// buffer (nk,3,ns,L):  seg[k,c,s,tau] = w[tau] q[k,c,(s0+s) H + tau].  One workgroup row per (k,c,s) row of the buffer:
+// reads and writes are coalesced along tau.  (s0+s) H + tau <= (n_seg - 1) H + L - 1 <= T - 1.
+__global__ void __launch_bounds__(256)
+segment_window_kernel(const float2* __restrict__ q, const float* __restrict__ w, float2* __restrict__ seg, int64_t T,
+                      int64_t L, int64_t H, int64_t s0, int ns, int n_rows) {
+    for (int row = blockIdx.y; row < n_rows; row += gridDim.y) {
+        const int     s = row % ns, kc = row / ns;
+        const float2* src = q + (int64_t)kc * T + (s0 + s) * H;
+        float2*       dst = seg + (int64_t)row * L;
+        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < L; t += (int64_t)gridDim.x * 256) {
+            const float2 v = src[t];
+            const float  wt = w[t];
+            dst[t] = make_float2(wt * v.x, wt * v.y);
+        }
+    }
+}
+
+int launch_segment_window(psa_ctx* c, const float2* d_q, const float* d_w, float2* d_seg, int64_t T, int64_t L, int64_t H,
+                          int64_t s0, int64_t ns, int64_t nk) {
+    const int64_t n_rows = nk * 3 * ns;
+    if (n_rows == 0) return PSA_OK;
+    PSA_REQUIRE(n_rows < (1ll << 31) && (s0 + ns - 1) * H + L <= T, "segment block outside q");
+    const int64_t gx = std::min<int64_t>((L + 255) / 256, 64), gy = std::min<int64_t>(n_rows, 65535);
+    hipLaunchKernelGGL(segment_window_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, c->stream, d_q, d_w, d_seg, T, L,
+                       H, s0, (int)ns, (int)n_rows);
+    PSA_HIP_CHECK(hipGetLastError());
+    return PSA_OK;
+}
+
+// After the length-L FFT of the segment buffer (nk,3,ns,L): acc rows (nk, L) -- the caller passes the slab from row k0
+// on -- get inv_norm sum_s sum_c |F/L|^2, in the arithmetic of intensity_accumulate_kernel (with one segment and
+// inv_norm = 1 the same bits); first: overwrite, else accumulate (further groups, further segment blocks).  Each
+// element of the buffer is read once, 4 nk L bytes are written.
+__global__ void __launch_bounds__(256)
+segment_power_kernel(const float2* __restrict__ seg, float* __restrict__ acc, int64_t L, int ns, int nk, float inv_norm,
+                     int first) {
+    const float n_l = (float)L;
+    for (int k = blockIdx.y; k < nk; k += gridDim.y) {
+        for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < L; w += (int64_t)gridDim.x * 256) {
+            float s = 0.f;
+            for (int sg = 0; sg < ns; ++sg) {
+#pragma unroll
+                for (int cc = 0; cc < 3; ++cc) {
+                    const float2 v = seg[(((int64_t)k * 3 + cc) * ns + sg) * L + w];
+                    const float  re = __fdiv_rn(v.x, n_l), im = __fdiv_rn(v.y, n_l);
+                    s += re * re + im * im;
+                }
+            }
+            const float  p = s * inv_norm;
+            const int64_t i = (int64_t)k * L + w;
+            acc[i] = first ? p : acc[i] + p;
+        }
+    }
+}
+
+int launch_segment_power(psa_ctx* c, const float2* d_seg, float* d_rows, int64_t L, int64_t ns, int64_t nk, float inv_norm,
+                         bool first) {
+    if (nk == 0) return PSA_OK;
+    PSA_REQUIRE(nk < (1ll << 31) && ns < (1ll << 31), "segment block too large");
+    const int64_t gx = std::min<int64_t>((L + 255) / 256, 64), gy = std::min<int64_t>(nk, 65535);
+    hipLaunchKernelGGL(segment_power_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, c->stream, d_seg, d_rows, L,
+                       (int)ns, (int)nk, inv_norm, first ? 1 : 0);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;
 }

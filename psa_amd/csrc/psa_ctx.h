@@ -254,6 +254,12 @@ struct psa_ctx {
     int64_t      weights_N = 0;
     float        weights_scale = 1.f;
 
+    // Welch segments of every intensity projection (psa_set_segments): length seg_L (0 = none), hop seg_hop, the window
+    // (seg_L float32) in d_seg_window, seg_U = (1/L) sum w^2 in float64; d_seg: the segment buffer (at most the q buffer)
+    psa::DevBuf  d_seg_window, d_seg;
+    int64_t      seg_L = 0, seg_hop = 0;
+    double       seg_U = 0.0;
+
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
                                           // plane builds, trajectory uploads (psa_oneoff_stats)
@@ -342,6 +348,12 @@ int launch_scale_transpose_c64(psa_ctx* c, const float2* d_slab, float2* d_out, 
 int launch_intensity_accumulate(psa_ctx* c, const float2* d_q, float* d_slab_rows, int64_t T,
                                 int64_t K_local, bool first_group);
 int launch_transpose_f32(psa_ctx* c, const float* d_slab, float* d_out, int64_t T, int64_t K, const int32_t* d_srcs);
+// Welch segments: rows [0, nk) of q (from the block's first row) x segments [s0, s0 + ns) -> windowed segment buffer
+// (nk,3,ns,L); after its FFT, inv_norm sum_s sum_c |F/L|^2 into slab rows (nk, L) (first: overwrite)
+int launch_segment_window(psa_ctx* c, const float2* d_q, const float* d_w, float2* d_seg, int64_t T, int64_t L, int64_t H,
+                          int64_t s0, int64_t ns, int64_t nk);
+int launch_segment_power(psa_ctx* c, const float2* d_seg, float* d_rows, int64_t L, int64_t ns, int64_t nk, float inv_norm,
+                         bool first);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 
