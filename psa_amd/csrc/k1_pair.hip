@@ -2,7 +2,7 @@
 // k1_mfma.hip, D[m, (c,t)] = sum_a P'[m, a] * d[t, a, c], on the float16 matrix cores with
 // fp32-equivalent accuracy ("2 x f16": k1_f16.h), in a workgroup of eight wavefronts, two per SIMD.
 //
-// Why eight.  Measured on MI355X (tools/k1_experiments.sh, tools/pmc_k1.sh, configuration 3): a
+// Why eight.  Measured on MI355X (profiles/r1g_C3_k1_experiments.txt, tools/pmc_k1.sh, configuration 3): a
 // wavefront streams memory at about 10 bytes per cycle -- every 1-KiB memory instruction (LDS-DMA
 // piece or global_load_dwordx4) holds the wavefront that issues it for 100-190 cycles, and nothing
 // else of that wavefront issues meanwhile.  A 128 x 64 tile of 32 atoms needs 40 KiB: with four
@@ -28,14 +28,6 @@
 //  - The atom axis is padded to 2 stages (64 atoms, zero phase columns); loads past the last stage
 //    are clamped to it.
 #include "k1_f16.h"
-
-// Timing experiments (tools/k1_experiments.sh builds side libraries with -DPSA_K1_EXPERIMENT=bits;
-// results are WRONG by construction, only the kernel time is of interest):
-//   1: no DMA in the main loop   2: no MFMAs (operands kept alive)   4: no split   8: no fold
-//  16: P' pieces re-read stage 0 (L2 hits)   32: V pieces re-read stage 0
-#ifndef PSA_K1_EXPERIMENT
-#define PSA_K1_EXPERIMENT 0
-#endif
 
 namespace psa {
 
@@ -136,15 +128,14 @@ k1_pair_kernel(const float* __restrict__ V, const _Float16* __restrict__ Pb, con
     auto dma_stage = [&](int st, int slot, int atom) {
         const int      sc = st < last ? st : last;
         const unsigned dst = lds0 + slot * C::STAGE_BYTES;
-        const int      scp = (PSA_K1_EXPERIMENT & 16) ? 0 : sc, scv = (PSA_K1_EXPERIMENT & 32) ? 0 : sc;
 #pragma unroll
         for (int i = 0; i < C::P_DMA; ++i)
-            lds_dma16(pp + (size_t)scp * C::P_STAGE_BYTES + 1024 * i, dst + 1024 * (w * C::P_DMA + i));
+            lds_dma16(pp + (size_t)sc * C::P_STAGE_BYTES + 1024 * i, dst + 1024 * (w * C::P_DMA + i));
         const unsigned vdst = dst + C::P_STAGE_BYTES + wf * C::RAW_GROUP_BYTES + wh * C::V_DMA * C::V_PIECE_BYTES;
 #pragma unroll
         for (int j = 0; j < C::V_DMA; ++j) {
             if constexpr (GATHER) lds_dma12(vp[j] + 3 * (int64_t)atom, vdst + j * C::V_PIECE_BYTES);
-            else lds_dma16(vp[j] + (size_t)scv * K1_VROW, vdst + j * C::V_PIECE_BYTES);
+            else lds_dma16(vp[j] + (size_t)sc * K1_VROW, vdst + j * C::V_PIECE_BYTES);
         }
         if constexpr (GATHER) {
             const int* src = idx ? idx + pos_of(st + 2) : nullptr;
@@ -213,11 +204,6 @@ k1_pair_kernel(const float* __restrict__ V, const _Float16* __restrict__ Pb, con
 
     // All products of one row tile; MFMAs that depend on one another are two instructions apart.
     auto mfma_tile = [&](int mt, int par, bool restart) {
-        if constexpr ((PSA_K1_EXPERIMENT & 2) != 0) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) asm volatile("" ::"v"(a[0][mt]), "v"(a[1][mt]), "v"(bs[par][c][0]), "v"(bs[par][c][1]));
-            return;
-        }
         f32x4 ch[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c)
@@ -239,17 +225,15 @@ k1_pair_kernel(const float* __restrict__ V, const _Float16* __restrict__ Pb, con
         const int      slot1 = slot == C::RING - 1 ? 0 : slot + 1;
         // gathered: the index row of stage s+RING came with the batch issued two stages ago,
         // awaited by the counted vmcnt at the end of the last stage
-        if constexpr ((PSA_K1_EXPERIMENT & 1) == 0) dma_stage(s + C::RING, slot, atom_from_ring(s + C::RING));
+        dma_stage(s + C::RING, slot, atom_from_ring(s + C::RING));
         read_raw(slot1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int mt = 0; mt < MT16; ++mt) {
-            if constexpr ((PSA_K1_EXPERIMENT & 4) == 0) {
-                // the three components beside regions 1, 2, 3 (four row tiles) or 0, 1, 1 (two)
-                if (mt == (MT16 >= 4 ? 1 : 0)) split_component<0>(raw, vscale, bs[par ^ 1][0]);
-                if (mt == (MT16 >= 4 ? 2 : 1)) split_component<1>(raw, vscale, bs[par ^ 1][1]);
-                if (mt == (MT16 >= 4 ? 3 : 1)) split_component<2>(raw, vscale, bs[par ^ 1][2]);
-            }
+            // the three components beside regions 1, 2, 3 (four row tiles) or 0, 1, 1 (two)
+            if (mt == (MT16 >= 4 ? 1 : 0)) split_component<0>(raw, vscale, bs[par ^ 1][0]);
+            if (mt == (MT16 >= 4 ? 2 : 1)) split_component<1>(raw, vscale, bs[par ^ 1][1]);
+            if (mt == (MT16 >= 4 ? 3 : 1)) split_component<2>(raw, vscale, bs[par ^ 1][2]);
             mfma_tile(mt, par, restart);
 #pragma unroll
             for (int i = 0; i < 3 * PR::NTERM; ++i) {
@@ -262,10 +246,7 @@ k1_pair_kernel(const float* __restrict__ V, const _Float16* __restrict__ Pb, con
         }
         // own pieces of stage s+2 landed (the batch just issued may stay in flight), own LDS reads
         // returned (the next stage's DMA overwrites the slot they read); then everyone's
-        if constexpr ((PSA_K1_EXPERIMENT & 1) == 0)
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((C::RING - 2) * C::BATCH) : "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((C::RING - 2) * C::BATCH) : "memory");
     };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -283,12 +264,10 @@ k1_pair_kernel(const float* __restrict__ V, const _Float16* __restrict__ Pb, con
             stage(I1{}, std::false_type{}, s + i + 1, slot);
             next_slot();
         }
-        if constexpr ((PSA_K1_EXPERIMENT & 8) == 0) {
 #pragma unroll
-            for (int mt = 0; mt < MT16; ++mt)
+        for (int mt = 0; mt < MT16; ++mt)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) lo[mt][c] += hi[mt][c];
-        }
+            for (int c = 0; c < 3; ++c) lo[mt][c] += hi[mt][c];
         s += len;
     }
 
@@ -304,10 +283,9 @@ k1_pair_kernel(const float* __restrict__ V, const _Float16* __restrict__ Pb, con
                 const int k = (m0 + mt * 16 + 4 * q + 2 * pr) >> 1;
                 if (k < K) {
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const f32x4 sum = (PSA_K1_EXPERIMENT & 8) ? hi[mt][c] : lo[mt][c];
-                        Q[((int64_t)k * 3 + c) * q_stride + t] = make_float2(sum[2 * pr] * qscale, sum[2 * pr + 1] * qscale);
-                    }
+                    for (int c = 0; c < 3; ++c)
+                        Q[((int64_t)k * 3 + c) * q_stride + t] =
+                            make_float2(lo[mt][c][2 * pr] * qscale, lo[mt][c][2 * pr + 1] * qscale);
                 }
             }
         }

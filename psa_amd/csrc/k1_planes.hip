@@ -19,38 +19,23 @@
 //
 // Frames: the planes hold whole frame groups of 16 (zero-padded); T bounds the stores.  q is
 // written with row stride q_stride so that a launch may cover a frame sub-range of a longer slab.
+//
+// Schedule (configuration 3; profiles/r3_k1_experiments.txt, DESIGN.md "K1 from cached split planes"):
+// waves 0-3 issue their LDS-DMA at the top of the stage, their SIMD partners (waves 4-7) behind the
+// middle row tile and at s_setprio 1 -- while one wavefront of a SIMD sits in its memory instructions
+// the other feeds the matrix pipe; no sched_barrier inside the stage (the compiler interleaves the LDS
+// reads with the MFMAs).  The DMA is addressed as SGPR base + per-lane 32-bit offset, the pieces of a
+// group told apart by the instruction offset (it moves the global AND the LDS address:
+// tools/probes/dma_offset.hip) -- one M0 write per group and no 64-bit VALU address arithmetic.
+// Measured and not kept: the main loop unrolled over the slot ring (3 % slower); a 4-slot ring for the
+// one-M-block 128-row launch; other stagger points and priorities; DMA pieces or B-fragment reads spread
+// over the row-tile regions, or a wavefront's pieces issued one by one; V pieces before P'; other MFMA
+// operand orders (1.3 % between the best and the worst: not a lever).  A fragments double-buffered with
+// all 14 LDS reads of the next stage at the top of the stage took 16.4 ms against 14.9 (an in-order
+// wavefront cannot issue its MFMAs behind a read burst that fills the LDS queue); the same with the
+// reads paced one per two MFMAs (sched_group_barrier) 14.9 ms -- no schedule moves the launch any more:
+// it is power-limited.
 #include "k1_f16.h"
-
-// Schedule experiments (tools/k1_experiments.sh builds side libraries with -DPSA_K1P_X=bits):
-//   1: the second row half (waves 4-7, the SIMD partners of 0-3) issues its DMA half a stage later
-//   2: s_setprio 1 for waves 4-7      4: DMA pieces spread over the row-tile regions
-//   8: B-fragment reads spread over the regions   16: no sched_barrier between the regions
-//  32: DMA addressed as SGPR base + per-lane 32-bit offset, the pieces of a group told apart by the
-//      instruction offset (it moves the global AND the LDS address: tools/probes/dma_offset.hip) --
-//      one M0 write per group and no 64-bit VALU address arithmetic
-//  64: main loop unrolled over the slot ring (LDS addresses become instruction offsets)
-// Tried and removed (configuration 3, same box, 14.9 ms shipped): A fragments double-buffered with all
-// 14 LDS reads of the next stage at the top of the stage 16.4 ms (an in-order wavefront cannot issue
-// its MFMAs behind a read burst that fills the LDS queue); the same with the reads paced one per two
-// MFMAs (sched_group_barrier) 14.9 ms -- no schedule moves the launch any more: it is power-limited.
-// 256: no non-temporal policy on the planes of a one-M-block launch    512: running source pointers
-// Timing-only experiments (WRONG results): 128 every V read an L2 hit; 1024 no MFMAs; 2048 the P' tile
-// always stage 0 (L2-hot); 8192 no LDS fragment reads; 16384 no LDS-DMA in the main loop; 32768 no s_barrier
-// Operand-order experiments (results stay right): 65536 / 131072 / 262144, see mfma_tile / mfma_stage_ordered --
-// 1.3 % between the best and the worst order: not a lever (profiles/r3_k1_experiments.txt)
-// 524288: a wavefront's DMA pieces issued one by one, spread over the stage (no gain either)
-#ifndef PSA_K1P_X
-#define PSA_K1P_X 563       // product build: 1 + 2 + 16 + 32 + 512 (64 measured 3 % slower)
-#endif
-#ifndef PSA_K1P_POS
-#define PSA_K1P_POS -1      // row tile after which waves 4-7 issue their DMA (-1: the middle one)
-#endif
-#ifndef PSA_K1P_RING1
-#define PSA_K1P_RING1 3     // ring slots of the 128-row variant when the launch has one M block (4 = all 160 KiB of LDS)
-#endif
-#ifndef PSA_K1P_PRIO
-#define PSA_K1P_PRIO 1      // which row half runs at s_setprio 1 (bit 2 of PSA_K1P_X)
-#endif
 
 namespace psa {
 
@@ -74,7 +59,7 @@ struct K1pCfg {
 };
 
 // NT_V: the launch has ONE M block, so every byte of the planes is read exactly once -> streamed with
-// the non-temporal policy (PSA_K1P_X bit 256 switches it off for comparison)
+// the non-temporal policy
 template <int MT16_, int RING_, bool NT_V>
 __global__ void __launch_bounds__(512, 1)
 k1_planes_kernel(const _Float16* __restrict__ planes, const _Float16* __restrict__ Pb, float2* __restrict__ Q,
@@ -99,78 +84,26 @@ k1_planes_kernel(const _Float16* __restrict__ planes, const _Float16* __restrict
     const int     wh = w >> 2, wf = w & 3;
     const int     r16 = lane & 15, q = lane >> 4;
     const int64_t t0 = (int64_t)tb * C::T_BLK + wf * 16;
-    const int     last = n_stage - 1;
     int           fg = tb * 4 + wf;                                  // frame group (past the end: the last one, never stored)
     if (fg >= n_fg) fg = n_fg - 1;
-    if constexpr ((PSA_K1P_X & 128) != 0) fg &= 63;   // experiment (WRONG results): every V read is an L2 / MALL hit
 
     // ---- DMA sources: this wavefront's blocks of the V planes and of the P' tile ----------------
-    const unsigned char* vp = reinterpret_cast<const unsigned char*>(planes) +
-                              (size_t)fg * n_stage * C::V_GROUP_BYTES + 1024 * (wh * C::V_DMA) + 16 * lane;
-    const int            pw = C::P_PIECES >= 8 ? w * C::P_DMA : (w & 3);
-    const unsigned char* pp = reinterpret_cast<const unsigned char*>(Pb) + (size_t)mb * n_stage * C::P_STAGE_BYTES +
-                              1024 * pw + 16 * lane;
-    // the same as (uniform base, per-lane offset) pairs for the SGPR-base form
-    const unsigned char* vbase = reinterpret_cast<const unsigned char*>(planes) + (size_t)fg * n_stage * C::V_GROUP_BYTES;
-    const unsigned char* pbase = reinterpret_cast<const unsigned char*>(Pb) + (size_t)mb * n_stage * C::P_STAGE_BYTES;
-    const unsigned       v_voff = 1024 * (wh * C::V_DMA) + 16 * lane, p_voff = 1024 * pw + 16 * lane;
-    // piece i of this wavefront's BATCH for stage st (clamped) -> slot: P' pieces first, then V
-    auto dma_piece = [&](int i, int st, int slot) {
-        const int      sc = st < last ? st : last;
-        const unsigned dst = lds0 + slot * C::STAGE_BYTES;
-        if (i < C::P_DMA) {
-            lds_dma16(pp + (size_t)sc * C::P_STAGE_BYTES + 1024 * i, dst + 1024 * (pw + i));
-        } else {
-            const int      j = i - C::P_DMA;
-            const unsigned vdst = dst + C::P_STAGE_BYTES + wf * C::V_GROUP_BYTES + 1024 * (wh * C::V_DMA);
-            lds_dma16(vp + (size_t)sc * C::V_GROUP_BYTES + 1024 * j, vdst + 1024 * j);
-        }
-    };
-    // bit 512: the sources of the next stage to fetch as running uniform pointers (one s_add_u32 /
-    // s_addc_u32 pair each per stage instead of clamp + 64-bit multiply-add); stages past the end are
+    // The next stage to fetch as running uniform pointers (one s_add_u32 / s_addc_u32 pair each per
+    // stage instead of clamp + 64-bit multiply-add) and per-lane offsets; stages past the end are
     // fetched from the bytes that follow (the next frame group / M block, or the RING stages of padding
     // behind the buffers: k1_planes_tail_pad) and never read
-    const unsigned char* p_next = pbase;
-    const unsigned char* v_next = vbase;
-    auto dma_stage = [&](int st, int slot) {
-        if constexpr ((PSA_K1P_X & 512) != 0) {
-            const unsigned dst = lds0 + slot * C::STAGE_BYTES;
-            if constexpr ((PSA_K1P_X & 4096) != 0)          // experiment: the HBM-served pieces first
-                lds_dma16_group<C::V_DMA, NT_V && (PSA_K1P_X & 256) == 0>(
-                    v_next, v_voff, dst + C::P_STAGE_BYTES + wf * C::V_GROUP_BYTES + 1024 * (wh * C::V_DMA));
-            lds_dma16_group<C::P_DMA>(p_next, p_voff, dst + 1024 * pw);
-            if constexpr ((PSA_K1P_X & 4096) == 0)
-                lds_dma16_group<C::V_DMA, NT_V && (PSA_K1P_X & 256) == 0>(
-                    v_next, v_voff, dst + C::P_STAGE_BYTES + wf * C::V_GROUP_BYTES + 1024 * (wh * C::V_DMA));
-            if constexpr ((PSA_K1P_X & 2048) == 0) p_next += C::P_STAGE_BYTES;
-            v_next += C::V_GROUP_BYTES;
-        } else if constexpr ((PSA_K1P_X & 32) != 0) {
-            const int      sc = st < last ? st : last;
-            const unsigned dst = lds0 + slot * C::STAGE_BYTES;
-            lds_dma16_group<C::P_DMA>(pbase + (size_t)sc * C::P_STAGE_BYTES, p_voff, dst + 1024 * pw);
-            lds_dma16_group<C::V_DMA, NT_V && (PSA_K1P_X & 256) == 0>(
-                vbase + (size_t)sc * C::V_GROUP_BYTES, v_voff, dst + C::P_STAGE_BYTES + wf * C::V_GROUP_BYTES + 1024 * (wh * C::V_DMA));
-        } else {
-#pragma unroll
-            for (int i = 0; i < C::BATCH; ++i) dma_piece(i, st, slot);
-        }
-    };
-
-    // bit 524288 (experiment): the BATCH pieces of a wavefront issued one by one, spread over the stage
-    // (running pointers advance behind the last piece)
-    auto dma_one = [&](auto i_c, int slot) {
-        constexpr int  i = decltype(i_c)::value;
+    const unsigned char* v_next = reinterpret_cast<const unsigned char*>(planes) + (size_t)fg * n_stage * C::V_GROUP_BYTES;
+    const int            lane16 = 16 * lane;                          // the lane's 16 bytes of a 1-KiB piece
+    const int            pw = C::P_PIECES >= 8 ? w * C::P_DMA : (w & 3);
+    const unsigned char* p_next = reinterpret_cast<const unsigned char*>(Pb) + (size_t)mb * n_stage * C::P_STAGE_BYTES;
+    const unsigned       v_voff = 1024 * (wh * C::V_DMA) + lane16, p_voff = 1024 * pw + lane16;
+    // this wavefront's BATCH for the next stage -> slot: P' pieces first, then V
+    auto dma_stage = [&](int slot) {
         const unsigned dst = lds0 + slot * C::STAGE_BYTES;
-        if constexpr (i < C::P_DMA) {
-            lds_dma16_at<1024 * i>(p_next, p_voff, dst + 1024 * pw);
-        } else {
-            lds_dma16_at<1024 * (i - C::P_DMA), NT_V && (PSA_K1P_X & 256) == 0>(
-                v_next, v_voff, dst + C::P_STAGE_BYTES + wf * C::V_GROUP_BYTES + 1024 * (wh * C::V_DMA));
-        }
-        if constexpr (i == C::BATCH - 1) {
-            p_next += C::P_STAGE_BYTES;
-            v_next += C::V_GROUP_BYTES;
-        }
+        lds_dma16_group<C::P_DMA>(p_next, p_voff, dst + 1024 * pw);
+        lds_dma16_group<C::V_DMA, NT_V>(v_next, v_voff, dst + C::P_STAGE_BYTES + wf * C::V_GROUP_BYTES + 1024 * (wh * C::V_DMA));
+        p_next += C::P_STAGE_BYTES;
+        v_next += C::V_GROUP_BYTES;
     };
 
     // ---- LDS read addresses: both images use the 64-byte rows / swizzled 16-byte slots of k1_f16.h
@@ -180,41 +113,13 @@ k1_planes_kernel(const _Float16* __restrict__ planes, const _Float16* __restrict
     E8    a[NP][MT16];
     E8    bs[2][3][NP];                            // B fragments of stage k: bs[k & 1][component][piece]
     f32x4 hi[MT16][3], lo[MT16][3];                // the running MFMA chains / the float32 sums
-    if constexpr ((PSA_K1P_X & 8192) != 0) {       // (timing experiment without LDS reads: operands that are
-        // defined, different from register to register and random-looking, so that the matrix pipe sees the
-        // switching activity of real data -- constant operands would let the chip clock up)
-        auto junk = [&](unsigned salt) {
-            E8 v;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                unsigned h = (unsigned)(lane * 8 + e) * 2654435761u ^ (salt * 40503u + 0x9E3779B9u);
-                h ^= h >> 15;
-                h *= 2246822519u;
-                h ^= h >> 13;
-                v[e] = (_Float16)((float)(int)(h & 0xFFFF) * (1.f / 8.f) - 4096.f);
-            }
-            return v;
-        };
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-#pragma unroll
-            for (int mt = 0; mt < MT16; ++mt) a[p][mt] = junk(p * 8 + mt);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                bs[0][c][p] = junk(100 + p * 8 + c);
-                bs[1][c][p] = junk(200 + p * 8 + c);
-            }
-        }
-    }
     auto  read_a_tile = [&](int mt, int slot) {
-        if constexpr ((PSA_K1P_X & 8192) != 0) return;
         const unsigned base = p_lane + slot * C::STAGE_BYTES;
 #pragma unroll
         for (int p = 0; p < NP; ++p)
             a[p][mt] = *reinterpret_cast<lds_cv8*>((const lds_u8*)(size_t)(base + (p * C::M_BLK + mt * 16) * 64));
     };
     auto read_b1 = [&](int par, int slot, int i) {
-        if constexpr ((PSA_K1P_X & 8192) != 0) return;
         bs[par][i >> 1][i & 1] = *reinterpret_cast<lds_cv8*>((const lds_u8*)(size_t)(v_lane + slot * C::STAGE_BYTES + i * 1024));
     };
     auto read_b = [&](int par, int slot) {
@@ -229,12 +134,10 @@ k1_planes_kernel(const _Float16* __restrict__ planes, const _Float16* __restrict
             lo[mt][c] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
 
-    if constexpr ((PSA_K1P_X & 2) != 0) {
-        if (wh == PSA_K1P_PRIO) __builtin_amdgcn_s_setprio(1);
-    }
+    if (wh == 1) __builtin_amdgcn_s_setprio(1);
     // ---- prologue: stages 0 .. RING-1 in flight; stage 0 into registers --------------------------
 #pragma unroll
-    for (int k = 0; k < C::RING; ++k) dma_stage(k, k);
+    for (int k = 0; k < C::RING; ++k) dma_stage(k);
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((C::RING - 1) * C::BATCH) : "memory");      // stage 0 landed
     read_b(0, 0);
 #pragma unroll
@@ -242,37 +145,7 @@ k1_planes_kernel(const _Float16* __restrict__ planes, const _Float16* __restrict
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((C::RING - 2) * C::BATCH) : "memory");   // stage 1 landed, slot 0 read
 
     auto mfma_tile = [&](int mt, int par, bool restart) {
-        if constexpr ((PSA_K1P_X & 1024) != 0) {        // timing experiment: operands consumed, no matrix work
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                asm volatile("" ::"v"(a[0][mt]), "v"(a[1][mt]), "v"(bs[par][c][0]), "v"(bs[par][c][1]));
-                if (restart) hi[mt][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            return;
-        }
         f32x4 ch[3];
-        if constexpr ((PSA_K1P_X & 65536) != 0) {
-            // experiment: every MFMA differs from its predecessor in ONE operand register (the component
-            // order snakes: up, down, up within a row tile, mirrored on odd row tiles); the order of the
-            // three terms of a chain is kept
-            const bool up = (mt & 1) == 0;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int c = up ? i : 2 - i;
-                ch[c] = PR::mma(a[1][mt], bs[par][c][0], restart ? f32x4{0.f, 0.f, 0.f, 0.f} : hi[mt][c]);
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int c = up ? 2 - i : i;
-                ch[c] = PR::mma(a[0][mt], bs[par][c][1], ch[c]);
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int c = up ? i : 2 - i;
-                hi[mt][c] = PR::mma(a[0][mt], bs[par][c][0], ch[c]);
-            }
-            return;
-        }
 #pragma unroll
         for (int c = 0; c < 3; ++c)
             ch[c] = PR::mma(a[1][mt], bs[par][c][0], restart ? f32x4{0.f, 0.f, 0.f, 0.f} : hi[mt][c]);
@@ -281,131 +154,39 @@ k1_planes_kernel(const _Float16* __restrict__ planes, const _Float16* __restrict
 #pragma unroll
         for (int c = 0; c < 3; ++c) hi[mt][c] = PR::mma(a[0][mt], bs[par][c][0], ch[c]);
     };
-    // experiments 131072 / 262144: all 36 MFMAs of a stage in one block, term by term over the twelve
-    // (row tile, component) pairs -- 131072: snake order, one operand register changes per MFMA;
-    // 262144: diagonal order, both change every time.  Same instructions, same reads (all behind the block).
-    auto mfma_stage_ordered = [&](int par, bool restart, bool snake) {
-#pragma unroll
-        for (int term = 0; term < 3; ++term) {
-#pragma unroll
-            for (int j = 0; j < 12; ++j) {
-                int mt, c;
-                if (snake) {
-                    mt = j / 3;
-                    c = (mt & 1) ? 2 - j % 3 : j % 3;
-                    if (term == 1) {             // walk back so that phase B ends where phase C starts
-                        mt = 3 - mt;
-                        c = 2 - c;
-                    }
-                } else {
-                    mt = j % 4;
-                    c = (j + j / 4) % 3;
-                }
-                if (term == 0)
-                    hi[mt][c] = PR::mma(a[1][mt], bs[par][c][0], restart ? f32x4{0.f, 0.f, 0.f, 0.f} : hi[mt][c]);
-                else if (term == 1)
-                    hi[mt][c] = PR::mma(a[0][mt], bs[par][c][1], hi[mt][c]);
-                else
-                    hi[mt][c] = PR::mma(a[0][mt], bs[par][c][0], hi[mt][c]);
-            }
-        }
-    };
     // One stage: slot holds stage s (in registers already), slot1 stage s+1 (landed).  The DMA of
-    // stage s+RING goes into slot; the B fragments of stage s+1 are read at the top, each row tile's
-    // A fragments right behind the MFMAs that consumed the old ones.
-    auto stage = [&](auto par_c, auto restart_c, int s, auto slot_c) {
+    // stage s+RING goes into slot -- waves 0-3 at the top, waves 4-7 behind the middle row tile; the
+    // B fragments of stage s+1 are read at the top, each row tile's A fragments right behind the MFMAs
+    // that consumed the old ones.
+    auto stage = [&](auto par_c, auto restart_c, int slot) {
         constexpr int  par = decltype(par_c)::value;
         constexpr bool restart = decltype(restart_c)::value;
-        const int      slot = slot_c;                  // an int, or an integral_constant (unrolled loop)
         const int      slot1 = slot == C::RING - 1 ? 0 : slot + 1;
-        constexpr bool STAGGER = (PSA_K1P_X & 1) != 0, SPREAD_DMA = (PSA_K1P_X & 4) != 0,
-                       SPREAD_B = (PSA_K1P_X & 8) != 0, FREE = (PSA_K1P_X & 16) != 0;
-        constexpr bool NO_DMA = (PSA_K1P_X & 16384) != 0;
-        constexpr bool SPREAD_RP = (PSA_K1P_X & 524288) != 0 && MT16 == 4 && C::BATCH == 5;
-        if constexpr (SPREAD_RP) {
-            dma_one(std::integral_constant<int, 0>{}, slot);
-        } else if constexpr (!SPREAD_DMA && !NO_DMA) {
-            if (!STAGGER || wh == 0) dma_stage(s + C::RING, slot);
-        }
-        if constexpr (!SPREAD_B) read_b(par ^ 1, slot1);
-        if constexpr (!FREE) __builtin_amdgcn_sched_barrier(0);
-        if constexpr ((PSA_K1P_X & (131072 | 262144)) != 0 && MT16 == 4) {
-            mfma_stage_ordered(par, restart, (PSA_K1P_X & 131072) != 0);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int mt = 0; mt < MT16; ++mt) {
-                read_a_tile(mt, slot1);
-                if constexpr (STAGGER && !NO_DMA) {
-                    if (mt == 1 && wh == 1) dma_stage(s + C::RING, slot);
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((C::RING - 2) * C::BATCH) : "memory");
-            return;
-        }
+        if (wh == 0) dma_stage(slot);
+        read_b(par ^ 1, slot1);
 #pragma unroll
         for (int mt = 0; mt < MT16; ++mt) {
-            if constexpr (SPREAD_B) {
-#pragma unroll
-                for (int i = mt * 6 / MT16; i < (mt + 1) * 6 / MT16; ++i) read_b1(par ^ 1, slot1, i);
-            }
-            if constexpr (SPREAD_DMA) {
-#pragma unroll
-                for (int i = mt * C::BATCH / MT16; i < (mt + 1) * C::BATCH / MT16; ++i) dma_piece(i, s + C::RING, slot);
-            }
             mfma_tile(mt, par, restart);
-            if constexpr (!FREE) __builtin_amdgcn_sched_barrier(0);
             read_a_tile(mt, slot1);
-            if constexpr (SPREAD_RP) {
-                if (mt == 0) dma_one(std::integral_constant<int, 1>{}, slot);
-                if (mt == 1) dma_one(std::integral_constant<int, 2>{}, slot);
-                if (mt == 2) dma_one(std::integral_constant<int, 3>{}, slot);
-                if (mt == 3) dma_one(std::integral_constant<int, 4>{}, slot);
-            }
-            if constexpr (STAGGER && !SPREAD_DMA && !NO_DMA && !SPREAD_RP) {
-                if (mt == (PSA_K1P_POS < 0 ? (MT16 - 1) / 2 : (PSA_K1P_POS < MT16 ? PSA_K1P_POS : MT16 - 1)) && wh == 1)
-                    dma_stage(s + C::RING, slot);
-            }
-            if constexpr (!FREE) __builtin_amdgcn_sched_barrier(0);
+            if (mt == (MT16 - 1) / 2 && wh == 1) dma_stage(slot);
         }
         // own blocks of stage s+2 landed (younger batches stay in flight), own LDS reads returned
-        if constexpr ((PSA_K1P_X & 32768) != 0)
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((C::RING - 2) * C::BATCH) : "memory");
-        else if constexpr (NO_DMA)
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((C::RING - 2) * C::BATCH) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((C::RING - 2) * C::BATCH) : "memory");
     };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
-    int s0 = 0;
-    if constexpr ((PSA_K1P_X & 64) != 0) {
-        // main loop: one fold period per iteration, slots and parities compile-time
-        // (RING 3: 6 stages, RING 4: 8 -- both within the <= FOLD stages a chain may run)
-        constexpr int PERIOD = C::RING == 3 ? 6 : 8;
-        static_assert(PERIOD <= C::FOLD && PERIOD % C::RING == 0 && PERIOD % 2 == 0, "period");
-        for (; s0 + PERIOD <= n_stage; s0 += PERIOD) {
-            [&]<int... I>(std::integer_sequence<int, I...>) {
-                (stage(std::integral_constant<int, (I & 1)>{}, std::bool_constant<I == 0>{}, s0 + I,
-                       std::integral_constant<int, I % C::RING>{}), ...);
-            }(std::make_integer_sequence<int, PERIOD>{});
-#pragma unroll
-            for (int mt = 0; mt < MT16; ++mt)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) lo[mt][c] += hi[mt][c];
-        }
-    }
-    int  slot = 0;                                     // s % RING  (s0 is a multiple of RING)
+    int  slot = 0;                                     // s % RING
     auto next_slot = [&]() { slot = slot == C::RING - 1 ? 0 : slot + 1; };
-    for (int s = s0; s < n_stage;) {                   // n_stage is even; a chain is an even number of stages
+    for (int s = 0; s < n_stage;) {                    // n_stage is even; a chain is an even number of stages
         const int len = n_stage - s < C::FOLD ? n_stage - s : C::FOLD;
-        stage(I0{}, std::true_type{}, s, slot);
+        stage(I0{}, std::true_type{}, slot);
         next_slot();
-        stage(I1{}, std::false_type{}, s + 1, slot);
+        stage(I1{}, std::false_type{}, slot);
         next_slot();
         for (int i = 2; i < len; i += 2) {
-            stage(I0{}, std::false_type{}, s + i, slot);
+            stage(I0{}, std::false_type{}, slot);
             next_slot();
-            stage(I1{}, std::false_type{}, s + i + 1, slot);
+            stage(I1{}, std::false_type{}, slot);
             next_slot();
         }
 #pragma unroll
@@ -570,7 +351,6 @@ int launch_k1_planes(psa_ctx* c, const void* d_planes, const void* d_phase, floa
                 "planes kernel needs 32-, 64- or 128-row M blocks");
     PSA_REQUIRE(g.A_pad % (2 * K1_BA) == 0 && g.A_pad > 0, "planes kernel needs the atom axis padded to %d", 2 * K1_BA);
     PSA_REQUIRE(g.vscale > 0.f && n_fg * 16 >= g.T, "planes do not cover the launch");
-    if (g.m_blk == 128 && g.M_pad == 128) return launch_planes_variant<4, PSA_K1P_RING1>(c, d_planes, d_phase, d_q, g, n_fg);
     if (g.m_blk == 128) return launch_planes_variant<4, 3>(c, d_planes, d_phase, d_q, g, n_fg);
     if (g.m_blk == 64) return launch_planes_variant<2, 4>(c, d_planes, d_phase, d_q, g, n_fg);
     return launch_planes_variant<1, 4>(c, d_planes, d_phase, d_q, g, n_fg);

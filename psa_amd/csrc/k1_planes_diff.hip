@@ -19,7 +19,7 @@
 // LDS address is a constant.  Entering stage s (stage s-1's units are free) waves 0-3 issue the units 28..43 of
 // stage s+2 and 0..27 of stage s+3 (the 160 - 3 x 44 = 28 spare units) -- eleven LDS-DMA instructions each,
 // their SIMD partners none (the issuing wavefront is held per instruction, its partner multiplies meanwhile:
-// PSA_K1W_SOLO of k1_planes_wide.hip).  The barrier that ends stage s is preceded by vmcnt(7): all of stages s+1
+// the scheme of k1_planes_wide.hip).  The barrier that ends stage s is preceded by vmcnt(7): all of stages s+1
 // and s+2 have landed, so a stage reads the next one's fragments while it multiplies.
 // Per stage and CU: 44 KiB of LDS-DMA (11 per 128 rows; the 256-row kernel needs 28), 384 MFMAs.
 #include <utility>

@@ -21,30 +21,27 @@
 // u = 8 k + w (k = 0..6) of every stage: k = 0..2 are the planes (unit 8 c + 4 p + j = component c, piece p,
 // frame group j: a wavefront copies its own frame group's piece h), k = 3..6 the phase tile in the order
 // the row tiles are consumed (unit 24 + 4 mt + 2 h + p).  Entering stage s (barrier s-1 passed; stage s-1's 56
-// units are free) a wavefront issues (s+1, k=6) and (s+2, k=0..5) -- in the shipped form waves 0-3 issue their
-// SIMD partners' units too (PSA_K1W_SOLO); the barrier that ends a stage is preceded by vmcnt(2) (SOLO: 4):
-// everything but (s+2, k=4..5) has landed -- all of stage s+1 and the first 32 units of stage s+2, i.e. its planes
-// and row tiles 0-1, which is what the last row tile of a stage prefetches.  Every unit has at least one
-// stage time (~1.7 us) between issue and first use.  Ring positions repeat every 20 stages (7 blocks of
-// 8 KiB per stage, 20 blocks): the main loop is unrolled 20 times and every LDS address is a constant.
+// units are free) waves 0-3 issue (s+1, k=6) and (s+2, k=0..5), each its own units and its SIMD partner's
+// (waves 4-7 issue none); the barrier that ends a stage is preceded by vmcnt(4): everything but (s+2, k=4..5)
+// has landed -- all of stage s+1 and the first 32 units of stage s+2, i.e. its planes and row tiles 0-1,
+// which is what the last row tile of a stage prefetches.  Every unit has at least one stage time (~1.7 us)
+// between issue and first use.  Ring positions repeat every 20 stages (7 blocks of 8 KiB per stage, 20
+// blocks): the main loop is unrolled 20 times and every LDS address is a constant.
 // Chains are folded into the float32 sums every 10 stages (a divisor of 20; bound 10 x 2^-24).
 #include <utility>
 
 #include "k1_f16.h"
 
-// Schedule switches (tools/k1_experiments.sh with KERNEL=k1_planes_wide MACRO=PSA_K1W_X, EXTRA_DEFS for the others; results
-// stay right; measurements in profiles/r3_k1_experiments.txt):
-//   PSA_K1W_X bits   1: chains folded every 20 stages instead of every 10 (no gain)   2: s_setprio 1 for waves 4-7 (no gain)
-//                    4: the stages past the group's last one are skipped instead of multiplying zeros (-1 %: configuration 3
-//                       has 1024 stages = 51 periods + 4)
-//                    8: the next row tile's A fragments read before the tile's first MFMA (left alone hipcc reads them behind
-//                       the third and reuses the dead low piece's registers; no gain)
-//   PSA_K1W_SOLO 1   waves 0-3 issue ALL LDS-DMA -- their own units and their SIMD partners' --, waves 4-7 none: a wavefront is
-//                    held ~70 cycles per LDS-DMA instruction, its partner multiplies meanwhile (-1.8 % against the next line)
-//   PSA_K1W_POS p    (SOLO 0) waves 4-7 issue their LDS-DMA behind row tile p instead of at the top of the stage, where their
-//                    partners are issuing too (p = 1: -2 %; p = 3: +5 %, the units arrive late)
-//   PSA_K1W_STAMP 1  DIAGNOSTIC build: every wavefront of workgroups 0-7 sums s_memtime differences over its stages (top of the
-//                    stage -> LDS-DMA issued -> row tile 0 -> tiles 1-3 -> tiles 4-7 -> fold + vmcnt -> barrier) and prints them
+// Schedule, measured (profiles/r3_k1_experiments.txt; results stay right in every variant):
+//   * waves 0-3 issue ALL LDS-DMA -- their own units and their SIMD partners' --, waves 4-7 none: a wavefront is held ~70
+//     cycles per LDS-DMA instruction, its partner multiplies meanwhile.  -1.8 % against waves 4-7 issuing their own units
+//     behind row tile 1, which is itself -2 % against issuing them at the top of the stage, where their partners are issuing
+//     too (behind row tile 3: +5 %, the units arrive late).
+//   * the stages past the group's last one are skipped instead of multiplying zeros (-1 %: configuration 3 has 1024
+//     stages = 51 periods + 4).
+//   * no gain: chains folded every 20 stages instead of every 10; s_setprio 1 for waves 4-7; the next row tile's A fragments
+//     read before the tile's first MFMA (left alone hipcc reads them behind the third and reuses the dead low piece's
+//     registers).
 // Issuing part of the LDS-DMA from inside the row-tile sequence (the units that have two stages to land, or the loads spread
 // over the stage) could not be measured: every such build spills 6-350 VGPRs -- any asm statement between the row tiles does
 // it, a C++ branch around a role's loads too -- and scratch traffic both costs time and breaks the counted vmcnt
@@ -53,23 +50,11 @@
 // instructions that have one stage to land at the top of the stage, waves 4-7 the four that have two at its end: +4 %
 // (waves 4-7 are not early at the barrier: from the moment waves 0-3 compute too, the two halves share the matrix pipe);
 // the same split with the loads under an EXEC mask instead of a jump: +13 % (a load under EXEC = 0 still costs its issue).
-#ifndef PSA_K1W_X
-#define PSA_K1W_X 4
-#endif
-#ifndef PSA_K1W_SOLO
-#define PSA_K1W_SOLO 1
-#endif
-#ifndef PSA_K1W_POS
-#define PSA_K1W_POS 1
-#endif
-#ifndef PSA_K1W_STAMP
-#define PSA_K1W_STAMP 0
-#endif
 
 namespace psa {
 
 namespace {
-constexpr int W_M_BLK = 256, W_T_BLK = 64, W_FOLD = (PSA_K1W_X & 1) ? 20 : 10, W_PERIOD = 20;
+constexpr int W_M_BLK = 256, W_T_BLK = 64, W_FOLD = 10, W_PERIOD = 20;
 constexpr int W_STAGE_UNITS = 56, W_RING_UNITS = 160;
 constexpr int W_P_STAGE_BYTES = F16x2::NP * W_M_BLK * K1_BA * 2;        // 32 KiB
 constexpr int W_V_GROUP_BYTES = PL_STAGE_ELEMS * 2;                     // 6 KiB
@@ -122,7 +107,7 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
         const int y = 8 * (k - 3) + w, mt = y >> 2, h = (y >> 1) & 1, p = y & 1;
         src[k] = ph0 + 1024 * (p * 16 + h * 8 + mt);                    // image [piece][256 rows][32 atoms]: 1 KiB per row tile
     }
-    // (PSA_K1W_SOLO: the partner's streams, units 8 k + w + 4 -- piece 1 of the same planes, the other half's row tiles)
+    // the SIMD partner's streams (waves 0-3 issue them too): units 8 k + w + 4 -- piece 1 of the same planes, the other half's row tiles
     const unsigned char* src2[7];
 #pragma unroll
     for (int k = 0; k < 3; ++k) src2[k] = pl0 + (size_t)fg * n_stage * W_V_GROUP_BYTES + 1024 * (2 * k + 1);
@@ -143,18 +128,14 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
             // planes come from a block of zeros, their phase tile is whatever follows (finite float16)
             w_dma<OFF, NT_V>(to_issue > 0 ? src[KK] : reinterpret_cast<const unsigned char*>(zeros), dma_voff, wbase);
             src[KK] += W_V_GROUP_BYTES;
-            if constexpr (PSA_K1W_SOLO != 0) {
-                w_dma<OFF + 4096, NT_V>(to_issue > 0 ? src2[KK] : reinterpret_cast<const unsigned char*>(zeros), dma_voff, wbase);
-                src2[KK] += W_V_GROUP_BYTES;
-            }
+            w_dma<OFF + 4096, NT_V>(to_issue > 0 ? src2[KK] : reinterpret_cast<const unsigned char*>(zeros), dma_voff, wbase);
+            src2[KK] += W_V_GROUP_BYTES;
             if constexpr (KK == 2) --to_issue;
         } else {
             w_dma<OFF, false>(src[KK], dma_voff, wbase);
             src[KK] += W_P_STAGE_BYTES;
-            if constexpr (PSA_K1W_SOLO != 0) {
-                w_dma<OFF + 4096, false>(src2[KK], dma_voff, wbase);
-                src2[KK] += W_P_STAGE_BYTES;
-            }
+            w_dma<OFF + 4096, false>(src2[KK], dma_voff, wbase);
+            src2[KK] += W_P_STAGE_BYTES;
         }
     };
     using std::integral_constant;
@@ -208,8 +189,8 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
     // ---- prologue: stage 0 (k = 0..6) and stage 1 (k = 0..5) ----------------------------------------------
     using I0 = integral_constant<int, 0>;
     using I1 = integral_constant<int, 1>;
-    constexpr int PENDING = PSA_K1W_SOLO ? 4 : 2;                          // DMA instructions a barrier leaves in flight per issuing wavefront
-    if (PSA_K1W_SOLO == 0 || wh == 0) {
+    constexpr int PENDING = 4;                                             // DMA instructions a barrier leaves in flight per issuing wavefront
+    if (wh == 0) {
         dma_range(I0{}, std::make_integer_sequence<int, 7>{});
         dma_range(I1{}, std::make_integer_sequence<int, 6>{});
     }
@@ -221,51 +202,22 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
 
     // ---- one stage; returns false behind the last one -------------------------------------------------------
     int  left = n_stage;                                                   // stages to go when the period began
-#if PSA_K1W_STAMP
-    unsigned st_acc[6] = {0, 0, 0, 0, 0, 0}, st_prev = 0, st_n = 0;
-    auto     stamp_now = [&]() __attribute__((always_inline)) {
-        unsigned long long t;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        return (unsigned)t;
-    };
-    auto stamp = [&](int i) __attribute__((always_inline)) {
-        const unsigned t = stamp_now();
-        st_acc[i] += t - st_prev;
-        st_prev = t;
-    };
-    st_prev = stamp_now();
-#define PSA_STAMP(i) stamp(i)
-#else
-#define PSA_STAMP(i)
-#endif
     auto stage = [&](auto s20_c) __attribute__((always_inline)) {
         constexpr int  S20 = decltype(s20_c)::value;
-        if constexpr ((PSA_K1W_X & 4) != 0) {
-            if (left <= S20) return;
-        }
+        if (left <= S20) return;                                           // past the group's last stage
         constexpr bool restart = S20 % W_FOLD == 0, folds = S20 % W_FOLD == W_FOLD - 1;
         using SN = integral_constant<int, (S20 + 1) % W_PERIOD>;
         using SNN = integral_constant<int, (S20 + 2) % W_PERIOD>;
-        // stage s-1's units are free: (s+1, k=6), (s+2, k=0..5)
-        auto issue = [&]() __attribute__((always_inline)) {
+        if (wh == 0) {                                                     // stage s-1's units are free: (s+1, k=6), (s+2, k=0..5)
             dma(SN{}, integral_constant<int, 6>{});
             dma_range(SNN{}, std::make_integer_sequence<int, 6>{});
-        };
-        if constexpr (PSA_K1W_SOLO != 0) {
-            if (wh == 0) issue();
-        } else if constexpr (PSA_K1W_POS < 0) {
-            issue();
-        } else {
-            if (wh == 0) issue();
         }
-        PSA_STAMP(0);
         auto tile = [&](auto mt_c) __attribute__((always_inline)) {
             constexpr int MTI = decltype(mt_c)::value, cur = MTI & 1;
             if constexpr (MTI < MT - 1)
                 read_a(s20_c, integral_constant<int, (cur ^ 1)>{}, integral_constant<int, MTI + 1>{});
             else
-                read_a(SN{}, integral_constant<int, (cur ^ 1)>{}, I0{});
-            if constexpr ((PSA_K1W_X & 8) != 0) __builtin_amdgcn_sched_barrier(0);      // the reads stay in front of the tile's MFMAs                          // row tile 0 of the next stage (landed: k = 3)
+                read_a(SN{}, integral_constant<int, (cur ^ 1)>{}, I0{});   // row tile 0 of the next stage (landed: k = 3)
             auto comp = [&](auto c_c) __attribute__((always_inline)) {
                 constexpr int CC = decltype(c_c)::value;
                 f32x4 ch = PR::mma(a[cur][1], bf[CC][0], restart ? f32x4{0.f, 0.f, 0.f, 0.f} : hi[MTI][CC]);
@@ -276,43 +228,19 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
             comp(I0{});
             comp(I1{});
             comp(integral_constant<int, 2>{});
-            if constexpr (PSA_K1W_SOLO == 0 && PSA_K1W_POS >= 0 && MTI == PSA_K1W_POS) {
-                if (wh != 0) issue();
-            }
             __builtin_amdgcn_sched_barrier(0);     // 232 registers are live by design: nothing moves across a row tile
-            if constexpr (MTI == 0) PSA_STAMP(1);
-            if constexpr (MTI == 3) PSA_STAMP(2);
-            if constexpr (MTI == 7) PSA_STAMP(3);
         };
         [&]<int... Ms>(std::integer_sequence<int, Ms...>) __attribute__((always_inline)) { (tile(integral_constant<int, Ms>{}), ...); }(std::make_integer_sequence<int, MT>{});
         if constexpr (folds) fold();
-        else if constexpr ((PSA_K1W_X & 4) != 0) {
-            if (left == S20 + 1) fold();                                  // the last stage of the group
-        }
+        else if (left == S20 + 1) fold();                                 // the last stage of the group
         // What this stage read from its own units has been consumed by the MFMAs above (it has returned); the
         // reads still in flight come from stage s+1's units, which nothing overwrites before barrier s+1.
-#if PSA_K1W_STAMP
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PENDING) : "memory");
-        PSA_STAMP(4);
-        asm volatile("s_barrier" ::: "memory");
-        PSA_STAMP(5);
-        ++st_n;
-#else
         asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(PENDING) : "memory");
-#endif
     };
-    if constexpr ((PSA_K1W_X & 2) != 0) {
-        if (wh) __builtin_amdgcn_s_setprio(1);
-    }
     for (; left > 0; left -= W_PERIOD)
         [&]<int... Ss>(std::integer_sequence<int, Ss...>) __attribute__((always_inline)) { (stage(integral_constant<int, Ss>{}), ...); }(
             std::make_integer_sequence<int, W_PERIOD>{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // nothing in flight when LDS is handed on
-#if PSA_K1W_STAMP
-    if (blockIdx.x < 8 && lane == 0 && st_n)
-        printf("[k1w stamp] block %d wave %d stages %u: dma %u  tile0 %u  tiles1-3 %u  tiles4-7 %u  fold+vmcnt %u  barrier %u  (cycles per stage)\n",
-               (int)blockIdx.x, w, st_n, st_acc[0] / st_n, st_acc[1] / st_n, st_acc[2] / st_n, st_acc[3] / st_n, st_acc[4] / st_n, st_acc[5] / st_n);
-#endif
 
     // ---- epilogue (k1_planes.hip): register j of lane (r16, q) is row 4q + j, column r16 of its 16x16 tile ----
     // (the lane's coordinates are taken afresh: carried through the loop they are two more live registers there)

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """The 256-row form of the planes kernel (PSA_OPT_K1_WIDE) and the 128-row forms against the oracle, before the FFT,
-on a few ragged shapes (GPU box; PSA_HIP_LIBRARY selects a side build of tools/k1_experiments.sh).  The oracle is the
-checker here, as in tests/."""
+on a few ragged shapes (GPU box).  The oracle is the checker here, as in tests/."""
 import sys
 from pathlib import Path
 
