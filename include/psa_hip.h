@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PSA_HIP_ABI_VERSION 5
+#define PSA_HIP_ABI_VERSION 6
 
 /* error codes */
 #define PSA_OK          0
@@ -141,6 +141,10 @@ int         psa_set_k1(psa_ctx* ctx, int selector);     /* PSA_K1_* */
 #define PSA_OPT_K1_LOWRANK      8
 #define PSA_OPT_K1_LOWRANK_MIN_K 9
 #define PSA_OPT_K1_LOWRANK_MIN_LOCAL 10
+/*   PSA_OPT_VDOS_WORK_BYTES [1 GiB] bytes of device memory the work buffer of psa_vdos may take, whatever N and T:
+ *                             the call loops over (atom block x segment block).  Must hold 32 atom pairs x 3
+ *                             components x one segment: 768 L bytes. */
+#define PSA_OPT_VDOS_WORK_BYTES 11
 int         psa_set_option(psa_ctx* ctx, int option, int64_t value);
 /* device name / CU count / HBM bytes of the context's GPU */
 int         psa_device_info(psa_ctx* ctx, char* name, int name_len,
@@ -273,6 +277,36 @@ int psa_sed_calculate(psa_ctx* ctx, int slot, const float* mean_pos_all,
                       const int32_t* group_idx, const int64_t* group_off, int32_t G,
                       int32_t flags, void* out_host, size_t out_bytes,
                       float* out_intensity, size_t out_intensity_bytes);
+
+/* Vibrational density of states: the power spectrum of the atoms' own series, summed over atom groups -- the
+ * k-integrated companion of the SED (which sums amplitudes over atoms BEFORE the FFT; this sums powers AFTER it).
+ * d[t,a,c] is the slot's data: velocities, or positions minus mean_pos_all under PSA_F_DISPLACEMENTS.  With segment
+ * length L, hop H and real window win (the context's psa_set_segments setting; none set: L = H = T, win = 1) and
+ * weights w_a (psa_set_atom_weights; none set: 1), for the atom groups g = 0 .. G-1:
+ *     n_seg      = 1 + (T - L) / H                          (integer division, as for segments)
+ *     U          = (1/L) sum_tau win[tau]^2
+ *     X_s[a,c,o] = (1/L) sum_tau win[tau] d[s H + tau, a, c] exp(-2 pi i o tau / L)
+ *     D[o,g,c]   = 1/(n_seg U) sum_s sum_{a in g} w_a^2 |X_s[a,c,o]|^2      o = 0 .. L/2   (L/2 + 1 rows, integer
+ *                                                                            division: 32 rows for L = 63)
+ * One-sided because the series are real: row o is the two-sided value at bin o, NOT doubled.  Frequencies are
+ * np.fft.rfftfreq(L, dt).  No detrending.  The weight is squared so that w = sqrt(m) gives sum m |v(omega)|^2, the
+ * convention of the weighted SED: for a group of one atom a, sum_c D[o,{a},c] is the PSA_F_INTENSITY result of the
+ * group {a} at any k.  With win = 1 and H = L, D[0] + 2 sum_{0<o<L/2} D[o] (+ D[L/2] for even L) is the mean square of
+ * the frames used.
+ *   group_idx / group_off / G as for psa_sed_project (NULL with G = 1: all atoms); the groups must be DISJOINT -- a
+ *   partial density of states is a partition, and one pass serves all groups; an empty group gives zeros;
+ *   out_host: (G, 3, L/2+1) float32, out_bytes exactly its size.
+ * PSA_EINVAL: out_bytes not exact, L > T, an index out of range, an atom listed twice, weights set for another N, a
+ * work budget (PSA_OPT_VDOS_WORK_BYTES) below 768 L bytes.
+ * One pass over the selected atoms' columns of the resident array per (overlapping) segment: gather and transpose
+ * through LDS with mean, weight and window applied; a batched length-L rocFFT in which two atoms of one group share a
+ * complex series (|X_a|^2 + |X_b|^2 = (|Z[o]|^2 + |Z[L-o]|^2) / 2, so nothing is untangled); |.|^2 summed in float64
+ * per (group, component, bin), each element by one thread per launch, launches in order on the context's stream:
+ * deterministic.  The slab, the k map, the plane cache and every result of the SED entry points are left as they are.
+ * Stage times go to psa_last_timings: [6] gather, [3] FFT, [4] power, [7] device->host. */
+int psa_vdos(psa_ctx* ctx, int slot, const float* mean_pos_all /* (N,3); read only under PSA_F_DISPLACEMENTS */,
+             const int32_t* group_idx, const int64_t* group_off, int32_t G,
+             int32_t flags /* PSA_F_DISPLACEMENTS or 0 */, float* out_host /* (G,3,L/2+1) */, size_t out_bytes);
 
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting

@@ -15,8 +15,9 @@ from .core import SED, SEDCalculator, Trajectory
 from .core.sed import fast_intensity
 from .utils.helpers import parse_direction
 from .segments import Segments
+from .vdos import VDOS
 from .weights import mass_weights
 
 __version__ = "0.2.0"
 __all__ = ["Trajectory", "SED", "SEDCalculator", "parse_direction", "fast_intensity", "mass_weights", "Segments",
-           "__version__"]
+           "VDOS", "__version__"]

@@ -27,8 +27,9 @@ OPT_K1_WIDE = 7
 OPT_K1_LOWRANK = 8
 OPT_K1_LOWRANK_MIN_K = 9
 OPT_K1_LOWRANK_MIN_LOCAL = 10
+OPT_VDOS_WORK_BYTES = 11
 KMAP_MIRROR = 0x80000000
-ABI_VERSION = 5
+ABI_VERSION = 6
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -68,6 +69,7 @@ SIGNATURES = {
     "psa_sed_finalize": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, _f32p, C.c_size_t]),
     "psa_sed_calculate": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p, _i64p,
                                     C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, _f32p, C.c_size_t]),
+    "psa_vdos": (C.c_int, [_ctx, C.c_int, _f32p, _i32p, _i64p, C.c_int32, C.c_int32, _f32p, C.c_size_t]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p]),
@@ -581,6 +583,22 @@ class Engine:
             out.ctypes.data_as(C.c_void_p), out.nbytes,
             _f32(inten) if inten is not None else None, inten.nbytes if inten is not None else 0), "psa_sed_calculate")
         return (out, inten) if with_intensity else out
+
+    def vdos(self, slot, mean_pos_all, groups=None, flags=0) -> np.ndarray:
+        """Vibrational density of states of the resident array (psa_vdos): (L/2+1, G, 3) float32, the power spectrum
+        of each atom's own series summed over the atoms of each group (disjoint index arrays; None: all atoms as one
+        group), with the context's atom weights and segments (none set: L = T).  `mean_pos_all` is read only under
+        F_DISPLACEMENTS.  The result of the SED entry points resident on the device is not touched."""
+        T, N = self.shape(slot)
+        L = self.segment_length or T
+        mean = None if mean_pos_all is None else _as_f32(mean_pos_all, (3,))
+        idx, off, G = pack_groups(groups)
+        out = np.empty((G, 3, L // 2 + 1), np.float32)
+        _check(self._lib.psa_vdos(
+            self._h, slot, _f32(mean) if mean is not None else None,
+            idx.ctypes.data_as(_i32p) if idx is not None else None,
+            off.ctypes.data_as(_i64p) if off is not None else None, G, flags, _f32(out), out.nbytes), "psa_vdos")
+        return np.ascontiguousarray(out.transpose(2, 0, 1))
 
     def set_kmap(self, kmap: np.ndarray):
         """Install the k map of a result whose slab rows were projected from a folded list (`k_pairs`)."""

@@ -33,6 +33,7 @@ from .. import _hip
 from ..io.writer import out_to_qdump
 from ..segments import Segments
 from ..utils.helpers import parse_direction
+from ..vdos import VDOS
 from ..weights import check_atom_weights
 from .sed import SED
 from .trajectory import Trajectory
@@ -399,6 +400,54 @@ class SEDCalculator:
             # `sed.intensity` right after the calculation is served from the result still on the device
             sed._device_intensity = self._engine.intensity_source(data)
         return sed
+
+    # ------------------------------------------------------------------ density of states
+    def calculate_vdos(self, basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                       basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                       atom_weights: Optional[np.ndarray] = None, segments: Optional[Segments] = None) -> VDOS:
+        """Vibrational density of states (not in the reference; definition in psa_amd/vdos.py): the power spectrum of
+        each atom's own velocity series (displacement series with `use_displacements=True`) summed over the atoms of
+        each group, computed on the GPU from the array resident in HBM.
+
+        Groups are resolved like those of an incoherent `calculate`: `basis_atom_types=[1, 2]` gives the two partial
+        densities of states, nothing gives all atoms as one group.  They must be disjoint (ValueError).
+        `atom_weights`: as for `calculate`; they enter squared, so `psa_amd.mass_weights` gives sum_a m_a |v_a(w)|^2.
+        `segments`: a `psa_amd.Segments` for the Welch average; None is one boxcar segment of all frames.  A sharded
+        calculator refuses (NotImplementedError).  Returns a `psa_amd.VDOS` with `dos` (L // 2 + 1, G, 3) float32.
+        """
+        weights = None if atom_weights is None else check_atom_weights(atom_weights, self.traj.n_atoms)
+        if segments is not None and not isinstance(segments, Segments):
+            raise TypeError(f"segments must be a psa_amd.Segments, got {type(segments).__name__}")
+        if self._shard is not None and self._shard.nranks > 1:
+            raise NotImplementedError("the density of states is not available on a sharded calculator")
+        n_t, n_atoms = self.traj.n_frames, self.traj.n_atoms
+        if n_t == 0 or n_atoms == 0:
+            logger.warning("Cannot calculate VDOS: 0 frames or 0 atoms.")
+            return VDOS(np.zeros((0, 0, 3), np.float32), np.zeros(0, np.float64), [])
+        if segments is not None:
+            segments.count(n_t)                          # ValueError if L > T
+        groups = self._resolve_groups(basis_atom_indices, basis_atom_types, "incoherent")
+        members = np.concatenate(groups)
+        if np.unique(members).size != members.size:
+            raise ValueError("atom groups of a density of states must be disjoint (an atom is listed twice)")
+        L = n_t if segments is None else segments.length
+        slot, data, flags = self._data_slot()
+        mean_pos_all = self._mean_positions() if self.use_displacements else None
+        eng = self.engine
+        with eng.lock:
+            if weights is not None:
+                eng.set_atom_weights(weights)
+            try:
+                if segments is not None:             # (before the upload: its FFT primer then builds length L)
+                    eng.set_segments(segments)
+                eng.ensure_resident(slot, data)      # later SED calls find it resident
+                dos = eng.vdos(slot, mean_pos_all, self._device_groups(groups), flags)
+            finally:
+                if weights is not None:
+                    eng.set_atom_weights(None)
+                if segments is not None:
+                    eng.set_segments(None)
+        return VDOS(dos, np.fft.rfftfreq(L, d=self.dt_ps), [np.asarray(g) for g in groups])
 
     # ------------------------------------------------------------------ chiral phase
     def calculate_chiral_phase(self, Z1: np.ndarray, Z2: np.ndarray, angle_range_opt: str = "C") -> np.ndarray:

@@ -275,7 +275,9 @@ int psa_destroy(psa_ctx* c) {
         if (c->d2h_ready) (void)hipEventDestroy(c->d2h_ready);
         for (DevBuf* b : {&c->d_kvec, &c->d_mean_all, &c->d_idx, &c->d_mean_g, &c->d_phase, &c->d_qwork,
                           &c->d_fft_work, &c->d_tables, &c->d_absmax, &c->d_slab, &c->d_out, &c->d_aux, &c->d_sync,
-                          &c->d_qrows, &c->d_stage, &c->d_bin, &c->d_upload_max, &c->d_zeros, &c->d_kmap, &c->d_cols, &c->d_inten})
+                          &c->d_qrows, &c->d_stage, &c->d_bin, &c->d_upload_max, &c->d_zeros, &c->d_kmap, &c->d_cols, &c->d_inten,
+                          &c->d_vdos_work, &c->d_vdos_pairs, &c->d_vdos_off, &c->d_vdos_mean, &c->d_vdos_part, &c->d_vdos_acc,
+                          &c->d_vdos_out})
             b->release();
         (void)hipStreamDestroy(c->stream);
     }
@@ -339,6 +341,10 @@ int psa_set_option(psa_ctx* c, int option, int64_t value) {
         case PSA_OPT_K1_LOWRANK_MIN_K:
             PSA_REQUIRE(value >= 1, "PSA_OPT_K1_LOWRANK_MIN_K must be >= 1");
             c->opt_k1_lowrank_min_k = value;
+            return PSA_OK;
+        case PSA_OPT_VDOS_WORK_BYTES:
+            PSA_REQUIRE(value >= 1, "PSA_OPT_VDOS_WORK_BYTES must be >= 1");
+            c->opt_vdos_work_bytes = value;
             return PSA_OK;
     }
     set_error("unknown option %d", option);

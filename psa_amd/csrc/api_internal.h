@@ -4,6 +4,7 @@
 //   api_data.hip     trajectory residency: staging pipeline, uploads, magnitude passes, mean, displacements
 //   api_project.hip  the hot path: plane cache, geometry, projection, project / finalize / calculate, diagnostics
 //   api_shard.hip    sharding over RCCL: communicator, k-row gather, frame sharding
+//   api_vdos.hip     the vibrational density of states: a second, non-projecting pass over the resident array
 #pragma once
 #include <algorithm>
 #include <chrono>

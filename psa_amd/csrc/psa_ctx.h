@@ -260,6 +260,12 @@ struct psa_ctx {
     int64_t      seg_L = 0, seg_hop = 0;
     double       seg_U = 0.0;
 
+    // vibrational density of states (psa_vdos, api_vdos.hip): the work buffer of one (atom block x segment block) is held
+    // to opt_vdos_work_bytes (PSA_OPT_VDOS_WORK_BYTES); the pair list, the groups' pair offsets, the mean, the chunk
+    // partials, the float64 accumulator and the float32 result.  All kept between calls.
+    psa::DevBuf  d_vdos_work, d_vdos_pairs, d_vdos_off, d_vdos_mean, d_vdos_part, d_vdos_acc, d_vdos_out;
+    int64_t      opt_vdos_work_bytes = (int64_t)1 << 30;
+
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
                                           // plane builds, trajectory uploads (psa_oneoff_stats)
@@ -354,6 +360,19 @@ int launch_segment_window(psa_ctx* c, const float2* d_q, const float* d_w, float
                           int64_t s0, int64_t ns, int64_t nk);
 int launch_segment_power(psa_ctx* c, const float2* d_seg, float* d_rows, int64_t L, int64_t ns, int64_t nk, float inv_norm,
                          bool first);
+// --- vdos.hip (psa_vdos: per-atom series -> power summed per atom group; two atoms share one complex series)
+constexpr int VDOS_TILE_PAIRS = 32;   // atom pairs per gather tile: the unit of an atom block
+// pairs [0, n_pairs) of d_pair_atoms (2 atom indices each, -1: none) x segments [s0, s0 + ns) of the resident array ->
+// d_work (3, n_pairs, ns, L) complex64: w_a win[tau] (d - mean); mean, weights, win may be null
+int launch_vdos_gather(psa_ctx* c, const float* d_data, const float* d_mean, const float* d_weights, const float* d_win,
+                       const int* d_pair_atoms, float2* d_work, int64_t T, int64_t N, int64_t L, int64_t H, int64_t s0,
+                       int64_t ns, int64_t n_pairs);
+// after the FFT of d_work, the block being pairs [p0, p0 + n_pairs) of the list: acc (G,3,L) float64 rows of groups
+// [g_first, g_first + n_groups) += sum over the group's rows of |Z|^2, through n_chunks partials (n_chunks, n_groups, 3, L)
+int launch_vdos_power(psa_ctx* c, const float2* d_work, const int64_t* d_pair_off, double* d_part, double* d_acc, int64_t L,
+                      int64_t ns, int64_t n_pairs, int64_t p0, int64_t g_first, int64_t n_groups, int64_t n_chunks);
+// out (rows, L/2 + 1) float32 = scale (acc[o] + acc[(L - o) mod L])
+int launch_vdos_finish(psa_ctx* c, const double* d_acc, float* d_out, int64_t L, int64_t rows, double scale);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 
