@@ -7,8 +7,10 @@ import numpy as np
 import pytest
 
 import cases as C
+import dense_cases
 from conftest import make_calculator, rel_max
 from oracle import psa_oracle as O
+from ref64 import gamma, project64, scale_B
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -429,6 +431,14 @@ def test_f16_kernel_wide_dynamic_range(engine):
         got = calc.calculate(mags, vecs, **kw)
         ref, _, _ = O.calculate(tr.positions, tr.velocities, tr.types, tr.dt_ps, vecs, **kw)
         assert rel_max(got.sed, ref) <= TOL
+        # ... and every element before the FFT against float64, in units of its own scale sum_a |d| (tests/ref64.py)
+        mean = O.mean_positions(tr.positions)
+        engine.ensure_resident(0, tr.velocities)
+        q = engine.debug_project_only(0, mean, vecs, idx)
+        g = gamma(q, project64(tr.velocities, mean, vecs, idx), scale_B(tr.velocities, mean, idx))
+        bound = dense_cases.bound("pair", 384 if idx is None else len(idx))
+        print(f"wide dynamic range, {384 if idx is None else len(idx)} atoms: gamma {g:.3e} = {g / bound:.3f} x bound {bound:.2e}")
+        assert g <= bound
 
 
 def test_f16_kernel_linearity_and_atom_order(engine):
