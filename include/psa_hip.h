@@ -145,6 +145,12 @@ int         psa_set_k1(psa_ctx* ctx, int selector);     /* PSA_K1_* */
  *                             the call loops over (atom block x segment block).  Must hold 32 atom pairs x 3
  *                             components x one segment: 768 L bytes. */
 #define PSA_OPT_VDOS_WORK_BYTES 11
+/*   PSA_OPT_MODES_WORK_BYTES [4 GiB] bytes of device memory the stacked spectra of psa_sed_modes may take: the call
+ *                             loops over blocks of k-vectors of 24 B T bytes each (B groups x 3 components x T
+ *                             complex64).  The default holds 256 k-vectors of 65536 frames and 8 sites in one block.
+ *                             Any value >= 1 is accepted; a call whose single k-vector does not fit is PSA_EINVAL.
+ *                             The (T,K,M) float32 result on the device is not part of the budget. */
+#define PSA_OPT_MODES_WORK_BYTES 12
 int         psa_set_option(psa_ctx* ctx, int option, int64_t value);
 /* device name / CU count / HBM bytes of the context's GPU */
 int         psa_device_info(psa_ctx* ctx, char* name, int name_len,
@@ -308,6 +314,35 @@ int psa_vdos(psa_ctx* ctx, int slot, const float* mean_pos_all /* (N,3); read on
              const int32_t* group_idx, const int64_t* group_off, int32_t G,
              int32_t flags /* PSA_F_DISPLACEMENTS or 0 */, float* out_host /* (G,3,L/2+1) */, size_t out_bytes);
 
+/* Mode-projected SED (normal-mode decomposition): the spectra of the B basis-site groups of a crystal, contracted with
+ * the polarisation vectors of M modes per k-point BEFORE the modulus is taken -- one column per phonon branch instead of
+ * one per k-point.  d[t,a,c] is the slot's data: velocities, or positions minus mean_pos_all under PSA_F_DISPLACEMENTS;
+ * w_a the context's atom weights (psa_set_atom_weights; none set: 1); r_a = mean_pos_all[a].  For the disjoint atom
+ * groups b = 0 .. B-1 ("site b in every cell") and the mode vectors eig (K, M, B, 3) complex64, C order:
+ *     q_b[k,c,t]  = sum_{a in b} w_a d[t,a,c] exp(+i k.r_a)            the projection of psa_sed_project, every route
+ *     S_b[k,c,w]  = (1/T) sum_t q_b[k,c,t] exp(-2 pi i w t / T)
+ *     Q[k,nu,w]   = sum_b sum_c conj(eig[k,nu,b,c]) S_b[k,c,w]
+ *     Phi[w,k,nu] = |Q[k,nu,w]|^2                                      out_host (T, K, M) float32, w in FFT order
+ * eig is used as given: not normalised, not required to be orthogonal, M is free (the 3 acoustic branches alone are as
+ * valid as all 3B).  The sign conventions are the projection's: exp(+i k.r_a) with each atom's OWN mean position (not
+ * its cell origin), and conj(eig) in the contraction; a lattice-dynamics code with another phase convention has its
+ * vectors converted by the caller.  Pairs (k, -k) are not folded: each k-vector has its own vectors.  An empty group
+ * contributes nothing.
+ *   group_idx / group_off / B as for psa_sed_project (NULL with B = 1: all atoms); the groups must be disjoint;
+ *   out_bytes exactly 4 T K M.
+ * PSA_EINVAL: eig or out_host null, M < 1, a non-finite eig value, an atom in two groups, an index out of range,
+ * out_bytes not exact, segments set (psa_set_segments: no segment average here), weights set for another N, a work
+ * budget (PSA_OPT_MODES_WORK_BYTES) below 24 B T bytes.
+ * Per block of k-vectors: B projections into one stacked buffer (B, kb, 3, T), one batched rocFFT of 3 B kb series,
+ * one pass (modes.hip) that contracts and takes the modulus; blocks of a k-path keep PSA_OPT_K1_LOWRANK_MIN_LOCAL
+ * vectors where the budget allows.  The slab, the k map and every result of the SED entry points are left as they are;
+ * the call returns after the stream has drained.  Stage times go to psa_last_timings: [2] projection, [3] FFT,
+ * [4] contraction, [7] device->host. */
+int psa_sed_modes(psa_ctx* ctx, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K,
+                  const int32_t* group_idx, const int64_t* group_off, int32_t B,
+                  const void* eig /* (K,M,B,3) complex64 */, int64_t M, int32_t flags /* PSA_F_DISPLACEMENTS or 0 */,
+                  float* out_host /* (T,K,M) */, size_t out_bytes);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is
@@ -380,6 +415,10 @@ int psa_debug_project_frames(psa_ctx* ctx, int slot, const float* mean_pos_all,
                              const float* k_vectors, int64_t K,
                              const int32_t* idx, int64_t n_g, int32_t flags,
                              int64_t t_begin, int64_t t_count, void* out_host);
+/* the contraction kernel of psa_sed_modes alone, on spectra the caller uploads: S_host (B,K,3,T) complex64 taken as
+ * they are (no division by T), eig (K,M,B,3) complex64 -> out_host (T,K,M) float32 = |sum_{b,c} conj(eig) S|^2 */
+int psa_debug_mode_power(psa_ctx* ctx, const void* S_host, const void* eig, int32_t B, int64_t K, int64_t M, int64_t T,
+                         float* out_host);
 /* number of plane sets in the cache and their bytes */
 int psa_debug_plane_cache(psa_ctx* ctx, int64_t* n_sets, int64_t* bytes);
 

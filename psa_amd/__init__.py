@@ -15,9 +15,10 @@ from .core import SED, SEDCalculator, Trajectory
 from .core.sed import fast_intensity
 from .utils.helpers import parse_direction
 from .segments import Segments
+from .modes import ModeSED, site_groups
 from .vdos import VDOS
 from .weights import mass_weights
 
 __version__ = "0.2.0"
 __all__ = ["Trajectory", "SED", "SEDCalculator", "parse_direction", "fast_intensity", "mass_weights", "Segments",
-           "VDOS", "__version__"]
+           "VDOS", "ModeSED", "site_groups", "__version__"]

@@ -28,6 +28,7 @@ OPT_K1_LOWRANK = 8
 OPT_K1_LOWRANK_MIN_K = 9
 OPT_K1_LOWRANK_MIN_LOCAL = 10
 OPT_VDOS_WORK_BYTES = 11
+OPT_MODES_WORK_BYTES = 12
 KMAP_MIRROR = 0x80000000
 ABI_VERSION = 6
 UNIQUE_ID_BYTES = 128
@@ -70,6 +71,8 @@ SIGNATURES = {
     "psa_sed_calculate": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p, _i64p,
                                     C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, _f32p, C.c_size_t]),
     "psa_vdos": (C.c_int, [_ctx, C.c_int, _f32p, _i32p, _i64p, C.c_int32, C.c_int32, _f32p, C.c_size_t]),
+    "psa_sed_modes": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p, _i64p, C.c_int32, C.c_void_p, C.c_int64,
+                                C.c_int32, _f32p, C.c_size_t]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p]),
@@ -89,6 +92,7 @@ SIGNATURES = {
                                          C.c_int64, C.c_int32, C.c_void_p]),
     "psa_debug_project_frames": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p,
                                            C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
+    "psa_debug_mode_power": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _f32p]),
     "psa_debug_plane_cache": (C.c_int, [_ctx, _i64p, _i64p]),
     "psa_comm_unique_id": (C.c_int, [C.c_void_p]),
     "psa_comm_init": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int]),
@@ -599,6 +603,42 @@ class Engine:
             idx.ctypes.data_as(_i32p) if idx is not None else None,
             off.ctypes.data_as(_i64p) if off is not None else None, G, flags, _f32(out), out.nbytes), "psa_vdos")
         return np.ascontiguousarray(out.transpose(2, 0, 1))
+
+    def sed_modes(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags=0) -> np.ndarray:
+        """Mode-projected SED of the resident array (psa_sed_modes): (T, K, M) float32 = |sum_{b,c} conj(eig) S_b|^2 for
+        the B disjoint site groups (index arrays; None: all atoms as one group) and `eigenvectors` (K, M, B, 3)
+        complex64, with the context's atom weights; the definition is in psa_amd/modes.py.  The result of the SED entry
+        points resident on the device is not touched."""
+        T, _ = self.shape(slot)
+        mean = _as_f32(mean_pos_all, (3,))
+        kv = _as_f32(k_vectors, (3,))
+        idx, off, B = pack_groups(groups)
+        eig = np.ascontiguousarray(eigenvectors, np.complex64)
+        K = kv.shape[0]
+        if eig.ndim != 4 or eig.shape[0] != K or eig.shape[2:] != (B, 3) or eig.shape[1] < 1:
+            raise ValueError(f"eigenvectors have shape {eig.shape}, expected (K, M, B, 3) = ({K}, M, {B}, 3)")
+        M = eig.shape[1]
+        out = pinned_empty((T, K, M), np.float32)
+        _check(self._lib.psa_sed_modes(
+            self._h, slot, _f32(mean), _f32(kv), K,
+            idx.ctypes.data_as(_i32p) if idx is not None else None,
+            off.ctypes.data_as(_i64p) if off is not None else None, B,
+            eig.ctypes.data_as(C.c_void_p), M, flags, _f32(out), out.nbytes), "psa_sed_modes")
+        return out
+
+    def debug_mode_power(self, spectra: np.ndarray, eigenvectors: np.ndarray) -> np.ndarray:
+        """The contraction kernel of `sed_modes` alone (psa_debug_mode_power): spectra (B, K, 3, T) complex64 taken as
+        they are, eigenvectors (K, M, B, 3) complex64 -> (T, K, M) float32."""
+        S = np.ascontiguousarray(spectra, np.complex64)
+        eig = np.ascontiguousarray(eigenvectors, np.complex64)
+        B, K, _, T = S.shape
+        if S.shape[2] != 3 or eig.ndim != 4 or eig.shape[0] != K or eig.shape[2:] != (B, 3):
+            raise ValueError(f"spectra {S.shape} and eigenvectors {eig.shape} do not fit (B,K,3,T) and (K,M,B,3)")
+        M = eig.shape[1]
+        out = np.empty((T, K, M), np.float32)
+        _check(self._lib.psa_debug_mode_power(self._h, S.ctypes.data_as(C.c_void_p), eig.ctypes.data_as(C.c_void_p), B, K, M, T,
+                                              _f32(out)), "psa_debug_mode_power")
+        return out
 
     def set_kmap(self, kmap: np.ndarray):
         """Install the k map of a result whose slab rows were projected from a folded list (`k_pairs`)."""

@@ -31,6 +31,7 @@ import numpy as np
 
 from .. import _hip
 from ..io.writer import out_to_qdump
+from ..modes import ModeSED
 from ..segments import Segments
 from ..utils.helpers import parse_direction
 from ..vdos import VDOS
@@ -448,6 +449,73 @@ class SEDCalculator:
                 if segments is not None:
                     eng.set_segments(None)
         return VDOS(dos, np.fft.rfftfreq(L, d=self.dt_ps), [np.asarray(g) for g in groups])
+
+    # ------------------------------------------------------------------ mode projection
+    def calculate_mode_sed(self, k_points_mags: np.ndarray, k_vectors_3d: np.ndarray, eigenvectors: np.ndarray,
+                           basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                           basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                           atom_weights: Optional[np.ndarray] = None) -> ModeSED:
+        """Mode-projected SED (normal-mode decomposition; not in the reference; definition in psa_amd/modes.py):
+
+            Phi[w,k,nu] = | sum_b sum_c conj(eigenvectors[k,nu,b,c]) S_b[k,c,w] |^2
+
+        where S_b is what `calculate` returns for the atom group b ("site b of the primitive cell in every cell"),
+        computed on the GPU without the B group spectra ever leaving HBM.
+
+        The B groups are resolved like those of an incoherent `calculate` (`basis_atom_indices` as a list of index
+        lists or arrays -- `psa_amd.site_groups(labels)` makes them from a site index per atom -- or
+        `basis_atom_types`); they must be disjoint (ValueError).  `eigenvectors` is (K, M, B, 3) complex, used as
+        given: no normalisation, M free.  The phase convention is the projection's, exp(+i k.r_a) with each atom's own
+        mean position, and the vectors enter conjugated; converting the vectors of a lattice-dynamics code that uses
+        another convention is the caller's business.  Pairs (k, -k) are not folded.  `atom_weights` as for `calculate`
+        (`psa_amd.mass_weights` for the mass-weighted mode coordinate).  A sharded calculator refuses
+        (NotImplementedError).  Returns a `psa_amd.ModeSED` with `sed` (T, K, M) float32."""
+        weights = None if atom_weights is None else check_atom_weights(atom_weights, self.traj.n_atoms)
+        if self._shard is not None and self._shard.nranks > 1:
+            raise NotImplementedError("the mode-projected SED is not available on a sharded calculator")
+        eig = np.asarray(eigenvectors)
+        k_vectors = np.asarray(k_vectors_3d, np.float32).reshape(-1, 3)
+        n_t, n_atoms, n_k = self.traj.n_frames, self.traj.n_atoms, len(k_vectors)
+        if n_t == 0 or n_atoms == 0:
+            logger.warning("Cannot calculate the mode-projected SED: 0 frames or 0 atoms.")
+            return ModeSED(np.zeros((0, 0, 0), np.float32), np.zeros(0, np.float64), k_points_mags, k_vectors_3d, [])
+        if (basis_atom_types is None and isinstance(basis_atom_indices, (list, tuple)) and len(basis_atom_indices)
+                and all(isinstance(g, np.ndarray) for g in basis_atom_indices)):
+            # index arrays (`site_groups`) are taken as they are, with the checks of `_resolve_groups`: no detour
+            # through Python lists of a whole crystal's atoms
+            groups = [g.astype(int).ravel() for g in basis_atom_indices if g.size]
+            if any(np.any(g >= n_atoms) or np.any(g < 0) for g in groups):
+                raise ValueError("Atom indices in basis out of bounds.")
+            if not groups:
+                groups = [np.arange(n_atoms)]
+        else:
+            groups = self._resolve_groups(basis_atom_indices, basis_atom_types, "incoherent")
+        members = np.concatenate(groups)
+        if np.unique(members).size != members.size:
+            raise ValueError("atom groups of a mode projection must be disjoint (an atom is listed twice)")
+        if eig.ndim != 4 or eig.shape[0] != n_k or eig.shape[2:] != (len(groups), 3) or eig.shape[1] < 1:
+            raise ValueError(f"eigenvectors have shape {eig.shape}, expected (K, M, B, 3) = ({n_k}, M, {len(groups)}, 3) "
+                             f"for {n_k} k-vectors and {len(groups)} atom groups")
+        if not np.all(np.isfinite(eig)):
+            raise ValueError("eigenvectors must be finite")
+        freqs = np.fft.fftfreq(n_t, d=self.dt_ps)
+        out_groups = [np.asarray(g) for g in groups]
+        if n_k == 0:
+            logger.warning("k_vectors_3d is empty. Returning ModeSED object with empty data.")
+            return ModeSED(np.zeros((n_t, 0, eig.shape[1]), np.float32), freqs, k_points_mags, k_vectors_3d, out_groups)
+        mean_pos_all = self._mean_positions()
+        slot, data, flags = self._data_slot()
+        eng = self.engine
+        with eng.lock:
+            if weights is not None:
+                eng.set_atom_weights(weights)
+            try:
+                eng.ensure_resident(slot, data)      # later SED calls find it resident
+                phi = eng.sed_modes(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64), flags)
+            finally:
+                if weights is not None:
+                    eng.set_atom_weights(None)
+        return ModeSED(phi, freqs, k_points_mags, k_vectors_3d, out_groups)
 
     # ------------------------------------------------------------------ chiral phase
     def calculate_chiral_phase(self, Z1: np.ndarray, Z2: np.ndarray, angle_range_opt: str = "C") -> np.ndarray:

@@ -277,7 +277,7 @@ int psa_destroy(psa_ctx* c) {
                           &c->d_fft_work, &c->d_tables, &c->d_absmax, &c->d_slab, &c->d_out, &c->d_aux, &c->d_sync,
                           &c->d_qrows, &c->d_stage, &c->d_bin, &c->d_upload_max, &c->d_zeros, &c->d_kmap, &c->d_cols, &c->d_inten,
                           &c->d_vdos_work, &c->d_vdos_pairs, &c->d_vdos_off, &c->d_vdos_mean, &c->d_vdos_part, &c->d_vdos_acc,
-                          &c->d_vdos_out})
+                          &c->d_vdos_out, &c->d_modes_work, &c->d_modes_coef, &c->d_modes_out})
             b->release();
         (void)hipStreamDestroy(c->stream);
     }
@@ -345,6 +345,10 @@ int psa_set_option(psa_ctx* c, int option, int64_t value) {
         case PSA_OPT_VDOS_WORK_BYTES:
             PSA_REQUIRE(value >= 1, "PSA_OPT_VDOS_WORK_BYTES must be >= 1");
             c->opt_vdos_work_bytes = value;
+            return PSA_OK;
+        case PSA_OPT_MODES_WORK_BYTES:
+            PSA_REQUIRE(value >= 1, "PSA_OPT_MODES_WORK_BYTES must be >= 1");
+            c->opt_modes_work_bytes = value;
             return PSA_OK;
     }
     set_error("unknown option %d", option);

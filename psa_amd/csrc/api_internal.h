@@ -5,6 +5,7 @@
 //   api_project.hip  the hot path: plane cache, geometry, projection, project / finalize / calculate, diagnostics
 //   api_shard.hip    sharding over RCCL: communicator, k-row gather, frame sharding
 //   api_vdos.hip     the vibrational density of states: a second, non-projecting pass over the resident array
+//   api_modes.hip    the mode-projected SED: the B site groups' spectra contracted with the mode vectors
 #pragma once
 #include <algorithm>
 #include <chrono>

@@ -266,6 +266,12 @@ struct psa_ctx {
     psa::DevBuf  d_vdos_work, d_vdos_pairs, d_vdos_off, d_vdos_mean, d_vdos_part, d_vdos_acc, d_vdos_out;
     int64_t      opt_vdos_work_bytes = (int64_t)1 << 30;
 
+    // mode-projected SED (psa_sed_modes, api_modes.hip): the stacked spectra (B, kb, 3, T) of one block of k-vectors, held
+    // to opt_modes_work_bytes (PSA_OPT_MODES_WORK_BYTES); the packed coefficient table conj(eig); the (T, K, M) result.
+    // All kept between calls.
+    psa::DevBuf  d_modes_work, d_modes_coef, d_modes_out;
+    int64_t      opt_modes_work_bytes = (int64_t)4 << 30;
+
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
                                           // plane builds, trajectory uploads (psa_oneoff_stats)
@@ -373,6 +379,13 @@ int launch_vdos_power(psa_ctx* c, const float2* d_work, const int64_t* d_pair_of
                       int64_t ns, int64_t n_pairs, int64_t p0, int64_t g_first, int64_t n_groups, int64_t n_chunks);
 // out (rows, L/2 + 1) float32 = scale (acc[o] + acc[(L - o) mod L])
 int launch_vdos_finish(psa_ctx* c, const double* d_acc, float* d_out, int64_t L, int64_t rows, double scale);
+// --- modes.hip (psa_sed_modes: contraction of the B groups' spectra with the mode vectors, fused with the modulus)
+int modes_tile(int64_t M);            // modes per pass (MT) of the kernel that serves M mode vectors
+// S (B, nk, 3, T) complex64 unscaled spectra of a block of nk k-vectors; coef: the block's rows of the packed table
+// [k][pass][3B][MT] complex64 = conj(eig), zero beyond M; out (T, K_pitch, M) float32, columns k_col0 .. k_col0 + nk - 1:
+// |sum_n coef S|^2 inv_n2 (inv_n2 = 1/T^2 for unscaled spectra)
+int launch_mode_power(psa_ctx* c, const float2* d_S, const float2* d_coef, float* d_out, int64_t T, int64_t nk, int64_t B,
+                      int64_t M, int MT, int64_t K_pitch, int64_t k_col0, float inv_n2);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 
