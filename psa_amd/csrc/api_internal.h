@@ -10,6 +10,8 @@
 //   api_shard.hip    sharding over RCCL: communicator, k-row gather, frame sharding
 //   api_vdos.hip     the vibrational density of states: a second, non-projecting pass over the resident array
 //   api_modes.hip    the mode-projected SED: the B site groups' spectra contracted with the mode vectors
+// What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
+// k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
 #pragma once
 #include <algorithm>
 #include <chrono>

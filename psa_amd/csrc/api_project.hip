@@ -327,7 +327,7 @@ static int launch_projection_once(psa_ctx* c, const GroupView& v, ProjGeom g, fl
     d_q += t_begin;
     if (g.split == K1Family::f16_planes) {
         PSA_REQUIRE(ps != nullptr && t_begin % 16 == 0, "planes are cut in groups of 16 frames");
-        const int64_t fg0 = t_begin / 16;
+        const int64_t fg0 = t_begin / 16, n_fg = ps->n_fg - fg0;        // frame groups from the launch's first frame on
         const _Float16* pl = ps->buf.as<_Float16>() + (size_t)fg0 * (size_t)(ps->A_pad / K1_BA) * PL_STAGE_ELEMS;
         // PSA_OPT_K1_LOADER_WAVES [1]: 128-row M blocks go to the loader-wavefront form of the kernel
         // (k1_planes_lw.hip; 2-3 % faster than the eight-wavefront form on every shape, round 3); 0 = never
@@ -338,10 +338,10 @@ static int launch_projection_once(psa_ctx* c, const GroupView& v, ProjGeom g, fl
             gn.m_blk = gn.M_pad = 2 * LOWRANK_NODES;
             gn.q_stride = t_count;
             PSA_REQUIRE(c->d_lr_qn.cap >= (size_t)LOWRANK_NODES * 3 * t_count * sizeof(float2), "node projections not reserved");
-            PSA_TRY(launch_k1_planes_lw(c, pl, c->d_phase.ptr, c->d_lr_qn.as<float2>(), gn, ps->n_fg - fg0));
+            PSA_TRY(launch_k1_planes_lw(c, pl, c->d_phase.ptr, c->d_lr_qn.as<float2>(), gn, n_fg));
             ProjGeom gd = g;
             gd.M_pad = g.M_pad_d;
-            PSA_TRY(launch_k1_planes_diff(c, pl, c->d_lr_diff.ptr, d_q, gd, ps->n_fg - fg0, g.dscale));
+            PSA_TRY(launch_k1_planes_diff(c, pl, c->d_lr_diff.ptr, d_q, gd, n_fg, g.dscale));
             if (c->k1_combine_arm == 0)
                 PSA_TRY(launch_lowrank_combine(c, c->d_lr_qn.as<float2>(), c->d_lr_C.as<float2>(), d_q, g, t_count));
             else
@@ -349,9 +349,9 @@ static int launch_projection_once(psa_ctx* c, const GroupView& v, ProjGeom g, fl
             ++c->lowrank_launches;
             return PSA_OK;
         }
-        if (g.m_blk == 256) return launch_k1_planes_wide(c, pl, c->d_phase.ptr, d_q, g, ps->n_fg - fg0);
-        if (g.m_blk == 128 && c->opt_k1_loader_waves) return launch_k1_planes_lw(c, pl, c->d_phase.ptr, d_q, g, ps->n_fg - fg0);
-        return launch_k1_planes(c, pl, c->d_phase.ptr, d_q, g, ps->n_fg - fg0);
+        if (g.m_blk == 256) return launch_k1_planes_wide(c, pl, c->d_phase.ptr, d_q, g, n_fg);
+        if (g.m_blk == 128 && c->opt_k1_loader_waves) return launch_k1_planes_lw(c, pl, c->d_phase.ptr, d_q, g, n_fg);
+        return launch_k1_planes(c, pl, c->d_phase.ptr, d_q, g, n_fg);
     }
     if (g.split == K1Family::f16_fly) return launch_k1_pair(c, d_v, c->d_phase.ptr, v.d_idx, d_q, g);
     if (g.split == K1Family::bf16) return launch_k1_split(c, d_v, c->d_phase.ptr, v.d_idx, d_q, g);

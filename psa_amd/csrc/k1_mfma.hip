@@ -44,7 +44,7 @@
 // Roofline: 12 flop per (k,t,atom); V is read once per M-block (12 B per (t,atom)).
 // At K >= ~25 k-points per device the kernel is bound by the fp32 MFMA rate
 // (157.3 TFLOP/s), below that by HBM.
-#include "psa_ctx.h"
+#include "k1_tile.h"
 
 namespace psa {
 
@@ -67,8 +67,6 @@ struct K1Cfg {
     static_assert((T_BLK * 24) % 256 == 0, "V tile must be whole wave-instructions");
 };
 
-__device__ __forceinline__ int v_phys_slot(int s, int row) { return (s & ~7) | ((s & 7) ^ (row & 7)); }
-
 // VDMA  : the group is "all atoms in order", N % 4 == 0, no displacement: the V tile is
 //         copied HBM -> LDS by LDS-DMA.
 // !VDMA : arbitrary index list (duplicates, any order), unaligned N, or displacement mode
@@ -85,13 +83,8 @@ k1_mfma_kernel(const float* __restrict__ V, const float* __restrict__ P,
     float* Vs = smem;                       // [2][T_BLK][96]   swizzled slots
     float* Ps = smem + 2 * C::V_STAGE;      // [2][M_BLK][36]
 
-    // XCD-aware block map: blocks b and b+8 share an XCD (and its L2); give them the
-    // M-blocks of one frame tile so the second read of that V tile is an L2 hit.
-    const int b  = blockIdx.x;
-    const int r8 = b >> 3;
-    const int mb = r8 % n_mblk;
-    const int tb = (r8 / n_mblk) * 8 + (b & 7);
-    if (tb >= n_tblk) return;
+    int mb, tb;                                        // M block, frame tile (k1_block_map: XCD-aware)
+    if (!k1_block_map(n_mblk, n_tblk, mb, tb)) return;
 
     const int     tid  = threadIdx.x;
     const int     lane = tid & 63;
@@ -114,7 +107,7 @@ k1_mfma_kernel(const float* __restrict__ V, const float* __restrict__ P,
             int64_t   t = t0 + row;
             if (t >= T) t = T - 1;                              // rows past the end: finite filler
             v_row[j] = t * 3 * N_tot;
-            v_s4[j] = 4 * v_phys_slot(phys, row);               // the swizzle is an involution
+            v_s4[j] = 4 * vs_phys_slot(phys, row);               // the swizzle is an involution
         }
     }
     float vx[VDMA ? 1 : C::V_ITEMS], vy[VDMA ? 1 : C::V_ITEMS], vz[VDMA ? 1 : C::V_ITEMS];
@@ -184,7 +177,7 @@ k1_mfma_kernel(const float* __restrict__ V, const float* __restrict__ P,
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const int e = 3 * al + c;                      // float index in the row
-                    vs[row * K1_VROW + 4 * v_phys_slot(e >> 2, row) + (e & 3)] = val[c];
+                    vs[row * K1_VROW + 4 * vs_phys_slot(e >> 2, row) + (e & 3)] = val[c];
                 }
             }
         }
@@ -209,7 +202,7 @@ k1_mfma_kernel(const float* __restrict__ V, const float* __restrict__ P,
         const float* vs = Vs + buf * C::V_STAGE + vrow * K1_VROW;
 #pragma unroll
         for (int j = 0; j < 3; ++j)
-            bv[j] = *reinterpret_cast<const float4*>(vs + 4 * v_phys_slot(6 * g + 3 * h + j, vrow));
+            bv[j] = *reinterpret_cast<const float4*>(vs + 4 * vs_phys_slot(6 * g + 3 * h + j, vrow));
     };
 
     auto mfma_group = [&](const float4 (&a)[MT], const float4 (&bv)[3]) {
@@ -317,12 +310,10 @@ static int launch_variant(psa_ctx* c, const float* d_v, const float* d_phase, co
                           const float* d_mean_g, float2* d_q, const ProjGeom& g) {
     using C = K1Cfg<MT, WM, WN>;
     auto kern = k1_mfma_kernel<MT, WM, WN, VDMA, DISP>;
-    const int     n_mblk = g.M_pad / C::M_BLK;
-    const int64_t n_tblk = (g.T + C::T_BLK - 1) / C::T_BLK;
-    const int64_t grid = ((n_tblk + 7) / 8) * 8 * n_mblk;
-    PSA_REQUIRE(grid < (1ll << 31) && n_tblk < (1ll << 31), "projection grid too large");
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, c->stream, d_v, d_phase,
-                       d_idx, d_mean_g, d_q, g.T, g.q_stride, g.N_tot, g.n_g, g.A_pad, g.K, n_mblk, (int)n_tblk);
+    K1Grid gr;
+    PSA_TRY(k1_grid(g, C::M_BLK, C::T_BLK, gr));
+    hipLaunchKernelGGL(kern, dim3(gr.blocks), dim3(256), 0, c->stream, d_v, d_phase,
+                       d_idx, d_mean_g, d_q, g.T, g.q_stride, g.N_tot, g.n_g, g.A_pad, g.K, gr.n_mblk, gr.n_tblk);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;
 }

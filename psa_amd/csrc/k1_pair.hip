@@ -41,7 +41,7 @@ struct K1qCfg {
     // LDS slots: stage s+1 being read, s+2 .. s+RING in flight (a fourth slot measured no gain:
     // 4.87 vs 4.84 ms on the HBM-bound 64-row variant, 18.6 vs 18.6 ms on configuration 3)
     static constexpr int RING = 3;
-    static constexpr int P_STAGE_BYTES = F16x2::NP * M_BLK * K1_BA * 2;    // 16 KiB
+    static constexpr int P_STAGE_BYTES = pf16_stage_bytes(M_BLK);          // 16 KiB
     static constexpr int P_DMA = P_STAGE_BYTES / 1024 / 8;                 // pieces per wavefront: 2 (or 1)
     // V image of a frame group.  Whole trajectory: 16 rows x 384 B in 6 pieces of 1 KiB.  Gathered:
     // 8 pieces of (2 frames x 32 atoms x 16 B) -- one (frame, atom) triple is a 12-byte LDS-DMA
@@ -76,13 +76,8 @@ k1_pair_kernel(const float* __restrict__ V, const _Float16* __restrict__ Pb, con
     __shared__ __attribute__((aligned(16))) unsigned char smem[C::LDS_BYTES];
     const unsigned lds0 = (unsigned)(size_t)(lds_u8*)smem;
 
-    // XCD-aware block map: blocks b and b+8 share an XCD (and its L2); they get the M-blocks
-    // of one frame tile, so V is fetched from HBM once per frame tile.
-    const int b  = blockIdx.x;
-    const int r8 = b >> 3;
-    const int mb = r8 % n_mblk;
-    const int tb = (r8 / n_mblk) * 8 + (b & 7);
-    if (tb >= n_tblk) return;
+    int mb, tb;                                        // M block, frame tile (k1_block_map: XCD-aware)
+    if (!k1_block_map(n_mblk, n_tblk, mb, tb)) return;
 
     const int     tid = threadIdx.x, lane = tid & 63;
     const int     w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -151,7 +146,7 @@ k1_pair_kernel(const float* __restrict__ V, const _Float16* __restrict__ Pb, con
     };
 
     // ---- LDS read addresses ---------------------------------------------------------------------
-    const int      gsw = (0x78 >> (2 * ((r16 >> 2) & 3))) & 3;     // P' slot swizzle: k1_f16.h
+    const int      gsw = pl_swizzle(r16);
     const unsigned p_lane = lds0 + (wh * (C::M_BLK / 2) + r16) * (K1_BA * 2) + ((q ^ gsw) << 4);
     const unsigned raw_lane = lds0 + C::P_STAGE_BYTES + wf * C::RAW_GROUP_BYTES +
                               (GATHER ? (r16 >> 1) * C::V_PIECE_BYTES + (r16 & 1) * 512 + q * 128 : r16 * (K1_VROW * 4));
@@ -172,6 +167,7 @@ k1_pair_kernel(const float* __restrict__ V, const _Float16* __restrict__ Pb, con
             raw[j] = *reinterpret_cast<lds_cf32x4*>((const lds_u8*)(size_t)(
                 raw_lane + slot * C::STAGE_BYTES + (GATHER ? 16 * j : 16 * vs_phys_slot(6 * q + j, r16))));
     };
+    // (zeroed in place: through a shared helper the compiler orders this kernel's instructions differently)
 #pragma unroll
     for (int mt = 0; mt < MT16; ++mt)
 #pragma unroll
@@ -248,48 +244,9 @@ k1_pair_kernel(const float* __restrict__ V, const _Float16* __restrict__ Pb, con
         // returned (the next stage's DMA overwrites the slot they read); then everyone's
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((C::RING - 2) * C::BATCH) : "memory");
     };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    int slot = 0;                                      // s % RING
-    auto next_slot = [&]() { slot = slot == C::RING - 1 ? 0 : slot + 1; };
-    for (int s = 0; s < n_stage;) {                    // n_stage is even; a chain is an even number of stages
-        const int len = n_stage - s < C::FOLD ? n_stage - s : C::FOLD;
-        stage(I0{}, std::true_type{}, s, slot);
-        next_slot();
-        stage(I1{}, std::false_type{}, s + 1, slot);
-        next_slot();
-        for (int i = 2; i < len; i += 2) {
-            stage(I0{}, std::false_type{}, s + i, slot);
-            next_slot();
-            stage(I1{}, std::false_type{}, s + i + 1, slot);
-            next_slot();
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT16; ++mt)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) lo[mt][c] += hi[mt][c];
-        s += len;
-    }
+    k1_chain_loop<C::RING, C::FOLD>(n_stage, lo, hi, stage);
 
-    // epilogue: register j of lane (r16, q) is row 4q + j, column r16 of its 16x16 tile; rows
-    // 2p, 2p+1 are the cos / sin rows of one k -> one complex64 per lane and register pair
-    const int     m0 = mb * C::M_BLK + wh * (C::M_BLK / 2);
-    const int64_t t = t0 + r16;
-    if (t < T) {
-#pragma unroll
-        for (int mt = 0; mt < MT16; ++mt) {
-#pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {
-                const int k = (m0 + mt * 16 + 4 * q + 2 * pr) >> 1;
-                if (k < K) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        Q[((int64_t)k * 3 + c) * q_stride + t] =
-                            make_float2(lo[mt][c][2 * pr] * qscale, lo[mt][c][2 * pr + 1] * qscale);
-                }
-            }
-        }
-    }
+    k1_store_q(Q, lo, wh * (C::M_BLK / 2) + mb * C::M_BLK, q, t0 + r16, T, K, q_stride, qscale);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -375,13 +332,11 @@ template <int MT16, bool GATHER>
 static int launch_pair_variant(psa_ctx* c, const float* d_v, const void* d_phase, const int* d_idx, float2* d_q,
                                const ProjGeom& g) {
     using C = K1qCfg<MT16, GATHER>;
-    const int     n_mblk = g.M_pad / C::M_BLK;
-    const int64_t n_tblk = (g.T + C::T_BLK - 1) / C::T_BLK;
-    const int64_t grid = ((n_tblk + 7) / 8) * 8 * n_mblk;
-    PSA_REQUIRE(grid < (1ll << 31) && n_tblk < (1ll << 31), "projection grid too large");
+    K1Grid gr;
+    PSA_TRY(k1_grid(g, C::M_BLK, C::T_BLK, gr));
     const float qscale = 1.f / (g.vscale * F16x2::P_SCALE) * g.wscale;   // powers of two: exact
-    hipLaunchKernelGGL((k1_pair_kernel<MT16, GATHER>), dim3((unsigned)grid), dim3(512), 0, c->stream, d_v,
-                       (const _Float16*)d_phase, d_idx, d_q, g.T, g.q_stride, g.N_tot, g.n_g, g.A_pad / K1_BA, g.K, n_mblk, (int)n_tblk,
+    hipLaunchKernelGGL((k1_pair_kernel<MT16, GATHER>), dim3(gr.blocks), dim3(512), 0, c->stream, d_v,
+                       (const _Float16*)d_phase, d_idx, d_q, g.T, g.q_stride, g.N_tot, g.n_g, g.A_pad / K1_BA, g.K, gr.n_mblk, gr.n_tblk,
                        g.vscale, qscale);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;

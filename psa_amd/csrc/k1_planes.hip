@@ -46,10 +46,10 @@ struct K1pCfg {
     static constexpr int T_BLK = 64;
     static constexpr int FOLD = 8;
     static constexpr int RING = RING_;
-    static constexpr int P_STAGE_BYTES = F16x2::NP * M_BLK * K1_BA * 2;      // 16 / 8 / 4 KiB
+    static constexpr int P_STAGE_BYTES = pf16_stage_bytes(M_BLK);            // 16 / 8 / 4 KiB
     static constexpr int P_PIECES = P_STAGE_BYTES / 1024;
     static constexpr int P_DMA = P_PIECES >= 8 ? P_PIECES / 8 : 1;           // per wavefront (4 pieces: waves 4-7 repeat 0-3)
-    static constexpr int V_GROUP_BYTES = PL_STAGE_ELEMS * 2;                 // 6 KiB
+    static constexpr int V_GROUP_BYTES = PL_STAGE_BYTES;                     // 6 KiB
     static constexpr int V_DMA = 3;
     static constexpr int STAGE_BYTES = P_STAGE_BYTES + 4 * V_GROUP_BYTES;    // 40 / 32 / 28 KiB
     static constexpr int LDS_BYTES = RING * STAGE_BYTES;
@@ -71,13 +71,8 @@ k1_planes_kernel(const _Float16* __restrict__ planes, const _Float16* __restrict
     __shared__ __attribute__((aligned(16))) unsigned char smem[C::LDS_BYTES];
     const unsigned lds0 = (unsigned)(size_t)(lds_u8*)smem;
 
-    // XCD-aware block map (k1_pair.hip): blocks b and b+8 share an XCD and get the M blocks of one
-    // frame tile, so the tile's planes come from HBM once.
-    const int b  = blockIdx.x;
-    const int r8 = b >> 3;
-    const int mb = r8 % n_mblk;
-    const int tb = (r8 / n_mblk) * 8 + (b & 7);
-    if (tb >= n_tblk) return;
+    int mb, tb;                                        // M block, 64-frame tile (k1_block_map: XCD-aware)
+    if (!k1_block_map(n_mblk, n_tblk, mb, tb)) return;
 
     const int     tid = threadIdx.x, lane = tid & 63;
     const int     w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -126,6 +121,7 @@ k1_planes_kernel(const _Float16* __restrict__ planes, const _Float16* __restrict
 #pragma unroll
         for (int i = 0; i < 3 * NP; ++i) read_b1(par, slot, i);
     };
+    // (zeroed in place: through a shared helper the compiler orders this kernel's instructions differently)
 #pragma unroll
     for (int mt = 0; mt < MT16; ++mt)
 #pragma unroll
@@ -173,6 +169,7 @@ k1_planes_kernel(const _Float16* __restrict__ planes, const _Float16* __restrict
         // own blocks of stage s+2 landed (younger batches stay in flight), own LDS reads returned
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((C::RING - 2) * C::BATCH) : "memory");
     };
+    // k1_chain_loop (k1_f16.h) written out: through the helper the 32-row variant's loop branch changes its form
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
     int  slot = 0;                                     // s % RING
@@ -199,25 +196,7 @@ k1_planes_kernel(const _Float16* __restrict__ planes, const _Float16* __restrict
     // workgroup's LDS is handed to the next one
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-    // epilogue: register j of lane (r16, q) is row 4q + j, column r16 of its 16x16 tile; rows
-    // 2p, 2p+1 are the cos / sin rows of one k -> one complex64 per lane and register pair
-    const int     m0 = mb * C::M_BLK + wh * (C::M_BLK / 2);
-    const int64_t t = t0 + r16;
-    if (t < T) {
-#pragma unroll
-        for (int mt = 0; mt < MT16; ++mt) {
-#pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {
-                const int k = (m0 + mt * 16 + 4 * q + 2 * pr) >> 1;
-                if (k < K) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        Q[((int64_t)k * 3 + c) * q_stride + t] =
-                            make_float2(lo[mt][c][2 * pr] * qscale, lo[mt][c][2 * pr + 1] * qscale);
-                }
-            }
-        }
-    }
+    k1_store_q(Q, lo, wh * (C::M_BLK / 2) + mb * C::M_BLK, q, t0 + r16, T, K, q_stride, qscale);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -326,22 +305,8 @@ int k1_planes_block_rows(int K, bool wide) {
 template <int MT16, int RING>
 static int launch_planes_variant(psa_ctx* c, const void* d_planes, const void* d_phase, float2* d_q, const ProjGeom& g,
                                  int64_t n_fg) {
-    using C = K1pCfg<MT16, RING>;
-    const int     n_mblk = g.M_pad / C::M_BLK;
-    const int64_t n_tblk = (g.T + C::T_BLK - 1) / C::T_BLK;
-    const int64_t grid = ((n_tblk + 7) / 8) * 8 * n_mblk;
-    PSA_REQUIRE(grid < (1ll << 31) && n_tblk < (1ll << 29) && n_fg < (1ll << 31), "projection grid too large");
-    const float qscale = 1.f / (g.vscale * F16x2::P_SCALE) * g.wscale;   // powers of two: exact (wscale: psa_ctx.h)
-    if (n_mblk == 1)
-        hipLaunchKernelGGL((k1_planes_kernel<MT16, RING, true>), dim3((unsigned)grid), dim3(512), 0, c->stream,
-                           (const _Float16*)d_planes, (const _Float16*)d_phase, d_q, g.T, g.q_stride, (int)n_fg,
-                           g.A_pad / K1_BA, g.K, n_mblk, (int)n_tblk, qscale);
-    else
-        hipLaunchKernelGGL((k1_planes_kernel<MT16, RING, false>), dim3((unsigned)grid), dim3(512), 0, c->stream,
-                           (const _Float16*)d_planes, (const _Float16*)d_phase, d_q, g.T, g.q_stride, (int)n_fg,
-                           g.A_pad / K1_BA, g.K, n_mblk, (int)n_tblk, qscale);
-    PSA_HIP_CHECK(hipGetLastError());
-    return PSA_OK;
+    return launch_planes_family(c, k1_planes_kernel<MT16, RING, true>, k1_planes_kernel<MT16, RING, false>, 32 * MT16, 512,
+                                "planes kernel", 2 * K1_BA, F16x2::P_SCALE, d_planes, d_phase, d_q, g, n_fg);
 }
 
 // d_planes: the group's planes from the frame group that holds the launch's first frame on
@@ -349,8 +314,6 @@ static int launch_planes_variant(psa_ctx* c, const void* d_planes, const void* d
 int launch_k1_planes(psa_ctx* c, const void* d_planes, const void* d_phase, float2* d_q, const ProjGeom& g, int64_t n_fg) {
     PSA_REQUIRE((g.m_blk == 128 || g.m_blk == 64 || g.m_blk == 32) && g.M_pad % g.m_blk == 0,
                 "planes kernel needs 32-, 64- or 128-row M blocks");
-    PSA_REQUIRE(g.A_pad % (2 * K1_BA) == 0 && g.A_pad > 0, "planes kernel needs the atom axis padded to %d", 2 * K1_BA);
-    PSA_REQUIRE(g.vscale > 0.f && n_fg * 16 >= g.T, "planes do not cover the launch");
     if (g.m_blk == 128) return launch_planes_variant<4, 3>(c, d_planes, d_phase, d_q, g, n_fg);
     if (g.m_blk == 64) return launch_planes_variant<2, 4>(c, d_planes, d_phase, d_q, g, n_fg);
     return launch_planes_variant<1, 4>(c, d_planes, d_phase, d_q, g, n_fg);

@@ -32,18 +32,8 @@ namespace {
 constexpr int D_M_BLK = 512, D_T_BLK = 64, D_MT = 16, D_PERIOD = 40;
 constexpr int D_STAGE_UNITS = 44, D_RING_UNITS = 160, D_EARLY = D_RING_UNITS - 3 * D_STAGE_UNITS;   // 28
 constexpr int D_STAGE_BYTES = D_M_BLK * K1_BA * 2;                                               // 32 KiB of D per stage
-constexpr int D_V_GROUP_BYTES = PL_STAGE_ELEMS * 2;                                              // 6 KiB
 static_assert(D_EARLY == 28 && D_RING_UNITS % 4 == 0 && D_STAGE_UNITS % 4 == 0, "ring arithmetic");
-constexpr unsigned d_unit_off(int s40, int unit) { return (unsigned)((D_STAGE_UNITS * (s40 % D_PERIOD) + unit) % D_RING_UNITS) * 1024u; }
-
-// one LDS-DMA instruction: uniform 64-bit base + per-lane offset -> LDS at wbase + OFF (+ lane * 16)
-template <unsigned OFF, bool NT>
-__device__ __forceinline__ void d_dma(const void* sbase, unsigned voff, unsigned wbase) {
-    if constexpr (NT)
-        asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(voff), "s"(sbase), "s"(wbase), "n"(OFF) : "memory", "scc");
-    else
-        asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(wbase), "n"(OFF) : "memory", "scc");
-}
+constexpr auto d_unit_off = unit_off<D_STAGE_UNITS, D_RING_UNITS, D_PERIOD>;
 }  // namespace
 
 // element (row m, atom a) of the D image: [M block of 512][atom stage][unit 2 mt + h][16 rows][32 atoms] (float16), the
@@ -65,12 +55,8 @@ k1_planes_diff_kernel(const _Float16* __restrict__ planes, const _Float16* __res
     __shared__ __attribute__((aligned(16))) unsigned char smem[D_RING_UNITS * 1024];
     const unsigned lds0 = (unsigned)(size_t)(lds_u8*)smem;
 
-    // XCD-aware block map (k1_planes.hip)
-    const int b = blockIdx.x;
-    const int r8 = b >> 3;
-    const int mb = r8 % n_mblk;
-    const int tb = (r8 / n_mblk) * 8 + (b & 7);
-    if (tb >= n_tblk) return;
+    int mb, tb;                                        // M block, 64-frame tile (k1_block_map: XCD-aware)
+    if (!k1_block_map(n_mblk, n_tblk, mb, tb)) return;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -83,7 +69,7 @@ k1_planes_diff_kernel(const _Float16* __restrict__ planes, const _Float16* __res
     {
         int fg = tb * 4 + (w & 3);                                      // frame group (past the end: the last one, never stored)
         if (fg >= n_fg) fg = n_fg - 1;
-        const unsigned char* pl0 = reinterpret_cast<const unsigned char*>(planes) + (size_t)fg * n_stage * D_V_GROUP_BYTES;
+        const unsigned char* pl0 = reinterpret_cast<const unsigned char*>(planes) + (size_t)fg * n_stage * PL_STAGE_BYTES;
 #pragma unroll
         for (int i = 0; i < 3; ++i) src[i] = pl0 + 1024 * (2 * i);      // (component i, piece 0) = block 2 i of the 6
         const unsigned char* d0 = reinterpret_cast<const unsigned char*>(Db) + (size_t)mb * n_stage * D_STAGE_BYTES;
@@ -97,10 +83,10 @@ k1_planes_diff_kernel(const _Float16* __restrict__ planes, const _Float16* __res
         constexpr int      S40 = decltype(s40_c)::value, I = decltype(i_c)::value;
         constexpr unsigned OFF = d_unit_off(S40, 4 * I);
         if constexpr (I < 3) {
-            d_dma<OFF, NT_V>(src[I], dma_voff, wbase);
-            src[I] += D_V_GROUP_BYTES;
+            lds_dma16_at<OFF, NT_V>(src[I], dma_voff, wbase);
+            src[I] += PL_STAGE_BYTES;
         } else {
-            d_dma<OFF, false>(src[I], dma_voff, wbase);
+            lds_dma16_at<OFF, false>(src[I], dma_voff, wbase);
             src[I] += D_STAGE_BYTES;
         }
     };
@@ -118,15 +104,8 @@ k1_planes_diff_kernel(const _Float16* __restrict__ planes, const _Float16* __res
     // ---- fragment reads: every unit is 16 rows (frames) x 64 bytes, lane (r16, q) takes 16 bytes ----------
     const unsigned lane_off = lds0 + r16 * (K1_BA * 2) + ((q ^ pl_swizzle(r16)) << 4);
     unsigned       lane_a[3], lane_b[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        lane_a[i] = lane_off + 1024 * wh + 65536 * i;                 // D unit 12 + 2 mt + h: 1024 h past unit 12 + 2 mt (even)
-        lane_b[i] = lane_off + 1024 * wf + 65536 * i;                 // plane unit 4 c + f
-        asm volatile("" : "+v"(lane_a[i]), "+v"(lane_b[i]));
-    }
-    auto lds_frag = [&](const unsigned (&base)[3], unsigned off) __attribute__((always_inline)) {
-        return *reinterpret_cast<lds_cv8*>((const lds_u8*)(size_t)(base[off >> 16] + (off & 0xFFFFu)));
-    };
+    // D unit 12 + 2 mt + h: 1024 h past unit 12 + 2 mt (even); plane unit 4 c + f
+    unit_ring_windows(lane_off + 1024 * wh, lane_off + 1024 * wf, lane_a, lane_b);
     E8    a[4];                                    // A fragments of row tiles mt .. mt+3 (mod 4), read two ahead
     E8    bf[3];                                   // hi B fragments of the stage in work
     f32x4 acc[D_MT][3];
@@ -138,6 +117,7 @@ k1_planes_diff_kernel(const _Float16* __restrict__ planes, const _Float16* __res
         constexpr int S40 = decltype(s40_c)::value, CC = decltype(c_c)::value;
         bf[CC] = lds_frag(lane_b, d_unit_off(S40, 4 * CC));
     };
+    // (zeroed in place: through a shared helper the compiler orders this kernel's instructions differently)
 #pragma unroll
     for (int mt = 0; mt < D_MT; ++mt)
 #pragma unroll
@@ -198,46 +178,19 @@ k1_planes_diff_kernel(const _Float16* __restrict__ planes, const _Float16* __res
             std::make_integer_sequence<int, D_PERIOD>{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // nothing in flight when LDS is handed on
 
-    // ---- epilogue (k1_planes.hip): register j of lane (r16, q) is row 4q + j, column r16 of its 16x16 tile ----
-    const int     lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const int     r16_e = lane_e & 15, q_e = lane_e >> 4;
-    const int     m0 = mb * D_M_BLK + wh * (D_M_BLK / 2);
-    const int64_t t = (int64_t)tb * D_T_BLK + wf * 16 + r16_e;
-    if (t < T) {
-#pragma unroll
-        for (int mt = 0; mt < D_MT; ++mt) {
-#pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {
-                const int k = (m0 + mt * 16 + 4 * q_e + 2 * pr) >> 1;
-                if (k < K) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        Q[((int64_t)k * 3 + c) * q_stride + t] = make_float2(acc[mt][c][2 * pr] * qscale, acc[mt][c][2 * pr + 1] * qscale);
-                }
-            }
-        }
-    }
+    // ---- epilogue: the lane's coordinates are taken afresh (not carried through the loop: k1_planes_wide.hip)
+    const int lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int r16_e = lane_e & 15, q_e = lane_e >> 4;
+    k1_store_q(Q, acc, wh * (D_M_BLK / 2) + mb * D_M_BLK, q_e, (int64_t)tb * D_T_BLK + wf * 16 + r16_e, T, K, q_stride, qscale);
 }
 
 // d_planes: the group's planes from its first frame group on; d_diff: the D image (pd16_index), g.M_pad rows; dscale: the
 // power of two the image was multiplied by
 int launch_k1_planes_diff(psa_ctx* c, const void* d_planes, const void* d_diff, float2* d_q, const ProjGeom& g, int64_t n_fg, float dscale) {
     PSA_REQUIRE(g.M_pad % D_M_BLK == 0 && g.M_pad >= 2 * g.K && g.M_pad > 0, "D pass: 512-row M blocks only");
-    PSA_REQUIRE(g.A_pad % K1_BA == 0 && g.A_pad > 0, "D pass needs the atom axis padded to %d", K1_BA);
-    PSA_REQUIRE(g.vscale > 0.f && dscale > 0.f && n_fg * 16 >= g.T, "planes do not cover the launch");
-    const int     n_mblk = g.M_pad / D_M_BLK;
-    const int64_t n_tblk = (g.T + D_T_BLK - 1) / D_T_BLK;
-    const int64_t grid = ((n_tblk + 7) / 8) * 8 * n_mblk;
-    PSA_REQUIRE(grid < (1ll << 31) && n_tblk < (1ll << 29) && n_fg < (1ll << 31), "projection grid too large");
-    const float qscale = 1.f / (g.vscale * dscale) * g.wscale;           // powers of two: exact (wscale: psa_ctx.h)
-    if (n_mblk == 1)
-        hipLaunchKernelGGL((k1_planes_diff_kernel<true>), dim3((unsigned)grid), dim3(512), 0, c->stream, (const _Float16*)d_planes,
-                           (const _Float16*)d_diff, d_q, g.T, g.q_stride, (int)n_fg, g.A_pad / K1_BA, g.K, n_mblk, (int)n_tblk, qscale);
-    else
-        hipLaunchKernelGGL((k1_planes_diff_kernel<false>), dim3((unsigned)grid), dim3(512), 0, c->stream, (const _Float16*)d_planes,
-                           (const _Float16*)d_diff, d_q, g.T, g.q_stride, (int)n_fg, g.A_pad / K1_BA, g.K, n_mblk, (int)n_tblk, qscale);
-    PSA_HIP_CHECK(hipGetLastError());
-    return PSA_OK;
+    PSA_REQUIRE(dscale > 0.f, "planes do not cover the launch");
+    return launch_planes_family(c, k1_planes_diff_kernel<true>, k1_planes_diff_kernel<false>, D_M_BLK, 512, "D pass", K1_BA, dscale,
+                                d_planes, d_diff, d_q, g, n_fg);
 }
 
 // ---------------------------------------------------------------------------------------------

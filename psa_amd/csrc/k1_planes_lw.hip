@@ -35,20 +35,16 @@ k1_planes_lw_kernel(const _Float16* __restrict__ planes, const _Float16* __restr
     using PR = F16x2;
     using E8 = PR::v8;
     constexpr int NP = PR::NP, MT16 = 4, M_BLK = 128, T_BLK = 64, FOLD = 8, RING = 4;
-    constexpr int P_STAGE_BYTES = NP * M_BLK * K1_BA * 2;                   // 16 KiB
-    constexpr int V_GROUP_BYTES = PL_STAGE_ELEMS * 2;                       // 6 KiB
+    constexpr int P_STAGE_BYTES = pf16_stage_bytes(M_BLK);                  // 16 KiB
+    constexpr int V_GROUP_BYTES = PL_STAGE_BYTES;                           // 6 KiB
     constexpr int STAGE_BYTES = P_STAGE_BYTES + 4 * V_GROUP_BYTES;          // 40 KiB
     constexpr int BATCH = 10;                                               // LDS-DMA instructions per loader and stage
     static_assert(RING * STAGE_BYTES == 160 * 1024, "the ring is all of LDS");
     __shared__ __attribute__((aligned(16))) unsigned char smem[RING * STAGE_BYTES];
     const unsigned lds0 = (unsigned)(size_t)(lds_u8*)smem;
 
-    // XCD-aware block map (k1_planes.hip): blocks b and b+8 share an XCD and get the M blocks of one frame tile
-    const int b = blockIdx.x;
-    const int r8 = b >> 3;
-    const int mb = r8 % n_mblk;
-    const int tb = (r8 / n_mblk) * 8 + (b & 7);
-    if (tb >= n_tblk) return;
+    int mb, tb;                                        // M block, 64-frame tile (k1_block_map: XCD-aware)
+    if (!k1_block_map(n_mblk, n_tblk, mb, tb)) return;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -62,7 +58,7 @@ k1_planes_lw_kernel(const _Float16* __restrict__ planes, const _Float16* __restr
         const unsigned char* v_next = reinterpret_cast<const unsigned char*>(planes) + (size_t)fg * n_stage * V_GROUP_BYTES;
         const unsigned       p_voff = 4096 * j + 16 * lane, v_voff = 16 * lane;
         // stages past the end are fetched from the bytes that follow (next M block / frame group, or the
-        // padding behind the buffers) and never read -- as in k1_planes.hip
+        // padding behind the buffers) and never read -- as in k1_planes_kernel
         auto dma_stage = [&](int slot) {
             const unsigned dst = lds0 + slot * STAGE_BYTES;
             lds_dma16_group<4>(p_next, p_voff, dst + 4096 * j);
@@ -109,6 +105,7 @@ k1_planes_lw_kernel(const _Float16* __restrict__ planes, const _Float16* __restr
         for (int p = 0; p < NP; ++p)
             bb[buf][p] = *reinterpret_cast<lds_cv8*>((const lds_u8*)(size_t)(v_lane + slot * STAGE_BYTES + (c * NP + p) * 1024));
     };
+    // (zeroed in place: through a shared helper the compiler orders this kernel's instructions differently)
 #pragma unroll
     for (int mt = 0; mt < MT16; ++mt)
 #pragma unroll
@@ -125,7 +122,7 @@ k1_planes_lw_kernel(const _Float16* __restrict__ planes, const _Float16* __restr
 
     // One stage: A of stage s and B (component 0) of stage s are in registers, in bb[par]; slot holds the
     // stage's other B fragments, slot1 stage s + 1.
-    auto stage = [&](auto par_c, auto restart_c, int slot) {
+    auto stage = [&](auto par_c, auto restart_c, int, int slot) {
         constexpr int  par = decltype(par_c)::value;        // buffer of component 0; the components alternate from there
         constexpr bool restart = decltype(restart_c)::value;
         const int      slot1 = slot == RING - 1 ? 0 : slot + 1;
@@ -152,69 +149,17 @@ k1_planes_lw_kernel(const _Float16* __restrict__ planes, const _Float16* __restr
         // once and has to wait here.)
         asm volatile("s_barrier" ::: "memory");
     };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    int  slot = 0;
-    auto next_slot = [&]() { slot = slot == RING - 1 ? 0 : slot + 1; };
-    for (int s = 0; s < n_stage;) {                    // n_stage is even; three components per stage flip the buffer parity
-        const int len = n_stage - s < FOLD ? n_stage - s : FOLD;
-        stage(I0{}, std::true_type{}, slot);
-        next_slot();
-        stage(I1{}, std::false_type{}, slot);
-        next_slot();
-        for (int i = 2; i < len; i += 2) {
-            stage(I0{}, std::false_type{}, slot);
-            next_slot();
-            stage(I1{}, std::false_type{}, slot);
-            next_slot();
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT16; ++mt)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) lo[mt][c] += hi[mt][c];
-        s += len;
-    }
+    // (three components per stage flip the buffer parity)
+    k1_chain_loop<RING, FOLD>(n_stage, lo, hi, stage);
 
-    // epilogue (k1_planes.hip): register j of lane (r16, q) is row 4q + j, column r16 of its 16x16 tile
-    const int     m0 = mb * M_BLK + wh * (M_BLK / 2);
-    const int64_t t = t0 + r16;
-    if (t < T) {
-#pragma unroll
-        for (int mt = 0; mt < MT16; ++mt) {
-#pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {
-                const int k = (m0 + mt * 16 + 4 * q + 2 * pr) >> 1;
-                if (k < K) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        Q[((int64_t)k * 3 + c) * q_stride + t] =
-                            make_float2(lo[mt][c][2 * pr] * qscale, lo[mt][c][2 * pr + 1] * qscale);
-                }
-            }
-        }
-    }
+    k1_store_q(Q, lo, wh * (M_BLK / 2) + mb * M_BLK, q, t0 + r16, T, K, q_stride, qscale);
 }
 
 // the 128-row shapes of launch_k1_planes (k1_planes.hip)
 int launch_k1_planes_lw(psa_ctx* c, const void* d_planes, const void* d_phase, float2* d_q, const ProjGeom& g, int64_t n_fg) {
     PSA_REQUIRE(g.m_blk == 128 && g.M_pad % 128 == 0, "loader-wave planes kernel: 128-row M blocks only");
-    PSA_REQUIRE(g.A_pad % (2 * K1_BA) == 0 && g.A_pad > 0, "planes kernel needs the atom axis padded to %d", 2 * K1_BA);
-    PSA_REQUIRE(g.vscale > 0.f && n_fg * 16 >= g.T, "planes do not cover the launch");
-    const int     n_mblk = g.M_pad / 128;
-    const int64_t n_tblk = (g.T + 63) / 64;
-    const int64_t grid = ((n_tblk + 7) / 8) * 8 * n_mblk;
-    PSA_REQUIRE(grid < (1ll << 31) && n_tblk < (1ll << 29) && n_fg < (1ll << 31), "projection grid too large");
-    const float qscale = 1.f / (g.vscale * F16x2::P_SCALE) * g.wscale;   // powers of two: exact (wscale: psa_ctx.h)
-    if (n_mblk == 1)        // (nt with several M blocks: the siblings start to miss -- 38.7 GB fetched instead of 34.4, +2 % time)
-        hipLaunchKernelGGL((k1_planes_lw_kernel<true>), dim3((unsigned)grid), dim3(768), 0, c->stream, (const _Float16*)d_planes,
-                           (const _Float16*)d_phase, d_q, g.T, g.q_stride, (int)n_fg, g.A_pad / K1_BA, g.K, n_mblk, (int)n_tblk,
-                           qscale);
-    else
-        hipLaunchKernelGGL((k1_planes_lw_kernel<false>), dim3((unsigned)grid), dim3(768), 0, c->stream, (const _Float16*)d_planes,
-                           (const _Float16*)d_phase, d_q, g.T, g.q_stride, (int)n_fg, g.A_pad / K1_BA, g.K, n_mblk, (int)n_tblk,
-                           qscale);
-    PSA_HIP_CHECK(hipGetLastError());
-    return PSA_OK;
+    return launch_planes_family(c, k1_planes_lw_kernel<true>, k1_planes_lw_kernel<false>, 128, 768, "planes kernel", 2 * K1_BA,
+                                F16x2::P_SCALE, d_planes, d_phase, d_q, g, n_fg);
 }
 
 }  // namespace psa

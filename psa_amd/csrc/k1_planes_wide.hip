@@ -56,19 +56,9 @@ namespace psa {
 namespace {
 constexpr int W_M_BLK = 256, W_T_BLK = 64, W_FOLD = 10, W_PERIOD = 20;
 constexpr int W_STAGE_UNITS = 56, W_RING_UNITS = 160;
-constexpr int W_P_STAGE_BYTES = F16x2::NP * W_M_BLK * K1_BA * 2;        // 32 KiB
-constexpr int W_V_GROUP_BYTES = PL_STAGE_ELEMS * 2;                     // 6 KiB
+constexpr int W_P_STAGE_BYTES = pf16_stage_bytes(W_M_BLK);              // 32 KiB
 // byte offset in LDS of unit `unit` of a stage whose number is s20 (mod 20)
-constexpr unsigned w_unit_off(int s20, int unit) { return (unsigned)((W_STAGE_UNITS * (s20 % W_PERIOD) + unit) % W_RING_UNITS) * 1024u; }
-
-// one LDS-DMA instruction: uniform 64-bit base + per-lane offset -> LDS at wbase + OFF (+ lane * 16)
-template <unsigned OFF, bool NT>
-__device__ __forceinline__ void w_dma(const void* sbase, unsigned voff, unsigned wbase) {
-    if constexpr (NT)
-        asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(voff), "s"(sbase), "s"(wbase), "n"(OFF) : "memory", "scc");
-    else
-        asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(wbase), "n"(OFF) : "memory", "scc");
-}
+constexpr auto w_unit_off = unit_off<W_STAGE_UNITS, W_RING_UNITS, W_PERIOD>;
 }  // namespace
 
 template <bool NT_V>
@@ -81,12 +71,8 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
     __shared__ __attribute__((aligned(16))) unsigned char smem[W_RING_UNITS * 1024];
     const unsigned lds0 = (unsigned)(size_t)(lds_u8*)smem;
 
-    // XCD-aware block map (k1_planes.hip): blocks b and b+8 share an XCD and get the M blocks of one frame tile
-    const int b = blockIdx.x;
-    const int r8 = b >> 3;
-    const int mb = r8 % n_mblk;
-    const int tb = (r8 / n_mblk) * 8 + (b & 7);
-    if (tb >= n_tblk) return;
+    int mb, tb;                                        // M block, 64-frame tile (k1_block_map: XCD-aware)
+    if (!k1_block_map(n_mblk, n_tblk, mb, tb)) return;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -100,7 +86,7 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
     if (fg >= n_fg) fg = n_fg - 1;
 #pragma unroll
     for (int k = 0; k < 3; ++k)                                         // unit 8 k + w = component k, piece wh, frame group wf
-        src[k] = pl0 + (size_t)fg * n_stage * W_V_GROUP_BYTES + 1024 * (2 * k + wh);
+        src[k] = pl0 + (size_t)fg * n_stage * PL_STAGE_BYTES + 1024 * (2 * k + wh);
     const unsigned char* ph0 = reinterpret_cast<const unsigned char*>(Pb) + (size_t)mb * n_stage * W_P_STAGE_BYTES;
 #pragma unroll
     for (int k = 3; k < 7; ++k) {
@@ -110,7 +96,7 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
     // the SIMD partner's streams (waves 0-3 issue them too): units 8 k + w + 4 -- piece 1 of the same planes, the other half's row tiles
     const unsigned char* src2[7];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) src2[k] = pl0 + (size_t)fg * n_stage * W_V_GROUP_BYTES + 1024 * (2 * k + 1);
+    for (int k = 0; k < 3; ++k) src2[k] = pl0 + (size_t)fg * n_stage * PL_STAGE_BYTES + 1024 * (2 * k + 1);
 #pragma unroll
     for (int k = 3; k < 7; ++k) {
         const int y = 8 * (k - 3) + w + 4, mt = y >> 2, h = (y >> 1) & 1, p = y & 1;
@@ -126,15 +112,15 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
         if constexpr (KK < 3) {
             // stages past the group's last one (the loop runs whole periods of 20) multiply zeros: their
             // planes come from a block of zeros, their phase tile is whatever follows (finite float16)
-            w_dma<OFF, NT_V>(to_issue > 0 ? src[KK] : reinterpret_cast<const unsigned char*>(zeros), dma_voff, wbase);
-            src[KK] += W_V_GROUP_BYTES;
-            w_dma<OFF + 4096, NT_V>(to_issue > 0 ? src2[KK] : reinterpret_cast<const unsigned char*>(zeros), dma_voff, wbase);
-            src2[KK] += W_V_GROUP_BYTES;
+            lds_dma16_at<OFF, NT_V>(to_issue > 0 ? src[KK] : reinterpret_cast<const unsigned char*>(zeros), dma_voff, wbase);
+            src[KK] += PL_STAGE_BYTES;
+            lds_dma16_at<OFF + 4096, NT_V>(to_issue > 0 ? src2[KK] : reinterpret_cast<const unsigned char*>(zeros), dma_voff, wbase);
+            src2[KK] += PL_STAGE_BYTES;
             if constexpr (KK == 2) --to_issue;
         } else {
-            w_dma<OFF, false>(src[KK], dma_voff, wbase);
+            lds_dma16_at<OFF, false>(src[KK], dma_voff, wbase);
             src[KK] += W_P_STAGE_BYTES;
-            w_dma<OFF + 4096, false>(src2[KK], dma_voff, wbase);
+            lds_dma16_at<OFF + 4096, false>(src2[KK], dma_voff, wbase);
             src2[KK] += W_P_STAGE_BYTES;
         }
     };
@@ -145,18 +131,8 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
 
     // ---- fragment reads: every unit is 16 rows (frames) x 64 bytes, lane (r16, q) takes 16 bytes ----------
     const unsigned lane_off = lds0 + r16 * (K1_BA * 2) + ((q ^ pl_swizzle(r16)) << 4);
-    // ds_read offsets reach 64 KiB: one base register per 64-KiB window of the ring and operand, opaque to the
-    // optimizer (left to itself it forms a new base for almost every constant and spills them)
     unsigned lane_a[3], lane_b[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        lane_a[i] = lane_off + 2048 * wh + 65536 * i;
-        lane_b[i] = lane_off + 1024 * wf + 65536 * i;
-        asm volatile("" : "+v"(lane_a[i]), "+v"(lane_b[i]));
-    }
-    auto lds_frag = [&](const unsigned (&base)[3], unsigned off) __attribute__((always_inline)) {
-        return *reinterpret_cast<lds_cv8*>((const lds_u8*)(size_t)(base[off >> 16] + (off & 0xFFFFu)));
-    };
+    unit_ring_windows(lane_off + 2048 * wh, lane_off + 1024 * wf, lane_a, lane_b);
     E8    a[2][NP];                                // A fragments: row tile in work / the next one
     E8    bf[3][NP];                               // B fragments of the stage in work
     f32x4 hi[MT][3], lo[MT][3];
@@ -172,6 +148,7 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
         for (int p = 0; p < NP; ++p)
             bf[CC][p] = lds_frag(lane_b, w_unit_off(S20, 8 * CC) + 4096 * p);
     };
+    // (zeroed in place: through a shared helper the compiler orders this kernel's instructions differently)
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -179,12 +156,6 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
             hi[mt][c] = f32x4{0.f, 0.f, 0.f, 0.f};
             lo[mt][c] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-    auto fold = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) lo[mt][c] += hi[mt][c];
-    };
 
     // ---- prologue: stage 0 (k = 0..6) and stage 1 (k = 0..5) ----------------------------------------------
     using I0 = integral_constant<int, 0>;
@@ -231,8 +202,8 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
             __builtin_amdgcn_sched_barrier(0);     // 232 registers are live by design: nothing moves across a row tile
         };
         [&]<int... Ms>(std::integer_sequence<int, Ms...>) __attribute__((always_inline)) { (tile(integral_constant<int, Ms>{}), ...); }(std::make_integer_sequence<int, MT>{});
-        if constexpr (folds) fold();
-        else if (left == S20 + 1) fold();                                 // the last stage of the group
+        if constexpr (folds) k1_fold(lo, hi);
+        else if (left == S20 + 1) k1_fold(lo, hi);                                 // the last stage of the group
         // What this stage read from its own units has been consumed by the MFMAs above (it has returned); the
         // reads still in flight come from stage s+1's units, which nothing overwrites before barrier s+1.
         asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(PENDING) : "memory");
@@ -242,52 +213,20 @@ k1_planes_wide_kernel(const _Float16* __restrict__ planes, const _Float16* __res
             std::make_integer_sequence<int, W_PERIOD>{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // nothing in flight when LDS is handed on
 
-    // ---- epilogue (k1_planes.hip): register j of lane (r16, q) is row 4q + j, column r16 of its 16x16 tile ----
-    // (the lane's coordinates are taken afresh: carried through the loop they are two more live registers there)
-    const int     lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const int     r16_e = lane_e & 15, q_e = lane_e >> 4;
-    const int     m0 = mb * W_M_BLK + wh * (W_M_BLK / 2);
-    const int64_t t = (int64_t)tb * W_T_BLK + wf * 16 + r16_e;
-    if (t < T) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {
-                const int k = (m0 + mt * 16 + 4 * q_e + 2 * pr) >> 1;
-                if (k < K) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        Q[((int64_t)k * 3 + c) * q_stride + t] =
-                            make_float2(lo[mt][c][2 * pr] * qscale, lo[mt][c][2 * pr + 1] * qscale);
-                }
-            }
-        }
-    }
+    // ---- epilogue: the lane's coordinates are taken afresh (carried through the loop they are two more live registers there)
+    const int lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int r16_e = lane_e & 15, q_e = lane_e >> 4;
+    k1_store_q(Q, lo, wh * (W_M_BLK / 2) + mb * W_M_BLK, q_e, (int64_t)tb * W_T_BLK + wf * 16 + r16_e, T, K, q_stride, qscale);
 }
 
 int launch_k1_planes_wide(psa_ctx* c, const void* d_planes, const void* d_phase, float2* d_q, const ProjGeom& g, int64_t n_fg) {
     PSA_REQUIRE(g.m_blk == W_M_BLK && g.M_pad % W_M_BLK == 0, "wide planes kernel: 256-row M blocks only");
-    PSA_REQUIRE(g.A_pad % (2 * K1_BA) == 0 && g.A_pad > 0, "planes kernel needs the atom axis padded to %d", 2 * K1_BA);
-    PSA_REQUIRE(g.vscale > 0.f && n_fg * 16 >= g.T, "planes do not cover the launch");
-    const int     n_mblk = g.M_pad / W_M_BLK;
-    const int64_t n_tblk = (g.T + W_T_BLK - 1) / W_T_BLK;
-    const int64_t grid = ((n_tblk + 7) / 8) * 8 * n_mblk;
-    PSA_REQUIRE(grid < (1ll << 31) && n_tblk < (1ll << 29) && n_fg < (1ll << 31), "projection grid too large");
-    const float qscale = 1.f / (g.vscale * F16x2::P_SCALE) * g.wscale;   // powers of two: exact (wscale: psa_ctx.h)
     if (!c->d_zeros.ptr) {
         PSA_TRY(c->d_zeros.reserve(1024));
         PSA_HIP_CHECK(hipMemsetAsync(c->d_zeros.ptr, 0, 1024, c->stream));
     }
-    if (n_mblk == 1)
-        hipLaunchKernelGGL((k1_planes_wide_kernel<true>), dim3((unsigned)grid), dim3(512), 0, c->stream, (const _Float16*)d_planes,
-                           (const _Float16*)d_phase, c->d_zeros.ptr, d_q, g.T, g.q_stride, (int)n_fg, g.A_pad / K1_BA, g.K, n_mblk,
-                           (int)n_tblk, qscale);
-    else
-        hipLaunchKernelGGL((k1_planes_wide_kernel<false>), dim3((unsigned)grid), dim3(512), 0, c->stream, (const _Float16*)d_planes,
-                           (const _Float16*)d_phase, c->d_zeros.ptr, d_q, g.T, g.q_stride, (int)n_fg, g.A_pad / K1_BA, g.K, n_mblk,
-                           (int)n_tblk, qscale);
-    PSA_HIP_CHECK(hipGetLastError());
-    return PSA_OK;
+    return launch_planes_family(c, k1_planes_wide_kernel<true>, k1_planes_wide_kernel<false>, W_M_BLK, 512, "planes kernel",
+                                2 * K1_BA, F16x2::P_SCALE, d_planes, d_phase, d_q, g, n_fg, (const void*)c->d_zeros.ptr);
 }
 
 }  // namespace psa

@@ -37,12 +37,10 @@
 //    clock on it (MI355X_MICROARCH.md, DVFS give-back item 7; measured here +5 %).
 #include <type_traits>
 
-#include "psa_ctx.h"
+#include "k1_tile.h"
 
 namespace psa {
 
-typedef float  f32x4 __attribute__((ext_vector_type(4)));
-typedef float  f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -76,8 +74,6 @@ struct K1sCfg {
     static_assert(P_CHUNKS % 64 == 0, "P' tile must be whole wave-instructions");
     static_assert(WG_PER_CU * LDS_BYTES <= 160 * 1024, "LDS budget");
 };
-
-__device__ __forceinline__ int vs_phys_slot(int s, int row) { return (s & ~7) | ((s & 7) ^ (row & 7)); }
 
 // One 16-byte LDS read at a byte address (+ compile-time offset).  hipcc (ROCm 7.2) puts
 // s_waitcnt vmcnt(0) in front of every ds_read it can see while an LDS-DMA is in flight (it cannot
@@ -139,13 +135,8 @@ k1_split_kernel(const float* __restrict__ V, const __bf16* __restrict__ Pb, cons
     __shared__ __attribute__((aligned(16))) unsigned char smem[C::LDS_BYTES];
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
 
-    // XCD-aware block map: blocks b and b+8 share an XCD (and its L2); they get the M-blocks
-    // of one frame tile, so V is fetched from HBM once per frame tile.
-    const int b  = blockIdx.x;
-    const int r8 = b >> 3;
-    const int mb = r8 % n_mblk;
-    const int tb = (r8 / n_mblk) * 8 + (b & 7);
-    if (tb >= n_tblk) return;
+    int mb, tb;                                        // M block, frame tile (k1_block_map: XCD-aware)
+    if (!k1_block_map(n_mblk, n_tblk, mb, tb)) return;
 
     const int     tid = threadIdx.x, lane = tid & 63;
     const int     wn = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: DMA targets in SGPRs
@@ -247,8 +238,7 @@ k1_split_kernel(const float* __restrict__ V, const __bf16* __restrict__ Pb, cons
             lo[mt][c] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
 
-    // P' slot swizzle: slot q of row r is stored at q ^ g((r>>2)&3), g = {0,2,3,1} packed two bits
-    // each = 0x78 (makes the four 16-lane ds_read_b128 groups of the A fragment conflict-free)
+    // P' slot swizzle = pl_swizzle(r16), spelled out: through the call the gather variants compile to other instructions
     const int      gsw = (0x78 >> (2 * ((r16 >> 2) & 3))) & 3;
     // this lane's frame row (gathered: its 8-atom group too) in the wavefront's V tile
     const unsigned v_lane = lds0 + wn * C::V_WAVE_BYTES +
@@ -464,7 +454,7 @@ k1_split_kernel(const float* __restrict__ V, const __bf16* __restrict__ Pb, cons
 __host__ __device__ inline size_t pb_tile_index(int piece, int m, int a, int m_blk, int n_stage) {
     const int    row = m % m_blk, al = a % K1_BA;
     const size_t tile = ((size_t)(m / m_blk) * n_stage + a / K1_BA) * (3 * (size_t)m_blk * K1_BA);
-    const int    sw = (0x78 >> (2 * ((row >> 2) & 3))) & 3;           // g = {0,2,3,1}
+    const int    sw = pl_swizzle(row);
     return tile + ((size_t)piece * m_blk + row) * K1_BA + (((al >> 3) ^ sw) << 3) + (al & 7);
 }
 
@@ -518,19 +508,12 @@ template <int MT16>
 static int launch_split_variant(psa_ctx* c, const float* d_v, const void* d_phase, const int* d_idx,
                                 float2* d_q, const ProjGeom& g) {
     using C = K1sCfg<MT16, false>;
-    const int     n_mblk = g.M_pad / C::M_BLK;
-    const int64_t n_tblk = (g.T + C::T_BLK - 1) / C::T_BLK;
-    const int64_t grid = ((n_tblk + 7) / 8) * 8 * n_mblk;
-    PSA_REQUIRE(grid < (1ll << 31) && n_tblk < (1ll << 31), "projection grid too large");
+    K1Grid gr;
+    PSA_TRY(k1_grid(g, C::M_BLK, C::T_BLK, gr));
     const bool contiguous = d_idx == nullptr && g.N_tot % 4 == 0 && g.n_g == g.N_tot;
-    if (contiguous)
-        hipLaunchKernelGGL((k1_split_kernel<MT16, false>), dim3((unsigned)grid), dim3(256), 0, c->stream, d_v,
-                           (const __bf16*)d_phase, d_idx, d_q, g.T, g.q_stride, g.N_tot, g.n_g, g.A_pad, g.K, n_mblk,
-                           (int)n_tblk);
-    else
-        hipLaunchKernelGGL((k1_split_kernel<MT16, true>), dim3((unsigned)grid), dim3(256), 0, c->stream, d_v,
-                           (const __bf16*)d_phase, d_idx, d_q, g.T, g.q_stride, g.N_tot, g.n_g, g.A_pad, g.K, n_mblk,
-                           (int)n_tblk);
+    hipLaunchKernelGGL((contiguous ? k1_split_kernel<MT16, false> : k1_split_kernel<MT16, true>), dim3(gr.blocks), dim3(256),
+                       0, c->stream, d_v, (const __bf16*)d_phase, d_idx, d_q, g.T, g.q_stride, g.N_tot, g.n_g, g.A_pad, g.K,
+                       gr.n_mblk, gr.n_tblk);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;
 }

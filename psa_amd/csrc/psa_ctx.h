@@ -303,6 +303,8 @@ int launch_subtract_mean(psa_ctx* c, const float* d_x, const float* d_mean, floa
 int launch_absmax_bits(psa_ctx* c, const float* d_x, int64_t n, unsigned* d_out, bool reset = true);
 int launch_absmax_blocks(psa_ctx* c, const float* d_x, const float* d_mean, int64_t T, int64_t N, unsigned* d_out);
 
+// K1 launchers.  The block map and its grid are in k1_tile.h, the parts of the "2 x f16" kernels and the launch of
+// the planes family in k1_f16.h.
 // --- k1_mfma.hip / k1_wave.hip
 int  k1_mfma_block_rows(int K);                    // M block of the variant chosen for K
 int  launch_k1_mfma(psa_ctx* c, const float* d_v, const float* d_phase, const int* d_idx,

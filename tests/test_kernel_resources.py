@@ -22,7 +22,8 @@ def _flags():
     return [f.replace("$(ARCH)", "gfx950").replace("$(ROOT)", str(ROOT)) for f in raw if not f.startswith("-W")]
 
 
-@pytest.mark.parametrize("source, max_vgprs", [("k1_planes_wide.hip", 256), ("k1_planes_lw.hip", 168)])
+@pytest.mark.parametrize("source, max_vgprs", [("k1_planes_wide.hip", 256), ("k1_planes_lw.hip", 168), ("k1_planes_diff.hip", 256),
+                                               ("k1_planes.hip", 256)])
 def test_counted_vmcnt_kernels_use_no_scratch(source, max_vgprs, tmp_path):
     if not Path(HIPCC).exists():
         pytest.skip("no hipcc")
