@@ -358,10 +358,11 @@ int psa_sed_set_kmap(psa_ctx* ctx, const int32_t* kmap, int64_t K_out);
 
 /* The low-rank plan of a k-list for one atom group (api_lowrank.hip) as a host-only service for tests:
  * *ok = 1 when the route serves; geo[12] = u (3), k0 (3), x_c, h_x, interval width, interval id, bound on
- * |D|, scale of D; kappa[64] the nodes, C[K * 64 * 2] the complex64 combine matrix (either may be null).
+ * |D|, scale of D; kappa[64] the nodes, C[K * 64 * 2] the complex64 combine matrix, L[K * 64] its real factor
+ * (the Lagrange weights) and phi[K * 2] its complex64 phase factor, C[j, l] = phi[j] L[j, l] (any may be null).
  * No context, no GPU. */
 int psa_lowrank_plan(const float* k_vectors, int64_t K, const float* mean_pos_all, int64_t N, const int32_t* idx,
-                     int64_t n_g, int32_t* ok, double* geo, double* kappa, float* C);
+                     int64_t n_g, int32_t* ok, double* geo, double* kappa, float* C, float* L, float* phi);
 
 /* One (k, omega) bin: S[c] = FFT_t(q)[i_w] / T for ONE k-vector and one atom group, as 3
  * complex64 -- what iSED consumes of a group's spectrum (sed_calculator.py:483, :494-499: only

@@ -75,7 +75,7 @@ SIGNATURES = {
                                 C.c_int32, _f32p, C.c_size_t]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
-                                   C.POINTER(C.c_double), _f32p]),
+                                   C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
     "psa_sed_set_kmap": (C.c_int, [_ctx, _i32p, C.c_int64]),
     "psa_sed_single_bin": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, _i32p, C.c_int64, C.c_int32, C.c_int64, _f32p]),
     "psa_slab_read": (C.c_int, [_ctx, C.c_int64, C.c_int64, C.c_void_p]),
@@ -179,7 +179,7 @@ def k_pairs(k_vectors):
 def lowrank_plan(k_vectors, mean_pos_all, idx=None):
     """The low-rank plan of a k-list for one atom group (psa_lowrank_plan; host only): None when the list stays on
     the dense kernels, else a dict with u, k0, x_c, h_x, width, interval, d_bound, dscale, kappa (64,) and
-    C (K, 64) complex64."""
+    C (K, 64) complex64, and C's two factors L (K, 64) float32 and phi (K,) complex64."""
     kv = _as_f32(k_vectors, (3,))
     mean = _as_f32(mean_pos_all, (3,))
     K, N = kv.shape[0], mean.shape[0]
@@ -187,14 +187,15 @@ def lowrank_plan(k_vectors, mean_pos_all, idx=None):
     n_g = N if ix is None else ix.size
     ok, geo = C.c_int32(0), np.zeros(12, np.float64)
     kappa, cm = np.zeros(64, np.float64), np.zeros((K, 64), np.complex64)
+    lw, phi = np.zeros((K, 64), np.float32), np.zeros(K, np.complex64)
     dp = C.POINTER(C.c_double)
     _check(load_library().psa_lowrank_plan(_f32(kv), K, _f32(mean), N, None if ix is None else ix.ctypes.data_as(_i32p), n_g,
                                            C.byref(ok), geo.ctypes.data_as(dp), kappa.ctypes.data_as(dp),
-                                           cm.ctypes.data_as(_f32p)), "psa_lowrank_plan")
+                                           cm.ctypes.data_as(_f32p), _f32(lw), phi.ctypes.data_as(_f32p)), "psa_lowrank_plan")
     if not ok.value:
         return None
     return {"u": geo[0:3].copy(), "k0": geo[3:6].copy(), "x_c": geo[6], "h_x": geo[7], "width": geo[8],
-            "interval": int(geo[9]), "d_bound": geo[10], "dscale": geo[11], "kappa": kappa, "C": cm}
+            "interval": int(geo[9]), "d_bound": geo[10], "dscale": geo[11], "kappa": kappa, "C": cm, "L": lw, "phi": phi}
 
 
 def host_mean_frames(x: np.ndarray, threads: int = 0) -> np.ndarray:

@@ -147,6 +147,8 @@ struct LowRankPlan {
     float               dscale = 0.f;                         // power of two the D image carries
     std::vector<double> kline;                                // (K, 3) the k-vectors projected on the line
     std::vector<float>  C;                                    // (K, 64) complex64 combine matrix
+    std::vector<float>  L;                                    // (K, 64) its real factor, the Lagrange weights L_l(kappa_j)
+    std::vector<float>  phi;                                  // (K) complex64, its phase factor exp(i kappa_j x_c)
 };
 int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, const int32_t* h_idx, int64_t n_g, LowRankPlan* p);
 int prepare_lowrank(psa_ctx* c, const GroupView& v, const ProjectArgs& list, int64_t k_first, int64_t nk, ProjGeom* g);

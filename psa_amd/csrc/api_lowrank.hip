@@ -4,7 +4,9 @@
 //     exp(i k_j.r_a) = exp(i kappa_j x_c) * sum_l L_l(kappa_j) W[l, a],   W[l, a] = exp(i k0.r_a) exp(i kappa_l (x_a - x_c)),
 // where kappa_l are 64 Chebyshev nodes of an interval of kappa and L_l their Lagrange polynomials: Chebyshev
 // interpolation of exp(i kappa (x - x_c)) over an interval of half-width h_k, |x - x_c| <= h_x, is exact to fp64
-// rounding with 64 nodes while h_k h_x <= 30.  C[j, l] = exp(i kappa_j x_c) L_l(kappa_j).
+// rounding with 64 nodes while h_k h_x <= 30.  C[j, l] = exp(i kappa_j x_c) L_l(kappa_j); the plan also carries its
+// two factors on their own, L[j, l] = L_l(kappa_j) (real) and phi[j] = exp(i kappa_j x_c), for the combine that
+// sums the nodes with real weights and applies the phase once per output element (lowrank_combine_r_kernel).
 // What the line does not carry goes to D = P_ref - exp(i k~_j.r) (k~_j: k_j projected on the line), bounded by
 //     |D| <= 2^-22 sum_i max|k_i| max|r_i|   (float32 rounding of the reference's phase argument)
 //          + max_j |k_j - k~_j| max_a |r_a|  (the vectors off the line)
@@ -12,7 +14,7 @@
 // and accepted when the bound is at most 2^-13: D times the hi plane alone then misses at most 2^-25 of |v| per term.
 //
 // The plan is ROW-DETERMINISTIC for the lists it serves: u, k0, the node interval and hence the nodes and each row
-// of C depend on the line and the atom group, not on which part of the path a launch holds, so a list split over
+// of C, L and phi depend on the line and the atom group, not on which part of the path a launch holds, so a list split over
 // calls projects every row with the same arithmetic.  That needs a line the float32 k-vectors determine EXACTLY:
 // any quantity estimated from them carries their rounding (~1e-7 relative) and lands on different grid points for
 // different sub-lists.  So the route serves lines through Gamma (k0 = 0) along a small-integer (lattice) direction
@@ -154,8 +156,10 @@ int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, co
         p->kappa[l] = mid + half * std::cos(th);
         bw[l] = ((l & 1) ? -1.0 : 1.0) * std::sin(th);           // barycentric weights of Chebyshev points of the first kind
     }
-    // ---- C[j, l] = exp(i kappa_j x_c) L_l(kappa_j), complex64
+    // ---- C[j, l] = exp(i kappa_j x_c) L_l(kappa_j), complex64; L[j, l] and phi[j], each rounded from fp64 on its own
     p->C.assign((size_t)K * LOWRANK_NODES * 2, 0.f);
+    p->L.assign((size_t)K * LOWRANK_NODES, 0.f);
+    p->phi.assign((size_t)K * 2, 0.f);
     for (int64_t j = 0; j < K; ++j) {
         const double kj = kap[(size_t)j];
         double       L[LOWRANK_NODES], den = 0.0;
@@ -172,7 +176,10 @@ int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, co
             for (double& v : L) v /= den;
         }
         const double cr = std::cos(kj * p->x_c), ci = std::sin(kj * p->x_c);
+        p->phi[(size_t)j * 2 + 0] = (float)cr;
+        p->phi[(size_t)j * 2 + 1] = (float)ci;
         for (int l = 0; l < LOWRANK_NODES; ++l) {
+            p->L[(size_t)j * LOWRANK_NODES + l] = (float)L[l];
             p->C[((size_t)j * LOWRANK_NODES + l) * 2 + 0] = (float)(cr * L[l]);
             p->C[((size_t)j * LOWRANK_NODES + l) * 2 + 1] = (float)(ci * L[l]);
         }
@@ -184,7 +191,8 @@ int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, co
 }
 
 // Decide the route of one projection launch (a group's planes, nk k-vectors from k_first of the list) and, when the
-// low-rank route serves, upload what it needs: fp64 [k0 (3), u (3), x_c, kappa (64), kline (nk x 3)] and C.
+// low-rank route serves, upload what it needs: fp64 [k0 (3), u (3), x_c, kappa (64), kline (nk x 3)] and the combine
+// matrix of the context's arm (C, or L and phi).
 // The decision depends on the list, the group and the options only -- never on how the list is split over
 // calls -- as long as every part keeps PSA_OPT_K1_LOWRANK_MIN_LOCAL vectors (default 128: a 512-row D block at
 // least half full).
@@ -203,7 +211,12 @@ int prepare_lowrank(psa_ctx* c, const GroupView& v, const ProjectArgs& list, int
     std::memcpy(f64.data() + 7, p.kappa, sizeof(p.kappa));
     std::memcpy(f64.data() + 7 + LOWRANK_NODES, p.kline.data(), p.kline.size() * sizeof(double));
     PSA_TRY(upload(c, c->d_lr_f64, f64.data(), f64.size() * sizeof(double)));
-    PSA_TRY(upload(c, c->d_lr_C, p.C.data(), p.C.size() * sizeof(float)));
+    if (c->k1_combine_arm == 2) {
+        PSA_TRY(upload(c, c->d_lr_L, p.L.data(), p.L.size() * sizeof(float)));
+        PSA_TRY(upload(c, c->d_lr_phi, p.phi.data(), p.phi.size() * sizeof(float)));
+    } else {
+        PSA_TRY(upload(c, c->d_lr_C, p.C.data(), p.C.size() * sizeof(float)));
+    }
     PSA_TRY(c->d_lr_qn.reserve((size_t)LOWRANK_NODES * 3 * (size_t)c->slot[v.slot].T * sizeof(float2)));
     g->lowrank = true;
     g->dscale = p.dscale;
@@ -218,7 +231,7 @@ using namespace psa;
 extern "C" {
 
 int psa_lowrank_plan(const float* k_vectors, int64_t K, const float* mean_pos_all, int64_t N, const int32_t* idx, int64_t n_g,
-                     int32_t* ok, double* geo, double* kappa, float* C) {
+                     int32_t* ok, double* geo, double* kappa, float* C, float* L, float* phi) {
     PSA_REQUIRE(K >= 0 && K < (1ll << 29) && N >= 1 && n_g >= 0 && n_g <= (idx ? (int64_t)1 << 30 : N) && ok && geo &&
                     (K == 0 || k_vectors) && mean_pos_all,
                 "bad argument");
@@ -229,6 +242,8 @@ int psa_lowrank_plan(const float* k_vectors, int64_t K, const float* mean_pos_al
     std::memcpy(geo, g, sizeof(g));
     if (p.ok && kappa) std::memcpy(kappa, p.kappa, sizeof(p.kappa));
     if (p.ok && C) std::memcpy(C, p.C.data(), p.C.size() * sizeof(float));
+    if (p.ok && L) std::memcpy(L, p.L.data(), p.L.size() * sizeof(float));
+    if (p.ok && phi) std::memcpy(phi, p.phi.data(), p.phi.size() * sizeof(float));
     return PSA_OK;
 }
 

@@ -332,7 +332,7 @@ static int launch_projection_once(psa_ctx* c, const GroupView& v, ProjGeom g, fl
         // PSA_OPT_K1_LOADER_WAVES [1]: 128-row M blocks go to the loader-wavefront form of the kernel
         // (k1_planes_lw.hip; 2-3 % faster than the eight-wavefront form on every shape, round 3); 0 = never
         if (g.lowrank) {
-            // node rows (the 128-row planes kernel on the node table in d_phase) -> d_lr_qn; D pass -> q; q += C Qn
+            // node rows (the 128-row planes kernel on the node table in d_phase) -> d_lr_qn; D pass -> q; q += C Qn (C = phi L)
             ProjGeom gn = g;
             gn.K = LOWRANK_NODES;
             gn.m_blk = gn.M_pad = 2 * LOWRANK_NODES;
@@ -344,8 +344,11 @@ static int launch_projection_once(psa_ctx* c, const GroupView& v, ProjGeom g, fl
             PSA_TRY(launch_k1_planes_diff(c, pl, c->d_lr_diff.ptr, d_q, gd, n_fg, g.dscale));
             if (c->k1_combine_arm == 0)
                 PSA_TRY(launch_lowrank_combine(c, c->d_lr_qn.as<float2>(), c->d_lr_C.as<float2>(), d_q, g, t_count));
-            else
+            else if (c->k1_combine_arm == 1)
                 PSA_TRY(launch_lowrank_combine_v(c, c->d_lr_qn.as<float2>(), c->d_lr_C.as<float2>(), d_q, g, t_count));
+            else
+                PSA_TRY(launch_lowrank_combine_r(c, c->d_lr_qn.as<float2>(), c->d_lr_L.as<float>(), c->d_lr_phi.as<float2>(), d_q, g,
+                                                 t_count));
             ++c->lowrank_launches;
             return PSA_OK;
         }

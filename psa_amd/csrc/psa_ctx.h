@@ -251,9 +251,12 @@ struct psa_ctx {
     int64_t      opt_k1_lowrank_min_k = 256;    // PSA_OPT_K1_LOWRANK_MIN_K: shortest whole k-list it serves
     int64_t      opt_k1_lowrank_min_local = 128; // PSA_OPT_K1_LOWRANK_MIN_LOCAL: shortest part of it one launch serves
     int64_t      lowrank_launches = 0;          // projection launches that took the route (psa_k1_lowrank_launches)
-    int          k1_combine_arm = 1;            // PSA_K1_COMBINE (environment, psa_create): 1 lowrank_combine.hip, 0 the scalar combine
-    // its D image, node projections, C, fp64 inputs (the node table goes into d_phase); released when the route is switched off
-    psa::DevBuf  d_lr_diff, d_lr_qn, d_lr_C, d_lr_f64;
+    // PSA_K1_COMBINE (environment, psa_create): 2 real weights + one phase per element (lowrank_combine_r_kernel),
+    // 1 packed complex weights (lowrank_combine_v_kernel), 0 the scalar combine (bit-identical to 1)
+    int          k1_combine_arm = 2;
+    // its D image, node projections, C (arms 0, 1) or L and phi (arm 2), fp64 inputs (the node table goes into d_phase);
+    // released when the route is switched off
+    psa::DevBuf  d_lr_diff, d_lr_qn, d_lr_C, d_lr_L, d_lr_phi, d_lr_f64;
 
     // per-atom weights of every projection (psa_set_atom_weights): d_weights holds weights_N values, none when 0;
     // weights_scale = 2^e, the smallest power of two >= their largest magnitude
@@ -355,8 +358,11 @@ int    launch_k1_planes_diff(psa_ctx* c, const void* d_planes, const void* d_dif
                              float dscale);
 int    launch_lowrank_combine(psa_ctx* c, const float2* d_qn, const float2* d_C, float2* d_q, const ProjGeom& g, int64_t qn_stride);
 
-// --- lowrank_combine.hip (the packed combine; the arm: psa_ctx::k1_combine_arm)
+// --- lowrank_combine.hip (the packed combines: _v complex weights, arm 1; _r real weights + one phase per element,
+// arm 2, the default; the arm: psa_ctx::k1_combine_arm, PSA_K1_COMBINE)
 int    launch_lowrank_combine_v(psa_ctx* c, const float2* d_qn, const float2* d_C, float2* d_q, const ProjGeom& g, int64_t qn_stride);
+int    launch_lowrank_combine_r(psa_ctx* c, const float2* d_qn, const float* d_L, const float2* d_phi, float2* d_q, const ProjGeom& g,
+                                int64_t qn_stride);
 
 // --- k2_epilogue.hip
 int launch_dft_bin(psa_ctx* c, const float2* d_q, int64_t T, int64_t bin, float2* d_out3);

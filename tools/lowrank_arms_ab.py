@@ -1,5 +1,6 @@
-"""K1 time per launch of the low-rank k-path route at configuration 3 with the scalar combine (k1_planes_diff.hip) and
-the packed one (lowrank_combine.hip).  PSA_K1_COMBINE is read when an engine is created, so every arm runs in a
+"""K1 time per launch of the low-rank k-path route at configuration 3 with each arm of its combine: PSA_K1_COMBINE=0
+the scalar kernel (k1_planes_diff.hip), 1 the packed complex-weights kernel and 2, the default, the packed
+real-weights kernel (both lowrank_combine.hip).  PSA_K1_COMBINE is read when an engine is created, so every arm runs in a
 process of its own; rounds interleave the arms.  K1 = node pass + D pass + combine, timed together (psa_k1_stats).
     python tools/lowrank_arms_ab.py [rounds] [reps]        one JSON line per arm and round"""
 import json
@@ -9,7 +10,7 @@ import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
-ARMS = {"scalar_combine": "0", "packed_combine": "1"}
+ARMS = {"scalar_combine": "0", "packed_combine": "1", "real_weights_combine": "2"}
 
 CHILD = r"""
 import json, sys
