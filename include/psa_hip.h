@@ -343,6 +343,42 @@ int psa_sed_modes(psa_ctx* ctx, int slot, const float* mean_pos_all, const float
                   const void* eig /* (K,M,B,3) complex64 */, int64_t M, int32_t flags /* PSA_F_DISPLACEMENTS or 0 */,
                   float* out_host /* (T,K,M) */, size_t out_bytes);
 
+/* Lorentzian fits of spectrum peaks: frequency and half width per column, on the device.  A spectrum is phi (F, C)
+ * float32, C order; row i is bin i of an F-point transform, f_i = i df.  Only the positive half is used, bins
+ * 1 .. ceil(F/2) - 1.  Column j has the band [lo_j, hi_j) of bins (bands (C, 2) int32, or NULL: [lo, hi) for all).
+ *   1. p = the lowest bin of the band at which phi is largest; half = 0.5f phi[p]; l (r) = the number of consecutive
+ *      bins below (above) p, not past the band, with phi >= half; h0 = max(1, (l + r + 1) / 2) bins;
+ *      n = clamp(ceil(window_hwhm h0), 4, 2047), or clamp(half_window_bins, 4, 2047) when that is not 0; the window is
+ *      [a, b) = [max(lo, p - n), min(hi, p + n + 1)).  Integer and float32 comparisons only.
+ *   2. unweighted least squares of  height hwhm^2 / ((f - f0)^2 + hwhm^2) + baseline  over the window's bins, by
+ *      Levenberg-Marquardt with Marquardt's diagonal scaling in the units x = (i - p) / h0, y = phi[i] / phi[p], from
+ *      f0 = 0, hwhm = 1, baseline = min y, height = 1 - baseline; steps with hwhm <= 0 are rejected; at most max_iter
+ *      iterations; stop when the largest step is at most 1e-6 (f0, hwhm relative to hwhm; height, baseline relative
+ *      to height).  Sums and solve are float64.
+ * fit (C, 6) float32: f0, hwhm (in the units of df), height, baseline, rss (units of phi^2), peak bin p.
+ * info (C, 4) int32: status, iterations, a, b - a.  Status 0 converged; 1 iteration cap reached (the best so far);
+ * 2 no fit -- a band of fewer than 5 bins, phi[p] <= 0 or a non-finite value in the band: the six floats are NaN, the
+ * rest of info 0; 3 converged, but f0 outside [a, b) or hwhm above b - a bins.
+ * PSA_EINVAL: a null spectrum or output, F < 12, C < 1, a band outside [1, ceil(F/2)) or with lo >= hi, window_hwhm <= 0,
+ * half_window_bins < 0, max_iter < 1.  Two kernels (peaks.hip): one streaming pass that finds the peak bins, one
+ * wavefront per column that fits from LDS; deterministic (two calls give the same bits, a column's result does not
+ * depend on the other columns).  No result of another entry point is touched.  Stage times go to psa_last_timings:
+ * [0] upload, [4] both kernels, [7] device->host. */
+typedef struct {
+    float   window_hwhm;        /* half width of the fit window in units of the peak's half width at half maximum [8] */
+    int32_t half_window_bins;   /* the same in bins, overriding window_hwhm; 0 = automatic */
+    int32_t max_iter;           /* iteration cap [50] */
+} psa_peak_opts;
+/* any spectrum: spec_host (F, C) float32 is uploaded; opts NULL = the defaults */
+int psa_fit_peaks(psa_ctx* ctx, const float* spec_host, int64_t F, int64_t C, double df, const int32_t* bands, int32_t lo,
+                  int32_t hi, const psa_peak_opts* opts, float* fit /* (C,6) */, int32_t* info /* (C,4) */);
+/* psa_sed_modes and the fit of its (T, K M) result where it lies: psa_sed_modes' arguments and refusals, then the
+ * fit's with F = T, C = K M (column k M + nu).  out_host may be NULL: the spectra are then not copied to the host. */
+int psa_sed_modes_fit(psa_ctx* ctx, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K,
+                      const int32_t* group_idx, const int64_t* group_off, int32_t B, const void* eig, int64_t M,
+                      int32_t flags, double df, const int32_t* bands, int32_t lo, int32_t hi, const psa_peak_opts* opts,
+                      float* fit /* (K*M,6) */, int32_t* info /* (K*M,4) */, float* out_host, size_t out_bytes);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is

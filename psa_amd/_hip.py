@@ -73,6 +73,11 @@ SIGNATURES = {
     "psa_vdos": (C.c_int, [_ctx, C.c_int, _f32p, _i32p, _i64p, C.c_int32, C.c_int32, _f32p, C.c_size_t]),
     "psa_sed_modes": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p, _i64p, C.c_int32, C.c_void_p, C.c_int64,
                                 C.c_int32, _f32p, C.c_size_t]),
+    "psa_fit_peaks": (C.c_int, [_ctx, _f32p, C.c_int64, C.c_int64, C.c_double, _i32p, C.c_int32, C.c_int32, C.c_void_p,
+                                _f32p, _i32p]),
+    "psa_sed_modes_fit": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p, _i64p, C.c_int32, C.c_void_p, C.c_int64,
+                                    C.c_int32, C.c_double, _i32p, C.c_int32, C.c_int32, C.c_void_p, _f32p, _i32p, _f32p,
+                                    C.c_size_t]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
@@ -107,6 +112,11 @@ SIGNATURES = {
     "psa_sed_fs_write": (C.c_int, [_ctx, C.c_int64, C.c_int64, C.c_void_p]),
     "psa_sed_fs_finish": (C.c_int, [_ctx, C.c_int32]),
 }
+
+
+class PeakOpts(C.Structure):
+    """psa_peak_opts"""
+    _fields_ = [("window_hwhm", C.c_float), ("half_window_bins", C.c_int32), ("max_iter", C.c_int32)]
 
 
 class PsaHipError(RuntimeError):
@@ -626,6 +636,53 @@ class Engine:
             off.ctypes.data_as(_i64p) if off is not None else None, B,
             eig.ctypes.data_as(C.c_void_p), M, flags, _f32(out), out.nbytes), "psa_sed_modes")
         return out
+
+    def fit_peaks(self, spectrum, df, *, band=None, centers=None, search=None, window_hwhm=8.0, half_window=None,
+                  max_iter=50):
+        """Lorentzian fit of the peak of every column of `spectrum` (F, ...) float32 with frequency step `df` THz
+        (psa_fit_peaks; definition in psa_amd/peaks.py): a `psa_amd.PeakFit` whose fields have the spectrum's column
+        shape.  `band` = (fmin, fmax) THz for all columns (default: the positive half); `centers` (one frequency per
+        column) with `search`: each column's own interval; `window_hwhm`: half width of the fit window in units of the
+        peak's half width at half maximum, `half_window` THz overrides it; `max_iter`: the iteration cap."""
+        from . import peaks
+        spec, shape = peaks.spectrum_columns(spectrum)
+        F, ncol = spec.shape
+        peaks.check_fit_options(window_hwhm, max_iter)
+        bands = peaks.peak_bands(F, df, ncol, band, centers, search)
+        opts = PeakOpts(float(window_hwhm), peaks.half_window_bins(half_window, df), int(max_iter))
+        fit, info = np.empty((ncol, 6), np.float32), np.empty((ncol, 4), np.int32)
+        _check(self._lib.psa_fit_peaks(self._h, _f32(spec), F, ncol, float(df), bands.ctypes.data_as(_i32p), 0, 0,
+                                       C.byref(opts), _f32(fit), info.ctypes.data_as(_i32p)), "psa_fit_peaks")
+        return peaks.PeakFit.from_arrays(fit, info, shape)
+
+    def sed_modes_fit(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, df, flags=0, *, return_sed=False, band=None,
+                      centers=None, search=None, window_hwhm=8.0, half_window=None, max_iter=50):
+        """`sed_modes` and `fit_peaks` of its result in one library call (psa_sed_modes_fit): the (T, K, M) spectra are
+        fitted where they lie and cross to the host only with `return_sed`.  Returns (PeakFit with (K, M) fields, the
+        spectra or None)."""
+        from . import peaks
+        T, _ = self.shape(slot)
+        mean = _as_f32(mean_pos_all, (3,))
+        kv = _as_f32(k_vectors, (3,))
+        idx, off, B = pack_groups(groups)
+        eig = np.ascontiguousarray(eigenvectors, np.complex64)
+        K = kv.shape[0]
+        if eig.ndim != 4 or eig.shape[0] != K or eig.shape[2:] != (B, 3) or eig.shape[1] < 1:
+            raise ValueError(f"eigenvectors have shape {eig.shape}, expected (K, M, B, 3) = ({K}, M, {B}, 3)")
+        M = eig.shape[1]
+        peaks.check_fit_options(window_hwhm, max_iter)
+        bands = peaks.peak_bands(T, df, K * M, band, centers, search)
+        opts = PeakOpts(float(window_hwhm), peaks.half_window_bins(half_window, df), int(max_iter))
+        fit, info = np.empty((K * M, 6), np.float32), np.empty((K * M, 4), np.int32)
+        out = pinned_empty((T, K, M), np.float32) if return_sed else None
+        _check(self._lib.psa_sed_modes_fit(
+            self._h, slot, _f32(mean), _f32(kv), K,
+            idx.ctypes.data_as(_i32p) if idx is not None else None,
+            off.ctypes.data_as(_i64p) if off is not None else None, B,
+            eig.ctypes.data_as(C.c_void_p), M, flags, float(df), bands.ctypes.data_as(_i32p), 0, 0, C.byref(opts),
+            _f32(fit), info.ctypes.data_as(_i32p), _f32(out) if out is not None else None,
+            out.nbytes if out is not None else 0), "psa_sed_modes_fit")
+        return peaks.PeakFit.from_arrays(fit, info, (K, M)), out
 
     def debug_mode_power(self, spectra: np.ndarray, eigenvectors: np.ndarray) -> np.ndarray:
         """The contraction kernel of `sed_modes` alone (psa_debug_mode_power): spectra (B, K, 3, T) complex64 taken as

@@ -32,6 +32,7 @@ import numpy as np
 from .. import _hip
 from ..io.writer import out_to_qdump
 from ..modes import ModeSED
+from ..peaks import PeakFit
 from ..segments import Segments
 from ..utils.helpers import parse_direction
 from ..vdos import VDOS
@@ -470,6 +471,28 @@ class SEDCalculator:
         another convention is the caller's business.  Pairs (k, -k) are not folded.  `atom_weights` as for `calculate`
         (`psa_amd.mass_weights` for the mass-weighted mode coordinate).  A sharded calculator refuses
         (NotImplementedError).  Returns a `psa_amd.ModeSED` with `sed` (T, K, M) float32."""
+        weights, eig, k_vectors, groups, empty = self._mode_inputs(k_points_mags, k_vectors_3d, eigenvectors,
+                                                                   basis_atom_indices, basis_atom_types, atom_weights)
+        if empty is not None:
+            return empty
+        freqs = np.fft.fftfreq(self.traj.n_frames, d=self.dt_ps)
+        mean_pos_all = self._mean_positions()
+        slot, data, flags = self._data_slot()
+        eng = self.engine
+        with eng.lock:
+            if weights is not None:
+                eng.set_atom_weights(weights)
+            try:
+                eng.ensure_resident(slot, data)      # later SED calls find it resident
+                phi = eng.sed_modes(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64), flags)
+            finally:
+                if weights is not None:
+                    eng.set_atom_weights(None)
+        return ModeSED(phi, freqs, k_points_mags, k_vectors_3d, [np.asarray(g) for g in groups])
+
+    def _mode_inputs(self, k_points_mags, k_vectors_3d, eigenvectors, basis_atom_indices, basis_atom_types, atom_weights):
+        """What the mode projections check and resolve: (weights, eig, k_vectors (K, 3) float32, groups, the empty ModeSED
+        to return as it is -- no frames, no atoms or no k-vectors -- or None)."""
         weights = None if atom_weights is None else check_atom_weights(atom_weights, self.traj.n_atoms)
         if self._shard is not None and self._shard.nranks > 1:
             raise NotImplementedError("the mode-projected SED is not available on a sharded calculator")
@@ -478,7 +501,8 @@ class SEDCalculator:
         n_t, n_atoms, n_k = self.traj.n_frames, self.traj.n_atoms, len(k_vectors)
         if n_t == 0 or n_atoms == 0:
             logger.warning("Cannot calculate the mode-projected SED: 0 frames or 0 atoms.")
-            return ModeSED(np.zeros((0, 0, 0), np.float32), np.zeros(0, np.float64), k_points_mags, k_vectors_3d, [])
+            return weights, eig, k_vectors, [], ModeSED(np.zeros((0, 0, 0), np.float32), np.zeros(0, np.float64), k_points_mags,
+                                                        k_vectors_3d, [])
         if (basis_atom_types is None and isinstance(basis_atom_indices, (list, tuple)) and len(basis_atom_indices)
                 and all(isinstance(g, np.ndarray) for g in basis_atom_indices)):
             # index arrays (`site_groups`) are taken as they are, with the checks of `_resolve_groups`: no detour
@@ -498,11 +522,35 @@ class SEDCalculator:
                              f"for {n_k} k-vectors and {len(groups)} atom groups")
         if not np.all(np.isfinite(eig)):
             raise ValueError("eigenvectors must be finite")
-        freqs = np.fft.fftfreq(n_t, d=self.dt_ps)
-        out_groups = [np.asarray(g) for g in groups]
         if n_k == 0:
             logger.warning("k_vectors_3d is empty. Returning ModeSED object with empty data.")
-            return ModeSED(np.zeros((n_t, 0, eig.shape[1]), np.float32), freqs, k_points_mags, k_vectors_3d, out_groups)
+            return weights, eig, k_vectors, groups, ModeSED(np.zeros((n_t, 0, eig.shape[1]), np.float32),
+                                                            np.fft.fftfreq(n_t, d=self.dt_ps), k_points_mags, k_vectors_3d,
+                                                            [np.asarray(g) for g in groups])
+        return weights, eig, k_vectors, groups, None
+
+    def calculate_mode_peaks(self, k_points_mags: np.ndarray, k_vectors_3d: np.ndarray, eigenvectors: np.ndarray,
+                             basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                             basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                             atom_weights: Optional[np.ndarray] = None, return_sed: bool = False, band=None, centers=None,
+                             search=None, window_hwhm: float = 8.0, half_window: Optional[float] = None, max_iter: int = 50
+                             ) -> Union[PeakFit, Tuple[PeakFit, ModeSED]]:
+        """Frequency and lifetime of every mode (k, nu): `calculate_mode_sed` and a Lorentzian fit of the peak of each of
+        its K x M columns (definition in psa_amd/peaks.py), in one pass on the GPU -- the (T, K, M) spectra are fitted
+        where they lie and do not cross to the host unless `return_sed` asks for them.
+
+        The projection's arguments, checks, weights and restrictions are those of `calculate_mode_sed` (not sharded;
+        no segment average).  `band` = (fmin, fmax) THz searched in every column (default: all positive frequencies);
+        `centers` (K, M) THz with `search`: each mode's own interval center +- search, for spectra in which a column
+        shows more than its own branch; `window_hwhm`, `half_window`, `max_iter` as for `Engine.fit_peaks`.  Returns a
+        `psa_amd.PeakFit` with (K, M) fields (`frequency`, `hwhm`, `lifetime`, `status`, ...); with `return_sed`
+        (PeakFit, ModeSED)."""
+        weights, eig, k_vectors, groups, empty = self._mode_inputs(k_points_mags, k_vectors_3d, eigenvectors,
+                                                                   basis_atom_indices, basis_atom_types, atom_weights)
+        if empty is not None:
+            raise ValueError("nothing to fit: the trajectory has no frames or atoms, or the k-list is empty")
+        n_t = self.traj.n_frames
+        freqs = np.fft.fftfreq(n_t, d=self.dt_ps)
         mean_pos_all = self._mean_positions()
         slot, data, flags = self._data_slot()
         eng = self.engine
@@ -511,11 +559,15 @@ class SEDCalculator:
                 eng.set_atom_weights(weights)
             try:
                 eng.ensure_resident(slot, data)      # later SED calls find it resident
-                phi = eng.sed_modes(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64), flags)
+                fit, phi = eng.sed_modes_fit(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64),
+                                             1.0 / (n_t * self.dt_ps), flags, return_sed=return_sed, band=band, centers=centers,
+                                             search=search, window_hwhm=window_hwhm, half_window=half_window, max_iter=max_iter)
             finally:
                 if weights is not None:
                     eng.set_atom_weights(None)
-        return ModeSED(phi, freqs, k_points_mags, k_vectors_3d, out_groups)
+        if not return_sed:
+            return fit
+        return fit, ModeSED(phi, freqs, k_points_mags, k_vectors_3d, [np.asarray(g) for g in groups])
 
     # ------------------------------------------------------------------ chiral phase
     def calculate_chiral_phase(self, Z1: np.ndarray, Z2: np.ndarray, angle_range_opt: str = "C") -> np.ndarray:

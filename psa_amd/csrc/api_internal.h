@@ -10,6 +10,7 @@
 //   api_shard.hip    sharding over RCCL: communicator, k-row gather, frame sharding
 //   api_vdos.hip     the vibrational density of states: a second, non-projecting pass over the resident array
 //   api_modes.hip    the mode-projected SED: the B site groups' spectra contracted with the mode vectors
+//   api_peaks.hip    Lorentzian peak fits of spectrum columns: an uploaded spectrum, or the mode spectra where they lie
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
 // k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
 #pragma once
@@ -152,6 +153,11 @@ struct LowRankPlan {
 };
 int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, const int32_t* h_idx, int64_t n_g, LowRankPlan* p);
 int prepare_lowrank(psa_ctx* c, const GroupView& v, const ProjectArgs& list, int64_t k_first, int64_t nk, ProjGeom* g);
+// api_modes.hip: the body of psa_sed_modes; the (T, K, M) result is left in c->d_modes_out.  out_host may be null only
+// with `device_only` (psa_sed_modes_fit), and is then not copied to
+int modes_run(psa_ctx* c, int slot_in, const float* mean_pos_all, const float* k_vectors, int64_t K, const int32_t* group_idx,
+              const int64_t* group_off, int32_t B, const float* eig, int64_t M, int32_t flags, float* out_host, size_t out_bytes,
+              bool device_only);
 int    check_weights(psa_ctx* c, int64_t N);            // the context's atom weights fit a slot of N atoms
 void   set_geom_weights(const psa_ctx* c, ProjGeom* g);  // ... and go into a launch's geometry
 int    begin_result(psa_ctx* c, int64_t T, int64_t K_total, int64_t k_offset, bool intensity, char** rows);

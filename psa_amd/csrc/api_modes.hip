@@ -28,14 +28,17 @@ int pack_coef(const float* eig, int64_t K, int64_t M, int64_t B, int MT, std::ve
     return PSA_OK;
 }
 
+}  // namespace
+
 int modes_run(psa_ctx* c, int slot_in, const float* mean_pos_all, const float* k_vectors, int64_t K, const int32_t* group_idx,
-              const int64_t* group_off, int32_t B, const float* eig, int64_t M, int32_t flags, float* out_host, size_t out_bytes) {
+              const int64_t* group_off, int32_t B, const float* eig, int64_t M, int32_t flags, float* out_host, size_t out_bytes,
+              bool device_only) {
     PSA_TRY(check_slot(c, slot_in));
     const int64_t T = c->slot[slot_in].T, N = c->slot[slot_in].N;
     const bool    disp_in = (flags & PSA_F_DISPLACEMENTS) != 0;
     PSA_REQUIRE((flags & ~PSA_F_DISPLACEMENTS) == 0, "psa_sed_modes takes PSA_F_DISPLACEMENTS or 0, got flags 0x%x", (unsigned)flags);
     PSA_REQUIRE(eig != nullptr, "null eig");
-    PSA_REQUIRE(out_host != nullptr, "null output");
+    PSA_REQUIRE(out_host != nullptr || device_only, "null output");
     PSA_REQUIRE(mean_pos_all != nullptr, "null mean_pos_all");
     PSA_REQUIRE(M >= 1 && M < (1ll << 30), "need at least one mode vector per k-point (M = %lld)", (long long)M);
     PSA_REQUIRE(K >= 0 && K < (1ll << 29), "bad number of k-vectors %lld", (long long)K);
@@ -45,7 +48,7 @@ int modes_run(psa_ctx* c, int slot_in, const float* mean_pos_all, const float* k
     PSA_REQUIRE(c->seg_L == 0, "psa_sed_modes has no segment average: clear psa_set_segments first (length %lld is set)",
                 (long long)c->seg_L);
     const size_t want = (size_t)T * (size_t)K * (size_t)M * sizeof(float);
-    PSA_REQUIRE(out_bytes == want, "out_bytes is %zu, the (%lld,%lld,%lld) float32 result has %zu", out_bytes, (long long)T,
+    PSA_REQUIRE(out_bytes == want || !out_host, "out_bytes is %zu, the (%lld,%lld,%lld) float32 result has %zu", out_bytes, (long long)T,
                 (long long)K, (long long)M, want);
     if (group_idx) {
         std::vector<uint8_t> seen((size_t)N, 0);
@@ -119,13 +122,12 @@ int modes_run(psa_ctx* c, int slot_in, const float* mean_pos_all, const float* k
         }
         k0 += nk;
     }
+    if (!out_host) return PSA_OK;
     StageTimer st(c, PSA_T_D2H);
     PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_modes_out.ptr, want, hipMemcpyDeviceToHost, c->stream));
     PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return PSA_OK;
 }
-
-}  // namespace
 
 }  // namespace psa
 
@@ -139,7 +141,7 @@ int psa_sed_modes(psa_ctx* c, int slot, const float* mean_pos_all, const float* 
     PSA_TRY(enter(c));
     Guard     guard(c);
     const int rc = modes_run(c, slot, mean_pos_all, k_vectors, K, group_idx, group_off, B, (const float*)eig, M, flags, out_host,
-                             out_bytes);
+                             out_bytes, false);
     // the caller's arrays are only read during the call, whichever way it ends
     if (hipStreamSynchronize(c->stream) != hipSuccess && rc == PSA_OK) {
         set_error("hipStreamSynchronize failed after psa_sed_modes");

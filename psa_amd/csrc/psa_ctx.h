@@ -282,6 +282,10 @@ struct psa_ctx {
     psa::DevBuf  d_modes_work, d_modes_coef, d_modes_out;
     int64_t      opt_modes_work_bytes = (int64_t)4 << 30;
 
+    // Lorentzian peak fits (psa_fit_peaks, psa_sed_modes_fit; api_peaks.hip): an uploaded spectrum, the per-column bands,
+    // the row slices' partial maxima (value, bin, non-finite flag) and the results.  All kept between calls.
+    psa::DevBuf  d_peaks_spec, d_peaks_bands, d_peaks_part, d_peaks_fit, d_peaks_info;
+
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
                                           // plane builds, trajectory uploads (psa_oneoff_stats)
@@ -401,6 +405,16 @@ int modes_tile(int64_t M);            // modes per pass (MT) of the kernel that 
 // |sum_n coef S|^2 inv_n2 (inv_n2 = 1/T^2 for unscaled spectra)
 int launch_mode_power(psa_ctx* c, const float2* d_S, const float2* d_coef, float* d_out, int64_t T, int64_t nk, int64_t B,
                       int64_t M, int MT, int64_t K_pitch, int64_t k_col0, float inv_n2);
+// --- peaks.hip (psa_fit_peaks: per column of a spectrum (F, C) the largest value of its band, then a Lorentzian fit)
+int peaks_slices(int64_t C, int64_t rows);   // row slices peak_find splits `rows` rows of C columns into (at most 64)
+// rows [row0, row_end) in n_slices slices -> (n_slices, C) partials: largest value of the column's band [lo, hi) (d_bands
+// (C, 2), or null: lo, hi for all), its lowest bin, whether the band holds a non-finite value
+int launch_peak_find(psa_ctx* c, const float* d_spec, int64_t C, const int32_t* d_bands, int lo, int hi, int row0, int row_end,
+                     int n_slices, float* d_pmax, int* d_pidx, int* d_pflag);
+// folds the partials, sets the window and fits: d_fit (C, 6) float32, d_info (C, 4) int32 as psa_fit_peaks returns them
+int launch_peak_fit(psa_ctx* c, const float* d_spec, int64_t C, const int32_t* d_bands, int lo, int hi, const float* d_pmax,
+                    const int* d_pidx, const int* d_pflag, int n_slices, double df, float window_hwhm, int half_window_bins,
+                    int max_iter, float* d_fit, int32_t* d_info);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 

@@ -8,9 +8,12 @@ warm-up, medians of `--runs` calls of
       one `calculate(basis_atom_indices=site b)` per site plus np.abs(np.einsum(...))**2 on the host.  The B complex
       results are fetched in full; the einsum is timed on `--contract-frames` of the T frames and scaled to T (it is
       linear in T), which the output states;
-  (c) the incoherent `calculate` of the same 8 groups, which does the same projections and the same transforms.
-Kernel time of mode_power_kernel: run it under `rocprofv3 --kernel-trace --stats` (with --skip-baseline).
-    python tools/modes_timing.py [--cfg C3] [--n-k 256] [--modes 24] [--runs 10] [--skip-baseline]"""
+  (c) the incoherent `calculate` of the same 8 groups, which does the same projections and the same transforms;
+  (d) with --peaks: SEDCalculator.calculate_mode_peaks() end to end without and with `return_sed`, the stage times of
+      psa_sed_modes_fit (the two fit kernels are in the "epilogue" stage beside the contraction) and the statuses.
+Kernel time of mode_power_kernel, peak_find_kernel, peak_fit_kernel: run it under `rocprofv3 --kernel-trace --stats`
+(with --skip-baseline).
+    python tools/modes_timing.py [--cfg C3] [--n-k 256] [--modes 24] [--runs 10] [--skip-baseline] [--peaks]"""
 import argparse
 import json
 import sys
@@ -31,6 +34,7 @@ ap.add_argument("--runs", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--contract-frames", type=int, default=2048)
 ap.add_argument("--skip-baseline", action="store_true")
+ap.add_argument("--peaks", action="store_true")
 args = ap.parse_args()
 
 spec, req = synth.baseline_spec(args.cfg)
@@ -71,6 +75,25 @@ def e2e_modes():
     t0 = time.perf_counter()
     calc.calculate_mode_sed(mags, vecs, eig, groups, atom_weights=w)
     return 1e3 * (time.perf_counter() - t0)
+
+
+def e2e_peaks(return_sed=False):
+    t0 = time.perf_counter()
+    calc.calculate_mode_peaks(mags, vecs, eig, groups, atom_weights=w, return_sed=return_sed)
+    return 1e3 * (time.perf_counter() - t0)
+
+
+def stages_peaks():
+    """psa_last_timings of one psa_sed_modes_fit call that leaves the spectra on the device"""
+    eng.set_atom_weights(w)
+    try:
+        eng.timings()
+        t0 = time.perf_counter()
+        eng.sed_modes_fit(0, r0, vecs, groups, eig, 1.0 / (T * spec.dt_ps))
+        call_ms = 1e3 * (time.perf_counter() - t0)
+        return dict(eng.timings(), call=call_ms)
+    finally:
+        eng.set_atom_weights(None)
 
 
 def e2e_incoherent():
@@ -116,6 +139,20 @@ st = runs_of(stages_incoherent)
 out["stages_incoherent_ms"] = {k: float(np.median([r[k] for r in st])) for k in ("h2d", "phase", "project", "fft", "epilogue",
                                                                                   "transpose", "d2h")}
 out["e2e_incoherent_ms"] = stats(runs_of(e2e_incoherent))
+if args.peaks:
+    st = runs_of(stages_peaks)
+    out["peaks_stages_ms"] = {k: float(np.median([r[k] for r in st])) for k in ("h2d", "phase", "project", "fft", "epilogue", "d2h",
+                                                                               "call")}
+    out["peaks_fit_kernels_ms"] = out["peaks_stages_ms"]["epilogue"] - out["stages_ms"]["epilogue"]
+    out["e2e_peaks_ms"] = stats(runs_of(e2e_peaks))
+    out["e2e_peaks_with_sed_ms"] = stats(runs_of(lambda: e2e_peaks(True)))
+    out["e2e_modes_again_ms"] = stats(runs_of(e2e_modes))                 # the spectra alone once more, after the fit calls
+    fit = calc.calculate_mode_peaks(mags, vecs, eig, groups, atom_weights=w)
+    out["peaks_statuses"] = np.bincount(fit.status.ravel(), minlength=4).tolist()
+    out["peaks_iterations"] = stats(fit.iterations.ravel())
+    out["peaks_window_bins"] = stats(fit.window[..., 1] - fit.window[..., 0])
+    out["peak_find_bytes"] = 4 * ((T + 1) // 2 - 1) * K * M
+    out["peak_find_floor_ms"] = out["peak_find_bytes"] / 8e12 * 1e3
 if not args.skip_baseline:
     per_site_calls()                                                      # warm-up
     ms, spectra = zip(*[per_site_calls() for _ in range(3)])
