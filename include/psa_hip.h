@@ -145,7 +145,8 @@ int         psa_set_k1(psa_ctx* ctx, int selector);     /* PSA_K1_* */
  *                             the call loops over (atom block x segment block).  Must hold 32 atom pairs x 3
  *                             components x one segment: 768 L bytes. */
 #define PSA_OPT_VDOS_WORK_BYTES 11
-/*   PSA_OPT_MODES_WORK_BYTES [4 GiB] bytes of device memory the stacked spectra of psa_sed_modes may take: the call
+/*   PSA_OPT_MODES_WORK_BYTES [4 GiB] bytes of device memory the stacked spectra of psa_sed_modes may take (and, for
+ *                             psa_sed_modes_welch, they and the segment buffer together: at least 24 B (T + L)): the call
  *                             loops over blocks of k-vectors of 24 B T bytes each (B groups x 3 components x T
  *                             complex64).  The default holds 256 k-vectors of 65536 frames and 8 sites in one block.
  *                             Any value >= 1 is accepted; a call whose single k-vector does not fit is PSA_EINVAL.
@@ -379,6 +380,36 @@ int psa_sed_modes_fit(psa_ctx* ctx, int slot, const float* mean_pos_all, const f
                       int32_t flags, double df, const int32_t* bands, int32_t lo, int32_t hi, const psa_peak_opts* opts,
                       float* fit /* (K*M,6) */, int32_t* info /* (K*M,4) */, float* out_host, size_t out_bytes);
 
+/* Welch-averaged mode spectra: the mode-projected SED with the context's segments (psa_set_segments: length L, hop H,
+ * real window win; n_seg = 1 + (T - L) / H, U = (1/L) sum win^2; no detrending, two-sided, FFT order, frames after the
+ * last segment unused) between the projection and the contraction.  q_b and eig as for psa_sed_modes:
+ *     F_b,s[k,c,w] = (1/L) sum_tau win[tau] q_b[k,c,s H + tau] exp(-2 pi i w tau / L)
+ *     Q_s[k,nu,w]  = sum_b sum_c conj(eig[k,nu,b,c]) F_b,s[k,c,w]
+ *     Phi[w,k,nu]  = 1/(n_seg U) sum_s |Q_s[k,nu,w]|^2                  out_host (L, K, M) float32
+ * With no segments set the call is one boxcar segment of T frames (L = T): psa_sed_modes' result.  out_bytes exactly
+ * 4 L K M.  PSA_EINVAL: what psa_sed_modes refuses other than segments; L > T; a work budget
+ * (PSA_OPT_MODES_WORK_BYTES) that cannot hold one k-vector of q and one (k-vector, segment) unit, 24 B (T + L) bytes
+ * (24 B T with no segments set: q is then transformed in place).
+ * Per block of kb k-vectors the B projections are psa_sed_modes' own (plane cache, weights, displacement mode, the
+ * low-rank k-path route, its block rule); then per sub-block of bk k-vectors x bs segments: the window pass into
+ * (B, bk, 3, bs, L), one batched rocFFT of 3 B bk bs series of length L, one pass (modes_welch.hip) that contracts,
+ * takes the modulus and sums the sub-block's segments on chip; the first segments of a column overwrite it, later ones
+ * add to it.  q and the segment buffer share the budget; the (L,K,M) result on the device is outside it.  No atomics;
+ * launches in order on the context's stream: two identical calls give the same bits.  The slab, the k map, the plane
+ * cache and every result of the SED entry points are left as they are.  Stage times go to psa_last_timings:
+ * [2] projection, [3] FFT, [4] window and contraction, [7] device->host. */
+int psa_sed_modes_welch(psa_ctx* ctx, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K,
+                        const int32_t* group_idx, const int64_t* group_off, int32_t B,
+                        const void* eig /* (K,M,B,3) complex64 */, int64_t M, int32_t flags /* PSA_F_DISPLACEMENTS or 0 */,
+                        float* out_host /* (L,K,M) */, size_t out_bytes);
+/* psa_sed_modes_welch and the fit of its (L, K M) result where it lies: psa_sed_modes_welch's arguments and refusals,
+ * then the fit's with F = L, C = K M (column k M + nu); df is the caller's (1 / (L dt) for bins of the segment
+ * transform).  out_host may be NULL: the spectra are then not copied to the host. */
+int psa_sed_modes_welch_fit(psa_ctx* ctx, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K,
+                            const int32_t* group_idx, const int64_t* group_off, int32_t B, const void* eig, int64_t M,
+                            int32_t flags, double df, const int32_t* bands, int32_t lo, int32_t hi, const psa_peak_opts* opts,
+                            float* fit /* (K*M,6) */, int32_t* info /* (K*M,4) */, float* out_host, size_t out_bytes);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is
@@ -456,6 +487,12 @@ int psa_debug_project_frames(psa_ctx* ctx, int slot, const float* mean_pos_all,
  * they are (no division by T), eig (K,M,B,3) complex64 -> out_host (T,K,M) float32 = |sum_{b,c} conj(eig) S|^2 */
 int psa_debug_mode_power(psa_ctx* ctx, const void* S_host, const void* eig, int32_t B, int64_t K, int64_t M, int64_t T,
                          float* out_host);
+/* the contraction kernel of psa_sed_modes_welch alone, on transformed segments the caller uploads: S_host (B,K,3,ns,L)
+ * complex64 taken as they are, eig (K,M,B,3) complex64 -> out_host (L,K,M) float32 = sum_s scale |sum_{b,c} conj(eig) S_s|^2.
+ * seg_block = 0: one launch; seg_block > 0: launches of at most that many segments, the later ones adding to the result
+ * of the earlier (the path a budget-bound call takes) */
+int psa_debug_mode_power_welch(psa_ctx* ctx, const void* S_host, const void* eig, int32_t B, int64_t K, int64_t M, int64_t L,
+                               int64_t ns, int64_t seg_block, float scale, float* out_host);
 /* number of plane sets in the cache and their bytes */
 int psa_debug_plane_cache(psa_ctx* ctx, int64_t* n_sets, int64_t* bytes);
 

@@ -78,6 +78,11 @@ SIGNATURES = {
     "psa_sed_modes_fit": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p, _i64p, C.c_int32, C.c_void_p, C.c_int64,
                                     C.c_int32, C.c_double, _i32p, C.c_int32, C.c_int32, C.c_void_p, _f32p, _i32p, _f32p,
                                     C.c_size_t]),
+    "psa_sed_modes_welch": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p, _i64p, C.c_int32, C.c_void_p, C.c_int64,
+                                      C.c_int32, _f32p, C.c_size_t]),
+    "psa_sed_modes_welch_fit": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p, _i64p, C.c_int32, C.c_void_p,
+                                          C.c_int64, C.c_int32, C.c_double, _i32p, C.c_int32, C.c_int32, C.c_void_p, _f32p,
+                                          _i32p, _f32p, C.c_size_t]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
@@ -98,6 +103,8 @@ SIGNATURES = {
     "psa_debug_project_frames": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p,
                                            C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
     "psa_debug_mode_power": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _f32p]),
+    "psa_debug_mode_power_welch": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                             C.c_int64, C.c_int64, C.c_float, _f32p]),
     "psa_debug_plane_cache": (C.c_int, [_ctx, _i64p, _i64p]),
     "psa_comm_unique_id": (C.c_int, [C.c_void_p]),
     "psa_comm_init": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int]),
@@ -615,12 +622,8 @@ class Engine:
             off.ctypes.data_as(_i64p) if off is not None else None, G, flags, _f32(out), out.nbytes), "psa_vdos")
         return np.ascontiguousarray(out.transpose(2, 0, 1))
 
-    def sed_modes(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags=0) -> np.ndarray:
-        """Mode-projected SED of the resident array (psa_sed_modes): (T, K, M) float32 = |sum_{b,c} conj(eig) S_b|^2 for
-        the B disjoint site groups (index arrays; None: all atoms as one group) and `eigenvectors` (K, M, B, 3)
-        complex64, with the context's atom weights; the definition is in psa_amd/modes.py.  The result of the SED entry
-        points resident on the device is not touched."""
-        T, _ = self.shape(slot)
+    def _sed_modes(self, entry, rows, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags):
+        """psa_sed_modes / psa_sed_modes_welch (`entry`) into a pinned (rows, K, M) float32 array"""
         mean = _as_f32(mean_pos_all, (3,))
         kv = _as_f32(k_vectors, (3,))
         idx, off, B = pack_groups(groups)
@@ -629,13 +632,27 @@ class Engine:
         if eig.ndim != 4 or eig.shape[0] != K or eig.shape[2:] != (B, 3) or eig.shape[1] < 1:
             raise ValueError(f"eigenvectors have shape {eig.shape}, expected (K, M, B, 3) = ({K}, M, {B}, 3)")
         M = eig.shape[1]
-        out = pinned_empty((T, K, M), np.float32)
-        _check(self._lib.psa_sed_modes(
+        out = pinned_empty((rows, K, M), np.float32)
+        _check(getattr(self._lib, entry)(
             self._h, slot, _f32(mean), _f32(kv), K,
             idx.ctypes.data_as(_i32p) if idx is not None else None,
             off.ctypes.data_as(_i64p) if off is not None else None, B,
-            eig.ctypes.data_as(C.c_void_p), M, flags, _f32(out), out.nbytes), "psa_sed_modes")
+            eig.ctypes.data_as(C.c_void_p), M, flags, _f32(out), out.nbytes), entry)
         return out
+
+    def sed_modes(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags=0) -> np.ndarray:
+        """Mode-projected SED of the resident array (psa_sed_modes): (T, K, M) float32 = |sum_{b,c} conj(eig) S_b|^2 for
+        the B disjoint site groups (index arrays; None: all atoms as one group) and `eigenvectors` (K, M, B, 3)
+        complex64, with the context's atom weights; the definition is in psa_amd/modes.py.  The result of the SED entry
+        points resident on the device is not touched."""
+        return self._sed_modes("psa_sed_modes", self.shape(slot)[0], slot, mean_pos_all, k_vectors, groups, eigenvectors, flags)
+
+    def sed_modes_welch(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags=0) -> np.ndarray:
+        """`sed_modes` averaged over the context's Welch segments (psa_sed_modes_welch; `set_segments`): (L, K, M)
+        float32 = 1/(n_seg U) sum_s |sum_{b,c} conj(eig) F_b,s|^2.  With no segments set: one boxcar segment of all T
+        frames, L = T."""
+        return self._sed_modes("psa_sed_modes_welch", self.segment_length or self.shape(slot)[0], slot, mean_pos_all, k_vectors,
+                               groups, eigenvectors, flags)
 
     def fit_peaks(self, spectrum, df, *, band=None, centers=None, search=None, window_hwhm=8.0, half_window=None,
                   max_iter=50):
@@ -655,13 +672,10 @@ class Engine:
                                        C.byref(opts), _f32(fit), info.ctypes.data_as(_i32p)), "psa_fit_peaks")
         return peaks.PeakFit.from_arrays(fit, info, shape)
 
-    def sed_modes_fit(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, df, flags=0, *, return_sed=False, band=None,
-                      centers=None, search=None, window_hwhm=8.0, half_window=None, max_iter=50):
-        """`sed_modes` and `fit_peaks` of its result in one library call (psa_sed_modes_fit): the (T, K, M) spectra are
-        fitted where they lie and cross to the host only with `return_sed`.  Returns (PeakFit with (K, M) fields, the
-        spectra or None)."""
+    def _sed_modes_fit(self, entry, rows, slot, mean_pos_all, k_vectors, groups, eigenvectors, df, flags, return_sed, band,
+                       centers, search, window_hwhm, half_window, max_iter):
+        """psa_sed_modes_fit / psa_sed_modes_welch_fit (`entry`) of spectra with `rows` frequency bins"""
         from . import peaks
-        T, _ = self.shape(slot)
         mean = _as_f32(mean_pos_all, (3,))
         kv = _as_f32(k_vectors, (3,))
         idx, off, B = pack_groups(groups)
@@ -671,18 +685,34 @@ class Engine:
             raise ValueError(f"eigenvectors have shape {eig.shape}, expected (K, M, B, 3) = ({K}, M, {B}, 3)")
         M = eig.shape[1]
         peaks.check_fit_options(window_hwhm, max_iter)
-        bands = peaks.peak_bands(T, df, K * M, band, centers, search)
+        bands = peaks.peak_bands(rows, df, K * M, band, centers, search)
         opts = PeakOpts(float(window_hwhm), peaks.half_window_bins(half_window, df), int(max_iter))
         fit, info = np.empty((K * M, 6), np.float32), np.empty((K * M, 4), np.int32)
-        out = pinned_empty((T, K, M), np.float32) if return_sed else None
-        _check(self._lib.psa_sed_modes_fit(
+        out = pinned_empty((rows, K, M), np.float32) if return_sed else None
+        _check(getattr(self._lib, entry)(
             self._h, slot, _f32(mean), _f32(kv), K,
             idx.ctypes.data_as(_i32p) if idx is not None else None,
             off.ctypes.data_as(_i64p) if off is not None else None, B,
             eig.ctypes.data_as(C.c_void_p), M, flags, float(df), bands.ctypes.data_as(_i32p), 0, 0, C.byref(opts),
             _f32(fit), info.ctypes.data_as(_i32p), _f32(out) if out is not None else None,
-            out.nbytes if out is not None else 0), "psa_sed_modes_fit")
+            out.nbytes if out is not None else 0), entry)
         return peaks.PeakFit.from_arrays(fit, info, (K, M)), out
+
+    def sed_modes_fit(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, df, flags=0, *, return_sed=False, band=None,
+                      centers=None, search=None, window_hwhm=8.0, half_window=None, max_iter=50):
+        """`sed_modes` and `fit_peaks` of its result in one library call (psa_sed_modes_fit): the (T, K, M) spectra are
+        fitted where they lie and cross to the host only with `return_sed`.  Returns (PeakFit with (K, M) fields, the
+        spectra or None)."""
+        return self._sed_modes_fit("psa_sed_modes_fit", self.shape(slot)[0], slot, mean_pos_all, k_vectors, groups, eigenvectors,
+                                   df, flags, return_sed, band, centers, search, window_hwhm, half_window, max_iter)
+
+    def sed_modes_welch_fit(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, df, flags=0, *, return_sed=False,
+                            band=None, centers=None, search=None, window_hwhm=8.0, half_window=None, max_iter=50):
+        """`sed_modes_welch` and `fit_peaks` of its (L, K, M) result in one library call (psa_sed_modes_welch_fit); `df`
+        is the step of the segment transform, 1 / (L dt).  Returns (PeakFit with (K, M) fields, the spectra or None)."""
+        return self._sed_modes_fit("psa_sed_modes_welch_fit", self.segment_length or self.shape(slot)[0], slot, mean_pos_all,
+                                   k_vectors, groups, eigenvectors, df, flags, return_sed, band, centers, search, window_hwhm,
+                                   half_window, max_iter)
 
     def debug_mode_power(self, spectra: np.ndarray, eigenvectors: np.ndarray) -> np.ndarray:
         """The contraction kernel of `sed_modes` alone (psa_debug_mode_power): spectra (B, K, 3, T) complex64 taken as
@@ -696,6 +726,25 @@ class Engine:
         out = np.empty((T, K, M), np.float32)
         _check(self._lib.psa_debug_mode_power(self._h, S.ctypes.data_as(C.c_void_p), eig.ctypes.data_as(C.c_void_p), B, K, M, T,
                                               _f32(out)), "psa_debug_mode_power")
+        return out
+
+    def debug_mode_power_welch(self, segments: np.ndarray, eigenvectors: np.ndarray, scale: float = 1.0, seg_block: int = 0
+                               ) -> np.ndarray:
+        """The contraction kernel of `sed_modes_welch` alone (psa_debug_mode_power_welch): transformed segments
+        (B, K, 3, ns, L) complex64 taken as they are, eigenvectors (K, M, B, 3) complex64 -> (L, K, M) float32 =
+        sum_s scale |sum conj(eig) S_s|^2; `seg_block` > 0: launches of at most that many segments."""
+        S = np.ascontiguousarray(segments, np.complex64)
+        eig = np.ascontiguousarray(eigenvectors, np.complex64)
+        if S.ndim != 5 or S.shape[2] != 3 or eig.ndim != 4 or eig.shape[0] != S.shape[1] or eig.shape[2:] != (S.shape[0], 3):
+            raise ValueError(f"segments {S.shape} and eigenvectors {eig.shape} do not fit (B,K,3,ns,L) and (K,M,B,3)")
+        if int(seg_block) < 0:
+            raise ValueError(f"seg_block = {seg_block} must not be negative")
+        B, K, _, ns, L = S.shape
+        M = eig.shape[1]
+        out = np.empty((L, K, M), np.float32)
+        _check(self._lib.psa_debug_mode_power_welch(self._h, S.ctypes.data_as(C.c_void_p), eig.ctypes.data_as(C.c_void_p), B, K, M,
+                                                    L, ns, int(seg_block), float(scale), _f32(out)),
+               "psa_debug_mode_power_welch")
         return out
 
     def set_kmap(self, kmap: np.ndarray):

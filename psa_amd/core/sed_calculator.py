@@ -455,7 +455,7 @@ class SEDCalculator:
     def calculate_mode_sed(self, k_points_mags: np.ndarray, k_vectors_3d: np.ndarray, eigenvectors: np.ndarray,
                            basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
                            basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
-                           atom_weights: Optional[np.ndarray] = None) -> ModeSED:
+                           atom_weights: Optional[np.ndarray] = None, segments: Optional[Segments] = None) -> ModeSED:
         """Mode-projected SED (normal-mode decomposition; not in the reference; definition in psa_amd/modes.py):
 
             Phi[w,k,nu] = | sum_b sum_c conj(eigenvectors[k,nu,b,c]) S_b[k,c,w] |^2
@@ -469,13 +469,16 @@ class SEDCalculator:
         given: no normalisation, M free.  The phase convention is the projection's, exp(+i k.r_a) with each atom's own
         mean position, and the vectors enter conjugated; converting the vectors of a lattice-dynamics code that uses
         another convention is the caller's business.  Pairs (k, -k) are not folded.  `atom_weights` as for `calculate`
-        (`psa_amd.mass_weights` for the mass-weighted mode coordinate).  A sharded calculator refuses
+        (`psa_amd.mass_weights` for the mass-weighted mode coordinate).  `segments` (keyword only): a
+        `psa_amd.Segments` -- the Welch average of the mode spectra over segments of the projected series, taken
+        between the projection and the contraction (psa_amd/modes.py): `sed` is then (L, K, M) and `freqs`
+        np.fft.fftfreq(L, dt_ps); TypeError for anything else, ValueError if L > T.  A sharded calculator refuses
         (NotImplementedError).  Returns a `psa_amd.ModeSED` with `sed` (T, K, M) float32."""
         weights, eig, k_vectors, groups, empty = self._mode_inputs(k_points_mags, k_vectors_3d, eigenvectors,
-                                                                   basis_atom_indices, basis_atom_types, atom_weights)
+                                                                   basis_atom_indices, basis_atom_types, atom_weights, segments)
         if empty is not None:
             return empty
-        freqs = np.fft.fftfreq(self.traj.n_frames, d=self.dt_ps)
+        freqs = np.fft.fftfreq(self.traj.n_frames if segments is None else segments.length, d=self.dt_ps)
         mean_pos_all = self._mean_positions()
         slot, data, flags = self._data_slot()
         eng = self.engine
@@ -483,17 +486,26 @@ class SEDCalculator:
             if weights is not None:
                 eng.set_atom_weights(weights)
             try:
+                if segments is not None:             # (before the upload: its FFT primer then builds length L)
+                    eng.set_segments(segments)
                 eng.ensure_resident(slot, data)      # later SED calls find it resident
-                phi = eng.sed_modes(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64), flags)
+                run = eng.sed_modes if segments is None else eng.sed_modes_welch
+                phi = run(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64), flags)
             finally:
                 if weights is not None:
                     eng.set_atom_weights(None)
+                if segments is not None:
+                    eng.set_segments(None)
         return ModeSED(phi, freqs, k_points_mags, k_vectors_3d, [np.asarray(g) for g in groups])
 
-    def _mode_inputs(self, k_points_mags, k_vectors_3d, eigenvectors, basis_atom_indices, basis_atom_types, atom_weights):
+    def _mode_inputs(self, k_points_mags, k_vectors_3d, eigenvectors, basis_atom_indices, basis_atom_types, atom_weights,
+                     segments=None):
         """What the mode projections check and resolve: (weights, eig, k_vectors (K, 3) float32, groups, the empty ModeSED
-        to return as it is -- no frames, no atoms or no k-vectors -- or None)."""
+        to return as it is -- no frames, no atoms or no k-vectors -- or None).  `segments` are validated as `calculate`
+        validates them."""
         weights = None if atom_weights is None else check_atom_weights(atom_weights, self.traj.n_atoms)
+        if segments is not None and not isinstance(segments, Segments):
+            raise TypeError(f"segments must be a psa_amd.Segments, got {type(segments).__name__}")
         if self._shard is not None and self._shard.nranks > 1:
             raise NotImplementedError("the mode-projected SED is not available on a sharded calculator")
         eig = np.asarray(eigenvectors)
@@ -503,6 +515,8 @@ class SEDCalculator:
             logger.warning("Cannot calculate the mode-projected SED: 0 frames or 0 atoms.")
             return weights, eig, k_vectors, [], ModeSED(np.zeros((0, 0, 0), np.float32), np.zeros(0, np.float64), k_points_mags,
                                                         k_vectors_3d, [])
+        if segments is not None:
+            segments.count(n_t)                          # ValueError if L > T
         if (basis_atom_types is None and isinstance(basis_atom_indices, (list, tuple)) and len(basis_atom_indices)
                 and all(isinstance(g, np.ndarray) for g in basis_atom_indices)):
             # index arrays (`site_groups`) are taken as they are, with the checks of `_resolve_groups`: no detour
@@ -524,8 +538,9 @@ class SEDCalculator:
             raise ValueError("eigenvectors must be finite")
         if n_k == 0:
             logger.warning("k_vectors_3d is empty. Returning ModeSED object with empty data.")
-            return weights, eig, k_vectors, groups, ModeSED(np.zeros((n_t, 0, eig.shape[1]), np.float32),
-                                                            np.fft.fftfreq(n_t, d=self.dt_ps), k_points_mags, k_vectors_3d,
+            n_f = n_t if segments is None else segments.length
+            return weights, eig, k_vectors, groups, ModeSED(np.zeros((n_f, 0, eig.shape[1]), np.float32),
+                                                            np.fft.fftfreq(n_f, d=self.dt_ps), k_points_mags, k_vectors_3d,
                                                             [np.asarray(g) for g in groups])
         return weights, eig, k_vectors, groups, None
 
@@ -533,23 +548,26 @@ class SEDCalculator:
                              basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
                              basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
                              atom_weights: Optional[np.ndarray] = None, return_sed: bool = False, band=None, centers=None,
-                             search=None, window_hwhm: float = 8.0, half_window: Optional[float] = None, max_iter: int = 50
-                             ) -> Union[PeakFit, Tuple[PeakFit, ModeSED]]:
+                             search=None, window_hwhm: float = 8.0, half_window: Optional[float] = None, max_iter: int = 50,
+                             segments: Optional[Segments] = None) -> Union[PeakFit, Tuple[PeakFit, ModeSED]]:
         """Frequency and lifetime of every mode (k, nu): `calculate_mode_sed` and a Lorentzian fit of the peak of each of
         its K x M columns (definition in psa_amd/peaks.py), in one pass on the GPU -- the (T, K, M) spectra are fitted
         where they lie and do not cross to the host unless `return_sed` asks for them.
 
-        The projection's arguments, checks, weights and restrictions are those of `calculate_mode_sed` (not sharded;
-        no segment average).  `band` = (fmin, fmax) THz searched in every column (default: all positive frequencies);
+        The projection's arguments, checks, weights and restrictions are those of `calculate_mode_sed` (not sharded).
+        `segments`: as there -- the Welch-averaged (L, K, M) spectra are fitted instead, with the frequency step
+        1 / (L dt_ps); on thermal data this is what makes the fits converge (a single periodogram is noise of the
+        size of the signal), at the price of resolution: choose L so that a peak's half width spans a few bins.
+        `band` = (fmin, fmax) THz searched in every column (default: all positive frequencies);
         `centers` (K, M) THz with `search`: each mode's own interval center +- search, for spectra in which a column
         shows more than its own branch; `window_hwhm`, `half_window`, `max_iter` as for `Engine.fit_peaks`.  Returns a
         `psa_amd.PeakFit` with (K, M) fields (`frequency`, `hwhm`, `lifetime`, `status`, ...); with `return_sed`
         (PeakFit, ModeSED)."""
         weights, eig, k_vectors, groups, empty = self._mode_inputs(k_points_mags, k_vectors_3d, eigenvectors,
-                                                                   basis_atom_indices, basis_atom_types, atom_weights)
+                                                                   basis_atom_indices, basis_atom_types, atom_weights, segments)
         if empty is not None:
             raise ValueError("nothing to fit: the trajectory has no frames or atoms, or the k-list is empty")
-        n_t = self.traj.n_frames
+        n_t = self.traj.n_frames if segments is None else segments.length      # frequency bins of the fitted spectra
         freqs = np.fft.fftfreq(n_t, d=self.dt_ps)
         mean_pos_all = self._mean_positions()
         slot, data, flags = self._data_slot()
@@ -558,13 +576,18 @@ class SEDCalculator:
             if weights is not None:
                 eng.set_atom_weights(weights)
             try:
+                if segments is not None:             # (before the upload: its FFT primer then builds length L)
+                    eng.set_segments(segments)
                 eng.ensure_resident(slot, data)      # later SED calls find it resident
-                fit, phi = eng.sed_modes_fit(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64),
-                                             1.0 / (n_t * self.dt_ps), flags, return_sed=return_sed, band=band, centers=centers,
-                                             search=search, window_hwhm=window_hwhm, half_window=half_window, max_iter=max_iter)
+                run = eng.sed_modes_fit if segments is None else eng.sed_modes_welch_fit
+                fit, phi = run(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64),
+                               1.0 / (n_t * self.dt_ps), flags, return_sed=return_sed, band=band, centers=centers,
+                               search=search, window_hwhm=window_hwhm, half_window=half_window, max_iter=max_iter)
             finally:
                 if weights is not None:
                     eng.set_atom_weights(None)
+                if segments is not None:
+                    eng.set_segments(None)
         if not return_sed:
             return fit
         return fit, ModeSED(phi, freqs, k_points_mags, k_vectors_3d, [np.asarray(g) for g in groups])

@@ -6,19 +6,6 @@
 
 namespace psa {
 
-namespace {
-
-struct PeakArgs {
-    int64_t        F, C;
-    double         df;
-    const int32_t* bands;
-    int32_t        lo, hi;
-    psa_peak_opts  opts;
-    float*         fit;
-    int32_t*       info;
-    int            row0 = 0, row_end = 0;      // the rows some band covers
-};
-
 int check_peak_args(const psa_peak_opts* opts, PeakArgs* a) {
     a->opts = opts ? *opts : psa_peak_opts{8.f, 0, 50};
     PSA_REQUIRE(a->fit != nullptr, "null fit");
@@ -80,6 +67,8 @@ int peaks_run(psa_ctx* c, const float* d_spec, const PeakArgs& a) {
     PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return PSA_OK;
 }
+
+namespace {
 
 int fit_uploaded(psa_ctx* c, const float* spec_host, PeakArgs* a, const psa_peak_opts* opts) {
     PSA_REQUIRE(spec_host != nullptr, "null spec_host");

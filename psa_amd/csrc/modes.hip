@@ -17,12 +17,11 @@
 // stores a whole row of the result apart.  The (w, k, nu) tile therefore goes through LDS (row stride 4 MT + 1
 // floats: the column writes of the 64 lanes fall into 64 different banks) and leaves as runs of 4 MT consecutive
 // floats per frequency (16 M bytes when M fits one pass), consecutive lanes on consecutive addresses.
+// The tile constants and the row walk are shared with the segment-averaging sibling (modes_welch.hip): modes_rows.h.
+#include "modes_rows.h"
 #include "psa_ctx.h"
 
 namespace psa {
-
-constexpr int MODES_TW = 64;   // frequencies per workgroup tile: one per lane
-constexpr int MODES_TK = 4;    // k-vectors per workgroup tile: one per wavefront
 
 // Modes per pass for M mode vectors.  A pass costs its rows' loads once (about 8 FMA-equivalents per row and lane)
 // plus 4 MT FMAs per row, padding included: the cheapest of 8, 16, 24, 32; ties go to the wider tile.
@@ -35,8 +34,6 @@ int modes_tile(int64_t M) {
     }
     return best;
 }
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));   // (re, im): one v_pk_fma_f32 per product
 
 // S: (B, nk, 3, T) complex64, the unscaled spectra of one block of nk k-vectors; coef: the block's part of the
 // packed table; out: (T, K_pitch, M) float32, the block's columns starting at k_col0; inv_n2: 1/T^2 (1 when the
@@ -58,23 +55,7 @@ mode_power_kernel(const float2* __restrict__ S, const float2* __restrict__ coef,
 #pragma unroll
             for (int j = 0; j < MT; ++j) acc[j] = f32x2{0.f, 0.f};
             const float2* cf = coef + ((size_t)k * n_pass + p) * (size_t)n3 * MT;
-            for (int b = 0; b < B; ++b) {
-                const float2* row = S + ((size_t)b * nk + k) * 3 * (size_t)T + t;
-                float2        s[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) s[c] = t < T ? row[(size_t)c * T] : make_float2(0.f, 0.f);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const f32x2   xy = {s[c].x, s[c].y}, yx = {-s[c].y, s[c].x};
-                    const float2* e = cf + (size_t)(3 * b + c) * MT;
-#pragma unroll
-                    for (int j = 0; j < MT; ++j) {              // (p + iq)(x + iy), p + iq = conj(eig)
-                        const float2 pq = e[j];
-                        acc[j] = __builtin_elementwise_fma(f32x2{pq.x, pq.x}, xy, acc[j]);
-                        acc[j] = __builtin_elementwise_fma(f32x2{pq.y, pq.y}, yx, acc[j]);
-                    }
-                }
-            }
+            mode_rows<MT>(acc, S + (size_t)k * 3 * (size_t)T + t, (size_t)nk * 3 * (size_t)T, (size_t)T, cf, B, t < T);
 #pragma unroll
             for (int j = 0; j < MT; ++j) {
                 tile[lane][wave * MT + j] = fmaf(acc[j].x, acc[j].x, acc[j].y * acc[j].y) * inv_n2;

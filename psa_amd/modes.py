@@ -18,6 +18,18 @@ position, not the origin of its cell, and the vectors enter conjugated.  Eigenve
 (phonopy, GULP) that uses exp(-i k.r), cell origins, or another ordering of the sites have to be converted by the
 caller.  Pairs (k, -k) are not folded: every k-vector has its own vectors.  With unitary vectors (M = 3B) the columns
 sum to the incoherent SED of the B groups; with the Cartesian unit vectors they are its |S_b[k,c,w]|^2.
+
+Welch average (`calculate_mode_sed(..., segments=psa_amd.Segments(L, H, window))`; conventions of psa_amd/segments.py:
+n_seg = 1 + (T - L) // H, U = (1/L) sum win^2, no detrending, two-sided, FFT order, frames after the last segment
+unused).  The segments are cut from the projected series, between the projection and the contraction:
+
+    F_b,s[k,c,w] = (1/L) sum_tau win[tau] q_b[k,c,s H + tau] exp(-2 pi i w tau / L)
+    Q_s[k,nu,w]  = sum_b sum_c conj(eig[k,nu,b,c]) F_b,s[k,c,w]
+    Phi[w,k,nu]  = 1/(n_seg U) sum_s |Q_s[k,nu,w]|^2                (L, K, M) float32, freqs = fftfreq(L, dt_ps)
+
+One boxcar segment of T frames is the definition above.  With the Cartesian unit vectors of one site (M = 3) the sum
+over nu is the segment-averaged `calculate` of that site.  The noise of a thermal spectrum falls as 1/sqrt(n_seg) --
+which is what lets `calculate_mode_peaks(..., segments=...)` converge on it -- at the price of resolution: 1 / (L dt).
 """
 from __future__ import annotations
 
@@ -30,7 +42,7 @@ import numpy as np
 @dataclass
 class ModeSED:
     """Result of `SEDCalculator.calculate_mode_sed`: `sed` (T, K, M) float32 per frequency, k-point and mode vector;
-    `freqs` (T,) = np.fft.fftfreq(T, dt_ps); `k_points` (K,), `k_vectors` (K, 3); `groups`: the B atom-index arrays."""
+    `freqs` (T,) = np.fft.fftfreq(T, dt_ps) -- (L, K, M) and fftfreq(L, dt_ps) with `segments` of length L; `k_points` (K,), `k_vectors` (K, 3); `groups`: the B atom-index arrays."""
     sed: np.ndarray
     freqs: np.ndarray
     k_points: np.ndarray

@@ -2,7 +2,8 @@
 Frequencies and lifetimes: Lorentzian fits of spectrum peaks on the GPU (psa_fit_peaks; kernels: csrc/peaks.hip).
 
 A spectrum is phi (F, ...) float32 whose row i is bin i of an F-point transform, f_i = i df with df = 1 / (F dt_ps) THz --
-the (T, K, M) mode spectra of `calculate_mode_sed`, the (T, K) or Welch-averaged (L, K) SED of `calculate`.  Only the
+the (T, K, M) mode spectra of `calculate_mode_sed` or its Welch-averaged (L, K, M) spectra (`segments=`; F = L, what
+`calculate_mode_peaks(..., segments=...)` fits), the (T, K) or Welch-averaged (L, K) SED of `calculate`.  Only the
 positive half is used, bins 1 .. ceil(F/2) - 1 (no DC, no Nyquist).  Every column is fitted on its own:
 
     band     [lo, hi) bins: `band` = (fmin, fmax) THz for all columns (default: the positive half), with `centers` (one

@@ -11,9 +11,13 @@ warm-up, medians of `--runs` calls of
   (c) the incoherent `calculate` of the same 8 groups, which does the same projections and the same transforms;
   (d) with --peaks: SEDCalculator.calculate_mode_peaks() end to end without and with `return_sed`, the stage times of
       psa_sed_modes_fit (the two fit kernels are in the "epilogue" stage beside the contraction) and the statuses.
-Kernel time of mode_power_kernel, peak_find_kernel, peak_fit_kernel: run it under `rocprofv3 --kernel-trace --stats`
-(with --skip-baseline).
-    python tools/modes_timing.py [--cfg C3] [--n-k 256] [--modes 24] [--runs 10] [--skip-baseline] [--peaks]"""
+  (e) with --segments L,H (Hann window): the same for the Welch-averaged mode spectra beside the figures above, measured
+      in the same process -- the stage times of psa_sed_modes_welch (window and contraction in the "epilogue" stage),
+      calculate_mode_sed(segments=...) end to end and, with --peaks, calculate_mode_peaks(segments=...), the stage times of
+      psa_sed_modes_welch_fit and the statuses; the contraction's floors are those of mode_welch_kernel.
+Kernel time of mode_power_kernel, mode_welch_kernel, peak_find_kernel, peak_fit_kernel: run it under `rocprofv3
+--kernel-trace --stats` (with --skip-baseline).
+    python tools/modes_timing.py [--cfg C3] [--n-k 256] [--modes 24] [--runs 10] [--skip-baseline] [--peaks] [--segments L,H]"""
 import argparse
 import json
 import sys
@@ -24,7 +28,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 import numpy as np                                                                   # noqa: E402
-from psa_amd import SEDCalculator, Trajectory, _hip, mass_weights, site_groups, synth     # noqa: E402
+from psa_amd import SEDCalculator, Segments, Trajectory, _hip, mass_weights, site_groups, synth     # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--cfg", default="C3")
@@ -35,7 +39,9 @@ ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--contract-frames", type=int, default=2048)
 ap.add_argument("--skip-baseline", action="store_true")
 ap.add_argument("--peaks", action="store_true")
+ap.add_argument("--segments", default=None, metavar="L,H", help="also measure the Welch average: segments of L frames, H apart, Hann")
 args = ap.parse_args()
+seg = Segments(*(int(v) for v in args.segments.split(",")), "hann") if args.segments else None
 
 spec, req = synth.baseline_spec(args.cfg)
 r0, types, box = synth.lattice(spec.cells)
@@ -71,15 +77,33 @@ def stages():
         eng.set_atom_weights(None)
 
 
-def e2e_modes():
+def stages_welch(fit=False):
+    """psa_last_timings of one psa_sed_modes_welch call (fit: psa_sed_modes_welch_fit, the spectra left on the device)"""
+    eng.set_atom_weights(w)
+    eng.set_segments(seg)
+    try:
+        eng.timings()
+        t0 = time.perf_counter()
+        if fit:
+            eng.sed_modes_welch_fit(0, r0, vecs, groups, eig, 1.0 / (seg.length * spec.dt_ps))
+        else:
+            eng.sed_modes_welch(0, r0, vecs, groups, eig)
+        call_ms = 1e3 * (time.perf_counter() - t0)
+        return dict(eng.timings(), call=call_ms)
+    finally:
+        eng.set_atom_weights(None)
+        eng.set_segments(None)
+
+
+def e2e_modes(segments=None):
     t0 = time.perf_counter()
-    calc.calculate_mode_sed(mags, vecs, eig, groups, atom_weights=w)
+    calc.calculate_mode_sed(mags, vecs, eig, groups, atom_weights=w, segments=segments)
     return 1e3 * (time.perf_counter() - t0)
 
 
-def e2e_peaks(return_sed=False):
+def e2e_peaks(return_sed=False, segments=None):
     t0 = time.perf_counter()
-    calc.calculate_mode_peaks(mags, vecs, eig, groups, atom_weights=w, return_sed=return_sed)
+    calc.calculate_mode_peaks(mags, vecs, eig, groups, atom_weights=w, return_sed=return_sed, segments=segments)
     return 1e3 * (time.perf_counter() - t0)
 
 
@@ -153,6 +177,27 @@ if args.peaks:
     out["peaks_window_bins"] = stats(fit.window[..., 1] - fit.window[..., 0])
     out["peak_find_bytes"] = 4 * ((T + 1) // 2 - 1) * K * M
     out["peak_find_floor_ms"] = out["peak_find_bytes"] / 8e12 * 1e3
+STAGES = ("h2d", "phase", "project", "fft", "epilogue", "d2h", "call")
+if seg is not None:
+    L, n_seg = seg.length, seg.count(T)
+    wb, wf = 24 * B * K * n_seg * L + 4 * L * K * M, 8 * 3 * B * M * L * K * n_seg
+    out["welch"] = dict(L=L, hop=seg.hop, n_seg=n_seg, window="hann", kernel_bytes=wb, kernel_flop=wf, floor_bytes_ms=wb / 8e12 * 1e3,
+                        floor_flop_ms=wf / 157e12 * 1e3, result_bytes=4 * L * K * M, segment_data_over_q=n_seg * L / T)
+    n0 = eng.lowrank_launches()
+    st = runs_of(stages_welch)
+    out["welch"]["lowrank_launches_per_call"] = (eng.lowrank_launches() - n0) / (args.warmup + args.runs)
+    out["welch"]["stages_ms"] = {k: float(np.median([r[k] for r in st])) for k in STAGES}
+    out["welch"]["e2e_modes_ms"] = stats(runs_of(lambda: e2e_modes(seg)))
+    if args.peaks:
+        st = runs_of(lambda: stages_welch(True))
+        out["welch"]["peaks_stages_ms"] = {k: float(np.median([r[k] for r in st])) for k in STAGES}
+        out["welch"]["e2e_peaks_ms"] = stats(runs_of(lambda: e2e_peaks(False, seg)))
+        out["welch"]["e2e_peaks_with_sed_ms"] = stats(runs_of(lambda: e2e_peaks(True, seg)))
+        fit = calc.calculate_mode_peaks(mags, vecs, eig, groups, atom_weights=w, segments=seg)
+        out["welch"]["peaks_statuses"] = np.bincount(fit.status.ravel(), minlength=4).tolist()
+        out["welch"]["peaks_iterations"] = stats(fit.iterations.ravel())
+        out["welch"]["peaks_window_bins"] = stats(fit.window[..., 1] - fit.window[..., 0])
+    out["e2e_modes_after_welch_ms"] = stats(runs_of(e2e_modes))           # the unsegmented call once more, same process
 if not args.skip_baseline:
     per_site_calls()                                                      # warm-up
     ms, spectra = zip(*[per_site_calls() for _ in range(3)])
