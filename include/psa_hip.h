@@ -333,7 +333,7 @@ int psa_vdos(psa_ctx* ctx, int slot, const float* mean_pos_all /* (N,3); read on
  *   out_bytes exactly 4 T K M.
  * PSA_EINVAL: eig or out_host null, M < 1, a non-finite eig value, an atom in two groups, an index out of range,
  * out_bytes not exact, segments set (psa_set_segments: no segment average here), weights set for another N, a work
- * budget (PSA_OPT_MODES_WORK_BYTES) below 24 B T bytes.
+ * budget (PSA_OPT_MODES_WORK_BYTES) below 24 B T bytes, T > 2^31 - 64 (the contraction indexes frequencies in 32 bits).
  * Per block of k-vectors: B projections into one stacked buffer (B, kb, 3, T), one batched rocFFT of 3 B kb series,
  * one pass (modes.hip) that contracts and takes the modulus; blocks of a k-path keep PSA_OPT_K1_LOWRANK_MIN_LOCAL
  * vectors where the budget allows.  The slab, the k map and every result of the SED entry points are left as they are;
@@ -392,7 +392,7 @@ int psa_sed_modes_fit(psa_ctx* ctx, int slot, const float* mean_pos_all, const f
  * (24 B T with no segments set: q is then transformed in place).
  * Per block of kb k-vectors the B projections are psa_sed_modes' own (plane cache, weights, displacement mode, the
  * low-rank k-path route, its block rule); then per sub-block of bk k-vectors x bs segments: the window pass into
- * (B, bk, 3, bs, L), one batched rocFFT of 3 B bk bs series of length L, one pass (modes_welch.hip) that contracts,
+ * (B, bk, 3, bs, L), one batched rocFFT of 3 B bk bs series of length L, one pass (modes.hip) that contracts,
  * takes the modulus and sums the sub-block's segments on chip; the first segments of a column overwrite it, later ones
  * add to it.  q and the segment buffer share the budget; the (L,K,M) result on the device is outside it.  No atomics;
  * launches in order on the context's stream: two identical calls give the same bits.  The slab, the k map, the plane

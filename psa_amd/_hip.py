@@ -622,8 +622,9 @@ class Engine:
             off.ctypes.data_as(_i64p) if off is not None else None, G, flags, _f32(out), out.nbytes), "psa_vdos")
         return np.ascontiguousarray(out.transpose(2, 0, 1))
 
-    def _sed_modes(self, entry, rows, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags):
-        """psa_sed_modes / psa_sed_modes_welch (`entry`) into a pinned (rows, K, M) float32 array"""
+    def _modes_args(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags):
+        """What the four mode entries are called with first (handle ... flags), K and M, and the arrays behind the
+        pointers, which the caller holds until the call has returned"""
         mean = _as_f32(mean_pos_all, (3,))
         kv = _as_f32(k_vectors, (3,))
         idx, off, B = pack_groups(groups)
@@ -632,12 +633,17 @@ class Engine:
         if eig.ndim != 4 or eig.shape[0] != K or eig.shape[2:] != (B, 3) or eig.shape[1] < 1:
             raise ValueError(f"eigenvectors have shape {eig.shape}, expected (K, M, B, 3) = ({K}, M, {B}, 3)")
         M = eig.shape[1]
+        head = (self._h, slot, _f32(mean), _f32(kv), K,
+                idx.ctypes.data_as(_i32p) if idx is not None else None,
+                off.ctypes.data_as(_i64p) if off is not None else None, B,
+                eig.ctypes.data_as(C.c_void_p), M, flags)
+        return head, K, M, (mean, kv, idx, off, eig)
+
+    def _sed_modes(self, entry, rows, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags):
+        """psa_sed_modes / psa_sed_modes_welch (`entry`) into a pinned (rows, K, M) float32 array"""
+        head, K, M, _held = self._modes_args(slot, mean_pos_all, k_vectors, groups, eigenvectors, flags)
         out = pinned_empty((rows, K, M), np.float32)
-        _check(getattr(self._lib, entry)(
-            self._h, slot, _f32(mean), _f32(kv), K,
-            idx.ctypes.data_as(_i32p) if idx is not None else None,
-            off.ctypes.data_as(_i64p) if off is not None else None, B,
-            eig.ctypes.data_as(C.c_void_p), M, flags, _f32(out), out.nbytes), entry)
+        _check(getattr(self._lib, entry)(*head, _f32(out), out.nbytes), entry)
         return out
 
     def sed_modes(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags=0) -> np.ndarray:
@@ -676,26 +682,15 @@ class Engine:
                        centers, search, window_hwhm, half_window, max_iter):
         """psa_sed_modes_fit / psa_sed_modes_welch_fit (`entry`) of spectra with `rows` frequency bins"""
         from . import peaks
-        mean = _as_f32(mean_pos_all, (3,))
-        kv = _as_f32(k_vectors, (3,))
-        idx, off, B = pack_groups(groups)
-        eig = np.ascontiguousarray(eigenvectors, np.complex64)
-        K = kv.shape[0]
-        if eig.ndim != 4 or eig.shape[0] != K or eig.shape[2:] != (B, 3) or eig.shape[1] < 1:
-            raise ValueError(f"eigenvectors have shape {eig.shape}, expected (K, M, B, 3) = ({K}, M, {B}, 3)")
-        M = eig.shape[1]
+        head, K, M, _held = self._modes_args(slot, mean_pos_all, k_vectors, groups, eigenvectors, flags)
         peaks.check_fit_options(window_hwhm, max_iter)
         bands = peaks.peak_bands(rows, df, K * M, band, centers, search)
         opts = PeakOpts(float(window_hwhm), peaks.half_window_bins(half_window, df), int(max_iter))
         fit, info = np.empty((K * M, 6), np.float32), np.empty((K * M, 4), np.int32)
         out = pinned_empty((rows, K, M), np.float32) if return_sed else None
         _check(getattr(self._lib, entry)(
-            self._h, slot, _f32(mean), _f32(kv), K,
-            idx.ctypes.data_as(_i32p) if idx is not None else None,
-            off.ctypes.data_as(_i64p) if off is not None else None, B,
-            eig.ctypes.data_as(C.c_void_p), M, flags, float(df), bands.ctypes.data_as(_i32p), 0, 0, C.byref(opts),
-            _f32(fit), info.ctypes.data_as(_i32p), _f32(out) if out is not None else None,
-            out.nbytes if out is not None else 0), entry)
+            *head, float(df), bands.ctypes.data_as(_i32p), 0, 0, C.byref(opts), _f32(fit), info.ctypes.data_as(_i32p),
+            _f32(out) if out is not None else None, out.nbytes if out is not None else 0), entry)
         return peaks.PeakFit.from_arrays(fit, info, (K, M)), out
 
     def sed_modes_fit(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, df, flags=0, *, return_sed=False, band=None,

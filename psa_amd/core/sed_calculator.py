@@ -22,6 +22,7 @@ chiral phase -> `SED`.
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import weakref
 from pathlib import Path
@@ -158,6 +159,24 @@ class SEDCalculator:
             return None
         return [np.asarray(g) for g in groups]
 
+    @contextlib.contextmanager
+    def _engine_state(self, weights, segments):
+        """The engine locked, with `weights` and `segments` (each only when not None: an engine without them never hears
+        of them) set for the block alone: no later calculation (iSED included) sees them."""
+        eng = self.engine
+        with eng.lock:
+            if weights is not None:
+                eng.set_atom_weights(weights)
+            try:
+                if segments is not None:     # (inside the try: cleared whatever happens)
+                    eng.set_segments(segments)
+                yield
+            finally:
+                if weights is not None:
+                    eng.set_atom_weights(None)
+                if segments is not None:
+                    eng.set_segments(None)
+
     def _run_device(self, k_vectors: np.ndarray, groups, intensity: bool, mean_pos_all,
                     fetch: bool = True, atom_weights: Optional[np.ndarray] = None,
                     segments: Optional[Segments] = None):
@@ -172,30 +191,20 @@ class SEDCalculator:
             flags |= _hip.F_INTENSITY
         want = not intensity
         eng = self.engine
-        with eng.lock:                       # project + finalize must not interleave across threads
+        with self._engine_state(atom_weights, segments):   # project + finalize must not interleave across threads
             K = len(k_vectors)
             T = self.traj.n_frames if segments is None else segments.length
-            if atom_weights is not None:     # (only then: an engine without weights never hears of them)
-                eng.set_atom_weights(atom_weights)
-            try:
-                if segments is not None:     # (inside the try: cleared whatever happens)
-                    eng.set_segments(segments)
-                if self._shard is not None and self._shard.nranks > 1:
-                    out = self._shard.run(slot, data, mean_pos_all, k_vectors, groups, flags, T, fetch, with_intensity=want)
-                elif not eng.is_resident(slot, data):
-                    # first call on this array: upload and project, overlapped
-                    eng.project_upload(slot, data, mean_pos_all, k_vectors, groups, flags)
-                    out = eng.finalize(T, K, intensity, fetch, with_intensity=want)
-                elif fetch:                  # one library call; long complex results leave block by block
-                    out = eng.calculate(slot, mean_pos_all, k_vectors, groups, flags, with_intensity=want)
-                else:
-                    eng.project(slot, mean_pos_all, k_vectors, groups, flags)
-                    out = eng.finalize(T, K, intensity, False, with_intensity=want)
-            finally:
-                if atom_weights is not None:  # no later calculation (iSED included) sees them
-                    eng.set_atom_weights(None)
-                if segments is not None:
-                    eng.set_segments(None)
+            if self._shard is not None and self._shard.nranks > 1:
+                out = self._shard.run(slot, data, mean_pos_all, k_vectors, groups, flags, T, fetch, with_intensity=want)
+            elif not eng.is_resident(slot, data):
+                # first call on this array: upload and project, overlapped
+                eng.project_upload(slot, data, mean_pos_all, k_vectors, groups, flags)
+                out = eng.finalize(T, K, intensity, fetch, with_intensity=want)
+            elif fetch:                  # one library call; long complex results leave block by block
+                out = eng.calculate(slot, mean_pos_all, k_vectors, groups, flags, with_intensity=want)
+            else:
+                eng.project(slot, mean_pos_all, k_vectors, groups, flags)
+                out = eng.finalize(T, K, intensity, False, with_intensity=want)
         if want:
             return out if out is not None else (None, None)
         return out, None
@@ -436,19 +445,9 @@ class SEDCalculator:
         slot, data, flags = self._data_slot()
         mean_pos_all = self._mean_positions() if self.use_displacements else None
         eng = self.engine
-        with eng.lock:
-            if weights is not None:
-                eng.set_atom_weights(weights)
-            try:
-                if segments is not None:             # (before the upload: its FFT primer then builds length L)
-                    eng.set_segments(segments)
-                eng.ensure_resident(slot, data)      # later SED calls find it resident
-                dos = eng.vdos(slot, mean_pos_all, self._device_groups(groups), flags)
-            finally:
-                if weights is not None:
-                    eng.set_atom_weights(None)
-                if segments is not None:
-                    eng.set_segments(None)
+        with self._engine_state(weights, segments):  # (segments before the upload: its FFT primer then builds length L)
+            eng.ensure_resident(slot, data)      # later SED calls find it resident
+            dos = eng.vdos(slot, mean_pos_all, self._device_groups(groups), flags)
         return VDOS(dos, np.fft.rfftfreq(L, d=self.dt_ps), [np.asarray(g) for g in groups])
 
     # ------------------------------------------------------------------ mode projection
@@ -482,20 +481,10 @@ class SEDCalculator:
         mean_pos_all = self._mean_positions()
         slot, data, flags = self._data_slot()
         eng = self.engine
-        with eng.lock:
-            if weights is not None:
-                eng.set_atom_weights(weights)
-            try:
-                if segments is not None:             # (before the upload: its FFT primer then builds length L)
-                    eng.set_segments(segments)
-                eng.ensure_resident(slot, data)      # later SED calls find it resident
-                run = eng.sed_modes if segments is None else eng.sed_modes_welch
-                phi = run(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64), flags)
-            finally:
-                if weights is not None:
-                    eng.set_atom_weights(None)
-                if segments is not None:
-                    eng.set_segments(None)
+        with self._engine_state(weights, segments):  # (segments before the upload: its FFT primer then builds length L)
+            eng.ensure_resident(slot, data)      # later SED calls find it resident
+            run = eng.sed_modes if segments is None else eng.sed_modes_welch
+            phi = run(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64), flags)
         return ModeSED(phi, freqs, k_points_mags, k_vectors_3d, [np.asarray(g) for g in groups])
 
     def _mode_inputs(self, k_points_mags, k_vectors_3d, eigenvectors, basis_atom_indices, basis_atom_types, atom_weights,
@@ -572,22 +561,12 @@ class SEDCalculator:
         mean_pos_all = self._mean_positions()
         slot, data, flags = self._data_slot()
         eng = self.engine
-        with eng.lock:
-            if weights is not None:
-                eng.set_atom_weights(weights)
-            try:
-                if segments is not None:             # (before the upload: its FFT primer then builds length L)
-                    eng.set_segments(segments)
-                eng.ensure_resident(slot, data)      # later SED calls find it resident
-                run = eng.sed_modes_fit if segments is None else eng.sed_modes_welch_fit
-                fit, phi = run(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64),
-                               1.0 / (n_t * self.dt_ps), flags, return_sed=return_sed, band=band, centers=centers,
-                               search=search, window_hwhm=window_hwhm, half_window=half_window, max_iter=max_iter)
-            finally:
-                if weights is not None:
-                    eng.set_atom_weights(None)
-                if segments is not None:
-                    eng.set_segments(None)
+        with self._engine_state(weights, segments):  # (segments before the upload: its FFT primer then builds length L)
+            eng.ensure_resident(slot, data)      # later SED calls find it resident
+            run = eng.sed_modes_fit if segments is None else eng.sed_modes_welch_fit
+            fit, phi = run(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64),
+                           1.0 / (n_t * self.dt_ps), flags, return_sed=return_sed, band=band, centers=centers,
+                           search=search, window_hwhm=window_hwhm, half_window=half_window, max_iter=max_iter)
         if not return_sed:
             return fit
         return fit, ModeSED(phi, freqs, k_points_mags, k_vectors_3d, [np.asarray(g) for g in groups])

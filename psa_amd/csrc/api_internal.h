@@ -9,8 +9,8 @@
 //   api_lowrank.hip  the low-rank route for k-paths: its plan and what a launch needs on the device
 //   api_shard.hip    sharding over RCCL: communicator, k-row gather, frame sharding
 //   api_vdos.hip     the vibrational density of states: a second, non-projecting pass over the resident array
-//   api_modes.hip    the mode-projected SED: the B site groups' spectra contracted with the mode vectors
-//   api_modes_welch.hip  the same with the Welch segment average between projection and contraction, and its fit
+//   api_modes.hip    the mode-projected SED: the B site groups' spectra contracted with the mode vectors, with or without
+//                    the Welch segment average between projection and contraction
 //   api_peaks.hip    Lorentzian peak fits of spectrum columns: an uploaded spectrum, or the mode spectra where they lie
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
 // k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
@@ -44,6 +44,15 @@ struct Guard {
 };
 
 int          enter(psa_ctx* c);                          // null check + hipSetDevice
+// how an entry point ends that hands the caller's arrays to the stream: they are only read or written during the call,
+// whichever way it ends
+inline int synchronised(psa_ctx* c, int rc, const char* entry) {
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == PSA_OK) {
+        set_error("hipStreamSynchronize failed after %s", entry);
+        return PSA_EHIP;
+    }
+    return rc;
+}
 TimingState& timing(psa_ctx* c);
 int          get_event(TimingState& ts, hipEvent_t* ev);
 int          collect(psa_ctx* c, TimingState& ts);
@@ -154,38 +163,24 @@ struct LowRankPlan {
 };
 int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, const int32_t* h_idx, int64_t n_g, LowRankPlan* p);
 int prepare_lowrank(psa_ctx* c, const GroupView& v, const ProjectArgs& list, int64_t k_first, int64_t nk, ProjGeom* g);
-// api_modes.hip: the pieces of a mode projection (psa_sed_modes, psa_sed_modes_welch and their fits)
-struct ModesCall {
-    int64_t                T = 0, N = 0, K = 0, M = 0;
-    int32_t                B = 0;
-    int                    MT = 0;       // modes per pass of the contraction (modes_tile)
-    size_t                 coef_k = 0;   // float2 per k-vector in the packed table
-    int64_t                per_k = 0;    // bytes of one k-vector in the stacked buffer (B, kb, 3, T): 24 B T
-    int64_t                kb_max = 0;   // most k-vectors a block may hold whatever the budget
-    ProjectArgs            list;         // the call's list (the low-rank route is offered on it)
-    std::vector<float>     coef;         // conj(eig) as the kernels read it: [k][pass][3B][MT]
-    std::vector<GroupView> src;          // the B groups and where their data comes from
+// api_modes.hip: what psa_sed_modes, psa_sed_modes_welch and their fits were called with, and their one body.  The result,
+// (T, K, M) or with segments (L, K, M), is left in c->d_modes_out.  `segments`: the context's segments are honoured or
+// refused.  out may be null only with `device_only` (the fits), and is then not copied to.
+struct ModesArgs {
+    int            slot;
+    const float*   mean_pos_all;
+    const float*   k_vectors;
+    int64_t        K;
+    const int32_t* group_idx;
+    const int64_t* group_off;
+    int32_t        B;
+    const float*   eig;
+    int64_t        M;
+    int32_t        flags;
+    float*         out;
+    size_t         out_bytes;
 };
-int pack_coef(const float* eig, int64_t K, int64_t M, int64_t B, int MT, std::vector<float>* coef);
-// every check that does not depend on segments, result size or budget (`what`: the entry point, for the flags message;
-// need_out: the caller requires an output it was not given), then the coefficient table and the sizes
-int modes_check(psa_ctx* c, const char* what, int slot_in, const float* mean_pos_all, const float* k_vectors, int64_t K,
-                const int32_t* group_idx, const int64_t* group_off, int32_t B, const float* eig, int64_t M, int32_t flags,
-                bool need_out, ModesCall* m);
-int modes_upload(psa_ctx* c, ModesCall* m);           // k-vectors, mean, lists, coefficients; resolves the group sources
-// k-vectors of the block that starts at k0 under a block size kb: a k-path leaves no tail below
-// PSA_OPT_K1_LOWRANK_MIN_LOCAL where the budget allows
-int64_t modes_block(const psa_ctx* c, const ModesCall& m, int64_t k0, int64_t kb);
-int modes_project(psa_ctx* c, const ModesCall& m, int64_t k0, int64_t nk, float2* d_work);   // the B groups into (B, nk, 3, T)
-// the body of psa_sed_modes; the (T, K, M) result is left in c->d_modes_out.  out_host may be null only
-// with `device_only` (psa_sed_modes_fit), and is then not copied to
-int modes_run(psa_ctx* c, int slot_in, const float* mean_pos_all, const float* k_vectors, int64_t K, const int32_t* group_idx,
-              const int64_t* group_off, int32_t B, const float* eig, int64_t M, int32_t flags, float* out_host, size_t out_bytes,
-              bool device_only);
-// api_modes_welch.hip: the same for psa_sed_modes_welch; the (L, K, M) result is left in c->d_modes_out
-int modes_welch_run(psa_ctx* c, int slot_in, const float* mean_pos_all, const float* k_vectors, int64_t K, const int32_t* group_idx,
-                    const int64_t* group_off, int32_t B, const float* eig, int64_t M, int32_t flags, float* out_host,
-                    size_t out_bytes, bool device_only);
+int modes_run(psa_ctx* c, const ModesArgs& a, bool segments, bool device_only);
 // api_peaks.hip: the arguments of a fit, and the fit of a spectrum (F, C) resident on the device
 struct PeakArgs {
     int64_t        F, C;

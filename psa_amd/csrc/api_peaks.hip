@@ -1,5 +1,5 @@
-// psa_fit_peaks / psa_sed_modes_fit: Lorentzian fits of the peaks of spectrum columns (definition: include/psa_hip.h;
-// kernels: peaks.hip).  The spectrum is either uploaded -- any (F, C) float32 array: an SED, a Welch-averaged SED, mode
+// psa_fit_peaks / psa_sed_modes_fit / psa_sed_modes_welch_fit: Lorentzian fits of the peaks of spectrum columns
+// (definition: include/psa_hip.h; kernels: peaks.hip).  The spectrum is either uploaded -- any (F, C) float32 array: an SED, a Welch-averaged SED, mode
 // spectra saved earlier -- or the result of the mode projection where it lies (psa_ctx::d_modes_out), so that of a
 // (T, K, M) array only 10 numbers per column cross to the host.  Nothing of the SED entry points' result state is touched.
 #include "api_internal.h"
@@ -80,16 +80,15 @@ int fit_uploaded(psa_ctx* c, const float* spec_host, PeakArgs* a, const psa_peak
     return peaks_run(c, c->d_peaks_spec.as<float>(), *a);
 }
 
-int fit_modes(psa_ctx* c, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K, const int32_t* group_idx,
-              const int64_t* group_off, int32_t B, const float* eig, int64_t M, int32_t flags, PeakArgs* a, const psa_peak_opts* opts,
-              float* out_host, size_t out_bytes) {
-    PSA_TRY(check_slot(c, slot));
-    PSA_REQUIRE(K >= 0 && K < (1ll << 29) && M >= 0 && M < (1ll << 30), "bad number of k-vectors %lld or mode vectors %lld",
-                (long long)K, (long long)M);
-    a->F = c->slot[slot].T, a->C = K * M;
-    PSA_TRY(check_peak_args(opts, a));
-    PSA_TRY(modes_run(c, slot, mean_pos_all, k_vectors, K, group_idx, group_off, B, eig, M, flags, out_host, out_bytes, true));
-    return peaks_run(c, c->d_modes_out.as<float>(), *a);
+// the mode spectra of `a` and their fit where they lie; `segments` as for modes_run
+int fit_modes(psa_ctx* c, const ModesArgs& a, bool segments, PeakArgs* p, const psa_peak_opts* opts) {
+    PSA_TRY(check_slot(c, a.slot));
+    PSA_REQUIRE(a.K >= 0 && a.K < (1ll << 29) && a.M >= 0 && a.M < (1ll << 30), "bad number of k-vectors %lld or mode vectors %lld",
+                (long long)a.K, (long long)a.M);
+    p->F = segments && c->seg_L ? c->seg_L : c->slot[a.slot].T, p->C = a.K * a.M;
+    PSA_TRY(check_peak_args(opts, p));
+    PSA_TRY(modes_run(c, a, segments, true));
+    return peaks_run(c, c->d_modes_out.as<float>(), *p);
 }
 
 }  // namespace
@@ -103,30 +102,30 @@ extern "C" {
 int psa_fit_peaks(psa_ctx* c, const float* spec_host, int64_t F, int64_t C, double df, const int32_t* bands, int32_t lo, int32_t hi,
                   const psa_peak_opts* opts, float* fit, int32_t* info) {
     PSA_TRY(enter(c));
-    Guard     guard(c);
-    PeakArgs  a{F, C, df, bands, lo, hi, {}, fit, info};
-    const int rc = fit_uploaded(c, spec_host, &a, opts);
-    // the caller's arrays are only read or written during the call, whichever way it ends
-    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == PSA_OK) {
-        set_error("hipStreamSynchronize failed after psa_fit_peaks");
-        return PSA_EHIP;
-    }
-    return rc;
+    Guard    guard(c);
+    PeakArgs a{F, C, df, bands, lo, hi, {}, fit, info};
+    return synchronised(c, fit_uploaded(c, spec_host, &a, opts), "psa_fit_peaks");
 }
 
 int psa_sed_modes_fit(psa_ctx* c, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K, const int32_t* group_idx,
                       const int64_t* group_off, int32_t B, const void* eig, int64_t M, int32_t flags, double df, const int32_t* bands,
                       int32_t lo, int32_t hi, const psa_peak_opts* opts, float* fit, int32_t* info, float* out_host, size_t out_bytes) {
     PSA_TRY(enter(c));
-    Guard     guard(c);
-    PeakArgs  a{0, 0, df, bands, lo, hi, {}, fit, info};
-    const int rc = fit_modes(c, slot, mean_pos_all, k_vectors, K, group_idx, group_off, B, (const float*)eig, M, flags, &a, opts,
-                             out_host, out_bytes);
-    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == PSA_OK) {
-        set_error("hipStreamSynchronize failed after psa_sed_modes_fit");
-        return PSA_EHIP;
-    }
-    return rc;
+    Guard           guard(c);
+    const ModesArgs a{slot, mean_pos_all, k_vectors, K, group_idx, group_off, B, (const float*)eig, M, flags, out_host, out_bytes};
+    PeakArgs        p{0, 0, df, bands, lo, hi, {}, fit, info};
+    return synchronised(c, fit_modes(c, a, false, &p, opts), "psa_sed_modes_fit");
+}
+
+int psa_sed_modes_welch_fit(psa_ctx* c, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K,
+                            const int32_t* group_idx, const int64_t* group_off, int32_t B, const void* eig, int64_t M, int32_t flags,
+                            double df, const int32_t* bands, int32_t lo, int32_t hi, const psa_peak_opts* opts, float* fit,
+                            int32_t* info, float* out_host, size_t out_bytes) {
+    PSA_TRY(enter(c));
+    Guard           guard(c);
+    const ModesArgs a{slot, mean_pos_all, k_vectors, K, group_idx, group_off, B, (const float*)eig, M, flags, out_host, out_bytes};
+    PeakArgs        p{0, 0, df, bands, lo, hi, {}, fit, info};
+    return synchronised(c, fit_modes(c, a, true, &p, opts), "psa_sed_modes_welch_fit");
 }
 
 }  // extern "C"

@@ -276,10 +276,10 @@ struct psa_ctx {
     psa::DevBuf  d_vdos_work, d_vdos_pairs, d_vdos_off, d_vdos_mean, d_vdos_part, d_vdos_acc, d_vdos_out;
     int64_t      opt_vdos_work_bytes = (int64_t)1 << 30;
 
-    // mode-projected SED (psa_sed_modes, api_modes.hip): the stacked spectra (B, kb, 3, T) of one block of k-vectors, held
-    // to opt_modes_work_bytes (PSA_OPT_MODES_WORK_BYTES); the packed coefficient table conj(eig); the (T, K, M) result.
-    // psa_sed_modes_welch (api_modes_welch.hip) uses the same three -- its result is (L, K, M) -- and d_seg for the
-    // segments (B, bk, 3, bs, L) of a sub-block, q and d_seg together within the budget.
+    // mode-projected SED (psa_sed_modes, psa_sed_modes_welch; api_modes.hip): the stacked spectra (B, kb, 3, T) of one
+    // block of k-vectors, held to opt_modes_work_bytes (PSA_OPT_MODES_WORK_BYTES); the packed coefficient table
+    // conj(eig); the (T, K, M) result -- (L, K, M) with segments set, which also use d_seg for the segments
+    // (B, bk, 3, bs, L) of a sub-block, q and d_seg together within the budget.
     // All kept between calls.
     psa::DevBuf  d_modes_work, d_modes_coef, d_modes_out;
     int64_t      opt_modes_work_bytes = (int64_t)4 << 30;
@@ -400,17 +400,14 @@ int launch_vdos_power(psa_ctx* c, const float2* d_work, const int64_t* d_pair_of
                       int64_t ns, int64_t n_pairs, int64_t p0, int64_t g_first, int64_t n_groups, int64_t n_chunks);
 // out (rows, L/2 + 1) float32 = scale (acc[o] + acc[(L - o) mod L])
 int launch_vdos_finish(psa_ctx* c, const double* d_acc, float* d_out, int64_t L, int64_t rows, double scale);
-// --- modes.hip (psa_sed_modes: contraction of the B groups' spectra with the mode vectors, fused with the modulus)
+// --- modes.hip (psa_sed_modes, psa_sed_modes_welch: contraction of the B groups' transforms with the mode vectors, fused
+// with the modulus and the sum over Welch segments)
 int modes_tile(int64_t M);            // modes per pass (MT) of the kernel that serves M mode vectors
-// S (B, nk, 3, T) complex64 unscaled spectra of a block of nk k-vectors; coef: the block's rows of the packed table
-// [k][pass][3B][MT] complex64 = conj(eig), zero beyond M; out (T, K_pitch, M) float32, columns k_col0 .. k_col0 + nk - 1:
-// |sum_n coef S|^2 inv_n2 (inv_n2 = 1/T^2 for unscaled spectra)
-int launch_mode_power(psa_ctx* c, const float2* d_S, const float2* d_coef, float* d_out, int64_t T, int64_t nk, int64_t B,
-                      int64_t M, int MT, int64_t K_pitch, int64_t k_col0, float inv_n2);
-// --- modes_welch.hip (psa_sed_modes_welch: the same contraction summed over Welch segments)
-// S (B, nk, 3, ns, L) complex64 unscaled transforms of ns segments; coef as for launch_mode_power; out (L, K_pitch, M)
-// float32, columns k_col0 .. k_col0 + nk - 1: (first ? 0 : out) + sum_s |sum_n coef S_s|^2 scale, one float32 chain in s
-int launch_mode_welch(psa_ctx* c, const float2* d_S, const float2* d_coef, float* d_out, int64_t L, int64_t ns, int64_t nk,
+// S (B, nk, 3, ns, L) complex64 unscaled transforms of ns segments of a block of nk k-vectors (psa_sed_modes: one of T
+// frames, scale = 1/T^2); coef: the block's rows of the packed table [k][pass][3B][MT] complex64 = conj(eig), zero beyond
+// M; out (L, K_pitch, M) float32, columns k_col0 .. k_col0 + nk - 1: (first ? 0 : out) + sum_s |sum_n coef S_s|^2 scale,
+// one float32 chain in s.  L <= 2^31 - 64.
+int launch_mode_power(psa_ctx* c, const float2* d_S, const float2* d_coef, float* d_out, int64_t L, int64_t ns, int64_t nk,
                       int64_t B, int64_t M, int MT, int64_t K_pitch, int64_t k_col0, float scale, bool first);
 // --- peaks.hip (psa_fit_peaks: per column of a spectrum (F, C) the largest value of its band, then a Lorentzian fit)
 int peaks_slices(int64_t C, int64_t rows);   // row slices peak_find splits `rows` rows of C columns into (at most 64)

@@ -111,6 +111,24 @@ def test_kernel_against_the_derived_bound(engine):
         assert e2 <= W64.bound(B, ns)
 
 
+@pytest.mark.parametrize("M", [5, 16, 24, 32, 40])
+def test_one_segment_is_the_plain_contraction(engine, M):
+    """The two debug entries share one body and the two instantiations of a tile one result: psa_debug_mode_power is
+    bit-equal to psa_debug_mode_power_welch on the same spectra as one segment, and to the segment given twice at scale
+    0.5 (x 0.5 + x 0.5 is exact), summed in one launch or over two.  B = 2; K = 5: a full tile of 4 k-vectors and a tail of
+    one wavefront; T = 100: a partial tile of 64 frequencies; M picks the tiles 8 (padded), 16, 24, 32, and 8 with five passes"""
+    import modes_welch64 as W64
+    S = W64.kernel_case(2, 6, 100, 5, 1)[0]                                  # (B, K, 3, 1, T)
+    rng = np.random.default_rng(M)
+    eig = (rng.standard_normal((5, M, 2, 3)) + 1j * rng.standard_normal((5, M, 2, 3))).astype(np.complex64)
+    plain = engine.debug_mode_power(S[:, :, :, 0, :], eig)
+    assert plain.shape == (100, 5, M) and np.all(plain > 0)
+    assert _bits(engine.debug_mode_power_welch(S, eig, 1.0)) == _bits(plain)
+    twice = np.repeat(S, 2, axis=3)
+    assert _bits(engine.debug_mode_power_welch(twice, eig, 0.5)) == _bits(plain)
+    assert _bits(engine.debug_mode_power_welch(twice, eig, 0.5, seg_block=1)) == _bits(plain)
+
+
 # ------------------------------------------------------------------------------------------------- 2. end to end
 # every segment shape with every value of every other factor: two complementary cases per shape (L = 256 needs T = 256)
 E2E = [
@@ -182,7 +200,7 @@ def test_one_boxcar_segment_is_the_mode_sed(engine, syn):
         err = rel_max(none_set, old)
         print(f"T={T}: psa_sed_modes_welch with no segments set against psa_sed_modes: rel_max {err:.3e} "
               f"(bit-identical: {_bits(none_set) == _bits(old)})")
-        assert none_set.shape == (T, len(vecs), 24) and err <= 1e-5
+        assert none_set.shape == (T, len(vecs), 24) and _bits(none_set) == _bits(old)      # the same code
 
 
 def test_cartesian_vectors_are_the_segment_averaged_group_spectra(engine, syn):

@@ -270,9 +270,10 @@ def test_binding_header_and_makefile():
     assert all(f"int {n}(" in header for n in new) and "#define PSA_HIP_ABI_VERSION 6" in header
     mk = (HERE.parent / "psa_amd" / "csrc" / "Makefile").read_text()
     srcs = next(ln for ln in mk.splitlines() if ln.startswith("SRCS"))
-    assert " modes_welch.hip" in srcs and " api_modes_welch.hip" in srcs
+    assert " modes.hip" in srcs and " api_modes.hip" in srcs
     import re
-    assert re.search(r"for f in [^;]*\bmodes_welch\b[^;]*; do", mk)                   # the asm list
+    assert re.search(r"for f in [^;]*\bmodes\b[^;]*; do", mk)                         # the asm list
+    assert all((HERE.parent / "psa_amd" / "csrc" / f).is_file() for f in srcs.split(":=")[1].split())
 
 
 def test_debug_binding_checks_its_arguments():

@@ -14,8 +14,8 @@ warm-up, medians of `--runs` calls of
   (e) with --segments L,H (Hann window): the same for the Welch-averaged mode spectra beside the figures above, measured
       in the same process -- the stage times of psa_sed_modes_welch (window and contraction in the "epilogue" stage),
       calculate_mode_sed(segments=...) end to end and, with --peaks, calculate_mode_peaks(segments=...), the stage times of
-      psa_sed_modes_welch_fit and the statuses; the contraction's floors are those of mode_welch_kernel.
-Kernel time of mode_power_kernel, mode_welch_kernel, peak_find_kernel, peak_fit_kernel: run it under `rocprofv3
+      psa_sed_modes_welch_fit and the statuses; the contraction's floors are those of mode_power_kernel<MT, true>.
+Kernel time of mode_power_kernel<MT, false> (no segments), mode_power_kernel<MT, true>, peak_find_kernel, peak_fit_kernel: run it under `rocprofv3
 --kernel-trace --stats` (with --skip-baseline).
     python tools/modes_timing.py [--cfg C3] [--n-k 256] [--modes 24] [--runs 10] [--skip-baseline] [--peaks] [--segments L,H]"""
 import argparse
