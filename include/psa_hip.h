@@ -344,6 +344,29 @@ int psa_sed_modes(psa_ctx* ctx, int slot, const float* mean_pos_all, const float
                   const void* eig /* (K,M,B,3) complex64 */, int64_t M, int32_t flags /* PSA_F_DISPLACEMENTS or 0 */,
                   float* out_host /* (T,K,M) */, size_t out_bytes);
 
+/* Spectral covariance of the site groups' projections: the frequency-weighted sum of the outer products of the B groups'
+ * spectra -- the matrix whose eigenvectors are the mode vectors psa_sed_modes contracts with (the Green's-function
+ * method: the displacement covariance of the mass-weighted site coordinates at k is k_B T D(k)^-1).  q_b, S_b, the groups,
+ * the weights and the flags as for psa_sed_modes; with i = 3 b + c, n = 3 B and the weight rows g_m (n_w, T) float32 in
+ * FFT order:
+ *     G^(m)[k,i,j] = sum_w g_m[w] S_i[k,w] conj(S_j[k,w])              out_host (n_w, K, n, n) complex128, C order
+ * g = 1 gives (1/T) sum_t q q^+ (Parseval); the weights are used as given, the bin w = 0 included.  out_bytes exactly
+ * 16 n_w K n^2.  PSA_EINVAL: n_w outside 1..2, a non-finite weight, 3 B > 96, what psa_sed_modes refuses of its k-list,
+ * groups (an atom in two groups, an index out of range), weights and T, a null pointer, out_bytes not exact, segments
+ * set (no segment average here), a work budget (PSA_OPT_MODES_WORK_BYTES) that cannot hold one k-vector (24 B T bytes
+ * and its partial sums).
+ * Per block of k-vectors: psa_sed_modes' B projections and batched rocFFT, then two kernels (covariance.hip): float32
+ * products and sums on the fp32 matrix cores -- at most 128 frequencies per accumulator, folded at most 32 times into a
+ * second float32 sum, one partial slab per k-vector and 4096 frequencies -- and a pass that adds the slabs in float64,
+ * scales by 1/T^2 in float64 and mirrors: G[j,i] is the exact conjugate of G[i,j], Im G[i,i] exactly 0.  No atomics; the
+ * result does not depend on the blocking; two identical calls give the same bits.  The slab, the k map, the plane cache
+ * and every result of the other entry points are left as they are.  Stage times go to psa_last_timings:
+ * [2] projection, [3] FFT, [4] the covariance kernels, [7] device->host. */
+int psa_sed_covariance(psa_ctx* ctx, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K,
+                       const int32_t* group_idx, const int64_t* group_off, int32_t B,
+                       const float* freq_weights /* (n_w, T) */, int32_t n_w, int32_t flags /* PSA_F_DISPLACEMENTS or 0 */,
+                       double* out_host /* (n_w, K, 3B, 3B, 2) */, size_t out_bytes);
+
 /* Lorentzian fits of spectrum peaks: frequency and half width per column, on the device.  A spectrum is phi (F, C)
  * float32, C order; row i is bin i of an F-point transform, f_i = i df.  Only the positive half is used, bins
  * 1 .. ceil(F/2) - 1.  Column j has the band [lo_j, hi_j) of bins (bands (C, 2) int32, or NULL: [lo, hi) for all).
@@ -487,6 +510,10 @@ int psa_debug_project_frames(psa_ctx* ctx, int slot, const float* mean_pos_all,
  * they are (no division by T), eig (K,M,B,3) complex64 -> out_host (T,K,M) float32 = |sum_{b,c} conj(eig) S|^2 */
 int psa_debug_mode_power(psa_ctx* ctx, const void* S_host, const void* eig, int32_t B, int64_t K, int64_t M, int64_t T,
                          float* out_host);
+/* the covariance kernels of psa_sed_covariance alone, on spectra the caller uploads: S_host (B,K,3,T) complex64 taken as
+ * the transforms S_b (used as given), freq_weights (n_w,T), out_host (n_w,K,3B,3B) complex128 = scale sum_w g S S^+ */
+int psa_debug_covariance(psa_ctx* ctx, const void* S_host /* (B, K, 3, T) complex64, used as given */, int32_t B, int64_t K,
+                         int64_t T, const float* freq_weights, int32_t n_w, double scale, double* out_host);
 /* the contraction kernel of psa_sed_modes_welch alone, on transformed segments the caller uploads: S_host (B,K,3,ns,L)
  * complex64 taken as they are, eig (K,M,B,3) complex64 -> out_host (L,K,M) float32 = sum_s scale |sum_{b,c} conj(eig) S_s|^2.
  * seg_block = 0: one launch; seg_block > 0: launches of at most that many segments, the later ones adding to the result

@@ -31,6 +31,12 @@ OPT_VDOS_WORK_BYTES = 11
 OPT_MODES_WORK_BYTES = 12
 KMAP_MIRROR = 0x80000000
 ABI_VERSION = 6
+# the summation structure of the covariance kernel (psa_amd/csrc/covariance.hip), mirrored for the bound of tests/cov64.py
+COV_CHAIN = 128     # frequencies one float32 accumulator sums before it is folded
+COV_FOLDS = 32      # folds into the second float32 sum per partial slab
+COV_TILE = 64       # frequencies per staged tile
+COV_CHUNK = COV_CHAIN * COV_FOLDS   # frequencies per workgroup and partial slab
+COV_MAX_ROWS = 96   # 3 B served
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -105,6 +111,10 @@ SIGNATURES = {
     "psa_debug_mode_power": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _f32p]),
     "psa_debug_mode_power_welch": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                              C.c_int64, C.c_int64, C.c_float, _f32p]),
+    "psa_sed_covariance": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p, _i64p, C.c_int32, _f32p, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_size_t]),
+    "psa_debug_covariance": (C.c_int, [_ctx, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, _f32p, C.c_int32, C.c_double,
+                                       C.c_void_p]),
     "psa_debug_plane_cache": (C.c_int, [_ctx, _i64p, _i64p]),
     "psa_comm_unique_id": (C.c_int, [C.c_void_p]),
     "psa_comm_init": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int]),
@@ -740,6 +750,41 @@ class Engine:
         _check(self._lib.psa_debug_mode_power_welch(self._h, S.ctypes.data_as(C.c_void_p), eig.ctypes.data_as(C.c_void_p), B, K, M,
                                                     L, ns, int(seg_block), float(scale), _f32(out)),
                "psa_debug_mode_power_welch")
+        return out
+
+    def sed_covariance(self, slot, mean_pos_all, k_vectors, groups, freq_weights, flags=0) -> np.ndarray:
+        """Spectral covariance of the resident array (psa_sed_covariance): (n_w, K, n, n) complex128 =
+        sum_w g_m[w] S_i[k,w] conj(S_j[k,w]) over the n = 3B rows i = 3b + c of the B disjoint site groups (index arrays;
+        None: all atoms as one group), with the context's atom weights and `freq_weights` (n_w, T) float32, n_w 1 or 2;
+        the definition is in psa_amd/covariance.py.  The result of the SED entry points resident on the device is not
+        touched."""
+        mean = _as_f32(mean_pos_all, (3,))
+        kv = _as_f32(k_vectors, (3,))
+        idx, off, B = pack_groups(groups)
+        g = np.ascontiguousarray(freq_weights, np.float32)
+        T = self.shape(slot)[0]
+        if g.ndim != 2 or g.shape[1] != T:
+            raise ValueError(f"freq_weights have shape {g.shape}, expected (n_w, T) = (n_w, {T})")
+        K, n = kv.shape[0], 3 * B
+        out = np.empty((g.shape[0], K, n, n), np.complex128)
+        _check(self._lib.psa_sed_covariance(
+            self._h, slot, _f32(mean), _f32(kv), K,
+            idx.ctypes.data_as(_i32p) if idx is not None else None,
+            off.ctypes.data_as(_i64p) if off is not None else None, B, _f32(g), g.shape[0], flags,
+            out.ctypes.data_as(C.c_void_p), out.nbytes), "psa_sed_covariance")
+        return out
+
+    def debug_covariance(self, spectra: np.ndarray, freq_weights: np.ndarray, scale: float = 1.0) -> np.ndarray:
+        """The covariance kernels of `sed_covariance` alone (psa_debug_covariance): spectra (B, K, 3, T) complex64 taken
+        as they are, freq_weights (n_w, T) float32 -> (n_w, K, 3B, 3B) complex128 = scale sum_w g S S^+."""
+        S = np.ascontiguousarray(spectra, np.complex64)
+        g = np.ascontiguousarray(freq_weights, np.float32)
+        if S.ndim != 4 or S.shape[2] != 3 or g.ndim != 2 or g.shape[1] != S.shape[3]:
+            raise ValueError(f"spectra {S.shape} and freq_weights {g.shape} do not fit (B,K,3,T) and (n_w,T)")
+        B, K, _, T = S.shape
+        out = np.empty((g.shape[0], K, 3 * B, 3 * B), np.complex128)
+        _check(self._lib.psa_debug_covariance(self._h, S.ctypes.data_as(C.c_void_p), B, K, T, _f32(g), g.shape[0], float(scale),
+                                              out.ctypes.data_as(C.c_void_p)), "psa_debug_covariance")
         return out
 
     def set_kmap(self, kmap: np.ndarray):

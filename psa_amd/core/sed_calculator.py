@@ -32,6 +32,7 @@ import numpy as np
 
 from .. import _hip
 from ..io.writer import out_to_qdump
+from ..covariance import ModeVectors, mode_vectors, spectral_weights
 from ..modes import ModeSED
 from ..peaks import PeakFit
 from ..segments import Segments
@@ -487,23 +488,20 @@ class SEDCalculator:
             phi = run(slot, mean_pos_all, k_vectors, self._device_groups(groups), eig.astype(np.complex64), flags)
         return ModeSED(phi, freqs, k_points_mags, k_vectors_3d, [np.asarray(g) for g in groups])
 
-    def _mode_inputs(self, k_points_mags, k_vectors_3d, eigenvectors, basis_atom_indices, basis_atom_types, atom_weights,
-                     segments=None):
-        """What the mode projections check and resolve: (weights, eig, k_vectors (K, 3) float32, groups, the empty ModeSED
-        to return as it is -- no frames, no atoms or no k-vectors -- or None).  `segments` are validated as `calculate`
-        validates them."""
+    def _site_inputs(self, k_vectors_3d, basis_atom_indices, basis_atom_types, atom_weights, segments=None,
+                     what="the mode-projected SED"):
+        """What every projection of site groups checks and resolves, whatever is done with the B spectra: (weights,
+        k_vectors (K, 3) float32, the disjoint groups -- None if the trajectory has no frames or no atoms).  `segments`
+        are validated as `calculate` validates them; a sharded calculator refuses."""
         weights = None if atom_weights is None else check_atom_weights(atom_weights, self.traj.n_atoms)
         if segments is not None and not isinstance(segments, Segments):
             raise TypeError(f"segments must be a psa_amd.Segments, got {type(segments).__name__}")
         if self._shard is not None and self._shard.nranks > 1:
-            raise NotImplementedError("the mode-projected SED is not available on a sharded calculator")
-        eig = np.asarray(eigenvectors)
+            raise NotImplementedError(f"{what} is not available on a sharded calculator")
         k_vectors = np.asarray(k_vectors_3d, np.float32).reshape(-1, 3)
-        n_t, n_atoms, n_k = self.traj.n_frames, self.traj.n_atoms, len(k_vectors)
+        n_t, n_atoms = self.traj.n_frames, self.traj.n_atoms
         if n_t == 0 or n_atoms == 0:
-            logger.warning("Cannot calculate the mode-projected SED: 0 frames or 0 atoms.")
-            return weights, eig, k_vectors, [], ModeSED(np.zeros((0, 0, 0), np.float32), np.zeros(0, np.float64), k_points_mags,
-                                                        k_vectors_3d, [])
+            return weights, k_vectors, None
         if segments is not None:
             segments.count(n_t)                          # ValueError if L > T
         if (basis_atom_types is None and isinstance(basis_atom_indices, (list, tuple)) and len(basis_atom_indices)
@@ -520,6 +518,21 @@ class SEDCalculator:
         members = np.concatenate(groups)
         if np.unique(members).size != members.size:
             raise ValueError("atom groups of a mode projection must be disjoint (an atom is listed twice)")
+        return weights, k_vectors, groups
+
+    def _mode_inputs(self, k_points_mags, k_vectors_3d, eigenvectors, basis_atom_indices, basis_atom_types, atom_weights,
+                     segments=None):
+        """What the mode projections check and resolve: (weights, eig, k_vectors (K, 3) float32, groups, the empty ModeSED
+        to return as it is -- no frames, no atoms or no k-vectors -- or None).  `segments` are validated as `calculate`
+        validates them."""
+        weights, k_vectors, groups = self._site_inputs(k_vectors_3d, basis_atom_indices, basis_atom_types, atom_weights,
+                                                       segments)
+        eig = np.asarray(eigenvectors)
+        n_t, n_k = self.traj.n_frames, len(k_vectors)
+        if groups is None:
+            logger.warning("Cannot calculate the mode-projected SED: 0 frames or 0 atoms.")
+            return weights, eig, k_vectors, [], ModeSED(np.zeros((0, 0, 0), np.float32), np.zeros(0, np.float64), k_points_mags,
+                                                        k_vectors_3d, [])
         if eig.ndim != 4 or eig.shape[0] != n_k or eig.shape[2:] != (len(groups), 3) or eig.shape[1] < 1:
             raise ValueError(f"eigenvectors have shape {eig.shape}, expected (K, M, B, 3) = ({n_k}, M, {len(groups)}, 3) "
                              f"for {n_k} k-vectors and {len(groups)} atom groups")
@@ -532,6 +545,75 @@ class SEDCalculator:
                                                             np.fft.fftfreq(n_f, d=self.dt_ps), k_points_mags, k_vectors_3d,
                                                             [np.asarray(g) for g in groups])
         return weights, eig, k_vectors, groups, None
+
+    # ------------------------------------------------------------------ spectral covariance, mode vectors
+    def calculate_spectral_covariance(self, k_points_mags: np.ndarray, k_vectors_3d: np.ndarray,
+                                      basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                      basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                      atom_weights: Optional[np.ndarray] = None, freq_weights: np.ndarray) -> np.ndarray:
+        """Spectral covariance of the site projections (not in the reference; definition in psa_amd/covariance.py):
+
+            G^(m)[k,i,j] = sum_w g_m[w] S_i[k,w] conj(S_j[k,w])          i = 3b + c, (n_w, K, 3B, 3B) complex128
+
+        where S_b is what `calculate` returns for the atom group b, reduced over frequency on the GPU without the B
+        group spectra ever leaving HBM.  Groups, `atom_weights`, empty inputs and the sharded refusal
+        (NotImplementedError) are those of `calculate_mode_sed`.  `freq_weights` (keyword only) is (T,) or (n_w, T) with
+        n_w 1 or 2, finite, in FFT order and used as given (`psa_amd.spectral_weights` makes the rows of a moment and a
+        band); at most 32 groups (3B <= 96).  A trajectory without frames or atoms gives a (n_w, 0, 0, 0) array, an
+        empty k-list (n_w, 0, 3B, 3B)."""
+        return self._spectral_covariance(k_vectors_3d, basis_atom_indices, basis_atom_types, atom_weights, freq_weights)[0]
+
+    def _spectral_covariance(self, k_vectors_3d, basis_atom_indices, basis_atom_types, atom_weights, freq_weights):
+        """(the covariance, the resolved groups -- None without frames or atoms) of `calculate_spectral_covariance`"""
+        g = np.asarray(freq_weights, np.float64)
+        if g.ndim == 1:
+            g = g[None]
+        n_t = self.traj.n_frames
+        if g.ndim != 2 or g.shape[1] != n_t or not 1 <= g.shape[0] <= 2:
+            raise ValueError(f"freq_weights have shape {np.shape(freq_weights)}, expected (T,) or (n_w, T) with T = {n_t} "
+                             f"frames and n_w = 1 or 2")
+        if not np.all(np.isfinite(g)):
+            raise ValueError("freq_weights must be finite")
+        weights, k_vectors, groups = self._site_inputs(k_vectors_3d, basis_atom_indices, basis_atom_types, atom_weights,
+                                                       what="the spectral covariance")
+        if groups is None:
+            logger.warning("Cannot calculate the spectral covariance: 0 frames or 0 atoms.")
+            return np.zeros((g.shape[0], 0, 0, 0), np.complex128), None
+        n = 3 * len(groups)
+        if n > _hip.COV_MAX_ROWS:
+            raise ValueError(f"the spectral covariance serves at most {_hip.COV_MAX_ROWS // 3} atom groups, got {len(groups)}")
+        if len(k_vectors) == 0:
+            logger.warning("k_vectors_3d is empty. Returning an empty covariance.")
+            return np.zeros((g.shape[0], 0, n, n), np.complex128), groups
+        mean_pos_all = self._mean_positions()
+        slot, data, flags = self._data_slot()
+        eng = self.engine
+        with self._engine_state(weights, None):
+            eng.ensure_resident(slot, data)      # later SED calls find it resident
+            return eng.sed_covariance(slot, mean_pos_all, k_vectors, self._device_groups(groups), g.astype(np.float32), flags), groups
+
+    def calculate_mode_vectors(self, k_points_mags: np.ndarray, k_vectors_3d: np.ndarray,
+                               basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                               basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                               atom_weights: Optional[np.ndarray] = None, band=None) -> ModeVectors:
+        """Mode vectors and frequencies from the trajectory itself (definition and caveats in psa_amd/covariance.py):
+        the displacement covariance G_u and the velocity covariance G_v of the site projections in one GPU call
+        (`calculate_spectral_covariance` with two weight rows: the moments (-2, 0) of a velocity calculator, (0, +2) with
+        `use_displacements=True`; `band` = (fmin, fmax) THz restricts both), then `psa_amd.mode_vectors` on the host:
+        the eigenvectors of G_u, frequency = sqrt(e^+ G_v e / e^+ G_u e) / 2 pi, ascending.  Pass
+        `atom_weights=psa_amd.mass_weights(...)`: the method rests on equipartition of the mass-weighted coordinates.
+        Degenerate branches return some basis of their subspace.  Returns a `psa_amd.ModeVectors` whose `eigenvectors`
+        (K, 3B, B, 3) complex64 are ready to pass to `calculate_mode_sed` / `calculate_mode_peaks`.  Empty inputs as for
+        `calculate_mode_sed`: a trajectory without frames or atoms gives (0, 0, 0, 3) vectors and no groups, an empty
+        k-list (0, 3B, B, 3), each with a warning."""
+        moments = (0, 2) if self.use_displacements else (-2, 0)
+        g = np.stack([spectral_weights(self.traj.n_frames, self.dt_ps, m, band) for m in moments]) if self.traj.n_frames \
+            else np.zeros((2, 0), np.float32)
+        G, groups = self._spectral_covariance(k_vectors_3d, basis_atom_indices, basis_atom_types, atom_weights, g)
+        mv = mode_vectors(G[0], G[1])        # (an empty covariance -- logged above -- gives an empty ModeVectors)
+        groups = groups or []
+        mv.k_points, mv.k_vectors, mv.groups = k_points_mags, k_vectors_3d, [np.asarray(x) for x in groups]
+        return mv
 
     def calculate_mode_peaks(self, k_points_mags: np.ndarray, k_vectors_3d: np.ndarray, eigenvectors: np.ndarray,
                              basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,

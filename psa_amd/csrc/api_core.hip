@@ -277,7 +277,7 @@ int psa_destroy(psa_ctx* c) {
                           &c->d_fft_work, &c->d_tables, &c->d_absmax, &c->d_slab, &c->d_out, &c->d_aux, &c->d_sync,
                           &c->d_qrows, &c->d_stage, &c->d_bin, &c->d_upload_max, &c->d_zeros, &c->d_kmap, &c->d_cols, &c->d_inten,
                           &c->d_vdos_work, &c->d_vdos_pairs, &c->d_vdos_off, &c->d_vdos_mean, &c->d_vdos_part, &c->d_vdos_acc,
-                          &c->d_vdos_out, &c->d_modes_work, &c->d_modes_coef, &c->d_modes_out, &c->d_peaks_spec, &c->d_peaks_bands,
+                          &c->d_vdos_out, &c->d_modes_work, &c->d_modes_coef, &c->d_modes_out, &c->d_cov_slab, &c->d_cov_g, &c->d_cov_out, &c->d_peaks_spec, &c->d_peaks_bands,
                           &c->d_peaks_part, &c->d_peaks_fit, &c->d_peaks_info})
             b->release();
         (void)hipStreamDestroy(c->stream);

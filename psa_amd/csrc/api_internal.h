@@ -11,6 +11,7 @@
 //   api_vdos.hip     the vibrational density of states: a second, non-projecting pass over the resident array
 //   api_modes.hip    the mode-projected SED: the B site groups' spectra contracted with the mode vectors, with or without
 //                    the Welch segment average between projection and contraction
+//   api_covariance.hip  the spectral covariance of the B site groups' spectra: the frequency-weighted sum of their outer products
 //   api_peaks.hip    Lorentzian peak fits of spectrum columns: an uploaded spectrum, or the mode spectra where they lie
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
 // k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
@@ -181,6 +182,24 @@ struct ModesArgs {
     size_t         out_bytes;
 };
 int modes_run(psa_ctx* c, const ModesArgs& a, bool segments, bool device_only);
+// the pieces of such a call, shared with psa_sed_covariance (api_covariance.hip): checks of the k-list and the site
+// groups, uploads and group sources, the block rule, the B projections of a block
+struct ModesCall {
+    int64_t                T = 0, N = 0, K = 0, M = 0;
+    int32_t                B = 0;
+    int                    MT = 0;       // modes per pass of the contraction (modes_tile)
+    size_t                 coef_k = 0;   // float2 per k-vector in the packed table
+    int64_t                per_k = 0;    // bytes of one k-vector in the stacked buffer (B, kb, 3, T): 24 B T
+    int64_t                kb_max = 0;   // most k-vectors a block may hold whatever the budget
+    ProjectArgs            list;         // the call's list (the low-rank route is offered on it)
+    std::vector<float>     coef;         // conj(eig) as the kernel reads it: [k][pass][3B][MT] (empty: no mode vectors)
+    std::vector<GroupView> src;          // the B groups and where their data comes from
+};
+int     modes_check_groups(psa_ctx* c, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K, const int32_t* group_idx,
+                           const int64_t* group_off, int32_t B, int32_t flags, ModesCall* m);
+int     modes_upload(psa_ctx* c, ModesCall* m);
+int64_t modes_block(const psa_ctx* c, const ModesCall& m, int64_t k0, int64_t kb);
+int     modes_project(psa_ctx* c, const ModesCall& m, int64_t k0, int64_t nk, float2* d_work);
 // api_peaks.hip: the arguments of a fit, and the fit of a spectrum (F, C) resident on the device
 struct PeakArgs {
     int64_t        F, C;

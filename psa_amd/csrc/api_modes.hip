@@ -23,20 +23,38 @@
 
 namespace psa {
 
-namespace {
+// what modes_check checks of the k-list and the site groups, and the sizes that follow from them (shared with
+// psa_sed_covariance, which has no mode vectors)
+int modes_check_groups(psa_ctx* c, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K, const int32_t* group_idx,
+                       const int64_t* group_off, int32_t B, int32_t flags, ModesCall* m) {
+    const int64_t T = c->slot[slot].T, N = c->slot[slot].N;
+    PSA_REQUIRE(K >= 0 && K < (1ll << 29), "bad number of k-vectors %lld", (long long)K);
+    PSA_REQUIRE(K == 0 || k_vectors != nullptr, "null k_vectors");
+    PSA_REQUIRE(T <= (1ll << 31) - 64, "T = %lld frames: the mode contraction indexes frequencies in 32 bits (T <= 2^31 - 64)",
+                (long long)T);
+    PSA_TRY(validate_groups(N, group_idx, group_off, B));
+    PSA_TRY(check_weights(c, N));
+    if (group_idx) {
+        std::vector<uint8_t> seen((size_t)N, 0);
+        for (int32_t b = 0; b < B; ++b)
+            for (int64_t i = group_off[b]; i < group_off[b + 1]; ++i) {
+                PSA_REQUIRE(!seen[group_idx[i]], "atom %d is listed twice (group %d): the site groups of a mode projection must be disjoint",
+                            (int)group_idx[i], (int)b);
+                seen[group_idx[i]] = 1;
+            }
+    }
+    m->per_k = (int64_t)B * 3 * T * (int64_t)sizeof(float2);
+    int64_t n_max = 0;
+    for (int32_t b = 0; b < B; ++b) n_max = std::max(n_max, group_idx ? group_off[b + 1] - group_off[b] : N);
+    // a block of k-vectors: a group's phase table under 2 GiB (as project_groups), the contraction's grid
+    m->kb_max = std::min<int64_t>(std::max<int64_t>(64, (((int64_t)2 << 30) / (8 * ((n_max + 63) / 64 * 64 + 64))) / 64 * 64),
+                                  (int64_t)65535 * 4);
+    m->T = T, m->N = N, m->K = K, m->B = B;
+    m->list = ProjectArgs{slot, mean_pos_all, k_vectors, K, K, 0, group_idx, group_off, B, flags};
+    return PSA_OK;
+}
 
-// the pieces of a call: checks and coefficient table, uploads and group sources, the block rule, the B projections of a block
-struct ModesCall {
-    int64_t                T = 0, N = 0, K = 0, M = 0;
-    int32_t                B = 0;
-    int                    MT = 0;       // modes per pass of the contraction (modes_tile)
-    size_t                 coef_k = 0;   // float2 per k-vector in the packed table
-    int64_t                per_k = 0;    // bytes of one k-vector in the stacked buffer (B, kb, 3, T): 24 B T
-    int64_t                kb_max = 0;   // most k-vectors a block may hold whatever the budget
-    ProjectArgs            list;         // the call's list (the low-rank route is offered on it)
-    std::vector<float>     coef;         // conj(eig) as the kernel reads it: [k][pass][3B][MT]
-    std::vector<GroupView> src;          // the B groups and where their data comes from
-};
+namespace {
 
 // conj(eig) of k-vectors [0, K) as the kernel reads it: [k][pass][n = 3b + c][MT], zero beyond M
 int pack_coef(const float* eig, int64_t K, int64_t M, int64_t B, int MT, std::vector<float>* coef) {
@@ -60,43 +78,24 @@ int pack_coef(const float* eig, int64_t K, int64_t M, int64_t B, int MT, std::ve
 // need_out: the caller requires an output it was not given), then the coefficient table and the sizes
 int modes_check(psa_ctx* c, const char* what, const ModesArgs& a, bool need_out, ModesCall* m) {
     PSA_TRY(check_slot(c, a.slot));
-    const int64_t T = c->slot[a.slot].T, N = c->slot[a.slot].N, K = a.K, M = a.M;
+    const int64_t K = a.K, M = a.M;
     const int32_t B = a.B;
     PSA_REQUIRE((a.flags & ~PSA_F_DISPLACEMENTS) == 0, "%s takes PSA_F_DISPLACEMENTS or 0, got flags 0x%x", what, (unsigned)a.flags);
     PSA_REQUIRE(a.eig != nullptr, "null eig");
     PSA_REQUIRE(!need_out, "null output");
     PSA_REQUIRE(a.mean_pos_all != nullptr, "null mean_pos_all");
     PSA_REQUIRE(M >= 1 && M < (1ll << 30), "need at least one mode vector per k-point (M = %lld)", (long long)M);
-    PSA_REQUIRE(K >= 0 && K < (1ll << 29), "bad number of k-vectors %lld", (long long)K);
-    PSA_REQUIRE(K == 0 || a.k_vectors != nullptr, "null k_vectors");
-    PSA_REQUIRE(T <= (1ll << 31) - 64, "T = %lld frames: the mode contraction indexes frequencies in 32 bits (T <= 2^31 - 64)",
-                (long long)T);
-    PSA_TRY(validate_groups(N, a.group_idx, a.group_off, B));
-    PSA_TRY(check_weights(c, N));
-    if (a.group_idx) {
-        std::vector<uint8_t> seen((size_t)N, 0);
-        for (int32_t b = 0; b < B; ++b)
-            for (int64_t i = a.group_off[b]; i < a.group_off[b + 1]; ++i) {
-                PSA_REQUIRE(!seen[a.group_idx[i]], "atom %d is listed twice (group %d): the site groups of a mode projection must be disjoint",
-                            (int)a.group_idx[i], (int)b);
-                seen[a.group_idx[i]] = 1;
-            }
-    }
+    PSA_TRY(modes_check_groups(c, a.slot, a.mean_pos_all, a.k_vectors, K, a.group_idx, a.group_off, B, a.flags, m));
     m->MT = modes_tile(M);
     PSA_TRY(pack_coef(a.eig, K, M, B, m->MT, &m->coef));
     m->coef_k = (size_t)((M + m->MT - 1) / m->MT) * 3 * (size_t)B * (size_t)m->MT;
-    m->per_k = (int64_t)B * 3 * T * (int64_t)sizeof(float2);
-    int64_t n_max = 0;
-    for (int32_t b = 0; b < B; ++b) n_max = std::max(n_max, a.group_idx ? a.group_off[b + 1] - a.group_off[b] : N);
-    // a block of k-vectors: a group's phase table under 2 GiB (as project_groups), the contraction's grid
-    m->kb_max = std::min<int64_t>(std::max<int64_t>(64, (((int64_t)2 << 30) / (8 * ((n_max + 63) / 64 * 64 + 64))) / 64 * 64),
-                                  (int64_t)65535 * 4);
-    m->T = T, m->N = N, m->K = K, m->M = M, m->B = B;
-    m->list = ProjectArgs{a.slot, a.mean_pos_all, a.k_vectors, K, K, 0, a.group_idx, a.group_off, B, a.flags};
+    m->M = M;
     return PSA_OK;
 }
 
-// k-vectors, mean, lists, coefficients; resolves the group sources
+}  // namespace
+
+// k-vectors, mean, lists, coefficients (if any); resolves the group sources
 int modes_upload(psa_ctx* c, ModesCall* m) {
     const ProjectArgs& a = m->list;
     {
@@ -104,7 +103,7 @@ int modes_upload(psa_ctx* c, ModesCall* m) {
         PSA_TRY(upload(c, c->d_kvec, a.k_vectors, (size_t)m->K * 3 * sizeof(float)));
         PSA_TRY(upload(c, c->d_mean_all, a.mean_pos_all, (size_t)m->N * 3 * sizeof(float)));
         if (a.group_idx) PSA_TRY(upload(c, c->d_idx, a.group_idx, (size_t)a.group_off[m->B] * sizeof(int32_t)));
-        PSA_TRY(upload(c, c->d_modes_coef, m->coef.data(), m->coef.size() * sizeof(float)));
+        if (!m->coef.empty()) PSA_TRY(upload(c, c->d_modes_coef, m->coef.data(), m->coef.size() * sizeof(float)));
     }
     // where each group's data comes from (its cached planes, the float32 slot, the displacement array)
     c->plane_call_mark = c->plane_tick + 1;
@@ -139,8 +138,6 @@ int modes_project(psa_ctx* c, const ModesCall& m, int64_t k0, int64_t nk, float2
     }
     return PSA_OK;
 }
-
-}  // namespace
 
 // Shared by the four entries.  The result, (T, K, M) or with segments (L, K, M), is left in c->d_modes_out.  `segments`: the
 // context's segments are honoured (psa_sed_modes_welch) or refused (psa_sed_modes).  a.out may be null only with

@@ -284,6 +284,11 @@ struct psa_ctx {
     psa::DevBuf  d_modes_work, d_modes_coef, d_modes_out;
     int64_t      opt_modes_work_bytes = (int64_t)4 << 30;
 
+    // spectral covariance (psa_sed_covariance; api_covariance.hip): the stacked spectra lie in d_modes_work, under the same
+    // budget as the partial slabs [k][chunk][slot][pair][part][256] of a block; the weight table (n_w, T); the (n_w, K, 3B, 3B)
+    // complex128 result.  All kept between calls.
+    psa::DevBuf  d_cov_slab, d_cov_g, d_cov_out;
+
     // Lorentzian peak fits (psa_fit_peaks, psa_sed_modes_fit; api_peaks.hip): an uploaded spectrum, the per-column bands,
     // the row slices' partial maxima (value, bin, non-finite flag) and the results.  All kept between calls.
     psa::DevBuf  d_peaks_spec, d_peaks_bands, d_peaks_part, d_peaks_fit, d_peaks_info;
@@ -409,6 +414,14 @@ int modes_tile(int64_t M);            // modes per pass (MT) of the kernel that 
 // one float32 chain in s.  L <= 2^31 - 64.
 int launch_mode_power(psa_ctx* c, const float2* d_S, const float2* d_coef, float* d_out, int64_t L, int64_t ns, int64_t nk,
                       int64_t B, int64_t M, int MT, int64_t K_pitch, int64_t k_col0, float scale, bool first);
+// --- covariance.hip (psa_sed_covariance: sum over frequency of g_m S_i conj(S_j) on the fp32 matrix cores)
+int64_t covariance_chunks(int64_t T);                                 // frequency chunks (slabs per k-vector and tile) of T frames
+int64_t covariance_slab_floats(int64_t T, int64_t n, int n_w);        // floats of one k-vector's slabs, n = 3 B rows
+// S (B, nk, 3, T) complex64 unscaled transforms of a block of nk k-vectors, g (n_w, T) float32 -> slabs -> out
+// (n_w, K_pitch, 3B, 3B) complex128, k-vectors k_col0 .. k_col0 + nk - 1, times `scale` in float64.  3 B <= 96, n_w 1 or 2,
+// T <= 2^31 - 64, nk covariance_chunks(T) < 2^31.
+int launch_covariance(psa_ctx* c, const float2* d_S, const float* d_g, float* d_slab, double2* d_out, int64_t T, int64_t nk, int64_t B,
+                      int n_w, int64_t K_pitch, int64_t k_col0, double scale);
 // --- peaks.hip (psa_fit_peaks: per column of a spectrum (F, C) the largest value of its band, then a Lorentzian fit)
 int peaks_slices(int64_t C, int64_t rows);   // row slices peak_find splits `rows` rows of C columns into (at most 64)
 // rows [row0, row_end) in n_slices slices -> (n_slices, C) partials: largest value of the column's band [lo, hi) (d_bands
