@@ -448,9 +448,9 @@ int psa_sed_set_kmap(psa_ctx* ctx, const int32_t* kmap, int64_t K_out);
 
 /* The low-rank plan of a k-list for one atom group (api_lowrank.hip) as a host-only service for tests:
  * *ok = 1 when the route serves; geo[12] = u (3), k0 (3), x_c, h_x, interval width, interval id, bound on
- * |D|, scale of D; kappa[64] the nodes, C[K * 64 * 2] the complex64 combine matrix, L[K * 64] its real factor
- * (the Lagrange weights) and phi[K * 2] its complex64 phase factor, C[j, l] = phi[j] L[j, l] (any may be null).
- * No context, no GPU. */
+ * |D|, scale of D; kappa[64] the nodes, L[K * 64] the combine's real Lagrange weights and phi[K * 2] its complex64
+ * row phases, C[K * 64 * 2] complex64 their product phi[j] L[j, l] rounded once from fp64: the reference the two
+ * factors are checked against, which no kernel reads (any may be null).  No context, no GPU. */
 int psa_lowrank_plan(const float* k_vectors, int64_t K, const float* mean_pos_all, int64_t N, const int32_t* idx,
                      int64_t n_g, int32_t* ok, double* geo, double* kappa, float* C, float* L, float* phi);
 

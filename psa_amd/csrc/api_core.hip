@@ -235,7 +235,6 @@ int psa_create(int device, psa_ctx** out) {
     // A/B switches of the low-rank route, read once here (psa_set_option overrides them)
     if (const char* v = std::getenv("PSA_K1_LOWRANK")) c->opt_k1_lowrank = std::atoi(v) != 0;
     if (const char* v = std::getenv("PSA_K1_LOWRANK_MIN_K")) c->opt_k1_lowrank_min_k = std::max(1, std::atoi(v));
-    if (const char* v = std::getenv("PSA_K1_COMBINE")) c->k1_combine_arm = std::clamp(std::atoi(v), 0, 2);
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
@@ -332,7 +331,7 @@ int psa_set_option(psa_ctx* c, int option, int64_t value) {
             c->opt_k1_lowrank = value != 0;
             if (!c->opt_k1_lowrank) {
                 PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
-                for (psa::DevBuf* b : {&c->d_lr_diff, &c->d_lr_qn, &c->d_lr_C, &c->d_lr_L, &c->d_lr_phi, &c->d_lr_f64}) b->release();
+                for (psa::DevBuf* b : {&c->d_lr_diff, &c->d_lr_qn, &c->d_lr_L, &c->d_lr_phi, &c->d_lr_f64}) b->release();
             }
             return PSA_OK;
         case PSA_OPT_K1_LOWRANK_MIN_LOCAL:

@@ -158,11 +158,13 @@ struct LowRankPlan {
     double              d_bound = 0;                          // bound on |P_ref - P_line|
     float               dscale = 0.f;                         // power of two the D image carries
     std::vector<double> kline;                                // (K, 3) the k-vectors projected on the line
-    std::vector<float>  C;                                    // (K, 64) complex64 combine matrix
-    std::vector<float>  L;                                    // (K, 64) its real factor, the Lagrange weights L_l(kappa_j)
-    std::vector<float>  phi;                                  // (K) complex64, its phase factor exp(i kappa_j x_c)
+    std::vector<float>  L;                                    // (K, 64) the combine's real Lagrange weights L_l(kappa_j)
+    std::vector<float>  phi;                                  // (K) complex64, the combine's row phases exp(i kappa_j x_c)
 };
-int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, const int32_t* h_idx, int64_t n_g, LowRankPlan* p);
+// C (may be null; written only when the plan is ok): (K, 64) complex64, the product phi L rounded once from fp64 -- what
+// psa_lowrank_plan reports beside the two factors.  No kernel reads it, so a launch asks for none.
+int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, const int32_t* h_idx, int64_t n_g, LowRankPlan* p,
+                 float* C = nullptr);
 int prepare_lowrank(psa_ctx* c, const GroupView& v, const ProjectArgs& list, int64_t k_first, int64_t nk, ProjGeom* g);
 // api_modes.hip: what psa_sed_modes, psa_sed_modes_welch and their fits were called with, and their one body.  The result,
 // (T, K, M) or with segments (L, K, M), is left in c->d_modes_out.  `segments`: the context's segments are honoured or

@@ -33,7 +33,8 @@ constexpr double LR_OMEGA = 30.0;                 // half-width product h_k h_x 
 constexpr double LR_D_MAX = 1.0 / 8192.0;         // 2^-13
 }  // namespace
 
-int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, const int32_t* h_idx, int64_t n_g, LowRankPlan* p) {
+int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, const int32_t* h_idx, int64_t n_g, LowRankPlan* p,
+                 float* C) {
     *p = LowRankPlan{};
     auto fail = [&](const char* why) {
         p->why = why;
@@ -156,8 +157,8 @@ int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, co
         p->kappa[l] = mid + half * std::cos(th);
         bw[l] = ((l & 1) ? -1.0 : 1.0) * std::sin(th);           // barycentric weights of Chebyshev points of the first kind
     }
-    // ---- C[j, l] = exp(i kappa_j x_c) L_l(kappa_j), complex64; L[j, l] and phi[j], each rounded from fp64 on its own
-    p->C.assign((size_t)K * LOWRANK_NODES * 2, 0.f);
+    // ---- L[j, l] and phi[j], each rounded from fp64 on its own; for a caller that asks, C[j, l] = exp(i kappa_j x_c)
+    // L_l(kappa_j), complex64, their product rounded once
     p->L.assign((size_t)K * LOWRANK_NODES, 0.f);
     p->phi.assign((size_t)K * 2, 0.f);
     for (int64_t j = 0; j < K; ++j) {
@@ -180,8 +181,10 @@ int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, co
         p->phi[(size_t)j * 2 + 1] = (float)ci;
         for (int l = 0; l < LOWRANK_NODES; ++l) {
             p->L[(size_t)j * LOWRANK_NODES + l] = (float)L[l];
-            p->C[((size_t)j * LOWRANK_NODES + l) * 2 + 0] = (float)(cr * L[l]);
-            p->C[((size_t)j * LOWRANK_NODES + l) * 2 + 1] = (float)(ci * L[l]);
+            if (C) {
+                C[((size_t)j * LOWRANK_NODES + l) * 2 + 0] = (float)(cr * L[l]);
+                C[((size_t)j * LOWRANK_NODES + l) * 2 + 1] = (float)(ci * L[l]);
+            }
         }
     }
     // ---- scale of D: the bound lands at or below 2^14 (float16 maximum 65504)
@@ -191,8 +194,8 @@ int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, co
 }
 
 // Decide the route of one projection launch (a group's planes, nk k-vectors from k_first of the list) and, when the
-// low-rank route serves, upload what it needs: fp64 [k0 (3), u (3), x_c, kappa (64), kline (nk x 3)] and the combine
-// matrix of the context's arm (C, or L and phi).
+// low-rank route serves, upload what it needs: fp64 [k0 (3), u (3), x_c, kappa (64), kline (nk x 3)] and the
+// combine's weights L and phases phi.
 // The decision depends on the list, the group and the options only -- never on how the list is split over
 // calls -- as long as every part keeps PSA_OPT_K1_LOWRANK_MIN_LOCAL vectors (default 128: a 512-row D block at
 // least half full).
@@ -211,12 +214,8 @@ int prepare_lowrank(psa_ctx* c, const GroupView& v, const ProjectArgs& list, int
     std::memcpy(f64.data() + 7, p.kappa, sizeof(p.kappa));
     std::memcpy(f64.data() + 7 + LOWRANK_NODES, p.kline.data(), p.kline.size() * sizeof(double));
     PSA_TRY(upload(c, c->d_lr_f64, f64.data(), f64.size() * sizeof(double)));
-    if (c->k1_combine_arm == 2) {
-        PSA_TRY(upload(c, c->d_lr_L, p.L.data(), p.L.size() * sizeof(float)));
-        PSA_TRY(upload(c, c->d_lr_phi, p.phi.data(), p.phi.size() * sizeof(float)));
-    } else {
-        PSA_TRY(upload(c, c->d_lr_C, p.C.data(), p.C.size() * sizeof(float)));
-    }
+    PSA_TRY(upload(c, c->d_lr_L, p.L.data(), p.L.size() * sizeof(float)));
+    PSA_TRY(upload(c, c->d_lr_phi, p.phi.data(), p.phi.size() * sizeof(float)));
     PSA_TRY(c->d_lr_qn.reserve((size_t)LOWRANK_NODES * 3 * (size_t)c->slot[v.slot].T * sizeof(float2)));
     g->lowrank = true;
     g->dscale = p.dscale;
@@ -236,12 +235,11 @@ int psa_lowrank_plan(const float* k_vectors, int64_t K, const float* mean_pos_al
                     (K == 0 || k_vectors) && mean_pos_all,
                 "bad argument");
     LowRankPlan p;
-    PSA_TRY(plan_lowrank(k_vectors, K, mean_pos_all, N, idx, n_g, &p));
+    PSA_TRY(plan_lowrank(k_vectors, K, mean_pos_all, N, idx, n_g, &p, C));
     *ok = p.ok;
     const double g[12] = {p.u[0], p.u[1], p.u[2], p.k0[0], p.k0[1], p.k0[2], p.x_c, p.h_x, p.width, (double)p.interval, p.d_bound, p.dscale};
     std::memcpy(geo, g, sizeof(g));
     if (p.ok && kappa) std::memcpy(kappa, p.kappa, sizeof(p.kappa));
-    if (p.ok && C) std::memcpy(C, p.C.data(), p.C.size() * sizeof(float));
     if (p.ok && L) std::memcpy(L, p.L.data(), p.L.size() * sizeof(float));
     if (p.ok && phi) std::memcpy(phi, p.phi.data(), p.phi.size() * sizeof(float));
     return PSA_OK;

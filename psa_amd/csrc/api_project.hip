@@ -342,13 +342,8 @@ static int launch_projection_once(psa_ctx* c, const GroupView& v, ProjGeom g, fl
             ProjGeom gd = g;
             gd.M_pad = g.M_pad_d;
             PSA_TRY(launch_k1_planes_diff(c, pl, c->d_lr_diff.ptr, d_q, gd, n_fg, g.dscale));
-            if (c->k1_combine_arm == 0)
-                PSA_TRY(launch_lowrank_combine(c, c->d_lr_qn.as<float2>(), c->d_lr_C.as<float2>(), d_q, g, t_count));
-            else if (c->k1_combine_arm == 1)
-                PSA_TRY(launch_lowrank_combine_v(c, c->d_lr_qn.as<float2>(), c->d_lr_C.as<float2>(), d_q, g, t_count));
-            else
-                PSA_TRY(launch_lowrank_combine_r(c, c->d_lr_qn.as<float2>(), c->d_lr_L.as<float>(), c->d_lr_phi.as<float2>(), d_q, g,
-                                                 t_count));
+            PSA_TRY(launch_lowrank_combine_r(c, c->d_lr_qn.as<float2>(), c->d_lr_L.as<float>(), c->d_lr_phi.as<float2>(), d_q, g,
+                                             t_count));
             ++c->lowrank_launches;
             return PSA_OK;
         }

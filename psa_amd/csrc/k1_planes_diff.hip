@@ -6,7 +6,7 @@
 // small (|D| <= 2^-13, checked by the plan) and goes through ONE float16 product with the hi plane.  So
 //     q = C (W v) + D v_hi
 // = a 128-row "2 x f16" launch of the existing planes kernel (node_table_kernel -> k1_planes_lw.hip), the D pass
-// below (one MFMA per row tile and component instead of three, hi plane only), and lowrank_combine_kernel.
+// below (one MFMA per row tile and component instead of three, hi plane only), and the combine (lowrank_combine.hip).
 //
 // D pass: 512-ROW x 64-frame workgroup tile.  Eight wavefronts, two per SIMD; wavefront w = 4 h + f owns rows
 // [256 h, +256) x frames [16 f, +16) x 3 components = 48 accumulator tiles (192 registers), the stage's three B
@@ -271,48 +271,6 @@ int launch_lowrank_tables(psa_ctx* c, const float* d_kvec, const double* d_kline
                                  c->stream));
     hipLaunchKernelGGL(node_table_kernel, dim3(LOWRANK_NODES, (g.A_pad + 255) / 256), dim3(256), 0, c->stream, d_geo, d_kappa, d_mean_all,
                        d_idx, g.weights, 1.f / g.wscale, (_Float16*)d_nodes, g.n_g, g.A_pad);
-    PSA_HIP_CHECK(hipGetLastError());
-    return PSA_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// q[j, c, t] += sum_l C[j, l] Qn[l, c, t]: float32, l in order (the result of a row does not depend on the
-// other rows of the launch).  A thread holds the 64 node values of one (c, t) and walks JB rows; C is uniform
-// across the block (scalar loads).
-// ---------------------------------------------------------------------------------------------
-constexpr int COMBINE_JB = 64;
-__global__ void __launch_bounds__(256)
-lowrank_combine_kernel(const float2* __restrict__ Qn, const float2* __restrict__ Cm, float2* __restrict__ q, int64_t T,
-                       int64_t q_stride, int64_t qn_stride, int K) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int     c = blockIdx.y;
-    const int     j0 = blockIdx.z * COMBINE_JB;
-    if (t >= T) return;
-    float2 v[LOWRANK_NODES];
-#pragma unroll
-    for (int l = 0; l < LOWRANK_NODES; ++l) v[l] = Qn[((int64_t)l * 3 + c) * qn_stride + t];
-    const int j1 = j0 + COMBINE_JB < K ? j0 + COMBINE_JB : K;
-    for (int j = j0; j < j1; ++j) {
-        const float2* cj = Cm + (size_t)j * LOWRANK_NODES;
-        float         sr = 0.f, si = 0.f;
-#pragma unroll
-        for (int l = 0; l < LOWRANK_NODES; ++l) {
-            const float2 w = cj[l];
-            sr = __fmaf_rn(w.x, v[l].x, sr);
-            sr = __fmaf_rn(-w.y, v[l].y, sr);
-            si = __fmaf_rn(w.x, v[l].y, si);
-            si = __fmaf_rn(w.y, v[l].x, si);
-        }
-        float2& o = q[((int64_t)j * 3 + c) * q_stride + t];
-        o = make_float2(o.x + sr, o.y + si);
-    }
-}
-
-int launch_lowrank_combine(psa_ctx* c, const float2* d_qn, const float2* d_C, float2* d_q, const ProjGeom& g, int64_t qn_stride) {
-    const int64_t nb = (g.T + 255) / 256;
-    PSA_REQUIRE(nb < (1ll << 31) && g.K > 0, "combine grid too large");
-    hipLaunchKernelGGL(lowrank_combine_kernel, dim3((unsigned)nb, 3, (unsigned)((g.K + COMBINE_JB - 1) / COMBINE_JB)), dim3(256), 0,
-                       c->stream, d_qn, d_C, d_q, g.T, g.q_stride, qn_stride, g.K);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;
 }

@@ -251,12 +251,9 @@ struct psa_ctx {
     int64_t      opt_k1_lowrank_min_k = 256;    // PSA_OPT_K1_LOWRANK_MIN_K: shortest whole k-list it serves
     int64_t      opt_k1_lowrank_min_local = 128; // PSA_OPT_K1_LOWRANK_MIN_LOCAL: shortest part of it one launch serves
     int64_t      lowrank_launches = 0;          // projection launches that took the route (psa_k1_lowrank_launches)
-    // PSA_K1_COMBINE (environment, psa_create): 2 real weights + one phase per element (lowrank_combine_r_kernel),
-    // 1 packed complex weights (lowrank_combine_v_kernel), 0 the scalar combine (bit-identical to 1)
-    int          k1_combine_arm = 2;
-    // its D image, node projections, C (arms 0, 1) or L and phi (arm 2), fp64 inputs (the node table goes into d_phase);
+    // its D image, node projections, the combine's L and phi, fp64 inputs (the node table goes into d_phase);
     // released when the route is switched off
-    psa::DevBuf  d_lr_diff, d_lr_qn, d_lr_C, d_lr_L, d_lr_phi, d_lr_f64;
+    psa::DevBuf  d_lr_diff, d_lr_qn, d_lr_L, d_lr_phi, d_lr_f64;
 
     // per-atom weights of every projection (psa_set_atom_weights): d_weights holds weights_N values, none when 0;
     // weights_scale = 2^e, the smallest power of two >= their largest magnitude
@@ -360,18 +357,15 @@ int    launch_k1_planes_lw(psa_ctx* c, const void* d_planes, const void* d_phase
 int    launch_k1_planes_wide(psa_ctx* c, const void* d_planes, const void* d_phase, float2* d_q, const ProjGeom& g,
                              int64_t n_fg);
 
-// --- k1_planes_diff.hip (low-rank route for k-paths: tables, D pass, combine; planned in api_lowrank.hip)
+// --- k1_planes_diff.hip (low-rank route for k-paths: tables, D pass; planned in api_lowrank.hip)
 size_t pd16_table_bytes(int M_pad, int A_pad);
 int    launch_lowrank_tables(psa_ctx* c, const float* d_kvec, const double* d_kline, const double* d_geo, const double* d_kappa,
                              const float* d_mean_all, const int* d_idx, void* d_diff, void* d_nodes, const ProjGeom& g, int M_pad_d,
                              float dscale);
 int    launch_k1_planes_diff(psa_ctx* c, const void* d_planes, const void* d_diff, float2* d_q, const ProjGeom& g, int64_t n_fg,
                              float dscale);
-int    launch_lowrank_combine(psa_ctx* c, const float2* d_qn, const float2* d_C, float2* d_q, const ProjGeom& g, int64_t qn_stride);
 
-// --- lowrank_combine.hip (the packed combines: _v complex weights, arm 1; _r real weights + one phase per element,
-// arm 2, the default; the arm: psa_ctx::k1_combine_arm, PSA_K1_COMBINE)
-int    launch_lowrank_combine_v(psa_ctx* c, const float2* d_qn, const float2* d_C, float2* d_q, const ProjGeom& g, int64_t qn_stride);
+// --- lowrank_combine.hip (the route's combine: real weights + one phase per element)
 int    launch_lowrank_combine_r(psa_ctx* c, const float2* d_qn, const float* d_L, const float2* d_phi, float2* d_q, const ProjGeom& g,
                                 int64_t qn_stride);
 

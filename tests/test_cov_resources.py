@@ -6,23 +6,10 @@ that two workgroups share a compute unit's 160 KiB, the products on the fp32 mat
 stream: the accumulators are the MFMA's own registers (4 per tile pair, at most one more tile's worth in AGPRs) and the block that holds the
 MFMAs has no branch but its own back edge and does not copy the accumulators."""
 import re
-import shutil
-import subprocess
-from pathlib import Path
 
 import pytest
 
-from conftest import ROOT
-
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-SRC = ROOT / "psa_amd" / "csrc"
-
-
-def _flags():
-    line = next(ln for ln in (SRC / "Makefile").read_text().splitlines() if ln.startswith("CXXFLAGS"))
-    cont = (SRC / "Makefile").read_text().split(line)[1].splitlines()[1]
-    raw = (line.split(":=")[1].rstrip("\\") + " " + cont).split()
-    return [f.replace("$(ARCH)", "gfx950").replace("$(ROOT)", str(ROOT)) for f in raw if not f.startswith("-W")]
+from kernel_build import SRC, device_compile
 
 
 def test_makefile_lists_the_sources():
@@ -34,21 +21,11 @@ def test_makefile_lists_the_sources():
 
 
 @pytest.fixture(scope="module")
-def compiled(tmp_path_factory):
+def compiled():
     """(resource remarks per kernel, assembly) of covariance.hip, compiled once"""
-    if not Path(HIPCC).exists():
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("covariance") / "k.s"
-    res = subprocess.run([HIPCC, *_flags(), "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                          str(SRC / "covariance.hip"), "-o", str(out)], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr[-2000:]
-    blocks = re.split(r"remark: [^\n]*Function Name: ", res.stderr)[1:]
-    usage = {}
-    for b in blocks:
-        usage[b.split()[0]] = {k: int(v) for k, v in re.findall(
-            r"(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|VGPRs|AGPRs|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", b)}
-    print(usage)
-    return usage, out.read_text()
+    c = device_compile("covariance.hip")
+    print(c.usage)
+    return c.usage, c.asm
 
 
 def test_covariance_kernels_resources(compiled):

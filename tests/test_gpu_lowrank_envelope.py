@@ -2,13 +2,12 @@
 (tests/ref64.py) at the edges of what its plan accepts: other lattice directions and the negative side, segments
 away from Gamma, D at its limit (positions far from the origin, k-vectors off the line, mass weights), row tails of
 the D pass's 512-row blocks and of the combine's 64-row / odd-row staging, frame and atom tails, incoherent groups
-with different plans, long lists cut into k-blocks, split invariance and both combine arms.
+with different plans, long lists cut into k-blocks and split invariance.
 
 Every case forces the route on (any list length, any launch size, planes for every group) and checks, besides the
 global max-norm error, the error of each k-row against that row's own maximum.  In the "D at its limit" cases the
 line-only reference (the route with its D term lost) must lie at least 10x the tolerance away from the true one, so a
 D pass that is wrong cannot pass.  Each case prints its route, its errors and that margin."""
-import os
 import time
 
 import numpy as np
@@ -162,8 +161,9 @@ def test_atom_tails(forced, case):
 
 # ---- incoherent groups whose plans differ -------------------------------------------------------------------------
 def test_incoherent_groups_with_different_plans(forced):
-    """A thin slab across u, the whole box and one atom: three plans (x_c, node interval width), three uploads of C and
-    the fp64 table, one after the other.  The lone atom moves sqrt(N) times faster, so its group is not lost in the sum."""
+    """A thin slab across u, the whole box and one atom: three plans (x_c, node interval width), three uploads of L,
+    phi and the fp64 table, one after the other.  The lone atom moves sqrt(N) times faster, so its group is not lost in
+    the sum."""
     from psa_amd import _hip
     t0 = time.perf_counter()
     k, r, _ = geometry("plain_100")
@@ -212,38 +212,13 @@ def test_split_invariance(forced, name):
         assert np.array_equal(got.view(np.uint32), whole.view(np.uint32)), parts
 
 
-# ---- both combine arms on tail shapes -----------------------------------------------------------------------------
-def _arm_engine(arm):
-    from psa_amd import _hip
-    old = os.environ.get("PSA_K1_COMBINE")
-    os.environ["PSA_K1_COMBINE"] = arm
-    try:
-        return _hip.Engine(0)
-    finally:
-        if old is None:
-            os.environ.pop("PSA_K1_COMBINE", None)
-        else:
-            os.environ["PSA_K1_COMBINE"] = old
-
-
-def test_combine_arms_on_tails():
-    """PSA_K1_COMBINE=0 (scalar) and 1 (packed), one engine each: bit-identical, and both within tolerance"""
-    shapes = [3, 65, 257]
-    k_r = {K: geometry("seg_1", K) for K in shapes}
+# ---- the combine on tail shapes away from Gamma ------------------------------------------------------------------
+def test_combine_on_tails(forced):
+    """A segment away from Gamma x odd rows and 64-row-stage row tails x a 17-frame block"""
     x = _data(17, N_ATOMS, 30)
-    refs = {K: _refs(x, k_r[K][1], k_r[K][0]) for K in shapes}
-    out = {}
-    for arm in ("0", "1"):
-        eng = _arm_engine(arm)
-        try:
-            _force(eng)
-            for K in shapes:
-                k, r, _ = k_r[K]
-                got, n = _project(eng, x, r, k)
-                out[arm, K] = got
-                _check(f"arm {arm}, K={K}, T=17", got, refs[K], n)
-        finally:
-            eng.close()
-    for K in shapes:
-        diff = np.count_nonzero(out["0", K].view(np.uint32) != out["1", K].view(np.uint32))
-        assert diff == 0, f"K={K}: {diff} words differ between the arms"
+    for K in (3, 65, 257):
+        t0 = time.perf_counter()
+        k, r, interval = geometry("seg_1", K)
+        _plan(k, r, interval=interval)
+        got, n = _project(forced, x, r, k)
+        _check(f"seg_1, K={K}, T=17", got, _refs(x, r, k), n, t0=t0)

@@ -3,34 +3,19 @@ and no spills (its 64 node values per thread live in registers), at most 256 VGP
 v_pk_fma_f32 per node and row and one ds_read_b128 per four nodes and row, and per output element the phase sequence
 of two multiplies and two FMAs -- no second packed FMA per node, no scalar-FMA fallback for the node sum."""
 import re
-import subprocess
-from pathlib import Path
 
-import pytest
-
-from test_lowrank_combine_resources import HIPCC, SRC, _flags
+from kernel_build import device_compile
 
 KERNEL = "lowrank_combine_r_kernel"
 
 
-def test_lowrank_combine_r_budget(tmp_path):
-    if not Path(HIPCC).exists():
-        pytest.skip("no hipcc")
-    asm = tmp_path / "k.s"
-    res = subprocess.run([HIPCC, *_flags(), "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                          str(SRC / "lowrank_combine.hip"), "-o", str(asm)], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr[-2000:]
-    usage = res.stderr[res.stderr.index(KERNEL):]
-    nxt = usage.find("Function Name", 1)
-    usage = usage if nxt < 0 else usage[:nxt]
-    scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", usage).group(1))
-    spills = int(re.search(r"VGPRs Spill: (\d+)", usage).group(1))
-    vgprs = int(re.search(r" VGPRs: (\d+)", usage).group(1))
-    lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", usage).group(1))
+def test_lowrank_combine_r_budget():
+    _, usage, text = device_compile("lowrank_combine.hip")
+    u = next(v for k, v in usage.items() if KERNEL in k)
+    scratch, spills, vgprs, lds = u["ScratchSize [bytes/lane]"], u["VGPRs Spill"], u["VGPRs"], u["LDS Size [bytes/block]"]
     print(f"{KERNEL}: {vgprs} VGPRs, {spills} spilled, {scratch} B scratch per lane, {lds} B LDS")
     assert scratch == 0 and spills == 0 and vgprs <= 256, (scratch, spills, vgprs)
     assert lds == 64 * 64 * 4 + 64 * 8, lds                     # 64 rows of L and their phases
-    text = asm.read_text()
     body = text[re.search(rf"^_ZN3psa\d+{KERNEL}\w*:", text, re.M).start():]
     body = body[:body.index("s_endpgm")]
     assert "scratch_" not in body

@@ -2,17 +2,12 @@
 its combine matrix times the node exponentials gives the line's phases, that its bound on D holds, and that it does
 not depend on how a path is split.  No GPU: the plan is host code, the D-pass kernel is checked by its resources."""
 import re
-import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from kernel_build import device_compile
 from lowrank_cases import D_LIMIT, DIRECTIONS, LIMITS, geometry, mass_weights
-
-SRC = ROOT / "psa_amd" / "csrc"
 
 
 def _path(cfg):
@@ -136,23 +131,14 @@ def test_index_list_group():
     _check_plan(p, vecs, r0[idx])
 
 
-def test_diff_kernel_uses_no_scratch(tmp_path):
+def test_diff_kernel_uses_no_scratch():
     """The D pass waits for its LDS-DMA with a counted vmcnt: no scratch, no spill (tests/test_kernel_resources.py)."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not Path(hipcc).exists():
-        pytest.skip("no hipcc")
-    line = next(ln for ln in (SRC / "Makefile").read_text().splitlines() if ln.startswith("CXXFLAGS"))
-    cont = (SRC / "Makefile").read_text().split(line)[1].splitlines()[1]
-    flags = [f.replace("$(ARCH)", "gfx950").replace("$(ROOT)", str(ROOT))
-             for f in (line.split(":=")[1].rstrip("\\") + " " + cont).split() if not f.startswith("-W")]
-    res = subprocess.run([hipcc, *flags, "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                          str(SRC / "k1_planes_diff.hip"), "-o", str(tmp_path / "k.s")], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr[-2000:]
+    res = device_compile("k1_planes_diff.hip")
     scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", res.stderr)]
     spills = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", res.stderr)]
     assert scratch and all(s == 0 for s in scratch), res.stderr[-1500:]
     assert all(s == 0 for s in spills), spills
-    asm = (tmp_path / "k.s").read_text()
+    asm = res.asm
     assert "scratch_" not in asm
     # two instantiations x 40 unrolled stages x 16 row tiles x 3 components
     assert asm.count("v_mfma_f32_16x16x32_f16") == 2 * 40 * 48

@@ -6,27 +6,14 @@ registers, within the 128 VGPRs that four wavefronts per SIMD allow, the LDS til
 4 x 33024 bytes, still share a compute unit's 160 KiB), the coefficients through uniform loads, and neither instantiation
 above the registers or below the occupancy of the separate kernel it replaced."""
 import re
-import shutil
-import subprocess
-from pathlib import Path
 
 import pytest
 
-from conftest import ROOT
-
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-SRC = ROOT / "psa_amd" / "csrc"
+from kernel_build import SRC, device_compile
 LDS_PER_CU = 160 * 1024
 # (VGPRs, wavefronts per SIMD) of mode_power_kernel<MT> and mode_welch_kernel<MT> before they became one template
 BEFORE = {(8, False): (38, 8), (16, False): (54, 8), (24, False): (66, 6), (32, False): (86, 4),
           (8, True): (54, 8), (16, True): (78, 6), (24, True): (96, 5), (32, True): (94, 4)}
-
-
-def _flags():
-    line = next(ln for ln in (SRC / "Makefile").read_text().splitlines() if ln.startswith("CXXFLAGS"))
-    cont = (SRC / "Makefile").read_text().split(line)[1].splitlines()[1]
-    raw = (line.split(":=")[1].rstrip("\\") + " " + cont).split()
-    return [f.replace("$(ARCH)", "gfx950").replace("$(ROOT)", str(ROOT)) for f in raw if not f.startswith("-W")]
 
 
 def test_makefile_lists_the_sources():
@@ -38,21 +25,11 @@ def test_makefile_lists_the_sources():
 
 
 @pytest.fixture(scope="module")
-def compiled(tmp_path_factory):
+def compiled():
     """(resource remarks per kernel, assembly) of modes.hip, compiled once"""
-    if not Path(HIPCC).exists():
-        pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("modes") / "k.s"
-    res = subprocess.run([HIPCC, *_flags(), "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", str(SRC / "modes.hip"),
-                          "-o", str(out)], capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr[-2000:]
-    blocks = re.split(r"remark: [^\n]*Function Name: ", res.stderr)[1:]
-    usage = {}
-    for b in blocks:
-        usage[b.split()[0]] = {k: int(v) for k, v in re.findall(
-            r"(ScratchSize \[bytes/lane\]|VGPRs Spill|SGPRs Spill|VGPRs|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", b)}
-    print(usage)
-    return usage, out.read_text()
+    c = device_compile("modes.hip")
+    print(c.usage)
+    return c.usage, c.asm
 
 
 def _check(compiled, summed):
