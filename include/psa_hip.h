@@ -500,7 +500,15 @@ int psa_debug_project_only(psa_ctx* ctx, int slot, const float* mean_pos_all,
                            const float* k_vectors, int64_t K,
                            const int32_t* idx, int64_t n_g, int32_t flags,
                            void* out_host);
-/* the same for frames [t_begin, t_begin + t_count) only, written into those columns of a zeroed
+/* the same over all frames, launched as psa_sed_project launches a list that consists of these K vectors: it takes the
+ * low-rank route for k-paths (PSA_OPT_K1_LOWRANK) where that call would, and psa_k1_lowrank_launches counts it.  The
+ * list is taken as it is: not folded ((k, -k) pairs, twins) and not cut into k-blocks.
+ * psa_debug_project_only and psa_debug_project_frames never take that route. */
+int psa_debug_project_route(psa_ctx* ctx, int slot, const float* mean_pos_all,
+                            const float* k_vectors, int64_t K,
+                            const int32_t* idx, int64_t n_g, int32_t flags,
+                            void* out_host);
+/* psa_debug_project_only for frames [t_begin, t_begin + t_count) only, written into those columns of a zeroed
  * (K,3,T) slab (what a frame-sharded or streaming projection does per piece) */
 int psa_debug_project_frames(psa_ctx* ctx, int slot, const float* mean_pos_all,
                              const float* k_vectors, int64_t K,

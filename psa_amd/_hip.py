@@ -106,6 +106,8 @@ SIGNATURES = {
                                         C.c_int64, C.c_void_p]),
     "psa_debug_project_only": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p,
                                          C.c_int64, C.c_int32, C.c_void_p]),
+    "psa_debug_project_route": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p,
+                                          C.c_int64, C.c_int32, C.c_void_p]),
     "psa_debug_project_frames": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p,
                                            C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
     "psa_debug_mode_power": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _f32p]),
@@ -878,9 +880,13 @@ class Engine:
             out.ctypes.data_as(C.c_void_p)), "psa_debug_phase_table")
         return out
 
-    def debug_project_only(self, slot, mean_pos_all, k_vectors, idx=None, flags=0, frames=None) -> np.ndarray:
+    def debug_project_only(self, slot, mean_pos_all, k_vectors, idx=None, flags=0, frames=None, route=False) -> np.ndarray:
         """q before the FFT, (K,3,T); `frames=(t_begin, t_count)` projects only those frames (the
-        other columns are zero)."""
+        other columns are zero).  It never takes the low-rank route for k-paths unless `route=True`: then the
+        launch is routed as `project` routes a list of these k-vectors (all frames; psa_debug_project_route) and
+        `lowrank_launches` counts it."""
+        if route and frames is not None:
+            raise ValueError("route=True projects all frames")
         T, N = self.shape(slot)
         mean = _as_f32(mean_pos_all, (3,))
         kv = _as_f32(k_vectors, (3,))
@@ -888,7 +894,11 @@ class Engine:
         n_g = N if ii is None else len(ii)
         out = np.empty((kv.shape[0], 3, T), np.complex64)
         ip = ii.ctypes.data_as(_i32p) if ii is not None else None
-        if frames is None:
+        if route:
+            _check(self._lib.psa_debug_project_route(
+                self._h, slot, _f32(mean), _f32(kv), kv.shape[0], ip, n_g, flags,
+                out.ctypes.data_as(C.c_void_p)), "psa_debug_project_route")
+        elif frames is None:
             _check(self._lib.psa_debug_project_only(
                 self._h, slot, _f32(mean), _f32(kv), kv.shape[0], ip, n_g, flags,
                 out.ctypes.data_as(C.c_void_p)), "psa_debug_project_only")

@@ -1,4 +1,5 @@
-// Diagnostics: the float32 phase table, the projection without its FFT (all frames or a range), the plane cache.
+// Diagnostics: the float32 phase table, the projection without its FFT (all frames or a range, or as a list of its own
+// is routed), the plane cache.
 // (part of the C ABI of libpsa_hip.so, include/psa_hip.h; shared declarations: api_internal.h)
 #include "api_internal.h"
 
@@ -38,8 +39,14 @@ int psa_debug_phase_table(psa_ctx* c, const float* mean_pos_all, const float* k_
     return PSA_OK;
 }
 
+// route: the launch goes through project_block with the K vectors offered as a whole list, as project_groups hands
+// psa_sed_project's list to it -- so the low-rank route for k-paths serves where its plan, the options and the group's
+// planes let it, and psa_k1_lowrank_launches counts it -- over all frames of the slot.  What psa_sed_project does to a list
+// before that is not done here: the list is neither folded (begin_list: pairs (k, -k), twins) nor cut into k-blocks
+// (PSA_PHASE_TABLE_MIB).
 static int debug_project(psa_ctx* c, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K,
-                         const int32_t* idx, int64_t n_g, int32_t flags, int64_t t_begin, int64_t t_count, void* out_host) {
+                         const int32_t* idx, int64_t n_g, int32_t flags, int64_t t_begin, int64_t t_count, void* out_host,
+                         bool route = false) {
     PSA_TRY(enter(c));
     Guard guard(c);
     PSA_TRY(check_slot(c, slot));
@@ -53,15 +60,20 @@ static int debug_project(psa_ctx* c, int slot, const float* mean_pos_all, const 
     PSA_TRY(upload_single_group(c, &v, N, k_vectors, K, mean_pos_all));
     c->plane_call_mark = c->plane_tick + 1;
     PSA_TRY(group_source(c, &v, mean_pos_all, K));
-    // project_block's pieces (no low-rank route), with the zero-fill where it has always been issued and the launch
-    // over the caller's frame range
-    ProjGeom g;
-    PSA_TRY(make_geom(c, v, K, GeomRule::product, &g));
     const size_t bytes = (size_t)K * 3 * T * sizeof(float2);
     PSA_TRY(c->d_qwork.reserve(bytes));
-    if (t_count != T) PSA_HIP_CHECK(hipMemsetAsync(c->d_qwork.ptr, 0, bytes, c->stream));
-    PSA_TRY(prepare_phase(c, v, g, 0));
-    if (t_count > 0) PSA_TRY(launch_projection(c, v, g, c->d_qwork.as<float2>(), T, t_begin, t_count));
+    if (route) {
+        const ProjectArgs list{slot, mean_pos_all, k_vectors, K, K, 0, nullptr, nullptr, 1, flags};
+        PSA_TRY(project_block(c, v, &list, 0, K, c->d_qwork.as<float2>()));
+    } else {
+        // project_block's pieces (no low-rank route), with the zero-fill where it has always been issued and the launch
+        // over the caller's frame range
+        ProjGeom g;
+        PSA_TRY(make_geom(c, v, K, GeomRule::product, &g));
+        if (t_count != T) PSA_HIP_CHECK(hipMemsetAsync(c->d_qwork.ptr, 0, bytes, c->stream));
+        PSA_TRY(prepare_phase(c, v, g, 0));
+        if (t_count > 0) PSA_TRY(launch_projection(c, v, g, c->d_qwork.as<float2>(), T, t_begin, t_count));
+    }
     PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_qwork.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
     PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return PSA_OK;
@@ -70,6 +82,12 @@ static int debug_project(psa_ctx* c, int slot, const float* mean_pos_all, const 
 int psa_debug_project_only(psa_ctx* c, int slot, const float* mean_pos_all, const float* k_vectors,
                            int64_t K, const int32_t* idx, int64_t n_g, int32_t flags, void* out_host) {
     return debug_project(c, slot, mean_pos_all, k_vectors, K, idx, n_g, flags, 0, -1, out_host);
+}
+
+// The projection routed as a list of its own: see debug_project
+int psa_debug_project_route(psa_ctx* c, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K,
+                            const int32_t* idx, int64_t n_g, int32_t flags, void* out_host) {
+    return debug_project(c, slot, mean_pos_all, k_vectors, K, idx, n_g, flags, 0, -1, out_host, true);
 }
 
 int psa_debug_project_frames(psa_ctx* c, int slot, const float* mean_pos_all, const float* k_vectors, int64_t K,

@@ -81,15 +81,17 @@ QUIET_FAMILIES = ["quiet_frames", "quiet_blocks", "coherent", "pow2_max_0", "pow
                   "pow2_max_below_1", "weighted_mass", "weighted_charge"]
 
 
-def case(family, K=None, n=None, T=None, quiet_exp=-10):
+def case(family, K=None, n=None, T=None, quiet_exp=-10, r=None, k=None):
     """dict(data (T, N, 3) float32, r (N, 3) float32 mean positions, k (K, 3) float32, idx, weights, disp, quiet (T,) bool
     or None, n_g).  K, n, T default to the family's own shape (BASE; coherent: 4096 atoms; quiet_blocks: 160 frames);
-    the quiet frames are 2^quiet_exp of the others."""
+    the quiet frames are 2^quiet_exp of the others.  r, k: the family on these positions and k-vectors instead of its
+    own random ones (tests/lowrank_env_cases.py: a k-path; displacement mode keeps its own positions)."""
     K = K or BASE["K"]
     n = n or (4096 if family == "coherent" else BASE["n"])
     T = T or (160 if family == "quiet_blocks" else BASE["T"])
     seed = 100 + FAMILIES.index(family)
-    r, k = positions(n, seed), k_list(K)
+    r, k = positions(n, seed) if r is None else r, k_list(K) if k is None else k
+    assert r.shape == (n, 3) and k.shape == (K, 3) and r.dtype == k.dtype == np.float32
     out = dict(name=family, r=r, k=k, idx=None, weights=None, disp=False, quiet=None)
     if family in ("quiet_frames", "quiet_blocks", "weighted_mass", "weighted_charge"):
         out["quiet"] = quiet_mask(T, family == "quiet_blocks")
@@ -145,7 +147,7 @@ def with_idx(c, idx):
 
 
 # ---- NumPy models of the two splits ---------------------------------------------------------------------------------
-def _group_inputs(c):
+def group_inputs(c):
     """(d (T, n, 3) float32 group data, P (2, K, n) float32 cos / sin table, the group's atoms)"""
     g = np.arange(c["data"].shape[1]) if c["idx"] is None else np.asarray(c["idx"], np.int64)
     d = c["data"][:, g, :]
@@ -178,32 +180,49 @@ def _accumulate(terms, scale):
     return out[0] + 1j * out[1]
 
 
+def f16_weights(c, g):
+    """(w / 2^ew (n,) float32 or None, 2^ew): the group's weights as the "2 x f16" tables carry them, 2^ew >= max|w|"""
+    if c["weights"] is None:
+        return None, 1.0
+    w = c["weights"][g]
+    wscale = 2.0 ** math.ceil(math.log2(float(np.abs(w).max())))
+    return w * np.float32(1.0 / wscale), wscale
+
+
+def f16_pieces(x):
+    """x1 = f16(x), x2 = f16(x - x1) as float32 arrays; of a float32 x the residual is exact, of a float64 x (the
+    low-rank route's node table) it is rounded to float32 once"""
+    x1 = _f16(np.asarray(x, np.float32))
+    return x1, _f16(np.asarray(x - x1, np.float32))
+
+
+def f16_data(d, lose=None):
+    """(x1, x2, 2^(14-e)): the two float16 pieces of the group data d times 2^(14-e), 2^e >= max|d|; lose: frames whose
+    x2 is lost"""
+    amax = float(np.abs(d).max())
+    vscale = 2.0 ** (14 - math.ceil(math.log2(amax))) if amax > 0 else 1.0
+    x1, x2 = f16_pieces(d * np.float32(vscale))
+    if lose is not None:
+        x2[lose] = 0
+    return x1, x2, vscale
+
+
 def model_f16(c, lose=None):
     """The "2 x f16" split (k1_f16.h): d times 2^(14-e), 2^e >= max|d| of the group; P' = (w / 2^ew) (cos, sin) times
     2^14; each into x1 = f16(x), x2 = f16(x - x1); kept x1 y1 + x1 y2 + x2 y1.  lose: frames whose x2 of d is lost."""
-    d, P, g = _group_inputs(c)
-    wscale = 1.0
-    if c["weights"] is not None:
-        w = c["weights"][g]
-        wscale = 2.0 ** math.ceil(math.log2(float(np.abs(w).max())))
-        P = P * (w * np.float32(1.0 / wscale))[None, None, :]
-    amax = float(np.abs(d).max())
-    vscale = 2.0 ** (14 - math.ceil(math.log2(amax))) if amax > 0 else 1.0
-    x = d * np.float32(vscale)
-    x1 = _f16(x)
-    x2 = _f16(x - x1)
-    if lose is not None:
-        x2[lose] = 0
-    y = P * np.float32(2.0 ** 14)
-    y1 = _f16(y)
-    y2 = _f16(y - y1)
+    d, P, g = group_inputs(c)
+    wn, wscale = f16_weights(c, g)
+    if wn is not None:
+        P = P * wn[None, None, :]
+    x1, x2, vscale = f16_data(d, lose)
+    y1, y2 = f16_pieces(P * np.float32(2.0 ** 14))
     return _accumulate([(y1, x1), (y2, x1), (y1, x2)], wscale / (vscale * 2.0 ** 14))
 
 
 def model_bf16(c, lose=None):
     """The "3 x bf16" split (k1_split.hip): no scale; x = x1 + x2 + x3 in bf16, residuals exact; kept x1 y1 + x1 y2 +
     x2 y1 + x2 y2 + x1 y3 + x3 y1.  lose: frames whose x2 of d is lost (x3 is still the residual of x - x1 - x2)."""
-    d, P, g = _group_inputs(c)
+    d, P, g = group_inputs(c)
     if c["weights"] is not None:
         P = P * c["weights"][g][None, None, :]
     x1 = _bf16(d)

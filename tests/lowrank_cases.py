@@ -32,31 +32,37 @@ def mass_weights(n, seed):
 
 N_ATOMS = 2048
 
-# name: (k-vectors, positions, expected interval); the box is 40 A centred on the origin unless named otherwise
-def geometry(name, K=300):
-    centred = box(N_ATOMS, 40.0, 1, -20.0)
+# name: (k-vectors, expected interval); limit_* are "D at its limit": d_bound in D_LIMIT
+def k_vectors(name, K=300):
     if name == "dir_1-10":
-        return path([1, -1, 0], 0.0, 1.5, K), centred, 0
+        return path([1, -1, 0], 0.0, 1.5, K), 0
     if name == "dir_111":
-        return path([1, 1, 1], 0.0, 1.5, K), centred, 0
+        return path([1, 1, 1], 0.0, 1.5, K), 0
     if name == "dir_210":
-        return path([2, 1, 0], 0.0, 1.5, K), centred, 0
+        return path([2, 1, 0], 0.0, 1.5, K), 0
     if name == "neg_-1-10":                  # the canonical sign flips u: the list lies on the side kappa <= 0
-        return path([-1, -1, 0], 0.0, 1.5, K), centred, -1
+        return path([-1, -1, 0], 0.0, 1.5, K), -1
     if name == "neg_00-1":
-        return path([0, 0, -1], 0.0, 1.5, K), centred, -1
-    if name == "seg_1":                      # a segment inside [w, 2w), w = 60 / 40 * 2 = 3.0 for this box
-        return path([1, 0, 0], 3.2, 5.5, K), centred, 1
+        return path([0, 0, -1], 0.0, 1.5, K), -1
+    if name == "seg_1":                      # a segment inside [w, 2w), w = 60 / 40 * 2 = 3.0 for the centred box
+        return path([1, 0, 0], 3.2, 5.5, K), 1
     if name == "seg_-2":                     # its mirror image
-        return path([-1, 0, 0], 3.2, 5.5, K), centred, -2
+        return path([-1, 0, 0], 3.2, 5.5, K), -2
     if name == "plain_100":
-        return path([1, 0, 0], 0.0, 1.5, K), centred, 0
-    # ---- D at its limit: d_bound in D_LIMIT
-    if name == "limit_shift":                # a 20 A box 110 A from the origin: phases up to ~450 rad, 3 roundings
-        return path([1, 1, 1], 0.0, 2.0, K), box(N_ATOMS, 20.0, 1, 110.0), 0
+        return path([1, 0, 0], 0.0, 1.5, K), 0
+    if name == "limit_shift":                # with its box 110 A from the origin: phases up to ~450 rad, 3 roundings
+        return path([1, 1, 1], 0.0, 2.0, K), 0
     if name == "limit_offline":              # 1e-6 of perpendicular scatter: D carries a real off-line phase
-        return scattered(path([1, 0, 0], 0.0, 1.5, K), 1e-6, 2), centred, 0
+        return scattered(path([1, 0, 0], 0.0, 1.5, K), 1e-6, 2), 0
     raise KeyError(name)
+
+
+# name: (k-vectors, positions, expected interval); the box is 40 A centred on the origin, but limit_shift's: 20 A, 110 A
+# from the origin
+def geometry(name, K=300):
+    k, interval = k_vectors(name, K)
+    r = box(N_ATOMS, 20.0, 1, 110.0) if name == "limit_shift" else box(N_ATOMS, 40.0, 1, -20.0)
+    return k, r, interval
 
 
 DIRECTIONS = ["dir_1-10", "dir_111", "dir_210", "neg_-1-10", "neg_00-1", "seg_1", "seg_-2"]

@@ -121,8 +121,11 @@ def test_odd_shapes_against_dense(engine, case):
             out[lr] = engine.finalize(T, K, False)
             taken[lr] = engine.lowrank_launches() - n0
         assert taken[0] == 0
-        if case != "displacements":
-            assert taken[1] == 1
+        # displacement mode too: group_source takes the group's planes of positions - mean (get_planes builds them here:
+        # all atoms, 300 k-vectors >= PSA_OPT_PLANES_MIN_K, finite data, room in HBM), the launch is a planes launch and
+        # prepare_lowrank serves it like any other.  Only without that plane set -- the float32 displacement array or the
+        # subtract-while-staging kernel -- does displacement mode stay off the route.
+        assert taken[1] == 1
         err = rel_max(out[1], out[0])
         print(f"{case}: route taken {taken[1]}, lowrank vs dense rel_max {err:.3e}")
         assert err <= 1e-6
