@@ -152,6 +152,12 @@ int         psa_set_k1(psa_ctx* ctx, int selector);     /* PSA_K1_* */
  *                             Any value >= 1 is accepted; a call whose single k-vector does not fit is PSA_EINVAL.
  *                             The (T,K,M) float32 result on the device is not part of the budget. */
 #define PSA_OPT_MODES_WORK_BYTES 12
+/*   PSA_OPT_DYNAMIC_WORK_BYTES [4 GiB] bytes of device memory the frame-dependent projections q of psa_dynamic_spectra
+ *                             and its segment buffer may take together: the call loops over blocks of k-vectors of
+ *                             8 NC T bytes each (NC = 1, with currents 4, series of T complex64).  Any value >= 1 is
+ *                             accepted; a call whose single k-vector (and one segment of it) does not fit is PSA_EINVAL.
+ *                             The (1 or 3, L, K) float32 result on the device is not part of the budget. */
+#define PSA_OPT_DYNAMIC_WORK_BYTES 13
 int         psa_set_option(psa_ctx* ctx, int option, int64_t value);
 /* device name / CU count / HBM bytes of the context's GPU */
 int         psa_device_info(psa_ctx* ctx, char* name, int name_len,
@@ -433,6 +439,51 @@ int psa_sed_modes_welch_fit(psa_ctx* ctx, int slot, const float* mean_pos_all, c
                             int32_t flags, double df, const int32_t* bands, int32_t lo, int32_t hi, const psa_peak_opts* opts,
                             float* fit /* (K*M,6) */, int32_t* info /* (K*M,4) */, float* out_host, size_t out_bytes);
 
+/* Dynamic structure factor and current correlations: spectra whose phase comes from the atoms' positions in every frame,
+ * not from their time average -- what an inelastic neutron or X-ray measurement sees (multi-phonon lines, the
+ * Debye-Waller decay with |k|, the quasi-elastic line), and the only meaningful spectra of a run whose atoms do not stay
+ * at a site (a liquid, a glass, a superionic conductor).  r[t,a,:] is the positions slot as stored (no mean is
+ * subtracted; PSA_F_DISPLACEMENTS does not apply), v[t,a,:] the velocities slot, w_a the context's atom weights
+ * (psa_set_atom_weights; none set: 1), idx one atom set (NULL: all atoms), k_vectors (K, 3) float32.  The phase is
+ * exp(+i k.r) of the float32 inputs taken as exact real numbers (the float64 definition, not a float32 FMA chain):
+ *     q_0[k,t]          = sum_{a in idx} w_a exp(i k.r[t,a])                   density rho(k,t)
+ *     q_c[k,t]          = sum_{a in idx} w_a v[t,a,c] exp(i k.r[t,a])          c = 1,2,3: current j(k,t), only with `currents`
+ *     F_s[k,c,o]        = (1/L) sum_tau win[tau] q_c[k, s H + tau] exp(-2 pi i o tau / L)
+ *     density[o,k]      = 1/(n_seg U) sum_s |F_s[k,0,o]|^2
+ *     longitudinal[o,k] = 1/(n_seg U) sum_s |sum_c khat_c F_s[k,c,o]|^2        khat = k/|k| in float64 from the float32 k
+ *     transverse[o,k]   = ( 1/(n_seg U) sum_s sum_c |F_s[k,c,o]|^2 - longitudinal[o,k] ) / 2
+ * with the context's segments (psa_set_segments: L, H, win; none set: L = H = T, win = 1); n_seg, U, no detrending,
+ * two-sided, FFT order and the unused frames after the last segment exactly as there.  out_host is (1, L, K) float32
+ * (density) or, with currents = 1, (3, L, K): density, longitudinal, transverse.  out_bytes exactly its size.
+ *   - The physical S(k,omega) is density L dt / sum_a w_a^2; the factor is the caller's (psa_amd.DynamicSpectra applies it).
+ *   - A k = 0 row has khat = 0: longitudinal 0, transverse (1/2) sum_c |j_c|^2.
+ *   - The static part of rho at a reciprocal-lattice vector (the Bragg peak, N^2 for unit weights) sits in bin 0, and in
+ *     its neighbours under a tapered window.
+ *   - Pairs (k, -k) are not folded.  An empty atom set (idx non-NULL, n_g = 0) gives zeros.
+ * PSA_EINVAL: a null pointer, K < 1, out_bytes not exact, the positions slot not resident, currents with the velocities
+ * slot absent or of another shape, an index out of range, weights set for another N, L > T, a work budget
+ * (PSA_OPT_DYNAMIC_WORK_BYTES) that cannot hold one k-vector (8 NC (T + L) bytes; 8 NC T with no segments), a non-finite
+ * k, a sharded context (psa_comm_init).
+ * Per block of k-vectors: one VALU kernel (dynamic.hip) over all frames -- lanes own k-vectors, a frame's atoms are staged
+ * in LDS and read as broadcasts, short k-lists split the lanes over atom slices; the phase is formed in turns from
+ * kappa = k / 2 pi (float64 on the host, float32 hi + lo on the device) with error-free products whose integer parts are
+ * removed exactly before v_sin_f32 / v_cos_f32 --, the window pass, one batched length-L rocFFT, and a power pass that
+ * contracts with khat before the modulus.  Per element of q, against the float64 evaluation q64 of the definition,
+ *     |q_c[k,t] - q64_c[k,t]| <= (eps_term + (DYN_CHAIN + folds(N_g) + 4) 2^-24) sum_a |w_a| |d_a,c(t)|    d = 1 (c = 0), v_c
+ * with DYN_CHAIN = 128 atoms per float32 accumulator, folds(N_g) = ceil(ceil(N_g / 2) / DYN_CHAIN) foldings into a second
+ * float32 sum, and eps_term = 2 pi 1.51 2^-24 + sqrt(2) DYN_SINCOS_ERR <= 2^-18 the error of one unit-modulus term
+ * (DYN_SINCOS_ERR = 2.6e-7: twice the measured error of the hardware sine and cosine, 1.253e-7; eps_term = 9.3e-7; derivation
+ * in dynamic.hip, figures in DESIGN section 7), for P = sum_c |k_c r_c| / 2 pi <= 2^12 turns (2.5e4 rad).  Beyond that
+ * nothing is refused and nothing breaks: the argument's error is 1.5 u + 12 u^2 P turns (u = 2^-24) for any P, so eps_term
+ * becomes 2 pi (1.5 u + 12 u^2 P) + sqrt(2) DYN_SINCOS_ERR -- 1 % larger at 1e5 rad, doubled at 1.3e7 rad, where the
+ * float32 positions themselves carry a phase uncertainty of order 1 rad.  No atomics: two identical calls give the same bits, and the result
+ * does not depend on how the budget cuts the k-list into blocks.  The slab, the k map, the plane cache and every result
+ * of the SED entry points are left as they are.  Stage times go to psa_last_timings: [2] the kernel, [3] FFT, [4] window
+ * and power, [7] device->host. */
+int psa_dynamic_spectra(psa_ctx* ctx, const float* k_vectors, int64_t K, const int32_t* idx, int64_t n_g,
+                        int32_t currents /* 0: density only, 1: all three */, float* out_host /* (1 or 3, L, K) */,
+                        size_t out_bytes);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is
@@ -528,6 +579,13 @@ int psa_debug_covariance(psa_ctx* ctx, const void* S_host /* (B, K, 3, T) comple
  * of the earlier (the path a budget-bound call takes) */
 int psa_debug_mode_power_welch(psa_ctx* ctx, const void* S_host, const void* eig, int32_t B, int64_t K, int64_t M, int64_t L,
                                int64_t ns, int64_t seg_block, float scale, float* out_host);
+/* the kernel of psa_dynamic_spectra alone, block by block under the same budget rule: out_host (K, NC, T) complex64,
+ * NC = currents ? 4 : 1, the projections q before the window and the FFT (the context's segments only enter the
+ * block size) */
+int psa_debug_dynamic_project(psa_ctx* ctx, const float* k_vectors, int64_t K, const int32_t* idx, int64_t n_g,
+                              int32_t currents, void* out_host);
+/* the sine and cosine of that kernel on n arguments in turns (|x| <= 2): out_host (n, 2) float32 = sin, cos of 2 pi x */
+int psa_debug_dynamic_sincos(psa_ctx* ctx, const float* turns, int64_t n, float* out_host);
 /* number of plane sets in the cache and their bytes */
 int psa_debug_plane_cache(psa_ctx* ctx, int64_t* n_sets, int64_t* bytes);
 

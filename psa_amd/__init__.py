@@ -19,9 +19,10 @@ from .modes import ModeSED, site_groups
 from .covariance import ModeVectors, mode_vectors, spectral_weights
 from .peaks import PeakFit, fit_peaks
 from .vdos import VDOS
+from .dynamic import DynamicSpectra
 from .weights import mass_weights
 
 __version__ = "0.2.0"
 __all__ = ["Trajectory", "SED", "SEDCalculator", "parse_direction", "fast_intensity", "mass_weights", "Segments",
-           "VDOS", "ModeSED", "site_groups", "PeakFit", "fit_peaks", "ModeVectors",
+           "VDOS", "DynamicSpectra", "ModeSED", "site_groups", "PeakFit", "fit_peaks", "ModeVectors",
            "mode_vectors", "spectral_weights", "__version__"]

@@ -29,6 +29,7 @@ OPT_K1_LOWRANK_MIN_K = 9
 OPT_K1_LOWRANK_MIN_LOCAL = 10
 OPT_VDOS_WORK_BYTES = 11
 OPT_MODES_WORK_BYTES = 12
+OPT_DYNAMIC_WORK_BYTES = 13
 KMAP_MIRROR = 0x80000000
 ABI_VERSION = 6
 # the summation structure of the covariance kernel (psa_amd/csrc/covariance.hip), mirrored for the bound of tests/cov64.py
@@ -37,6 +38,13 @@ COV_FOLDS = 32      # folds into the second float32 sum per partial slab
 COV_TILE = 64       # frequencies per staged tile
 COV_CHUNK = COV_CHAIN * COV_FOLDS   # frequencies per workgroup and partial slab
 COV_MAX_ROWS = 96   # 3 B served
+# the summation structure of the dynamic-spectra kernel (psa_amd/csrc/dynamic.hip), mirrored for the bound of
+# tests/dynamic_cases.py
+DYN_THREADS = 256   # lanes of a workgroup: k-vectors x atom slices
+DYN_ATOMS = 512     # atoms of a frame staged per tile
+DYN_CHAIN = 128     # atoms one float32 accumulator sums before it is folded
+DYN_FRAMES = 4      # frames per workgroup
+DYN_SINCOS_ERR = 2.6e-7      # twice the largest error of v_sin_f32 / v_cos_f32 measured on [-2, 2] turns: 1.253e-7
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -89,6 +97,9 @@ SIGNATURES = {
     "psa_sed_modes_welch_fit": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p, _i64p, C.c_int32, C.c_void_p,
                                           C.c_int64, C.c_int32, C.c_double, _i32p, C.c_int32, C.c_int32, C.c_void_p, _f32p,
                                           _i32p, _f32p, C.c_size_t]),
+    "psa_dynamic_spectra": (C.c_int, [_ctx, _f32p, C.c_int64, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t]),
+    "psa_debug_dynamic_project": (C.c_int, [_ctx, _f32p, C.c_int64, _i32p, C.c_int64, C.c_int32, C.c_void_p]),
+    "psa_debug_dynamic_sincos": (C.c_int, [_ctx, _f32p, C.c_int64, _f32p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
@@ -633,6 +644,47 @@ class Engine:
             idx.ctypes.data_as(_i32p) if idx is not None else None,
             off.ctypes.data_as(_i64p) if off is not None else None, G, flags, _f32(out), out.nbytes), "psa_vdos")
         return np.ascontiguousarray(out.transpose(2, 0, 1))
+
+    @staticmethod
+    def _dynamic_args(k_vectors, idx):
+        """(k-vectors (K, 3) float32, index array or None, its pointer, n_g); an empty set keeps a valid pointer"""
+        kv = _as_f32(np.asarray(k_vectors, np.float32).reshape(-1, 3), (3,))
+        if idx is None:
+            return kv, None, None, 0
+        ii = np.ascontiguousarray(idx, np.int32).ravel()
+        keep = ii if ii.size else np.zeros(1, np.int32)
+        return kv, keep, keep.ctypes.data_as(_i32p), int(ii.size)
+
+    def dynamic_spectra(self, k_vectors, idx=None, currents: bool = True) -> np.ndarray:
+        """Dynamic spectra of the resident positions (and velocities) slots (psa_dynamic_spectra): (3, L, K) float32 --
+        density, longitudinal, transverse -- or (1, L, K) with `currents=False`; the phase of every term is
+        exp(i k.r_a(t)) with the position of that frame.  `idx`: one atom set (None: all atoms).  The context's atom
+        weights and segments apply (none set: L = T).  The result of the SED entry points resident on the device is
+        not touched."""
+        T, _ = self.shape(SLOT_POSITIONS)
+        L = self.segment_length or T
+        kv, keep, ip, n_g = self._dynamic_args(k_vectors, idx)
+        out = np.empty((3 if currents else 1, L, kv.shape[0]), np.float32)
+        _check(self._lib.psa_dynamic_spectra(self._h, _f32(kv), kv.shape[0], ip, n_g, 1 if currents else 0, _f32(out), out.nbytes),
+               "psa_dynamic_spectra")
+        return out
+
+    def debug_dynamic_project(self, k_vectors, idx=None, currents: bool = True) -> np.ndarray:
+        """The kernel of `dynamic_spectra` alone: q (K, NC, T) complex64 before the window and the FFT, NC = 4 with
+        currents (density, j_x, j_y, j_z), else 1."""
+        T, _ = self.shape(SLOT_POSITIONS)
+        kv, keep, ip, n_g = self._dynamic_args(k_vectors, idx)
+        out = np.empty((kv.shape[0], 4 if currents else 1, T), np.complex64)
+        _check(self._lib.psa_debug_dynamic_project(self._h, _f32(kv), kv.shape[0], ip, n_g, 1 if currents else 0,
+                                                   out.ctypes.data_as(C.c_void_p)), "psa_debug_dynamic_project")
+        return out
+
+    def debug_dynamic_sincos(self, turns) -> np.ndarray:
+        """(n, 2) float32: sine and cosine of 2 pi x as that kernel computes them, x in turns, |x| <= 2"""
+        x = np.ascontiguousarray(turns, np.float32).ravel()
+        out = np.empty((x.size, 2), np.float32)
+        _check(self._lib.psa_debug_dynamic_sincos(self._h, _f32(x), x.size, _f32(out)), "psa_debug_dynamic_sincos")
+        return out
 
     def _modes_args(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags):
         """What the four mode entries are called with first (handle ... flags), K and M, and the arrays behind the

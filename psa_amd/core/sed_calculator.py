@@ -33,6 +33,7 @@ import numpy as np
 from .. import _hip
 from ..io.writer import out_to_qdump
 from ..covariance import ModeVectors, mode_vectors, spectral_weights
+from ..dynamic import DynamicSpectra
 from ..modes import ModeSED
 from ..peaks import PeakFit
 from ..segments import Segments
@@ -450,6 +451,57 @@ class SEDCalculator:
             eng.ensure_resident(slot, data)      # later SED calls find it resident
             dos = eng.vdos(slot, mean_pos_all, self._device_groups(groups), flags)
         return VDOS(dos, np.fft.rfftfreq(L, d=self.dt_ps), [np.asarray(g) for g in groups])
+
+    # ------------------------------------------------------------------ dynamic structure factor, currents
+    def calculate_dynamic_spectra(self, k_points_mags: np.ndarray, k_vectors_3d: np.ndarray,
+                                  basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                  basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                  atom_weights: Optional[np.ndarray] = None, segments: Optional[Segments] = None,
+                                  currents: bool = True) -> DynamicSpectra:
+        """Dynamic structure factor and longitudinal / transverse current correlations (not in the reference;
+        definition in psa_amd/dynamic.py): the spectra of rho(k,t) = sum_a w_a exp(i k.r_a(t)) and
+        j(k,t) = sum_a w_a v_a(t) exp(i k.r_a(t)), the phase from the positions of every frame, computed on the GPU
+        from the positions and velocities resident in HBM.
+
+        The atom set is resolved like that of a coherent `calculate` (several groups act as their union).  The
+        positions are used as stored whatever `use_displacements` says.  `atom_weights` as for `calculate`
+        (scattering lengths; `psa_amd.mass_weights`).  `segments`: a `psa_amd.Segments` for the Welch average; None is
+        one boxcar segment of all frames; TypeError for anything else, ValueError if L > T.  `currents=False` computes
+        the density alone (a quarter of the work) and needs no velocities.  A sharded calculator refuses
+        (NotImplementedError).  Returns a `psa_amd.DynamicSpectra` with (L, K) float32 fields."""
+        weights = None if atom_weights is None else check_atom_weights(atom_weights, self.traj.n_atoms)
+        if segments is not None and not isinstance(segments, Segments):
+            raise TypeError(f"segments must be a psa_amd.Segments, got {type(segments).__name__}")
+        if self._shard is not None and self._shard.nranks > 1:
+            raise NotImplementedError("the dynamic spectra are not available on a sharded calculator")
+        k_vectors = np.asarray(k_vectors_3d, np.float32)
+        if k_vectors.ndim != 2 or k_vectors.shape[1] != 3:
+            raise ValueError(f"k_vectors_3d must be (K, 3), got {k_vectors.shape}")
+        if not np.all(np.isfinite(k_vectors)):
+            raise ValueError("k_vectors_3d must be finite")
+        n_t, n_atoms, n_k = self.traj.n_frames, self.traj.n_atoms, k_vectors.shape[0]
+        if segments is not None and n_t:
+            segments.count(n_t)                          # ValueError if L > T
+        L = n_t if segments is None else segments.length
+        freqs = np.fft.fftfreq(L, d=self.dt_ps) if L else np.zeros(0, np.float64)
+        if n_t == 0 or n_atoms == 0 or n_k == 0:
+            logger.warning("Cannot calculate dynamic spectra: 0 frames, 0 atoms or 0 k-vectors.")
+            zero = np.zeros((L, n_k), np.float32)
+            return DynamicSpectra(zero, zero.copy() if currents else None, zero.copy() if currents else None, freqs,
+                                  k_points_mags, k_vectors_3d, np.zeros(0, int), 0.0, self.dt_ps)
+        groups = self._resolve_groups(basis_atom_indices, basis_atom_types, "coherent")
+        atoms = np.unique(np.concatenate(groups)).astype(int) if len(groups) > 1 else groups[0]
+        w2 = np.ones(n_atoms, np.float64) if weights is None else weights.astype(np.float64) ** 2
+        eng = self.engine
+        with self._engine_state(weights, segments):  # (segments before the upload: its FFT primer then builds length L)
+            eng.ensure_resident(_hip.SLOT_POSITIONS, self.traj.positions)
+            if currents:
+                eng.ensure_resident(_hip.SLOT_VELOCITIES, self.traj.velocities)
+            listed = self._device_groups([atoms])    # None: all atoms in order
+            out = eng.dynamic_spectra(k_vectors, None if listed is None else listed[0], currents)
+        lon, tra = (out[1], out[2]) if currents else (None, None)
+        return DynamicSpectra(out[0], lon, tra, freqs, k_points_mags, k_vectors_3d, np.asarray(atoms),
+                              float(np.sum(w2[atoms])), self.dt_ps)
 
     # ------------------------------------------------------------------ mode projection
     def calculate_mode_sed(self, k_points_mags: np.ndarray, k_vectors_3d: np.ndarray, eigenvectors: np.ndarray,

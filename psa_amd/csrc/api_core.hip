@@ -277,7 +277,8 @@ int psa_destroy(psa_ctx* c) {
                           &c->d_qrows, &c->d_stage, &c->d_bin, &c->d_upload_max, &c->d_zeros, &c->d_kmap, &c->d_cols, &c->d_inten,
                           &c->d_vdos_work, &c->d_vdos_pairs, &c->d_vdos_off, &c->d_vdos_mean, &c->d_vdos_part, &c->d_vdos_acc,
                           &c->d_vdos_out, &c->d_modes_work, &c->d_modes_coef, &c->d_modes_out, &c->d_cov_slab, &c->d_cov_g, &c->d_cov_out, &c->d_peaks_spec, &c->d_peaks_bands,
-                          &c->d_peaks_part, &c->d_peaks_fit, &c->d_peaks_info})
+                          &c->d_peaks_part, &c->d_peaks_fit, &c->d_peaks_info, &c->d_dyn_q, &c->d_dyn_kappa, &c->d_dyn_khat, &c->d_dyn_idx,
+                          &c->d_dyn_out})
             b->release();
         (void)hipStreamDestroy(c->stream);
     }
@@ -349,6 +350,10 @@ int psa_set_option(psa_ctx* c, int option, int64_t value) {
         case PSA_OPT_MODES_WORK_BYTES:
             PSA_REQUIRE(value >= 1, "PSA_OPT_MODES_WORK_BYTES must be >= 1");
             c->opt_modes_work_bytes = value;
+            return PSA_OK;
+        case PSA_OPT_DYNAMIC_WORK_BYTES:
+            PSA_REQUIRE(value >= 1, "PSA_OPT_DYNAMIC_WORK_BYTES must be >= 1");
+            c->opt_dynamic_work_bytes = value;
             return PSA_OK;
     }
     set_error("unknown option %d", option);

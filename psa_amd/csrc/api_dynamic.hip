@@ -1,0 +1,239 @@
+// psa_dynamic_spectra: the dynamic structure factor and the longitudinal and transverse current correlations (definition:
+// include/psa_hip.h; kernels: dynamic.hip).  The phase of every term comes from the atom's position in that very frame, so
+// this path shares nothing with the projection machinery of psa_sed_project -- no phase table, no planes, no matrix
+// cores -- and everything after the projection with the Welch paths.  Per block of kb k-vectors: the kernel writes
+// q (kb, NC, T), NC = 1 (density) or 4 (density and the three current components), over all frames of the slots; without
+// segments q is transformed in place by one batched rocFFT and read by the power pass as (kb, NC, 1, T); with segments
+// it is cut, in sub-blocks of bk k-vectors x bs segments, into the segment buffer (bk, NC, bs, L) by the window pass,
+// transformed by one batched length-L rocFFT and reduced; the power pass contracts the currents with k / |k| before the
+// modulus, keeps the sum over a sub-block's segments on chip, overwrites the sub-block's columns of the (1 or 3, L, K)
+// result with the first segments and adds to them with later ones.  Nothing of the SED entry points' state is touched.
+// Budget (PSA_OPT_DYNAMIC_WORK_BYTES = W; q and the segment buffer share it, the result is outside), as for
+// psa_sed_modes_welch: the segment buffer is promised min(what all K vectors' segments need, max(one (k, segment) unit,
+// W / 8)), never more than W less one k-vector of q; q takes kb = the rest / (8 NC T) k-vectors, and the segment buffer
+// then gets whatever q left over, cut into as many k-vectors as fit x the segments that then fit.
+#include "api_internal.h"
+
+namespace psa {
+
+namespace {
+
+struct DynCall {
+    int64_t T = 0, N = 0, K = 0, n_g = 0;
+    int     NC = 1, slices = 1;
+    bool    cut = false;                 // false: one boxcar segment of T frames, q transformed in place
+    int64_t L = 0, H = 0, n_seg = 0;
+    int64_t per_k = 0, unit = 0;         // bytes of one k-vector of q; of one (k-vector, segment) of the segment buffer
+    int64_t kb = 0, bk = 0, bs = 0;      // k-vectors per block of q; k-vectors x segments per sub-block
+    std::vector<float> kappa, khat;      // (K, 6) k / 2 pi as hi xyz, lo xyz; (K, 3) k / |k|
+};
+
+// every refusal, the sizes and the block rule
+int dynamic_check(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents, DynCall* d) {
+    PSA_REQUIRE(k_vectors != nullptr, "null k_vectors");
+    PSA_REQUIRE(K >= 1 && K < (1ll << 29), "need at least one k-vector (K = %lld)", (long long)K);
+    PSA_REQUIRE(currents == 0 || currents == 1, "currents is 0 (density only) or 1 (density and currents), got %d", (int)currents);
+    PSA_REQUIRE(c->comm == nullptr && c->nranks == 1, "psa_dynamic_spectra is not available on a sharded context (%d ranks)",
+                c->nranks);
+    const DataSlot& pos = c->slot[PSA_SLOT_POSITIONS];
+    const DataSlot& vel = c->slot[PSA_SLOT_VELOCITIES];
+    PSA_REQUIRE(pos.valid, "the positions slot holds no array: the phase of psa_dynamic_spectra is exp(i k.r(t))");
+    const int64_t T = pos.T, N = pos.N;
+    PSA_REQUIRE(!currents || vel.valid, "currents need the velocities slot, which holds no array");
+    PSA_REQUIRE(!currents || (vel.T == T && vel.N == N), "currents need velocities of the positions' shape: (%lld, %lld, 3) against "
+                "(%lld, %lld, 3)", (long long)vel.T, (long long)vel.N, (long long)T, (long long)N);
+    PSA_REQUIRE(idx == nullptr || (n_g >= 0 && n_g < (1ll << 31) - DYN_ATOMS), "bad number of atoms %lld", (long long)n_g);
+    for (int64_t i = 0; idx && i < n_g; ++i) PSA_REQUIRE(idx[i] >= 0 && idx[i] < N, "Atom indices in basis out of bounds.");
+    PSA_TRY(check_weights(c, N));
+    for (int64_t i = 0; i < 3 * K; ++i)
+        PSA_REQUIRE(std::isfinite(k_vectors[i]), "k_vectors[%lld, %lld] is not finite", (long long)(i / 3), (long long)(i % 3));
+    d->T = T, d->N = N, d->K = K, d->n_g = idx ? n_g : N;
+    d->NC = currents ? 4 : 1;
+    d->slices = dynamic_slices(K);
+    d->cut = c->seg_L != 0;
+    d->L = d->cut ? c->seg_L : T, d->H = d->cut ? c->seg_hop : T;
+    PSA_REQUIRE(d->L <= T, "segment length %lld exceeds the trajectory's %lld frames", (long long)d->L, (long long)T);
+    d->n_seg = 1 + (T - d->L) / d->H;
+
+    // the budget: q (kb k-vectors) first, the segment buffer (units of one k-vector x one segment) from the rest
+    const int64_t W = c->opt_dynamic_work_bytes;
+    d->per_k = (int64_t)d->NC * T * (int64_t)sizeof(float2);
+    d->unit = d->cut ? (int64_t)d->NC * d->L * (int64_t)sizeof(float2) : 0;
+    PSA_REQUIRE(W >= d->per_k + d->unit, "the work budget of %lld bytes (PSA_OPT_DYNAMIC_WORK_BYTES) cannot hold one k-vector: "
+                "%d series x (%lld frames + a segment of %lld) need %lld bytes", (long long)W, d->NC, (long long)T,
+                (long long)(d->cut ? d->L : 0), (long long)(d->per_k + d->unit));
+    int64_t seg_bytes = 0;
+    if (d->cut) {
+        const int64_t all = (double)K * (double)d->n_seg * (double)d->unit < 9e18 ? K * d->n_seg * d->unit : INT64_MAX;
+        seg_bytes = std::min(std::min(all, std::max(d->unit, W / 8)), W - d->per_k);
+    }
+    // (the projection's grid: at most 65535 tiles of at least one k-vector; the passes' rows in 31 bits)
+    d->kb = std::min<int64_t>({(W - seg_bytes) / d->per_k, K, 65535});
+    d->bk = d->kb, d->bs = 1;
+    if (d->cut) {
+        const int64_t units = std::min((W - d->kb * d->per_k) / d->unit, d->kb * d->n_seg);
+        if (units >= d->kb) d->bs = std::min(d->n_seg, units / d->kb);
+        else d->bk = units;
+        d->bs = std::min(d->bs, std::max<int64_t>(1, ((1ll << 31) - 1) / (d->bk * d->NC)));
+    }
+
+    // kappa = k / 2 pi in float64 from the float32 k, as float32 hi + lo; k / |k| in float64 (k = 0: 0)
+    const double two_pi = 6.283185307179586476925286766559;
+    d->kappa.resize((size_t)K * 6);
+    d->khat.assign((size_t)K * 3, 0.f);
+    for (int64_t k = 0; k < K; ++k) {
+        const double x = k_vectors[3 * k], y = k_vectors[3 * k + 1], z = k_vectors[3 * k + 2], norm = std::sqrt(x * x + y * y + z * z);
+        for (int cc = 0; cc < 3; ++cc) {
+            const double kap = (double)k_vectors[3 * k + cc] / two_pi;
+            const float  hi = (float)kap;
+            d->kappa[(size_t)k * 6 + cc] = hi;
+            d->kappa[(size_t)k * 6 + 3 + cc] = (float)(kap - (double)hi);
+            if (norm > 0.0) d->khat[(size_t)k * 3 + cc] = (float)((double)k_vectors[3 * k + cc] / norm);
+        }
+    }
+    return PSA_OK;
+}
+
+int dynamic_upload(psa_ctx* c, const DynCall& d, const int32_t* idx) {
+    StageTimer st(c, PSA_T_H2D);
+    PSA_TRY(upload(c, c->d_dyn_kappa, d.kappa.data(), d.kappa.size() * sizeof(float)));
+    PSA_TRY(upload(c, c->d_dyn_khat, d.khat.data(), d.khat.size() * sizeof(float)));
+    if (idx) PSA_TRY(upload(c, c->d_dyn_idx, idx, (size_t)d.n_g * sizeof(int32_t)));
+    return PSA_OK;
+}
+
+// k-vectors [k0, k0 + nk) over all frames into d_q (nk, NC, T)
+int dynamic_project(psa_ctx* c, const DynCall& d, const int32_t* idx, int64_t k0, int64_t nk, float2* d_q) {
+    StageTimer st(c, PSA_T_PROJECT);
+    return launch_dynamic_project(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(),
+                                  d.NC == 4 ? c->slot[PSA_SLOT_VELOCITIES].buf.as<float>() : nullptr,
+                                  c->weights_N ? c->d_weights.as<float>() : nullptr, idx ? c->d_dyn_idx.as<int>() : nullptr,
+                                  c->d_dyn_kappa.as<float>() + (size_t)k0 * 6, d_q, d.T, d.N, d.n_g, nk, d.NC == 4, d.slices);
+}
+
+int dynamic_run(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents, float* out_host,
+                size_t out_bytes) {
+    PSA_REQUIRE(out_host != nullptr, "null output");
+    DynCall d;
+    PSA_TRY(dynamic_check(c, k_vectors, K, idx, n_g, currents, &d));
+    const int64_t L = d.L, T = d.T, rows = currents ? 3 : 1;
+    const size_t  want = (size_t)rows * (size_t)L * (size_t)K * sizeof(float);
+    PSA_REQUIRE(out_bytes == want, "out_bytes is %zu, the (%lld,%lld,%lld) float32 result has %zu", out_bytes, (long long)rows,
+                (long long)L, (long long)K, want);
+    if (d.n_g == 0) {                                        // an empty atom set: zeros
+        std::memset(out_host, 0, out_bytes);
+        return PSA_OK;
+    }
+    PSA_TRY(dynamic_upload(c, d, idx));
+    PSA_TRY(c->d_dyn_q.reserve((size_t)d.kb * (size_t)d.per_k));
+    if (d.cut) PSA_TRY(c->d_seg.reserve((size_t)d.bk * (size_t)d.bs * (size_t)d.unit));
+    PSA_TRY(c->d_dyn_out.reserve(want));
+
+    const double U = d.cut ? c->seg_U : 1.0;
+    const float  scale = (float)(1.0 / ((double)L * (double)L * (double)d.n_seg * U));
+    float2*      d_q = c->d_dyn_q.as<float2>();
+    float2*      d_seg = d.cut ? c->d_seg.as<float2>() : nullptr;
+    float*       d_out = c->d_dyn_out.as<float>();
+    const float* d_khat = c->d_dyn_khat.as<float>();
+    for (int64_t k0 = 0; k0 < K; k0 += d.kb) {
+        const int64_t nk = std::min(d.kb, K - k0);
+        PSA_TRY(dynamic_project(c, d, idx, k0, nk, d_q));
+        if (!d.cut) {
+            {
+                StageTimer st(c, PSA_T_FFT);
+                PSA_TRY(run_fft(c, d_q, T, (int64_t)d.NC * nk));
+            }
+            StageTimer st(c, PSA_T_EPILOGUE);
+            PSA_TRY(launch_dynamic_power(c, d_q, d_khat + (size_t)k0 * 3, d_out, T, 1, nk, currents != 0, K, k0, scale, true));
+        }
+        for (int64_t k1 = 0; d.cut && k1 < nk; k1 += d.bk) {
+            const int64_t nb = std::min(d.bk, nk - k1);
+            for (int64_t s0 = 0; s0 < d.n_seg; s0 += d.bs) {
+                const int64_t ns = std::min(d.bs, d.n_seg - s0);
+                {
+                    StageTimer st(c, PSA_T_EPILOGUE);
+                    PSA_TRY(launch_segment_window_rows(c, d_q + (size_t)k1 * (size_t)d.NC * (size_t)T, c->d_seg_window.as<float>(), d_seg,
+                                                       T, L, d.H, s0, ns, nb * d.NC));
+                }
+                {
+                    StageTimer st(c, PSA_T_FFT);
+                    PSA_TRY(run_fft(c, d_seg, L, (int64_t)d.NC * nb * ns));
+                }
+                StageTimer st(c, PSA_T_EPILOGUE);
+                PSA_TRY(launch_dynamic_power(c, d_seg, d_khat + (size_t)(k0 + k1) * 3, d_out, L, ns, nb, currents != 0, K, k0 + k1,
+                                             scale, s0 == 0));
+            }
+        }
+    }
+    StageTimer st(c, PSA_T_D2H);
+    PSA_HIP_CHECK(hipMemcpyAsync(out_host, d_out, want, hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return PSA_OK;
+}
+
+// the kernel alone, block by block under the same rule: q (K, NC, T) before any FFT
+int dynamic_debug_project(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents,
+                          void* out_host) {
+    PSA_REQUIRE(out_host != nullptr, "null output");
+    DynCall d;
+    PSA_TRY(dynamic_check(c, k_vectors, K, idx, n_g, currents, &d));
+    if (d.n_g == 0) {
+        std::memset(out_host, 0, (size_t)K * (size_t)d.per_k);
+        return PSA_OK;
+    }
+    PSA_TRY(dynamic_upload(c, d, idx));
+    PSA_TRY(c->d_dyn_q.reserve((size_t)d.kb * (size_t)d.per_k));
+    for (int64_t k0 = 0; k0 < K; k0 += d.kb) {
+        const int64_t nk = std::min(d.kb, K - k0);
+        PSA_TRY(dynamic_project(c, d, idx, k0, nk, c->d_dyn_q.as<float2>()));
+        PSA_HIP_CHECK(hipMemcpyAsync((char*)out_host + (size_t)k0 * (size_t)d.per_k, c->d_dyn_q.ptr, (size_t)nk * (size_t)d.per_k,
+                                     hipMemcpyDeviceToHost, c->stream));
+    }
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return PSA_OK;
+}
+
+}  // namespace
+
+}  // namespace psa
+
+using namespace psa;
+
+extern "C" {
+
+int psa_dynamic_spectra(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents,
+                        float* out_host, size_t out_bytes) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    return synchronised(c, dynamic_run(c, k_vectors, K, idx, n_g, currents, out_host, out_bytes), "psa_dynamic_spectra");
+}
+
+int psa_debug_dynamic_project(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents,
+                              void* out_host) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    return synchronised(c, dynamic_debug_project(c, k_vectors, K, idx, n_g, currents, out_host), "psa_debug_dynamic_project");
+}
+
+int psa_debug_dynamic_sincos(psa_ctx* c, const float* turns, int64_t n, float* out_host) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    PSA_REQUIRE(turns != nullptr && out_host != nullptr && n >= 1 && n < (1ll << 28), "bad argument");
+    // (scratch of this call alone: the projections' buffer, which holds nothing between calls)
+    PSA_TRY(c->d_dyn_q.reserve((size_t)n * (sizeof(float) + sizeof(float2))));
+    float2* d_out = c->d_dyn_q.as<float2>();
+    float*  d_in = reinterpret_cast<float*>(d_out + n);
+    int     rc = PSA_OK;
+    if (hipMemcpyAsync(d_in, turns, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+        set_error("upload of the sweep failed");
+        rc = PSA_EHIP;
+    }
+    if (rc == PSA_OK) rc = launch_dynamic_sincos(c, d_in, d_out, n);
+    if (rc == PSA_OK && hipMemcpyAsync(out_host, d_out, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+        set_error("copy of the sweep failed");
+        rc = PSA_EHIP;
+    }
+    return synchronised(c, rc, "psa_debug_dynamic_sincos");
+}
+
+}  // extern "C"

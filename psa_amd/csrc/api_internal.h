@@ -13,6 +13,7 @@
 //                    the Welch segment average between projection and contraction
 //   api_covariance.hip  the spectral covariance of the B site groups' spectra: the frequency-weighted sum of their outer products
 //   api_peaks.hip    Lorentzian peak fits of spectrum columns: an uploaded spectrum, or the mode spectra where they lie
+//   api_dynamic.hip  the dynamic structure factor and the current correlations: the phase of every frame's own positions
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
 // k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
 #pragma once

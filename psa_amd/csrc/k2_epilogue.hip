@@ -151,7 +151,12 @@ segment_window_kernel(const float2* __restrict__ q, const float* __restrict__ w,
 
 int launch_segment_window(psa_ctx* c, const float2* d_q, const float* d_w, float2* d_seg, int64_t T, int64_t L, int64_t H,
                           int64_t s0, int64_t ns, int64_t nk) {
-    const int64_t n_rows = nk * 3 * ns;
+    return launch_segment_window_rows(c, d_q, d_w, d_seg, T, L, H, s0, ns, nk * 3);
+}
+
+int launch_segment_window_rows(psa_ctx* c, const float2* d_q, const float* d_w, float2* d_seg, int64_t T, int64_t L, int64_t H,
+                               int64_t s0, int64_t ns, int64_t n_series) {
+    const int64_t n_rows = n_series * ns;
     if (n_rows == 0) return PSA_OK;
     PSA_REQUIRE(n_rows < (1ll << 31) && (s0 + ns - 1) * H + L <= T, "segment block outside q");
     const int64_t gx = std::min<int64_t>((L + 255) / 256, 64), gy = std::min<int64_t>(n_rows, 65535);

@@ -290,6 +290,13 @@ struct psa_ctx {
     // the row slices' partial maxima (value, bin, non-finite flag) and the results.  All kept between calls.
     psa::DevBuf  d_peaks_spec, d_peaks_bands, d_peaks_part, d_peaks_fit, d_peaks_info;
 
+    // dynamic structure factor and current correlations (psa_dynamic_spectra; api_dynamic.hip): the frame-dependent
+    // projections q (kb, NC, T) of one block of k-vectors, held -- together with the segment buffer d_seg -- to
+    // opt_dynamic_work_bytes (PSA_OPT_DYNAMIC_WORK_BYTES); kappa = k / 2 pi as float32 hi and lo parts (K, 6), the unit
+    // vectors k / |k| (K, 3), the atom list, the (1 or 3, L, K) float32 result.  All kept between calls.
+    psa::DevBuf  d_dyn_q, d_dyn_kappa, d_dyn_khat, d_dyn_idx, d_dyn_out;
+    int64_t      opt_dynamic_work_bytes = (int64_t)4 << 30;
+
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
                                           // plane builds, trajectory uploads (psa_oneoff_stats)
@@ -384,6 +391,9 @@ int launch_transpose_f32(psa_ctx* c, const float* d_slab, float* d_out, int64_t 
 // (nk,3,ns,L); after its FFT, inv_norm sum_s sum_c |F/L|^2 into slab rows (nk, L) (first: overwrite)
 int launch_segment_window(psa_ctx* c, const float2* d_q, const float* d_w, float2* d_seg, int64_t T, int64_t L, int64_t H,
                           int64_t s0, int64_t ns, int64_t nk);
+// the same for n_series rows of q (n_series, T), whatever they are: (n_series, ns, L)
+int launch_segment_window_rows(psa_ctx* c, const float2* d_q, const float* d_w, float2* d_seg, int64_t T, int64_t L, int64_t H,
+                               int64_t s0, int64_t ns, int64_t n_series);
 int launch_segment_power(psa_ctx* c, const float2* d_seg, float* d_rows, int64_t L, int64_t ns, int64_t nk, float inv_norm,
                          bool first);
 // --- vdos.hip (psa_vdos: per-atom series -> power summed per atom group; two atoms share one complex series)
@@ -426,6 +436,24 @@ int launch_peak_find(psa_ctx* c, const float* d_spec, int64_t C, const int32_t* 
 int launch_peak_fit(psa_ctx* c, const float* d_spec, int64_t C, const int32_t* d_bands, int lo, int hi, const float* d_pmax,
                     const int* d_pidx, const int* d_pflag, int n_slices, double df, float window_hwhm, int half_window_bins,
                     int max_iter, float* d_fit, int32_t* d_info);
+// --- dynamic.hip (psa_dynamic_spectra: q_c[k,t] = sum_a w_a d_a,c(t) exp(i k.r_a(t)) with the phase of every frame's own
+// positions; the summation structure and the bound are in its header)
+constexpr int DYN_THREADS = 256;   // lanes of a workgroup: DYN_THREADS / slices k-vectors x `slices` atom slices
+constexpr int DYN_ATOMS = 512;     // atoms of one frame staged per tile
+constexpr int DYN_CHAIN = 128;     // atoms one float32 accumulator sums before it is folded into the second float32 sum
+constexpr int DYN_FRAMES = 4;      // frames one workgroup projects, one after the other
+int dynamic_slices(int64_t K);     // atom slices the lanes of a workgroup are split into for a call of K k-vectors
+// nk k-vectors (kappa: their rows of the (K, 6) table) x all T frames -> q (nk, NC, T) complex64, NC = currents ? 4 : 1;
+// d_vel, d_weights, d_idx may be null (no currents, unit weights, all atoms); slices = dynamic_slices(K of the call)
+int launch_dynamic_project(psa_ctx* c, const float* d_pos, const float* d_vel, const float* d_weights, const int* d_idx,
+                           const float* d_kappa, float2* d_q, int64_t T, int64_t N, int64_t n_g, int64_t nk, bool currents,
+                           int slices);
+// after the FFT of the segment buffer (nk, NC, ns, L): out (1 or 3, L, K_pitch) float32, columns k_col0 .. k_col0 + nk - 1:
+// (first ? 0 : out) + scale sum_s { |F_0|^2;  |sum_c khat_c F_c|^2;  (sum_c |F_c|^2 - |sum_c khat_c F_c|^2) / 2 }
+int launch_dynamic_power(psa_ctx* c, const float2* d_seg, const float* d_khat, float* d_out, int64_t L, int64_t ns, int64_t nk,
+                         bool currents, int64_t K_pitch, int64_t k_col0, float scale, bool first);
+// (sin, cos)(2 pi x) of n arguments in turns by the kernel's own routine (the sweep that measures its error)
+int launch_dynamic_sincos(psa_ctx* c, const float* d_turns, float2* d_out, int64_t n);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 
