@@ -484,6 +484,53 @@ int psa_dynamic_spectra(psa_ctx* ctx, const float* k_vectors, int64_t K, const i
                         int32_t currents /* 0: density only, 1: all three */, float* out_host /* (1 or 3, L, K) */,
                         size_t out_bytes);
 
+/* The same spectra on the reciprocal lattice of the simulation box, per vector or averaged over shells of |k| (the
+ * powder average): what a liquid, a glass or a superionic conductor has instead of a direction.  Under periodic
+ * boundaries only the commensurate vectors k = n_1 G_1 + n_2 G_2 + n_3 G_3, n integer, are legitimate, and on them the
+ * phase is defined by the integers, not by a rounded k:
+ *   - H is the box matrix, its rows the box vectors; its float32 entries are taken as exact numbers.
+ *   - box_inverse = Hinv, the float64 inverse of H as the caller formed it (psa_amd: np.linalg.inv), 9 doubles row-major.
+ *     The library and a float64 reference use the same 9 numbers.
+ *   - G = 2 pi Hinv^T; its rows are G_1, G_2, G_3.
+ *   - s[t,a,:] = r[t,a,:] . Hinv, on the float32 positions taken as exact: the fractional coordinates.
+ *     q_0[n,t] = sum_{a in idx} w_a exp(2 pi i n.s[t,a])
+ *     q_c[n,t] = sum_{a in idx} w_a v[t,a,c] exp(2 pi i n.s[t,a])                c = 1, 2, 3
+ *   - F_s, density, longitudinal and transverse per vector are exactly those of psa_dynamic_spectra (segments, U,
+ *     scaling, FFT order), with khat = n.G / |n.G| formed in float64.
+ *   - Powder average: a bin b holds a set V_b of vectors of the FULL sphere, n = 0 never among them, and
+ *         X_b[o] = (1/|V_b|) sum_{n in V_b} X_n[o]                               X = density, longitudinal, transverse.
+ *     One vector of each pair (n, -n) is projected -- the half-space member, whose first non-zero index is positive --
+ *     and X_{-n}[o] = X_n[(L - o) mod L] supplies the other (q(-n) = conj q(n) for real weights).  A bin with no vector
+ *     is a row of zeros.
+ * indices is (K, 3) int32, |n_j| <= 64 (LAT_MAX_INDEX).
+ *   bin_of == NULL  the per-vector form: out_host (1 or 3, L, K) as psa_dynamic_spectra returns it; the vectors are
+ *                   projected as given, n = 0 allowed, nothing folded.
+ *   bin_of != NULL  the shell form: bin_of[k] in [0, n_bins) is vector k's bin, every vector a half-space member that
+ *                   stands for itself and its partner; out_host (1 or 3, L, n_bins).  The sum over a shell is formed on
+ *                   the device in float64, scaled by 1 / (2 n_half_b n_seg U L^2) in float64 and rounded once to float32.
+ * PSA_EINVAL: a null pointer, K < 1, out_bytes not exact, a non-finite or singular box_inverse, |n_j| > 64, a bin index
+ * outside [0, n_bins), a shell-form vector that is 0 or not a half-space member, and every refusal of psa_dynamic_spectra
+ * that concerns the slots, the weights, the segments, the budget (PSA_OPT_DYNAMIC_WORK_BYTES, the same rule) and sharding.
+ * Per block of vectors: one VALU kernel (lattice.hip) in which the phase factorises, exp(2 pi i n.s) = E_1[n_1] E_2[n_2]
+ * E_3[n_3] with E_j[m] = exp(2 pi i m s_j): per staged atom the factors a tile of 512 vectors needs are evaluated once,
+ * each directly from m and s_j carried as two float32 (error-free products, integer parts removed exactly), and a
+ * (vector, atom, frame) unit is two float32 complex products and the accumulation -- no sine or cosine.  Per element
+ *     |q_c[n,t] - q64_c[n,t]| <= (eps_lat + (LAT_CHAIN + folds(N_g) + 4) 2^-24) sum_a |w_a| |d_a,c(t)|     d = 1 (c = 0), v_c
+ * with LAT_CHAIN = 128, folds(N_g) = ceil(N_g / LAT_CHAIN) and eps_lat = 3 (2 pi 2^-24 + sqrt(2) DYN_SINCOS_ERR) + 6 2^-24
+ * = 2.59e-6 <= 2^-18 for every |n_j| <= 64, independent of |r| up to sum_c |Hinv_cj r_c| <= 2^12 turns (derivation in
+ * lattice.hip).  No atomics: two identical calls give the same bits; the projections q do not depend on how the budget
+ * cuts the list into blocks; the per-vector result depends on it as psa_dynamic_spectra's does (a budget that also cuts
+ * the segments into sub-blocks adds the later ones in float32), the shell form in the order of its float64 sums alone
+ * (one float32 ulp at the most).  The plan costs 4 KiB of host and device memory per tile of 512 vectors and every block
+ * starts a new tile, so a budget that leaves a handful of vectors per block pays that, and a 256-lane workgroup, per
+ * handful.  The result, and the shell form's float64 accumulator (8 bytes x (1 or 3) x L x n_bins), lie outside the
+ * budget, as psa_dynamic_spectra's result does.  Nothing of the SED entry points' state or of psa_dynamic_spectra's is touched.  Stage times go to
+ * psa_last_timings as for psa_dynamic_spectra: [2] the kernel, [3] FFT, [4] window, power or shell pass, [7] device->host. */
+int psa_lattice_spectra(psa_ctx* ctx, const double* box_inverse /* 9 */, const int32_t* indices /* (K,3) */, int64_t K,
+                        const int32_t* bin_of /* K or NULL */, int64_t n_bins, const int32_t* idx, int64_t n_g,
+                        int32_t currents /* 0: density only, 1: all three */, float* out_host /* (1 or 3, L, K or n_bins) */,
+                        size_t out_bytes);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is
@@ -586,6 +633,10 @@ int psa_debug_dynamic_project(psa_ctx* ctx, const float* k_vectors, int64_t K, c
                               int32_t currents, void* out_host);
 /* the sine and cosine of that kernel on n arguments in turns (|x| <= 2): out_host (n, 2) float32 = sin, cos of 2 pi x */
 int psa_debug_dynamic_sincos(psa_ctx* ctx, const float* turns, int64_t n, float* out_host);
+/* the projection kernel of psa_lattice_spectra alone (per-vector form), block by block under the same budget rule:
+ * out_host (K, NC, T) complex64 in the caller's order, NC = currents ? 4 : 1 */
+int psa_debug_lattice_project(psa_ctx* ctx, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* idx,
+                              int64_t n_g, int32_t currents, void* out_host);
 /* number of plane sets in the cache and their bytes */
 int psa_debug_plane_cache(psa_ctx* ctx, int64_t* n_sets, int64_t* bytes);
 

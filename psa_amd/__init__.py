@@ -20,9 +20,10 @@ from .covariance import ModeVectors, mode_vectors, spectral_weights
 from .peaks import PeakFit, fit_peaks
 from .vdos import VDOS
 from .dynamic import DynamicSpectra
+from .lattice import PowderSpectra, commensurate_vectors, shell_bins
 from .weights import mass_weights
 
 __version__ = "0.2.0"
 __all__ = ["Trajectory", "SED", "SEDCalculator", "parse_direction", "fast_intensity", "mass_weights", "Segments",
-           "VDOS", "DynamicSpectra", "ModeSED", "site_groups", "PeakFit", "fit_peaks", "ModeVectors",
+           "VDOS", "DynamicSpectra", "PowderSpectra", "commensurate_vectors", "shell_bins", "ModeSED", "site_groups", "PeakFit", "fit_peaks", "ModeVectors",
            "mode_vectors", "spectral_weights", "__version__"]

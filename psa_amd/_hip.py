@@ -45,6 +45,16 @@ DYN_ATOMS = 512     # atoms of a frame staged per tile
 DYN_CHAIN = 128     # atoms one float32 accumulator sums before it is folded
 DYN_FRAMES = 4      # frames per workgroup
 DYN_SINCOS_ERR = 2.6e-7      # twice the largest error of v_sin_f32 / v_cos_f32 measured on [-2, 2] turns: 1.253e-7
+# the summation structure of the lattice-spectra kernel (psa_amd/csrc/lattice.hip), mirrored for the bound of
+# tests/lattice_cases.py
+LAT_THREADS = 256   # lanes of a workgroup
+LAT_KS = 512        # vectors of a tile: two per lane
+LAT_ATOMS = 128     # most atoms of a frame staged per tile
+LAT_TABLE = 3584    # entries of the per-atom factor tables in LDS
+LAT_CHAIN = 128     # atoms one float32 accumulator sums before it is folded
+LAT_FRAMES = 4      # frames per workgroup
+LAT_MAX_INDEX = 64  # largest |n_j| served
+LAT_MAX_ENTRIES = 3 * (2 * LAT_MAX_INDEX + 1)
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -100,6 +110,9 @@ SIGNATURES = {
     "psa_dynamic_spectra": (C.c_int, [_ctx, _f32p, C.c_int64, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t]),
     "psa_debug_dynamic_project": (C.c_int, [_ctx, _f32p, C.c_int64, _i32p, C.c_int64, C.c_int32, C.c_void_p]),
     "psa_debug_dynamic_sincos": (C.c_int, [_ctx, _f32p, C.c_int64, _f32p]),
+    "psa_lattice_spectra": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64, C.c_int32,
+                                      _f32p, C.c_size_t]),
+    "psa_debug_lattice_project": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, C.c_int32, C.c_void_p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
@@ -684,6 +697,49 @@ class Engine:
         x = np.ascontiguousarray(turns, np.float32).ravel()
         out = np.empty((x.size, 2), np.float32)
         _check(self._lib.psa_debug_dynamic_sincos(self._h, _f32(x), x.size, _f32(out)), "psa_debug_dynamic_sincos")
+        return out
+
+    @staticmethod
+    def _lattice_args(box_inverse, indices, idx):
+        """(Hinv (3, 3) float64, indices (K, 3) int32, index array or None, its pointer, n_g)"""
+        inv = np.ascontiguousarray(box_inverse, np.float64)
+        if inv.shape != (3, 3):
+            raise ValueError(f"box_inverse must be (3, 3), got {inv.shape}")
+        n = np.ascontiguousarray(np.asarray(indices, np.int32).reshape(-1, 3))
+        if idx is None:
+            return inv, n, None, None, 0
+        ii = np.ascontiguousarray(idx, np.int32).ravel()
+        keep = ii if ii.size else np.zeros(1, np.int32)
+        return inv, n, keep, keep.ctypes.data_as(_i32p), int(ii.size)
+
+    def lattice_spectra(self, box_inverse, indices, bin_of=None, n_bins=0, idx=None, currents: bool = True) -> np.ndarray:
+        """Dynamic spectra on the box's reciprocal lattice (psa_lattice_spectra): k = n.G with integer `indices` (K, 3),
+        `box_inverse` the float64 inverse of the box matrix (rows = box vectors).  `bin_of` None: per vector, (3, L, K)
+        float32 -- density, longitudinal, transverse -- or (1, L, K) with `currents=False`.  `bin_of` (K,) with `n_bins`:
+        the shell form, (3 or 1, L, n_bins), every vector a half-space member standing for itself and its partner -n.
+        Atom set, weights and segments as for `dynamic_spectra`."""
+        T, _ = self.shape(SLOT_POSITIONS)
+        L = self.segment_length or T
+        inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
+        K = n.shape[0]
+        bins = None if bin_of is None else np.ascontiguousarray(bin_of, np.int32).ravel()
+        if bins is not None and bins.size != K:
+            raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
+        out = np.empty((3 if currents else 1, L, K if bins is None else int(n_bins)), np.float32)
+        _check(self._lib.psa_lattice_spectra(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p), K,
+                                             None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g,
+                                             1 if currents else 0, _f32(out), out.nbytes), "psa_lattice_spectra")
+        return out
+
+    def debug_lattice_project(self, box_inverse, indices, idx=None, currents: bool = True) -> np.ndarray:
+        """The projection kernel of `lattice_spectra` alone: q (K, NC, T) complex64 before the window and the FFT, NC = 4
+        with currents (density, j_x, j_y, j_z), else 1."""
+        T, _ = self.shape(SLOT_POSITIONS)
+        inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
+        out = np.empty((n.shape[0], 4 if currents else 1, T), np.complex64)
+        _check(self._lib.psa_debug_lattice_project(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p),
+                                                   n.shape[0], ip, n_g, 1 if currents else 0, out.ctypes.data_as(C.c_void_p)),
+               "psa_debug_lattice_project")
         return out
 
     def _modes_args(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags):

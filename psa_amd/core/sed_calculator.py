@@ -34,6 +34,8 @@ from .. import _hip
 from ..io.writer import out_to_qdump
 from ..covariance import ModeVectors, mode_vectors, spectral_weights
 from ..dynamic import DynamicSpectra
+from .. import lattice
+from ..lattice import PowderSpectra
 from ..modes import ModeSED
 from ..peaks import PeakFit
 from ..segments import Segments
@@ -469,39 +471,137 @@ class SEDCalculator:
         one boxcar segment of all frames; TypeError for anything else, ValueError if L > T.  `currents=False` computes
         the density alone (a quarter of the work) and needs no velocities.  A sharded calculator refuses
         (NotImplementedError).  Returns a `psa_amd.DynamicSpectra` with (L, K) float32 fields."""
-        weights = None if atom_weights is None else check_atom_weights(atom_weights, self.traj.n_atoms)
-        if segments is not None and not isinstance(segments, Segments):
-            raise TypeError(f"segments must be a psa_amd.Segments, got {type(segments).__name__}")
-        if self._shard is not None and self._shard.nranks > 1:
-            raise NotImplementedError("the dynamic spectra are not available on a sharded calculator")
+        weights = self._dynamic_arguments(atom_weights, segments, "the dynamic spectra")
         k_vectors = np.asarray(k_vectors_3d, np.float32)
         if k_vectors.ndim != 2 or k_vectors.shape[1] != 3:
             raise ValueError(f"k_vectors_3d must be (K, 3), got {k_vectors.shape}")
         if not np.all(np.isfinite(k_vectors)):
             raise ValueError("k_vectors_3d must be finite")
-        n_t, n_atoms, n_k = self.traj.n_frames, self.traj.n_atoms, k_vectors.shape[0]
-        if segments is not None and n_t:
-            segments.count(n_t)                          # ValueError if L > T
-        L = n_t if segments is None else segments.length
-        freqs = np.fft.fftfreq(L, d=self.dt_ps) if L else np.zeros(0, np.float64)
-        if n_t == 0 or n_atoms == 0 or n_k == 0:
-            logger.warning("Cannot calculate dynamic spectra: 0 frames, 0 atoms or 0 k-vectors.")
+        n_k = k_vectors.shape[0]
+        L, freqs = self._dynamic_lengths(segments)
+        if self._dynamic_nothing(n_k, "dynamic spectra"):
             zero = np.zeros((L, n_k), np.float32)
             return DynamicSpectra(zero, zero.copy() if currents else None, zero.copy() if currents else None, freqs,
                                   k_points_mags, k_vectors_3d, np.zeros(0, int), 0.0, self.dt_ps)
+        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, currents,
+                                             lambda eng, listed: eng.dynamic_spectra(k_vectors, listed, currents))
+        lon, tra = (out[1], out[2]) if currents else (None, None)
+        return DynamicSpectra(out[0], lon, tra, freqs, k_points_mags, k_vectors_3d, atoms, norm, self.dt_ps)
+
+    # what calculate_dynamic_spectra, calculate_lattice_spectra and calculate_powder_spectra share: the checks of the
+    # weights, the segments and the sharding; the lengths; the empty inputs; the atom set, the residency and the call
+    def _dynamic_arguments(self, atom_weights, segments, what):
+        weights = None if atom_weights is None else check_atom_weights(atom_weights, self.traj.n_atoms)
+        if segments is not None and not isinstance(segments, Segments):
+            raise TypeError(f"segments must be a psa_amd.Segments, got {type(segments).__name__}")
+        if self._shard is not None and self._shard.nranks > 1:
+            raise NotImplementedError(f"{what} are not available on a sharded calculator")
+        return weights
+
+    def _dynamic_lengths(self, segments):
+        n_t = self.traj.n_frames
+        if segments is not None and n_t:
+            segments.count(n_t)                          # ValueError if L > T
+        L = n_t if segments is None else segments.length
+        return L, (np.fft.fftfreq(L, d=self.dt_ps) if L else np.zeros(0, np.float64))
+
+    def _dynamic_nothing(self, n_k, what):
+        if self.traj.n_frames == 0 or self.traj.n_atoms == 0 or n_k == 0:
+            logger.warning(f"Cannot calculate {what}: 0 frames, 0 atoms or 0 k-vectors.")
+            return True
+        return False
+
+    def _dynamic_run(self, basis_atom_indices, basis_atom_types, weights, segments, currents, call):
+        """(what `call(engine, atom list or None)` returns, the atom-index array, sum_a w_a^2 over it)"""
         groups = self._resolve_groups(basis_atom_indices, basis_atom_types, "coherent")
         atoms = np.unique(np.concatenate(groups)).astype(int) if len(groups) > 1 else groups[0]
-        w2 = np.ones(n_atoms, np.float64) if weights is None else weights.astype(np.float64) ** 2
+        w2 = np.ones(self.traj.n_atoms, np.float64) if weights is None else weights.astype(np.float64) ** 2
         eng = self.engine
         with self._engine_state(weights, segments):  # (segments before the upload: its FFT primer then builds length L)
             eng.ensure_resident(_hip.SLOT_POSITIONS, self.traj.positions)
             if currents:
                 eng.ensure_resident(_hip.SLOT_VELOCITIES, self.traj.velocities)
             listed = self._device_groups([atoms])    # None: all atoms in order
-            out = eng.dynamic_spectra(k_vectors, None if listed is None else listed[0], currents)
+            out = call(eng, None if listed is None else listed[0])
+        return out, np.asarray(atoms), float(np.sum(w2[atoms]))
+
+    # ------------------------------------------------------------------ spectra on the box's reciprocal lattice
+    def _lattice_indices(self, indices):
+        n = np.asarray(indices)
+        if n.ndim != 2 or n.shape[1] != 3:
+            raise ValueError(f"indices must be (K, 3), got {n.shape}")
+        if n.size and not (np.issubdtype(n.dtype, np.integer) or np.all(n == np.rint(n))):
+            raise ValueError("indices must be integers")
+        n = n.astype(np.int64)
+        if n.size and int(np.max(np.abs(n))) > _hip.LAT_MAX_INDEX:
+            raise ValueError(f"indices up to |n_j| = {_hip.LAT_MAX_INDEX} are served, got {int(np.max(np.abs(n)))}")
+        return n.astype(np.int32)
+
+    def calculate_lattice_spectra(self, indices: np.ndarray,
+                                  basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                  basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                  atom_weights: Optional[np.ndarray] = None, segments: Optional[Segments] = None,
+                                  currents: bool = True) -> DynamicSpectra:
+        """The dynamic spectra of `calculate_dynamic_spectra` on the reciprocal lattice of the simulation box (not in
+        the reference; definition in psa_amd/lattice.py): k = n_1 G_1 + n_2 G_2 + n_3 G_3 for the integer `indices`
+        (K, 3), |n_j| <= 64, G the reciprocal vectors of `traj.box_matrix`; the phase is exp(2 pi i n.s) of the
+        fractional coordinates, exact for a commensurate vector where a float32 k is not.  Vectors are projected as
+        given: n = 0 is allowed, pairs (n, -n) are not folded.
+
+        Atom set, `atom_weights`, `segments`, `currents`, residency, the empty inputs and the sharded refusal are those
+        of `calculate_dynamic_spectra`.  Returns a `psa_amd.DynamicSpectra` whose `k_vectors` are n.G in float64 and
+        `k_points` their lengths."""
+        weights = self._dynamic_arguments(atom_weights, segments, "the lattice spectra")
+        n = self._lattice_indices(indices)
+        inv = lattice.box_inverse(self.traj.box_matrix)
+        k = lattice.lattice_k(n, inv)
+        mags = np.linalg.norm(k, axis=1)
+        L, freqs = self._dynamic_lengths(segments)
+        if self._dynamic_nothing(n.shape[0], "lattice spectra"):
+            zero = np.zeros((L, n.shape[0]), np.float32)
+            return DynamicSpectra(zero, zero.copy() if currents else None, zero.copy() if currents else None, freqs,
+                                  mags, k, np.zeros(0, int), 0.0, self.dt_ps)
+        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, currents,
+                                             lambda eng, listed: eng.lattice_spectra(inv, n, None, 0, listed, currents))
         lon, tra = (out[1], out[2]) if currents else (None, None)
-        return DynamicSpectra(out[0], lon, tra, freqs, k_points_mags, k_vectors_3d, np.asarray(atoms),
-                              float(np.sum(w2[atoms])), self.dt_ps)
+        return DynamicSpectra(out[0], lon, tra, freqs, mags, k, atoms, norm, self.dt_ps)
+
+    def calculate_powder_spectra(self, q_edges: np.ndarray,
+                                 basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                 basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                 atom_weights: Optional[np.ndarray] = None, segments: Optional[Segments] = None,
+                                 currents: bool = True, max_per_bin: Optional[int] = None, seed: int = 0) -> PowderSpectra:
+        """Powder-averaged dynamic spectra (not in the reference; definition in psa_amd/lattice.py): S(Q, w), C_L(Q, w)
+        and C_T(Q, w) averaged over all vectors of the box's reciprocal lattice in each shell
+        q_edges[b] <= |k| < q_edges[b + 1] -- the spectra of a liquid, a glass or a superionic conductor.  The half
+        space of every shell is projected on the GPU, -n supplied by the frequency mirror, and the shells are summed
+        there in float64.  `max_per_bin` caps the half-space vectors drawn per shell (a seeded draw without
+        replacement: `seed`); None takes them all.  ValueError where a shell reaches past |n_j| = 64.
+
+        Atom set, `atom_weights`, `segments`, `currents`, residency, the empty inputs and the sharded refusal are those
+        of `calculate_dynamic_spectra`.  Returns a `psa_amd.PowderSpectra` with (L, n_bins) float32 fields."""
+        weights = self._dynamic_arguments(atom_weights, segments, "the powder spectra")
+        edges = np.asarray(q_edges, np.float64).ravel()
+        lattice.shell_bins(np.zeros(0), edges, max_per_bin=max_per_bin)     # ValueError for bad edges or a bad cap
+        n_bins = edges.size - 1
+        inv = lattice.box_inverse(self.traj.box_matrix)
+        reach = lattice.index_reach(self.traj.box_matrix, edges[-1])
+        if np.max(reach) > _hip.LAT_MAX_INDEX:
+            raise ValueError(f"indices up to |n_j| = {_hip.LAT_MAX_INDEX} are served: q_edges reach |n_j| = {int(np.max(reach))}")
+        n_all, _, q_all = lattice.commensurate_vectors(self.traj.box_matrix, edges[-1], edges[0], half_space=True)
+        bins, selected, available, used = lattice.shell_bins(q_all, edges, max_per_bin=max_per_bin, seed=seed)
+        n, b, q = n_all[selected], bins[selected], q_all[selected]
+        q_mean = np.full(n_bins, np.nan)
+        np.divide(np.bincount(b, weights=q, minlength=n_bins), used, out=q_mean, where=used > 0)
+        L, freqs = self._dynamic_lengths(segments)
+
+        def result(out, atoms, norm):
+            lon, tra = (out[1], out[2]) if currents else (None, None)
+            return PowderSpectra(out[0], lon, tra, q_mean, edges, 2 * used, 2 * available, n, b, freqs, atoms, norm, self.dt_ps)
+        if self._dynamic_nothing(n.shape[0], "powder spectra"):
+            return result(np.zeros((3 if currents else 1, L, n_bins), np.float32), np.zeros(0, int), 0.0)
+        return result(*self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, currents,
+                                         lambda eng, listed: eng.lattice_spectra(inv, n, b, n_bins, listed, currents)))
 
     # ------------------------------------------------------------------ mode projection
     def calculate_mode_sed(self, k_points_mags: np.ndarray, k_vectors_3d: np.ndarray, eigenvectors: np.ndarray,

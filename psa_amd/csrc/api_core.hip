@@ -278,7 +278,8 @@ int psa_destroy(psa_ctx* c) {
                           &c->d_vdos_work, &c->d_vdos_pairs, &c->d_vdos_off, &c->d_vdos_mean, &c->d_vdos_part, &c->d_vdos_acc,
                           &c->d_vdos_out, &c->d_modes_work, &c->d_modes_coef, &c->d_modes_out, &c->d_cov_slab, &c->d_cov_g, &c->d_cov_out, &c->d_peaks_spec, &c->d_peaks_bands,
                           &c->d_peaks_part, &c->d_peaks_fit, &c->d_peaks_info, &c->d_dyn_q, &c->d_dyn_kappa, &c->d_dyn_khat, &c->d_dyn_idx,
-                          &c->d_dyn_out})
+                          &c->d_dyn_out, &c->d_lat_q, &c->d_lat_tiles, &c->d_lat_ent, &c->d_lat_slot, &c->d_lat_dest, &c->d_lat_khat,
+                          &c->d_lat_idx, &c->d_lat_bins, &c->d_lat_scale, &c->d_lat_acc, &c->d_lat_out})
             b->release();
         (void)hipStreamDestroy(c->stream);
     }

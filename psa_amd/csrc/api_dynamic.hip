@@ -16,28 +16,14 @@
 
 namespace psa {
 
-namespace {
-
-struct DynCall {
-    int64_t T = 0, N = 0, K = 0, n_g = 0;
-    int     NC = 1, slices = 1;
-    bool    cut = false;                 // false: one boxcar segment of T frames, q transformed in place
-    int64_t L = 0, H = 0, n_seg = 0;
-    int64_t per_k = 0, unit = 0;         // bytes of one k-vector of q; of one (k-vector, segment) of the segment buffer
-    int64_t kb = 0, bk = 0, bs = 0;      // k-vectors per block of q; k-vectors x segments per sub-block
-    std::vector<float> kappa, khat;      // (K, 6) k / 2 pi as hi xyz, lo xyz; (K, 3) k / |k|
-};
-
-// every refusal, the sizes and the block rule
-int dynamic_check(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents, DynCall* d) {
-    PSA_REQUIRE(k_vectors != nullptr, "null k_vectors");
+// the refusals that concern the call's shape, the slots, the atom set and the weights (`entry`: who is asking)
+int dynamic_inputs(psa_ctx* c, const char* entry, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents, DynCall* d) {
     PSA_REQUIRE(K >= 1 && K < (1ll << 29), "need at least one k-vector (K = %lld)", (long long)K);
     PSA_REQUIRE(currents == 0 || currents == 1, "currents is 0 (density only) or 1 (density and currents), got %d", (int)currents);
-    PSA_REQUIRE(c->comm == nullptr && c->nranks == 1, "psa_dynamic_spectra is not available on a sharded context (%d ranks)",
-                c->nranks);
+    PSA_REQUIRE(c->comm == nullptr && c->nranks == 1, "%s is not available on a sharded context (%d ranks)", entry, c->nranks);
     const DataSlot& pos = c->slot[PSA_SLOT_POSITIONS];
     const DataSlot& vel = c->slot[PSA_SLOT_VELOCITIES];
-    PSA_REQUIRE(pos.valid, "the positions slot holds no array: the phase of psa_dynamic_spectra is exp(i k.r(t))");
+    PSA_REQUIRE(pos.valid, "the positions slot holds no array: the phase of %s is exp(i k.r(t))", entry);
     const int64_t T = pos.T, N = pos.N;
     PSA_REQUIRE(!currents || vel.valid, "currents need the velocities slot, which holds no array");
     PSA_REQUIRE(!currents || (vel.T == T && vel.N == N), "currents need velocities of the positions' shape: (%lld, %lld, 3) against "
@@ -45,11 +31,14 @@ int dynamic_check(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* 
     PSA_REQUIRE(idx == nullptr || (n_g >= 0 && n_g < (1ll << 31) - DYN_ATOMS), "bad number of atoms %lld", (long long)n_g);
     for (int64_t i = 0; idx && i < n_g; ++i) PSA_REQUIRE(idx[i] >= 0 && idx[i] < N, "Atom indices in basis out of bounds.");
     PSA_TRY(check_weights(c, N));
-    for (int64_t i = 0; i < 3 * K; ++i)
-        PSA_REQUIRE(std::isfinite(k_vectors[i]), "k_vectors[%lld, %lld] is not finite", (long long)(i / 3), (long long)(i % 3));
     d->T = T, d->N = N, d->K = K, d->n_g = idx ? n_g : N;
     d->NC = currents ? 4 : 1;
-    d->slices = dynamic_slices(K);
+    return PSA_OK;
+}
+
+// the context's segments, the sizes and the block rule of the budget
+int dynamic_plan(psa_ctx* c, DynCall* d) {
+    const int64_t T = d->T, K = d->K;
     d->cut = c->seg_L != 0;
     d->L = d->cut ? c->seg_L : T, d->H = d->cut ? c->seg_hop : T;
     PSA_REQUIRE(d->L <= T, "segment length %lld exceeds the trajectory's %lld frames", (long long)d->L, (long long)T);
@@ -76,6 +65,19 @@ int dynamic_check(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* 
         else d->bk = units;
         d->bs = std::min(d->bs, std::max<int64_t>(1, ((1ll << 31) - 1) / (d->bk * d->NC)));
     }
+    return PSA_OK;
+}
+
+namespace {
+
+// every refusal, the sizes and the block rule
+int dynamic_check(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents, DynCall* d) {
+    PSA_REQUIRE(k_vectors != nullptr, "null k_vectors");
+    PSA_TRY(dynamic_inputs(c, "psa_dynamic_spectra", K, idx, n_g, currents, d));
+    for (int64_t i = 0; i < 3 * K; ++i)
+        PSA_REQUIRE(std::isfinite(k_vectors[i]), "k_vectors[%lld, %lld] is not finite", (long long)(i / 3), (long long)(i % 3));
+    d->slices = dynamic_slices(K);
+    PSA_TRY(dynamic_plan(c, d));
 
     // kappa = k / 2 pi in float64 from the float32 k, as float32 hi + lo; k / |k| in float64 (k = 0: 0)
     const double two_pi = 6.283185307179586476925286766559;

@@ -14,6 +14,7 @@
 //   api_covariance.hip  the spectral covariance of the B site groups' spectra: the frequency-weighted sum of their outer products
 //   api_peaks.hip    Lorentzian peak fits of spectrum columns: an uploaded spectrum, or the mode spectra where they lie
 //   api_dynamic.hip  the dynamic structure factor and the current correlations: the phase of every frame's own positions
+//   api_lattice.hip  the same spectra on the box's reciprocal lattice, per vector or averaged over shells of |k|
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
 // k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
 #pragma once
@@ -216,6 +217,19 @@ struct PeakArgs {
 };
 int check_peak_args(const psa_peak_opts* opts, PeakArgs* a);
 int peaks_run(psa_ctx* c, const float* d_spec, const PeakArgs& a);
+// api_dynamic.hip: the shape of a psa_dynamic_spectra call, shared with psa_lattice_spectra (api_lattice.hip): the checks
+// of the slots, the atom set and the weights, then the context's segments and the block rule of the budget
+struct DynCall {
+    int64_t T = 0, N = 0, K = 0, n_g = 0;
+    int     NC = 1, slices = 1;
+    bool    cut = false;                 // false: one boxcar segment of T frames, q transformed in place
+    int64_t L = 0, H = 0, n_seg = 0;
+    int64_t per_k = 0, unit = 0;         // bytes of one k-vector of q; of one (k-vector, segment) of the segment buffer
+    int64_t kb = 0, bk = 0, bs = 0;      // k-vectors per block of q; k-vectors x segments per sub-block
+    std::vector<float> kappa, khat;      // (K, 6) k / 2 pi as hi xyz, lo xyz; (K, 3) k / |k|
+};
+int dynamic_inputs(psa_ctx* c, const char* entry, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents, DynCall* d);
+int dynamic_plan(psa_ctx* c, DynCall* d);
 int    check_weights(psa_ctx* c, int64_t N);            // the context's atom weights fit a slot of N atoms
 void   set_geom_weights(const psa_ctx* c, ProjGeom* g);  // ... and go into a launch's geometry
 int    begin_result(psa_ctx* c, int64_t T, int64_t K_total, int64_t k_offset, bool intensity, char** rows);

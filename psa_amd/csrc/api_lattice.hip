@@ -1,0 +1,301 @@
+// psa_lattice_spectra: the dynamic structure factor and the current correlations on the reciprocal lattice of the
+// simulation box, per vector or averaged over shells of |k| (definition: include/psa_hip.h; kernels: lattice.hip).  The
+// flow is psa_dynamic_spectra's (api_dynamic.hip), with its checks of the slots, the atom set and the weights, its segments
+// and its budget rule (PSA_OPT_DYNAMIC_WORK_BYTES): per block of kb vectors the projection kernel writes q (kb, NC, T);
+// the window pass, the rocFFT and -- in the per-vector form -- dynamic.hip's power pass follow unchanged.  In the shell
+// form the power pass is replaced by the shell pass, which adds every sub-block's vectors to a float64 accumulator
+// (1 or 3, L, n_bins) on the device, and one last launch scales and rounds it: (L, n_bins) crosses to the host, not (L, K).
+//
+// The plan.  The projection kernel wants the vectors of a tile close in index space (a tile's table holds one entry per
+// distinct (axis, index) pair), the shell pass wants every bin's vectors of a block in one contiguous range.  So the
+// vectors are processed in an order of the host's choosing:
+//   per-vector form   block by block as given, inside a block sorted by (n_1, n_2, n_3); a vector's row of q is its place
+//                     in the caller's list, so everything after the projection sees the caller's order;
+//   shell form        the whole list sorted by (bin, n_1, n_2, n_3), then cut into blocks; a vector's row of q is its
+//                     place in that order.
+// A block is cut into tiles of LAT_KS vectors.  Per tile: its entries (axis << 8 | m + 128), ascending; per vector the
+// three entries it reads and its row.  A vector's sum over atoms does not depend on which tile or block it is in.
+// Every block starts a new tile, and a tile's slot and row tables have LAT_KS entries whatever it holds: a budget that
+// leaves a handful of vectors per block costs 4 KiB of plan and a 256-lane workgroup per handful -- correct, and slow.
+// Outside the budget, like d_dyn_out: the result and the shell form's accumulator, 8 (1 or 3) L n_bins bytes.
+#include <numeric>
+
+#include "api_internal.h"
+
+namespace psa {
+
+namespace {
+
+struct LatCall {
+    DynCall  d;                                      // sizes, segments, block rule (kappa unused; khat in row order)
+    bool     shell = false;
+    int64_t  n_bins = 0;
+    float    box_hi[9], box_lo[9];
+    std::vector<int64_t>  block_tile0;               // first tile of block b (n_blocks + 1)
+    std::vector<int32_t>  tile_off, dest;            // (n_tiles + 1); (n_tiles LAT_KS)
+    std::vector<uint16_t> ent;
+    std::vector<uint32_t> slot;                      // (n_tiles LAT_KS)
+    std::vector<int32_t>  bin_start;                 // (n_bins + 1) in the processing order
+    std::vector<double>   scale;                     // (n_bins) 1 / (2 n_half n_seg U L^2); an empty bin: 0
+};
+
+int lattice_check(psa_ctx* c, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t n_bins,
+                  const int32_t* idx, int64_t n_g, int32_t currents, LatCall* p) {
+    PSA_REQUIRE(box_inverse != nullptr, "null box_inverse");
+    PSA_REQUIRE(indices != nullptr, "null indices");
+    DynCall& d = p->d;
+    PSA_TRY(dynamic_inputs(c, "psa_lattice_spectra", K, idx, n_g, currents, &d));
+    const double* B = box_inverse;
+    for (int i = 0; i < 9; ++i) PSA_REQUIRE(std::isfinite(B[i]), "box_inverse[%d] is not finite", i);
+    const double det = B[0] * (B[4] * B[8] - B[5] * B[7]) - B[1] * (B[3] * B[8] - B[5] * B[6]) + B[2] * (B[3] * B[7] - B[4] * B[6]);
+    PSA_REQUIRE(std::isfinite(det) && det != 0.0, "box_inverse is singular");
+    for (int64_t i = 0; i < 3 * K; ++i)
+        PSA_REQUIRE(indices[i] >= -LAT_MAX_INDEX && indices[i] <= LAT_MAX_INDEX, "indices[%lld, %lld] = %d: |n_j| <= %d is served",
+                    (long long)(i / 3), (long long)(i % 3), (int)indices[i], LAT_MAX_INDEX);
+    p->shell = bin_of != nullptr;
+    p->n_bins = p->shell ? n_bins : 0;
+    if (p->shell) {
+        PSA_REQUIRE(n_bins >= 1 && n_bins < (1ll << 24), "need at least one bin (n_bins = %lld)", (long long)n_bins);
+        for (int64_t k = 0; k < K; ++k) {
+            PSA_REQUIRE(bin_of[k] >= 0 && bin_of[k] < n_bins, "bin_of[%lld] = %d is outside [0, %lld)", (long long)k, (int)bin_of[k],
+                        (long long)n_bins);
+            const int32_t* n = indices + 3 * k;
+            const int32_t  lead = n[0] != 0 ? n[0] : n[1] != 0 ? n[1] : n[2];
+            PSA_REQUIRE(lead > 0, "indices[%lld] = (%d, %d, %d) is not a half-space member (first non-zero index positive): the "
+                        "shell form folds -n onto n", (long long)k, (int)n[0], (int)n[1], (int)n[2]);
+        }
+    }
+    PSA_TRY(dynamic_plan(c, &d));
+
+    for (int i = 0; i < 9; ++i) {
+        p->box_hi[i] = (float)B[i];
+        p->box_lo[i] = (float)(B[i] - (double)p->box_hi[i]);
+    }
+    // the processing order
+    std::vector<int64_t> order((size_t)K);
+    std::iota(order.begin(), order.end(), (int64_t)0);
+    auto by_index = [&](int64_t a, int64_t b) {
+        const int32_t *x = indices + 3 * a, *y = indices + 3 * b;
+        return x[0] != y[0] ? x[0] < y[0] : x[1] != y[1] ? x[1] < y[1] : x[2] != y[2] ? x[2] < y[2] : a < b;
+    };
+    if (p->shell)
+        std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return bin_of[a] != bin_of[b] ? bin_of[a] < bin_of[b] : by_index(a, b); });
+    else
+        for (int64_t k0 = 0; k0 < K; k0 += d.kb) std::sort(order.begin() + k0, order.begin() + std::min(K, k0 + d.kb), by_index);
+
+    // k / |k| in float64, k = 2 pi sum_j n_j Hinv[:, j], in the order of the rows of q
+    const double two_pi = 6.283185307179586476925286766559;
+    d.khat.assign((size_t)K * 3, 0.f);
+    for (int64_t r = 0; r < K; ++r) {
+        const int32_t* n = indices + 3 * (p->shell ? order[r] : r);
+        double         k[3];
+        for (int cc = 0; cc < 3; ++cc) k[cc] = two_pi * ((double)n[0] * B[3 * cc] + (double)n[1] * B[3 * cc + 1] + (double)n[2] * B[3 * cc + 2]);
+        const double norm = std::sqrt(k[0] * k[0] + k[1] * k[1] + k[2] * k[2]);
+        for (int cc = 0; cc < 3; ++cc)
+            if (norm > 0.0) d.khat[(size_t)r * 3 + cc] = (float)(k[cc] / norm);
+    }
+
+    // blocks, tiles, entries
+    p->block_tile0.assign(1, 0);
+    p->tile_off.assign(1, 0);
+    for (int64_t k0 = 0; k0 < K; k0 += d.kb) {
+        const int64_t nk = std::min(d.kb, K - k0);
+        for (int64_t t0 = 0; t0 < nk; t0 += LAT_KS) {
+            const int64_t nt = std::min<int64_t>(LAT_KS, nk - t0);
+            int           where[3][2 * LAT_MAX_INDEX + 1];
+            bool          used[3][2 * LAT_MAX_INDEX + 1] = {};
+            for (int64_t i = 0; i < nt; ++i)
+                for (int j = 0; j < 3; ++j) used[j][indices[3 * order[k0 + t0 + i] + j] + LAT_MAX_INDEX] = true;
+            int R = 0;
+            for (int j = 0; j < 3; ++j)
+                for (int m = 0; m <= 2 * LAT_MAX_INDEX; ++m)
+                    if (used[j][m]) {
+                        where[j][m] = R++;
+                        p->ent.push_back((uint16_t)((j << 8) | (m - LAT_MAX_INDEX + 128)));
+                    }
+            p->tile_off.push_back((int32_t)p->ent.size());
+            for (int64_t i = 0; i < LAT_KS; ++i) {
+                uint32_t s = 0;
+                int32_t  row = -1;
+                if (i < nt) {
+                    const int64_t  v = order[k0 + t0 + i];
+                    const int32_t* n = indices + 3 * v;
+                    s = (uint32_t)where[0][n[0] + LAT_MAX_INDEX] | (uint32_t)where[1][n[1] + LAT_MAX_INDEX] << 9 |
+                        (uint32_t)where[2][n[2] + LAT_MAX_INDEX] << 18;
+                    row = (int32_t)(p->shell ? t0 + i : v - k0);
+                }
+                p->slot.push_back(s);
+                p->dest.push_back(row);
+            }
+        }
+        p->block_tile0.push_back((int64_t)p->tile_off.size() - 1);
+    }
+    PSA_REQUIRE(p->ent.size() < (1ull << 31) && p->tile_off.size() < (1ull << 22), "the vector list needs too many tiles");
+
+    if (p->shell) {
+        std::vector<int64_t> count((size_t)n_bins, 0);
+        for (int64_t k = 0; k < K; ++k) ++count[(size_t)bin_of[k]];
+        p->bin_start.assign((size_t)n_bins + 1, 0);
+        p->scale.assign((size_t)n_bins, 0.0);
+        const double U = d.cut ? c->seg_U : 1.0;
+        for (int64_t b = 0; b < n_bins; ++b) {
+            p->bin_start[(size_t)b + 1] = (int32_t)(p->bin_start[(size_t)b] + count[(size_t)b]);
+            if (count[(size_t)b]) p->scale[(size_t)b] = 1.0 / (2.0 * (double)count[(size_t)b] * (double)d.n_seg * U * (double)d.L * (double)d.L);
+        }
+    }
+    return PSA_OK;
+}
+
+int lattice_upload(psa_ctx* c, const LatCall& p, const int32_t* idx) {
+    StageTimer st(c, PSA_T_H2D);
+    PSA_TRY(upload(c, c->d_lat_tiles, p.tile_off.data(), p.tile_off.size() * sizeof(int32_t)));
+    PSA_TRY(upload(c, c->d_lat_ent, p.ent.data(), p.ent.size() * sizeof(uint16_t)));
+    PSA_TRY(upload(c, c->d_lat_slot, p.slot.data(), p.slot.size() * sizeof(uint32_t)));
+    PSA_TRY(upload(c, c->d_lat_dest, p.dest.data(), p.dest.size() * sizeof(int32_t)));
+    PSA_TRY(upload(c, c->d_lat_khat, p.d.khat.data(), p.d.khat.size() * sizeof(float)));
+    if (idx) PSA_TRY(upload(c, c->d_lat_idx, idx, (size_t)p.d.n_g * sizeof(int32_t)));
+    if (p.shell) {
+        PSA_TRY(upload(c, c->d_lat_bins, p.bin_start.data(), p.bin_start.size() * sizeof(int32_t)));
+        PSA_TRY(upload(c, c->d_lat_scale, p.scale.data(), p.scale.size() * sizeof(double)));
+    }
+    return PSA_OK;
+}
+
+// block b of the plan over all frames into d_q (nk, NC, T)
+int lattice_project(psa_ctx* c, const LatCall& p, const int32_t* idx, int64_t block, float2* d_q) {
+    StageTimer st(c, PSA_T_PROJECT);
+    const DynCall& d = p.d;
+    return launch_lattice_project(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(),
+                                  d.NC == 4 ? c->slot[PSA_SLOT_VELOCITIES].buf.as<float>() : nullptr,
+                                  c->weights_N ? c->d_weights.as<float>() : nullptr, idx ? c->d_lat_idx.as<int>() : nullptr, p.box_hi,
+                                  p.box_lo, c->d_lat_tiles.as<int>(), c->d_lat_ent.as<unsigned short>(), c->d_lat_slot.as<unsigned>(),
+                                  c->d_lat_dest.as<int>(), d_q, d.T, d.N, d.n_g, p.block_tile0[(size_t)block],
+                                  p.block_tile0[(size_t)block + 1] - p.block_tile0[(size_t)block], d.NC == 4);
+}
+
+int lattice_run(psa_ctx* c, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t n_bins,
+                const int32_t* idx, int64_t n_g, int32_t currents, float* out_host, size_t out_bytes) {
+    PSA_REQUIRE(out_host != nullptr, "null output");
+    LatCall p;
+    PSA_TRY(lattice_check(c, box_inverse, indices, K, bin_of, n_bins, idx, n_g, currents, &p));
+    const DynCall& d = p.d;
+    const int64_t  L = d.L, T = d.T, rows = currents ? 3 : 1, cols = p.shell ? n_bins : K;
+    const size_t   want = (size_t)rows * (size_t)L * (size_t)cols * sizeof(float);
+    PSA_REQUIRE(out_bytes == want, "out_bytes is %zu, the (%lld,%lld,%lld) float32 result has %zu", out_bytes, (long long)rows,
+                (long long)L, (long long)cols, want);
+    if (d.n_g == 0) {                                        // an empty atom set: zeros
+        std::memset(out_host, 0, out_bytes);
+        return PSA_OK;
+    }
+    PSA_TRY(lattice_upload(c, p, idx));
+    PSA_TRY(c->d_lat_q.reserve((size_t)d.kb * (size_t)d.per_k));
+    if (d.cut) PSA_TRY(c->d_seg.reserve((size_t)d.bk * (size_t)d.bs * (size_t)d.unit));
+    PSA_TRY(c->d_lat_out.reserve(want));
+    double* d_acc = nullptr;
+    if (p.shell) {
+        PSA_TRY(c->d_lat_acc.reserve(want * 2));
+        d_acc = c->d_lat_acc.as<double>();
+        PSA_HIP_CHECK(hipMemsetAsync(d_acc, 0, want * 2, c->stream));
+    }
+
+    const double U = d.cut ? c->seg_U : 1.0;
+    const float  scale = (float)(1.0 / ((double)L * (double)L * (double)d.n_seg * U));
+    float2*      d_q = c->d_lat_q.as<float2>();
+    float2*      d_seg = d.cut ? c->d_seg.as<float2>() : nullptr;
+    float*       d_out = c->d_lat_out.as<float>();
+    const float* d_khat = c->d_lat_khat.as<float>();
+    const int*   d_bins = p.shell ? c->d_lat_bins.as<int>() : nullptr;
+    int64_t      block = 0;
+    for (int64_t k0 = 0; k0 < K; k0 += d.kb, ++block) {
+        const int64_t nk = std::min(d.kb, K - k0);
+        PSA_TRY(lattice_project(c, p, idx, block, d_q));
+        if (!d.cut) {
+            {
+                StageTimer st(c, PSA_T_FFT);
+                PSA_TRY(run_fft(c, d_q, T, (int64_t)d.NC * nk));
+            }
+            StageTimer st(c, PSA_T_EPILOGUE);
+            if (p.shell) PSA_TRY(launch_lattice_shell(c, d_q, d_khat + (size_t)k0 * 3, d_bins, d_acc, T, 1, k0, nk, n_bins, currents != 0));
+            else PSA_TRY(launch_dynamic_power(c, d_q, d_khat + (size_t)k0 * 3, d_out, T, 1, nk, currents != 0, K, k0, scale, true));
+        }
+        for (int64_t k1 = 0; d.cut && k1 < nk; k1 += d.bk) {
+            const int64_t nb = std::min(d.bk, nk - k1);
+            for (int64_t s0 = 0; s0 < d.n_seg; s0 += d.bs) {
+                const int64_t ns = std::min(d.bs, d.n_seg - s0);
+                {
+                    StageTimer st(c, PSA_T_EPILOGUE);
+                    PSA_TRY(launch_segment_window_rows(c, d_q + (size_t)k1 * (size_t)d.NC * (size_t)T, c->d_seg_window.as<float>(), d_seg,
+                                                       T, L, d.H, s0, ns, nb * d.NC));
+                }
+                {
+                    StageTimer st(c, PSA_T_FFT);
+                    PSA_TRY(run_fft(c, d_seg, L, (int64_t)d.NC * nb * ns));
+                }
+                StageTimer st(c, PSA_T_EPILOGUE);
+                if (p.shell)
+                    PSA_TRY(launch_lattice_shell(c, d_seg, d_khat + (size_t)(k0 + k1) * 3, d_bins, d_acc, L, ns, k0 + k1, nb, n_bins,
+                                                 currents != 0));
+                else
+                    PSA_TRY(launch_dynamic_power(c, d_seg, d_khat + (size_t)(k0 + k1) * 3, d_out, L, ns, nb, currents != 0, K, k0 + k1,
+                                                 scale, s0 == 0));
+            }
+        }
+    }
+    if (p.shell) {
+        StageTimer st(c, PSA_T_EPILOGUE);
+        PSA_TRY(launch_lattice_finish(c, d_acc, c->d_lat_scale.as<double>(), d_out, rows * L * n_bins, n_bins));
+    }
+    StageTimer st(c, PSA_T_D2H);
+    PSA_HIP_CHECK(hipMemcpyAsync(out_host, d_out, want, hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return PSA_OK;
+}
+
+// the projection kernel alone, block by block under the same rule: q (K, NC, T) before any FFT, rows in the caller's order
+int lattice_debug_project(psa_ctx* c, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* idx, int64_t n_g,
+                          int32_t currents, void* out_host) {
+    PSA_REQUIRE(out_host != nullptr, "null output");
+    LatCall p;
+    PSA_TRY(lattice_check(c, box_inverse, indices, K, nullptr, 0, idx, n_g, currents, &p));
+    const DynCall& d = p.d;
+    if (d.n_g == 0) {
+        std::memset(out_host, 0, (size_t)K * (size_t)d.per_k);
+        return PSA_OK;
+    }
+    PSA_TRY(lattice_upload(c, p, idx));
+    PSA_TRY(c->d_lat_q.reserve((size_t)d.kb * (size_t)d.per_k));
+    int64_t block = 0;
+    for (int64_t k0 = 0; k0 < K; k0 += d.kb, ++block) {
+        const int64_t nk = std::min(d.kb, K - k0);
+        PSA_TRY(lattice_project(c, p, idx, block, c->d_lat_q.as<float2>()));
+        PSA_HIP_CHECK(hipMemcpyAsync((char*)out_host + (size_t)k0 * (size_t)d.per_k, c->d_lat_q.ptr, (size_t)nk * (size_t)d.per_k,
+                                     hipMemcpyDeviceToHost, c->stream));
+    }
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return PSA_OK;
+}
+
+}  // namespace
+
+}  // namespace psa
+
+using namespace psa;
+
+extern "C" {
+
+int psa_lattice_spectra(psa_ctx* c, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t n_bins,
+                        const int32_t* idx, int64_t n_g, int32_t currents, float* out_host, size_t out_bytes) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    return synchronised(c, lattice_run(c, box_inverse, indices, K, bin_of, n_bins, idx, n_g, currents, out_host, out_bytes),
+                        "psa_lattice_spectra");
+}
+
+int psa_debug_lattice_project(psa_ctx* c, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* idx, int64_t n_g,
+                              int32_t currents, void* out_host) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    return synchronised(c, lattice_debug_project(c, box_inverse, indices, K, idx, n_g, currents, out_host), "psa_debug_lattice_project");
+}
+
+}  // extern "C"

@@ -297,6 +297,13 @@ struct psa_ctx {
     psa::DevBuf  d_dyn_q, d_dyn_kappa, d_dyn_khat, d_dyn_idx, d_dyn_out;
     int64_t      opt_dynamic_work_bytes = (int64_t)4 << 30;
 
+    // spectra on the box's reciprocal lattice (psa_lattice_spectra; api_lattice.hip), under the same budget: the
+    // projections q of one block; the plan of the call -- tile offsets, the tiles' entries, per vector its three entries
+    // and its row of q --; k / |k|, the atom list; the shell form's bin offsets, scales and float64 accumulator
+    // (1 or 3, L, n_bins); the float32 result.  All kept between calls.
+    psa::DevBuf  d_lat_q, d_lat_tiles, d_lat_ent, d_lat_slot, d_lat_dest, d_lat_khat, d_lat_idx, d_lat_bins, d_lat_scale,
+                 d_lat_acc, d_lat_out;
+
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
                                           // plane builds, trajectory uploads (psa_oneoff_stats)
@@ -454,6 +461,28 @@ int launch_dynamic_power(psa_ctx* c, const float2* d_seg, const float* d_khat, f
                          bool currents, int64_t K_pitch, int64_t k_col0, float scale, bool first);
 // (sin, cos)(2 pi x) of n arguments in turns by the kernel's own routine (the sweep that measures its error)
 int launch_dynamic_sincos(psa_ctx* c, const float* d_turns, float2* d_out, int64_t n);
+// --- lattice.hip (psa_lattice_spectra: q_c[n,t] = sum_a w_a d_a,c(t) exp(2 pi i n.s_a(t)) on the reciprocal lattice of the
+// box, the phase factorised per axis; the arithmetic, the summation structure and the bound are in its header)
+constexpr int LAT_THREADS = 256;       // lanes of a workgroup
+constexpr int LAT_KS = 512;            // vectors of a tile: two per lane
+constexpr int LAT_ATOMS = 128;         // most atoms of one frame staged per tile
+constexpr int LAT_TABLE = 3584;        // entries (cos, sin) of the per-atom factor tables in LDS: atoms per tile x entries
+constexpr int LAT_CHAIN = 128;         // atoms one float32 accumulator sums before it is folded into the second float32 sum
+constexpr int LAT_FRAMES = 4;          // frames one workgroup projects, one after the other
+constexpr int LAT_MAX_INDEX = 64;      // largest |n_j| served
+constexpr int LAT_MAX_ENTRIES = 3 * (2 * LAT_MAX_INDEX + 1);   // distinct (axis, m) pairs a tile can use
+// tiles tile0 .. tile0 + n_tiles - 1 of the uploaded plan x all T frames -> q (rows, NC, T) complex64 at the rows d_dest
+// names; box_hi, box_lo: the 9 entries of Hinv as float32 parts (host); d_vel, d_weights, d_idx may be null
+int launch_lattice_project(psa_ctx* c, const float* d_pos, const float* d_vel, const float* d_weights, const int* d_idx,
+                           const float* box_hi, const float* box_lo, const int* d_tile_off, const unsigned short* d_ent,
+                           const unsigned* d_slot, const int* d_dest, float2* d_q, int64_t T, int64_t N, int64_t n_g, int64_t tile0,
+                           int64_t n_tiles, bool currents);
+// after the FFT of the segment buffer (nb, NC, ns, L) of the vectors g0 .. g0 + nb - 1 (d_khat: their rows): acc
+// (1 or 3, L, n_bins) float64 += sum over the bin's vectors and the segments of X_n[o] + X_n[(L - o) mod L], unscaled
+int launch_lattice_shell(psa_ctx* c, const float2* d_seg, const float* d_khat, const int* d_bin_start, double* d_acc, int64_t L,
+                         int64_t ns, int64_t g0, int64_t nb, int64_t n_bins, bool currents);
+// out[i] = (float)(acc[i] scale[i mod n_bins]), n elements
+int launch_lattice_finish(psa_ctx* c, const double* d_acc, const double* d_scale, float* d_out, int64_t n, int64_t n_bins);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 
