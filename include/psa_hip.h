@@ -531,6 +531,41 @@ int psa_lattice_spectra(psa_ctx* ctx, const double* box_inverse /* 9 */, const i
                         int32_t currents /* 0: density only, 1: all three */, float* out_host /* (1 or 3, L, K or n_bins) */,
                         size_t out_bytes);
 
+/* The self (incoherent) part of the dynamic structure factor on that lattice: a sum over atoms of moduli where
+ * psa_lattice_spectra takes the modulus of a sum over atoms -- what an incoherent scatterer (hydrogen, lithium, sodium,
+ * vanadium; w_a = b_inc) shows in a quasi-elastic neutron measurement.  Hinv, s and box_inverse are those of
+ * psa_lattice_spectra, the segments L, H, win, U, n_seg and the forward FFT those of psa_dynamic_spectra:
+ *     z[a,n,t]     = w_a exp(2 pi i n.s[t,a])
+ *     Z_s[a,n,o]   = sum_l win[l] z[a,n,sH+l] exp(-2 pi i o l / L)
+ *     density[o,n] = 1/(n_seg U L^2) sum_{a in idx} sum_s |Z_s[a,n,o]|^2
+ * The weights enter squared (signed weights are legal) and the result is a SUM over atoms, not a mean:
+ * density L dt / sum_a w_a^2 normalises it, and sum_o density[o,n] = sum_a w_a^2 for every vector and every trajectory (Parseval
+ * and U = (1/L) sum win^2; exact for one boxcar segment, else up to the segments' coverage).  With integer n a whole
+ * box vector added to r changes nothing: the result is the same on wrapped and on unwrapped coordinates.
+ *   bin_of == NULL  the per-vector form: out_host (L, K), the vectors as given, n = 0 allowed, nothing folded.
+ *   bin_of != NULL  the shell form: out_host (L, n_bins), the mean of density over the FULL-sphere vectors of each shell;
+ *                   every vector is a half-space member and -n is read at the mirrored frequency, X_{-n}[o] =
+ *                   X_n[(L - o) mod L] (z_{-n} = conj z_n for a real window and real weights); bins, the empty bin and
+ *                   the scale 1 / (2 n_half_b n_seg U L^2) are exactly those of psa_lattice_spectra.
+ * PSA_EINVAL: everything psa_lattice_spectra refuses that does not concern velocities; the budget rule differs.  Only the
+ * positions slot is read.  Work: N_g K n_seg L units of 8 bytes, N_g times what the coherent density costs after its
+ * projection.  Per block (self.hip): the series kernel writes work (atoms, vectors, segments, L) complex64 -- the sine and
+ * the cosine once per (atom, frame, distinct (axis, index) pair of a vector tile), two float32 complex products per unit,
+ * a frame shared by overlapping segments evaluated once per segment (measured faster than sharing it) --, one batched rocFFT, and the power pass adds
+ * |Z|^2, formed in float32, in float64 into an accumulator (L, K or n_bins) that lives across blocks; the last launch
+ * scales in float64 and rounds once to float32.  Per series element before the window
+ *     |z - z64| <= (eps_lat + 2^-24) |w_a|                                  (eps_lat: psa_lattice_spectra)
+ * Budget (PSA_OPT_DYNAMIC_WORK_BYTES): a block is a whole number of atom tiles (4 atoms) x vector tiles (at most 64 vectors
+ * with at most 24 distinct (axis, index) pairs) x segments; segments shrink first, then vector tiles, then atom tiles; a
+ * budget below 4 atoms x the largest tile's vectors x 8 L bytes is refused.  The accumulator, the chunk sums of the power
+ * pass and the result lie outside it.  No atomics: two identical calls give the same bits; the series do not depend on the
+ * blocking, the result in the order of its float64 sums alone (one float32 ulp at the most).  Nothing of the other entry
+ * points' state is touched.  Stage times go to psa_last_timings: [6] the series kernel, [3] FFT, [4] power pass and
+ * finish, [7] device->host. */
+int psa_self_spectra(psa_ctx* ctx, const double* box_inverse /* 9 */, const int32_t* indices /* (K,3) */, int64_t K,
+                     const int32_t* bin_of /* K or NULL */, int64_t n_bins, const int32_t* idx, int64_t n_g,
+                     float* out_host /* (L, K or n_bins) */, size_t out_bytes);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is
@@ -637,6 +672,11 @@ int psa_debug_dynamic_sincos(psa_ctx* ctx, const float* turns, int64_t n, float*
  * out_host (K, NC, T) complex64 in the caller's order, NC = currents ? 4 : 1 */
 int psa_debug_lattice_project(psa_ctx* ctx, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* idx,
                               int64_t n_g, int32_t currents, void* out_host);
+/* the series kernel of psa_self_spectra alone (per-vector form), block by block under the same budget rule, before the
+ * window and the FFT (one boxcar segment of all T frames whatever segments the context holds): out_host (n_g, K, T)
+ * complex64, atoms in the order of the set, vectors in the caller's order */
+int psa_debug_self_series(psa_ctx* ctx, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* idx,
+                          int64_t n_g, void* out_host);
 /* number of plane sets in the cache and their bytes */
 int psa_debug_plane_cache(psa_ctx* ctx, int64_t* n_sets, int64_t* bytes);
 

@@ -55,6 +55,12 @@ LAT_CHAIN = 128     # atoms one float32 accumulator sums before it is folded
 LAT_FRAMES = 4      # frames per workgroup
 LAT_MAX_INDEX = 64  # largest |n_j| served
 LAT_MAX_ENTRIES = 3 * (2 * LAT_MAX_INDEX + 1)
+# the tiles of the self-spectra series kernel (psa_amd/csrc/self.hip), mirrored for the cases of tests/self_cases.py
+SELF_THREADS = 256  # lanes of a workgroup: SELF_ATOMS wavefronts, a lane per frame
+SELF_ATOMS = 4      # atoms of an atom tile
+SELF_FRAMES = 64    # frames of a frame tile
+SELF_ENTRIES = 24   # most distinct (axis, m) pairs of a vector tile
+SELF_KS = 64        # most vectors of a vector tile
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -113,6 +119,9 @@ SIGNATURES = {
     "psa_lattice_spectra": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64, C.c_int32,
                                       _f32p, C.c_size_t]),
     "psa_debug_lattice_project": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, C.c_int32, C.c_void_p]),
+    "psa_self_spectra": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64, _f32p,
+                                   C.c_size_t]),
+    "psa_debug_self_series": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, C.c_void_p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
@@ -740,6 +749,34 @@ class Engine:
         _check(self._lib.psa_debug_lattice_project(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p),
                                                    n.shape[0], ip, n_g, 1 if currents else 0, out.ctypes.data_as(C.c_void_p)),
                "psa_debug_lattice_project")
+        return out
+
+    def self_spectra(self, box_inverse, indices, bin_of=None, n_bins=0, idx=None) -> np.ndarray:
+        """The self (incoherent) dynamic structure factor on the box's reciprocal lattice (psa_self_spectra): per atom
+        z = w_a exp(2 pi i n.s_a(t)), its power summed over the atoms.  `bin_of` None: per vector, (L, K) float32;
+        `bin_of` (K,) with `n_bins`: the shell form, (L, n_bins), every vector a half-space member standing for itself and
+        its partner -n.  Arguments, atom set, weights and segments as for `lattice_spectra`; only positions are read."""
+        T, _ = self.shape(SLOT_POSITIONS)
+        L = self.segment_length or T
+        inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
+        K = n.shape[0]
+        bins = None if bin_of is None else np.ascontiguousarray(bin_of, np.int32).ravel()
+        if bins is not None and bins.size != K:
+            raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
+        out = np.empty((L, K if bins is None else int(n_bins)), np.float32)
+        _check(self._lib.psa_self_spectra(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p), K,
+                                          None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g, _f32(out),
+                                          out.nbytes), "psa_self_spectra")
+        return out
+
+    def debug_self_series(self, box_inverse, indices, idx=None) -> np.ndarray:
+        """The series kernel of `self_spectra` alone: z (n_g, K, T) complex64 before the window and the FFT, atoms in the
+        order of the set, vectors in the caller's order."""
+        T, N = self.shape(SLOT_POSITIONS)
+        inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
+        out = np.empty((N if idx is None else n_g, n.shape[0], T), np.complex64)
+        _check(self._lib.psa_debug_self_series(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p),
+                                               n.shape[0], ip, n_g, out.ctypes.data_as(C.c_void_p)), "psa_debug_self_series")
         return out
 
     def _modes_args(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags):

@@ -39,6 +39,7 @@ from ..lattice import PowderSpectra
 from ..modes import ModeSED
 from ..peaks import PeakFit
 from ..segments import Segments
+from ..self_spectra import check_max_atoms, draw_atoms
 from ..utils.helpers import parse_direction
 from ..vdos import VDOS
 from ..weights import check_atom_weights
@@ -511,10 +512,12 @@ class SEDCalculator:
             return True
         return False
 
-    def _dynamic_run(self, basis_atom_indices, basis_atom_types, weights, segments, currents, call):
-        """(what `call(engine, atom list or None)` returns, the atom-index array, sum_a w_a^2 over it)"""
+    def _dynamic_run(self, basis_atom_indices, basis_atom_types, weights, segments, currents, call, max_atoms=None, seed=0):
+        """(what `call(engine, atom list or None)` returns, the atom-index array, sum_a w_a^2 over it); `max_atoms`: that
+        many atoms of the resolved set, drawn by `seed` (the self spectra)"""
         groups = self._resolve_groups(basis_atom_indices, basis_atom_types, "coherent")
         atoms = np.unique(np.concatenate(groups)).astype(int) if len(groups) > 1 else groups[0]
+        atoms = draw_atoms(atoms, max_atoms, seed)
         w2 = np.ones(self.traj.n_atoms, np.float64) if weights is None else weights.astype(np.float64) ** 2
         eng = self.engine
         with self._engine_state(weights, segments):  # (segments before the upload: its FFT primer then builds length L)
@@ -581,6 +584,20 @@ class SEDCalculator:
         Atom set, `atom_weights`, `segments`, `currents`, residency, the empty inputs and the sharded refusal are those
         of `calculate_dynamic_spectra`.  Returns a `psa_amd.PowderSpectra` with (L, n_bins) float32 fields."""
         weights = self._dynamic_arguments(atom_weights, segments, "the powder spectra")
+        shells = self._powder_shells(q_edges, max_per_bin, seed)
+        L, freqs = self._dynamic_lengths(segments)
+
+        def result(out, atoms, norm):
+            lon, tra = (out[1], out[2]) if currents else (None, None)
+            return self._powder_result(shells, out[0], lon, tra, freqs, atoms, norm)
+        n, b, n_bins, inv = shells["indices"], shells["bins"], shells["n_bins"], shells["inverse"]
+        if self._dynamic_nothing(n.shape[0], "powder spectra"):
+            return result(np.zeros((3 if currents else 1, L, n_bins), np.float32), np.zeros(0, int), 0.0)
+        return result(*self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, currents,
+                                         lambda eng, listed: eng.lattice_spectra(inv, n, b, n_bins, listed, currents)))
+
+    # what the two powder methods share: the half space of every shell, its bins and the draw; the result
+    def _powder_shells(self, q_edges, max_per_bin, seed):
         edges = np.asarray(q_edges, np.float64).ravel()
         lattice.shell_bins(np.zeros(0), edges, max_per_bin=max_per_bin)     # ValueError for bad edges or a bad cap
         n_bins = edges.size - 1
@@ -593,15 +610,62 @@ class SEDCalculator:
         n, b, q = n_all[selected], bins[selected], q_all[selected]
         q_mean = np.full(n_bins, np.nan)
         np.divide(np.bincount(b, weights=q, minlength=n_bins), used, out=q_mean, where=used > 0)
-        L, freqs = self._dynamic_lengths(segments)
+        return dict(edges=edges, n_bins=n_bins, inverse=inv, indices=n, bins=b, q=q_mean, used=used, available=available)
 
-        def result(out, atoms, norm):
-            lon, tra = (out[1], out[2]) if currents else (None, None)
-            return PowderSpectra(out[0], lon, tra, q_mean, edges, 2 * used, 2 * available, n, b, freqs, atoms, norm, self.dt_ps)
-        if self._dynamic_nothing(n.shape[0], "powder spectra"):
-            return result(np.zeros((3 if currents else 1, L, n_bins), np.float32), np.zeros(0, int), 0.0)
-        return result(*self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, currents,
-                                         lambda eng, listed: eng.lattice_spectra(inv, n, b, n_bins, listed, currents)))
+    def _powder_result(self, shells, density, longitudinal, transverse, freqs, atoms, norm):
+        return PowderSpectra(density, longitudinal, transverse, shells["q"], shells["edges"], 2 * shells["used"],
+                             2 * shells["available"], shells["indices"], shells["bins"], freqs, atoms, norm, self.dt_ps)
+
+    # ------------------------------------------------------------------ the self (incoherent) part on that lattice
+    def calculate_self_spectra(self, indices: np.ndarray,
+                               basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                               basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                               atom_weights: Optional[np.ndarray] = None, segments: Optional[Segments] = None,
+                               max_atoms: Optional[int] = None, seed: int = 0) -> DynamicSpectra:
+        """The self (incoherent) dynamic structure factor on the reciprocal lattice of the simulation box (not in the
+        reference; definition in psa_amd/self_spectra.py): density[o,n] = 1/(n_seg U L^2) sum_a sum_s
+        |FFT(win w_a exp(2 pi i n.s_a))|^2 for the integer `indices` (K, 3), |n_j| <= 64 -- a sum over atoms of moduli,
+        what an incoherent scatterer shows (`atom_weights` = b_inc), correct on wrapped coordinates as stored.
+
+        `max_atoms` draws that many atoms of the resolved set without replacement by np.random.default_rng(`seed`)
+        (the work is linear in the atoms, the statistical error falls as 1/sqrt of them); `atoms` and `weight_norm` of
+        the result then describe the atoms used.  Only the positions are made resident.  Atom set, `atom_weights`,
+        `segments`, the empty inputs and the sharded refusal are those of `calculate_lattice_spectra`.  Returns a
+        `psa_amd.DynamicSpectra` whose two current fields are None."""
+        weights = self._dynamic_arguments(atom_weights, segments, "the self spectra")
+        n = self._lattice_indices(indices)
+        inv = lattice.box_inverse(self.traj.box_matrix)
+        k = lattice.lattice_k(n, inv)
+        mags = np.linalg.norm(k, axis=1)
+        L, freqs = self._dynamic_lengths(segments)
+        check_max_atoms(max_atoms)
+        if self._dynamic_nothing(n.shape[0], "self spectra"):
+            return DynamicSpectra(np.zeros((L, n.shape[0]), np.float32), None, None, freqs, mags, k, np.zeros(0, int), 0.0, self.dt_ps)
+        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, False,
+                                             lambda eng, listed: eng.self_spectra(inv, n, None, 0, listed), max_atoms, seed)
+        return DynamicSpectra(out, None, None, freqs, mags, k, atoms, norm, self.dt_ps)
+
+    def calculate_powder_self_spectra(self, q_edges: np.ndarray,
+                                      basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                      basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                      atom_weights: Optional[np.ndarray] = None, segments: Optional[Segments] = None,
+                                      max_per_bin: Optional[int] = None, max_atoms: Optional[int] = None,
+                                      seed: int = 0) -> PowderSpectra:
+        """The powder average of `calculate_self_spectra` (definition in psa_amd/self_spectra.py): S_self(Q, w) averaged
+        over all vectors of the box's reciprocal lattice in each shell q_edges[b] <= |k| < q_edges[b + 1].  Shells,
+        `max_per_bin`, counts and the empty shell are those of `calculate_powder_spectra`; `max_atoms` and everything
+        else those of `calculate_self_spectra` (`seed` serves both draws).  Returns a `psa_amd.PowderSpectra` whose two
+        current fields are None."""
+        weights = self._dynamic_arguments(atom_weights, segments, "the powder self spectra")
+        shells = self._powder_shells(q_edges, max_per_bin, seed)
+        L, freqs = self._dynamic_lengths(segments)
+        check_max_atoms(max_atoms)
+        n, b, n_bins, inv = shells["indices"], shells["bins"], shells["n_bins"], shells["inverse"]
+        if self._dynamic_nothing(n.shape[0], "powder self spectra"):
+            return self._powder_result(shells, np.zeros((L, n_bins), np.float32), None, None, freqs, np.zeros(0, int), 0.0)
+        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, False,
+                                             lambda eng, listed: eng.self_spectra(inv, n, b, n_bins, listed), max_atoms, seed)
+        return self._powder_result(shells, out, None, None, freqs, atoms, norm)
 
     # ------------------------------------------------------------------ mode projection
     def calculate_mode_sed(self, k_points_mags: np.ndarray, k_vectors_3d: np.ndarray, eigenvectors: np.ndarray,

@@ -279,7 +279,9 @@ int psa_destroy(psa_ctx* c) {
                           &c->d_vdos_out, &c->d_modes_work, &c->d_modes_coef, &c->d_modes_out, &c->d_cov_slab, &c->d_cov_g, &c->d_cov_out, &c->d_peaks_spec, &c->d_peaks_bands,
                           &c->d_peaks_part, &c->d_peaks_fit, &c->d_peaks_info, &c->d_dyn_q, &c->d_dyn_kappa, &c->d_dyn_khat, &c->d_dyn_idx,
                           &c->d_dyn_out, &c->d_lat_q, &c->d_lat_tiles, &c->d_lat_ent, &c->d_lat_slot, &c->d_lat_dest, &c->d_lat_khat,
-                          &c->d_lat_idx, &c->d_lat_bins, &c->d_lat_scale, &c->d_lat_acc, &c->d_lat_out})
+                          &c->d_lat_idx, &c->d_lat_bins, &c->d_lat_scale, &c->d_lat_acc, &c->d_lat_out, &c->d_self_work, &c->d_self_tiles,
+                          &c->d_self_ent, &c->d_self_slot, &c->d_self_idx, &c->d_self_groups, &c->d_self_scale, &c->d_self_part, &c->d_self_acc,
+                          &c->d_self_out})
             b->release();
         (void)hipStreamDestroy(c->stream);
     }

@@ -15,6 +15,7 @@
 //   api_peaks.hip    Lorentzian peak fits of spectrum columns: an uploaded spectrum, or the mode spectra where they lie
 //   api_dynamic.hip  the dynamic structure factor and the current correlations: the phase of every frame's own positions
 //   api_lattice.hip  the same spectra on the box's reciprocal lattice, per vector or averaged over shells of |k|
+//   api_self.hip     the self (incoherent) part on that lattice: per-atom series, their power summed over the atoms
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
 // k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
 #pragma once
@@ -230,6 +231,13 @@ struct DynCall {
 };
 int dynamic_inputs(psa_ctx* c, const char* entry, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents, DynCall* d);
 int dynamic_plan(psa_ctx* c, DynCall* d);
+// api_lattice.hip: what psa_lattice_spectra shares with psa_self_spectra (api_self.hip): the refusals that concern the box
+// and the vector list; Hinv as float32 hi + lo; the processing order (bin_of: by (bin, n); else every run of kb vectors by n);
+// one tile's entry list (appended to ent) and per vector the three entries it reads -- returns the tile's R
+int  lattice_inputs(const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t n_bins);
+void lattice_box_parts(const double* B, float* hi, float* lo);
+void lattice_order(const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t kb, std::vector<int64_t>* order);
+int  lattice_tile_entries(const int32_t* indices, const int64_t* members, int64_t nt, std::vector<uint16_t>* ent, uint32_t* slot);
 int    check_weights(psa_ctx* c, int64_t N);            // the context's atom weights fit a slot of N atoms
 void   set_geom_weights(const psa_ctx* c, ProjGeom* g);  // ... and go into a launch's geometry
 int    begin_result(psa_ctx* c, int64_t T, int64_t K_total, int64_t k_offset, bool intensity, char** rows);

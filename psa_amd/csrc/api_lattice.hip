@@ -24,6 +24,73 @@
 
 namespace psa {
 
+// the refusals that concern the box and the vector list (K >= 1, both pointers checked by the caller)
+int lattice_inputs(const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t n_bins) {
+    const double* B = box_inverse;
+    for (int i = 0; i < 9; ++i) PSA_REQUIRE(std::isfinite(B[i]), "box_inverse[%d] is not finite", i);
+    const double det = B[0] * (B[4] * B[8] - B[5] * B[7]) - B[1] * (B[3] * B[8] - B[5] * B[6]) + B[2] * (B[3] * B[7] - B[4] * B[6]);
+    PSA_REQUIRE(std::isfinite(det) && det != 0.0, "box_inverse is singular");
+    for (int64_t i = 0; i < 3 * K; ++i)
+        PSA_REQUIRE(indices[i] >= -LAT_MAX_INDEX && indices[i] <= LAT_MAX_INDEX, "indices[%lld, %lld] = %d: |n_j| <= %d is served",
+                    (long long)(i / 3), (long long)(i % 3), (int)indices[i], LAT_MAX_INDEX);
+    if (bin_of != nullptr) {
+        PSA_REQUIRE(n_bins >= 1 && n_bins < (1ll << 24), "need at least one bin (n_bins = %lld)", (long long)n_bins);
+        for (int64_t k = 0; k < K; ++k) {
+            PSA_REQUIRE(bin_of[k] >= 0 && bin_of[k] < n_bins, "bin_of[%lld] = %d is outside [0, %lld)", (long long)k, (int)bin_of[k],
+                        (long long)n_bins);
+            const int32_t* n = indices + 3 * k;
+            const int32_t  lead = n[0] != 0 ? n[0] : n[1] != 0 ? n[1] : n[2];
+            PSA_REQUIRE(lead > 0, "indices[%lld] = (%d, %d, %d) is not a half-space member (first non-zero index positive): the "
+                        "shell form folds -n onto n", (long long)k, (int)n[0], (int)n[1], (int)n[2]);
+        }
+    }
+    return PSA_OK;
+}
+
+void lattice_box_parts(const double* B, float* hi, float* lo) {
+    for (int i = 0; i < 9; ++i) {
+        hi[i] = (float)B[i];
+        lo[i] = (float)(B[i] - (double)hi[i]);
+    }
+}
+
+// the processing order: with bins the whole list by (bin, n_1, n_2, n_3); without, every run of kb vectors by (n_1, n_2, n_3)
+void lattice_order(const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t kb, std::vector<int64_t>* out) {
+    std::vector<int64_t>& order = *out;
+    order.resize((size_t)K);
+    std::iota(order.begin(), order.end(), (int64_t)0);
+    auto by_index = [&](int64_t a, int64_t b) {
+        const int32_t *x = indices + 3 * a, *y = indices + 3 * b;
+        return x[0] != y[0] ? x[0] < y[0] : x[1] != y[1] ? x[1] < y[1] : x[2] != y[2] ? x[2] < y[2] : a < b;
+    };
+    if (bin_of)
+        std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return bin_of[a] != bin_of[b] ? bin_of[a] < bin_of[b] : by_index(a, b); });
+    else
+        for (int64_t k0 = 0; k0 < K; k0 += kb) std::sort(order.begin() + k0, order.begin() + std::min(K, k0 + kb), by_index);
+}
+
+// One tile: its nt vectors are members[0 .. nt) of the list.  Appends the tile's entries (axis << 8 | m + 128), ascending,
+// to ent and writes per vector the three entries it reads (9 bits each, counted from the tile's first); returns their number R.
+int lattice_tile_entries(const int32_t* indices, const int64_t* members, int64_t nt, std::vector<uint16_t>* ent, uint32_t* slot) {
+    int  where[3][2 * LAT_MAX_INDEX + 1];
+    bool used[3][2 * LAT_MAX_INDEX + 1] = {};
+    for (int64_t i = 0; i < nt; ++i)
+        for (int j = 0; j < 3; ++j) used[j][indices[3 * members[i] + j] + LAT_MAX_INDEX] = true;
+    int R = 0;
+    for (int j = 0; j < 3; ++j)
+        for (int m = 0; m <= 2 * LAT_MAX_INDEX; ++m)
+            if (used[j][m]) {
+                where[j][m] = R++;
+                ent->push_back((uint16_t)((j << 8) | (m - LAT_MAX_INDEX + 128)));
+            }
+    for (int64_t i = 0; i < nt; ++i) {
+        const int32_t* n = indices + 3 * members[i];
+        slot[i] = (uint32_t)where[0][n[0] + LAT_MAX_INDEX] | (uint32_t)where[1][n[1] + LAT_MAX_INDEX] << 9 |
+                  (uint32_t)where[2][n[2] + LAT_MAX_INDEX] << 18;
+    }
+    return R;
+}
+
 namespace {
 
 struct LatCall {
@@ -45,43 +112,16 @@ int lattice_check(psa_ctx* c, const double* box_inverse, const int32_t* indices,
     PSA_REQUIRE(indices != nullptr, "null indices");
     DynCall& d = p->d;
     PSA_TRY(dynamic_inputs(c, "psa_lattice_spectra", K, idx, n_g, currents, &d));
+    PSA_TRY(lattice_inputs(box_inverse, indices, K, bin_of, n_bins));
     const double* B = box_inverse;
-    for (int i = 0; i < 9; ++i) PSA_REQUIRE(std::isfinite(B[i]), "box_inverse[%d] is not finite", i);
-    const double det = B[0] * (B[4] * B[8] - B[5] * B[7]) - B[1] * (B[3] * B[8] - B[5] * B[6]) + B[2] * (B[3] * B[7] - B[4] * B[6]);
-    PSA_REQUIRE(std::isfinite(det) && det != 0.0, "box_inverse is singular");
-    for (int64_t i = 0; i < 3 * K; ++i)
-        PSA_REQUIRE(indices[i] >= -LAT_MAX_INDEX && indices[i] <= LAT_MAX_INDEX, "indices[%lld, %lld] = %d: |n_j| <= %d is served",
-                    (long long)(i / 3), (long long)(i % 3), (int)indices[i], LAT_MAX_INDEX);
     p->shell = bin_of != nullptr;
     p->n_bins = p->shell ? n_bins : 0;
-    if (p->shell) {
-        PSA_REQUIRE(n_bins >= 1 && n_bins < (1ll << 24), "need at least one bin (n_bins = %lld)", (long long)n_bins);
-        for (int64_t k = 0; k < K; ++k) {
-            PSA_REQUIRE(bin_of[k] >= 0 && bin_of[k] < n_bins, "bin_of[%lld] = %d is outside [0, %lld)", (long long)k, (int)bin_of[k],
-                        (long long)n_bins);
-            const int32_t* n = indices + 3 * k;
-            const int32_t  lead = n[0] != 0 ? n[0] : n[1] != 0 ? n[1] : n[2];
-            PSA_REQUIRE(lead > 0, "indices[%lld] = (%d, %d, %d) is not a half-space member (first non-zero index positive): the "
-                        "shell form folds -n onto n", (long long)k, (int)n[0], (int)n[1], (int)n[2]);
-        }
-    }
     PSA_TRY(dynamic_plan(c, &d));
 
-    for (int i = 0; i < 9; ++i) {
-        p->box_hi[i] = (float)B[i];
-        p->box_lo[i] = (float)(B[i] - (double)p->box_hi[i]);
-    }
+    lattice_box_parts(B, p->box_hi, p->box_lo);
     // the processing order
-    std::vector<int64_t> order((size_t)K);
-    std::iota(order.begin(), order.end(), (int64_t)0);
-    auto by_index = [&](int64_t a, int64_t b) {
-        const int32_t *x = indices + 3 * a, *y = indices + 3 * b;
-        return x[0] != y[0] ? x[0] < y[0] : x[1] != y[1] ? x[1] < y[1] : x[2] != y[2] ? x[2] < y[2] : a < b;
-    };
-    if (p->shell)
-        std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return bin_of[a] != bin_of[b] ? bin_of[a] < bin_of[b] : by_index(a, b); });
-    else
-        for (int64_t k0 = 0; k0 < K; k0 += d.kb) std::sort(order.begin() + k0, order.begin() + std::min(K, k0 + d.kb), by_index);
+    std::vector<int64_t> order;
+    lattice_order(indices, K, p->shell ? bin_of : nullptr, d.kb, &order);
 
     // k / |k| in float64, k = 2 pi sum_j n_j Hinv[:, j], in the order of the rows of q
     const double two_pi = 6.283185307179586476925286766559;
@@ -102,30 +142,13 @@ int lattice_check(psa_ctx* c, const double* box_inverse, const int32_t* indices,
         const int64_t nk = std::min(d.kb, K - k0);
         for (int64_t t0 = 0; t0 < nk; t0 += LAT_KS) {
             const int64_t nt = std::min<int64_t>(LAT_KS, nk - t0);
-            int           where[3][2 * LAT_MAX_INDEX + 1];
-            bool          used[3][2 * LAT_MAX_INDEX + 1] = {};
-            for (int64_t i = 0; i < nt; ++i)
-                for (int j = 0; j < 3; ++j) used[j][indices[3 * order[k0 + t0 + i] + j] + LAT_MAX_INDEX] = true;
-            int R = 0;
-            for (int j = 0; j < 3; ++j)
-                for (int m = 0; m <= 2 * LAT_MAX_INDEX; ++m)
-                    if (used[j][m]) {
-                        where[j][m] = R++;
-                        p->ent.push_back((uint16_t)((j << 8) | (m - LAT_MAX_INDEX + 128)));
-                    }
+            uint32_t      slots[LAT_KS] = {};
+            lattice_tile_entries(indices, order.data() + k0 + t0, nt, &p->ent, slots);
             p->tile_off.push_back((int32_t)p->ent.size());
             for (int64_t i = 0; i < LAT_KS; ++i) {
-                uint32_t s = 0;
-                int32_t  row = -1;
-                if (i < nt) {
-                    const int64_t  v = order[k0 + t0 + i];
-                    const int32_t* n = indices + 3 * v;
-                    s = (uint32_t)where[0][n[0] + LAT_MAX_INDEX] | (uint32_t)where[1][n[1] + LAT_MAX_INDEX] << 9 |
-                        (uint32_t)where[2][n[2] + LAT_MAX_INDEX] << 18;
-                    row = (int32_t)(p->shell ? t0 + i : v - k0);
-                }
-                p->slot.push_back(s);
-                p->dest.push_back(row);
+                const int64_t v = i < nt ? order[k0 + t0 + i] : 0;
+                p->slot.push_back(slots[i]);
+                p->dest.push_back(i < nt ? (int32_t)(p->shell ? t0 + i : v - k0) : -1);
             }
         }
         p->block_tile0.push_back((int64_t)p->tile_off.size() - 1);

@@ -54,6 +54,7 @@
 // vectors of the bin (one contiguous range: the host orders by bin) and its segments, vector by vector, segment by
 // segment, and adds the total to the float64 accumulator (1 or 3, L, n_bins), which lives across sub-blocks and blocks.
 // lattice_finish_kernel scales by 1 / (2 n_half_b n_seg U L^2) in float64 and rounds once to float32.
+#include "lattice_math.h"
 #include "psa_ctx.h"
 
 namespace psa {
@@ -61,44 +62,6 @@ namespace psa {
 namespace {
 
 constexpr int LAT_KPL = LAT_KS / LAT_THREADS;      // vectors per lane
-
-struct LatBox {
-    float hi[9], lo[9];                            // Hinv[c][j] as float32 hi + lo, row-major: c Cartesian, j axis
-};
-
-// a x b of two complex numbers (cos, sin)
-__device__ __forceinline__ float2 lat_cmul(const float2 a, const float2 b) {
-    return make_float2(__fmaf_rn(a.x, b.x, -__fmul_rn(a.y, b.y)), __fmaf_rn(a.x, b.y, __fmul_rn(a.y, b.x)));
-}
-
-// fractional coordinate j of one atom in turns, reduced to about [-1/2, 1/2], as hi + lo
-__device__ __forceinline__ float2 lat_frac(const float x, const float y, const float z, const LatBox& b, const int j) {
-    const float hx = b.hi[j], hy = b.hi[3 + j], hz = b.hi[6 + j];
-    const float px = __fmul_rn(hx, x), py = __fmul_rn(hy, y), pz = __fmul_rn(hz, z);
-    const float ex = __fmaf_rn(hx, x, -px), ey = __fmaf_rn(hy, y, -py), ez = __fmaf_rn(hz, z, -pz);
-    const float fx = px - __builtin_rintf(px), fy = py - __builtin_rintf(py), fz = pz - __builtin_rintf(pz);
-    float       t = fx + fy;
-    float       bb = t - fx;
-    const float err1 = (fx - (t - bb)) + (fy - bb);
-    t -= __builtin_rintf(t);
-    const float t2 = t + fz;
-    bb = t2 - t;
-    const float err2 = (t - (t2 - bb)) + (fz - bb);
-    const float s_hi = t2 - __builtin_rintf(t2);
-    float       lo = (ex + ey) + ez;
-    lo = __fmaf_rn(b.lo[j], x, lo);
-    lo = __fmaf_rn(b.lo[3 + j], y, lo);
-    lo = __fmaf_rn(b.lo[6 + j], z, lo);
-    return make_float2(s_hi, lo + (err1 + err2));
-}
-
-// (cos, sin)(2 pi m s), s = hi + lo
-__device__ __forceinline__ float2 lat_entry(const float m, const float2 s) {
-    const float p = __fmul_rn(m, s.x), e = __fmaf_rn(m, s.x, -p);
-    const float g = p - __builtin_rintf(p);
-    const float turns = g + __fmaf_rn(m, s.y, e);
-    return make_float2(__builtin_amdgcn_cosf(turns), __builtin_amdgcn_sinf(turns));
-}
 
 // pos, vel: (T, N, 3) float32; idx: n_g atom indices or null.  Tiles tile0 + blockIdx.y of the call's plan: tile_off
 // (n_tiles + 1) offsets into ent, the tiles' entries (axis << 8 | m + 128); per tile LAT_KS vectors: slot = its three

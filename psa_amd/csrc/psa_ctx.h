@@ -304,6 +304,13 @@ struct psa_ctx {
     psa::DevBuf  d_lat_q, d_lat_tiles, d_lat_ent, d_lat_slot, d_lat_dest, d_lat_khat, d_lat_idx, d_lat_bins, d_lat_scale,
                  d_lat_acc, d_lat_out;
 
+    // the self part on the box's reciprocal lattice (psa_self_spectra; api_self.hip), under the same budget: the series of
+    // one block (atoms, vectors, segments, L); the plan -- tile offsets into the entries and into the vectors, the entries,
+    // per vector its three entries --; the atom list; per output column its first vector and its column; the scales; the
+    // chunks' float64 partial sums and the float64 accumulator (L, K or n_bins); the float32 result.  All kept between calls.
+    psa::DevBuf  d_self_work, d_self_tiles, d_self_ent, d_self_slot, d_self_idx, d_self_groups, d_self_scale, d_self_part,
+                 d_self_acc, d_self_out;
+
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
                                           // plane builds, trajectory uploads (psa_oneoff_stats)
@@ -483,6 +490,27 @@ int launch_lattice_shell(psa_ctx* c, const float2* d_seg, const float* d_khat, c
                          int64_t ns, int64_t g0, int64_t nb, int64_t n_bins, bool currents);
 // out[i] = (float)(acc[i] scale[i mod n_bins]), n elements
 int launch_lattice_finish(psa_ctx* c, const double* d_acc, const double* d_scale, float* d_out, int64_t n, int64_t n_bins);
+// --- self.hip (psa_self_spectra: z[a,n,t] = w_a exp(2 pi i n.s_a(t)) per atom, its power summed over the atoms; the
+// arithmetic and the bound are in its header)
+constexpr int SELF_THREADS = 256;      // lanes of a workgroup: SELF_ATOMS wavefronts, a lane per frame
+constexpr int SELF_ATOMS = 4;          // atoms of an atom tile, one per wavefront: the unit of an atom block
+constexpr int SELF_FRAMES = 64;        // frames of a frame tile: consecutive lanes, consecutive frames
+constexpr int SELF_ENTRIES = 24;       // most distinct (axis, m) pairs of a vector tile: the table is 512 B per atom and entry
+constexpr int SELF_KS = 64;            // most vectors of a vector tile
+// Series of one block: atoms [0, na) of the list d_idx (null: atoms a0 + i) x the vectors of tiles [tile0, tile0 + n_tiles) x
+// segments [s0, s0 + ns) -> work (na, nv, ns, L) complex64, nv the block's vectors, = win[l] w_a E_1 E_2 E_3 at frame
+// s H + l.  d_tile (2 (n_tiles_all + 1)): offsets of every tile into d_ent and into d_slot; v0: the block's first vector.
+// d_weights, d_idx, d_win may be null (unit weights, atoms in order, no window).
+int launch_self_series(psa_ctx* c, const float* d_pos, const float* d_weights, const int* d_idx, int64_t a0, const float* box_hi,
+                       const float* box_lo, const int* d_tile, const unsigned short* d_ent, const unsigned* d_slot, const float* d_win,
+                       float2* d_work, int64_t T, int64_t N, int64_t na, int64_t tile0, int64_t n_tiles, int64_t v0, int64_t nv,
+                       int64_t L, int64_t H, int64_t s0, int64_t ns);
+// After the FFT of work (na, nv, ns, L), the block's vectors being v0 .. v0 + nv - 1 of the processing order: column group
+// g in [g_first, g_first + ng) owns the vectors d_groups[2 g] .. d_groups[2 g + 2] - 1 and the column d_groups[2 g + 1] of
+// acc (L, cols) float64 += sum over its vectors in the block, the atoms and the segments of |Z[o]|^2 (mirror: + |Z[(L - o)
+// mod L]|^2), through n_chunks partial sums over atom chunks, added in order (d_part: n_chunks ng L float64)
+int launch_self_power(psa_ctx* c, const float2* d_work, const int* d_groups, double* d_part, double* d_acc, int64_t L, int64_t ns,
+                      int64_t na, int64_t v0, int64_t nv, int64_t g_first, int64_t ng, int64_t cols, int64_t n_chunks, bool mirror);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 
