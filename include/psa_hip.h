@@ -452,6 +452,10 @@ int psa_sed_modes_welch_fit(psa_ctx* ctx, int slot, const float* mean_pos_all, c
  *     density[o,k]      = 1/(n_seg U) sum_s |F_s[k,0,o]|^2
  *     longitudinal[o,k] = 1/(n_seg U) sum_s |sum_c khat_c F_s[k,c,o]|^2        khat = k/|k| in float64 from the float32 k
  *     transverse[o,k]   = ( 1/(n_seg U) sum_s sum_c |F_s[k,c,o]|^2 - longitudinal[o,k] ) / 2
+ *                       = 1/(2 n_seg U) sum_s sum_c |F_s[k,c,o] - khat_c (khat.F_s[k,.,o])|^2
+ * (the kernels form the transverse part the second way, from the component of F perpendicular to khat: a sum of squares,
+ * never negative, its error relative to sqrt(|F|^2 |F_perp|^2) and not to |F|^2 -- the difference of the first line loses
+ * a transverse part that is small beside the longitudinal one and can come out negative)
  * with the context's segments (psa_set_segments: L, H, win; none set: L = H = T, win = 1); n_seg, U, no detrending,
  * two-sided, FFT order and the unused frames after the last segment exactly as there.  out_host is (1, L, K) float32
  * (density) or, with currents = 1, (3, L, K): density, longitudinal, transverse.  out_bytes exactly its size.
@@ -677,6 +681,34 @@ int psa_debug_lattice_project(psa_ctx* ctx, const double* box_inverse, const int
  * complex64, atoms in the order of the set, vectors in the caller's order */
 int psa_debug_self_series(psa_ctx* ctx, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* idx,
                           int64_t n_g, void* out_host);
+/* The passes that follow the FFT in the three families above, alone, on TRANSFORMED segments the caller uploads (no
+ * projection, no window, no FFT): each entry cuts the call into sub-blocks as its family's run does and goes through the
+ * same host code and the same launches, so what it returns is what the run would make of these segments.  A block
+ * argument of 0 means "all at once".  PSA_EINVAL: a null pointer, a size that is not positive, a negative block, an input
+ * beyond 2^28 elements per sub-block, and what each entry names below.  They use their family's device buffers, which
+ * hold nothing between calls.
+ *   psa_debug_dynamic_power  the power pass of psa_dynamic_spectra (and of the per-vector form of psa_lattice_spectra):
+ *       seg_host (K, NC, n_seg, L) complex64, NC = currents ? 4 : 1; k / |k| is formed from k_vectors as psa_dynamic_spectra
+ *       forms it; out_host (currents ? 3 : 1, L, K) float32 = scale sum_s (density, longitudinal, transverse), the sum over
+ *       the segments of a sub-block in one float32 chain, later sub-blocks added in float32.  Refused: k_vectors not finite.
+ *   psa_debug_lattice_shell  the shell and finish passes of psa_lattice_spectra: the same seg_host with the vectors in the
+ *       processing order, bin_of (K) ascending, khat (K, 3) float32 as given (may be NULL without currents); the scale of bin
+ *       b is 1 / (2 n_b norm), norm = n_seg U L^2 as one double, an empty bin gives zeros; out_host (3 or 1, L, n_bins).
+ *       Refused: bin_of outside [0, n_bins) or descending, norm not positive, khat not finite.
+ *   psa_debug_self_power     the power, reduce and finish passes of psa_self_spectra: work_host (na, nv, n_seg, L)
+ *       complex64; groups (2 (n_groups + 1)) int32: per column group its first vector and its column of the result, the
+ *       last pair (nv, 0) -- a shell per group with mirror = 1, or one vector per group and any permutation of the
+ *       columns with mirror = 0; scale (cols) float64; n_chunks: chunks of a block's atoms, 0 = the rule of the run;
+ *       out_host (L, cols) float32.  Refused: groups that do not tile [0, nv) in ascending order, a column outside
+ *       [0, cols) or used twice, n_chunks above 65535. */
+int psa_debug_dynamic_power(psa_ctx* ctx, const void* seg_host, const float* k_vectors /* (K,3) */, int64_t K, int32_t currents,
+                            int64_t n_seg, int64_t L, int64_t k_block, int64_t seg_block, float scale, float* out_host);
+int psa_debug_lattice_shell(psa_ctx* ctx, const void* seg_host, const float* khat /* (K,3) */, const int32_t* bin_of /* K */,
+                            int64_t K, int64_t n_bins, int32_t currents, int64_t n_seg, int64_t L, int64_t k_block,
+                            int64_t seg_block, double norm, float* out_host);
+int psa_debug_self_power(psa_ctx* ctx, const void* work_host, int64_t na, int64_t nv, int64_t n_seg, int64_t L,
+                         const int32_t* groups, int64_t n_groups, int64_t cols, const double* scale, int32_t mirror,
+                         int64_t n_chunks, int64_t atom_block, int64_t vec_block, int64_t seg_block, float* out_host);
 /* number of plane sets in the cache and their bytes */
 int psa_debug_plane_cache(psa_ctx* ctx, int64_t* n_sets, int64_t* bytes);
 

@@ -122,6 +122,12 @@ SIGNATURES = {
     "psa_self_spectra": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64, _f32p,
                                    C.c_size_t]),
     "psa_debug_self_series": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, C.c_void_p]),
+    "psa_debug_dynamic_power": (C.c_int, [_ctx, C.c_void_p, _f32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                          C.c_float, _f32p]),
+    "psa_debug_lattice_shell": (C.c_int, [_ctx, C.c_void_p, _f32p, _i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                          C.c_int64, C.c_int64, C.c_double, _f32p]),
+    "psa_debug_self_power": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i32p, C.c_int64, C.c_int64,
+                                       C.POINTER(C.c_double), C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _f32p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
@@ -777,6 +783,55 @@ class Engine:
         out = np.empty((N if idx is None else n_g, n.shape[0], T), np.complex64)
         _check(self._lib.psa_debug_self_series(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p),
                                                n.shape[0], ip, n_g, out.ctypes.data_as(C.c_void_p)), "psa_debug_self_series")
+        return out
+
+    def debug_dynamic_power(self, segments, k_vectors, scale: float = 1.0, k_block: int = 0, seg_block: int = 0) -> np.ndarray:
+        """The power pass of `dynamic_spectra` alone (psa_debug_dynamic_power): transformed segments (K, NC, ns, L)
+        complex64 taken as they are, NC = 1 or 4 -> (1 or 3, L, K) float32; `k_block`, `seg_block` > 0: sub-blocks of at
+        most that many vectors and segments, as a budget-bound call is cut."""
+        S = np.ascontiguousarray(segments, np.complex64)
+        kv = _as_f32(np.asarray(k_vectors, np.float32).reshape(-1, 3), (3,))
+        if S.ndim != 4 or S.shape[0] != kv.shape[0] or S.shape[1] not in (1, 4):
+            raise ValueError(f"segments {S.shape} and k_vectors {kv.shape} do not fit (K,1 or 4,ns,L) and (K,3)")
+        K, NC, ns, L = S.shape
+        out = np.empty((3 if NC == 4 else 1, L, K), np.float32)
+        _check(self._lib.psa_debug_dynamic_power(self._h, S.ctypes.data_as(C.c_void_p), _f32(kv), K, 1 if NC == 4 else 0, ns, L,
+                                                 int(k_block), int(seg_block), float(scale), _f32(out)), "psa_debug_dynamic_power")
+        return out
+
+    def debug_lattice_shell(self, segments, khat, bin_of, n_bins: int, norm: float, k_block: int = 0, seg_block: int = 0
+                            ) -> np.ndarray:
+        """The shell and finish passes of `lattice_spectra` alone (psa_debug_lattice_shell): transformed segments
+        (K, NC, ns, L) complex64 of the vectors in processing order, `khat` (K, 3) float32, `bin_of` (K,) ascending ->
+        (1 or 3, L, n_bins) float32 with the bins' scales 1 / (2 n_b norm)."""
+        S = np.ascontiguousarray(segments, np.complex64)
+        kh = _as_f32(np.asarray(khat, np.float32).reshape(-1, 3), (3,))
+        bins = np.ascontiguousarray(bin_of, np.int32).ravel()
+        if S.ndim != 4 or S.shape[0] != kh.shape[0] or S.shape[0] != bins.size or S.shape[1] not in (1, 4):
+            raise ValueError(f"segments {S.shape}, khat {kh.shape} and bin_of {bins.shape} do not fit (K,1 or 4,ns,L), (K,3), (K,)")
+        K, NC, ns, L = S.shape
+        out = np.empty((3 if NC == 4 else 1, L, int(n_bins)), np.float32)
+        _check(self._lib.psa_debug_lattice_shell(self._h, S.ctypes.data_as(C.c_void_p), _f32(kh), bins.ctypes.data_as(_i32p), K,
+                                                 int(n_bins), 1 if NC == 4 else 0, ns, L, int(k_block), int(seg_block), float(norm),
+                                                 _f32(out)), "psa_debug_lattice_shell")
+        return out
+
+    def debug_self_power(self, work, groups, cols: int, scale, mirror: bool, n_chunks: int = 0, atom_block: int = 0,
+                         vec_block: int = 0, seg_block: int = 0) -> np.ndarray:
+        """The power, reduce and finish passes of `self_spectra` alone (psa_debug_self_power): transformed series
+        (na, nv, ns, L) complex64, `groups` (n_groups + 1, 2) int32 = (first vector, column) with the last row (nv, 0),
+        `scale` (cols,) float64 -> (L, cols) float32."""
+        Z = np.ascontiguousarray(work, np.complex64)
+        g = np.ascontiguousarray(groups, np.int32).reshape(-1, 2)
+        sc = np.ascontiguousarray(scale, np.float64).ravel()
+        if Z.ndim != 4 or g.shape[0] < 2 or sc.size != int(cols):
+            raise ValueError(f"work {Z.shape}, groups {g.shape} and scale {sc.shape} do not fit (na,nv,ns,L), (n_groups+1,2), (cols,)")
+        na, nv, ns, L = Z.shape
+        out = np.empty((L, int(cols)), np.float32)
+        _check(self._lib.psa_debug_self_power(self._h, Z.ctypes.data_as(C.c_void_p), na, nv, ns, L, g.ctypes.data_as(_i32p),
+                                              g.shape[0] - 1, int(cols), sc.ctypes.data_as(C.POINTER(C.c_double)), 1 if mirror else 0,
+                                              int(n_chunks), int(atom_block), int(vec_block), int(seg_block), _f32(out)),
+               "psa_debug_self_power")
         return out
 
     def _modes_args(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags):

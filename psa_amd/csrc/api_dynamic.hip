@@ -68,18 +68,42 @@ int dynamic_plan(psa_ctx* c, DynCall* d) {
     return PSA_OK;
 }
 
+int power_block(psa_ctx* c, const PowerPass& p, int64_t k0, int64_t nk, int64_t bk, int64_t bs, const SegFill& fill) {
+    for (int64_t k1 = 0; k1 < nk; k1 += bk) {
+        const int64_t nb = std::min(bk, nk - k1);
+        for (int64_t s0 = 0; s0 < p.n_seg; s0 += bs) {
+            const int64_t ns = std::min(bs, p.n_seg - s0);
+            const float2* d_seg = nullptr;
+            PSA_TRY(fill(k1, nb, s0, ns, &d_seg));
+            StageTimer st(c, PSA_T_EPILOGUE);
+            if (p.d_bins)
+                PSA_TRY(launch_lattice_shell(c, d_seg, p.d_khat + (size_t)(k0 + k1) * 3, p.d_bins, p.d_acc, p.L, ns, k0 + k1, nb, p.n_bins,
+                                             p.NC == 4));
+            else
+                PSA_TRY(launch_dynamic_power(c, d_seg, p.d_khat + (size_t)(k0 + k1) * 3, p.d_out, p.L, ns, nb, p.NC == 4, p.K, k0 + k1,
+                                             p.scale, s0 == 0));
+        }
+    }
+    return PSA_OK;
+}
+
+int upload_segments(psa_ctx* c, DevBuf& b, const void* host, int64_t r0, int64_t nr, int64_t n_seg, int64_t s0, int64_t ns, int64_t L) {
+    // (the launch that read the last upload has ended before its place is written again, and `part` outlives the copy)
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    std::vector<float2> part((size_t)nr * (size_t)ns * (size_t)L);
+    const float2*       S = (const float2*)host;
+    for (int64_t r = 0; r < nr; ++r)
+        std::memcpy(part.data() + (size_t)r * (size_t)ns * (size_t)L, S + ((size_t)(r0 + r) * (size_t)n_seg + (size_t)s0) * (size_t)L,
+                    (size_t)ns * (size_t)L * sizeof(float2));
+    PSA_TRY(upload(c, b, part.data(), part.size() * sizeof(float2)));
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return PSA_OK;
+}
+
 namespace {
 
-// every refusal, the sizes and the block rule
-int dynamic_check(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents, DynCall* d) {
-    PSA_REQUIRE(k_vectors != nullptr, "null k_vectors");
-    PSA_TRY(dynamic_inputs(c, "psa_dynamic_spectra", K, idx, n_g, currents, d));
-    for (int64_t i = 0; i < 3 * K; ++i)
-        PSA_REQUIRE(std::isfinite(k_vectors[i]), "k_vectors[%lld, %lld] is not finite", (long long)(i / 3), (long long)(i % 3));
-    d->slices = dynamic_slices(K);
-    PSA_TRY(dynamic_plan(c, d));
-
-    // kappa = k / 2 pi in float64 from the float32 k, as float32 hi + lo; k / |k| in float64 (k = 0: 0)
+// kappa = k / 2 pi in float64 from the float32 k, as float32 hi + lo; k / |k| in float64 (k = 0: 0)
+void dynamic_directions(const float* k_vectors, int64_t K, DynCall* d) {
     const double two_pi = 6.283185307179586476925286766559;
     d->kappa.resize((size_t)K * 6);
     d->khat.assign((size_t)K * 3, 0.f);
@@ -93,6 +117,18 @@ int dynamic_check(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* 
             if (norm > 0.0) d->khat[(size_t)k * 3 + cc] = (float)((double)k_vectors[3 * k + cc] / norm);
         }
     }
+}
+
+// every refusal, the sizes and the block rule
+int dynamic_check(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents, DynCall* d) {
+    PSA_REQUIRE(k_vectors != nullptr, "null k_vectors");
+    PSA_TRY(dynamic_inputs(c, "psa_dynamic_spectra", K, idx, n_g, currents, d));
+    for (int64_t i = 0; i < 3 * K; ++i)
+        PSA_REQUIRE(std::isfinite(k_vectors[i]), "k_vectors[%lld, %lld] is not finite", (long long)(i / 3), (long long)(i % 3));
+    d->slices = dynamic_slices(K);
+    PSA_TRY(dynamic_plan(c, d));
+
+    dynamic_directions(k_vectors, K, d);
     return PSA_OK;
 }
 
@@ -136,36 +172,25 @@ int dynamic_run(psa_ctx* c, const float* k_vectors, int64_t K, const int32_t* id
     float2*      d_q = c->d_dyn_q.as<float2>();
     float2*      d_seg = d.cut ? c->d_seg.as<float2>() : nullptr;
     float*       d_out = c->d_dyn_out.as<float>();
-    const float* d_khat = c->d_dyn_khat.as<float>();
+    PowerPass    pass;
+    pass.NC = d.NC, pass.L = L, pass.n_seg = d.n_seg, pass.K = K, pass.scale = scale;
+    pass.d_khat = c->d_dyn_khat.as<float>(), pass.d_out = d_out;
     for (int64_t k0 = 0; k0 < K; k0 += d.kb) {
         const int64_t nk = std::min(d.kb, K - k0);
         PSA_TRY(dynamic_project(c, d, idx, k0, nk, d_q));
-        if (!d.cut) {
-            {
-                StageTimer st(c, PSA_T_FFT);
-                PSA_TRY(run_fft(c, d_q, T, (int64_t)d.NC * nk));
-            }
-            StageTimer st(c, PSA_T_EPILOGUE);
-            PSA_TRY(launch_dynamic_power(c, d_q, d_khat + (size_t)k0 * 3, d_out, T, 1, nk, currents != 0, K, k0, scale, true));
-        }
-        for (int64_t k1 = 0; d.cut && k1 < nk; k1 += d.bk) {
-            const int64_t nb = std::min(d.bk, nk - k1);
-            for (int64_t s0 = 0; s0 < d.n_seg; s0 += d.bs) {
-                const int64_t ns = std::min(d.bs, d.n_seg - s0);
-                {
-                    StageTimer st(c, PSA_T_EPILOGUE);
-                    PSA_TRY(launch_segment_window_rows(c, d_q + (size_t)k1 * (size_t)d.NC * (size_t)T, c->d_seg_window.as<float>(), d_seg,
-                                                       T, L, d.H, s0, ns, nb * d.NC));
-                }
-                {
-                    StageTimer st(c, PSA_T_FFT);
-                    PSA_TRY(run_fft(c, d_seg, L, (int64_t)d.NC * nb * ns));
-                }
+        // without segments q is transformed where it lies: one sub-block (bk = kb) of the one segment
+        PSA_TRY(power_block(c, pass, k0, nk, d.bk, d.bs, [&](int64_t k1, int64_t nb, int64_t s0, int64_t ns, const float2** where) -> int {
+            float2* buf = d.cut ? d_seg : d_q;
+            if (d.cut) {
                 StageTimer st(c, PSA_T_EPILOGUE);
-                PSA_TRY(launch_dynamic_power(c, d_seg, d_khat + (size_t)(k0 + k1) * 3, d_out, L, ns, nb, currents != 0, K, k0 + k1,
-                                             scale, s0 == 0));
+                PSA_TRY(launch_segment_window_rows(c, d_q + (size_t)k1 * (size_t)d.NC * (size_t)T, c->d_seg_window.as<float>(), d_seg, T, L,
+                                                   d.H, s0, ns, nb * d.NC));
             }
-        }
+            StageTimer st(c, PSA_T_FFT);
+            PSA_TRY(run_fft(c, buf, L, (int64_t)d.NC * nb * ns));
+            *where = buf;
+            return PSA_OK;
+        }));
     }
     StageTimer st(c, PSA_T_D2H);
     PSA_HIP_CHECK(hipMemcpyAsync(out_host, d_out, want, hipMemcpyDeviceToHost, c->stream));
@@ -195,6 +220,40 @@ int dynamic_debug_project(psa_ctx* c, const float* k_vectors, int64_t K, const i
     return PSA_OK;
 }
 
+// the power pass alone on transformed segments (K, NC, n_seg, L) of the caller's: what dynamic_run does after its FFT,
+// cut into sub-blocks of k_block vectors x seg_block segments (0: all)
+int dynamic_debug_power(psa_ctx* c, const void* seg_host, const float* k_vectors, int64_t K, int32_t currents, int64_t n_seg, int64_t L,
+                        int64_t k_block, int64_t seg_block, float scale, float* out_host) {
+    PSA_REQUIRE(seg_host != nullptr && k_vectors != nullptr && out_host != nullptr, "null argument");
+    PSA_REQUIRE(currents == 0 || currents == 1, "currents is 0 (density only) or 1 (density and currents), got %d", (int)currents);
+    PSA_REQUIRE(K >= 1 && K < (1ll << 29) && n_seg >= 1 && L >= 1 && k_block >= 0 && seg_block >= 0,
+                "K, n_seg and L are positive, k_block and seg_block not negative (%lld, %lld, %lld, %lld, %lld)", (long long)K,
+                (long long)n_seg, (long long)L, (long long)k_block, (long long)seg_block);
+    const int     NC = currents ? 4 : 1;
+    const int64_t bk = k_block == 0 ? K : std::min(k_block, K), bs = seg_block == 0 ? n_seg : std::min(seg_block, n_seg);
+    PSA_REQUIRE((double)bk * NC * (double)bs * (double)L < (double)(1ll << 28) && (double)K * (double)L < (double)(1ll << 28),
+                "a sub-block of %lld x %d x %lld x %lld elements is more than this entry serves", (long long)bk, NC, (long long)bs,
+                (long long)L);
+    for (int64_t i = 0; i < 3 * K; ++i)
+        PSA_REQUIRE(std::isfinite(k_vectors[i]), "k_vectors[%lld, %lld] is not finite", (long long)(i / 3), (long long)(i % 3));
+    DynCall d;
+    dynamic_directions(k_vectors, K, &d);
+    const size_t want = (size_t)(currents ? 3 : 1) * (size_t)L * (size_t)K * sizeof(float);
+    PSA_TRY(upload(c, c->d_dyn_khat, d.khat.data(), d.khat.size() * sizeof(float)));
+    PSA_TRY(c->d_dyn_out.reserve(want));
+    PowerPass pass;
+    pass.NC = NC, pass.L = L, pass.n_seg = n_seg, pass.K = K, pass.scale = scale;
+    pass.d_khat = c->d_dyn_khat.as<float>(), pass.d_out = c->d_dyn_out.as<float>();
+    PSA_TRY(power_block(c, pass, 0, K, bk, bs, [&](int64_t k1, int64_t nb, int64_t s0, int64_t ns, const float2** where) -> int {
+        PSA_TRY(upload_segments(c, c->d_dyn_q, seg_host, k1 * NC, nb * NC, n_seg, s0, ns, L));
+        *where = c->d_dyn_q.as<float2>();
+        return PSA_OK;
+    }));
+    PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_dyn_out.ptr, want, hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return PSA_OK;
+}
+
 }  // namespace
 
 }  // namespace psa
@@ -215,6 +274,14 @@ int psa_debug_dynamic_project(psa_ctx* c, const float* k_vectors, int64_t K, con
     PSA_TRY(enter(c));
     Guard guard(c);
     return synchronised(c, dynamic_debug_project(c, k_vectors, K, idx, n_g, currents, out_host), "psa_debug_dynamic_project");
+}
+
+int psa_debug_dynamic_power(psa_ctx* c, const void* seg_host, const float* k_vectors, int64_t K, int32_t currents, int64_t n_seg, int64_t L,
+                            int64_t k_block, int64_t seg_block, float scale, float* out_host) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    return synchronised(c, dynamic_debug_power(c, seg_host, k_vectors, K, currents, n_seg, L, k_block, seg_block, scale, out_host),
+                        "psa_debug_dynamic_power");
 }
 
 int psa_debug_dynamic_sincos(psa_ctx* c, const float* turns, int64_t n, float* out_host) {

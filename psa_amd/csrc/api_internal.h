@@ -231,6 +231,25 @@ struct DynCall {
 };
 int dynamic_inputs(psa_ctx* c, const char* entry, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents, DynCall* d);
 int dynamic_plan(psa_ctx* c, DynCall* d);
+// The power part of a dynamic or lattice call, shared by the run and by the debug entries (psa_debug_dynamic_power,
+// psa_debug_lattice_shell), which differ only in where the transformed segments come from.  PowerPass: what every launch of
+// the pass gets; d_bins set: the shell pass into d_acc, else dynamic.hip's power pass into d_out.  power_block: vectors
+// [k0, k0 + nk) of the processing order in sub-blocks of bk vectors x bs segments; `fill` leaves the transformed segments
+// (nb, NC, ns, L) of vectors k0 + k1 .. and segments s0 .. on the device and says where.
+struct PowerPass {
+    int          NC = 1;
+    int64_t      L = 0, n_seg = 0, K = 0;
+    float        scale = 0.f;
+    const float* d_khat = nullptr;       // (K, 3), row 0 = vector 0 of the processing order
+    float*       d_out = nullptr;
+    const int*   d_bins = nullptr;
+    double*      d_acc = nullptr;
+    int64_t      n_bins = 0;
+};
+using SegFill = std::function<int(int64_t k1, int64_t nb, int64_t s0, int64_t ns, const float2** d_seg)>;
+int  power_block(psa_ctx* c, const PowerPass& p, int64_t k0, int64_t nk, int64_t bk, int64_t bs, const SegFill& fill);
+// rows [r0, r0 + nr) x segments [s0, s0 + ns) of host segments (rows, n_seg, L), packed as (nr, ns, L) and uploaded to b
+int  upload_segments(psa_ctx* c, DevBuf& b, const void* host, int64_t r0, int64_t nr, int64_t n_seg, int64_t s0, int64_t ns, int64_t L);
 // api_lattice.hip: what psa_lattice_spectra shares with psa_self_spectra (api_self.hip): the refusals that concern the box
 // and the vector list; Hinv as float32 hi + lo; the processing order (bin_of: by (bin, n); else every run of kb vectors by n);
 // one tile's entry list (appended to ent) and per vector the three entries it reads -- returns the tile's R
@@ -238,6 +257,10 @@ int  lattice_inputs(const double* box_inverse, const int32_t* indices, int64_t K
 void lattice_box_parts(const double* B, float* hi, float* lo);
 void lattice_order(const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t kb, std::vector<int64_t>* order);
 int  lattice_tile_entries(const int32_t* indices, const int64_t* members, int64_t nt, std::vector<uint16_t>* ent, uint32_t* slot);
+// where each bin's vectors begin in an order sorted by bin (n_bins + 1) and the bins' scales 1 / (2 n_half n_seg U L^2), an
+// empty bin: 0 (count: vectors per bin)
+void lattice_bins(const std::vector<int64_t>& count, double n_seg, double U, double L, std::vector<int32_t>* bin_start,
+                  std::vector<double>* scale);
 int    check_weights(psa_ctx* c, int64_t N);            // the context's atom weights fit a slot of N atoms
 void   set_geom_weights(const psa_ctx* c, ProjGeom* g);  // ... and go into a launch's geometry
 int    begin_result(psa_ctx* c, int64_t T, int64_t K_total, int64_t k_offset, bool intensity, char** rows);

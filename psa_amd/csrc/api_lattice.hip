@@ -91,6 +91,17 @@ int lattice_tile_entries(const int32_t* indices, const int64_t* members, int64_t
     return R;
 }
 
+void lattice_bins(const std::vector<int64_t>& count, double n_seg, double U, double L, std::vector<int32_t>* bin_start,
+                  std::vector<double>* scale) {
+    const size_t n_bins = count.size();
+    bin_start->assign(n_bins + 1, 0);
+    scale->assign(n_bins, 0.0);
+    for (size_t b = 0; b < n_bins; ++b) {
+        (*bin_start)[b + 1] = (int32_t)((*bin_start)[b] + count[b]);
+        if (count[b]) (*scale)[b] = 1.0 / (2.0 * (double)count[b] * n_seg * U * L * L);
+    }
+}
+
 namespace {
 
 struct LatCall {
@@ -158,13 +169,7 @@ int lattice_check(psa_ctx* c, const double* box_inverse, const int32_t* indices,
     if (p->shell) {
         std::vector<int64_t> count((size_t)n_bins, 0);
         for (int64_t k = 0; k < K; ++k) ++count[(size_t)bin_of[k]];
-        p->bin_start.assign((size_t)n_bins + 1, 0);
-        p->scale.assign((size_t)n_bins, 0.0);
-        const double U = d.cut ? c->seg_U : 1.0;
-        for (int64_t b = 0; b < n_bins; ++b) {
-            p->bin_start[(size_t)b + 1] = (int32_t)(p->bin_start[(size_t)b] + count[(size_t)b]);
-            if (count[(size_t)b]) p->scale[(size_t)b] = 1.0 / (2.0 * (double)count[(size_t)b] * (double)d.n_seg * U * (double)d.L * (double)d.L);
-        }
+        lattice_bins(count, (double)d.n_seg, d.cut ? c->seg_U : 1.0, (double)d.L, &p->bin_start, &p->scale);
     }
     return PSA_OK;
 }
@@ -182,6 +187,18 @@ int lattice_upload(psa_ctx* c, const LatCall& p, const int32_t* idx) {
         PSA_TRY(upload(c, c->d_lat_scale, p.scale.data(), p.scale.size() * sizeof(double)));
     }
     return PSA_OK;
+}
+
+// the shell form's float64 accumulator, zeroed; and its last launch: scale in float64, one rounding into d_out
+int lattice_shell_begin(psa_ctx* c, size_t bytes, double** d_acc) {
+    PSA_TRY(c->d_lat_acc.reserve(bytes));
+    *d_acc = c->d_lat_acc.as<double>();
+    PSA_HIP_CHECK(hipMemsetAsync(*d_acc, 0, bytes, c->stream));
+    return PSA_OK;
+}
+int lattice_shell_finish(psa_ctx* c, int64_t rows, int64_t L, int64_t n_bins, float* d_out) {
+    StageTimer st(c, PSA_T_EPILOGUE);
+    return launch_lattice_finish(c, c->d_lat_acc.as<double>(), c->d_lat_scale.as<double>(), d_out, rows * L * n_bins, n_bins);
 }
 
 // block b of the plan over all frames into d_q (nk, NC, T)
@@ -215,59 +232,36 @@ int lattice_run(psa_ctx* c, const double* box_inverse, const int32_t* indices, i
     if (d.cut) PSA_TRY(c->d_seg.reserve((size_t)d.bk * (size_t)d.bs * (size_t)d.unit));
     PSA_TRY(c->d_lat_out.reserve(want));
     double* d_acc = nullptr;
-    if (p.shell) {
-        PSA_TRY(c->d_lat_acc.reserve(want * 2));
-        d_acc = c->d_lat_acc.as<double>();
-        PSA_HIP_CHECK(hipMemsetAsync(d_acc, 0, want * 2, c->stream));
-    }
+    if (p.shell) PSA_TRY(lattice_shell_begin(c, want * 2, &d_acc));
 
     const double U = d.cut ? c->seg_U : 1.0;
     const float  scale = (float)(1.0 / ((double)L * (double)L * (double)d.n_seg * U));
     float2*      d_q = c->d_lat_q.as<float2>();
     float2*      d_seg = d.cut ? c->d_seg.as<float2>() : nullptr;
     float*       d_out = c->d_lat_out.as<float>();
-    const float* d_khat = c->d_lat_khat.as<float>();
-    const int*   d_bins = p.shell ? c->d_lat_bins.as<int>() : nullptr;
+    PowerPass    pass;
+    pass.NC = d.NC, pass.L = L, pass.n_seg = d.n_seg, pass.K = K, pass.scale = scale;
+    pass.d_khat = c->d_lat_khat.as<float>(), pass.d_out = d_out;
+    if (p.shell) pass.d_bins = c->d_lat_bins.as<int>(), pass.d_acc = d_acc, pass.n_bins = n_bins;
     int64_t      block = 0;
     for (int64_t k0 = 0; k0 < K; k0 += d.kb, ++block) {
         const int64_t nk = std::min(d.kb, K - k0);
         PSA_TRY(lattice_project(c, p, idx, block, d_q));
-        if (!d.cut) {
-            {
-                StageTimer st(c, PSA_T_FFT);
-                PSA_TRY(run_fft(c, d_q, T, (int64_t)d.NC * nk));
-            }
-            StageTimer st(c, PSA_T_EPILOGUE);
-            if (p.shell) PSA_TRY(launch_lattice_shell(c, d_q, d_khat + (size_t)k0 * 3, d_bins, d_acc, T, 1, k0, nk, n_bins, currents != 0));
-            else PSA_TRY(launch_dynamic_power(c, d_q, d_khat + (size_t)k0 * 3, d_out, T, 1, nk, currents != 0, K, k0, scale, true));
-        }
-        for (int64_t k1 = 0; d.cut && k1 < nk; k1 += d.bk) {
-            const int64_t nb = std::min(d.bk, nk - k1);
-            for (int64_t s0 = 0; s0 < d.n_seg; s0 += d.bs) {
-                const int64_t ns = std::min(d.bs, d.n_seg - s0);
-                {
-                    StageTimer st(c, PSA_T_EPILOGUE);
-                    PSA_TRY(launch_segment_window_rows(c, d_q + (size_t)k1 * (size_t)d.NC * (size_t)T, c->d_seg_window.as<float>(), d_seg,
-                                                       T, L, d.H, s0, ns, nb * d.NC));
-                }
-                {
-                    StageTimer st(c, PSA_T_FFT);
-                    PSA_TRY(run_fft(c, d_seg, L, (int64_t)d.NC * nb * ns));
-                }
+        // without segments q is transformed where it lies: one sub-block (bk = kb) of the one segment
+        PSA_TRY(power_block(c, pass, k0, nk, d.bk, d.bs, [&](int64_t k1, int64_t nb, int64_t s0, int64_t ns, const float2** where) -> int {
+            float2* buf = d.cut ? d_seg : d_q;
+            if (d.cut) {
                 StageTimer st(c, PSA_T_EPILOGUE);
-                if (p.shell)
-                    PSA_TRY(launch_lattice_shell(c, d_seg, d_khat + (size_t)(k0 + k1) * 3, d_bins, d_acc, L, ns, k0 + k1, nb, n_bins,
-                                                 currents != 0));
-                else
-                    PSA_TRY(launch_dynamic_power(c, d_seg, d_khat + (size_t)(k0 + k1) * 3, d_out, L, ns, nb, currents != 0, K, k0 + k1,
-                                                 scale, s0 == 0));
+                PSA_TRY(launch_segment_window_rows(c, d_q + (size_t)k1 * (size_t)d.NC * (size_t)T, c->d_seg_window.as<float>(), d_seg, T, L,
+                                                   d.H, s0, ns, nb * d.NC));
             }
-        }
+            StageTimer st(c, PSA_T_FFT);
+            PSA_TRY(run_fft(c, buf, L, (int64_t)d.NC * nb * ns));
+            *where = buf;
+            return PSA_OK;
+        }));
     }
-    if (p.shell) {
-        StageTimer st(c, PSA_T_EPILOGUE);
-        PSA_TRY(launch_lattice_finish(c, d_acc, c->d_lat_scale.as<double>(), d_out, rows * L * n_bins, n_bins));
-    }
+    if (p.shell) PSA_TRY(lattice_shell_finish(c, rows, L, n_bins, d_out));
     StageTimer st(c, PSA_T_D2H);
     PSA_HIP_CHECK(hipMemcpyAsync(out_host, d_out, want, hipMemcpyDeviceToHost, c->stream));
     PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -298,6 +292,58 @@ int lattice_debug_project(psa_ctx* c, const double* box_inverse, const int32_t* 
     return PSA_OK;
 }
 
+// the shell pass and the finish pass alone on transformed segments (K, NC, n_seg, L) of the caller's, the vectors in the
+// processing order (sorted by bin): what lattice_run does after its FFT in the shell form, cut into sub-blocks of k_block
+// vectors x seg_block segments (0: all); norm = n_seg U L^2 of the bins' scales
+int lattice_debug_shell(psa_ctx* c, const void* seg_host, const float* khat, const int32_t* bin_of, int64_t K, int64_t n_bins,
+                        int32_t currents, int64_t n_seg, int64_t L, int64_t k_block, int64_t seg_block, double norm, float* out_host) {
+    PSA_REQUIRE(seg_host != nullptr && bin_of != nullptr && out_host != nullptr && (khat != nullptr || !currents), "null argument");
+    PSA_REQUIRE(currents == 0 || currents == 1, "currents is 0 (density only) or 1 (density and currents), got %d", (int)currents);
+    PSA_REQUIRE(K >= 1 && K < (1ll << 29) && n_seg >= 1 && L >= 1 && k_block >= 0 && seg_block >= 0,
+                "K, n_seg and L are positive, k_block and seg_block not negative (%lld, %lld, %lld, %lld, %lld)", (long long)K,
+                (long long)n_seg, (long long)L, (long long)k_block, (long long)seg_block);
+    PSA_REQUIRE(n_bins >= 1 && n_bins < (1ll << 24), "need at least one bin (n_bins = %lld)", (long long)n_bins);
+    PSA_REQUIRE(std::isfinite(norm) && norm > 0.0, "the norm n_seg U L^2 must be positive");
+    const int     NC = currents ? 4 : 1;
+    const int64_t rows = currents ? 3 : 1, bk = k_block == 0 ? K : std::min(k_block, K), bs = seg_block == 0 ? n_seg : std::min(seg_block, n_seg);
+    PSA_REQUIRE((double)bk * NC * (double)bs * (double)L < (double)(1ll << 28) && (double)n_bins * (double)L < (double)(1ll << 28),
+                "a sub-block of %lld x %d x %lld x %lld elements is more than this entry serves", (long long)bk, NC, (long long)bs,
+                (long long)L);
+    std::vector<int64_t> count((size_t)n_bins, 0);
+    for (int64_t k = 0; k < K; ++k) {
+        PSA_REQUIRE(bin_of[k] >= 0 && bin_of[k] < n_bins, "bin_of[%lld] = %d is outside [0, %lld)", (long long)k, (int)bin_of[k],
+                    (long long)n_bins);
+        PSA_REQUIRE(k == 0 || bin_of[k - 1] <= bin_of[k], "bin_of[%lld] = %d after %d: the vectors come sorted by bin", (long long)k,
+                    (int)bin_of[k], (int)bin_of[k - 1]);
+        ++count[(size_t)bin_of[k]];
+    }
+    for (int64_t i = 0; currents && i < 3 * K; ++i) PSA_REQUIRE(std::isfinite(khat[i]), "khat[%lld] is not finite", (long long)i);
+    std::vector<int32_t> bin_start;
+    std::vector<double>  scale;
+    lattice_bins(count, norm, 1.0, 1.0, &bin_start, &scale);
+    const std::vector<float> zeros((size_t)K * 3, 0.f);
+    PSA_TRY(upload(c, c->d_lat_khat, currents ? khat : zeros.data(), (size_t)K * 3 * sizeof(float)));
+    PSA_TRY(upload(c, c->d_lat_bins, bin_start.data(), bin_start.size() * sizeof(int32_t)));
+    PSA_TRY(upload(c, c->d_lat_scale, scale.data(), scale.size() * sizeof(double)));
+    const size_t want = (size_t)rows * (size_t)L * (size_t)n_bins * sizeof(float);
+    PSA_TRY(c->d_lat_out.reserve(want));
+    double* d_acc = nullptr;
+    PSA_TRY(lattice_shell_begin(c, want * 2, &d_acc));
+    PowerPass pass;
+    pass.NC = NC, pass.L = L, pass.n_seg = n_seg, pass.K = K;
+    pass.d_khat = c->d_lat_khat.as<float>(), pass.d_out = c->d_lat_out.as<float>();
+    pass.d_bins = c->d_lat_bins.as<int>(), pass.d_acc = d_acc, pass.n_bins = n_bins;
+    PSA_TRY(power_block(c, pass, 0, K, bk, bs, [&](int64_t k1, int64_t nb, int64_t s0, int64_t ns, const float2** where) -> int {
+        PSA_TRY(upload_segments(c, c->d_lat_q, seg_host, k1 * NC, nb * NC, n_seg, s0, ns, L));
+        *where = c->d_lat_q.as<float2>();
+        return PSA_OK;
+    }));
+    PSA_TRY(lattice_shell_finish(c, rows, L, n_bins, pass.d_out));
+    PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_lat_out.ptr, want, hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return PSA_OK;
+}
+
 }  // namespace
 
 }  // namespace psa
@@ -312,6 +358,14 @@ int psa_lattice_spectra(psa_ctx* c, const double* box_inverse, const int32_t* in
     Guard guard(c);
     return synchronised(c, lattice_run(c, box_inverse, indices, K, bin_of, n_bins, idx, n_g, currents, out_host, out_bytes),
                         "psa_lattice_spectra");
+}
+
+int psa_debug_lattice_shell(psa_ctx* c, const void* seg_host, const float* khat, const int32_t* bin_of, int64_t K, int64_t n_bins,
+                            int32_t currents, int64_t n_seg, int64_t L, int64_t k_block, int64_t seg_block, double norm, float* out_host) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    return synchronised(c, lattice_debug_shell(c, seg_host, khat, bin_of, K, n_bins, currents, n_seg, L, k_block, seg_block, norm, out_host),
+                        "psa_debug_lattice_shell");
 }
 
 int psa_debug_lattice_project(psa_ctx* c, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* idx, int64_t n_g,

@@ -143,6 +143,59 @@ int self_series(psa_ctx* c, const SelfCall& p, const int32_t* idx, int64_t a0, i
                               p.cut ? c->d_seg_window.as<float>() : nullptr, d_work, p.d.T, p.d.N, na, t0, nt, v0, nv, p.L, p.H, s0, ns);
 }
 
+// The power part of a self call, shared by self_run and psa_debug_self_power, which differ only in where the transformed
+// series come from: the float64 accumulator (L, cols), zeroed; per block of Ab atoms x the vectors [vcut[b], vcut[b + 1]) of
+// the processing order x bs segments the columns the block touches, the chunk rule, the power and reduce launches; the
+// finish pass into d_self_out.  The groups table (2 (n_groups + 1)) and the columns' scales are on the device already.
+// `fill` leaves the transformed block (na, nv, ns, L) on the device and says where.
+struct SelfPower {
+    int64_t        L = 0, n_seg = 0, n_atoms = 0, cols = 0, n_groups = 0;
+    const int32_t* groups = nullptr;                 // the host's copy
+    bool           mirror = false;
+    int64_t        Ab = 0, bs = 0, n_chunks = 0;     // atoms and segments per block; chunks of a block's atoms (0: the rule)
+    const std::vector<int64_t>* vcut = nullptr;
+};
+using SelfFill = std::function<int(int64_t a0, int64_t na, int64_t vb, int64_t s0, int64_t ns, const float2** d_work)>;
+
+int self_power_run(psa_ctx* c, const SelfPower& w, const SelfFill& fill) {
+    const int64_t L = w.L, cols = w.cols;
+    const size_t  want = (size_t)L * (size_t)cols * sizeof(float);
+    PSA_TRY(c->d_self_acc.reserve(want * 2));
+    PSA_TRY(c->d_self_out.reserve(want));
+    double* d_acc = c->d_self_acc.as<double>();
+    PSA_HIP_CHECK(hipMemsetAsync(d_acc, 0, want * 2, c->stream));
+
+    const int*     d_groups = c->d_self_groups.as<int>();
+    const int64_t  n_ot = std::min<int64_t>((L + 255) / 256, 1 << 12);
+    std::vector<int32_t> starts((size_t)w.n_groups + 1);
+    for (int64_t g = 0; g <= w.n_groups; ++g) starts[(size_t)g] = w.groups[(size_t)(2 * g)];
+    for (int64_t a0 = 0; a0 < w.n_atoms; a0 += w.Ab) {
+        const int64_t na = std::min(w.Ab, w.n_atoms - a0);
+        for (size_t vb = 0; vb + 1 < w.vcut->size(); ++vb) {
+            const int64_t v0 = (*w.vcut)[vb], nv = (*w.vcut)[vb + 1] - v0;
+            // the columns with vectors in [v0, v0 + nv)
+            const int64_t g_first = (std::upper_bound(starts.begin(), starts.end(), (int32_t)v0) - starts.begin()) - 1;
+            const int64_t g_end = std::min<int64_t>(w.n_groups, std::lower_bound(starts.begin(), starts.end(), (int32_t)(v0 + nv)) - starts.begin());
+            const int64_t ng = g_end - g_first;
+            // enough workgroups for the power pass whatever L and the number of columns: the block's atoms are split into
+            // chunks whose float64 partial sums are added in order
+            const int64_t n_chunks = w.n_chunks ? w.n_chunks
+                                                : std::max<int64_t>(1, std::min<int64_t>({64, (2048 + n_ot * ng - 1) / (n_ot * ng), na}));
+            PSA_TRY(c->d_self_part.reserve((size_t)n_chunks * (size_t)ng * (size_t)L * sizeof(double)));
+            for (int64_t s0 = 0; s0 < w.n_seg; s0 += w.bs) {
+                const int64_t ns = std::min(w.bs, w.n_seg - s0);
+                const float2* d_work = nullptr;
+                PSA_TRY(fill(a0, na, (int64_t)vb, s0, ns, &d_work));
+                StageTimer st(c, PSA_T_EPILOGUE);
+                PSA_TRY(launch_self_power(c, d_work, d_groups, c->d_self_part.as<double>(), d_acc, L, ns, na, v0, nv, g_first, ng, cols,
+                                          n_chunks, w.mirror));
+            }
+        }
+    }
+    StageTimer st(c, PSA_T_EPILOGUE);
+    return launch_lattice_finish(c, d_acc, c->d_self_scale.as<double>(), c->d_self_out.as<float>(), L * cols, cols);
+}
+
 int self_run(psa_ctx* c, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t n_bins,
              const int32_t* idx, int64_t n_g, float* out_host, size_t out_bytes) {
     PSA_REQUIRE(out_host != nullptr, "null output");
@@ -159,46 +212,22 @@ int self_run(psa_ctx* c, const double* box_inverse, const int32_t* indices, int6
     PSA_TRY(self_upload(c, p, idx, true));
     const int64_t Ab = p.at * SELF_ATOMS, nv_max = std::min(K, p.vt * p.kt_max);
     PSA_TRY(c->d_self_work.reserve((size_t)std::min(Ab, p.d.n_g) * (size_t)nv_max * (size_t)p.bs * (size_t)L * sizeof(float2)));
-    PSA_TRY(c->d_self_acc.reserve(want * 2));
-    PSA_TRY(c->d_self_out.reserve(want));
-    double* d_acc = c->d_self_acc.as<double>();
-    PSA_HIP_CHECK(hipMemsetAsync(d_acc, 0, want * 2, c->stream));
-
-    float2*        d_work = c->d_self_work.as<float2>();
-    const int*     d_groups = c->d_self_groups.as<int>();
-    const int64_t  n_ot = std::min<int64_t>((L + 255) / 256, 1 << 12);
-    std::vector<int32_t> starts((size_t)p.n_groups + 1);
-    for (int64_t g = 0; g <= p.n_groups; ++g) starts[(size_t)g] = p.groups[(size_t)(2 * g)];
-    for (int64_t a0 = 0; a0 < p.d.n_g; a0 += Ab) {
-        const int64_t na = std::min(Ab, p.d.n_g - a0);
-        for (int64_t t0 = 0; t0 < p.n_tiles; t0 += p.vt) {
-            const int64_t nt = std::min(p.vt, p.n_tiles - t0);
-            const int64_t v0 = p.tile[(size_t)(2 * t0 + 1)], nv = p.tile[(size_t)(2 * (t0 + nt) + 1)] - v0;
-            // the columns with vectors in [v0, v0 + nv)
-            const int64_t g_first = (std::upper_bound(starts.begin(), starts.end(), (int32_t)v0) - starts.begin()) - 1;
-            const int64_t g_end = std::min<int64_t>(p.n_groups, std::lower_bound(starts.begin(), starts.end(), (int32_t)(v0 + nv)) - starts.begin());
-            const int64_t ng = g_end - g_first;
-            // enough workgroups for the power pass whatever L and the number of columns: the block's atoms are split into
-            // chunks whose float64 partial sums are added in order
-            const int64_t n_chunks = std::max<int64_t>(1, std::min<int64_t>({64, (2048 + n_ot * ng - 1) / (n_ot * ng), na}));
-            PSA_TRY(c->d_self_part.reserve((size_t)n_chunks * (size_t)ng * (size_t)L * sizeof(double)));
-            for (int64_t s0 = 0; s0 < p.n_seg; s0 += p.bs) {
-                const int64_t ns = std::min(p.bs, p.n_seg - s0);
-                PSA_TRY(self_series(c, p, idx, a0, na, t0, nt, s0, ns, d_work));
-                {
-                    StageTimer st(c, PSA_T_FFT);
-                    PSA_TRY(run_fft(c, d_work, L, na * nv * ns));
-                }
-                StageTimer st(c, PSA_T_EPILOGUE);
-                PSA_TRY(launch_self_power(c, d_work, d_groups, c->d_self_part.as<double>(), d_acc, L, ns, na, v0, nv, g_first, ng, cols,
-                                          n_chunks, p.shell));
-            }
-        }
-    }
-    {
-        StageTimer st(c, PSA_T_EPILOGUE);
-        PSA_TRY(launch_lattice_finish(c, d_acc, c->d_self_scale.as<double>(), c->d_self_out.as<float>(), L * cols, cols));
-    }
+    float2* d_work = c->d_self_work.as<float2>();
+    // a vector block is a run of vt tiles
+    std::vector<int64_t> vcut;
+    for (int64_t t0 = 0; t0 < p.n_tiles; t0 += p.vt) vcut.push_back(p.tile[(size_t)(2 * t0 + 1)]);
+    vcut.push_back(K);
+    SelfPower w;
+    w.L = L, w.n_seg = p.n_seg, w.n_atoms = p.d.n_g, w.cols = cols, w.n_groups = p.n_groups, w.groups = p.groups.data();
+    w.mirror = p.shell, w.Ab = Ab, w.bs = p.bs, w.vcut = &vcut;
+    PSA_TRY(self_power_run(c, w, [&](int64_t a0, int64_t na, int64_t vb, int64_t s0, int64_t ns, const float2** where) -> int {
+        const int64_t t0 = vb * p.vt, nt = std::min(p.vt, p.n_tiles - t0);
+        PSA_TRY(self_series(c, p, idx, a0, na, t0, nt, s0, ns, d_work));
+        StageTimer st(c, PSA_T_FFT);
+        PSA_TRY(run_fft(c, d_work, L, na * (vcut[(size_t)vb + 1] - vcut[(size_t)vb]) * ns));
+        *where = d_work;
+        return PSA_OK;
+    }));
     StageTimer st(c, PSA_T_D2H);
     PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_self_out.ptr, want, hipMemcpyDeviceToHost, c->stream));
     PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -236,6 +265,68 @@ int self_debug_series(psa_ctx* c, const double* box_inverse, const int32_t* indi
     return PSA_OK;
 }
 
+// the power, reduce and finish passes alone on transformed series work (na, nv, n_seg, L) of the caller's, the vectors in
+// the processing order: what self_run does after its FFT, with the caller's groups table and scales, cut into blocks of
+// atom_block atoms x vec_block vectors x seg_block segments (0: all)
+int self_debug_power(psa_ctx* c, const void* work_host, int64_t na, int64_t nv, int64_t n_seg, int64_t L, const int32_t* groups,
+                     int64_t n_groups, int64_t cols, const double* scale, int32_t mirror, int64_t n_chunks, int64_t atom_block,
+                     int64_t vec_block, int64_t seg_block, float* out_host) {
+    PSA_REQUIRE(work_host != nullptr && groups != nullptr && scale != nullptr && out_host != nullptr, "null argument");
+    PSA_REQUIRE(na >= 1 && na < (1ll << 31) && nv >= 1 && nv < (1ll << 30) && n_seg >= 1 && L >= 1 && n_groups >= 1 && cols >= 1,
+                "na, nv, n_seg, L, n_groups and cols are positive (%lld, %lld, %lld, %lld, %lld, %lld)", (long long)na, (long long)nv,
+                (long long)n_seg, (long long)L, (long long)n_groups, (long long)cols);
+    PSA_REQUIRE(mirror == 0 || mirror == 1, "mirror is 0 or 1, got %d", (int)mirror);
+    PSA_REQUIRE(n_chunks >= 0 && n_chunks <= 65535 && atom_block >= 0 && vec_block >= 0 && seg_block >= 0,
+                "n_chunks in [0, 65535], the blocks not negative");
+    PSA_REQUIRE(n_groups <= nv + cols && (double)cols * (double)L < (double)(1ll << 28), "too many groups or columns");
+    // the groups tile [0, nv): first vectors ascending from 0, the end entry nv; every column inside the result and used once
+    PSA_REQUIRE(groups[0] == 0 && groups[2 * n_groups] == nv, "the groups do not tile [0, %lld): they run from %d to %d", (long long)nv,
+                (int)groups[0], (int)groups[2 * n_groups]);
+    std::vector<char> seen((size_t)cols, 0);
+    for (int64_t g = 0; g < n_groups; ++g) {
+        PSA_REQUIRE(groups[2 * g] <= groups[2 * g + 2], "the groups do not tile [0, %lld): group %lld begins at %d, the next at %d",
+                    (long long)nv, (long long)g, (int)groups[2 * g], (int)groups[2 * g + 2]);
+        const int32_t col = groups[2 * g + 1];
+        PSA_REQUIRE(col >= 0 && col < cols && !seen[(size_t)col], "group %lld: column %d is outside [0, %lld) or used twice", (long long)g,
+                    (int)col, (long long)cols);
+        seen[(size_t)col] = 1;
+    }
+    for (int64_t i = 0; i < cols; ++i) PSA_REQUIRE(std::isfinite(scale[i]), "scale[%lld] is not finite", (long long)i);
+    const int64_t Ab = atom_block == 0 ? na : std::min(atom_block, na), bv = vec_block == 0 ? nv : std::min(vec_block, nv),
+                  bs = seg_block == 0 ? n_seg : std::min(seg_block, n_seg);
+    PSA_REQUIRE((double)Ab * (double)bv * (double)bs * (double)L < (double)(1ll << 28),
+                "a block of %lld x %lld x %lld x %lld elements is more than this entry serves", (long long)Ab, (long long)bv, (long long)bs,
+                (long long)L);
+    PSA_TRY(upload(c, c->d_self_groups, groups, (size_t)(2 * (n_groups + 1)) * sizeof(int32_t)));
+    PSA_TRY(upload(c, c->d_self_scale, scale, (size_t)cols * sizeof(double)));
+    std::vector<int64_t> vcut;
+    for (int64_t v0 = 0; v0 < nv; v0 += bv) vcut.push_back(v0);
+    vcut.push_back(nv);
+    SelfPower w;
+    w.L = L, w.n_seg = n_seg, w.n_atoms = na, w.cols = cols, w.n_groups = n_groups, w.groups = groups;
+    w.mirror = mirror != 0, w.Ab = Ab, w.bs = bs, w.n_chunks = n_chunks, w.vcut = &vcut;
+    std::vector<float2> part;
+    const float2*       S = (const float2*)work_host;
+    PSA_TRY(self_power_run(c, w, [&](int64_t a0, int64_t nab, int64_t vb, int64_t s0, int64_t ns, const float2** where) -> int {
+        const int64_t v0 = vcut[(size_t)vb], nvb = vcut[(size_t)vb + 1] - v0;
+        PSA_HIP_CHECK(hipStreamSynchronize(c->stream));     // the launches that read the last block have ended
+        part.resize((size_t)nab * (size_t)nvb * (size_t)ns * (size_t)L);
+        for (int64_t a = 0; a < nab; ++a)
+            for (int64_t v = 0; v < nvb; ++v)
+                std::memcpy(part.data() + ((size_t)a * (size_t)nvb + (size_t)v) * (size_t)ns * (size_t)L,
+                            S + (((size_t)(a0 + a) * (size_t)nv + (size_t)(v0 + v)) * (size_t)n_seg + (size_t)s0) * (size_t)L,
+                            (size_t)ns * (size_t)L * sizeof(float2));
+        PSA_TRY(upload(c, c->d_self_work, part.data(), part.size() * sizeof(float2)));
+        PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+        *where = c->d_self_work.as<float2>();
+        return PSA_OK;
+    }));
+    const size_t want = (size_t)L * (size_t)cols * sizeof(float);
+    PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_self_out.ptr, want, hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return PSA_OK;
+}
+
 }  // namespace
 
 }  // namespace psa
@@ -249,6 +340,16 @@ int psa_self_spectra(psa_ctx* c, const double* box_inverse, const int32_t* indic
     PSA_TRY(enter(c));
     Guard guard(c);
     return synchronised(c, self_run(c, box_inverse, indices, K, bin_of, n_bins, idx, n_g, out_host, out_bytes), "psa_self_spectra");
+}
+
+int psa_debug_self_power(psa_ctx* c, const void* work_host, int64_t na, int64_t nv, int64_t n_seg, int64_t L, const int32_t* groups,
+                         int64_t n_groups, int64_t cols, const double* scale, int32_t mirror, int64_t n_chunks, int64_t atom_block,
+                         int64_t vec_block, int64_t seg_block, float* out_host) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    return synchronised(c, self_debug_power(c, work_host, na, nv, n_seg, L, groups, n_groups, cols, scale, mirror, n_chunks, atom_block,
+                                            vec_block, seg_block, out_host),
+                        "psa_debug_self_power");
 }
 
 int psa_debug_self_series(psa_ctx* c, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* idx, int64_t n_g,

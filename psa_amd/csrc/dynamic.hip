@@ -216,7 +216,9 @@ dynamic_sincos_kernel(const float* __restrict__ turns, float2* __restrict__ out,
 }
 
 // seg: (nk, NC, ns, L) transformed segments; khat (nk, 3); out (1 or 3, L, K_pitch).  One thread per (k, bin): the sum
-// over the block's segments is one float32 chain per row.
+// over the block's segments is one float32 chain per row.  The transverse part is formed from the perpendicular
+// component F_c - h_c (h.F), not as the difference |F|^2 - |h.F|^2 of two nearly equal numbers: it is a sum of squares,
+// never negative, and its error is relative to sqrt(|F|^2 |F_perp|^2) instead of |F|^2 (tests/power_cases.py).
 template <int NC>
 __global__ void __launch_bounds__(256)
 dynamic_power_kernel(const float2* __restrict__ seg, const float* __restrict__ khat, float* __restrict__ out, int64_t L, int ns,
@@ -225,23 +227,28 @@ dynamic_power_kernel(const float2* __restrict__ seg, const float* __restrict__ k
         float h[3] = {0.f, 0.f, 0.f};
         if constexpr (NC == 4) h[0] = khat[(int64_t)k * 3], h[1] = khat[(int64_t)k * 3 + 1], h[2] = khat[(int64_t)k * 3 + 2];
         for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < L; o += (int64_t)gridDim.x * 256) {
-            float den = 0.f, lon = 0.f, all = 0.f;
+            float den = 0.f, lon = 0.f, tra = 0.f;
             for (int s = 0; s < ns; ++s) {
                 const float2 f0 = seg[(((int64_t)k * NC) * ns + s) * L + o];
                 den += f0.x * f0.x + f0.y * f0.y;
                 if constexpr (NC == 4) {
-                    float pr = 0.f, pi = 0.f;
+                    float2 fc[3];
+                    float  pr = 0.f, pi = 0.f;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
-                        const float2 fc = seg[(((int64_t)k * NC + 1 + c) * ns + s) * L + o];
-                        all += fc.x * fc.x + fc.y * fc.y;
-                        pr += h[c] * fc.x, pi += h[c] * fc.y;
+                        fc[c] = seg[(((int64_t)k * NC + 1 + c) * ns + s) * L + o];
+                        pr += h[c] * fc[c].x, pi += h[c] * fc[c].y;
                     }
                     lon += pr * pr + pi * pi;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const float tx = fc[c].x - h[c] * pr, ty = fc[c].y - h[c] * pi;
+                        tra += tx * tx + ty * ty;
+                    }
                 }
             }
             const int64_t i = o * K_pitch + k_col0 + k, row = L * K_pitch;
-            const float   d = den * scale, l = lon * scale, tr = 0.5f * ((all - lon) * scale);
+            const float   d = den * scale, l = lon * scale, tr = 0.5f * (tra * scale);
             out[i] = first ? d : out[i] + d;
             if constexpr (NC == 4) {
                 out[row + i] = first ? l : out[row + i] + l;

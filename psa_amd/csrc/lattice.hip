@@ -53,6 +53,8 @@
 // (bin, frequency o) adds X_n[o] + X_n[(L - o) mod L] -- each term float32, the sum float64 -- over the sub-block's
 // vectors of the bin (one contiguous range: the host orders by bin) and its segments, vector by vector, segment by
 // segment, and adds the total to the float64 accumulator (1 or 3, L, n_bins), which lives across sub-blocks and blocks.
+// The transverse term of a (vector, segment, side) is half the squared modulus of the perpendicular component
+// F_c - h_c (h.F), as in dynamic.hip: a sum of squares, never negative.
 // lattice_finish_kernel scales by 1 / (2 n_half_b n_seg U L^2) in float64 and rounds once to float32.
 #include "lattice_math.h"
 #include "psa_ctx.h"
@@ -190,16 +192,20 @@ lattice_shell_kernel(const float2* __restrict__ seg, const float* __restrict__ k
                         const float2  f0 = seg[(((int64_t)k * NC) * ns + s) * L + oo];
                         den += (double)(f0.x * f0.x + f0.y * f0.y);
                         if constexpr (NC == 4) {
-                            float pr = 0.f, pi = 0.f, all = 0.f;
+                            float2 fc[3];
+                            float  pr = 0.f, pi = 0.f, t = 0.f;
 #pragma unroll
                             for (int c = 0; c < 3; ++c) {
-                                const float2 fc = seg[(((int64_t)k * NC + 1 + c) * ns + s) * L + oo];
-                                all += fc.x * fc.x + fc.y * fc.y;
-                                pr += h[c] * fc.x, pi += h[c] * fc.y;
+                                fc[c] = seg[(((int64_t)k * NC + 1 + c) * ns + s) * L + oo];
+                                pr += h[c] * fc[c].x, pi += h[c] * fc[c].y;
                             }
-                            const float l = pr * pr + pi * pi;
-                            lon += (double)l;
-                            tra += (double)(0.5f * (all - l));
+                            lon += (double)(pr * pr + pi * pi);
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) {                  // the perpendicular component: dynamic.hip
+                                const float tx = fc[c].x - h[c] * pr, ty = fc[c].y - h[c] * pi;
+                                t += tx * tx + ty * ty;
+                            }
+                            tra += (double)(0.5f * t);
                         }
                     }
                 }

@@ -10,6 +10,10 @@ one-phonon term of a crystal, and noise for a run whose atoms do not stay at a s
     density[o,k]      = 1/(n_seg U) sum_s |F_s[k,0,o]|^2
     longitudinal[o,k] = 1/(n_seg U) sum_s |sum_c khat_c F_s[k,c,o]|^2          khat = k / |k|  (k = 0: khat = 0)
     transverse[o,k]   = ( 1/(n_seg U) sum_s sum_c |F_s[k,c,o]|^2 - longitudinal[o,k] ) / 2
+                      = 1/(2 n_seg U) sum_s sum_c |F_s[k,c,o] - khat_c (khat.F_s[k,.,o])|^2
+
+(the GPU forms the transverse part the second way, from the component of F perpendicular to khat: it is a sum of squares
+and never negative, however small beside the longitudinal part)
 
 over one atom set (all atoms by default), with per-atom weights w_a (none: 1; scattering lengths, `mass_weights`) and the
 segments of `psa_amd.Segments` (L, H, win; U = (1/L) sum win^2, n_seg = 1 + (T - L) // H; none: one boxcar segment of
