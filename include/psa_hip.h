@@ -570,6 +570,43 @@ int psa_self_spectra(psa_ctx* ctx, const double* box_inverse /* 9 */, const int3
                      const int32_t* bin_of /* K or NULL */, int64_t n_bins, const int32_t* idx, int64_t n_g,
                      float* out_host /* (L, K or n_bins) */, size_t out_bytes);
 
+/* The species-resolved (partial) spectra on that lattice: the matrix of partials S_ab(k, w), C_L^ab, C_T^ab of a system
+ * of S species, which scattering lengths, charges (charge-charge and number-number, Bhatia-Thornton) or concentrations
+ * combine afterwards.  H, Hinv, s, the segments, the window, U, the FFT order and khat are those of psa_lattice_spectra.
+ * Species a = 0 .. S - 1 are disjoint atom lists A_a, each in the order given: idx holds them one after the other,
+ * species_start (S + 1) their ascending offsets into it, species_start[0] = 0 and species_start[S] = the length of idx.
+ * The weights w are the context's atom weights.
+ *     q^a_0[n,t] = sum_{i in A_a} w_i exp(2 pi i n.s[t,i])        q^a_c[n,t] = sum_{i in A_a} w_i v[t,i,c] exp(2 pi i n.s[t,i])
+ *     F^a = the windowed transform of q^a per segment, as for psa_lattice_spectra
+ * One entry per pair a <= b, the pairs in row-major order over the upper triangle, (0,0), (0,1), .., (0,S-1), (1,1), ..:
+ * P = S (S + 1) / 2.  With scale = 1 / (L^2 n_seg U)
+ *     density_ab[o,n]      = scale sum_seg Re(F^a_0 conj F^b_0)
+ *     longitudinal_ab[o,n] = scale sum_seg Re((khat.F^a) conj(khat.F^b))
+ *     transverse_ab[o,n]   = scale 1/2 sum_seg sum_c Re(F_perp,c^a conj F_perp,c^b)        F_perp,c = F_c - khat_c (khat.F)
+ * the transverse part from the perpendicular components, never as a difference of the other two.  The real part is the
+ * symmetrised (ab + ba) / 2, the only part that enters sum_ab b_a b_b S_ab.  Off-diagonal entries are not doubled:
+ * sum_a X_aa + 2 sum_{a<b} X_ab is the field X of the union of the species.
+ *   bin_of == NULL  the per-vector form: out_host (1 or 3, P, L, K).
+ *   bin_of != NULL  the shell form, exactly as for psa_lattice_spectra: half-space members only, X^ab_-n[o] =
+ *                   X^ab_n[(L - o) mod L] (both factors mirrored: q^a(-n) = conj q^a(n) for real weights), float32 terms
+ *                   summed in float64 over a bin's vectors, segments and both sides, scaled by 1 / (2 n_half_b n_seg U L^2)
+ *                   in float64 and rounded once; an empty bin gives zeros; out_host (1 or 3, P, L, n_bins).
+ * An empty species gives zeros in all of its pairs.
+ * PSA_EINVAL: S < 1 or S > 8 (PARTIAL_MAX_SPECIES), a null idx or species_start, offsets that do not begin at 0 or are not
+ * ascending, an atom listed in two species, an index outside [0, N), and everything psa_lattice_spectra refuses.
+ * Per block of vectors q is (kb, S, NC, T): the projection kernel of psa_lattice_spectra, unchanged, runs once per species
+ * on that species' list, so a species' rows are bit for bit what psa_debug_lattice_project gives for its list and carry its
+ * per-element bound; the window pass and the rocFFT see S NC series per vector; the pair passes (partial.hip) then take one
+ * lane per (pair, vector or bin, frequency) with the float32 term and float64 sum structure of the passes they replace.
+ * The budget rule (PSA_OPT_DYNAMIC_WORK_BYTES) is psa_lattice_spectra's with S NC series per vector where it has NC.  No
+ * atomics: two identical calls give the same bits, and the per-vector form does not depend on how the budget cuts the
+ * list into blocks of vectors.  The result and the shell form's float64 accumulator lie outside the budget.  Nothing of
+ * the other entry points' state is touched.  Stage times as for psa_lattice_spectra. */
+int psa_partial_spectra(psa_ctx* ctx, const double* box_inverse /* 9 */, const int32_t* indices /* (K,3) */, int64_t K,
+                        const int32_t* bin_of /* K or NULL */, int64_t n_bins, const int32_t* idx, const int64_t* species_start /* S+1 */,
+                        int32_t n_species, int32_t currents /* 0: density only, 1: all three */,
+                        float* out_host /* (1 or 3, P, L, K or n_bins) */, size_t out_bytes);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is
@@ -709,6 +746,18 @@ int psa_debug_lattice_shell(psa_ctx* ctx, const void* seg_host, const float* kha
 int psa_debug_self_power(psa_ctx* ctx, const void* work_host, int64_t na, int64_t nv, int64_t n_seg, int64_t L,
                          const int32_t* groups, int64_t n_groups, int64_t cols, const double* scale, int32_t mirror,
                          int64_t n_chunks, int64_t atom_block, int64_t vec_block, int64_t seg_block, float* out_host);
+/* the projections of psa_partial_spectra alone (per-vector form), block by block under the same budget rule: out_host
+ * (K, S, NC, T) complex64 in the caller's order, NC = currents ? 4 : 1 */
+int psa_debug_partial_project(psa_ctx* ctx, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* idx,
+                              const int64_t* species_start, int32_t n_species, int32_t currents, void* out_host);
+/* the pair pass of psa_partial_spectra alone on TRANSFORMED segments seg_host (K, S, NC, n_seg, L) complex64, through the
+ * host loop of the run, as the three entries above: khat (K, 3) float32 as given (may be NULL without currents); norm =
+ * n_seg U L^2 as one double.  bin_of == NULL: the per-vector form, out_host (1 or 3, P, L, K), the scale (float)(1 / norm).
+ * bin_of (K) ascending: the shell and finish passes, the vectors in the processing order, out_host (1 or 3, P, L, n_bins),
+ * the scale of bin b 1 / (2 n_b norm).  Refused: what psa_debug_lattice_shell refuses, and S outside [1, 8]. */
+int psa_debug_partial_power(psa_ctx* ctx, const void* seg_host, const float* khat /* (K,3) */, const int32_t* bin_of /* K or NULL */,
+                            int64_t K, int64_t n_bins, int32_t n_species, int32_t currents, int64_t n_seg, int64_t L,
+                            int64_t k_block, int64_t seg_block, double norm, float* out_host);
 /* number of plane sets in the cache and their bytes */
 int psa_debug_plane_cache(psa_ctx* ctx, int64_t* n_sets, int64_t* bytes);
 

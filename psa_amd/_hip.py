@@ -55,6 +55,7 @@ LAT_CHAIN = 128     # atoms one float32 accumulator sums before it is folded
 LAT_FRAMES = 4      # frames per workgroup
 LAT_MAX_INDEX = 64  # largest |n_j| served
 LAT_MAX_ENTRIES = 3 * (2 * LAT_MAX_INDEX + 1)
+PARTIAL_MAX_SPECIES = 8   # most species of a partial-spectra call (psa_amd/csrc/partial.hip): 36 pairs
 # the tiles of the self-spectra series kernel (psa_amd/csrc/self.hip), mirrored for the cases of tests/self_cases.py
 SELF_THREADS = 256  # lanes of a workgroup: SELF_ATOMS wavefronts, a lane per frame
 SELF_ATOMS = 4      # atoms of an atom tile
@@ -128,6 +129,12 @@ SIGNATURES = {
                                           C.c_int64, C.c_int64, C.c_double, _f32p]),
     "psa_debug_self_power": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i32p, C.c_int64, C.c_int64,
                                        C.POINTER(C.c_double), C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _f32p]),
+    "psa_partial_spectra": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, _i32p, _i64p, C.c_int32,
+                                      C.c_int32, _f32p, C.c_size_t]),
+    "psa_debug_partial_project": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, _i64p, C.c_int32, C.c_int32,
+                                            C.c_void_p]),
+    "psa_debug_partial_power": (C.c_int, [_ctx, C.c_void_p, _f32p, _i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
+                                          C.c_int64, C.c_int64, C.c_int64, C.c_double, _f32p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
@@ -814,6 +821,72 @@ class Engine:
         _check(self._lib.psa_debug_lattice_shell(self._h, S.ctypes.data_as(C.c_void_p), _f32(kh), bins.ctypes.data_as(_i32p), K,
                                                  int(n_bins), 1 if NC == 4 else 0, ns, L, int(k_block), int(seg_block), float(norm),
                                                  _f32(out)), "psa_debug_lattice_shell")
+        return out
+
+    @staticmethod
+    def _species_args(species):
+        """(concatenated atom lists int32 -- one dummy entry where all are empty --, offsets (S + 1,) int64, S) of a
+        sequence of atom lists; ValueError for none or more than PARTIAL_MAX_SPECIES"""
+        lists = [np.ascontiguousarray(g, np.int32).ravel() for g in species]
+        if not 1 <= len(lists) <= PARTIAL_MAX_SPECIES:
+            raise ValueError(f"1 to {PARTIAL_MAX_SPECIES} species are served, got {len(lists)}")
+        off = np.concatenate([[0], np.cumsum([g.size for g in lists])]).astype(np.int64)
+        idx = np.concatenate(lists) if off[-1] else np.zeros(1, np.int32)
+        return np.ascontiguousarray(idx, np.int32), off, len(lists)
+
+    def partial_spectra(self, box_inverse, indices, species, bin_of=None, n_bins=0, currents: bool = True) -> np.ndarray:
+        """Species-resolved dynamic spectra on the box's reciprocal lattice (psa_partial_spectra): `species` is a sequence
+        of S <= 8 disjoint atom lists; one entry per pair a <= b in row-major upper-triangle order, P = S (S + 1) / 2.
+        `bin_of` None: per vector, (3, P, L, K) float32 -- density, longitudinal, transverse: the real parts of
+        F^a conj F^b -- or (1, P, L, K) with `currents=False`; `bin_of` (K,) with `n_bins`: the shell form,
+        (3 or 1, P, L, n_bins).  Box, vectors, weights and segments as for `lattice_spectra`."""
+        T, _ = self.shape(SLOT_POSITIONS)
+        L = self.segment_length or T
+        inv, n, _, _, _ = self._lattice_args(box_inverse, indices, None)
+        idx, off, S = self._species_args(species)
+        K = n.shape[0]
+        bins = None if bin_of is None else np.ascontiguousarray(bin_of, np.int32).ravel()
+        if bins is not None and bins.size != K:
+            raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
+        out = np.empty((3 if currents else 1, S * (S + 1) // 2, L, K if bins is None else int(n_bins)), np.float32)
+        _check(self._lib.psa_partial_spectra(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p), K,
+                                             None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins),
+                                             idx.ctypes.data_as(_i32p), off.ctypes.data_as(_i64p), S, 1 if currents else 0,
+                                             _f32(out), out.nbytes), "psa_partial_spectra")
+        return out
+
+    def debug_partial_project(self, box_inverse, indices, species, currents: bool = True) -> np.ndarray:
+        """The projections of `partial_spectra` alone: q (K, S, NC, T) complex64 before the window and the FFT, NC = 4 with
+        currents (density, j_x, j_y, j_z), else 1."""
+        T, _ = self.shape(SLOT_POSITIONS)
+        inv, n, _, _, _ = self._lattice_args(box_inverse, indices, None)
+        idx, off, S = self._species_args(species)
+        out = np.empty((n.shape[0], S, 4 if currents else 1, T), np.complex64)
+        _check(self._lib.psa_debug_partial_project(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p),
+                                                   n.shape[0], idx.ctypes.data_as(_i32p), off.ctypes.data_as(_i64p), S,
+                                                   1 if currents else 0, out.ctypes.data_as(C.c_void_p)),
+               "psa_debug_partial_project")
+        return out
+
+    def debug_partial_power(self, segments, khat, norm: float, bin_of=None, n_bins: int = 0, k_block: int = 0,
+                            seg_block: int = 0) -> np.ndarray:
+        """The pair pass of `partial_spectra` alone (psa_debug_partial_power): transformed segments (K, S, NC, ns, L)
+        complex64 taken as they are, `khat` (K, 3) float32.  `bin_of` None: per vector, (1 or 3, P, L, K) float32 with the
+        scale float32(1 / norm); `bin_of` (K,) ascending: the shell and finish passes, (1 or 3, P, L, n_bins) with the
+        bins' scales 1 / (2 n_b norm).  `k_block`, `seg_block` > 0: sub-blocks, as a budget-bound call is cut."""
+        Z = np.ascontiguousarray(segments, np.complex64)
+        kh = _as_f32(np.asarray(khat, np.float32).reshape(-1, 3), (3,))
+        bins = None if bin_of is None else np.ascontiguousarray(bin_of, np.int32).ravel()
+        if Z.ndim != 5 or Z.shape[0] != kh.shape[0] or Z.shape[2] not in (1, 4) or (bins is not None and bins.size != Z.shape[0]):
+            raise ValueError(f"segments {Z.shape}, khat {kh.shape} and bin_of do not fit (K,S,1 or 4,ns,L), (K,3), (K,)")
+        K, S, NC, ns, L = Z.shape
+        if not 1 <= S <= PARTIAL_MAX_SPECIES:
+            raise ValueError(f"1 to {PARTIAL_MAX_SPECIES} species are served, got {S}")
+        out = np.empty((3 if NC == 4 else 1, S * (S + 1) // 2, L, K if bins is None else int(n_bins)), np.float32)
+        _check(self._lib.psa_debug_partial_power(self._h, Z.ctypes.data_as(C.c_void_p), _f32(kh),
+                                                 None if bins is None else bins.ctypes.data_as(_i32p), K, int(n_bins), S,
+                                                 1 if NC == 4 else 0, ns, L, int(k_block), int(seg_block), float(norm), _f32(out)),
+               "psa_debug_partial_power")
         return out
 
     def debug_self_power(self, work, groups, cols: int, scale, mirror: bool, n_chunks: int = 0, atom_block: int = 0,

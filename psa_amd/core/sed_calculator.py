@@ -37,6 +37,7 @@ from ..dynamic import DynamicSpectra
 from .. import lattice
 from ..lattice import PowderSpectra
 from ..modes import ModeSED
+from ..partial import MAX_SPECIES, PartialSpectra, PowderPartialSpectra, pair_table
 from ..peaks import PeakFit
 from ..segments import Segments
 from ..self_spectra import check_max_atoms, draw_atoms
@@ -666,6 +667,83 @@ class SEDCalculator:
         out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, False,
                                              lambda eng, listed: eng.self_spectra(inv, n, b, n_bins, listed), max_atoms, seed)
         return self._powder_result(shells, out, None, None, freqs, atoms, norm)
+
+    # ------------------------------------------------------------------ partial (species-resolved) spectra on that lattice
+    def _partial_species(self, basis_atom_indices, basis_atom_types, weights):
+        """(the species' atom-index arrays, sum_a w_a^2 per species): resolved like the groups of `calculate_vdos`"""
+        groups = self._resolve_groups(basis_atom_indices, basis_atom_types, "incoherent")
+        if len(groups) > MAX_SPECIES:
+            raise ValueError(f"at most {MAX_SPECIES} species are served, got {len(groups)}")
+        members = np.concatenate(groups)
+        if np.unique(members).size != members.size:
+            raise ValueError("species of partial spectra must be disjoint (an atom is listed twice)")
+        w2 = np.ones(self.traj.n_atoms, np.float64) if weights is None else weights.astype(np.float64) ** 2
+        return [np.asarray(g) for g in groups], np.array([float(np.sum(w2[g])) for g in groups])
+
+    def _partial_run(self, groups, weights, segments, currents, call):
+        eng = self.engine
+        with self._engine_state(weights, segments):  # (segments before the upload: its FFT primer then builds length L)
+            eng.ensure_resident(_hip.SLOT_POSITIONS, self.traj.positions)
+            if currents:
+                eng.ensure_resident(_hip.SLOT_VELOCITIES, self.traj.velocities)
+            return call(eng)
+
+    def calculate_partial_spectra(self, indices: np.ndarray,
+                                  basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                  basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                  atom_weights: Optional[np.ndarray] = None, segments: Optional[Segments] = None,
+                                  currents: bool = True) -> PartialSpectra:
+        """The partial (species-resolved) dynamic spectra on the reciprocal lattice of the simulation box (not in the
+        reference; definition in psa_amd/partial.py): per pair a <= b of species the real parts of F^a conj F^b --
+        S_ab(k, w) and the partial current correlations C_L^ab, C_T^ab -- for the integer `indices` (K, 3), from one
+        projection of every atom.  `PartialSpectra.combine` forms neutron or X-ray totals, the charge-charge and the
+        number-number spectrum from them.
+
+        Species are resolved like the groups of `calculate_vdos`: `basis_atom_types=[1, 2]` gives two species, nothing
+        gives all atoms as one.  They must be disjoint and at most 8 (ValueError).  Vectors, `atom_weights`, `segments`,
+        `currents`, residency, the empty inputs and the sharded refusal are those of `calculate_lattice_spectra`.
+        Returns a `psa_amd.PartialSpectra` with (P, L, K) float32 fields, P = S (S + 1) / 2."""
+        weights = self._dynamic_arguments(atom_weights, segments, "the partial spectra")
+        n = self._lattice_indices(indices)
+        inv = lattice.box_inverse(self.traj.box_matrix)
+        k = lattice.lattice_k(n, inv)
+        mags = np.linalg.norm(k, axis=1)
+        L, freqs = self._dynamic_lengths(segments)
+
+        def result(out, groups, norms):
+            lon, tra = (out[1], out[2]) if currents else (None, None)
+            return PartialSpectra(out[0], lon, tra, pair_table(len(groups)), groups, norms, freqs, mags, k, self.dt_ps)
+        if self._dynamic_nothing(n.shape[0], "partial spectra"):
+            return result(np.zeros((3 if currents else 1, 1, L, n.shape[0]), np.float32), [np.zeros(0, int)], np.zeros(1))
+        groups, norms = self._partial_species(basis_atom_indices, basis_atom_types, weights)
+        return result(self._partial_run(groups, weights, segments, currents,
+                                        lambda eng: eng.partial_spectra(inv, n, groups, None, 0, currents)), groups, norms)
+
+    def calculate_powder_partial_spectra(self, q_edges: np.ndarray,
+                                         basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                         basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                         atom_weights: Optional[np.ndarray] = None, segments: Optional[Segments] = None,
+                                         currents: bool = True, max_per_bin: Optional[int] = None,
+                                         seed: int = 0) -> PowderPartialSpectra:
+        """The powder average of `calculate_partial_spectra` (definition in psa_amd/partial.py): S_ab(Q, w), C_L^ab(Q, w)
+        and C_T^ab(Q, w) averaged over all vectors of the box's reciprocal lattice in each shell
+        q_edges[b] <= |k| < q_edges[b + 1], the shells summed on the GPU in float64.  Shells, `max_per_bin`, `seed`,
+        counts and the empty shell are those of `calculate_powder_spectra`; species and everything else those of
+        `calculate_partial_spectra`.  Returns a `psa_amd.PowderPartialSpectra` with (P, L, n_bins) float32 fields."""
+        weights = self._dynamic_arguments(atom_weights, segments, "the powder partial spectra")
+        shells = self._powder_shells(q_edges, max_per_bin, seed)
+        L, freqs = self._dynamic_lengths(segments)
+        n, b, n_bins, inv = shells["indices"], shells["bins"], shells["n_bins"], shells["inverse"]
+
+        def result(out, groups, norms):
+            lon, tra = (out[1], out[2]) if currents else (None, None)
+            return PowderPartialSpectra(out[0], lon, tra, pair_table(len(groups)), groups, norms, shells["q"], shells["edges"],
+                                        2 * shells["used"], 2 * shells["available"], n, b, freqs, self.dt_ps)
+        if self._dynamic_nothing(n.shape[0], "powder partial spectra"):
+            return result(np.zeros((3 if currents else 1, 1, L, n_bins), np.float32), [np.zeros(0, int)], np.zeros(1))
+        groups, norms = self._partial_species(basis_atom_indices, basis_atom_types, weights)
+        return result(self._partial_run(groups, weights, segments, currents,
+                                        lambda eng: eng.partial_spectra(inv, n, groups, b, n_bins, currents)), groups, norms)
 
     # ------------------------------------------------------------------ mode projection
     def calculate_mode_sed(self, k_points_mags: np.ndarray, k_vectors_3d: np.ndarray, eigenvectors: np.ndarray,

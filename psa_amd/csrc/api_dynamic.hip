@@ -11,7 +11,8 @@
 // Budget (PSA_OPT_DYNAMIC_WORK_BYTES = W; q and the segment buffer share it, the result is outside), as for
 // psa_sed_modes_welch: the segment buffer is promised min(what all K vectors' segments need, max(one (k, segment) unit,
 // W / 8)), never more than W less one k-vector of q; q takes kb = the rest / (8 NC T) k-vectors, and the segment buffer
-// then gets whatever q left over, cut into as many k-vectors as fit x the segments that then fit.
+// then gets whatever q left over, cut into as many k-vectors as fit x the segments that then fit.  A call whose vectors
+// hold the series of S species each (psa_partial_spectra: DynCall::n_species) counts S NC series where this says NC.
 #include "api_internal.h"
 
 namespace psa {
@@ -46,10 +47,11 @@ int dynamic_plan(psa_ctx* c, DynCall* d) {
 
     // the budget: q (kb k-vectors) first, the segment buffer (units of one k-vector x one segment) from the rest
     const int64_t W = c->opt_dynamic_work_bytes;
-    d->per_k = (int64_t)d->NC * T * (int64_t)sizeof(float2);
-    d->unit = d->cut ? (int64_t)d->NC * d->L * (int64_t)sizeof(float2) : 0;
+    const int64_t series = (int64_t)d->n_species * d->NC;    // per vector
+    d->per_k = series * T * (int64_t)sizeof(float2);
+    d->unit = d->cut ? series * d->L * (int64_t)sizeof(float2) : 0;
     PSA_REQUIRE(W >= d->per_k + d->unit, "the work budget of %lld bytes (PSA_OPT_DYNAMIC_WORK_BYTES) cannot hold one k-vector: "
-                "%d series x (%lld frames + a segment of %lld) need %lld bytes", (long long)W, d->NC, (long long)T,
+                "%d series x (%lld frames + a segment of %lld) need %lld bytes", (long long)W, (int)series, (long long)T,
                 (long long)(d->cut ? d->L : 0), (long long)(d->per_k + d->unit));
     int64_t seg_bytes = 0;
     if (d->cut) {
@@ -63,7 +65,7 @@ int dynamic_plan(psa_ctx* c, DynCall* d) {
         const int64_t units = std::min((W - d->kb * d->per_k) / d->unit, d->kb * d->n_seg);
         if (units >= d->kb) d->bs = std::min(d->n_seg, units / d->kb);
         else d->bk = units;
-        d->bs = std::min(d->bs, std::max<int64_t>(1, ((1ll << 31) - 1) / (d->bk * d->NC)));
+        d->bs = std::min(d->bs, std::max<int64_t>(1, ((1ll << 31) - 1) / (d->bk * series)));
     }
     return PSA_OK;
 }
@@ -76,7 +78,13 @@ int power_block(psa_ctx* c, const PowerPass& p, int64_t k0, int64_t nk, int64_t 
             const float2* d_seg = nullptr;
             PSA_TRY(fill(k1, nb, s0, ns, &d_seg));
             StageTimer st(c, PSA_T_EPILOGUE);
-            if (p.d_bins)
+            if (p.n_species > 0 && p.d_bins)
+                PSA_TRY(launch_partial_shell(c, d_seg, p.d_khat + (size_t)(k0 + k1) * 3, p.d_bins, p.d_acc, p.L, ns, k0 + k1, nb, p.n_bins,
+                                             p.n_species, p.NC == 4));
+            else if (p.n_species > 0)
+                PSA_TRY(launch_partial_power(c, d_seg, p.d_khat + (size_t)(k0 + k1) * 3, p.d_out, p.L, ns, nb, p.n_species, p.NC == 4,
+                                             p.K, k0 + k1, p.scale, s0 == 0));
+            else if (p.d_bins)
                 PSA_TRY(launch_lattice_shell(c, d_seg, p.d_khat + (size_t)(k0 + k1) * 3, p.d_bins, p.d_acc, p.L, ns, k0 + k1, nb, p.n_bins,
                                              p.NC == 4));
             else

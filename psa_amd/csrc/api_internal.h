@@ -16,6 +16,7 @@
 //   api_dynamic.hip  the dynamic structure factor and the current correlations: the phase of every frame's own positions
 //   api_lattice.hip  the same spectra on the box's reciprocal lattice, per vector or averaged over shells of |k|
 //   api_self.hip     the self (incoherent) part on that lattice: per-atom series, their power summed over the atoms
+//   api_partial.hip  the species-resolved (partial) spectra on that lattice: one projection per species, products of pairs
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
 // k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
 #pragma once
@@ -223,9 +224,11 @@ int peaks_run(psa_ctx* c, const float* d_spec, const PeakArgs& a);
 struct DynCall {
     int64_t T = 0, N = 0, K = 0, n_g = 0;
     int     NC = 1, slices = 1;
+    int     n_species = 1;               // species whose NC series each vector holds (psa_partial_spectra; else 1)
     bool    cut = false;                 // false: one boxcar segment of T frames, q transformed in place
     int64_t L = 0, H = 0, n_seg = 0;
-    int64_t per_k = 0, unit = 0;         // bytes of one k-vector of q; of one (k-vector, segment) of the segment buffer
+    int64_t per_k = 0, unit = 0;         // bytes of one k-vector of q; of one (k-vector, segment) of the segment buffer:
+                                         // n_species NC series each
     int64_t kb = 0, bk = 0, bs = 0;      // k-vectors per block of q; k-vectors x segments per sub-block
     std::vector<float> kappa, khat;      // (K, 6) k / 2 pi as hi xyz, lo xyz; (K, 3) k / |k|
 };
@@ -233,11 +236,13 @@ int dynamic_inputs(psa_ctx* c, const char* entry, int64_t K, const int32_t* idx,
 int dynamic_plan(psa_ctx* c, DynCall* d);
 // The power part of a dynamic or lattice call, shared by the run and by the debug entries (psa_debug_dynamic_power,
 // psa_debug_lattice_shell), which differ only in where the transformed segments come from.  PowerPass: what every launch of
-// the pass gets; d_bins set: the shell pass into d_acc, else dynamic.hip's power pass into d_out.  power_block: vectors
+// the pass gets; d_bins set: the shell pass into d_acc, else dynamic.hip's power pass into d_out; n_species > 0: the pair
+// passes of partial.hip (psa_partial_spectra, psa_debug_partial_power) on (nb, n_species, NC, ns, L).  power_block: vectors
 // [k0, k0 + nk) of the processing order in sub-blocks of bk vectors x bs segments; `fill` leaves the transformed segments
 // (nb, NC, ns, L) of vectors k0 + k1 .. and segments s0 .. on the device and says where.
 struct PowerPass {
     int          NC = 1;
+    int          n_species = 0;          // 0: one series set per vector, moduli; else that many, products of pairs
     int64_t      L = 0, n_seg = 0, K = 0;
     float        scale = 0.f;
     const float* d_khat = nullptr;       // (K, 3), row 0 = vector 0 of the processing order

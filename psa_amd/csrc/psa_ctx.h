@@ -311,6 +311,13 @@ struct psa_ctx {
     psa::DevBuf  d_self_work, d_self_tiles, d_self_ent, d_self_slot, d_self_idx, d_self_groups, d_self_scale, d_self_part,
                  d_self_acc, d_self_out;
 
+    // the species-resolved (partial) spectra on that lattice (psa_partial_spectra; api_partial.hip), under the same budget:
+    // the projections q (kb, S, NC, T) of one block; the plan as for psa_lattice_spectra, its rows of q counted in vectors
+    // (the table holds S row); k / |k|; the species' atom lists, concatenated; the shell form's bin offsets, scales and
+    // float64 accumulator (1 or 3, P, L, n_bins); the float32 result (1 or 3, P, L, K or n_bins).  All kept between calls.
+    psa::DevBuf  d_par_q, d_par_tiles, d_par_ent, d_par_slot, d_par_dest, d_par_khat, d_par_idx, d_par_bins, d_par_scale,
+                 d_par_acc, d_par_out;
+
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
                                           // plane builds, trajectory uploads (psa_oneoff_stats)
@@ -490,6 +497,19 @@ int launch_lattice_shell(psa_ctx* c, const float2* d_seg, const float* d_khat, c
                          int64_t ns, int64_t g0, int64_t nb, int64_t n_bins, bool currents);
 // out[i] = (float)(acc[i] scale[i mod n_bins]), n elements
 int launch_lattice_finish(psa_ctx* c, const double* d_acc, const double* d_scale, float* d_out, int64_t n, int64_t n_bins);
+// --- partial.hip (psa_partial_spectra: the passes after the FFT of S species' series per vector, which take the products
+// F^a conj F^b of a pair of species where dynamic.hip and lattice.hip take moduli; the arithmetic is in its header)
+constexpr int PARTIAL_MAX_SPECIES = 8;                                                  // most species of a call
+constexpr int PARTIAL_MAX_PAIRS = PARTIAL_MAX_SPECIES * (PARTIAL_MAX_SPECIES + 1) / 2;  // pairs a <= b of them: 36
+// (pair p = (a, b), a <= b, row-major over the upper triangle: (0,0), (0,1), .., (0,S-1), (1,1), ..; P = S (S + 1) / 2)
+// after the FFT of the segment buffer (nk, S, NC, ns, L): out (1 or 3, P, L, K_pitch) float32, columns k_col0 .. k_col0 + nk - 1:
+// (first ? 0 : out) + scale sum_s { Re F_0^a conj F_0^b;  Re (khat.F^a) conj (khat.F^b);  sum_c Re F_perp,c^a conj F_perp,c^b / 2 }
+int launch_partial_power(psa_ctx* c, const float2* d_seg, const float* d_khat, float* d_out, int64_t L, int64_t ns, int64_t nk,
+                         int n_species, bool currents, int64_t K_pitch, int64_t k_col0, float scale, bool first);
+// the same segment buffer of the vectors g0 .. g0 + nb - 1 of the processing order: acc (1 or 3, P, L, n_bins) float64 += the
+// sum over the bin's vectors and the segments of X_n[o] + X_n[(L - o) mod L], unscaled
+int launch_partial_shell(psa_ctx* c, const float2* d_seg, const float* d_khat, const int* d_bin_start, double* d_acc, int64_t L,
+                         int64_t ns, int64_t g0, int64_t nb, int64_t n_bins, int n_species, bool currents);
 // --- self.hip (psa_self_spectra: z[a,n,t] = w_a exp(2 pi i n.s_a(t)) per atom, its power summed over the atoms; the
 // arithmetic and the bound are in its header)
 constexpr int SELF_THREADS = 256;      // lanes of a workgroup: SELF_ATOMS wavefronts, a lane per frame
