@@ -607,6 +607,50 @@ int psa_partial_spectra(psa_ctx* ctx, const double* box_inverse /* 9 */, const i
                         int32_t n_species, int32_t currents /* 0: density only, 1: all three */,
                         float* out_host /* (1 or 3, P, L, K or n_bins) */, size_t out_bytes);
 
+/* The time correlations on that lattice: the intermediate scattering function F(k,t) and the current correlations
+ * C_L(k,t), C_T(k,t) -- the functions of time whose spectra psa_lattice_spectra gives -- as the LINEAR, unbiased estimator
+ * (transforming a spectrum back gives the circular correlation of a segment, lag t contaminated by lag L - t).  Inputs as
+ * for psa_lattice_spectra.  Segments come from psa_set_segments and must carry the boxcar window, every value exactly 1.0f;
+ * with none set there is one segment of L = T frames; n_seg = 1 + (T - L) / H.  1 <= n_lags <= L.
+ *     P      = the smallest power of two >= L + n_lags - 1      (the padded FFT length: part of the definition)
+ *     A_s[o] = sum_{l<L} x[sH + l] exp(-2 pi i o l / P),  o = 0 .. P - 1
+ *     C[t]   = (1/P) sum_o (sum_s |A_s[o]|^2) cos(2 pi o t / P)  =  Re sum_s sum_{l=0}^{L-1-t} x[sH+l+t] conj x[sH+l]
+ *     F[t]   = C[t] / (n_seg (L - t)),  t = 0 .. n_lags - 1
+ * for the series x of a field: density from q_0, longitudinal from khat.q, transverse 1/2 sum_c over the perpendicular
+ * components q_c - khat_c (khat.q), built from the perpendicular form as in psa_lattice_spectra.  Only the real part -- per
+ * vector the part even in t -- is produced.  F[0] is the mean of |x|^2 over the frames used and, with the same boxcar
+ * segments, the sum over o of the matching field of psa_lattice_spectra.
+ *   bin_of == NULL  the per-vector form: out_host (1 or 3, n_lags, K).
+ *   bin_of != NULL  the shell form: out_host (1 or 3, n_lags, n_bins), the mean over the FULL-sphere vectors of each shell
+ *                   from its half-space members (C_{-n}[t] = conj C_n[t], so the mean is real); an empty bin gives zeros.
+ * PSA_EINVAL: everything psa_lattice_spectra refuses; n_lags outside [1, L]; segments whose window is not the boxcar; a
+ * sharded context.  The route is psa_lattice_spectra's with every segment zero-padded to P frames (correlation.hip: the
+ * first L values bit copies, the tail written for every block), the power summed where the spectra sum it -- float32 per
+ * vector, float64 per shell --, and a float64 back-transform out = float32(factor[t] scale[col] sum_o X[o] tab[(o t) mod P]),
+ * tab the float64 cosines from the host, factor[t] = 1 / (P n_seg (L - t)), one chain over o in a fixed order: no atomics,
+ * two identical calls give the same bits.  The budget rule (PSA_OPT_DYNAMIC_WORK_BYTES) is psa_lattice_spectra's with a
+ * segment buffer of P frames per series where that has L -- also without segments, where the spectra use none; the
+ * refusal names P.  The power (1 or 3, P, K or n_bins), the tables and the result lie outside the budget.  Nothing of the
+ * other entry points' state is touched.  Stage times go to psa_last_timings: [2] the projection, [5] the padding pass,
+ * [3] FFT, [4] power or shell pass, [1] the back-transform, [7] device->host. */
+int psa_lattice_correlations(psa_ctx* ctx, const double* box_inverse /* 9 */, const int32_t* indices /* (K,3) */, int64_t K,
+                             const int32_t* bin_of /* K or NULL */, int64_t n_bins, const int32_t* idx, int64_t n_g,
+                             int32_t currents /* 0: density only, 1: all three */, int64_t n_lags,
+                             float* out_host /* (1 or 3, n_lags, K or n_bins) */, size_t out_bytes);
+
+/* The self part in time, F_s(k,t): the sum over the atoms of the set of C_a[t] of z[a,n,.] = w_a exp(2 pi i n.s[.,a])
+ * (psa_self_spectra), by the definition above: the weights enter squared, F_s(n, 0) = sum_a w_a^2 for every vector, and
+ * the result is the same on wrapped and on unwrapped coordinates.  out_host (n_lags, K), or in the shell form
+ * (n_lags, n_bins).  PSA_EINVAL: everything psa_self_spectra refuses, and n_lags, the window and sharding as above.  The
+ * route is psa_self_spectra's with rows of P frames: the series kernel writes the first L values of a row, the padding
+ * pass the P - L others, for every block; the power pass runs without the frequency mirror in the shell form too (the
+ * cosine is even: the scale is 1 / n_half), one read of the transformed block instead of two.  Budget: psa_self_spectra's
+ * rule with 8 P bytes per series.  Stage times: [6] the series kernel, [5] the padding pass, [3] FFT, [4] power pass,
+ * [1] the back-transform, [7] device->host. */
+int psa_self_correlations(psa_ctx* ctx, const double* box_inverse /* 9 */, const int32_t* indices /* (K,3) */, int64_t K,
+                          const int32_t* bin_of /* K or NULL */, int64_t n_bins, const int32_t* idx, int64_t n_g, int64_t n_lags,
+                          float* out_host /* (n_lags, K or n_bins) */, size_t out_bytes);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is
@@ -801,6 +845,14 @@ int psa_sed_fs_read(psa_ctx* ctx, int64_t k0, int64_t nk, void* host);
 /* frames [t0, t0+nt) of my rows, (k_count,3,nt) complex64 */
 int psa_sed_fs_write(psa_ctx* ctx, int64_t t0, int64_t nt, const void* host);
 int psa_sed_fs_finish(psa_ctx* ctx, int32_t first_group);
+
+/* the back-transform of psa_lattice_correlations and psa_self_correlations alone, through the launch helper the runs use:
+ * X_host (fields, P, cols) float64 -- with as_float32 = 1 rounded to float32 first, the per-vector pass's type -- ->
+ * out_host (fields, n_lags, cols) float32 = 1 / (P n_seg (L - t)) sum_o X[f,o,col] cos(2 pi o t / P).  Any P >= 1, not only
+ * powers of two.  PSA_EINVAL: a null pointer, fields outside [1, 3], P outside [1, 2^30], a size that is not positive,
+ * n_lags outside [1, min(L, P)], a non-finite value, more than 2^28 elements. */
+int psa_debug_correlation_transform(psa_ctx* ctx, const double* X_host, int64_t fields, int64_t P, int64_t cols, int64_t L,
+                                    int64_t n_seg, int64_t n_lags, int32_t as_float32, float* out_host);
 
 #ifdef __cplusplus
 }

@@ -135,6 +135,12 @@ SIGNATURES = {
                                             C.c_void_p]),
     "psa_debug_partial_power": (C.c_int, [_ctx, C.c_void_p, _f32p, _i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
                                           C.c_int64, C.c_int64, C.c_int64, C.c_double, _f32p]),
+    "psa_lattice_correlations": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64,
+                                           C.c_int32, C.c_int64, _f32p, C.c_size_t]),
+    "psa_self_correlations": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64,
+                                        C.c_int64, _f32p, C.c_size_t]),
+    "psa_debug_correlation_transform": (C.c_int, [_ctx, C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                                  C.c_int64, C.c_int64, C.c_int32, _f32p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
@@ -905,6 +911,53 @@ class Engine:
                                               g.shape[0] - 1, int(cols), sc.ctypes.data_as(C.POINTER(C.c_double)), 1 if mirror else 0,
                                               int(n_chunks), int(atom_block), int(vec_block), int(seg_block), _f32(out)),
                "psa_debug_self_power")
+        return out
+
+    def lattice_correlations(self, box_inverse, indices, n_lags: int, bin_of=None, n_bins=0, idx=None, currents: bool = True
+                             ) -> np.ndarray:
+        """F(k,t), C_L(k,t), C_T(k,t) on the box's reciprocal lattice (psa_lattice_correlations): the linear, unbiased time
+        correlation of every (boxcar) segment at lags 0 .. n_lags - 1.  (3, n_lags, K) float32, or (1, n_lags, K) with
+        `currents=False`; with `bin_of` and `n_bins` the shell form, (3 or 1, n_lags, n_bins).  Everything else as for
+        `lattice_spectra`."""
+        inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
+        K = n.shape[0]
+        bins = None if bin_of is None else np.ascontiguousarray(bin_of, np.int32).ravel()
+        if bins is not None and bins.size != K:
+            raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
+        out = np.empty((3 if currents else 1, max(int(n_lags), 0), K if bins is None else int(n_bins)), np.float32)
+        _check(self._lib.psa_lattice_correlations(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p), K,
+                                                  None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g,
+                                                  1 if currents else 0, int(n_lags), _f32(out), out.nbytes),
+               "psa_lattice_correlations")
+        return out
+
+    def self_correlations(self, box_inverse, indices, n_lags: int, bin_of=None, n_bins=0, idx=None) -> np.ndarray:
+        """F_s(k,t) on the box's reciprocal lattice (psa_self_correlations): per atom the time correlation of
+        z = w_a exp(2 pi i n.s_a(t)), summed over the atoms.  (n_lags, K) float32, or with `bin_of` and `n_bins` the shell
+        form, (n_lags, n_bins).  Everything else as for `self_spectra`."""
+        inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
+        K = n.shape[0]
+        bins = None if bin_of is None else np.ascontiguousarray(bin_of, np.int32).ravel()
+        if bins is not None and bins.size != K:
+            raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
+        out = np.empty((max(int(n_lags), 0), K if bins is None else int(n_bins)), np.float32)
+        _check(self._lib.psa_self_correlations(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p), K,
+                                               None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g,
+                                               int(n_lags), _f32(out), out.nbytes), "psa_self_correlations")
+        return out
+
+    def debug_correlation_transform(self, power, L: int, n_seg: int, n_lags: int, as_float32: bool = False) -> np.ndarray:
+        """The back-transform of the time correlations alone (psa_debug_correlation_transform): `power` (fields, P, cols)
+        float64 -- rounded to float32 first with `as_float32`, the per-vector pass's type -- ->
+        (fields, n_lags, cols) float32 = 1 / (P n_seg (L - t)) sum_o power[f, o, col] cos(2 pi o t / P)."""
+        X = np.ascontiguousarray(power, np.float64)
+        if X.ndim != 3:
+            raise ValueError(f"power {X.shape} does not fit (fields, P, cols)")
+        fields, P, cols = X.shape
+        out = np.empty((fields, max(int(n_lags), 0), cols), np.float32)
+        _check(self._lib.psa_debug_correlation_transform(self._h, X.ctypes.data_as(C.POINTER(C.c_double)), fields, P, cols, int(L),
+                                                         int(n_seg), int(n_lags), 1 if as_float32 else 0, _f32(out)),
+               "psa_debug_correlation_transform")
         return out
 
     def _modes_args(self, slot, mean_pos_all, k_vectors, groups, eigenvectors, flags):

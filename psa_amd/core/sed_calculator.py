@@ -32,6 +32,7 @@ import numpy as np
 
 from .. import _hip
 from ..io.writer import out_to_qdump
+from ..correlations import PowderTimeCorrelations, TimeCorrelations, check_boxcar, check_lags
 from ..covariance import ModeVectors, mode_vectors, spectral_weights
 from ..dynamic import DynamicSpectra
 from .. import lattice
@@ -667,6 +668,123 @@ class SEDCalculator:
         out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, False,
                                              lambda eng, listed: eng.self_spectra(inv, n, b, n_bins, listed), max_atoms, seed)
         return self._powder_result(shells, out, None, None, freqs, atoms, norm)
+
+    # ------------------------------------------------------------------ time correlations on that lattice
+    def _correlation_arguments(self, atom_weights, segments, lags, what):
+        """(weights, n_lags, times, origins) of a time-correlation call, after the refusals of `_dynamic_arguments`, of a
+        tapered window and of `lags` outside [1, L] -- all before anything is uploaded"""
+        weights = self._dynamic_arguments(atom_weights, segments, what)
+        check_boxcar(segments)
+        L, _ = self._dynamic_lengths(segments)
+        n_t = self.traj.n_frames
+        if L == 0:                                       # no frames: nothing to correlate, whatever `lags`
+            return weights, 0, np.zeros(0, np.float64), np.zeros(0, np.int64)
+        n_lags = check_lags(lags, L)
+        n_seg = 1 if segments is None else segments.count(n_t)
+        return weights, n_lags, np.arange(n_lags) * float(self.dt_ps), n_seg * (L - np.arange(n_lags, dtype=np.int64))
+
+    def calculate_lattice_correlations(self, indices: np.ndarray,
+                                       basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                       basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                       atom_weights: Optional[np.ndarray] = None, lags: Optional[int] = None,
+                                       segments: Optional[Segments] = None, currents: bool = True) -> TimeCorrelations:
+        """The intermediate scattering function F(k,t) and the current correlations C_L(k,t), C_T(k,t) on the reciprocal
+        lattice of the simulation box (not in the reference; definition in psa_amd/correlations.py): the linear,
+        unbiased time correlation of the series whose spectra `calculate_lattice_spectra` gives, at the lags
+        0 .. `lags` - 1 (default L // 2; ValueError outside [1, L]).  `segments`: a boxcar `psa_amd.Segments` -- every
+        segment is correlated on its own and the lags averaged over n_seg (L - t) time origins --, None for one segment
+        of all frames; a tapered window is refused (ValueError) before anything is uploaded.
+
+        Vectors, atom set, `atom_weights`, `currents`, residency, the empty inputs and the sharded refusal are those of
+        `calculate_lattice_spectra`.  Returns a `psa_amd.TimeCorrelations` with (n_lags, K) float32 fields."""
+        weights, n_lags, times, origins = self._correlation_arguments(atom_weights, segments, lags, "the lattice correlations")
+        n = self._lattice_indices(indices)
+        inv = lattice.box_inverse(self.traj.box_matrix)
+        k = lattice.lattice_k(n, inv)
+        mags = np.linalg.norm(k, axis=1)
+        if self._dynamic_nothing(n.shape[0], "lattice correlations"):
+            zero = np.zeros((n_lags, n.shape[0]), np.float32)
+            return TimeCorrelations(zero, zero.copy() if currents else None, zero.copy() if currents else None, times, origins,
+                                    mags, k, np.zeros(0, int), 0.0, self.dt_ps)
+        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, currents,
+                                             lambda eng, listed: eng.lattice_correlations(inv, n, n_lags, None, 0, listed, currents))
+        lon, tra = (out[1], out[2]) if currents else (None, None)
+        return TimeCorrelations(out[0], lon, tra, times, origins, mags, k, atoms, norm, self.dt_ps)
+
+    def calculate_powder_correlations(self, q_edges: np.ndarray,
+                                      basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                      basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                      atom_weights: Optional[np.ndarray] = None, lags: Optional[int] = None,
+                                      segments: Optional[Segments] = None, currents: bool = True,
+                                      max_per_bin: Optional[int] = None, seed: int = 0) -> PowderTimeCorrelations:
+        """The powder average of `calculate_lattice_correlations`: F(Q,t), C_L(Q,t), C_T(Q,t) averaged over all vectors of
+        the box's reciprocal lattice in each shell q_edges[b] <= |k| < q_edges[b + 1].  The half space is projected; the
+        mean over the full sphere is real and the half-space members alone give it.  Shells, `max_per_bin`, `seed`,
+        counts and the empty shell are those of `calculate_powder_spectra`; `lags`, `segments` and everything else those
+        of `calculate_lattice_correlations`.  Returns a `psa_amd.PowderTimeCorrelations` with (n_lags, n_bins) fields."""
+        weights, n_lags, times, origins = self._correlation_arguments(atom_weights, segments, lags, "the powder correlations")
+        shells = self._powder_shells(q_edges, max_per_bin, seed)
+
+        def result(out, atoms, norm):
+            lon, tra = (out[1], out[2]) if currents else (None, None)
+            return self._powder_correlations(shells, out[0], lon, tra, times, origins, atoms, norm)
+        n, b, n_bins, inv = shells["indices"], shells["bins"], shells["n_bins"], shells["inverse"]
+        if self._dynamic_nothing(n.shape[0], "powder correlations"):
+            return result(np.zeros((3 if currents else 1, n_lags, n_bins), np.float32), np.zeros(0, int), 0.0)
+        return result(*self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, currents,
+                                         lambda eng, listed: eng.lattice_correlations(inv, n, n_lags, b, n_bins, listed, currents)))
+
+    def _powder_correlations(self, shells, density, longitudinal, transverse, times, origins, atoms, norm):
+        return PowderTimeCorrelations(density, longitudinal, transverse, times, origins, shells["q"], shells["edges"],
+                                      2 * shells["used"], 2 * shells["available"], shells["indices"], shells["bins"], atoms, norm,
+                                      self.dt_ps)
+
+    def calculate_self_correlations(self, indices: np.ndarray,
+                                    basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                    basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                    atom_weights: Optional[np.ndarray] = None, lags: Optional[int] = None,
+                                    segments: Optional[Segments] = None, max_atoms: Optional[int] = None,
+                                    seed: int = 0) -> TimeCorrelations:
+        """The self intermediate scattering function F_s(k,t) on the reciprocal lattice of the simulation box (definition
+        in psa_amd/correlations.py): per atom the linear, unbiased time correlation of w_a exp(2 pi i n.s_a(t)), summed
+        over the atoms -- F_s(n, 0) = sum_a w_a^2 --, correct on wrapped coordinates as stored.  `lags` and `segments` as
+        for `calculate_lattice_correlations`; vectors, atom set, `atom_weights`, `max_atoms`, `seed` and everything else
+        as for `calculate_self_spectra`.  Returns a `psa_amd.TimeCorrelations` whose two current fields are None."""
+        weights, n_lags, times, origins = self._correlation_arguments(atom_weights, segments, lags, "the self correlations")
+        n = self._lattice_indices(indices)
+        inv = lattice.box_inverse(self.traj.box_matrix)
+        k = lattice.lattice_k(n, inv)
+        mags = np.linalg.norm(k, axis=1)
+        check_max_atoms(max_atoms)
+        if self._dynamic_nothing(n.shape[0], "self correlations"):
+            return TimeCorrelations(np.zeros((n_lags, n.shape[0]), np.float32), None, None, times, origins, mags, k,
+                                    np.zeros(0, int), 0.0, self.dt_ps)
+        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, False,
+                                             lambda eng, listed: eng.self_correlations(inv, n, n_lags, None, 0, listed),
+                                             max_atoms, seed)
+        return TimeCorrelations(out, None, None, times, origins, mags, k, atoms, norm, self.dt_ps)
+
+    def calculate_powder_self_correlations(self, q_edges: np.ndarray,
+                                           basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                           basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                           atom_weights: Optional[np.ndarray] = None, lags: Optional[int] = None,
+                                           segments: Optional[Segments] = None, max_per_bin: Optional[int] = None,
+                                           max_atoms: Optional[int] = None, seed: int = 0) -> PowderTimeCorrelations:
+        """The powder average of `calculate_self_correlations`: F_s(Q,t) averaged over all vectors of the box's reciprocal
+        lattice in each shell.  Shells, `max_per_bin`, counts and the empty shell are those of
+        `calculate_powder_spectra`; everything else as for `calculate_self_correlations` (`seed` serves both draws).
+        Returns a `psa_amd.PowderTimeCorrelations` whose two current fields are None."""
+        weights, n_lags, times, origins = self._correlation_arguments(atom_weights, segments, lags, "the powder self correlations")
+        shells = self._powder_shells(q_edges, max_per_bin, seed)
+        check_max_atoms(max_atoms)
+        n, b, n_bins, inv = shells["indices"], shells["bins"], shells["n_bins"], shells["inverse"]
+        if self._dynamic_nothing(n.shape[0], "powder self correlations"):
+            return self._powder_correlations(shells, np.zeros((n_lags, n_bins), np.float32), None, None, times, origins,
+                                             np.zeros(0, int), 0.0)
+        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, False,
+                                             lambda eng, listed: eng.self_correlations(inv, n, n_lags, b, n_bins, listed),
+                                             max_atoms, seed)
+        return self._powder_correlations(shells, out, None, None, times, origins, atoms, norm)
 
     # ------------------------------------------------------------------ partial (species-resolved) spectra on that lattice
     def _partial_species(self, basis_atom_indices, basis_atom_types, weights):

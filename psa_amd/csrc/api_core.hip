@@ -282,7 +282,8 @@ int psa_destroy(psa_ctx* c) {
                           &c->d_lat_idx, &c->d_lat_bins, &c->d_lat_scale, &c->d_lat_acc, &c->d_lat_out, &c->d_self_work, &c->d_self_tiles,
                           &c->d_self_ent, &c->d_self_slot, &c->d_self_idx, &c->d_self_groups, &c->d_self_scale, &c->d_self_part, &c->d_self_acc,
                           &c->d_self_out, &c->d_par_q, &c->d_par_tiles, &c->d_par_ent, &c->d_par_slot, &c->d_par_dest, &c->d_par_khat,
-                          &c->d_par_idx, &c->d_par_bins, &c->d_par_scale, &c->d_par_acc, &c->d_par_out})
+                          &c->d_par_idx, &c->d_par_bins, &c->d_par_scale, &c->d_par_acc, &c->d_par_out, &c->d_corr_tab, &c->d_corr_factor,
+                          &c->d_corr_scale, &c->d_corr_in, &c->d_corr_out})
             b->release();
         (void)hipStreamDestroy(c->stream);
     }

@@ -37,31 +37,47 @@ int dynamic_inputs(psa_ctx* c, const char* entry, int64_t K, const int32_t* idx,
     return PSA_OK;
 }
 
-// the context's segments, the sizes and the block rule of the budget
+// The transform length of a call: L for the spectra (n_lags = 0); for the time correlations the smallest power of two
+// >= L + n_lags - 1, after their refusals: 1 <= n_lags <= L, and segments (cut) only with the boxcar window.
+int correlation_length(const psa_ctx* c, bool cut, int64_t L, int64_t n_lags, int64_t* P) {
+    *P = L;
+    if (n_lags == 0) return PSA_OK;
+    PSA_REQUIRE(!cut || c->seg_boxcar, "the time correlations need the boxcar window (every value exactly 1): a tapered window "
+                "biases a correlation function");
+    PSA_REQUIRE(n_lags >= 1 && n_lags <= L, "n_lags = %lld is outside [1, L = %lld]", (long long)n_lags, (long long)L);
+    for (*P = 1; *P < L + n_lags - 1;) *P *= 2;
+    return PSA_OK;
+}
+
+// the context's segments, the sizes and the block rule of the budget (d->n_lags set: of a time-correlation call, whose
+// segment buffer holds rows of P frames where the spectra's holds L)
 int dynamic_plan(psa_ctx* c, DynCall* d) {
     const int64_t T = d->T, K = d->K;
     d->cut = c->seg_L != 0;
     d->L = d->cut ? c->seg_L : T, d->H = d->cut ? c->seg_hop : T;
     PSA_REQUIRE(d->L <= T, "segment length %lld exceeds the trajectory's %lld frames", (long long)d->L, (long long)T);
     d->n_seg = 1 + (T - d->L) / d->H;
+    PSA_TRY(correlation_length(c, d->cut, d->L, d->n_lags, &d->P));
+    // (the time correlations pad every segment to P frames: they use the segment buffer with or without segments)
+    const bool buffered = d->cut || d->n_lags != 0;
 
     // the budget: q (kb k-vectors) first, the segment buffer (units of one k-vector x one segment) from the rest
     const int64_t W = c->opt_dynamic_work_bytes;
     const int64_t series = (int64_t)d->n_species * d->NC;    // per vector
     d->per_k = series * T * (int64_t)sizeof(float2);
-    d->unit = d->cut ? series * d->L * (int64_t)sizeof(float2) : 0;
+    d->unit = buffered ? series * d->P * (int64_t)sizeof(float2) : 0;
     PSA_REQUIRE(W >= d->per_k + d->unit, "the work budget of %lld bytes (PSA_OPT_DYNAMIC_WORK_BYTES) cannot hold one k-vector: "
                 "%d series x (%lld frames + a segment of %lld) need %lld bytes", (long long)W, (int)series, (long long)T,
-                (long long)(d->cut ? d->L : 0), (long long)(d->per_k + d->unit));
+                (long long)(buffered ? d->P : 0), (long long)(d->per_k + d->unit));
     int64_t seg_bytes = 0;
-    if (d->cut) {
+    if (buffered) {
         const int64_t all = (double)K * (double)d->n_seg * (double)d->unit < 9e18 ? K * d->n_seg * d->unit : INT64_MAX;
         seg_bytes = std::min(std::min(all, std::max(d->unit, W / 8)), W - d->per_k);
     }
     // (the projection's grid: at most 65535 tiles of at least one k-vector; the passes' rows in 31 bits)
     d->kb = std::min<int64_t>({(W - seg_bytes) / d->per_k, K, 65535});
     d->bk = d->kb, d->bs = 1;
-    if (d->cut) {
+    if (buffered) {
         const int64_t units = std::min((W - d->kb * d->per_k) / d->unit, d->kb * d->n_seg);
         if (units >= d->kb) d->bs = std::min(d->n_seg, units / d->kb);
         else d->bk = units;

@@ -17,6 +17,8 @@
 //   api_lattice.hip  the same spectra on the box's reciprocal lattice, per vector or averaged over shells of |k|
 //   api_self.hip     the self (incoherent) part on that lattice: per-atom series, their power summed over the atoms
 //   api_partial.hip  the species-resolved (partial) spectra on that lattice: one projection per species, products of pairs
+//   api_correlation.hip  F(k,t), F_s(k,t), C_L(k,t), C_T(k,t) on that lattice: the spectral calls with padded segments, then
+//                    the cosine back-transform of the summed power
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
 // k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
 #pragma once
@@ -227,6 +229,7 @@ struct DynCall {
     int     n_species = 1;               // species whose NC series each vector holds (psa_partial_spectra; else 1)
     bool    cut = false;                 // false: one boxcar segment of T frames, q transformed in place
     int64_t L = 0, H = 0, n_seg = 0;
+    int64_t n_lags = 0, P = 0;           // lags of a time-correlation call (0: spectra); the FFT length: L, or the padded one
     int64_t per_k = 0, unit = 0;         // bytes of one k-vector of q; of one (k-vector, segment) of the segment buffer:
                                          // n_species NC series each
     int64_t kb = 0, bk = 0, bs = 0;      // k-vectors per block of q; k-vectors x segments per sub-block
@@ -234,6 +237,7 @@ struct DynCall {
 };
 int dynamic_inputs(psa_ctx* c, const char* entry, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents, DynCall* d);
 int dynamic_plan(psa_ctx* c, DynCall* d);
+int correlation_length(const psa_ctx* c, bool cut, int64_t L, int64_t n_lags, int64_t* P);
 // The power part of a dynamic or lattice call, shared by the run and by the debug entries (psa_debug_dynamic_power,
 // psa_debug_lattice_shell), which differ only in where the transformed segments come from.  PowerPass: what every launch of
 // the pass gets; d_bins set: the shell pass into d_acc, else dynamic.hip's power pass into d_out; n_species > 0: the pair
@@ -266,6 +270,67 @@ int  lattice_tile_entries(const int32_t* indices, const int64_t* members, int64_
 // empty bin: 0 (count: vectors per bin)
 void lattice_bins(const std::vector<int64_t>& count, double n_seg, double U, double L, std::vector<int32_t>* bin_start,
                   std::vector<double>* scale);
+// a psa_lattice_spectra call and its pieces, shared with psa_lattice_correlations (api_correlation.hip; n_lags > 0: its
+// padded plan): every refusal, the plan and the block rule; the plan's uploads; the shell form's float64 accumulator,
+// zeroed; block b of the plan over all frames into d_q (nk, NC, T)
+struct LatCall {
+    DynCall  d;                                      // sizes, segments, block rule (kappa unused; khat in row order)
+    bool     shell = false;
+    int64_t  n_bins = 0;
+    float    box_hi[9], box_lo[9];
+    std::vector<int64_t>  block_tile0;               // first tile of block b (n_blocks + 1)
+    std::vector<int32_t>  tile_off, dest;            // (n_tiles + 1); (n_tiles LAT_KS)
+    std::vector<uint16_t> ent;
+    std::vector<uint32_t> slot;                      // (n_tiles LAT_KS)
+    std::vector<int64_t>  count;                     // (n_bins) vectors per bin
+    std::vector<int32_t>  bin_start;                 // (n_bins + 1) in the processing order
+    std::vector<double>   scale;                     // (n_bins) 1 / (2 n_half n_seg U L^2); an empty bin: 0
+};
+int lattice_check(psa_ctx* c, const char* entry, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of,
+                  int64_t n_bins, const int32_t* idx, int64_t n_g, int32_t currents, int64_t n_lags, LatCall* p);
+int lattice_upload(psa_ctx* c, const LatCall& p, const int32_t* idx);
+int lattice_shell_begin(psa_ctx* c, size_t bytes, double** d_acc);
+int lattice_project(psa_ctx* c, const LatCall& p, const int32_t* idx, int64_t block, float2* d_q);
+// api_self.hip: a psa_self_spectra call and its pieces, shared with psa_self_correlations in the same way
+struct SelfCall {
+    DynCall  d;                                      // T, N, K, n_g (the rest unused)
+    bool     cut = false, shell = false;
+    int64_t  L = 0, H = 0, n_seg = 0, cols = 0;
+    int64_t  P = 0;                                  // the rows of the work buffer and the FFT: L, or the padded length
+    float    box_hi[9], box_lo[9];
+    std::vector<int64_t>  order;                     // the processing order: places in the caller's list
+    std::vector<int32_t>  tile;                      // (2 (n_tiles + 1)): per tile its offset into ent, its first vector
+    std::vector<uint16_t> ent;
+    std::vector<uint32_t> slot;                      // (K) in the processing order
+    std::vector<int32_t>  groups;                    // (2 (n_groups + 1)): first vector, column; the last pair ends the list
+    std::vector<int64_t>  count;                     // (n_bins) vectors per bin (shell form)
+    std::vector<double>   scale;                     // (cols)
+    int64_t  n_tiles = 0, kt_max = 0, n_groups = 0;
+    int64_t  at = 0, vt = 0, bs = 0;                 // atom tiles, vector tiles, segments per block
+};
+// every refusal, the plan and the block rule; `segments`: the context's segments are honoured (false: one boxcar
+// segment of T frames, whatever the context holds -- the series before the window); n_lags > 0: a time-correlation call
+int self_check(psa_ctx* c, const char* entry, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of,
+               int64_t n_bins, const int32_t* idx, int64_t n_g, bool segments, int64_t n_lags, SelfCall* p);
+int self_upload(psa_ctx* c, const SelfCall& p, const int32_t* idx, bool columns);
+// atoms [a0, a0 + na) x tiles [t0, t0 + nt) x segments [s0, s0 + ns) into d_work (na, nv, ns, P)
+int self_series(psa_ctx* c, const SelfCall& p, const int32_t* idx, int64_t a0, int64_t na, int64_t t0, int64_t nt, int64_t s0, int64_t ns,
+                float2* d_work);
+// The power part of a self call, shared by self_run, psa_debug_self_power and psa_self_correlations, which differ only in
+// where the transformed series come from: the float64 accumulator (L, cols), zeroed; per block of Ab atoms x the vectors
+// [vcut[b], vcut[b + 1]) of the processing order x bs segments the columns the block touches, the chunk rule, the power and
+// reduce launches; with `finish` the finish pass into d_self_out (else the sums stay in d_self_acc).  The groups table
+// (2 (n_groups + 1)) and the columns' scales are on the device already.  `fill` leaves the transformed block
+// (na, nv, ns, L) on the device and says where.
+struct SelfPower {
+    int64_t        L = 0, n_seg = 0, n_atoms = 0, cols = 0, n_groups = 0;
+    const int32_t* groups = nullptr;                 // the host's copy
+    bool           mirror = false, finish = true;
+    int64_t        Ab = 0, bs = 0, n_chunks = 0;     // atoms and segments per block; chunks of a block's atoms (0: the rule)
+    const std::vector<int64_t>* vcut = nullptr;
+};
+using SelfFill = std::function<int(int64_t a0, int64_t na, int64_t vb, int64_t s0, int64_t ns, const float2** d_work)>;
+int self_power_run(psa_ctx* c, const SelfPower& w, const SelfFill& fill);
 int    check_weights(psa_ctx* c, int64_t N);            // the context's atom weights fit a slot of N atoms
 void   set_geom_weights(const psa_ctx* c, ProjGeom* g);  // ... and go into a launch's geometry
 int    begin_result(psa_ctx* c, int64_t T, int64_t K_total, int64_t k_offset, bool intensity, char** rows);

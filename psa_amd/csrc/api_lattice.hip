@@ -102,31 +102,17 @@ void lattice_bins(const std::vector<int64_t>& count, double n_seg, double U, dou
     }
 }
 
-namespace {
-
-struct LatCall {
-    DynCall  d;                                      // sizes, segments, block rule (kappa unused; khat in row order)
-    bool     shell = false;
-    int64_t  n_bins = 0;
-    float    box_hi[9], box_lo[9];
-    std::vector<int64_t>  block_tile0;               // first tile of block b (n_blocks + 1)
-    std::vector<int32_t>  tile_off, dest;            // (n_tiles + 1); (n_tiles LAT_KS)
-    std::vector<uint16_t> ent;
-    std::vector<uint32_t> slot;                      // (n_tiles LAT_KS)
-    std::vector<int32_t>  bin_start;                 // (n_bins + 1) in the processing order
-    std::vector<double>   scale;                     // (n_bins) 1 / (2 n_half n_seg U L^2); an empty bin: 0
-};
-
-int lattice_check(psa_ctx* c, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t n_bins,
-                  const int32_t* idx, int64_t n_g, int32_t currents, LatCall* p) {
+int lattice_check(psa_ctx* c, const char* entry, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of,
+                  int64_t n_bins, const int32_t* idx, int64_t n_g, int32_t currents, int64_t n_lags, LatCall* p) {
     PSA_REQUIRE(box_inverse != nullptr, "null box_inverse");
     PSA_REQUIRE(indices != nullptr, "null indices");
     DynCall& d = p->d;
-    PSA_TRY(dynamic_inputs(c, "psa_lattice_spectra", K, idx, n_g, currents, &d));
+    PSA_TRY(dynamic_inputs(c, entry, K, idx, n_g, currents, &d));
     PSA_TRY(lattice_inputs(box_inverse, indices, K, bin_of, n_bins));
     const double* B = box_inverse;
     p->shell = bin_of != nullptr;
     p->n_bins = p->shell ? n_bins : 0;
+    d.n_lags = n_lags;
     PSA_TRY(dynamic_plan(c, &d));
 
     lattice_box_parts(B, p->box_hi, p->box_lo);
@@ -167,9 +153,9 @@ int lattice_check(psa_ctx* c, const double* box_inverse, const int32_t* indices,
     PSA_REQUIRE(p->ent.size() < (1ull << 31) && p->tile_off.size() < (1ull << 22), "the vector list needs too many tiles");
 
     if (p->shell) {
-        std::vector<int64_t> count((size_t)n_bins, 0);
-        for (int64_t k = 0; k < K; ++k) ++count[(size_t)bin_of[k]];
-        lattice_bins(count, (double)d.n_seg, d.cut ? c->seg_U : 1.0, (double)d.L, &p->bin_start, &p->scale);
+        p->count.assign((size_t)n_bins, 0);
+        for (int64_t k = 0; k < K; ++k) ++p->count[(size_t)bin_of[k]];
+        lattice_bins(p->count, (double)d.n_seg, d.cut ? c->seg_U : 1.0, (double)d.L, &p->bin_start, &p->scale);
     }
     return PSA_OK;
 }
@@ -196,10 +182,14 @@ int lattice_shell_begin(psa_ctx* c, size_t bytes, double** d_acc) {
     PSA_HIP_CHECK(hipMemsetAsync(*d_acc, 0, bytes, c->stream));
     return PSA_OK;
 }
+namespace {
+
 int lattice_shell_finish(psa_ctx* c, int64_t rows, int64_t L, int64_t n_bins, float* d_out) {
     StageTimer st(c, PSA_T_EPILOGUE);
     return launch_lattice_finish(c, c->d_lat_acc.as<double>(), c->d_lat_scale.as<double>(), d_out, rows * L * n_bins, n_bins);
 }
+
+}  // namespace
 
 // block b of the plan over all frames into d_q (nk, NC, T)
 int lattice_project(psa_ctx* c, const LatCall& p, const int32_t* idx, int64_t block, float2* d_q) {
@@ -213,11 +203,13 @@ int lattice_project(psa_ctx* c, const LatCall& p, const int32_t* idx, int64_t bl
                                   p.block_tile0[(size_t)block + 1] - p.block_tile0[(size_t)block], d.NC == 4);
 }
 
+namespace {
+
 int lattice_run(psa_ctx* c, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t n_bins,
                 const int32_t* idx, int64_t n_g, int32_t currents, float* out_host, size_t out_bytes) {
     PSA_REQUIRE(out_host != nullptr, "null output");
     LatCall p;
-    PSA_TRY(lattice_check(c, box_inverse, indices, K, bin_of, n_bins, idx, n_g, currents, &p));
+    PSA_TRY(lattice_check(c, "psa_lattice_spectra", box_inverse, indices, K, bin_of, n_bins, idx, n_g, currents, 0, &p));
     const DynCall& d = p.d;
     const int64_t  L = d.L, T = d.T, rows = currents ? 3 : 1, cols = p.shell ? n_bins : K;
     const size_t   want = (size_t)rows * (size_t)L * (size_t)cols * sizeof(float);
@@ -273,7 +265,7 @@ int lattice_debug_project(psa_ctx* c, const double* box_inverse, const int32_t* 
                           int32_t currents, void* out_host) {
     PSA_REQUIRE(out_host != nullptr, "null output");
     LatCall p;
-    PSA_TRY(lattice_check(c, box_inverse, indices, K, nullptr, 0, idx, n_g, currents, &p));
+    PSA_TRY(lattice_check(c, "psa_lattice_spectra", box_inverse, indices, K, nullptr, 0, idx, n_g, currents, 0, &p));
     const DynCall& d = p.d;
     if (d.n_g == 0) {
         std::memset(out_host, 0, (size_t)K * (size_t)d.per_k);

@@ -607,9 +607,11 @@ int psa_set_segments(psa_ctx* c, int64_t L, int64_t hop, const float* window) {
     PSA_REQUIRE(hop >= 1, "segment hop %lld < 1", (long long)hop);
     PSA_REQUIRE(window != nullptr, "null window");
     double u = 0.0;
+    bool   boxcar = true;
     for (int64_t t = 0; t < L; ++t) {
         PSA_REQUIRE(std::isfinite(window[t]), "window value %lld is not finite", (long long)t);
         u += (double)window[t] * (double)window[t];
+        boxcar = boxcar && window[t] == 1.0f;
     }
     u /= (double)L;
     PSA_REQUIRE(u > 0.0, "the window is zero everywhere (U = 0)");
@@ -619,6 +621,7 @@ int psa_set_segments(psa_ctx* c, int64_t L, int64_t hop, const float* window) {
     c->seg_L = L;
     c->seg_hop = hop;
     c->seg_U = u;
+    c->seg_boxcar = boxcar;
     return PSA_OK;
 }
 

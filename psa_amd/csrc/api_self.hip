@@ -18,27 +18,8 @@
 
 namespace psa {
 
-namespace {
-
-struct SelfCall {
-    DynCall  d;                                      // T, N, K, n_g (the rest unused)
-    bool     cut = false, shell = false;
-    int64_t  L = 0, H = 0, n_seg = 0, cols = 0;
-    float    box_hi[9], box_lo[9];
-    std::vector<int64_t>  order;                     // the processing order: places in the caller's list
-    std::vector<int32_t>  tile;                      // (2 (n_tiles + 1)): per tile its offset into ent, its first vector
-    std::vector<uint16_t> ent;
-    std::vector<uint32_t> slot;                      // (K) in the processing order
-    std::vector<int32_t>  groups;                    // (2 (n_groups + 1)): first vector, column; the last pair ends the list
-    std::vector<double>   scale;                     // (cols)
-    int64_t  n_tiles = 0, kt_max = 0, n_groups = 0;
-    int64_t  at = 0, vt = 0, bs = 0;                 // atom tiles, vector tiles, segments per block
-};
-
-// every refusal, the plan and the block rule; `segments`: the context's segments are honoured (false: one boxcar
-// segment of T frames, whatever the context holds -- the series before the window)
 int self_check(psa_ctx* c, const char* entry, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of,
-               int64_t n_bins, const int32_t* idx, int64_t n_g, bool segments, SelfCall* p) {
+               int64_t n_bins, const int32_t* idx, int64_t n_g, bool segments, int64_t n_lags, SelfCall* p) {
     PSA_REQUIRE(box_inverse != nullptr, "null box_inverse");
     PSA_REQUIRE(indices != nullptr, "null indices");
     DynCall& d = p->d;
@@ -52,6 +33,7 @@ int self_check(psa_ctx* c, const char* entry, const double* box_inverse, const i
     p->L = p->cut ? c->seg_L : T, p->H = p->cut ? c->seg_hop : T;
     PSA_REQUIRE(p->L <= T, "segment length %lld exceeds the trajectory's %lld frames", (long long)p->L, (long long)T);
     p->n_seg = 1 + (T - p->L) / p->H;
+    PSA_TRY(correlation_length(c, p->cut, p->L, n_lags, &p->P));
     lattice_box_parts(box_inverse, p->box_hi, p->box_lo);
     lattice_order(indices, K, bin_of, K, &p->order);
 
@@ -81,7 +63,8 @@ int self_check(psa_ctx* c, const char* entry, const double* box_inverse, const i
     // columns
     const double U = p->cut ? c->seg_U : 1.0, norm = (double)p->n_seg * U * (double)p->L * (double)p->L;
     if (p->shell) {
-        std::vector<int64_t> count((size_t)n_bins, 0);
+        std::vector<int64_t>& count = p->count;
+        count.assign((size_t)n_bins, 0);
         for (int64_t k = 0; k < K; ++k) ++count[(size_t)bin_of[k]];
         p->scale.assign((size_t)n_bins, 0.0);
         int64_t first = 0;
@@ -103,11 +86,11 @@ int self_check(psa_ctx* c, const char* entry, const double* box_inverse, const i
 
     // the block rule
     const int64_t W = c->opt_dynamic_work_bytes;
-    const int64_t unit = (int64_t)SELF_ATOMS * p->kt_max * p->L * (int64_t)sizeof(float2);
+    const int64_t unit = (int64_t)SELF_ATOMS * p->kt_max * p->P * (int64_t)sizeof(float2);
     const int64_t units = W / unit;
     PSA_REQUIRE(units >= 1, "the work budget of %lld bytes (PSA_OPT_DYNAMIC_WORK_BYTES) cannot hold the smallest block: %d atoms x "
                 "%lld vectors x one segment of %lld frames need %lld bytes", (long long)W, SELF_ATOMS, (long long)p->kt_max,
-                (long long)p->L, (long long)unit);
+                (long long)p->P, (long long)unit);
     const int64_t n_at = (d.n_g + SELF_ATOMS - 1) / SELF_ATOMS;
     p->at = std::max<int64_t>(1, std::min<int64_t>({n_at, units, 65535}));
     p->vt = std::min<int64_t>({p->n_tiles, units / p->at, 65535});
@@ -132,7 +115,6 @@ int self_upload(psa_ctx* c, const SelfCall& p, const int32_t* idx, bool columns)
     return PSA_OK;
 }
 
-// atoms [a0, a0 + na) x tiles [t0, t0 + nt) x segments [s0, s0 + ns) into d_work (na, nv, ns, L)
 int self_series(psa_ctx* c, const SelfCall& p, const int32_t* idx, int64_t a0, int64_t na, int64_t t0, int64_t nt, int64_t s0, int64_t ns,
                 float2* d_work) {
     StageTimer    st(c, PSA_T_TRANSPOSE);
@@ -140,22 +122,8 @@ int self_series(psa_ctx* c, const SelfCall& p, const int32_t* idx, int64_t a0, i
     return launch_self_series(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), c->weights_N ? c->d_weights.as<float>() : nullptr,
                               idx ? c->d_self_idx.as<int>() : nullptr, a0, p.box_hi, p.box_lo, c->d_self_tiles.as<int>(),
                               c->d_self_ent.as<unsigned short>(), c->d_self_slot.as<unsigned>(),
-                              p.cut ? c->d_seg_window.as<float>() : nullptr, d_work, p.d.T, p.d.N, na, t0, nt, v0, nv, p.L, p.H, s0, ns);
+                              p.cut ? c->d_seg_window.as<float>() : nullptr, d_work, p.d.T, p.d.N, na, t0, nt, v0, nv, p.L, p.H, s0, ns, p.P);
 }
-
-// The power part of a self call, shared by self_run and psa_debug_self_power, which differ only in where the transformed
-// series come from: the float64 accumulator (L, cols), zeroed; per block of Ab atoms x the vectors [vcut[b], vcut[b + 1]) of
-// the processing order x bs segments the columns the block touches, the chunk rule, the power and reduce launches; the
-// finish pass into d_self_out.  The groups table (2 (n_groups + 1)) and the columns' scales are on the device already.
-// `fill` leaves the transformed block (na, nv, ns, L) on the device and says where.
-struct SelfPower {
-    int64_t        L = 0, n_seg = 0, n_atoms = 0, cols = 0, n_groups = 0;
-    const int32_t* groups = nullptr;                 // the host's copy
-    bool           mirror = false;
-    int64_t        Ab = 0, bs = 0, n_chunks = 0;     // atoms and segments per block; chunks of a block's atoms (0: the rule)
-    const std::vector<int64_t>* vcut = nullptr;
-};
-using SelfFill = std::function<int(int64_t a0, int64_t na, int64_t vb, int64_t s0, int64_t ns, const float2** d_work)>;
 
 int self_power_run(psa_ctx* c, const SelfPower& w, const SelfFill& fill) {
     const int64_t L = w.L, cols = w.cols;
@@ -192,15 +160,18 @@ int self_power_run(psa_ctx* c, const SelfPower& w, const SelfFill& fill) {
             }
         }
     }
+    if (!w.finish) return PSA_OK;
     StageTimer st(c, PSA_T_EPILOGUE);
     return launch_lattice_finish(c, d_acc, c->d_self_scale.as<double>(), c->d_self_out.as<float>(), L * cols, cols);
 }
+
+namespace {
 
 int self_run(psa_ctx* c, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t n_bins,
              const int32_t* idx, int64_t n_g, float* out_host, size_t out_bytes) {
     PSA_REQUIRE(out_host != nullptr, "null output");
     SelfCall p;
-    PSA_TRY(self_check(c, "psa_self_spectra", box_inverse, indices, K, bin_of, n_bins, idx, n_g, true, &p));
+    PSA_TRY(self_check(c, "psa_self_spectra", box_inverse, indices, K, bin_of, n_bins, idx, n_g, true, 0, &p));
     const int64_t L = p.L, cols = p.cols;
     const size_t  want = (size_t)L * (size_t)cols * sizeof(float);
     PSA_REQUIRE(out_bytes == want, "out_bytes is %zu, the (%lld,%lld) float32 result has %zu", out_bytes, (long long)L, (long long)cols,
@@ -240,7 +211,7 @@ int self_debug_series(psa_ctx* c, const double* box_inverse, const int32_t* indi
                       void* out_host) {
     PSA_REQUIRE(out_host != nullptr, "null output");
     SelfCall p;
-    PSA_TRY(self_check(c, "psa_debug_self_series", box_inverse, indices, K, nullptr, 0, idx, n_g, false, &p));
+    PSA_TRY(self_check(c, "psa_debug_self_series", box_inverse, indices, K, nullptr, 0, idx, n_g, false, 0, &p));
     if (p.d.n_g == 0) return PSA_OK;
     PSA_TRY(self_upload(c, p, idx, false));
     const int64_t T = p.d.T, Ab = p.at * SELF_ATOMS, nv_max = std::min(K, p.vt * p.kt_max);

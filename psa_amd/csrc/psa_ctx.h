@@ -266,6 +266,7 @@ struct psa_ctx {
     psa::DevBuf  d_seg_window, d_seg;
     int64_t      seg_L = 0, seg_hop = 0;
     double       seg_U = 0.0;
+    bool         seg_boxcar = false;                   // every window value is exactly 1.0f (the correlations need it)
 
     // vibrational density of states (psa_vdos, api_vdos.hip): the work buffer of one (atom block x segment block) is held
     // to opt_vdos_work_bytes (PSA_OPT_VDOS_WORK_BYTES); the pair list, the groups' pair offsets, the mean, the chunk
@@ -317,6 +318,12 @@ struct psa_ctx {
     // float64 accumulator (1 or 3, P, L, n_bins); the float32 result (1 or 3, P, L, K or n_bins).  All kept between calls.
     psa::DevBuf  d_par_q, d_par_tiles, d_par_ent, d_par_slot, d_par_dest, d_par_khat, d_par_idx, d_par_bins, d_par_scale,
                  d_par_acc, d_par_out;
+
+    // time correlations on that lattice (psa_lattice_correlations, psa_self_correlations; api_correlation.hip): they run
+    // the spectral calls' buffers with zero-padded rows of P >= L + n_lags - 1 and add the back-transform's cosine table
+    // (P float64), the lag factors (n_lags float64), the columns' scales (cols float64), the debug entry's uploaded power
+    // and the float32 result (1 or 3, n_lags, K or n_bins).  All kept between calls.
+    psa::DevBuf  d_corr_tab, d_corr_factor, d_corr_scale, d_corr_in, d_corr_out;
 
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
@@ -518,19 +525,33 @@ constexpr int SELF_FRAMES = 64;        // frames of a frame tile: consecutive la
 constexpr int SELF_ENTRIES = 24;       // most distinct (axis, m) pairs of a vector tile: the table is 512 B per atom and entry
 constexpr int SELF_KS = 64;            // most vectors of a vector tile
 // Series of one block: atoms [0, na) of the list d_idx (null: atoms a0 + i) x the vectors of tiles [tile0, tile0 + n_tiles) x
-// segments [s0, s0 + ns) -> work (na, nv, ns, L) complex64, nv the block's vectors, = win[l] w_a E_1 E_2 E_3 at frame
-// s H + l.  d_tile (2 (n_tiles_all + 1)): offsets of every tile into d_ent and into d_slot; v0: the block's first vector.
+// segments [s0, s0 + ns) -> work (na, nv, ns, pitch) complex64, nv the block's vectors, = win[l] w_a E_1 E_2 E_3 at frame
+// s H + l, l < L <= pitch (the spectra: pitch = L; the time correlations: pitch = P, the tail left to their padding pass).  d_tile (2 (n_tiles_all + 1)): offsets of every tile into d_ent and into d_slot; v0: the block's first vector.
 // d_weights, d_idx, d_win may be null (unit weights, atoms in order, no window).
 int launch_self_series(psa_ctx* c, const float* d_pos, const float* d_weights, const int* d_idx, int64_t a0, const float* box_hi,
                        const float* box_lo, const int* d_tile, const unsigned short* d_ent, const unsigned* d_slot, const float* d_win,
                        float2* d_work, int64_t T, int64_t N, int64_t na, int64_t tile0, int64_t n_tiles, int64_t v0, int64_t nv,
-                       int64_t L, int64_t H, int64_t s0, int64_t ns);
+                       int64_t L, int64_t H, int64_t s0, int64_t ns, int64_t pitch);
 // After the FFT of work (na, nv, ns, L), the block's vectors being v0 .. v0 + nv - 1 of the processing order: column group
 // g in [g_first, g_first + ng) owns the vectors d_groups[2 g] .. d_groups[2 g + 2] - 1 and the column d_groups[2 g + 1] of
 // acc (L, cols) float64 += sum over its vectors in the block, the atoms and the segments of |Z[o]|^2 (mirror: + |Z[(L - o)
 // mod L]|^2), through n_chunks partial sums over atom chunks, added in order (d_part: n_chunks ng L float64)
 int launch_self_power(psa_ctx* c, const float2* d_work, const int* d_groups, double* d_part, double* d_acc, int64_t L, int64_t ns,
                       int64_t na, int64_t v0, int64_t nv, int64_t g_first, int64_t ng, int64_t cols, int64_t n_chunks, bool mirror);
+// --- correlation.hip (psa_lattice_correlations, psa_self_correlations: the zero padding before the FFT and the float64
+// cosine back-transform of the summed power; the arithmetic and the layouts are in its header)
+constexpr int CORR_LAGS = 8;           // lags one lane of the column form carries
+constexpr int CORR_COLS_MIN = 64;      // columns from which the lanes go over columns; below, over lags
+// rows [0, n_rows) of d_q (n_rows, T) x segments [s0, s0 + ns) -> d_seg (n_rows, ns, P): bit copies of the L frames from
+// (s0 + s) H, zeros in [L, P).  d_q null: only the tails [L, P) of d_seg are written (the rows' heads are there already)
+int launch_correlation_pad(psa_ctx* c, const float2* d_q, float2* d_seg, int64_t T, int64_t L, int64_t P, int64_t H, int64_t s0,
+                           int64_t ns, int64_t n_rows);
+// out (fields, n_lags, cols) float32 = (float)(factor[t] scale[col] sum_o X[f, o, col] tab[(o t) mod P]), X (fields, P, cols)
+// float64 or float32, tab (P) = cos(2 pi j / P), factor (n_lags), scale (cols; null: 1) float64
+int launch_correlation_transform(psa_ctx* c, const double* d_X, const double* d_tab, const double* d_factor, const double* d_scale,
+                                 float* d_out, int64_t fields, int64_t P, int64_t cols, int64_t n_lags);
+int launch_correlation_transform(psa_ctx* c, const float* d_X, const double* d_tab, const double* d_factor, const double* d_scale,
+                                 float* d_out, int64_t fields, int64_t P, int64_t cols, int64_t n_lags);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 

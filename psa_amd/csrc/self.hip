@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(SELF_THREADS)
 self_series_kernel(const float* __restrict__ pos, const float* __restrict__ wgt, const int* __restrict__ idx, int64_t a0,
                    const LatBox box, const int* __restrict__ tile, const unsigned short* __restrict__ ent,
                    const unsigned* __restrict__ slot, const float* __restrict__ win, float2* __restrict__ work, int64_t N, int na,
-                   int tile0, int v0, int nv, int64_t L, int64_t H, int64_t s0, int ns, int n_ft) {
+                   int tile0, int v0, int nv, int64_t L, int64_t H, int64_t s0, int ns, int n_ft, int64_t pitch) {
     __shared__ float2 tab[SELF_ATOMS][SELF_ENTRIES][SELF_FRAMES];
     const int     wave = threadIdx.x / SELF_FRAMES, lane = threadIdx.x % SELF_FRAMES;
     const int     tl = tile0 + blockIdx.z;
@@ -97,8 +97,8 @@ self_series_kernel(const float* __restrict__ pos, const float* __restrict__ wgt,
 
     // series
     const float wv = win ? win[l] : 1.f;
-    float2*     dst = work + (((int64_t)al * nv + (p0 - v0)) * ns + s) * L + l;
-    for (int v = 0; v < nt; ++v, dst += (int64_t)ns * L) {
+    float2*     dst = work + (((int64_t)al * nv + (p0 - v0)) * ns + s) * pitch + l;
+    for (int v = 0; v < nt; ++v, dst += (int64_t)ns * pitch) {
         const unsigned u = slot[p0 + v];                                   // < R each
         const float2   E = lat_cmul(lat_cmul(mine[u & 511][lane], mine[(u >> 9) & 511][lane]), mine[(u >> 18) & 511][lane]);
         const float    re = __fmul_rn(w, E.x), im = __fmul_rn(w, E.y);
@@ -155,10 +155,10 @@ self_reduce_kernel(const double* __restrict__ part, const int* __restrict__ grou
 int launch_self_series(psa_ctx* c, const float* d_pos, const float* d_weights, const int* d_idx, int64_t a0, const float* box_hi,
                        const float* box_lo, const int* d_tile, const unsigned short* d_ent, const unsigned* d_slot, const float* d_win,
                        float2* d_work, int64_t T, int64_t N, int64_t na, int64_t tile0, int64_t n_tiles, int64_t v0, int64_t nv,
-                       int64_t L, int64_t H, int64_t s0, int64_t ns) {
+                       int64_t L, int64_t H, int64_t s0, int64_t ns, int64_t pitch) {
     if (na == 0 || n_tiles == 0 || ns == 0) return PSA_OK;
     const int64_t n_ft = (L + SELF_FRAMES - 1) / SELF_FRAMES, gx = n_ft * ns, gy = (na + SELF_ATOMS - 1) / SELF_ATOMS;
-    PSA_REQUIRE(L >= 1 && H >= 1 && s0 >= 0 && (s0 + ns - 1) * H + L <= T, "segment block outside the trajectory");
+    PSA_REQUIRE(L >= 1 && H >= 1 && s0 >= 0 && (s0 + ns - 1) * H + L <= T && pitch >= L, "segment block outside the trajectory");
     PSA_REQUIRE(gx < (1ll << 31) && gy <= 65535 && n_tiles <= 65535 && tile0 >= 0 && tile0 + n_tiles < (1ll << 30) && a0 >= 0 &&
                     a0 + na <= (1ll << 31) - 1 && N < (1ll << 31) && v0 >= 0 && v0 + nv < (1ll << 31) && ns < (1ll << 31),
                 "self series outside its grid");
@@ -166,7 +166,7 @@ int launch_self_series(psa_ctx* c, const float* d_pos, const float* d_weights, c
     for (int i = 0; i < 9; ++i) box.hi[i] = box_hi[i], box.lo[i] = box_lo[i];
     hipLaunchKernelGGL(self_series_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)n_tiles), dim3(SELF_THREADS), 0, c->stream, d_pos,
                        d_weights, d_idx, a0, box, d_tile, d_ent, d_slot, d_win, d_work, N, (int)na, (int)tile0, (int)v0, (int)nv, L, H, s0,
-                       (int)ns, (int)n_ft);
+                       (int)ns, (int)n_ft, pitch);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;
 }
