@@ -651,6 +651,66 @@ int psa_self_correlations(psa_ctx* ctx, const double* box_inverse /* 9 */, const
                           const int32_t* bin_of /* K or NULL */, int64_t n_bins, const int32_t* idx, int64_t n_g, int64_t n_lags,
                           float* out_host /* (n_lags, K or n_bins) */, size_t out_bytes);
 
+/* Real-space self dynamics: the moments of the displacement (mean-square displacement, non-Gaussian parameter) and the
+ * self van Hove function of atom groups, from the positions resident in PSA_SLOT_POSITIONS as stored, wrapped or not.
+ * H = box (9 doubles, rows = box vectors, r = s H), Hinv = box_inverse, the convention of psa_lattice_spectra.
+ *
+ * Unwrapping, float64 from the float32 positions:  d[t,a,:] = (r[t,a] - r[t-1,a]) Hinv (t >= 1),  m[t,a,j] = rint(d_j),
+ *     n[t,a] = -sum_{t' <= t} m[t',a]  (int32 image counts, n[0] = 0),   u[t,a] = (r[t,a] - r[0,a]) + n[t,a] H.
+ * Contract: no atom moves half a box length or more along a box axis between two stored frames -- the only convention
+ * possible without image flags.  On an unwrapped trajectory m = 0 and u = r(t) - r(0).  unwrap = 0 skips the image search:
+ * u = r(t) - r(0).  As evaluated (msd.hip): d_j = fma(e_z, Hinv[2][j], fma(e_y, Hinv[1][j], e_x Hinv[0][j])) with
+ * e = r[t] - r[t-1], and u_c = fma(n_2, H[2][c], fma(n_1, H[1][c], fma(n_0, H[0][c], r_c[t] - r_c[0]))): four roundings, so
+ *     |u - u_exact| <= 4 2^-53 (|r_c(t) - r_c(0)| + sum_j |n_j| |H_jc|).
+ * The image counts are integer sums over tiles of 64 frames, a scan over the tiles and a scan inside each tile: they do not
+ * depend on how the pass is cut.
+ *
+ * Groups g = 0 .. G-1, G <= 8: idx holds their atoms one group after the other, group_start (G + 1) their offsets; the
+ * groups are disjoint, a group may be empty; idx NULL: one group of all N atoms (n_groups = 1, group_start unused).
+ * Lags t = 0 .. n_lags-1, 1 <= n_lags <= T; origins O_t = {0, s, 2 s, ...: o + t <= T-1}, s = origin_step >= 1,
+ * n_o(t) = (T-1-t) / s + 1 (integer division).  With D = u[o+t,a] - u[o,a]:
+ *     M2_c[t,g] = 1/(N_g n_o) sum_{a in g} sum_{o in O_t} D_c^2  (c = x, y, z),   M4[t,g] = 1/(N_g n_o) sum sum (D_x^2+D_y^2+D_z^2)^2
+ * out_host (n_lags, G, 4) float64: M2_x, M2_y, M2_z, M4; an empty group gives zeros.  The caller forms msd = sum_c M2_c and
+ * alpha_2 = 3 M4 / (5 msd^2) - 1.
+ * A direct sum over origins, no FFT.  u is stored as float64 (n_a, 3, T); the moments kernel takes a tile of 256 lags (one
+ * per lane) and origin tiles of at most 1024 origins, and per atom stages float32(u[f] - u[o_0]), o_0 the tile's first
+ * origin (float64 subtraction, one rounding), for at most 1280 frames, so a staged value has the size of the excursion
+ * since o_0, not of the total displacement.  Per (lag, origin) in float32, each operation rounded once:
+ *     D_c = b_c - a_c;   q_c = D_c D_c;   r2 = fma(D_z, D_z, fma(D_y, D_y, q_x));   M2_c += (double) q_c;   M4 += (double)(r2 r2)
+ * the sums in float64 over origins, atoms, chunks of atoms and blocks, in a fixed order; the last pass divides by
+ * N_g n_o(t) in float64.  No atomics: two identical calls give the same bits; another blocking regroups the float64 sums.
+ * Budget (PSA_OPT_DYNAMIC_WORK_BYTES): u of a block, 24 T bytes per atom; a block is a whole number of atoms; a budget
+ * below one atom is refused and the refusal names the bytes needed.  The partial sums, the accumulator and the result lie
+ * outside it.
+ * PSA_EINVAL: a null pointer, no positions resident, a box or inverse that is not finite, a singular box, an inverse that
+ * is not the box's, n_groups outside [1, 8], offsets that do not begin at 0 or are not ascending, an atom in two groups, an
+ * index outside [0, N), n_lags outside [1, T], origin_step < 1, unwrap not 0 or 1, out_bytes not exact, a budget below one
+ * atom, a sharded context (psa_comm_init).
+ * Only the positions slot is read.  Atom weights and segments set on the context are ignored, not refused; the slab, the
+ * k map, the plane cache, the K1 selection, the FFT plans and every result of the other entry points are left as they
+ * are.  Stage times go to psa_last_timings: [5] unwrap, [6] the moments kernel, [4] reduce and finish, [7] device->host. */
+int psa_displacement_moments(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                             const int64_t* group_start /* G+1 */, int32_t n_groups, int64_t n_lags, int64_t origin_step,
+                             int32_t unwrap, double* out_host /* (n_lags, G, 4): M2x, M2y, M2z, M4 */, size_t out_bytes);
+
+/* The self van Hove function as counts: for the lags tau_j (n_vh <= 64 of them, each in [0, T-1]), the bin width dr > 0 and
+ * 1 <= n_r <= 1024 bins,  counts[j,g,i] = number of (a in g, o in O_{tau_j}) with i = floor(|D| / dr) < n_r, and
+ * counts[j,g,n_r] the overflow count; uint64, so sum_i counts[j,g,:] = N_g n_o(tau_j) exactly.  Unwrapping, groups,
+ * origins and the budget are those of psa_displacement_moments.  D and r2 are formed as there from a_c = float32(u_c[o] -
+ * u_c[o_0]) and b_c = float32(u_c[o+tau] - u_c[o_0]), o_0 the first origin of the same origin tiles; then
+ *     r = sqrt(r2) (rounded once);   x = r inv_dr (rounded once), inv_dr the float32 nearest to 1/dr;
+ *     bin = x < n_r ? (int) floorf(x) : n_r.
+ * Per workgroup a histogram in LDS with 32-bit integer adds -- the host keeps a workgroup's samples below 2^32 --, written
+ * to partials with plain stores and summed in 64-bit integers: integer adds commute, so the counts are bit-identical
+ * whatever the order and the blocking.  PSA_EINVAL: everything psa_displacement_moments refuses about the context, the
+ * box, the groups, origin_step, unwrap and the budget; n_vh outside [1, 64]; a lag outside [0, T-1]; dr <= 0 or not finite;
+ * n_r outside [1, 1024]; out_bytes not exact.  Stage times: [5] unwrap, [6] the histogram kernel, [4] reduce,
+ * [7] device->host. */
+int psa_van_hove_self(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                      const int64_t* group_start /* G+1 */, int32_t n_groups, const int64_t* lags /* n_vh */, int64_t n_vh,
+                      int64_t origin_step, int32_t unwrap, double dr, int32_t n_r, uint64_t* out_host /* (n_vh, G, n_r + 1) */,
+                      size_t out_bytes);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is
@@ -853,6 +913,13 @@ int psa_sed_fs_finish(psa_ctx* ctx, int32_t first_group);
  * n_lags outside [1, min(L, P)], a non-finite value, more than 2^28 elements. */
 int psa_debug_correlation_transform(psa_ctx* ctx, const double* X_host, int64_t fields, int64_t P, int64_t cols, int64_t L,
                                     int64_t n_seg, int64_t n_lags, int32_t as_float32, float* out_host);
+
+/* the unwrap pass of psa_displacement_moments and psa_van_hove_self alone, block by block under the same budget rule:
+ * out_u (T, n_g, 3) float64 the unwrapped displacements of the atoms idx (NULL: all N), out_images (T, n_g, 3) int32 the
+ * image counts n (may be NULL).  PSA_EINVAL: what those entries refuse about the context, the box, the indices, unwrap
+ * and the budget. */
+int psa_debug_unwrap(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx, int64_t n_g,
+                     int32_t unwrap, double* out_u /* (T, n_g, 3) */, int32_t* out_images /* (T, n_g, 3) or NULL */);
 
 #ifdef __cplusplus
 }

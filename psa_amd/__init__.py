@@ -24,9 +24,10 @@ from .lattice import PowderSpectra, commensurate_vectors, shell_bins
 from .partial import PartialSpectra, PowderPartialSpectra
 from .self_spectra import draw_atoms
 from .correlations import PowderTimeCorrelations, TimeCorrelations, relaxation_time
+from .displacements import MeanSquareDisplacement, VanHoveSelf
 from .weights import mass_weights
 
 __version__ = "0.2.0"
 __all__ = ["Trajectory", "SED", "SEDCalculator", "parse_direction", "fast_intensity", "mass_weights", "Segments",
-           "VDOS", "DynamicSpectra", "PowderSpectra", "PartialSpectra", "PowderPartialSpectra", "commensurate_vectors", "shell_bins", "draw_atoms", "TimeCorrelations", "PowderTimeCorrelations", "relaxation_time", "ModeSED", "site_groups", "PeakFit", "fit_peaks", "ModeVectors",
+           "VDOS", "DynamicSpectra", "PowderSpectra", "PartialSpectra", "PowderPartialSpectra", "commensurate_vectors", "shell_bins", "draw_atoms", "TimeCorrelations", "PowderTimeCorrelations", "relaxation_time", "MeanSquareDisplacement", "VanHoveSelf", "ModeSED", "site_groups", "PeakFit", "fit_peaks", "ModeVectors",
            "mode_vectors", "spectral_weights", "__version__"]

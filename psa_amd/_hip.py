@@ -62,6 +62,15 @@ SELF_ATOMS = 4      # atoms of an atom tile
 SELF_FRAMES = 64    # frames of a frame tile
 SELF_ENTRIES = 24   # most distinct (axis, m) pairs of a vector tile
 SELF_KS = 64        # most vectors of a vector tile
+# the tiles and caps of the displacement kernels (psa_amd/csrc/msd.hip), mirrored for the bounds of tests/msd_cases.py
+MSD_LAGS = 256         # lags of a lag tile, one per lane
+MSD_ORIGINS = 1024     # most origins of an origin tile
+MSD_WINDOW = 1280      # most frames of u64 staged per atom, origin tile and lag tile
+MSD_MAX_GROUPS = 8     # most atom groups of a call
+MSD_MAX_BINS = 1024    # most bins of a van Hove histogram
+MSD_MAX_VH_LAGS = 64   # most lags of a van Hove call
+MSD_UNWRAP_FRAMES = 64  # frames of an unwrap tile
+MSD_UNWRAP_ATOMS = 16   # atoms of an unwrap tile
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -141,6 +150,12 @@ SIGNATURES = {
                                         C.c_int64, _f32p, C.c_size_t]),
     "psa_debug_correlation_transform": (C.c_int, [_ctx, C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                                   C.c_int64, C.c_int64, C.c_int32, _f32p]),
+    "psa_displacement_moments": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i64p, C.c_int32, C.c_int64,
+                                           C.c_int64, C.c_int32, C.POINTER(C.c_double), C.c_size_t]),
+    "psa_van_hove_self": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i64p, C.c_int32, _i64p, C.c_int64,
+                                    C.c_int64, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_uint64), C.c_size_t]),
+    "psa_debug_unwrap": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, C.c_int64, C.c_int32,
+                                   C.POINTER(C.c_double), _i32p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
@@ -945,6 +960,72 @@ class Engine:
                                                None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g,
                                                int(n_lags), _f32(out), out.nbytes), "psa_self_correlations")
         return out
+
+    @staticmethod
+    def _displacement_args(box, box_inverse, groups):
+        """(H, Hinv (3, 3) float64, the groups' atoms concatenated or None, its pointer, the offsets or None, its pointer, G)"""
+        H = np.ascontiguousarray(box, np.float64)
+        if H.shape != (3, 3):
+            raise ValueError(f"box must be (3, 3), got {H.shape}")
+        if box_inverse is None:
+            try:
+                box_inverse = np.linalg.inv(H)
+            except np.linalg.LinAlgError as e:
+                raise ValueError(f"the box is singular: {e}") from None
+        inv = np.ascontiguousarray(box_inverse, np.float64)
+        if inv.shape != (3, 3):
+            raise ValueError(f"box_inverse must be (3, 3), got {inv.shape}")
+        if groups is None:
+            return H, inv, None, None, None, None, 1
+        lists = [np.asarray(g, np.int32).ravel() for g in groups]
+        start = np.zeros(len(lists) + 1, np.int64)
+        start[1:] = np.cumsum([g.size for g in lists])
+        flat = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.int32), np.int32)
+        keep = flat if flat.size else np.zeros(1, np.int32)
+        return H, inv, keep, keep.ctypes.data_as(_i32p), start, start.ctypes.data_as(_i64p), len(lists)
+
+    def displacement_moments(self, box, n_lags: int, groups=None, origin_step: int = 1, unwrap: bool = True,
+                             box_inverse=None) -> np.ndarray:
+        """The moments of the displacement D = u[o + t] - u[o] over time origins and the atoms of each group
+        (psa_displacement_moments): (n_lags, G, 4) float64 -- the means of D_x^2, D_y^2, D_z^2 and |D|^4.  `box` the
+        (3, 3) box matrix, rows = box vectors (`box_inverse`: its inverse where the caller has one); `groups` None: all
+        atoms as one group, else index arrays, disjoint, an empty one gives zeros; origins 0, origin_step, ...;
+        `unwrap=False` takes the positions as unwrapped.  Only positions are read."""
+        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
+        out = np.empty((max(int(n_lags), 0), G, 4), np.float64)
+        dp = C.POINTER(C.c_double)
+        _check(self._lib.psa_displacement_moments(self._h, H.ctypes.data_as(dp), inv.ctypes.data_as(dp), ip, sp, G, int(n_lags),
+                                                  int(origin_step), 1 if unwrap else 0, out.ctypes.data_as(dp), out.nbytes),
+               "psa_displacement_moments")
+        return out
+
+    def van_hove_self(self, box, lags, dr: float, n_r: int, groups=None, origin_step: int = 1, unwrap: bool = True,
+                      box_inverse=None) -> np.ndarray:
+        """The self van Hove function as counts (psa_van_hove_self): (n_vh, G, n_r + 1) uint64, bin i = floor(|D| / dr) of
+        the displacements over the lag `lags[j]`, the last entry the overflow count.  Everything else as for
+        `displacement_moments`."""
+        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
+        tau = np.ascontiguousarray(lags, np.int64).ravel()
+        held = tau if tau.size else np.zeros(1, np.int64)
+        out = np.empty((tau.size, G, max(int(n_r), 0) + 1), np.uint64)
+        dp = C.POINTER(C.c_double)
+        _check(self._lib.psa_van_hove_self(self._h, H.ctypes.data_as(dp), inv.ctypes.data_as(dp), ip, sp, G,
+                                           held.ctypes.data_as(_i64p), tau.size, int(origin_step), 1 if unwrap else 0, float(dr),
+                                           int(n_r), out.ctypes.data_as(C.POINTER(C.c_uint64)), out.nbytes), "psa_van_hove_self")
+        return out
+
+    def debug_unwrap(self, box, idx=None, unwrap: bool = True, images: bool = True, box_inverse=None):
+        """The unwrap pass alone (psa_debug_unwrap): (u (T, n_g, 3) float64, image counts (T, n_g, 3) int32 or None)."""
+        T, N = self.shape(SLOT_POSITIONS)
+        H, inv, keep, ip, _, _, _ = self._displacement_args(box, box_inverse, None if idx is None else [idx])
+        n_g = N if idx is None else int(np.asarray(idx).size)
+        u = np.empty((T, n_g, 3), np.float64)
+        img = np.empty((T, n_g, 3), np.int32) if images else None
+        dp = C.POINTER(C.c_double)
+        _check(self._lib.psa_debug_unwrap(self._h, H.ctypes.data_as(dp), inv.ctypes.data_as(dp), ip, n_g, 1 if unwrap else 0,
+                                          u.ctypes.data_as(dp), None if img is None else img.ctypes.data_as(_i32p)),
+               "psa_debug_unwrap")
+        return u, img
 
     def debug_correlation_transform(self, power, L: int, n_seg: int, n_lags: int, as_float32: bool = False) -> np.ndarray:
         """The back-transform of the time correlations alone (psa_debug_correlation_transform): `power` (fields, P, cols)

@@ -34,6 +34,7 @@ from .. import _hip
 from ..io.writer import out_to_qdump
 from ..correlations import PowderTimeCorrelations, TimeCorrelations, check_boxcar, check_lags
 from ..covariance import ModeVectors, mode_vectors, spectral_weights
+from ..displacements import MeanSquareDisplacement, VanHoveSelf, alpha2, check_origin_step, origin_counts
 from ..dynamic import DynamicSpectra
 from .. import lattice
 from ..lattice import PowderSpectra
@@ -785,6 +786,103 @@ class SEDCalculator:
                                              lambda eng, listed: eng.self_correlations(inv, n, n_lags, b, n_bins, listed),
                                              max_atoms, seed)
         return self._powder_correlations(shells, out, None, None, times, origins, atoms, norm)
+
+    # ------------------------------------------------------------------ displacements in real space
+    def _displacement_groups(self, basis_atom_indices, basis_atom_types, origin_step, unwrap, max_atoms, seed, what):
+        """(origin_step, the groups' atom-index arrays after the draw) of a displacement call, after its refusals"""
+        step = check_origin_step(origin_step)
+        if not isinstance(unwrap, (bool, np.bool_)):
+            raise TypeError(f"unwrap must be a bool, got {type(unwrap).__name__}")
+        check_max_atoms(max_atoms)
+        if self._shard is not None and self._shard.nranks > 1:
+            raise NotImplementedError(f"{what} is not available on a sharded calculator")
+        if self.traj.n_frames == 0 or self.traj.n_atoms == 0:
+            return step, None
+        groups = self._resolve_groups(basis_atom_indices, basis_atom_types, "incoherent")
+        if len(groups) > _hip.MSD_MAX_GROUPS:
+            raise ValueError(f"at most {_hip.MSD_MAX_GROUPS} atom groups are served, got {len(groups)}")
+        members = np.concatenate(groups)
+        if np.unique(members).size != members.size:
+            raise ValueError(f"atom groups of {what} must be disjoint (an atom is listed twice)")
+        return step, [np.asarray(draw_atoms(g, max_atoms, seed)) for g in groups]
+
+    def _displacement_run(self, call):
+        lattice.box_inverse(self.traj.box_matrix)                # ValueError for a box that is not finite or singular
+        eng = self.engine
+        eng.ensure_resident(_hip.SLOT_POSITIONS, self.traj.positions)
+        return call(eng, np.asarray(self.traj.box_matrix, np.float32).astype(np.float64))
+
+    def calculate_msd(self, basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                      basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *, lags: Optional[int] = None,
+                      origin_step: int = 1, unwrap: bool = True, max_atoms: Optional[int] = None,
+                      seed: int = 0) -> MeanSquareDisplacement:
+        """Mean-square displacement and non-Gaussian parameter of atom groups (not in the reference; definition in
+        psa_amd/displacements.py): msd[t,g] = <|u[o+t,a] - u[o,a]|^2> over the time origins o = 0, origin_step, ... and
+        the atoms of group g, its three components, the fourth moment and alpha2 = 3 <D^4> / (5 <D^2>^2) - 1, computed on
+        the GPU from the positions resident in HBM by a direct sum over origins.
+
+        The positions are used as stored: `unwrap=True` (default) recovers the displacements of a wrapped trajectory
+        from the box (no atom may move half a box length or more between two stored frames; an unwrapped trajectory
+        passes through unchanged), `unwrap=False` skips that search.  Groups are resolved like those of
+        `calculate_vdos`: `basis_atom_types=[1, 2]` gives one curve per species, nothing gives all atoms; they must be
+        disjoint, at most 8.  `lags`: number of lags t = 0 .. lags - 1 (None: T // 2); `max_atoms` draws that many atoms
+        of every group by `seed`, as the self spectra do.  A sharded calculator refuses (NotImplementedError).
+        Returns a `psa_amd.MeanSquareDisplacement`; `.diffusion(fit=(t0_ps, t1_ps))` fits D."""
+        n_t = self.traj.n_frames
+        n_lags = check_lags(lags, n_t) if n_t else 0
+        step, groups = self._displacement_groups(basis_atom_indices, basis_atom_types, origin_step, unwrap, max_atoms, seed,
+                                                 "the mean-square displacement")
+        times = np.arange(n_lags, dtype=np.float64) * (self.dt_ps if self.dt_ps is not None else 1.0)
+        if groups is None:
+            logger.warning("Cannot calculate the mean-square displacement: 0 frames or 0 atoms.")
+            zero = np.zeros((n_lags, 1), np.float64)
+            return MeanSquareDisplacement(zero, np.zeros((n_lags, 1, 3)), zero.copy(), np.full((n_lags, 1), np.nan), times,
+                                          np.zeros(n_lags, np.int64), [np.zeros(0, int)], np.zeros(1, np.int64), self.dt_ps)
+        out = self._displacement_run(lambda eng, box: eng.displacement_moments(box, n_lags, groups, step, bool(unwrap)))
+        msd = out[:, :, :3].sum(axis=2)
+        return MeanSquareDisplacement(msd, out[:, :, :3].copy(), out[:, :, 3].copy(), alpha2(msd, out[:, :, 3]), times,
+                                      origin_counts(n_t, n_lags, step), groups, np.array([g.size for g in groups], np.int64),
+                                      self.dt_ps)
+
+    def calculate_van_hove(self, lag_frames, r_max: float, n_r: int = 200,
+                           basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                           basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *, origin_step: int = 1,
+                           unwrap: bool = True, max_atoms: Optional[int] = None, seed: int = 0) -> VanHoveSelf:
+        """The self van Hove function G_s(r,t) of atom groups at the lags `lag_frames` (frames, at most 64, each in
+        [0, T - 1]) (not in the reference; definition in psa_amd/displacements.py): the histogram of |u[o+t,a] - u[o,a]|
+        over origins and atoms in `n_r` <= 1024 bins of width r_max / n_r, longer displacements counted in `overflow`.
+        Integer counts: sum_i counts + overflow = samples exactly.  Unwrapping, groups, `origin_step`, `max_atoms` and
+        the sharded refusal are those of `calculate_msd`.  Returns a `psa_amd.VanHoveSelf` with `radial_density`
+        (4 pi r^2 G_s) and `g_s`."""
+        tau = np.asarray(lag_frames)
+        if tau.ndim == 0:
+            tau = tau.reshape(1)
+        if tau.ndim != 1 or (tau.size and not (np.issubdtype(tau.dtype, np.integer) or np.all(tau == np.rint(tau)))):
+            raise ValueError("lag_frames must be a list of integers")
+        tau = tau.astype(np.int64)
+        if not 1 <= tau.size <= _hip.MSD_MAX_VH_LAGS:
+            raise ValueError(f"between 1 and {_hip.MSD_MAX_VH_LAGS} lags are served, got {tau.size}")
+        if isinstance(n_r, bool) or not isinstance(n_r, (int, np.integer)) or not 1 <= int(n_r) <= _hip.MSD_MAX_BINS:
+            raise ValueError(f"n_r must be an integer in [1, {_hip.MSD_MAX_BINS}], got {n_r!r}")
+        if not (np.isfinite(r_max) and float(r_max) > 0.0):
+            raise ValueError(f"r_max must be positive and finite, got {r_max!r}")
+        n_r, dr = int(n_r), float(r_max) / int(n_r)
+        n_t = self.traj.n_frames
+        if n_t and (np.any(tau < 0) or np.any(tau > n_t - 1)):
+            raise ValueError(f"lag_frames must lie in [0, T - 1 = {n_t - 1}]")
+        step, groups = self._displacement_groups(basis_atom_indices, basis_atom_types, origin_step, unwrap, max_atoms, seed,
+                                                 "the van Hove function")
+        edges = dr * np.arange(n_r + 1, dtype=np.float64)
+        centres = 0.5 * (edges[1:] + edges[:-1])
+        times = tau.astype(np.float64) * (self.dt_ps if self.dt_ps is not None else 1.0)
+        if groups is None:
+            logger.warning("Cannot calculate the van Hove function: 0 frames or 0 atoms.")
+            return VanHoveSelf(np.zeros((tau.size, 1, n_r), np.uint64), np.zeros((tau.size, 1), np.uint64), edges, centres,
+                               np.zeros((tau.size, 1), np.int64), tau, times, [np.zeros(0, int)], self.dt_ps)
+        out = self._displacement_run(lambda eng, box: eng.van_hove_self(box, tau, dr, n_r, groups, step, bool(unwrap)))
+        n_o = (n_t - 1 - tau) // step + 1
+        samples = n_o[:, None] * np.array([g.size for g in groups], np.int64)[None, :]
+        return VanHoveSelf(out[:, :, :n_r].copy(), out[:, :, n_r].copy(), edges, centres, samples, tau, times, groups, self.dt_ps)
 
     # ------------------------------------------------------------------ partial (species-resolved) spectra on that lattice
     def _partial_species(self, basis_atom_indices, basis_atom_types, weights):

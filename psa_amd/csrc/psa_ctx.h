@@ -325,6 +325,13 @@ struct psa_ctx {
     // and the float32 result (1 or 3, n_lags, K or n_bins).  All kept between calls.
     psa::DevBuf  d_corr_tab, d_corr_factor, d_corr_scale, d_corr_in, d_corr_out;
 
+    // real-space self dynamics (psa_displacement_moments, psa_van_hove_self, psa_debug_unwrap; api_msd.hip): the unwrapped
+    // displacements u64 (atoms of a block, 3, T) float64, held to opt_dynamic_work_bytes; outside it the debug entry's
+    // image counts, the unwrap pass's tile sums and offsets, the atom list, the chunk table, the groups' sizes, the van
+    // Hove lags, the chunk partials, the accumulator that lives across blocks and the scaled moments.  All kept between calls.
+    psa::DevBuf  d_msd_u, d_msd_img, d_msd_sums, d_msd_offs, d_msd_idx, d_msd_chunks, d_msd_sizes, d_msd_lags, d_msd_part,
+                 d_msd_acc, d_msd_out;
+
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
                                           // plane builds, trajectory uploads (psa_oneoff_stats)
@@ -552,6 +559,39 @@ int launch_correlation_transform(psa_ctx* c, const double* d_X, const double* d_
                                  float* d_out, int64_t fields, int64_t P, int64_t cols, int64_t n_lags);
 int launch_correlation_transform(psa_ctx* c, const float* d_X, const double* d_tab, const double* d_factor, const double* d_scale,
                                  float* d_out, int64_t fields, int64_t P, int64_t cols, int64_t n_lags);
+// --- msd.hip (psa_displacement_moments, psa_van_hove_self, psa_debug_unwrap: unwrapped displacements, their moments summed
+// directly over time origins, the histogram of their length; the arithmetic and the layouts are in its header)
+constexpr int MSD_LAGS = 256;          // lags of a lag tile, one per lane of the moments kernel's workgroup
+constexpr int MSD_ORIGINS = 1024;      // most origins of an origin tile
+constexpr int MSD_WINDOW = 1280;       // most frames of u64 the moments kernel stages per atom, origin tile and lag tile
+constexpr int MSD_MAX_GROUPS = 8;      // most atom groups of a call
+constexpr int MSD_MAX_BINS = 1024;     // most bins of a van Hove histogram (an overflow counter follows them)
+constexpr int MSD_MAX_VH_LAGS = 64;    // most lags of a van Hove call
+constexpr int MSD_UNWRAP_FRAMES = 64;  // frames of an unwrap tile: a lane per frame
+constexpr int MSD_UNWRAP_ATOMS = 16;   // atoms of an unwrap tile, four per wavefront
+int msd_origins(int64_t step);         // origins of an origin tile at this origin step: the window stays within MSD_WINDOW
+// atoms [a0, a0 + na) of the list d_idx (null: atoms a0 + i) over all T frames -> d_u (na, 3, T) float64 and, unless null,
+// d_img (na, 3, T) int32 image counts.  unwrap false: u = r(t) - r(0), counts 0, d_sums and d_offs unused; else both
+// (ceil(T / MSD_UNWRAP_FRAMES), na, 3) int32.  box, box_inverse: H and Hinv on the host
+int launch_msd_unwrap(psa_ctx* c, const float* d_pos, const int* d_idx, int64_t a0, int64_t na, const double* box,
+                      const double* box_inverse, bool unwrap, int* d_sums, int* d_offs, double* d_u, int* d_img, int64_t T, int64_t N);
+// d_chunks: n_chunks entries {first atom of the block, one past the last, group, 0} (int32 x 4), each of one group; n_os:
+// origin slabs per chunk, the chunks listed group by group.  The moments kernel writes d_part (n_chunks, n_os, n_lags, 4)
+// float64; the reduce adds a group's chunks and slabs in order to acc (n_lags, G, 4) -- group_first (G + 1, host): group
+// g's chunks are group_first[g] .. group_first[g + 1] - 1
+int launch_msd_moments(psa_ctx* c, const double* d_u, const void* d_chunks, int64_t n_chunks, double* d_part, int64_t T, int64_t n_lags,
+                       int64_t step, int64_t n_os);
+int launch_msd_moments_reduce(psa_ctx* c, const double* d_part, const int32_t* group_first, double* d_acc, int64_t n_lags, int64_t n_os,
+                              int32_t G);
+// out (n_lags, G, 4) = acc / (group_size[g] n_o(t)), an empty group: 0
+int launch_msd_moments_finish(psa_ctx* c, const double* d_acc, const int64_t* d_group_size, double* d_out, int64_t T, int64_t n_lags,
+                              int32_t G, int64_t step);
+// the histogram kernel writes d_part (n_chunks, n_os, n_vh, n_r + 1) uint32 -- a chunk's atoms x the origins of a lag stay
+// below 2^32 (the caller's chunk rule) --, the reduce adds them to acc (n_vh, G, n_r + 1) uint64
+int launch_msd_hist(psa_ctx* c, const double* d_u, const void* d_chunks, int64_t n_chunks, const int64_t* d_lags, int64_t n_vh,
+                    unsigned* d_part, int64_t T, int64_t step, int64_t n_os, float inv_dr, int32_t n_r);
+int launch_msd_hist_reduce(psa_ctx* c, const unsigned* d_part, const int32_t* group_first, unsigned long long* d_acc, int64_t n_vh,
+                           int64_t n_os, int32_t n_r, int32_t G);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 
