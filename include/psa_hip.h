@@ -711,6 +711,48 @@ int psa_van_hove_self(psa_ctx* ctx, const double* box /* 9 */, const double* box
                       int64_t origin_step, int32_t unwrap, double dr, int32_t n_r, uint64_t* out_host /* (n_vh, G, n_r + 1) */,
                       size_t out_bytes);
 
+/* Pair distributions: the radial distribution function g(r), its species-resolved partials and the distinct van Hove
+ * function G_d(r,t), as integer counts, from the positions resident in PSA_SLOT_POSITIONS as stored, wrapped or not.
+ * H = box (rows = box vectors, r = s H), Hinv = box_inverse.  Species alpha = 0 .. S-1, S <= 8, are listed like the
+ * groups of psa_displacement_moments (idx, group_start; disjoint; idx NULL: one species of all N atoms).  Lags tau_j in
+ * frames (n_lags <= 64 of them, each in [0, T-1]), origins O_tau = {0, s, 2 s, ...: o + tau <= T-1}, s = origin_step:
+ *     counts[j,alpha,beta,i] = #{(a in alpha, b in beta, b != a, o in O_tau_j): floor(|mi(r_b(o+tau_j) - r_a(o))| / dr) = i},  i < n_r
+ * and counts[j,alpha,beta,n_r] everything at or beyond r_max = n_r dr (the overflow), mi the minimum image.  tau = 0 is
+ * g(r), tau > 0 is G_d(r,t).  out_host (n_lags, S, S, n_r + 1) uint64 holds every ordered species pair; the counts are
+ * exact integers, sum_i counts[j,alpha,beta,:] = n_o(tau_j) N_alpha (N_beta - delta_alphabeta), and at tau = 0
+ * counts[alpha,beta] = counts[beta,alpha] bit for bit.  An empty species, and a species of one atom against itself, give
+ * zeros.
+ * Nothing is unwrapped: within r_max at most one periodic image of b lies around a, so the minimum image of the stored
+ * positions is the distance at any lag.  Served radius: with w_j = 1 / |column j of Hinv| the box's perpendicular widths,
+ * rounding the fractional difference to the nearest integer gives the true minimum image of every pair closer than
+ * min_j w_j / 2, whatever the tilt; r_max <= (1/2 - 2^-12) min_j w_j is served (compared with a relative slack of 2^-40),
+ * anything larger refused before anything is uploaded.  A pair whose fractional difference lies within rounding (2^-24)
+ * of 1/2 may take either image; both are then longer than r_max and are counted in the overflow.
+ * As evaluated (pair.hip).  Per (frame, atom), float64 from the float32 position:
+ *     sigma_j = fma(r_z, Hinv[2][j], fma(r_y, Hinv[1][j], r_x Hinv[0][j]));   c_j = float32(sigma_j - floor(sigma_j) - 0.5)
+ * per pair, float32, every operation rounded once, h = H rounded to float32, inv_dr = float32(1 / dr):
+ *     e_j = c_j(b) - c_j(a);  e_j = e_j - rintf(e_j) (exact);  d_c = fma(e_2, h[2][c], fma(e_1, h[1][c], e_0 h[0][c]))
+ *     r2 = fma(d_z, d_z, fma(d_y, d_y, d_x d_x));   x = sqrt(r2) inv_dr;   bin = x < n_r ? (int) floorf(x) : n_r
+ * so x carries at most (|delta d|_2 + 4.5 2^-24 |d|) / dr with |delta d_c| <= sum_j (2^-24 + 3 2^-24 |e_j|) |H_jc|.
+ * A workgroup takes 256 alpha-atoms (one per lane), beta-atoms staged in LDS 256 at a time and a slab of origins, and adds
+ * into a 32-bit integer histogram in LDS -- the host keeps a workgroup's samples below 2^32 --, written to partials with
+ * plain stores and summed in 64-bit integers: no global atomics, no float atomics; two identical calls, any blocking and
+ * any order of the atoms inside a species give the same bits.  At tau = 0 every unordered pair is evaluated once.
+ * Budget (PSA_OPT_DYNAMIC_WORK_BYTES): c of the listed atoms at a block of origins and at their partner frames, 24 n_a
+ * bytes per origin; a budget below one origin is refused and the refusal names the bytes needed.
+ * PSA_EINVAL: a null pointer, no positions resident, a box or inverse that is not finite, a singular box, an inverse that
+ * is not the box's, r_max beyond the served radius, n_groups outside [1, 8], offsets that do not begin at 0 or are not
+ * ascending, an atom in two species, an index outside [0, N), n_lags outside [1, 64], a lag outside [0, T-1],
+ * origin_step < 1, dr <= 0 or not finite, n_r outside [1, 1024], out_bytes not exact, a budget below one origin, a sharded
+ * context (psa_comm_init).
+ * Only the positions slot is read.  Atom weights and segments set on the context are ignored, not refused; every result
+ * and plan of the other entry points is left as it is.  Stage times: [5] the fraction pass, [6] the pair kernel,
+ * [4] reduce, [7] device->host. */
+int psa_pair_histogram(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                       const int64_t* group_start /* S+1 */, int32_t n_groups, const int64_t* lags /* n_lags */, int64_t n_lags,
+                       int64_t origin_step, double dr, int32_t n_r, uint64_t* out_host /* (n_lags, S, S, n_r + 1) */,
+                       size_t out_bytes);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is
@@ -920,6 +962,18 @@ int psa_debug_correlation_transform(psa_ctx* ctx, const double* X_host, int64_t 
  * and the budget. */
 int psa_debug_unwrap(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx, int64_t n_g,
                      int32_t unwrap, double* out_u /* (T, n_g, 3) */, int32_t* out_images /* (T, n_g, 3) or NULL */);
+
+/* the fraction pass of psa_pair_histogram alone, frame block by frame block under the same budget rule: out (T, n_g, 3)
+ * float32 the centred fractional coordinates c of the atoms idx (NULL: all N).  PSA_EINVAL: what that entry refuses about
+ * the context, the inverse, the indices and the budget. */
+int psa_debug_pair_fractions(psa_ctx* ctx, const double* box_inverse /* 9 */, const int32_t* idx, int64_t n_g,
+                             float* out /* (T, n_g, 3) */);
+
+/* the workgroup table psa_pair_histogram builds for species of these sizes over a block of n_origins <= 65535 origins
+ * (sym = 1: lag 0), on the host alone, no context: out[0] the most beta-tiles an item walks, out[1] the origin slabs,
+ * out[2] the items, out[3] the most samples one item can count (256 x its beta-atoms x its origins), which stays below
+ * 2^32.  PSA_EINVAL: a null pointer, n_groups outside [1, 8], a negative size, n_origins outside [1, 65535]. */
+int psa_debug_pair_plan(const int64_t* sizes /* n_groups */, int32_t n_groups, int32_t sym, int64_t n_origins, int64_t* out /* 4 */);
 
 #ifdef __cplusplus
 }

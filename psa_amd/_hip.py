@@ -71,6 +71,11 @@ MSD_MAX_BINS = 1024    # most bins of a van Hove histogram
 MSD_MAX_VH_LAGS = 64   # most lags of a van Hove call
 MSD_UNWRAP_FRAMES = 64  # frames of an unwrap tile
 MSD_UNWRAP_ATOMS = 16   # atoms of an unwrap tile
+# the tile and caps of the pair kernels (psa_amd/csrc/pair.hip)
+PAIR_TILE = 256        # alpha-atoms of a workgroup and beta-atoms of a staged tile
+PAIR_MAX_BINS = 1024   # most bins of a pair histogram
+PAIR_MAX_LAGS = 64     # most lags of a pair call
+PAIR_MAX_SPECIES = 8   # most species of a pair call
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -156,6 +161,10 @@ SIGNATURES = {
                                     C.c_int64, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_uint64), C.c_size_t]),
     "psa_debug_unwrap": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, C.c_int64, C.c_int32,
                                    C.POINTER(C.c_double), _i32p]),
+    "psa_pair_histogram": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i64p, C.c_int32, _i64p, C.c_int64,
+                                     C.c_int64, C.c_double, C.c_int32, C.POINTER(C.c_uint64), C.c_size_t]),
+    "psa_debug_pair_fractions": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _f32p]),
+    "psa_debug_pair_plan": (C.c_int, [_i64p, C.c_int32, C.c_int32, C.c_int64, _i64p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
@@ -1026,6 +1035,45 @@ class Engine:
                                           u.ctypes.data_as(dp), None if img is None else img.ctypes.data_as(_i32p)),
                "psa_debug_unwrap")
         return u, img
+
+    def pair_histogram(self, box, lags, dr: float, n_r: int, groups=None, origin_step: int = 1, box_inverse=None) -> np.ndarray:
+        """The histogram of minimum-image pair distances (psa_pair_histogram): (n_lags, S, S, n_r + 1) uint64, entry
+        [j, alpha, beta, i] the number of (a in alpha, b in beta, b != a, origin o) with floor(|mi(r_b(o + lags[j]) -
+        r_a(o))| / dr) = i, the last entry the overflow (r_max = n_r dr and beyond).  Lag 0 is g(r), later lags the
+        distinct van Hove function.  `box` the (3, 3) box matrix, rows = box vectors; `groups` None: all atoms as one
+        species, else index arrays, disjoint; origins 0, origin_step, ...  r_max beyond `psa_amd.max_pair_radius(box)`
+        is refused.  Only positions are read, as stored: nothing is unwrapped."""
+        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
+        tau = np.ascontiguousarray(lags, np.int64).ravel()
+        held = tau if tau.size else np.zeros(1, np.int64)
+        out = np.empty((tau.size, G, G, max(int(n_r), 0) + 1), np.uint64)
+        dp = C.POINTER(C.c_double)
+        _check(self._lib.psa_pair_histogram(self._h, H.ctypes.data_as(dp), inv.ctypes.data_as(dp), ip, sp, G,
+                                            held.ctypes.data_as(_i64p), tau.size, int(origin_step), float(dr), int(n_r),
+                                            out.ctypes.data_as(C.POINTER(C.c_uint64)), out.nbytes), "psa_pair_histogram")
+        return out
+
+    def debug_pair_fractions(self, box, idx=None, box_inverse=None) -> np.ndarray:
+        """The fraction pass of `pair_histogram` alone (psa_debug_pair_fractions): (T, n_g, 3) float32, the fractional
+        coordinates of the atoms `idx` (None: all) folded into [-0.5, 0.5]."""
+        T, N = self.shape(SLOT_POSITIONS)
+        H, inv, keep, ip, _, _, _ = self._displacement_args(box, box_inverse, None if idx is None else [idx])
+        n_g = N if idx is None else int(np.asarray(idx).size)
+        out = np.empty((T, n_g, 3), np.float32)
+        _check(self._lib.psa_debug_pair_fractions(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), ip, n_g, _f32(out)),
+               "psa_debug_pair_fractions")
+        return out
+
+    @staticmethod
+    def debug_pair_plan(sizes, sym: bool, n_origins: int) -> dict:
+        """The workgroup table `pair_histogram` builds for species of these sizes over a block of `n_origins` origins
+        (psa_debug_pair_plan; host only): the most beta-tiles of an item, the origin slabs, the items, the most samples
+        one item can count."""
+        n = np.ascontiguousarray(sizes, np.int64).ravel()
+        out = np.zeros(4, np.int64)
+        _check(load_library().psa_debug_pair_plan(n.ctypes.data_as(_i64p), n.size, 1 if sym else 0, int(n_origins),
+                                                  out.ctypes.data_as(_i64p)), "psa_debug_pair_plan")
+        return dict(run=int(out[0]), slabs=int(out[1]), items=int(out[2]), most_samples=int(out[3]))
 
     def debug_correlation_transform(self, power, L: int, n_seg: int, n_lags: int, as_float32: bool = False) -> np.ndarray:
         """The back-transform of the time correlations alone (psa_debug_correlation_transform): `power` (fields, P, cols)

@@ -36,6 +36,7 @@ from ..correlations import PowderTimeCorrelations, TimeCorrelations, check_boxca
 from ..covariance import ModeVectors, mode_vectors, spectral_weights
 from ..displacements import MeanSquareDisplacement, VanHoveSelf, alpha2, check_origin_step, origin_counts
 from ..dynamic import DynamicSpectra
+from ..pairs import RadialDistribution, VanHoveDistinct, max_pair_radius
 from .. import lattice
 from ..lattice import PowderSpectra
 from ..modes import ModeSED
@@ -883,6 +884,97 @@ class SEDCalculator:
         n_o = (n_t - 1 - tau) // step + 1
         samples = n_o[:, None] * np.array([g.size for g in groups], np.int64)[None, :]
         return VanHoveSelf(out[:, :, :n_r].copy(), out[:, :, n_r].copy(), edges, centres, samples, tau, times, groups, self.dt_ps)
+
+    # ------------------------------------------------------------------ pair distributions in real space
+    def _pair_call(self, tau, r_max, n_r, basis_atom_indices, basis_atom_types, origin_step, max_atoms, seed, what):
+        """(tau int64, n_r, dr, edges, centres, origin_step, the species' atom-index arrays or None, the (n_vh, S, S,
+        n_r + 1) counts or None) of a pair call after its refusals -- those of `calculate_van_hove` and the served radius"""
+        tau = np.asarray(tau)
+        if tau.ndim == 0:
+            tau = tau.reshape(1)
+        if tau.ndim != 1 or (tau.size and not (np.issubdtype(tau.dtype, np.integer) or np.all(tau == np.rint(tau)))):
+            raise ValueError("lag_frames must be a list of integers")
+        tau = tau.astype(np.int64)
+        if not 1 <= tau.size <= _hip.PAIR_MAX_LAGS:
+            raise ValueError(f"between 1 and {_hip.PAIR_MAX_LAGS} lags are served, got {tau.size}")
+        if isinstance(n_r, bool) or not isinstance(n_r, (int, np.integer)) or not 1 <= int(n_r) <= _hip.PAIR_MAX_BINS:
+            raise ValueError(f"n_r must be an integer in [1, {_hip.PAIR_MAX_BINS}], got {n_r!r}")
+        served = max_pair_radius(self.traj.box_matrix)           # ValueError for a box that is not finite or singular
+        if r_max is None:
+            r_max = served
+        if not (np.isfinite(r_max) and float(r_max) > 0.0):
+            raise ValueError(f"r_max must be positive and finite, got {r_max!r}")
+        if float(r_max) > served:
+            raise ValueError(f"r_max = {float(r_max)!r} is beyond the served radius {served!r} (psa_amd.max_pair_radius): "
+                             "(1/2 - 2^-12) of the box's least perpendicular width")
+        n_r, dr = int(n_r), float(r_max) / int(n_r)
+        n_t = self.traj.n_frames
+        if n_t and (np.any(tau < 0) or np.any(tau > n_t - 1)):
+            raise ValueError(f"lag_frames must lie in [0, T - 1 = {n_t - 1}]")
+        step, groups = self._displacement_groups(basis_atom_indices, basis_atom_types, origin_step, True, max_atoms, seed, what)
+        edges = dr * np.arange(n_r + 1, dtype=np.float64)
+        centres = 0.5 * (edges[1:] + edges[:-1])
+        if groups is None:
+            logger.warning(f"Cannot calculate {what}: 0 frames or 0 atoms.")
+            return tau, n_r, edges, centres, step, None, None
+        out = self._displacement_run(lambda eng, box: eng.pair_histogram(box, tau, dr, n_r, groups, step))
+        return tau, n_r, edges, centres, step, groups, out
+
+    def _pair_samples(self, tau, step, sizes):
+        """(n_o (n_vh,), samples (n_vh, S, S) = n_o N_a (N_b - delta_ab))"""
+        n_o = (self.traj.n_frames - 1 - tau) // step + 1
+        return n_o, n_o[:, None, None] * sizes[None, :, None] * (sizes[None, None, :] - np.eye(sizes.size, dtype=np.int64)[None])
+
+    def calculate_rdf(self, r_max: Optional[float] = None, n_r: int = 200,
+                      basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                      basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *, origin_step: int = 1,
+                      max_atoms: Optional[int] = None, seed: int = 0) -> RadialDistribution:
+        """The radial distribution function g(r) and its species-resolved partials g_ab(r) (not in the reference;
+        definition in psa_amd/pairs.py): the histogram of the minimum-image distance over all ordered pairs of atoms of
+        species a and b and the frames 0, origin_step, ..., in `n_r` <= 1024 bins of width r_max / n_r, computed on the
+        GPU from the positions resident in HBM.  Integer counts: sum_i counts + overflow = samples exactly, and
+        counts[a,b] = counts[b,a].
+
+        The positions are used as stored and nothing is unwrapped: within r_max at most one periodic image of an atom
+        lies around another, so the minimum image of a wrapped, an unwrapped or a partly wrapped trajectory is the
+        same distance.  `r_max=None` means `psa_amd.max_pair_radius(box)`, (1/2 - 2^-12) of the box's least
+        perpendicular width; a larger one is a ValueError.  Species are resolved like the groups of `calculate_vdos`
+        (disjoint, at most 8); `max_atoms` draws that many atoms of every species by `seed`.  A sharded calculator
+        refuses (NotImplementedError).  Returns a `psa_amd.RadialDistribution` with `g`, `coordination` and `pair(a, b)`."""
+        tau, n_r, edges, centres, step, groups, out = self._pair_call([0], r_max, n_r, basis_atom_indices, basis_atom_types,
+                                                                      origin_step, max_atoms, seed, "the radial distribution function")
+        volume = float(abs(np.linalg.det(np.asarray(self.traj.box_matrix, np.float32).astype(np.float64))))
+        if groups is None:
+            return RadialDistribution(np.zeros((1, 1, n_r), np.uint64), np.zeros((1, 1), np.uint64), np.zeros((1, 1), np.int64), edges,
+                                      centres, volume, [np.zeros(0, int)], np.zeros(1, np.int64), 0)
+        sizes = np.array([g.size for g in groups], np.int64)
+        n_o, samples = self._pair_samples(tau, step, sizes)
+        return RadialDistribution(out[0, :, :, :n_r].copy(), out[0, :, :, n_r].copy(), samples[0], edges, centres, volume, groups, sizes,
+                                  int(n_o[0]))
+
+    def calculate_distinct_van_hove(self, lag_frames, r_max: Optional[float] = None, n_r: int = 200,
+                                    basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                    basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *, origin_step: int = 1,
+                                    max_atoms: Optional[int] = None, seed: int = 0) -> VanHoveDistinct:
+        """The distinct van Hove function G_d(r,t) of species pairs at the lags `lag_frames` (frames, at most 64, each in
+        [0, T - 1]) (not in the reference; definition in psa_amd/pairs.py): the histogram of |mi(r_B(o + t) - r_A(o))|
+        over the ordered pairs B != A of species a and b and the origins o = 0, origin_step, ...; lag 0 is g(r).  The
+        (a, b) and (b, a) counts differ at t > 0.  Positions as stored, nothing unwrapped; `r_max`, `n_r`, species,
+        `max_atoms` and the refusals are those of `calculate_rdf`.  Returns a `psa_amd.VanHoveDistinct` with `g_d`
+        (tends to 1 at large r), `radial_density` (4 pi r^2 G_d) and `coordination`; with `VanHoveSelf` of
+        `calculate_van_hove` it completes G = G_s + G_d."""
+        tau, n_r, edges, centres, step, groups, out = self._pair_call(lag_frames, r_max, n_r, basis_atom_indices, basis_atom_types,
+                                                                      origin_step, max_atoms, seed, "the distinct van Hove function")
+        volume = float(abs(np.linalg.det(np.asarray(self.traj.box_matrix, np.float32).astype(np.float64))))
+        times = tau.astype(np.float64) * (self.dt_ps if self.dt_ps is not None else 1.0)
+        if groups is None:
+            z = np.zeros((tau.size, 1, 1), np.int64)
+            return VanHoveDistinct(np.zeros((tau.size, 1, 1, n_r), np.uint64), z.astype(np.uint64), z, edges, centres, volume,
+                                   [np.zeros(0, int)], np.zeros(1, np.int64), np.zeros(tau.size, np.int64), tau, times, self.dt_ps)
+        sizes = np.array([g.size for g in groups], np.int64)
+        n_o, samples = self._pair_samples(tau, step, sizes)
+        return VanHoveDistinct(out[:, :, :, :n_r].copy(), out[:, :, :, n_r].copy(), samples, edges, centres, volume, groups, sizes, n_o,
+                               tau, times, self.dt_ps)
 
     # ------------------------------------------------------------------ partial (species-resolved) spectra on that lattice
     def _partial_species(self, basis_atom_indices, basis_atom_types, weights):

@@ -331,6 +331,19 @@ struct SelfPower {
 };
 using SelfFill = std::function<int(int64_t a0, int64_t na, int64_t vb, int64_t s0, int64_t ns, const float2** d_work)>;
 int self_power_run(psa_ctx* c, const SelfPower& w, const SelfFill& fill);
+
+// ---- api_msd.hip / api_pair.hip: the atom groups of a real-space call
+struct MsdCall {
+    int64_t              T = 0, N = 0, n_a = 0, Ab = 0;
+    int32_t              G = 1;
+    bool                 listed = false;        // false: all N atoms in order, one group
+    std::vector<int64_t> start;                 // (G + 1) the groups' offsets into the atom list
+    std::vector<int64_t> size;                  // (G)
+};
+// what those entries refuse about the context (a communicator, no positions), the box and its inverse and the group
+// lists (at most MSD_MAX_GROUPS, disjoint, in bounds); fills everything of p but Ab
+int group_list_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
+                     const int64_t* group_start, int32_t n_groups, MsdCall* p);
 int    check_weights(psa_ctx* c, int64_t N);            // the context's atom weights fit a slot of N atoms
 void   set_geom_weights(const psa_ctx* c, ProjGeom* g);  // ... and go into a launch's geometry
 int    begin_result(psa_ctx* c, int64_t T, int64_t K_total, int64_t k_offset, bool intensity, char** rows);

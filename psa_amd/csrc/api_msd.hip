@@ -12,25 +12,13 @@
 
 namespace psa {
 
-namespace {
-
-constexpr int64_t MSD_TARGET_GROUPS = 4096;     // workgroups a launch aims at, where the work allows
-
-struct MsdCall {
-    int64_t              T = 0, N = 0, n_a = 0, Ab = 0;
-    int32_t              G = 1;
-    bool                 listed = false;        // false: all N atoms in order, one group
-    std::vector<int64_t> start;                 // (G + 1) the groups' offsets into the atom list
-    std::vector<int64_t> size;                  // (G)
-};
-
-int msd_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
-              const int64_t* group_start, int32_t n_groups, int32_t unwrap, MsdCall* p) {
+// the checks the real-space entries share (also api_pair.hip): the context, the box and its inverse, the group lists
+int group_list_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
+                     const int64_t* group_start, int32_t n_groups, MsdCall* p) {
     PSA_REQUIRE(c->comm == nullptr && c->nranks == 1, "%s is not available on a sharded context (%d ranks)", entry, c->nranks);
     const DataSlot& pos = c->slot[PSA_SLOT_POSITIONS];
     PSA_REQUIRE(pos.valid, "the positions slot holds no array: %s reads the positions", entry);
     PSA_REQUIRE(box != nullptr && box_inverse != nullptr, "null box or box_inverse");
-    PSA_REQUIRE(unwrap == 0 || unwrap == 1, "unwrap is 0 or 1, got %d", (int)unwrap);
     const double* H = box;
     const double  det = H[0] * (H[4] * H[8] - H[5] * H[7]) - H[1] * (H[3] * H[8] - H[5] * H[6]) + H[2] * (H[3] * H[7] - H[4] * H[6]);
     double        scale = 0.0;
@@ -71,6 +59,17 @@ int msd_check(psa_ctx* c, const char* entry, const double* box, const double* bo
     }
     p->n_a = p->start[(size_t)n_groups];
     for (int g = 0; g < n_groups; ++g) p->size.push_back(p->start[(size_t)g + 1] - p->start[(size_t)g]);
+    return PSA_OK;
+}
+
+namespace {
+
+constexpr int64_t MSD_TARGET_GROUPS = 4096;     // workgroups a launch aims at, where the work allows
+
+int msd_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
+              const int64_t* group_start, int32_t n_groups, int32_t unwrap, MsdCall* p) {
+    PSA_TRY(group_list_check(c, entry, box, box_inverse, idx, group_start, n_groups, p));
+    PSA_REQUIRE(unwrap == 0 || unwrap == 1, "unwrap is 0 or 1, got %d", (int)unwrap);
     const int64_t W = c->opt_dynamic_work_bytes, per_atom = 24 * p->T;
     PSA_REQUIRE(W / per_atom >= 1, "the work budget of %lld bytes (PSA_OPT_DYNAMIC_WORK_BYTES) cannot hold the smallest block: the "
                 "unwrapped displacements of one atom over %lld frames need %lld bytes", (long long)W, (long long)p->T, (long long)per_atom);

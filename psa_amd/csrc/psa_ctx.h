@@ -332,6 +332,12 @@ struct psa_ctx {
     psa::DevBuf  d_msd_u, d_msd_img, d_msd_sums, d_msd_offs, d_msd_idx, d_msd_chunks, d_msd_sizes, d_msd_lags, d_msd_part,
                  d_msd_acc, d_msd_out;
 
+    // pair distributions (psa_pair_histogram, psa_debug_pair_fractions; api_pair.hip): the centred fractional coordinates
+    // of a block of origin frames and of their partner frames (2, origins, 3, n_a) float32, held to opt_dynamic_work_bytes;
+    // outside it the atom list, the item table, the items' partial histograms and the accumulator that lives across
+    // blocks and lags.  All kept between calls.
+    psa::DevBuf  d_pair_c, d_pair_idx, d_pair_items, d_pair_part, d_pair_acc;
+
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
                                           // plane builds, trajectory uploads (psa_oneoff_stats)
@@ -592,6 +598,28 @@ int launch_msd_hist(psa_ctx* c, const double* d_u, const void* d_chunks, int64_t
                     unsigned* d_part, int64_t T, int64_t step, int64_t n_os, float inv_dr, int32_t n_r);
 int launch_msd_hist_reduce(psa_ctx* c, const unsigned* d_part, const int32_t* group_first, unsigned long long* d_acc, int64_t n_vh,
                            int64_t n_os, int32_t n_r, int32_t G);
+// --- pair.hip (psa_pair_histogram, psa_debug_pair_fractions: the histogram of minimum-image pair distances between two
+// species over time origins; the arithmetic and the tiling are in its header)
+constexpr int PAIR_TILE = 256;         // alpha-atoms of a workgroup, one per lane, and beta-atoms of a staged tile
+constexpr int PAIR_MAX_BINS = 1024;    // most bins of a pair histogram (an overflow counter follows them)
+constexpr int PAIR_MAX_LAGS = 64;      // most lags of a call
+constexpr int PAIR_MAX_SPECIES = 8;    // most species of a call
+// One workgroup's work: alpha-atoms [a_lo, a_lo + a_n) and beta-atoms [b_lo, b_hi) of the list, the origins slab, slab +
+// n_os, ... of the block.  diag: how the beta-tile that starts at a_lo is masked (0: not, 1: list position a < b, 2: b != a)
+struct PairItem {
+    int a_lo, a_n, b_lo, b_hi, slab, n_os, diag, pair;
+};
+// frames f0 + k df, k < n_frames, of the atoms d_idx (null: all N; n_a of them) -> d_out (n_frames, 3, n_a) float32
+int launch_pair_frac(psa_ctx* c, const float* d_pos, const int* d_idx, int64_t n_a, const double* box_inverse, float* d_out, int64_t f0,
+                     int64_t df, int64_t n_frames, int64_t T, int64_t N);
+// d_cA, d_cB (n_ob, 3, n_a): the fractions at the block's origins and at their partner frames; d_items: n_items PairItem,
+// listed species pair by species pair; d_part (n_items, n_r + 1) uint32 -- an item's samples stay below 2^32 (the caller's
+// rule).  The reduce adds to acc (S, S, n_r + 1) uint64; pair_first (S S + 1, host): where each pair's items begin;
+// sym: the items of (alpha <= beta) serve both orders (tau = 0)
+int launch_pair_hist(psa_ctx* c, const float* d_cA, const float* d_cB, const void* d_items, int64_t n_items, unsigned* d_part,
+                     const double* box, int64_t n_a, int64_t n_ob, float inv_dr, int32_t n_r);
+int launch_pair_hist_reduce(psa_ctx* c, const unsigned* d_part, const int32_t* pair_first, unsigned long long* d_acc, int32_t S,
+                            int32_t n_r, bool sym);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 
