@@ -158,6 +158,11 @@ int         psa_set_k1(psa_ctx* ctx, int selector);     /* PSA_K1_* */
  *                             accepted; a call whose single k-vector (and one segment of it) does not fit is PSA_EINVAL.
  *                             The (1 or 3, L, K) float32 result on the device is not part of the budget. */
 #define PSA_OPT_DYNAMIC_WORK_BYTES 13
+/*   PSA_OPT_K1_LOWRANK_PAIR [1] on the low-rank route (PSA_OPT_K1_LOWRANK), a launch whose D rows fill one 512-row block
+ *                             (at most 256 k-vectors) projects node rows and D rows in ONE kernel launch of two balanced
+ *                             workgroups per frame tile on one XCD (k1_lowrank_pair.hip) instead of the node pass and
+ *                             the D pass.  Same arithmetic, bit-identical results; 0 = always the two passes.  psa_k1_lowrank_pair_launches counts the launches it served. */
+#define PSA_OPT_K1_LOWRANK_PAIR 15   /* 14 is not assigned: psa_set_option refuses it as unknown */
 int         psa_set_option(psa_ctx* ctx, int option, int64_t value);
 /* device name / CU count / HBM bytes of the context's GPU */
 int         psa_device_info(psa_ctx* ctx, char* name, int name_len,
@@ -805,6 +810,12 @@ int psa_last_timings(psa_ctx* ctx, double* ms /* [8] */);
 int psa_k1_stats(psa_ctx* ctx, int64_t* launches, double* total_ms);
 /* projection launches of the context's life that took the low-rank route for k-paths (PSA_OPT_K1_LOWRANK) */
 int psa_k1_lowrank_launches(psa_ctx* ctx, int64_t* launches);
+/* ... of which the single pair launch served node rows and D rows (PSA_OPT_K1_LOWRANK_PAIR) */
+int psa_k1_lowrank_pair_launches(psa_ctx* ctx, int64_t* launches);
+/* The D image of that launch (k1_lowrank_pair.h) as a host-only service for tests: bytes = its size for n_stage 32-atom
+ * stages, padding included; index[512 * 32 n_stage] (may be null) = the float16 element index of (row m, atom a) at
+ * m * 32 n_stage + a.  No context, no GPU. */
+int psa_lowrank_pair_image(int32_t n_stage, int64_t* index, int64_t* bytes);
 /* host wall clock (ms) of work that is done once and then cached, summed since the last call:
  * [0] rocFFT plan builds (run-time compiled per (T, batch))  [1] largest-magnitude passes
  * [2] split-plane builds  [3] trajectory uploads (psa_data_upload / psa_sed_project_upload) */

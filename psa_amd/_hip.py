@@ -30,6 +30,7 @@ OPT_K1_LOWRANK_MIN_LOCAL = 10
 OPT_VDOS_WORK_BYTES = 11
 OPT_MODES_WORK_BYTES = 12
 OPT_DYNAMIC_WORK_BYTES = 13
+OPT_K1_LOWRANK_PAIR = 15        # (14 is not assigned)
 KMAP_MIRROR = 0x80000000
 ABI_VERSION = 6
 # the summation structure of the covariance kernel (psa_amd/csrc/covariance.hip), mirrored for the bound of tests/cov64.py
@@ -177,6 +178,8 @@ SIGNATURES = {
     "psa_last_timings": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
     "psa_k1_stats": (C.c_int, [_ctx, _i64p, C.POINTER(C.c_double)]),
     "psa_k1_lowrank_launches": (C.c_int, [_ctx, _i64p]),
+    "psa_k1_lowrank_pair_launches": (C.c_int, [_ctx, _i64p]),
+    "psa_lowrank_pair_image": (C.c_int, [C.c_int32, _i64p, _i64p]),
     "psa_oneoff_stats": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
     "psa_debug_phase_table": (C.c_int, [_ctx, _f32p, _f32p, C.c_int64, _i32p, C.c_int64,
                                         C.c_int64, C.c_void_p]),
@@ -301,6 +304,15 @@ def lowrank_plan(k_vectors, mean_pos_all, idx=None):
         return None
     return {"u": geo[0:3].copy(), "k0": geo[3:6].copy(), "x_c": geo[6], "h_x": geo[7], "width": geo[8],
             "interval": int(geo[9]), "d_bound": geo[10], "dscale": geo[11], "kappa": kappa, "C": cm, "L": lw, "phi": phi}
+
+
+def lowrank_pair_image(n_stage: int):
+    """The D image of the low-rank route's pair launch (psa_lowrank_pair_image; host only) for n_stage 32-atom stages:
+    (index, nbytes) with index (512, 32 n_stage) int64, the float16 element of (row, atom), and the image's size in
+    bytes, padding stages included."""
+    index, nbytes = np.zeros((512, 32 * int(n_stage)), np.int64), C.c_int64(0)
+    _check(load_library().psa_lowrank_pair_image(int(n_stage), index.ctypes.data_as(_i64p), C.byref(nbytes)), "psa_lowrank_pair_image")
+    return index, nbytes.value
 
 
 def host_mean_frames(x: np.ndarray, threads: int = 0) -> np.ndarray:
@@ -1319,6 +1331,12 @@ class Engine:
         """Projection launches so far that took the low-rank route for k-paths (PSA_OPT_K1_LOWRANK)."""
         n = C.c_int64(0)
         _check(self._lib.psa_k1_lowrank_launches(self._h, C.byref(n)), "psa_k1_lowrank_launches")
+        return n.value
+
+    def lowrank_pair_launches(self) -> int:
+        """... of which the pair launch projected node rows and D rows in one kernel (PSA_OPT_K1_LOWRANK_PAIR)."""
+        n = C.c_int64(0)
+        _check(self._lib.psa_k1_lowrank_pair_launches(self._h, C.byref(n)), "psa_k1_lowrank_pair_launches")
         return n.value
 
     # -- diagnostics -----------------------------------------------------------------

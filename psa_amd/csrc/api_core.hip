@@ -342,6 +342,7 @@ int psa_set_option(psa_ctx* c, int option, int64_t value) {
                 for (psa::DevBuf* b : {&c->d_lr_diff, &c->d_lr_qn, &c->d_lr_L, &c->d_lr_phi, &c->d_lr_f64}) b->release();
             }
             return PSA_OK;
+        case PSA_OPT_K1_LOWRANK_PAIR: c->opt_k1_lowrank_pair = value != 0; return PSA_OK;
         case PSA_OPT_K1_LOWRANK_MIN_LOCAL:
             PSA_REQUIRE(value >= 1, "PSA_OPT_K1_LOWRANK_MIN_LOCAL must be >= 1");
             c->opt_k1_lowrank_min_local = value;
@@ -408,6 +409,13 @@ int psa_k1_lowrank_launches(psa_ctx* c, int64_t* launches) {
     PSA_TRY(enter(c));
     PSA_REQUIRE(launches != nullptr, "null argument");
     *launches = c->lowrank_launches;
+    return PSA_OK;
+}
+
+int psa_k1_lowrank_pair_launches(psa_ctx* c, int64_t* launches) {
+    PSA_TRY(enter(c));
+    PSA_REQUIRE(launches != nullptr, "null argument");
+    *launches = c->lowrank_pair_launches;
     return PSA_OK;
 }
 

@@ -25,6 +25,7 @@
 // kernels.  A list that crosses Gamma declines as a whole while a part of it on one side may take the route, so
 // for such lists splitting can move rows by the ~1e-7 that separates the two routes.
 #include "api_internal.h"
+#include "k1_lowrank_pair.h"
 
 namespace psa {
 
@@ -220,6 +221,7 @@ int prepare_lowrank(psa_ctx* c, const GroupView& v, const ProjectArgs& list, int
     g->lowrank = true;
     g->dscale = p.dscale;
     g->M_pad_d = (int)((2 * nk + 511) / 512 * 512);
+    g->lr_pair = c->opt_k1_lowrank_pair && g->M_pad_d == LRP_ROWS;     // one D block: node rows and D rows in one launch
     return PSA_OK;
 }
 
@@ -242,6 +244,15 @@ int psa_lowrank_plan(const float* k_vectors, int64_t K, const float* mean_pos_al
     if (p.ok && kappa) std::memcpy(kappa, p.kappa, sizeof(p.kappa));
     if (p.ok && L) std::memcpy(L, p.L.data(), p.L.size() * sizeof(float));
     if (p.ok && phi) std::memcpy(phi, p.phi.data(), p.phi.size() * sizeof(float));
+    return PSA_OK;
+}
+
+int psa_lowrank_pair_image(int32_t n_stage, int64_t* index, int64_t* bytes) {
+    PSA_REQUIRE(n_stage >= 1 && n_stage < (1 << 20) && bytes, "bad argument");
+    *bytes = (int64_t)pd16_pair_table_bytes(n_stage);
+    if (index)
+        for (int m = 0; m < LRP_ROWS; ++m)
+            for (int a = 0; a < n_stage * K1_BA; ++a) index[(size_t)m * n_stage * K1_BA + a] = (int64_t)pd16_pair_index(m, a, n_stage);
     return PSA_OK;
 }
 

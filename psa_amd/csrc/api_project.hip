@@ -278,7 +278,7 @@ int prepare_phase(psa_ctx* c, const GroupView& v, const ProjGeom& g, int64_t k_f
         StageTimer    st(c, PSA_T_PHASE);
         const double* f64 = c->d_lr_f64.as<double>();
         return launch_lowrank_tables(c, d_kvec, f64 + 7 + LOWRANK_NODES, f64, f64 + 7, c->d_mean_all.as<float>(), d_idx,
-                                     c->d_lr_diff.ptr, c->d_phase.ptr, g, g.M_pad_d, g.dscale);
+                                     c->d_lr_diff.ptr, c->d_phase.ptr, g, g.M_pad_d, g.dscale, g.lr_pair);
     }
     PSA_TRY(c->d_phase.reserve(f16    ? pf16_table_bytes(g.M_pad, g.A_pad)
                                : bf16 ? pb_table_bytes(g.M_pad, g.A_pad)
@@ -338,10 +338,15 @@ static int launch_projection_once(psa_ctx* c, const GroupView& v, ProjGeom g, fl
             gn.m_blk = gn.M_pad = 2 * LOWRANK_NODES;
             gn.q_stride = t_count;
             PSA_REQUIRE(c->d_lr_qn.cap >= (size_t)LOWRANK_NODES * 3 * t_count * sizeof(float2), "node projections not reserved");
-            PSA_TRY(launch_k1_planes_lw(c, pl, c->d_phase.ptr, c->d_lr_qn.as<float2>(), gn, n_fg));
-            ProjGeom gd = g;
-            gd.M_pad = g.M_pad_d;
-            PSA_TRY(launch_k1_planes_diff(c, pl, c->d_lr_diff.ptr, d_q, gd, n_fg, g.dscale));
+            if (g.lr_pair) {      // one 512-row D block: both in one launch of balanced row pairs (the D image is in its layout)
+                PSA_TRY(launch_k1_lowrank_pair(c, pl, c->d_phase.ptr, c->d_lr_diff.ptr, c->d_lr_qn.as<float2>(), d_q, g, n_fg, g.dscale));
+                ++c->lowrank_pair_launches;
+            } else {
+                PSA_TRY(launch_k1_planes_lw(c, pl, c->d_phase.ptr, c->d_lr_qn.as<float2>(), gn, n_fg));
+                ProjGeom gd = g;
+                gd.M_pad = g.M_pad_d;
+                PSA_TRY(launch_k1_planes_diff(c, pl, c->d_lr_diff.ptr, d_q, gd, n_fg, g.dscale));
+            }
             PSA_TRY(launch_lowrank_combine_r(c, c->d_lr_qn.as<float2>(), c->d_lr_L.as<float>(), c->d_lr_phi.as<float2>(), d_q, g,
                                              t_count));
             ++c->lowrank_launches;

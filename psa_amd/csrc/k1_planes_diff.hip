@@ -25,6 +25,7 @@
 #include <utility>
 
 #include "k1_f16.h"
+#include "k1_lowrank_pair.h"
 
 namespace psa {
 
@@ -201,6 +202,8 @@ int launch_k1_planes_diff(psa_ctx* c, const void* d_planes, const void* d_diff, 
 // projected on the plan's line, kline[3 j..], in fp64.  Rows past 2K and atoms past n_g are zero.
 // Per-atom weights w (may be null): the route is linear per atom column, so D and the node rows both carry the same
 // w * wnorm (phase_table_f16_kernel, k1_pair.hip): |w wnorm| <= 1 keeps |D| under the plan's bound and dscale valid.
+// PAIR: the image of the pair launch (pd16_pair_index, k1_lowrank_pair.h; one 512-row block) instead of the D pass's.
+template <bool PAIR>
 __global__ void __launch_bounds__(256)
 diff_table_kernel(const float* __restrict__ kvec, const double* __restrict__ kline, const float* __restrict__ mean_all,
                   const int* __restrict__ idx, const float* __restrict__ w, float wnorm, _Float16* __restrict__ Db, int K,
@@ -224,8 +227,8 @@ diff_table_kernel(const float* __restrict__ kvec, const double* __restrict__ kli
         d[1] = (float)(((double)cs[1] - se) * (double)dscale * wa);
     }
     const int n_stage = A_pad / K1_BA;
-    Db[pd16_index(2 * k, a, n_stage)] = (_Float16)d[0];
-    Db[pd16_index(2 * k + 1, a, n_stage)] = (_Float16)d[1];
+    Db[PAIR ? pd16_pair_index(2 * k, a, n_stage) : pd16_index(2 * k, a, n_stage)] = (_Float16)d[0];
+    Db[PAIR ? pd16_pair_index(2 * k + 1, a, n_stage) : pd16_index(2 * k + 1, a, n_stage)] = (_Float16)d[1];
 }
 
 // Node rows W[l, a] = exp(i k0.r_a) exp(i kappa_l (u.r_a - x_c)), fp64 argument and sincos, in the two-piece phase-table
@@ -262,13 +265,22 @@ node_table_kernel(const double* __restrict__ geo, const double* __restrict__ kap
 
 int launch_lowrank_tables(psa_ctx* c, const float* d_kvec, const double* d_kline, const double* d_geo, const double* d_kappa,
                           const float* d_mean_all, const int* d_idx, void* d_diff, void* d_nodes, const ProjGeom& g, int M_pad_d,
-                          float dscale) {
+                          float dscale, bool pair) {
     PSA_REQUIRE(M_pad_d % D_M_BLK == 0 && M_pad_d >= 2 * g.K && g.A_pad % K1_BA == 0, "bad low-rank table geometry");
-    hipLaunchKernelGGL(diff_table_kernel, dim3(M_pad_d / 2, (g.A_pad + 255) / 256), dim3(256), 0, c->stream, d_kvec, d_kline, d_mean_all,
-                       d_idx, g.weights, 1.f / g.wscale, (_Float16*)d_diff, g.K, g.n_g, g.A_pad, dscale);
+    PSA_REQUIRE(!pair || M_pad_d == LRP_ROWS, "the pair launch's image is one 512-row block");
+    hipLaunchKernelGGL(pair ? diff_table_kernel<true> : diff_table_kernel<false>, dim3(M_pad_d / 2, (g.A_pad + 255) / 256), dim3(256), 0,
+                       c->stream, d_kvec, d_kline, d_mean_all, d_idx, g.weights, 1.f / g.wscale, (_Float16*)d_diff, g.K, g.n_g, g.A_pad,
+                       dscale);
     PSA_HIP_CHECK(hipGetLastError());
-    PSA_HIP_CHECK(hipMemsetAsync((char*)d_diff + (size_t)M_pad_d * g.A_pad * 2, 0, pd16_table_bytes(M_pad_d, g.A_pad) - (size_t)M_pad_d * g.A_pad * 2,
-                                 c->stream));
+    if (pair) {      // each role's part ends with its own padding stages
+        const size_t n_stage = (size_t)g.A_pad / K1_BA, a_pad = LRP_PAD_STAGES * LRP_A_UNITS * 1024, b_pad = LRP_PAD_STAGES * LRP_B_UNITS * 1024;
+        static_assert(LRP_ROWS == D_M_BLK, "the pair image has the size of one D block");
+        PSA_HIP_CHECK(hipMemsetAsync((char*)d_diff + n_stage * LRP_A_UNITS * 1024, 0, a_pad, c->stream));
+        PSA_HIP_CHECK(hipMemsetAsync((char*)d_diff + pd16_pair_table_bytes((int)n_stage) - b_pad, 0, b_pad, c->stream));
+    } else {
+        PSA_HIP_CHECK(hipMemsetAsync((char*)d_diff + (size_t)M_pad_d * g.A_pad * 2, 0,
+                                     pd16_table_bytes(M_pad_d, g.A_pad) - (size_t)M_pad_d * g.A_pad * 2, c->stream));
+    }
     hipLaunchKernelGGL(node_table_kernel, dim3(LOWRANK_NODES, (g.A_pad + 255) / 256), dim3(256), 0, c->stream, d_geo, d_kappa, d_mean_all,
                        d_idx, g.weights, 1.f / g.wscale, (_Float16*)d_nodes, g.n_g, g.A_pad);
     PSA_HIP_CHECK(hipGetLastError());

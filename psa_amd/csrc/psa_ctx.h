@@ -143,6 +143,7 @@ struct ProjGeom {
     bool    lowrank = false;  // f16_planes through the low-rank route for k-paths (api_lowrank.hip, k1_planes_diff.hip)
     int     M_pad_d = 0;      // lowrank: rows of the D image (2K rounded up to 512)
     float   dscale = 0.f;     // lowrank: power of two the D image carries
+    bool    lr_pair = false;  // lowrank: node rows and D rows in one launch (k1_lowrank_pair.hip; PSA_OPT_K1_LOWRANK_PAIR)
     // per-atom weights (psa_set_atom_weights), folded into the phase table: (N_tot) float32 on the device, indexed like
     // the mean positions; nullptr = none.  The float16 tables hold w 2^-e and their launches multiply qscale by
     // wscale = 2^e (the float32 and bf16 tables hold w itself)
@@ -251,6 +252,8 @@ struct psa_ctx {
     int64_t      opt_k1_lowrank_min_k = 256;    // PSA_OPT_K1_LOWRANK_MIN_K: shortest whole k-list it serves
     int64_t      opt_k1_lowrank_min_local = 128; // PSA_OPT_K1_LOWRANK_MIN_LOCAL: shortest part of it one launch serves
     int64_t      lowrank_launches = 0;          // projection launches that took the route (psa_k1_lowrank_launches)
+    int64_t      opt_k1_lowrank_pair = 1;       // PSA_OPT_K1_LOWRANK_PAIR: lists with one 512-row D block through k1_lowrank_pair.hip
+    int64_t      lowrank_pair_launches = 0;     // ... of which the pair launch served (psa_k1_lowrank_pair_launches)
     // its D image, node projections, the combine's L and phi, fp64 inputs (the node table goes into d_phase);
     // released when the route is switched off
     psa::DevBuf  d_lr_diff, d_lr_qn, d_lr_L, d_lr_phi, d_lr_f64;
@@ -409,9 +412,14 @@ int    launch_k1_planes_wide(psa_ctx* c, const void* d_planes, const void* d_pha
 size_t pd16_table_bytes(int M_pad, int A_pad);
 int    launch_lowrank_tables(psa_ctx* c, const float* d_kvec, const double* d_kline, const double* d_geo, const double* d_kappa,
                              const float* d_mean_all, const int* d_idx, void* d_diff, void* d_nodes, const ProjGeom& g, int M_pad_d,
-                             float dscale);
+                             float dscale, bool pair);
 int    launch_k1_planes_diff(psa_ctx* c, const void* d_planes, const void* d_diff, float2* d_q, const ProjGeom& g, int64_t n_fg,
                              float dscale);
+
+// --- k1_lowrank_pair.hip (the route's node rows and D rows as one launch of balanced row pairs: one 512-row D block;
+// the D image in the pair layout, launch_lowrank_tables with pair = true)
+int    launch_k1_lowrank_pair(psa_ctx* c, const void* d_planes, const void* d_nodes, const void* d_diff, float2* d_qn, float2* d_q,
+                              const ProjGeom& g, int64_t n_fg, float dscale);
 
 // --- lowrank_combine.hip (the route's combine: real weights + one phase per element)
 int    launch_lowrank_combine_r(psa_ctx* c, const float2* d_qn, const float* d_L, const float2* d_phi, float2* d_q, const ProjGeom& g,
