@@ -758,6 +758,58 @@ int psa_pair_histogram(psa_ctx* ctx, const double* box /* 9 */, const double* bo
                        int64_t origin_step, double dr, int32_t n_r, uint64_t* out_host /* (n_lags, S, S, n_r + 1) */,
                        size_t out_bytes);
 
+/* Bond-angle distributions and coordination statistics: the neighbour shell of every atom at every time origin, the
+ * histogram of the angles between pairs of neighbours and the histogram of the neighbour counts, as integer counts.
+ * Inputs.  The positions resident in PSA_SLOT_POSITIONS as stored; nothing is unwrapped, for the reason given at
+ * psa_pair_histogram.  H = box with its inverse, and S <= 8 disjoint species (idx, group_start), as for
+ * psa_pair_histogram.  r_cut (S, S) double, symmetric, every entry finite, >= 0 (0: no bond between these species) and
+ * <= the served radius of psa_pair_histogram (the same relative slack of 2^-40).  Origins o = 0, s, 2 s, ... <= T-1,
+ * s = origin_step, n_o = (T-1) / s + 1.  n_theta in [1, 1024].
+ * Neighbour.  b in beta is a neighbour of a in alpha at origin o when b != a, r_cut[alpha,beta] > 0 and x < 1, x being
+ * exactly the value psa_pair_histogram forms with dr = r_cut[alpha,beta]:
+ *     c_j from the float64 prepass;   e_j = c_j(b) - c_j(a);  e_j = e_j - rintf(e_j)
+ *     d_c = fma(e_2, h[2][c], fma(e_1, h[1][c], e_0 h[0][c]));   r2 = fma(d_z, d_z, fma(d_y, d_y, d_x d_x))
+ *     x = sqrt(r2) float32(1 / r_cut[alpha,beta])
+ * every operation rounded once.  With one scalar cut-off the number of neighbours is bit for bit the count that
+ * psa_pair_histogram puts into bin 0 with dr = r_cut, n_r = 1.
+ * Capacity.  A centre holds at most 64 neighbours (ANGLE_MAX_NEIGHBOURS), all species together.  A (centre, origin) with
+ * more is truncated: it contributes to neither histogram -- all or nothing, never its first 64 -- and is counted in
+ * truncated[alpha].
+ * Coordination.  coord[alpha,beta,n], n = 0 .. 64: the number of (a in alpha, o), not truncated, with exactly n
+ * neighbours of species beta.  sum_n coord[alpha,beta,n] + truncated[alpha] = n_o N_alpha for every beta, exactly.
+ * Angles.  For a centre a in alpha that is not truncated, every unordered pair {b, c} of its neighbours, b in beta, c in
+ * gamma, is filed under the species pair p(beta <= gamma) -- upper triangle, row-major, P = S (S + 1) / 2 pairs: (0,0),
+ * (0,1), .., (0,S-1), (1,1), .. -- by the angle at a.  float32, every operation rounded once, from the d of the two legs:
+ *     dot = fma(d_z(b), d_z(c), fma(d_y(b), d_y(c), d_x(b) d_x(c)));   q = r2(b) r2(c);   cos = dot / sqrt(q)
+ * clamped to [-1, 1]; every step is symmetric in b <-> c bit for bit, so the order of the list cannot move a count.
+ * Bins are uniform in theta over [0, pi], defined through the table cedge[i] = float32(cos(i pi / n_theta)) computed in
+ * float64 and rounded once, cedge[0] = 1 and cedge[n_theta] = -1 exactly (strictly decreasing up to 1024 bins):
+ * bin = the i with cedge[i+1] < cos <= cedge[i]; cos = -1 goes to the last bin; a cos that is not a number (a coincident
+ * neighbour, r2 = 0) goes to the extra counter n_theta ("undefined").  angles[alpha,p,i], i <= n_theta.
+ *     sum_i angles[alpha,p(beta,beta),i] = sum_n coord[alpha,beta,n] n (n - 1) / 2
+ *     sum_i angles[alpha,p(beta,gamma),i] = sum over the centres that are not truncated of n_beta n_gamma   (beta < gamma)
+ * exactly.
+ * As evaluated (angle.hip): the fraction pass of psa_pair_histogram; a neighbour pass in which a workgroup holds 256
+ * centres in registers and walks all beta-atoms staged in LDS, appending each hit {d_x, d_y, d_z, list position and
+ * species} to the lane's own list and counting on beyond 64; an angle pass in which a wavefront reads a centre's list
+ * once, its lanes take the pairs, and counts go by 32-bit integer adds into histograms in LDS -- the host keeps a
+ * workgroup's samples below 2^32 --, written to partials with plain stores and summed in 64-bit integers.  No global
+ * atomics, no float atomics; two identical calls, any budget and any order of the atoms inside a species give the same
+ * bits.
+ * Budget (PSA_OPT_DYNAMIC_WORK_BYTES): per origin of a block c, the counts and the lists of the listed atoms, 1040 n_a
+ * bytes; a block is a whole number of origins, a budget below one origin is refused and the refusal names the bytes
+ * needed.
+ * PSA_EINVAL: what psa_pair_histogram refuses about the context (a sharded one among it), the box, the inverse and the
+ * species; a null pointer; r_cut not symmetric, negative, not finite or beyond the served radius; origin_step < 1;
+ * n_theta outside [1, 1024]; angles_bytes or coord_bytes not exact; 2^28 or more listed atoms; a budget below one origin.
+ * Only the positions slot is read.  Atom weights and segments set on the context are ignored, not refused; every result
+ * and plan of the other entry points is left as it is.  Stage times: [0] the tables' upload, [5] the fraction pass,
+ * [6] the neighbour pass, [1] the angle pass, [4] reduce, [7] device->host. */
+int psa_angle_histogram(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                        const int64_t* group_start /* S+1 */, int32_t n_groups, const double* r_cut /* S*S */, int64_t origin_step,
+                        int32_t n_theta, uint64_t* angles /* (S, P, n_theta + 1) */, size_t angles_bytes,
+                        uint64_t* coord /* (S, S, 65) */, size_t coord_bytes, uint64_t* truncated /* S */);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is
@@ -985,6 +1037,14 @@ int psa_debug_pair_fractions(psa_ctx* ctx, const double* box_inverse /* 9 */, co
  * out[2] the items, out[3] the most samples one item can count (256 x its beta-atoms x its origins), which stays below
  * 2^32.  PSA_EINVAL: a null pointer, n_groups outside [1, 8], a negative size, n_origins outside [1, 65535]. */
 int psa_debug_pair_plan(const int64_t* sizes /* n_groups */, int32_t n_groups, int32_t sym, int64_t n_origins, int64_t* out /* 4 */);
+
+/* the fraction pass and the neighbour pass of psa_angle_histogram alone at one frame in [0, T-1]: count (n_a) int32 the
+ * true number of neighbours of every listed atom (it may exceed 64), list (n_a, 64) int32 the list positions of its
+ * first 64 neighbours in ascending order, padded with -1.  PSA_EINVAL: what that entry refuses about the context, the
+ * box, the species, r_cut and the budget; a frame outside [0, T-1]. */
+int psa_debug_neighbour_lists(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                              const int64_t* group_start /* S+1 */, int32_t n_groups, const double* r_cut /* S*S */, int64_t frame,
+                              int32_t* count /* n_a */, int32_t* list /* (n_a, 64) */);
 
 #ifdef __cplusplus
 }

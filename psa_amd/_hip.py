@@ -77,6 +77,9 @@ PAIR_TILE = 256        # alpha-atoms of a workgroup and beta-atoms of a staged t
 PAIR_MAX_BINS = 1024   # most bins of a pair histogram
 PAIR_MAX_LAGS = 64     # most lags of a pair call
 PAIR_MAX_SPECIES = 8   # most species of a pair call
+# the caps of the angle kernels (psa_amd/csrc/angle.hip)
+ANGLE_MAX_NEIGHBOURS = 64   # most neighbours a centre holds, all species together
+ANGLE_MAX_BINS = 1024       # most bins of an angle histogram
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -166,6 +169,11 @@ SIGNATURES = {
                                      C.c_int64, C.c_double, C.c_int32, C.POINTER(C.c_uint64), C.c_size_t]),
     "psa_debug_pair_fractions": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _f32p]),
     "psa_debug_pair_plan": (C.c_int, [_i64p, C.c_int32, C.c_int32, C.c_int64, _i64p]),
+    "psa_angle_histogram": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i64p, C.c_int32, C.POINTER(C.c_double),
+                                      C.c_int64, C.c_int32, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t,
+                                      C.POINTER(C.c_uint64)]),
+    "psa_debug_neighbour_lists": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i64p, C.c_int32,
+                                            C.POINTER(C.c_double), C.c_int64, _i32p, _i32p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
@@ -1086,6 +1094,51 @@ class Engine:
         _check(load_library().psa_debug_pair_plan(n.ctypes.data_as(_i64p), n.size, 1 if sym else 0, int(n_origins),
                                                   out.ctypes.data_as(_i64p)), "psa_debug_pair_plan")
         return dict(run=int(out[0]), slabs=int(out[1]), items=int(out[2]), most_samples=int(out[3]))
+
+    @staticmethod
+    def _cutoffs(r_cut, S: int) -> np.ndarray:
+        """r_cut as the (S, S) float64 matrix of a call: a scalar is every entry"""
+        rc = np.asarray(r_cut, np.float64)
+        rc = np.full((S, S), float(rc)) if rc.ndim == 0 else np.ascontiguousarray(rc)
+        if rc.shape != (S, S):
+            raise ValueError(f"r_cut must be a scalar or ({S}, {S}), got {rc.shape}")
+        return rc
+
+    def angle_histogram(self, box, r_cut, n_theta: int, groups=None, origin_step: int = 1, box_inverse=None):
+        """Bond angles and coordination as counts (psa_angle_histogram): (angles (S, P, n_theta + 1) uint64, coord (S, S,
+        65) uint64, truncated (S,) uint64).  b is a neighbour of a when b != a and |mi(r_b - r_a)| < r_cut[alpha, beta]
+        (`r_cut` a scalar or symmetric (S, S), 0: no bond); angles[alpha, p, i] counts the unordered neighbour pairs of
+        the centres of species alpha, filed under the species pair p (upper triangle, row-major) in bin i of `n_theta`
+        uniform bins of the angle at the centre, the last entry the undefined angles; coord[alpha, beta, n] the (centre,
+        origin) with exactly n beta-neighbours; a centre with more than 64 neighbours is left out of both and counted in
+        truncated[alpha].  `box`, `groups`, `origin_step` as for `pair_histogram`.  Only positions are read, as stored."""
+        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
+        rc = self._cutoffs(r_cut, G)
+        P, n1 = G * (G + 1) // 2, max(int(n_theta), 0) + 1
+        angles = np.empty((G, P, n1), np.uint64)
+        coord = np.empty((G, G, ANGLE_MAX_NEIGHBOURS + 1), np.uint64)
+        trunc = np.empty(G, np.uint64)
+        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+        _check(self._lib.psa_angle_histogram(self._h, H.ctypes.data_as(dp), inv.ctypes.data_as(dp), ip, sp, G, rc.ctypes.data_as(dp),
+                                             int(origin_step), int(n_theta), angles.ctypes.data_as(up), angles.nbytes,
+                                             coord.ctypes.data_as(up), coord.nbytes, trunc.ctypes.data_as(up)), "psa_angle_histogram")
+        return angles, coord, trunc
+
+    def debug_neighbour_lists(self, box, r_cut, frame: int, groups=None, box_inverse=None):
+        """The neighbour pass of `angle_histogram` alone at one frame (psa_debug_neighbour_lists): (count (n_a,) int32 the
+        true numbers of neighbours, list (n_a, 64) int32 the positions in the concatenated atom list of the first 64,
+        ascending, padded with -1)."""
+        T, N = self.shape(SLOT_POSITIONS)
+        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
+        rc = self._cutoffs(r_cut, G)
+        n_a = N if groups is None else int(start[-1])
+        count = np.zeros(max(n_a, 1), np.int32)
+        lst = np.full((max(n_a, 1), ANGLE_MAX_NEIGHBOURS), -1, np.int32)
+        dp = C.POINTER(C.c_double)
+        _check(self._lib.psa_debug_neighbour_lists(self._h, H.ctypes.data_as(dp), inv.ctypes.data_as(dp), ip, sp, G,
+                                                   rc.ctypes.data_as(dp), int(frame), count.ctypes.data_as(_i32p),
+                                                   lst.ctypes.data_as(_i32p)), "psa_debug_neighbour_lists")
+        return count[:n_a], lst[:n_a]
 
     def debug_correlation_transform(self, power, L: int, n_seg: int, n_lags: int, as_float32: bool = False) -> np.ndarray:
         """The back-transform of the time correlations alone (psa_debug_correlation_transform): `power` (fields, P, cols)

@@ -36,6 +36,8 @@ from ..correlations import PowderTimeCorrelations, TimeCorrelations, check_boxca
 from ..covariance import ModeVectors, mode_vectors, spectral_weights
 from ..displacements import MeanSquareDisplacement, VanHoveSelf, alpha2, check_origin_step, origin_counts
 from ..dynamic import DynamicSpectra
+from .. import angles
+from ..angles import BondAngleDistribution
 from ..pairs import RadialDistribution, VanHoveDistinct, max_pair_radius
 from .. import lattice
 from ..lattice import PowderSpectra
@@ -975,6 +977,51 @@ class SEDCalculator:
         n_o, samples = self._pair_samples(tau, step, sizes)
         return VanHoveDistinct(out[:, :, :, :n_r].copy(), out[:, :, :, n_r].copy(), samples, edges, centres, volume, groups, sizes, n_o,
                                tau, times, self.dt_ps)
+
+    # ------------------------------------------------------------------ bond angles and coordination
+    def calculate_bond_angles(self, r_cut, n_theta: int = 180,
+                              basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                              basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                              origin_step: int = 1) -> BondAngleDistribution:
+        """Bond-angle distributions of species triplets and the coordination statistics of species pairs (not in the
+        reference; definition in psa_amd/angles.py), computed on the GPU from the positions resident in HBM.  An atom b
+        of species beta is a neighbour of an atom a of species alpha when their minimum-image distance is below
+        `r_cut[alpha][beta]` -- `r_cut` a scalar or a symmetric (S, S) matrix, 0 meaning "no bond between these species",
+        no entry beyond `psa_amd.max_pair_radius(box)`.  Over the frames 0, origin_step, ... the angle at a between every
+        unordered pair of its neighbours is counted in `n_theta` <= 1024 uniform bins over [0, 180] degrees, per centre
+        species and species pair of the neighbours, and the number of beta-neighbours of every alpha-atom in
+        `coordination_counts`.  Integer counts, positions as stored, nothing unwrapped.
+
+        Species are resolved like those of `calculate_rdf` (disjoint, at most 8).  A centre holds at most 64 neighbours;
+        where a centre has more the call raises ValueError naming the species: choose a smaller `r_cut`
+        (`Engine.angle_histogram` returns the numbers instead).  A sharded calculator refuses (NotImplementedError).
+        Returns a `psa_amd.BondAngleDistribution` with `density`, `triplet(centre, b, c)`, `coordination_fraction` and
+        `mean_coordination`."""
+        if isinstance(n_theta, bool) or not isinstance(n_theta, (int, np.integer)) or not 1 <= int(n_theta) <= _hip.ANGLE_MAX_BINS:
+            raise ValueError(f"n_theta must be an integer in [1, {_hip.ANGLE_MAX_BINS}], got {n_theta!r}")
+        n_theta = int(n_theta)
+        rc = np.asarray(r_cut, np.float64)
+        if rc.ndim not in (0, 2) or not np.all(np.isfinite(rc)) or np.any(rc < 0.0):
+            raise ValueError("r_cut must be a scalar or an (S, S) matrix of finite values that are not negative")
+        served = max_pair_radius(self.traj.box_matrix)           # ValueError for a box that is not finite or singular
+        if rc.size and float(rc.max()) > served:
+            raise ValueError(f"r_cut = {float(rc.max())!r} is beyond the served radius {served!r} (psa_amd.max_pair_radius): "
+                             "(1/2 - 2^-12) of the box's least perpendicular width")
+        what = "the bond-angle distribution"
+        step, groups = self._displacement_groups(basis_atom_indices, basis_atom_types, origin_step, True, None, 0, what)
+        if groups is None:
+            logger.warning(f"Cannot calculate {what}: 0 frames or 0 atoms.")
+            return angles.distribution(np.zeros((1, 1, n_theta + 1), np.uint64), np.zeros((1, 1, _hip.ANGLE_MAX_NEIGHBOURS + 1), np.uint64),
+                                       np.zeros(1, np.uint64), n_theta, 0, [np.zeros(0, int)])
+        S = len(groups)
+        if rc.ndim == 2 and (rc.shape != (S, S) or not np.array_equal(rc, rc.T)):
+            raise ValueError(f"r_cut must be a scalar or a symmetric ({S}, {S}) matrix, got shape {rc.shape}")
+        out, coord, truncated = self._displacement_run(lambda eng, box: eng.angle_histogram(box, rc, n_theta, groups, step))
+        if truncated.any():
+            bad = ", ".join(f"species {a}: {int(truncated[a])}" for a in np.flatnonzero(truncated))
+            raise ValueError(f"centres with more than {_hip.ANGLE_MAX_NEIGHBOURS} neighbours were left out ({bad} (centre, frame) "
+                             "samples): r_cut reaches beyond the first shells, choose a smaller r_cut")
+        return angles.distribution(out, coord, truncated, n_theta, (self.traj.n_frames - 1) // step + 1, groups)
 
     # ------------------------------------------------------------------ partial (species-resolved) spectra on that lattice
     def _partial_species(self, basis_atom_indices, basis_atom_types, weights):

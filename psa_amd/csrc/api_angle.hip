@@ -1,0 +1,227 @@
+// psa_angle_histogram, psa_debug_neighbour_lists: the bond-angle distributions of species triplets and the coordination
+// statistics of species pairs over time origins (definition: include/psa_hip.h; kernels: angle.hip, and pair.hip's
+// fraction pass).  Only the positions slot is read; atom weights and segments set on the context are ignored; nothing of
+// the other entry points' state is touched.
+//
+// Budget (PSA_OPT_DYNAMIC_WORK_BYTES = W): per origin of a block the centred fractional coordinates of the listed atoms
+// (12 n_a bytes), their neighbour counts (4 n_a) and their neighbour lists (64 x 16 n_a): 1040 n_a bytes; a block is a
+// whole number of origins, W / (1040 n_a) of them, and a budget below one origin is refused.  The item table, the bin
+// edges, the partials, the accumulator and the result lie outside it.  Per block: the fraction pass, the neighbour pass,
+// the angle pass over the items, the reduce into the accumulator that lives across blocks.
+#include "api_internal.h"
+
+namespace psa {
+
+namespace {
+
+constexpr int64_t ANGLE_TARGET_GROUPS = 4096;   // workgroups the angle pass aims at, where the work allows
+constexpr int64_t ANGLE_ITEM_CENTRES = 64;      // centres of an item of the angle pass: 16 per wavefront and origin
+constexpr int64_t ANGLE_PART_BYTES = 64 << 20;  // what the items' partials aim to stay below
+// most origins of an item: 64 centres x 8192 origins x 2016 pairs of 64 neighbours stay below 2^32
+constexpr int64_t ANGLE_MAX_SLAB = 8192;
+static_assert((uint64_t)ANGLE_ITEM_CENTRES * ANGLE_MAX_SLAB * (ANGLE_MAX_NEIGHBOURS * (ANGLE_MAX_NEIGHBOURS - 1) / 2) < (1ull << 32),
+              "an item's samples fit 32 bits");
+constexpr int64_t ANGLE_ORIGIN_BYTES = 12 + 4 + 16 * ANGLE_MAX_NEIGHBOURS;   // per atom and origin
+
+// the box's least perpendicular width: 1 / |column j of Hinv|
+double angle_min_width(const double* inv) {
+    double w = INFINITY;
+    for (int j = 0; j < 3; ++j) w = std::min(w, 1.0 / std::sqrt(inv[j] * inv[j] + inv[3 + j] * inv[3 + j] + inv[6 + j] * inv[6 + j]));
+    return w;
+}
+
+// the shared checks, the cut-offs and the budget; fills p (Ab: origins of a block) and sp
+int angle_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
+                const int64_t* group_start, int32_t n_groups, const double* r_cut, MsdCall* p, AngleSpecies* sp) {
+    PSA_TRY(group_list_check(c, entry, box, box_inverse, idx, group_start, n_groups, p));
+    PSA_REQUIRE(r_cut != nullptr, "null r_cut");
+    const int    S = p->G;
+    const double served = (0.5 - 0x1p-12) * angle_min_width(box_inverse);
+    *sp = AngleSpecies{};
+    sp->S = S;
+    for (int a = 0; a < S; ++a)
+        for (int b = 0; b < S; ++b) {
+            const double r = r_cut[a * S + b];
+            PSA_REQUIRE(std::isfinite(r) && r >= 0.0, "r_cut[%d][%d] must be finite and not negative, got %g", a, b, r);
+            PSA_REQUIRE(r == r_cut[b * S + a], "r_cut is not symmetric: [%d][%d] = %.17g, [%d][%d] = %.17g", a, b, r, b, a, r_cut[b * S + a]);
+            PSA_REQUIRE(r <= served * (1.0 + 0x1p-40), "r_cut[%d][%d] = %.17g is beyond the served radius %.17g: (1/2 - 2^-12) of the "
+                        "box's least perpendicular width", a, b, r, served);
+            const float inv = r > 0.0 ? (float)(1.0 / r) : 0.f;
+            PSA_REQUIRE(r == 0.0 || (std::isfinite(inv) && inv > 0.f), "r_cut[%d][%d] = %g has no float32 reciprocal", a, b, r);
+            sp->inv_rc[a * S + b] = inv;
+        }
+    PSA_REQUIRE(p->n_a < (1ll << ANGLE_SPECIES_SHIFT), "at most 2^%d - 1 listed atoms are served, got %lld", ANGLE_SPECIES_SHIFT,
+                (long long)p->n_a);
+    for (int g = 0; g <= S; ++g) sp->start[g] = (int)p->start[(size_t)g];
+    for (int g = 0; g < S; ++g) sp->tile_first[g + 1] = sp->tile_first[g] + (int)((p->size[(size_t)g] + ANGLE_CENTRES - 1) / ANGLE_CENTRES);
+    const int64_t W = c->opt_dynamic_work_bytes, per_origin = ANGLE_ORIGIN_BYTES * std::max<int64_t>(p->n_a, 1);
+    PSA_REQUIRE(W / per_origin >= 1, "the work budget of %lld bytes (PSA_OPT_DYNAMIC_WORK_BYTES) cannot hold the smallest block: the "
+                "fractional coordinates, neighbour counts and neighbour lists of %lld atoms at one origin need %lld bytes", (long long)W,
+                (long long)p->n_a, (long long)per_origin);
+    p->Ab = W / per_origin;
+    return PSA_OK;
+}
+
+int angle_upload_list(psa_ctx* c, const MsdCall& p, const int32_t* idx) {
+    StageTimer st(c, PSA_T_H2D);
+    return p.listed ? upload(c, c->d_angle_idx, idx, (size_t)p.n_a * sizeof(int32_t)) : PSA_OK;
+}
+
+// the work buffer of a block of B origins: the lists first (16-byte entries), then c, then the counts
+struct AngleWork {
+    float4* list;
+    float*  c;
+    int*    count;
+};
+int angle_work(psa_ctx* c, int64_t n_a, int64_t B, AngleWork* w) {
+    const size_t rows = (size_t)B * (size_t)n_a;
+    PSA_TRY(c->d_angle_work.reserve(rows * (size_t)ANGLE_ORIGIN_BYTES));
+    char* base = static_cast<char*>(c->d_angle_work.ptr);
+    w->list = reinterpret_cast<float4*>(base);
+    w->c = reinterpret_cast<float*>(base + rows * 16 * ANGLE_MAX_NEIGHBOURS);
+    w->count = reinterpret_cast<int*>(base + rows * (16 * ANGLE_MAX_NEIGHBOURS + 12));
+    return PSA_OK;
+}
+
+// The items of the angle pass over n_ob origins, species by species, ANGLE_ITEM_CENTRES centres each; first (S + 1): where
+// each species' items begin.  The partials (items x row words) stay below ANGLE_PART_BYTES where one slab per tile allows
+std::vector<AngleItem> angle_items(const MsdCall& p, int64_t n_ob, int64_t row, int32_t* first) {
+    int64_t tiles = 0;
+    for (int g = 0; g < p.G; ++g) tiles += (p.size[(size_t)g] + ANGLE_ITEM_CENTRES - 1) / ANGLE_ITEM_CENTRES;
+    const int64_t target = std::max<int64_t>(1, std::min(ANGLE_TARGET_GROUPS, ANGLE_PART_BYTES / (row * (int64_t)sizeof(uint32_t))));
+    int64_t       n_os = std::max<int64_t>(1, std::min(n_ob, target / std::max<int64_t>(1, tiles)));
+    n_os = std::max(n_os, (n_ob + ANGLE_MAX_SLAB - 1) / ANGLE_MAX_SLAB);
+    std::vector<AngleItem> items;
+    for (int g = 0; g < p.G; ++g) {
+        first[g] = (int32_t)items.size();
+        for (int64_t lo = p.start[(size_t)g]; lo < p.start[(size_t)g + 1]; lo += ANGLE_ITEM_CENTRES)
+            for (int64_t slab = 0; slab < n_os; ++slab)
+                items.push_back(AngleItem{(int)lo, (int)std::min<int64_t>(ANGLE_ITEM_CENTRES, p.start[(size_t)g + 1] - lo), g, (int)slab, (int)n_os});
+    }
+    first[p.G] = (int32_t)items.size();
+    return items;
+}
+
+int angle_run(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start, int32_t n_groups,
+              const double* r_cut, int64_t origin_step, int32_t n_theta, uint64_t* angles, size_t angles_bytes, uint64_t* coord,
+              size_t coord_bytes, uint64_t* truncated) {
+    PSA_REQUIRE(angles != nullptr && coord != nullptr && truncated != nullptr, "null output");
+    MsdCall      p;
+    AngleSpecies sp;
+    PSA_TRY(angle_check(c, "psa_angle_histogram", box, box_inverse, idx, group_start, n_groups, r_cut, &p, &sp));
+    PSA_REQUIRE(origin_step >= 1, "origin_step must be at least 1, got %lld", (long long)origin_step);
+    PSA_REQUIRE(n_theta >= 1 && n_theta <= ANGLE_MAX_BINS, "the number of bins is in [1, %d], got %d", ANGLE_MAX_BINS, (int)n_theta);
+    const int    S = p.G, P = S * (S + 1) / 2, n1 = n_theta + 1, NC = ANGLE_MAX_NEIGHBOURS + 1;
+    const size_t want_a = (size_t)S * (size_t)P * (size_t)n1 * sizeof(uint64_t), want_c = (size_t)S * (size_t)S * (size_t)NC * sizeof(uint64_t);
+    PSA_REQUIRE(angles_bytes == want_a, "angles_bytes is %zu, the (%d,%d,%d) uint64 result has %zu", angles_bytes, S, P, n1, want_a);
+    PSA_REQUIRE(coord_bytes == want_c, "coord_bytes is %zu, the (%d,%d,%d) uint64 result has %zu", coord_bytes, S, S, NC, want_c);
+    std::memset(angles, 0, want_a);
+    std::memset(coord, 0, want_c);
+    std::memset(truncated, 0, (size_t)S * sizeof(uint64_t));
+    if (p.n_a == 0) return PSA_OK;                           // every species empty: zeros
+    const int64_t n_o = (p.T - 1) / origin_step + 1, B = std::min<int64_t>({n_o, p.Ab, 65535}), row = angle_row_words(S, n_theta);
+    std::vector<float> edges((size_t)n1);
+    for (int i = 0; i < n1; ++i) edges[(size_t)i] = (float)std::cos((double)i * M_PI / (double)n_theta);
+    edges[0] = 1.f, edges[(size_t)n_theta] = -1.f;
+    int32_t                      first[PAIR_MAX_SPECIES + 1];
+    const std::vector<AngleItem> items = angle_items(p, B, row, first);
+    AngleWork                    w;
+    PSA_TRY(angle_upload_list(c, p, idx));
+    {
+        StageTimer st(c, PSA_T_H2D);
+        PSA_TRY(upload(c, c->d_angle_edges, edges.data(), edges.size() * sizeof(float)));
+        PSA_TRY(upload(c, c->d_angle_items, items.data(), items.size() * sizeof(AngleItem)));
+    }
+    PSA_TRY(c->d_angle_part.reserve(items.size() * (size_t)row * sizeof(uint32_t)));
+    PSA_TRY(c->d_angle_acc.reserve((size_t)S * (size_t)row * sizeof(uint64_t)));
+    PSA_HIP_CHECK(hipMemsetAsync(c->d_angle_acc.ptr, 0, (size_t)S * (size_t)row * sizeof(uint64_t), c->stream));
+    PSA_TRY(angle_work(c, p.n_a, B, &w));
+    const float* d_pos = c->slot[PSA_SLOT_POSITIONS].buf.as<float>();
+    const int*   d_idx = p.listed ? c->d_angle_idx.as<int>() : nullptr;
+    for (int64_t k0 = 0; k0 < n_o; k0 += B) {
+        const int64_t nb = std::min(B, n_o - k0);
+        {
+            StageTimer st(c, PSA_T_GATHER);
+            PSA_TRY(launch_pair_frac(c, d_pos, d_idx, p.n_a, box_inverse, w.c, k0 * origin_step, origin_step, nb, p.T, p.N));
+        }
+        {
+            StageTimer st(c, PSA_T_TRANSPOSE);
+            PSA_TRY(launch_angle_neighbours(c, w.c, w.count, w.list, sp, box, p.n_a, nb));
+        }
+        {
+            StageTimer st(c, PSA_T_PHASE);
+            PSA_TRY(launch_angle_hist(c, w.count, w.list, c->d_angle_items.ptr, (int64_t)items.size(), c->d_angle_edges.as<float>(),
+                                      c->d_angle_part.as<unsigned>(), S, p.n_a, nb, n_theta));
+        }
+        StageTimer st(c, PSA_T_EPILOGUE);
+        PSA_TRY(launch_angle_reduce(c, c->d_angle_part.as<unsigned>(), first, c->d_angle_acc.as<unsigned long long>(), S, n_theta));
+    }
+    std::vector<uint64_t> acc((size_t)S * (size_t)row);
+    {
+        StageTimer st(c, PSA_T_D2H);
+        PSA_HIP_CHECK(hipMemcpyAsync(acc.data(), c->d_angle_acc.ptr, acc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
+    for (int a = 0; a < S; ++a) {
+        const uint64_t* r = acc.data() + (size_t)a * (size_t)row;
+        std::memcpy(angles + (size_t)a * (size_t)P * (size_t)n1, r, (size_t)P * (size_t)n1 * sizeof(uint64_t));
+        std::memcpy(coord + (size_t)a * (size_t)S * (size_t)NC, r + (size_t)P * (size_t)n1, (size_t)S * (size_t)NC * sizeof(uint64_t));
+        truncated[a] = r[(size_t)row - 1];
+    }
+    return PSA_OK;
+}
+
+// the fraction pass and the neighbour pass of one frame: the true counts and the first 64 list positions of every centre
+int debug_lists_run(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start,
+                    int32_t n_groups, const double* r_cut, int64_t frame, int32_t* count, int32_t* list) {
+    PSA_REQUIRE(count != nullptr && list != nullptr, "null output");
+    MsdCall      p;
+    AngleSpecies sp;
+    PSA_TRY(angle_check(c, "psa_debug_neighbour_lists", box, box_inverse, idx, group_start, n_groups, r_cut, &p, &sp));
+    PSA_REQUIRE(frame >= 0 && frame <= p.T - 1, "frame %lld is outside [0, T - 1 = %lld]", (long long)frame, (long long)(p.T - 1));
+    if (p.n_a == 0) return PSA_OK;
+    PSA_TRY(angle_upload_list(c, p, idx));
+    AngleWork w;
+    PSA_TRY(angle_work(c, p.n_a, 1, &w));
+    PSA_TRY(launch_pair_frac(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), p.listed ? c->d_angle_idx.as<int>() : nullptr, p.n_a,
+                             box_inverse, w.c, frame, 0, 1, p.T, p.N));
+    PSA_TRY(launch_angle_neighbours(c, w.c, w.count, w.list, sp, box, p.n_a, 1));
+    std::vector<float> h((size_t)p.n_a * ANGLE_MAX_NEIGHBOURS * 4);
+    PSA_HIP_CHECK(hipMemcpyAsync(count, w.count, (size_t)p.n_a * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipMemcpyAsync(h.data(), w.list, h.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (int64_t a = 0; a < p.n_a; ++a)
+        for (int s = 0; s < ANGLE_MAX_NEIGHBOURS; ++s) {
+            int32_t tag;
+            std::memcpy(&tag, &h[((size_t)a * ANGLE_MAX_NEIGHBOURS + (size_t)s) * 4 + 3], sizeof tag);
+            list[(size_t)a * ANGLE_MAX_NEIGHBOURS + (size_t)s] = s < count[a] ? (tag & ((1 << ANGLE_SPECIES_SHIFT) - 1)) : -1;
+        }
+    return PSA_OK;
+}
+
+}  // namespace
+
+}  // namespace psa
+
+using namespace psa;
+
+extern "C" {
+
+int psa_angle_histogram(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start,
+                        int32_t n_groups, const double* r_cut, int64_t origin_step, int32_t n_theta, uint64_t* angles, size_t angles_bytes,
+                        uint64_t* coord, size_t coord_bytes, uint64_t* truncated) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    return synchronised(c, angle_run(c, box, box_inverse, idx, group_start, n_groups, r_cut, origin_step, n_theta, angles, angles_bytes, coord,
+                                     coord_bytes, truncated), "psa_angle_histogram");
+}
+
+int psa_debug_neighbour_lists(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start,
+                              int32_t n_groups, const double* r_cut, int64_t frame, int32_t* count, int32_t* list) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    return synchronised(c, debug_lists_run(c, box, box_inverse, idx, group_start, n_groups, r_cut, frame, count, list),
+                        "psa_debug_neighbour_lists");
+}
+
+}  // extern "C"

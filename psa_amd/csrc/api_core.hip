@@ -285,7 +285,8 @@ int psa_destroy(psa_ctx* c) {
                           &c->d_par_idx, &c->d_par_bins, &c->d_par_scale, &c->d_par_acc, &c->d_par_out, &c->d_corr_tab, &c->d_corr_factor,
                           &c->d_corr_scale, &c->d_corr_in, &c->d_corr_out, &c->d_msd_u, &c->d_msd_img, &c->d_msd_sums, &c->d_msd_offs,
                           &c->d_msd_idx, &c->d_msd_chunks, &c->d_msd_sizes, &c->d_msd_lags, &c->d_msd_part, &c->d_msd_acc, &c->d_msd_out,
-                          &c->d_pair_c, &c->d_pair_idx, &c->d_pair_items, &c->d_pair_part, &c->d_pair_acc})
+                          &c->d_pair_c, &c->d_pair_idx, &c->d_pair_items, &c->d_pair_part, &c->d_pair_acc,
+                          &c->d_angle_work, &c->d_angle_idx, &c->d_angle_items, &c->d_angle_edges, &c->d_angle_part, &c->d_angle_acc})
             b->release();
         (void)hipStreamDestroy(c->stream);
     }

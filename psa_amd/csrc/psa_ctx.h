@@ -341,6 +341,12 @@ struct psa_ctx {
     // blocks and lags.  All kept between calls.
     psa::DevBuf  d_pair_c, d_pair_idx, d_pair_items, d_pair_part, d_pair_acc;
 
+    // bond angles and coordination (psa_angle_histogram, psa_debug_neighbour_lists; api_angle.hip): per origin of a block
+    // the centred fractional coordinates (3, n_a) float32, the neighbour counts (n_a) int32 and the neighbour lists
+    // (n_a, 64, 4) float32 -- 1040 n_a bytes, held to opt_dynamic_work_bytes; outside it the atom list, the item table,
+    // the bin edges, the items' partial histograms and the accumulator that lives across blocks.  All kept between calls.
+    psa::DevBuf  d_angle_work, d_angle_idx, d_angle_items, d_angle_edges, d_angle_part, d_angle_acc;
+
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
                                           // plane builds, trajectory uploads (psa_oneoff_stats)
@@ -628,6 +634,40 @@ int launch_pair_hist(psa_ctx* c, const float* d_cA, const float* d_cB, const voi
                      const double* box, int64_t n_a, int64_t n_ob, float inv_dr, int32_t n_r);
 int launch_pair_hist_reduce(psa_ctx* c, const unsigned* d_part, const int32_t* pair_first, unsigned long long* d_acc, int32_t S,
                             int32_t n_r, bool sym);
+// --- angle.hip (psa_angle_histogram, psa_debug_neighbour_lists: the neighbour shell of every atom, the angles between
+// pairs of neighbours and the coordination numbers; the arithmetic and the tiling are in its header)
+constexpr int ANGLE_MAX_NEIGHBOURS = 64;   // most neighbours a centre holds, all species together
+constexpr int ANGLE_MAX_BINS = 1024;       // most bins of an angle histogram (the counter of undefined angles follows them)
+constexpr int ANGLE_HIST_WORDS = 12288;    // 32-bit counters of a workgroup's angle histograms in LDS
+constexpr int ANGLE_CENTRES = 256;         // centres of a workgroup's tile in the neighbour pass; lanes of a workgroup in both
+constexpr int ANGLE_SPECIES_SHIFT = 28;    // a list entry's tag: list position | species << 28
+// the species of a call as the kernels take them: offsets into the atom list, the centre tiles' first index per species,
+// float32(1 / r_cut) per ordered species pair (0: no bond)
+struct AngleSpecies {
+    int   S, start[PAIR_MAX_SPECIES + 1], tile_first[PAIR_MAX_SPECIES + 1];
+    float inv_rc[PAIR_MAX_SPECIES * PAIR_MAX_SPECIES];
+};
+// One workgroup's work in the angle pass: centres [a_lo, a_lo + a_n) of species `species` (a wavefront takes every
+// fourth), the origins slab, slab + n_os, ...
+struct AngleItem {
+    int a_lo, a_n, species, slab, n_os;
+};
+// columns of a partial row and of a species' accumulator row: P (n_theta + 1) angle counters, S 65 coordination counters,
+// the truncated centres
+inline int64_t angle_row_words(int S, int n_theta) {
+    return (int64_t)(S * (S + 1) / 2) * (n_theta + 1) + (int64_t)S * (ANGLE_MAX_NEIGHBOURS + 1) + 1;
+}
+// d_c (n_ob, 3, n_a) -> d_count (n_ob, n_a) int32, the true number of neighbours, and d_list (n_ob, n_a, 64) float4
+// {d_x, d_y, d_z, tag}, the first 64 of them in the order of the atom list
+int launch_angle_neighbours(psa_ctx* c, const float* d_c, int* d_count, void* d_list, const AngleSpecies& sp, const double* box,
+                            int64_t n_a, int64_t n_ob);
+// d_items: n_items AngleItem listed species by species; d_part (n_items, angle_row_words) uint32 -- an item's samples stay
+// below 2^32 (the caller's rule); d_edges (n_theta + 1) float32.  The reduce adds to acc (S, angle_row_words) uint64;
+// item_first (S + 1, host): where each species' items begin
+int launch_angle_hist(psa_ctx* c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items, const float* d_edges,
+                      unsigned* d_part, int32_t S, int64_t n_a, int64_t n_ob, int32_t n_theta);
+int launch_angle_reduce(psa_ctx* c, const unsigned* d_part, const int32_t* item_first, unsigned long long* d_acc, int32_t S,
+                        int32_t n_theta);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 

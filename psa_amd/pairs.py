@@ -19,8 +19,8 @@ overflow = samples = n_o N_a (N_b - delta_ab), and at tau = 0 counts[a,b] = coun
     tilt.  `max_pair_radius(box)` = (1/2 - 2^-12) min_j w_j is the largest r_max served; `r_max=None` means that value.
   * g = counts / (n_o N_a rho_b shell volume), rho_b = N_b / V, tends to 1 - delta_ab / N_b for an ideal gas;
     coordination = cumsum(counts) / (n_o N_a) is N_ab(r), the mean number of b-atoms within r of an a-atom.
-  * Not here: cell lists for r_max much smaller than the box, S(Q) by transforming g(r), bond-angle distributions,
-    per-frame box changes, sharding.
+  * Not here: cell lists for r_max much smaller than the box, S(Q) by transforming g(r), per-frame box changes,
+    sharding (bond angles and coordination: psa_amd/angles.py).
 
 This module is host code only: the served radius and the result types.  `SEDCalculator.calculate_rdf` and
 `SEDCalculator.calculate_distinct_van_hove` run the kernels (psa_amd/csrc/pair.hip).
