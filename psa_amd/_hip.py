@@ -86,6 +86,8 @@ TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpo
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
+_f64p = C.POINTER(C.c_double)
+_u64p = C.POINTER(C.c_uint64)
 _ctx = C.c_void_p
 
 # name -> (restype, argtypes); must list every symbol include/psa_hip.h declares
@@ -135,60 +137,60 @@ SIGNATURES = {
     "psa_dynamic_spectra": (C.c_int, [_ctx, _f32p, C.c_int64, _i32p, C.c_int64, C.c_int32, _f32p, C.c_size_t]),
     "psa_debug_dynamic_project": (C.c_int, [_ctx, _f32p, C.c_int64, _i32p, C.c_int64, C.c_int32, C.c_void_p]),
     "psa_debug_dynamic_sincos": (C.c_int, [_ctx, _f32p, C.c_int64, _f32p]),
-    "psa_lattice_spectra": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64, C.c_int32,
+    "psa_lattice_spectra": (C.c_int, [_ctx, _f64p, _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64, C.c_int32,
                                       _f32p, C.c_size_t]),
-    "psa_debug_lattice_project": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, C.c_int32, C.c_void_p]),
-    "psa_self_spectra": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64, _f32p,
+    "psa_debug_lattice_project": (C.c_int, [_ctx, _f64p, _i32p, C.c_int64, _i32p, C.c_int64, C.c_int32, C.c_void_p]),
+    "psa_self_spectra": (C.c_int, [_ctx, _f64p, _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64, _f32p,
                                    C.c_size_t]),
-    "psa_debug_self_series": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, C.c_void_p]),
+    "psa_debug_self_series": (C.c_int, [_ctx, _f64p, _i32p, C.c_int64, _i32p, C.c_int64, C.c_void_p]),
     "psa_debug_dynamic_power": (C.c_int, [_ctx, C.c_void_p, _f32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.c_float, _f32p]),
     "psa_debug_lattice_shell": (C.c_int, [_ctx, C.c_void_p, _f32p, _i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
                                           C.c_int64, C.c_int64, C.c_double, _f32p]),
     "psa_debug_self_power": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i32p, C.c_int64, C.c_int64,
-                                       C.POINTER(C.c_double), C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _f32p]),
-    "psa_partial_spectra": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, _i32p, _i64p, C.c_int32,
+                                       _f64p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _f32p]),
+    "psa_partial_spectra": (C.c_int, [_ctx, _f64p, _i32p, C.c_int64, _i32p, C.c_int64, _i32p, _i64p, C.c_int32,
                                       C.c_int32, _f32p, C.c_size_t]),
-    "psa_debug_partial_project": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, _i64p, C.c_int32, C.c_int32,
+    "psa_debug_partial_project": (C.c_int, [_ctx, _f64p, _i32p, C.c_int64, _i32p, _i64p, C.c_int32, C.c_int32,
                                             C.c_void_p]),
     "psa_debug_partial_power": (C.c_int, [_ctx, C.c_void_p, _f32p, _i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
                                           C.c_int64, C.c_int64, C.c_int64, C.c_double, _f32p]),
-    "psa_lattice_correlations": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64,
+    "psa_lattice_correlations": (C.c_int, [_ctx, _f64p, _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64,
                                            C.c_int32, C.c_int64, _f32p, C.c_size_t]),
-    "psa_self_correlations": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64,
+    "psa_self_correlations": (C.c_int, [_ctx, _f64p, _i32p, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int64,
                                         C.c_int64, _f32p, C.c_size_t]),
-    "psa_debug_correlation_transform": (C.c_int, [_ctx, C.POINTER(C.c_double), C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+    "psa_debug_correlation_transform": (C.c_int, [_ctx, _f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                                   C.c_int64, C.c_int64, C.c_int32, _f32p]),
-    "psa_displacement_moments": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i64p, C.c_int32, C.c_int64,
-                                           C.c_int64, C.c_int32, C.POINTER(C.c_double), C.c_size_t]),
-    "psa_van_hove_self": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i64p, C.c_int32, _i64p, C.c_int64,
-                                    C.c_int64, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_uint64), C.c_size_t]),
-    "psa_debug_unwrap": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, C.c_int64, C.c_int32,
-                                   C.POINTER(C.c_double), _i32p]),
-    "psa_pair_histogram": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i64p, C.c_int32, _i64p, C.c_int64,
-                                     C.c_int64, C.c_double, C.c_int32, C.POINTER(C.c_uint64), C.c_size_t]),
-    "psa_debug_pair_fractions": (C.c_int, [_ctx, C.POINTER(C.c_double), _i32p, C.c_int64, _f32p]),
+    "psa_displacement_moments": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, C.c_int64,
+                                           C.c_int64, C.c_int32, _f64p, C.c_size_t]),
+    "psa_van_hove_self": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _i64p, C.c_int64,
+                                    C.c_int64, C.c_int32, C.c_double, C.c_int32, _u64p, C.c_size_t]),
+    "psa_debug_unwrap": (C.c_int, [_ctx, _f64p, _f64p, _i32p, C.c_int64, C.c_int32,
+                                   _f64p, _i32p]),
+    "psa_pair_histogram": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _i64p, C.c_int64,
+                                     C.c_int64, C.c_double, C.c_int32, _u64p, C.c_size_t]),
+    "psa_debug_pair_fractions": (C.c_int, [_ctx, _f64p, _i32p, C.c_int64, _f32p]),
     "psa_debug_pair_plan": (C.c_int, [_i64p, C.c_int32, C.c_int32, C.c_int64, _i64p]),
-    "psa_angle_histogram": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i64p, C.c_int32, C.POINTER(C.c_double),
-                                      C.c_int64, C.c_int32, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t,
-                                      C.POINTER(C.c_uint64)]),
-    "psa_debug_neighbour_lists": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i64p, C.c_int32,
-                                            C.POINTER(C.c_double), C.c_int64, _i32p, _i32p]),
+    "psa_angle_histogram": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p,
+                                      C.c_int64, C.c_int32, _u64p, C.c_size_t, _u64p, C.c_size_t,
+                                      _u64p]),
+    "psa_debug_neighbour_lists": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32,
+                                            _f64p, C.c_int64, _i32p, _i32p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
-    "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, C.POINTER(C.c_double),
-                                   C.POINTER(C.c_double), _f32p, _f32p, _f32p]),
+    "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, _f64p,
+                                   _f64p, _f32p, _f32p, _f32p]),
     "psa_sed_set_kmap": (C.c_int, [_ctx, _i32p, C.c_int64]),
     "psa_sed_single_bin": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, _i32p, C.c_int64, C.c_int32, C.c_int64, _f32p]),
     "psa_slab_read": (C.c_int, [_ctx, C.c_int64, C.c_int64, C.c_void_p]),
     "psa_slab_write": (C.c_int, [_ctx, C.c_int64, C.c_int64, C.c_void_p]),
     "psa_result_intensity": (C.c_int, [_ctx, _f32p, C.c_size_t]),
     "psa_result_chiral_phase": (C.c_int, [_ctx, C.c_int, C.c_int, _f32p, C.c_size_t]),
-    "psa_last_timings": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
-    "psa_k1_stats": (C.c_int, [_ctx, _i64p, C.POINTER(C.c_double)]),
+    "psa_last_timings": (C.c_int, [_ctx, _f64p]),
+    "psa_k1_stats": (C.c_int, [_ctx, _i64p, _f64p]),
     "psa_k1_lowrank_launches": (C.c_int, [_ctx, _i64p]),
     "psa_k1_lowrank_pair_launches": (C.c_int, [_ctx, _i64p]),
     "psa_lowrank_pair_image": (C.c_int, [C.c_int32, _i64p, _i64p]),
-    "psa_oneoff_stats": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
+    "psa_oneoff_stats": (C.c_int, [_ctx, _f64p]),
     "psa_debug_phase_table": (C.c_int, [_ctx, _f32p, _f32p, C.c_int64, _i32p, C.c_int64,
                                         C.c_int64, C.c_void_p]),
     "psa_debug_project_only": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p,
@@ -304,9 +306,8 @@ def lowrank_plan(k_vectors, mean_pos_all, idx=None):
     ok, geo = C.c_int32(0), np.zeros(12, np.float64)
     kappa, cm = np.zeros(64, np.float64), np.zeros((K, 64), np.complex64)
     lw, phi = np.zeros((K, 64), np.float32), np.zeros(K, np.complex64)
-    dp = C.POINTER(C.c_double)
     _check(load_library().psa_lowrank_plan(_f32(kv), K, _f32(mean), N, None if ix is None else ix.ctypes.data_as(_i32p), n_g,
-                                           C.byref(ok), geo.ctypes.data_as(dp), kappa.ctypes.data_as(dp),
+                                           C.byref(ok), geo.ctypes.data_as(_f64p), kappa.ctypes.data_as(_f64p),
                                            cm.ctypes.data_as(_f32p), _f32(lw), phi.ctypes.data_as(_f32p)), "psa_lowrank_plan")
     if not ok.value:
         return None
@@ -798,7 +799,7 @@ class Engine:
         if bins is not None and bins.size != K:
             raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
         out = np.empty((3 if currents else 1, L, K if bins is None else int(n_bins)), np.float32)
-        _check(self._lib.psa_lattice_spectra(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p), K,
+        _check(self._lib.psa_lattice_spectra(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
                                              None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g,
                                              1 if currents else 0, _f32(out), out.nbytes), "psa_lattice_spectra")
         return out
@@ -809,7 +810,7 @@ class Engine:
         T, _ = self.shape(SLOT_POSITIONS)
         inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
         out = np.empty((n.shape[0], 4 if currents else 1, T), np.complex64)
-        _check(self._lib.psa_debug_lattice_project(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p),
+        _check(self._lib.psa_debug_lattice_project(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p),
                                                    n.shape[0], ip, n_g, 1 if currents else 0, out.ctypes.data_as(C.c_void_p)),
                "psa_debug_lattice_project")
         return out
@@ -827,7 +828,7 @@ class Engine:
         if bins is not None and bins.size != K:
             raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
         out = np.empty((L, K if bins is None else int(n_bins)), np.float32)
-        _check(self._lib.psa_self_spectra(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p), K,
+        _check(self._lib.psa_self_spectra(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
                                           None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g, _f32(out),
                                           out.nbytes), "psa_self_spectra")
         return out
@@ -838,7 +839,7 @@ class Engine:
         T, N = self.shape(SLOT_POSITIONS)
         inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
         out = np.empty((N if idx is None else n_g, n.shape[0], T), np.complex64)
-        _check(self._lib.psa_debug_self_series(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p),
+        _check(self._lib.psa_debug_self_series(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p),
                                                n.shape[0], ip, n_g, out.ctypes.data_as(C.c_void_p)), "psa_debug_self_series")
         return out
 
@@ -899,7 +900,7 @@ class Engine:
         if bins is not None and bins.size != K:
             raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
         out = np.empty((3 if currents else 1, S * (S + 1) // 2, L, K if bins is None else int(n_bins)), np.float32)
-        _check(self._lib.psa_partial_spectra(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p), K,
+        _check(self._lib.psa_partial_spectra(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
                                              None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins),
                                              idx.ctypes.data_as(_i32p), off.ctypes.data_as(_i64p), S, 1 if currents else 0,
                                              _f32(out), out.nbytes), "psa_partial_spectra")
@@ -912,7 +913,7 @@ class Engine:
         inv, n, _, _, _ = self._lattice_args(box_inverse, indices, None)
         idx, off, S = self._species_args(species)
         out = np.empty((n.shape[0], S, 4 if currents else 1, T), np.complex64)
-        _check(self._lib.psa_debug_partial_project(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p),
+        _check(self._lib.psa_debug_partial_project(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p),
                                                    n.shape[0], idx.ctypes.data_as(_i32p), off.ctypes.data_as(_i64p), S,
                                                    1 if currents else 0, out.ctypes.data_as(C.c_void_p)),
                "psa_debug_partial_project")
@@ -952,7 +953,7 @@ class Engine:
         na, nv, ns, L = Z.shape
         out = np.empty((L, int(cols)), np.float32)
         _check(self._lib.psa_debug_self_power(self._h, Z.ctypes.data_as(C.c_void_p), na, nv, ns, L, g.ctypes.data_as(_i32p),
-                                              g.shape[0] - 1, int(cols), sc.ctypes.data_as(C.POINTER(C.c_double)), 1 if mirror else 0,
+                                              g.shape[0] - 1, int(cols), sc.ctypes.data_as(_f64p), 1 if mirror else 0,
                                               int(n_chunks), int(atom_block), int(vec_block), int(seg_block), _f32(out)),
                "psa_debug_self_power")
         return out
@@ -969,7 +970,7 @@ class Engine:
         if bins is not None and bins.size != K:
             raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
         out = np.empty((3 if currents else 1, max(int(n_lags), 0), K if bins is None else int(n_bins)), np.float32)
-        _check(self._lib.psa_lattice_correlations(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p), K,
+        _check(self._lib.psa_lattice_correlations(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
                                                   None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g,
                                                   1 if currents else 0, int(n_lags), _f32(out), out.nbytes),
                "psa_lattice_correlations")
@@ -985,7 +986,7 @@ class Engine:
         if bins is not None and bins.size != K:
             raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
         out = np.empty((max(int(n_lags), 0), K if bins is None else int(n_bins)), np.float32)
-        _check(self._lib.psa_self_correlations(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), n.ctypes.data_as(_i32p), K,
+        _check(self._lib.psa_self_correlations(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
                                                None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g,
                                                int(n_lags), _f32(out), out.nbytes), "psa_self_correlations")
         return out
@@ -1022,9 +1023,8 @@ class Engine:
         `unwrap=False` takes the positions as unwrapped.  Only positions are read."""
         H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
         out = np.empty((max(int(n_lags), 0), G, 4), np.float64)
-        dp = C.POINTER(C.c_double)
-        _check(self._lib.psa_displacement_moments(self._h, H.ctypes.data_as(dp), inv.ctypes.data_as(dp), ip, sp, G, int(n_lags),
-                                                  int(origin_step), 1 if unwrap else 0, out.ctypes.data_as(dp), out.nbytes),
+        _check(self._lib.psa_displacement_moments(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G, int(n_lags),
+                                                  int(origin_step), 1 if unwrap else 0, out.ctypes.data_as(_f64p), out.nbytes),
                "psa_displacement_moments")
         return out
 
@@ -1037,10 +1037,9 @@ class Engine:
         tau = np.ascontiguousarray(lags, np.int64).ravel()
         held = tau if tau.size else np.zeros(1, np.int64)
         out = np.empty((tau.size, G, max(int(n_r), 0) + 1), np.uint64)
-        dp = C.POINTER(C.c_double)
-        _check(self._lib.psa_van_hove_self(self._h, H.ctypes.data_as(dp), inv.ctypes.data_as(dp), ip, sp, G,
+        _check(self._lib.psa_van_hove_self(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G,
                                            held.ctypes.data_as(_i64p), tau.size, int(origin_step), 1 if unwrap else 0, float(dr),
-                                           int(n_r), out.ctypes.data_as(C.POINTER(C.c_uint64)), out.nbytes), "psa_van_hove_self")
+                                           int(n_r), out.ctypes.data_as(_u64p), out.nbytes), "psa_van_hove_self")
         return out
 
     def debug_unwrap(self, box, idx=None, unwrap: bool = True, images: bool = True, box_inverse=None):
@@ -1050,9 +1049,8 @@ class Engine:
         n_g = N if idx is None else int(np.asarray(idx).size)
         u = np.empty((T, n_g, 3), np.float64)
         img = np.empty((T, n_g, 3), np.int32) if images else None
-        dp = C.POINTER(C.c_double)
-        _check(self._lib.psa_debug_unwrap(self._h, H.ctypes.data_as(dp), inv.ctypes.data_as(dp), ip, n_g, 1 if unwrap else 0,
-                                          u.ctypes.data_as(dp), None if img is None else img.ctypes.data_as(_i32p)),
+        _check(self._lib.psa_debug_unwrap(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, n_g, 1 if unwrap else 0,
+                                          u.ctypes.data_as(_f64p), None if img is None else img.ctypes.data_as(_i32p)),
                "psa_debug_unwrap")
         return u, img
 
@@ -1067,10 +1065,9 @@ class Engine:
         tau = np.ascontiguousarray(lags, np.int64).ravel()
         held = tau if tau.size else np.zeros(1, np.int64)
         out = np.empty((tau.size, G, G, max(int(n_r), 0) + 1), np.uint64)
-        dp = C.POINTER(C.c_double)
-        _check(self._lib.psa_pair_histogram(self._h, H.ctypes.data_as(dp), inv.ctypes.data_as(dp), ip, sp, G,
+        _check(self._lib.psa_pair_histogram(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G,
                                             held.ctypes.data_as(_i64p), tau.size, int(origin_step), float(dr), int(n_r),
-                                            out.ctypes.data_as(C.POINTER(C.c_uint64)), out.nbytes), "psa_pair_histogram")
+                                            out.ctypes.data_as(_u64p), out.nbytes), "psa_pair_histogram")
         return out
 
     def debug_pair_fractions(self, box, idx=None, box_inverse=None) -> np.ndarray:
@@ -1080,7 +1077,7 @@ class Engine:
         H, inv, keep, ip, _, _, _ = self._displacement_args(box, box_inverse, None if idx is None else [idx])
         n_g = N if idx is None else int(np.asarray(idx).size)
         out = np.empty((T, n_g, 3), np.float32)
-        _check(self._lib.psa_debug_pair_fractions(self._h, inv.ctypes.data_as(C.POINTER(C.c_double)), ip, n_g, _f32(out)),
+        _check(self._lib.psa_debug_pair_fractions(self._h, inv.ctypes.data_as(_f64p), ip, n_g, _f32(out)),
                "psa_debug_pair_fractions")
         return out
 
@@ -1118,10 +1115,10 @@ class Engine:
         angles = np.empty((G, P, n1), np.uint64)
         coord = np.empty((G, G, ANGLE_MAX_NEIGHBOURS + 1), np.uint64)
         trunc = np.empty(G, np.uint64)
-        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
-        _check(self._lib.psa_angle_histogram(self._h, H.ctypes.data_as(dp), inv.ctypes.data_as(dp), ip, sp, G, rc.ctypes.data_as(dp),
-                                             int(origin_step), int(n_theta), angles.ctypes.data_as(up), angles.nbytes,
-                                             coord.ctypes.data_as(up), coord.nbytes, trunc.ctypes.data_as(up)), "psa_angle_histogram")
+        _check(self._lib.psa_angle_histogram(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G,
+                                             rc.ctypes.data_as(_f64p), int(origin_step), int(n_theta), angles.ctypes.data_as(_u64p),
+                                             angles.nbytes, coord.ctypes.data_as(_u64p), coord.nbytes, trunc.ctypes.data_as(_u64p)),
+               "psa_angle_histogram")
         return angles, coord, trunc
 
     def debug_neighbour_lists(self, box, r_cut, frame: int, groups=None, box_inverse=None):
@@ -1134,9 +1131,8 @@ class Engine:
         n_a = N if groups is None else int(start[-1])
         count = np.zeros(max(n_a, 1), np.int32)
         lst = np.full((max(n_a, 1), ANGLE_MAX_NEIGHBOURS), -1, np.int32)
-        dp = C.POINTER(C.c_double)
-        _check(self._lib.psa_debug_neighbour_lists(self._h, H.ctypes.data_as(dp), inv.ctypes.data_as(dp), ip, sp, G,
-                                                   rc.ctypes.data_as(dp), int(frame), count.ctypes.data_as(_i32p),
+        _check(self._lib.psa_debug_neighbour_lists(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G,
+                                                   rc.ctypes.data_as(_f64p), int(frame), count.ctypes.data_as(_i32p),
                                                    lst.ctypes.data_as(_i32p)), "psa_debug_neighbour_lists")
         return count[:n_a], lst[:n_a]
 
@@ -1149,7 +1145,7 @@ class Engine:
             raise ValueError(f"power {X.shape} does not fit (fields, P, cols)")
         fields, P, cols = X.shape
         out = np.empty((fields, max(int(n_lags), 0), cols), np.float32)
-        _check(self._lib.psa_debug_correlation_transform(self._h, X.ctypes.data_as(C.POINTER(C.c_double)), fields, P, cols, int(L),
+        _check(self._lib.psa_debug_correlation_transform(self._h, X.ctypes.data_as(_f64p), fields, P, cols, int(L),
                                                          int(n_seg), int(n_lags), 1 if as_float32 else 0, _f32(out)),
                "psa_debug_correlation_transform")
         return out

@@ -34,7 +34,8 @@ from .. import _hip
 from ..io.writer import out_to_qdump
 from ..correlations import PowderTimeCorrelations, TimeCorrelations, check_boxcar, check_lags
 from ..covariance import ModeVectors, mode_vectors, spectral_weights
-from ..displacements import MeanSquareDisplacement, VanHoveSelf, alpha2, check_origin_step, origin_counts
+from ..displacements import (MeanSquareDisplacement, VanHoveSelf, alpha2, check_count, check_lag_frames, check_origin_step,
+                             origin_counts, radial_bins)
 from ..dynamic import DynamicSpectra
 from .. import angles
 from ..angles import BondAngleDistribution
@@ -857,26 +858,12 @@ class SEDCalculator:
         Integer counts: sum_i counts + overflow = samples exactly.  Unwrapping, groups, `origin_step`, `max_atoms` and
         the sharded refusal are those of `calculate_msd`.  Returns a `psa_amd.VanHoveSelf` with `radial_density`
         (4 pi r^2 G_s) and `g_s`."""
-        tau = np.asarray(lag_frames)
-        if tau.ndim == 0:
-            tau = tau.reshape(1)
-        if tau.ndim != 1 or (tau.size and not (np.issubdtype(tau.dtype, np.integer) or np.all(tau == np.rint(tau)))):
-            raise ValueError("lag_frames must be a list of integers")
-        tau = tau.astype(np.int64)
-        if not 1 <= tau.size <= _hip.MSD_MAX_VH_LAGS:
-            raise ValueError(f"between 1 and {_hip.MSD_MAX_VH_LAGS} lags are served, got {tau.size}")
-        if isinstance(n_r, bool) or not isinstance(n_r, (int, np.integer)) or not 1 <= int(n_r) <= _hip.MSD_MAX_BINS:
-            raise ValueError(f"n_r must be an integer in [1, {_hip.MSD_MAX_BINS}], got {n_r!r}")
-        if not (np.isfinite(r_max) and float(r_max) > 0.0):
-            raise ValueError(f"r_max must be positive and finite, got {r_max!r}")
-        n_r, dr = int(n_r), float(r_max) / int(n_r)
         n_t = self.traj.n_frames
-        if n_t and (np.any(tau < 0) or np.any(tau > n_t - 1)):
-            raise ValueError(f"lag_frames must lie in [0, T - 1 = {n_t - 1}]")
+        tau = check_lag_frames(lag_frames, _hip.MSD_MAX_VH_LAGS, n_t)
+        n_r = check_count("n_r", n_r, _hip.MSD_MAX_BINS)
+        dr, edges, centres = radial_bins(r_max, n_r)
         step, groups = self._displacement_groups(basis_atom_indices, basis_atom_types, origin_step, unwrap, max_atoms, seed,
                                                  "the van Hove function")
-        edges = dr * np.arange(n_r + 1, dtype=np.float64)
-        centres = 0.5 * (edges[1:] + edges[:-1])
         times = tau.astype(np.float64) * (self.dt_ps if self.dt_ps is not None else 1.0)
         if groups is None:
             logger.warning("Cannot calculate the van Hove function: 0 frames or 0 atoms.")
@@ -891,31 +878,16 @@ class SEDCalculator:
     def _pair_call(self, tau, r_max, n_r, basis_atom_indices, basis_atom_types, origin_step, max_atoms, seed, what):
         """(tau int64, n_r, dr, edges, centres, origin_step, the species' atom-index arrays or None, the (n_vh, S, S,
         n_r + 1) counts or None) of a pair call after its refusals -- those of `calculate_van_hove` and the served radius"""
-        tau = np.asarray(tau)
-        if tau.ndim == 0:
-            tau = tau.reshape(1)
-        if tau.ndim != 1 or (tau.size and not (np.issubdtype(tau.dtype, np.integer) or np.all(tau == np.rint(tau)))):
-            raise ValueError("lag_frames must be a list of integers")
-        tau = tau.astype(np.int64)
-        if not 1 <= tau.size <= _hip.PAIR_MAX_LAGS:
-            raise ValueError(f"between 1 and {_hip.PAIR_MAX_LAGS} lags are served, got {tau.size}")
-        if isinstance(n_r, bool) or not isinstance(n_r, (int, np.integer)) or not 1 <= int(n_r) <= _hip.PAIR_MAX_BINS:
-            raise ValueError(f"n_r must be an integer in [1, {_hip.PAIR_MAX_BINS}], got {n_r!r}")
+        tau = check_lag_frames(tau, _hip.PAIR_MAX_LAGS, self.traj.n_frames)
+        n_r = check_count("n_r", n_r, _hip.PAIR_MAX_BINS)
         served = max_pair_radius(self.traj.box_matrix)           # ValueError for a box that is not finite or singular
         if r_max is None:
             r_max = served
-        if not (np.isfinite(r_max) and float(r_max) > 0.0):
-            raise ValueError(f"r_max must be positive and finite, got {r_max!r}")
+        dr, edges, centres = radial_bins(r_max, n_r)
         if float(r_max) > served:
             raise ValueError(f"r_max = {float(r_max)!r} is beyond the served radius {served!r} (psa_amd.max_pair_radius): "
                              "(1/2 - 2^-12) of the box's least perpendicular width")
-        n_r, dr = int(n_r), float(r_max) / int(n_r)
-        n_t = self.traj.n_frames
-        if n_t and (np.any(tau < 0) or np.any(tau > n_t - 1)):
-            raise ValueError(f"lag_frames must lie in [0, T - 1 = {n_t - 1}]")
         step, groups = self._displacement_groups(basis_atom_indices, basis_atom_types, origin_step, True, max_atoms, seed, what)
-        edges = dr * np.arange(n_r + 1, dtype=np.float64)
-        centres = 0.5 * (edges[1:] + edges[:-1])
         if groups is None:
             logger.warning(f"Cannot calculate {what}: 0 frames or 0 atoms.")
             return tau, n_r, edges, centres, step, None, None
@@ -997,9 +969,7 @@ class SEDCalculator:
         (`Engine.angle_histogram` returns the numbers instead).  A sharded calculator refuses (NotImplementedError).
         Returns a `psa_amd.BondAngleDistribution` with `density`, `triplet(centre, b, c)`, `coordination_fraction` and
         `mean_coordination`."""
-        if isinstance(n_theta, bool) or not isinstance(n_theta, (int, np.integer)) or not 1 <= int(n_theta) <= _hip.ANGLE_MAX_BINS:
-            raise ValueError(f"n_theta must be an integer in [1, {_hip.ANGLE_MAX_BINS}], got {n_theta!r}")
-        n_theta = int(n_theta)
+        n_theta = check_count("n_theta", n_theta, _hip.ANGLE_MAX_BINS)
         rc = np.asarray(r_cut, np.float64)
         if rc.ndim not in (0, 2) or not np.all(np.isfinite(rc)) or np.any(rc < 0.0):
             raise ValueError("r_cut must be a scalar or an (S, S) matrix of finite values that are not negative")

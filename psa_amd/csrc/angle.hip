@@ -6,13 +6,11 @@
 //   pair_frac (pair.hip)   positions -> c (origins of a block, 3, n_a) float32, the centred fractional coordinates
 //   angle_neighbours       c -> per (origin, centre) the true neighbour count and the first 64 neighbours {d_x, d_y, d_z, tag}
 //   angle_hist             the lists -> per-workgroup 32-bit histograms in LDS (angles, coordination, truncated) -> partials
-//   angle_reduce           the partials summed in 64-bit integers into the accumulator (S, row), eight strands per column
+//   hist_reduce (hist_reduce.hip)  the partials summed in 64-bit integers into the accumulator (S, row)
 //
-// Arithmetic.  The neighbour test is the displacement chain of pair.hip, operation for operation, with dr = r_cut:
-//     e_j = __fsub_rn(c_j(b), c_j(a));   e_j = e_j - rintf(e_j)
-//     d_c = fma(e_2, h[2][c], fma(e_1, h[1][c], e_0 h[0][c]))                    h = H rounded to float32
-//     r2  = fma(d_z, d_z, fma(d_y, d_y, d_x d_x));   x = __fmul_rn(__fsqrt_rn(r2), inv_rc)     inv_rc = float32(1 / r_cut)
-//     neighbour: x < 1
+// Arithmetic.  The neighbour test is the displacement chain stated in pair.hip's header, through the same functions
+// (min_image.h: min_image, radial_x), with dr = r_cut[alpha,beta]:
+//     neighbour: x = __fmul_rn(__fsqrt_rn(r2), inv_rc) < 1                       inv_rc = float32(1 / r_cut)
 // so with one cut-off the neighbours are bit for bit what pair.hip counts in bin 0 of dr = r_cut, n_r = 1.  The angle at a
 // between the legs b and c, float32, every operation rounded once, from the stored d (r2 is formed again from d: the same
 // bits):
@@ -35,26 +33,19 @@
 // integer adds commute, so the counts are the same bits whatever the blocking and the order of the atoms in a species.
 #include <algorithm>
 
+#include "min_image.h"
 #include "psa_ctx.h"
 
 namespace psa {
 
 namespace {
 
-struct AngleBox32 {
-    float h[9];
-};
-
-// One pair: is b a neighbour of a?  The chain of pair.hip's pair_bin; d is left in dx, dy, dz
-__device__ inline bool angle_leg(float ax, float ay, float az, float bx, float by, float bz, const AngleBox32& B, float inv_rc, float& dx,
+// One pair: is b a neighbour of a?  d is left in dx, dy, dz
+__device__ inline bool angle_leg(float ax, float ay, float az, float bx, float by, float bz, const Box32& B, float inv_rc, float& dx,
                                  float& dy, float& dz) {
-    float e0 = __fsub_rn(bx, ax), e1 = __fsub_rn(by, ay), e2 = __fsub_rn(bz, az);
-    e0 = __fsub_rn(e0, rintf(e0)), e1 = __fsub_rn(e1, rintf(e1)), e2 = __fsub_rn(e2, rintf(e2));
-    dx = __fmaf_rn(e2, B.h[6], __fmaf_rn(e1, B.h[3], __fmul_rn(e0, B.h[0])));
-    dy = __fmaf_rn(e2, B.h[7], __fmaf_rn(e1, B.h[4], __fmul_rn(e0, B.h[1])));
-    dz = __fmaf_rn(e2, B.h[8], __fmaf_rn(e1, B.h[5], __fmul_rn(e0, B.h[2])));
-    const float r2 = __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx)));
-    return __fmul_rn(__fsqrt_rn(r2), inv_rc) < 1.f;                        // (a value that is not a number: no neighbour)
+    const MinImage m = min_image(ax, ay, az, bx, by, bz, B);
+    dx = m.dx, dy = m.dy, dz = m.dz;
+    return radial_x(m.r2, inv_rc) < 1.f;                                   // (a value that is not a number: no neighbour)
 }
 
 // a hit goes to the lane's own list; the count goes on beyond the capacity
@@ -69,7 +60,7 @@ __device__ inline bool angle_leg(float ax, float ay, float az, float bx, float b
 // Grid (centre tiles of all species, origins of the block).  c (n_ob, 3, n_a); count (n_ob, n_a); list (n_ob, n_a, 64)
 __global__ void __launch_bounds__(ANGLE_CENTRES)
 angle_neighbours_kernel(const float* __restrict__ c, int* __restrict__ count, float4* __restrict__ list, const AngleSpecies sp,
-                        const AngleBox32 B, int n_a) {
+                        const Box32 B, int n_a) {
     __shared__ __attribute__((aligned(16))) float sb[3][ANGLE_CENTRES];
     const int lane = threadIdx.x, k = blockIdx.y;
     int       al = 0;
@@ -199,30 +190,6 @@ angle_hist_kernel(const int* __restrict__ count, const float4* __restrict__ list
         for (int i = threadIdx.x; i < n_coord; i += ANGLE_CENTRES) dst[(int64_t)P * n1 + i] = coord[i];
 }
 
-// the items of species alpha are first[alpha] .. first[alpha + 1] - 1 of the table (the host lists them species by species)
-struct AngleFirst {
-    int first[PAIR_MAX_SPECIES + 1];
-};
-
-// Grid (tiles of ANGLE_REDUCE_COLS columns, S).  acc[alpha][row] (uint64) += the partials of the species' items: a lane per
-// column, ANGLE_REDUCE_STRANDS strands of lanes each on every ANGLE_REDUCE_STRANDS-th item, their 64-bit sums added
-// through LDS (integer adds: any order, the same bits)
-constexpr int ANGLE_REDUCE_COLS = 32, ANGLE_REDUCE_STRANDS = 8;
-__global__ void __launch_bounds__(ANGLE_REDUCE_COLS * ANGLE_REDUCE_STRANDS)
-angle_reduce_kernel(const unsigned* __restrict__ part, const AngleFirst of, unsigned long long* __restrict__ acc, int64_t row) {
-    __shared__ unsigned long long strands[ANGLE_REDUCE_STRANDS][ANGLE_REDUCE_COLS];
-    const int     lane = threadIdx.x % ANGLE_REDUCE_COLS, strand = threadIdx.x / ANGLE_REDUCE_COLS, al = blockIdx.y;
-    const int64_t col = (int64_t)blockIdx.x * ANGLE_REDUCE_COLS + lane;
-    unsigned long long sum = 0;
-    if (col < row)
-        for (int64_t r = of.first[al] + strand; r < of.first[al + 1]; r += ANGLE_REDUCE_STRANDS) sum += part[r * row + col];
-    strands[strand][lane] = sum;
-    __syncthreads();
-    if (strand || col >= row) return;
-    for (int w = 1; w < ANGLE_REDUCE_STRANDS; ++w) sum += strands[w][lane];
-    acc[(int64_t)al * row + col] += sum;
-}
-
 }  // namespace
 
 int launch_angle_neighbours(psa_ctx* c, const float* d_c, int* d_count, void* d_list, const AngleSpecies& sp, const double* box,
@@ -231,10 +198,8 @@ int launch_angle_neighbours(psa_ctx* c, const float* d_c, int* d_count, void* d_
     if (tiles == 0 || n_ob == 0) return PSA_OK;
     PSA_REQUIRE(sp.S >= 1 && sp.S <= PAIR_MAX_SPECIES && n_a == sp.start[sp.S] && n_a < (1ll << ANGLE_SPECIES_SHIFT) && n_ob >= 1 &&
                     n_ob <= 65535, "neighbour pass outside its grid");
-    AngleBox32 B;
-    for (int i = 0; i < 9; ++i) B.h[i] = (float)box[i];
     hipLaunchKernelGGL(angle_neighbours_kernel, dim3((unsigned)tiles, (unsigned)n_ob), dim3(ANGLE_CENTRES), 0, c->stream, d_c, d_count,
-                       static_cast<float4*>(d_list), sp, B, (int)n_a);
+                       static_cast<float4*>(d_list), sp, Box32(box), (int)n_a);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;
 }
@@ -248,18 +213,6 @@ int launch_angle_hist(psa_ctx* c, const int* d_count, const void* d_list, const 
     hipLaunchKernelGGL(angle_hist_kernel, dim3((unsigned)n_items, (unsigned)((P + per_chunk - 1) / per_chunk)), dim3(ANGLE_CENTRES),
                        (size_t)per_chunk * (size_t)(n_theta + 1) * sizeof(unsigned), c->stream, d_count, static_cast<const float4*>(d_list), static_cast<const AngleItem*>(d_items), d_edges, d_part,
                        (int)S, (int)n_a, (int)n_ob, (int)n_theta, per_chunk);
-    PSA_HIP_CHECK(hipGetLastError());
-    return PSA_OK;
-}
-
-int launch_angle_reduce(psa_ctx* c, const unsigned* d_part, const int32_t* item_first, unsigned long long* d_acc, int32_t S,
-                        int32_t n_theta) {
-    if (item_first[S] == 0) return PSA_OK;
-    AngleFirst of = {};
-    for (int g = 0; g <= S; ++g) of.first[g] = item_first[g];
-    const int64_t row = angle_row_words(S, n_theta);
-    hipLaunchKernelGGL(angle_reduce_kernel, dim3((unsigned)((row + ANGLE_REDUCE_COLS - 1) / ANGLE_REDUCE_COLS), (unsigned)S),
-                       dim3(ANGLE_REDUCE_COLS * ANGLE_REDUCE_STRANDS), 0, c->stream, d_part, of, d_acc, row);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;
 }

@@ -14,7 +14,6 @@ namespace psa {
 
 namespace {
 
-constexpr int64_t ANGLE_TARGET_GROUPS = 4096;   // workgroups the angle pass aims at, where the work allows
 constexpr int64_t ANGLE_ITEM_CENTRES = 64;      // centres of an item of the angle pass: 16 per wavefront and origin
 constexpr int64_t ANGLE_PART_BYTES = 64 << 20;  // what the items' partials aim to stay below
 // most origins of an item: 64 centres x 8192 origins x 2016 pairs of 64 neighbours stay below 2^32
@@ -23,20 +22,12 @@ static_assert((uint64_t)ANGLE_ITEM_CENTRES * ANGLE_MAX_SLAB * (ANGLE_MAX_NEIGHBO
               "an item's samples fit 32 bits");
 constexpr int64_t ANGLE_ORIGIN_BYTES = 12 + 4 + 16 * ANGLE_MAX_NEIGHBOURS;   // per atom and origin
 
-// the box's least perpendicular width: 1 / |column j of Hinv|
-double angle_min_width(const double* inv) {
-    double w = INFINITY;
-    for (int j = 0; j < 3; ++j) w = std::min(w, 1.0 / std::sqrt(inv[j] * inv[j] + inv[3 + j] * inv[3 + j] + inv[6 + j] * inv[6 + j]));
-    return w;
-}
-
 // the shared checks, the cut-offs and the budget; fills p (Ab: origins of a block) and sp
 int angle_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
-                const int64_t* group_start, int32_t n_groups, const double* r_cut, MsdCall* p, AngleSpecies* sp) {
+                const int64_t* group_start, int32_t n_groups, const double* r_cut, AtomGroups* p, AngleSpecies* sp) {
     PSA_TRY(group_list_check(c, entry, box, box_inverse, idx, group_start, n_groups, p));
     PSA_REQUIRE(r_cut != nullptr, "null r_cut");
     const int    S = p->G;
-    const double served = (0.5 - 0x1p-12) * angle_min_width(box_inverse);
     *sp = AngleSpecies{};
     sp->S = S;
     for (int a = 0; a < S; ++a)
@@ -44,8 +35,9 @@ int angle_check(psa_ctx* c, const char* entry, const double* box, const double* 
             const double r = r_cut[a * S + b];
             PSA_REQUIRE(std::isfinite(r) && r >= 0.0, "r_cut[%d][%d] must be finite and not negative, got %g", a, b, r);
             PSA_REQUIRE(r == r_cut[b * S + a], "r_cut is not symmetric: [%d][%d] = %.17g, [%d][%d] = %.17g", a, b, r, b, a, r_cut[b * S + a]);
-            PSA_REQUIRE(r <= served * (1.0 + 0x1p-40), "r_cut[%d][%d] = %.17g is beyond the served radius %.17g: (1/2 - 2^-12) of the "
-                        "box's least perpendicular width", a, b, r, served);
+            char what[32];
+            std::snprintf(what, sizeof what, "r_cut[%d][%d]", a, b);
+            PSA_TRY(served_radius_check(box_inverse, what, r));
             const float inv = r > 0.0 ? (float)(1.0 / r) : 0.f;
             PSA_REQUIRE(r == 0.0 || (std::isfinite(inv) && inv > 0.f), "r_cut[%d][%d] = %g has no float32 reciprocal", a, b, r);
             sp->inv_rc[a * S + b] = inv;
@@ -60,11 +52,6 @@ int angle_check(psa_ctx* c, const char* entry, const double* box, const double* 
                 (long long)p->n_a, (long long)per_origin);
     p->Ab = W / per_origin;
     return PSA_OK;
-}
-
-int angle_upload_list(psa_ctx* c, const MsdCall& p, const int32_t* idx) {
-    StageTimer st(c, PSA_T_H2D);
-    return p.listed ? upload(c, c->d_angle_idx, idx, (size_t)p.n_a * sizeof(int32_t)) : PSA_OK;
 }
 
 // the work buffer of a block of B origins: the lists first (16-byte entries), then c, then the counts
@@ -85,10 +72,10 @@ int angle_work(psa_ctx* c, int64_t n_a, int64_t B, AngleWork* w) {
 
 // The items of the angle pass over n_ob origins, species by species, ANGLE_ITEM_CENTRES centres each; first (S + 1): where
 // each species' items begin.  The partials (items x row words) stay below ANGLE_PART_BYTES where one slab per tile allows
-std::vector<AngleItem> angle_items(const MsdCall& p, int64_t n_ob, int64_t row, int32_t* first) {
+std::vector<AngleItem> angle_items(const AtomGroups& p, int64_t n_ob, int64_t row, int32_t* first) {
     int64_t tiles = 0;
     for (int g = 0; g < p.G; ++g) tiles += (p.size[(size_t)g] + ANGLE_ITEM_CENTRES - 1) / ANGLE_ITEM_CENTRES;
-    const int64_t target = std::max<int64_t>(1, std::min(ANGLE_TARGET_GROUPS, ANGLE_PART_BYTES / (row * (int64_t)sizeof(uint32_t))));
+    const int64_t target = std::max<int64_t>(1, std::min(REALSPACE_TARGET_GROUPS, ANGLE_PART_BYTES / (row * (int64_t)sizeof(uint32_t))));
     int64_t       n_os = std::max<int64_t>(1, std::min(n_ob, target / std::max<int64_t>(1, tiles)));
     n_os = std::max(n_os, (n_ob + ANGLE_MAX_SLAB - 1) / ANGLE_MAX_SLAB);
     std::vector<AngleItem> items;
@@ -106,7 +93,7 @@ int angle_run(psa_ctx* c, const double* box, const double* box_inverse, const in
               const double* r_cut, int64_t origin_step, int32_t n_theta, uint64_t* angles, size_t angles_bytes, uint64_t* coord,
               size_t coord_bytes, uint64_t* truncated) {
     PSA_REQUIRE(angles != nullptr && coord != nullptr && truncated != nullptr, "null output");
-    MsdCall      p;
+    AtomGroups   p;
     AngleSpecies sp;
     PSA_TRY(angle_check(c, "psa_angle_histogram", box, box_inverse, idx, group_start, n_groups, r_cut, &p, &sp));
     PSA_REQUIRE(origin_step >= 1, "origin_step must be at least 1, got %lld", (long long)origin_step);
@@ -126,23 +113,24 @@ int angle_run(psa_ctx* c, const double* box, const double* box_inverse, const in
     int32_t                      first[PAIR_MAX_SPECIES + 1];
     const std::vector<AngleItem> items = angle_items(p, B, row, first);
     AngleWork                    w;
-    PSA_TRY(angle_upload_list(c, p, idx));
+    HistRows                     rows;
+    PSA_TRY(rows_of_groups(first, S, 1, &rows));
+    PSA_TRY(upload_atom_list(c, &p, idx));
     {
         StageTimer st(c, PSA_T_H2D);
         PSA_TRY(upload(c, c->d_angle_edges, edges.data(), edges.size() * sizeof(float)));
-        PSA_TRY(upload(c, c->d_angle_items, items.data(), items.size() * sizeof(AngleItem)));
+        PSA_TRY(upload(c, c->d_rs_items, items.data(), items.size() * sizeof(AngleItem)));
     }
-    PSA_TRY(c->d_angle_part.reserve(items.size() * (size_t)row * sizeof(uint32_t)));
-    PSA_TRY(c->d_angle_acc.reserve((size_t)S * (size_t)row * sizeof(uint64_t)));
-    PSA_HIP_CHECK(hipMemsetAsync(c->d_angle_acc.ptr, 0, (size_t)S * (size_t)row * sizeof(uint64_t), c->stream));
+    PSA_TRY(c->d_rs_part.reserve(items.size() * (size_t)row * sizeof(uint32_t)));
+    PSA_TRY(c->d_rs_acc.reserve((size_t)S * (size_t)row * sizeof(uint64_t)));
+    PSA_HIP_CHECK(hipMemsetAsync(c->d_rs_acc.ptr, 0, (size_t)S * (size_t)row * sizeof(uint64_t), c->stream));
     PSA_TRY(angle_work(c, p.n_a, B, &w));
     const float* d_pos = c->slot[PSA_SLOT_POSITIONS].buf.as<float>();
-    const int*   d_idx = p.listed ? c->d_angle_idx.as<int>() : nullptr;
     for (int64_t k0 = 0; k0 < n_o; k0 += B) {
         const int64_t nb = std::min(B, n_o - k0);
         {
             StageTimer st(c, PSA_T_GATHER);
-            PSA_TRY(launch_pair_frac(c, d_pos, d_idx, p.n_a, box_inverse, w.c, k0 * origin_step, origin_step, nb, p.T, p.N));
+            PSA_TRY(launch_pair_frac(c, d_pos, p.d_idx, p.n_a, box_inverse, w.c, k0 * origin_step, origin_step, nb, p.T, p.N));
         }
         {
             StageTimer st(c, PSA_T_TRANSPOSE);
@@ -150,16 +138,16 @@ int angle_run(psa_ctx* c, const double* box, const double* box_inverse, const in
         }
         {
             StageTimer st(c, PSA_T_PHASE);
-            PSA_TRY(launch_angle_hist(c, w.count, w.list, c->d_angle_items.ptr, (int64_t)items.size(), c->d_angle_edges.as<float>(),
-                                      c->d_angle_part.as<unsigned>(), S, p.n_a, nb, n_theta));
+            PSA_TRY(launch_angle_hist(c, w.count, w.list, c->d_rs_items.ptr, (int64_t)items.size(), c->d_angle_edges.as<float>(),
+                                      c->d_rs_part.as<unsigned>(), S, p.n_a, nb, n_theta));
         }
         StageTimer st(c, PSA_T_EPILOGUE);
-        PSA_TRY(launch_angle_reduce(c, c->d_angle_part.as<unsigned>(), first, c->d_angle_acc.as<unsigned long long>(), S, n_theta));
+        PSA_TRY(launch_hist_reduce(c, c->d_rs_part.as<unsigned>(), rows, S, 1, row, c->d_rs_acc.as<unsigned long long>()));
     }
     std::vector<uint64_t> acc((size_t)S * (size_t)row);
     {
         StageTimer st(c, PSA_T_D2H);
-        PSA_HIP_CHECK(hipMemcpyAsync(acc.data(), c->d_angle_acc.ptr, acc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        PSA_HIP_CHECK(hipMemcpyAsync(acc.data(), c->d_rs_acc.ptr, acc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
         PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
     }
     for (int a = 0; a < S; ++a) {
@@ -175,16 +163,15 @@ int angle_run(psa_ctx* c, const double* box, const double* box_inverse, const in
 int debug_lists_run(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start,
                     int32_t n_groups, const double* r_cut, int64_t frame, int32_t* count, int32_t* list) {
     PSA_REQUIRE(count != nullptr && list != nullptr, "null output");
-    MsdCall      p;
+    AtomGroups   p;
     AngleSpecies sp;
     PSA_TRY(angle_check(c, "psa_debug_neighbour_lists", box, box_inverse, idx, group_start, n_groups, r_cut, &p, &sp));
     PSA_REQUIRE(frame >= 0 && frame <= p.T - 1, "frame %lld is outside [0, T - 1 = %lld]", (long long)frame, (long long)(p.T - 1));
     if (p.n_a == 0) return PSA_OK;
-    PSA_TRY(angle_upload_list(c, p, idx));
+    PSA_TRY(upload_atom_list(c, &p, idx));
     AngleWork w;
     PSA_TRY(angle_work(c, p.n_a, 1, &w));
-    PSA_TRY(launch_pair_frac(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), p.listed ? c->d_angle_idx.as<int>() : nullptr, p.n_a,
-                             box_inverse, w.c, frame, 0, 1, p.T, p.N));
+    PSA_TRY(launch_pair_frac(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), p.d_idx, p.n_a, box_inverse, w.c, frame, 0, 1, p.T, p.N));
     PSA_TRY(launch_angle_neighbours(c, w.c, w.count, w.list, sp, box, p.n_a, 1));
     std::vector<float> h((size_t)p.n_a * ANGLE_MAX_NEIGHBOURS * 4);
     PSA_HIP_CHECK(hipMemcpyAsync(count, w.count, (size_t)p.n_a * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));

@@ -283,10 +283,9 @@ int psa_destroy(psa_ctx* c) {
                           &c->d_self_ent, &c->d_self_slot, &c->d_self_idx, &c->d_self_groups, &c->d_self_scale, &c->d_self_part, &c->d_self_acc,
                           &c->d_self_out, &c->d_par_q, &c->d_par_tiles, &c->d_par_ent, &c->d_par_slot, &c->d_par_dest, &c->d_par_khat,
                           &c->d_par_idx, &c->d_par_bins, &c->d_par_scale, &c->d_par_acc, &c->d_par_out, &c->d_corr_tab, &c->d_corr_factor,
-                          &c->d_corr_scale, &c->d_corr_in, &c->d_corr_out, &c->d_msd_u, &c->d_msd_img, &c->d_msd_sums, &c->d_msd_offs,
-                          &c->d_msd_idx, &c->d_msd_chunks, &c->d_msd_sizes, &c->d_msd_lags, &c->d_msd_part, &c->d_msd_acc, &c->d_msd_out,
-                          &c->d_pair_c, &c->d_pair_idx, &c->d_pair_items, &c->d_pair_part, &c->d_pair_acc,
-                          &c->d_angle_work, &c->d_angle_idx, &c->d_angle_items, &c->d_angle_edges, &c->d_angle_part, &c->d_angle_acc})
+                          &c->d_corr_scale, &c->d_corr_in, &c->d_corr_out, &c->d_rs_idx, &c->d_rs_items, &c->d_rs_part, &c->d_rs_acc, &c->d_msd_u,
+                          &c->d_msd_img, &c->d_msd_sums, &c->d_msd_offs, &c->d_msd_sizes, &c->d_msd_lags, &c->d_msd_out, &c->d_pair_c,
+                          &c->d_angle_work, &c->d_angle_edges})
             b->release();
         (void)hipStreamDestroy(c->stream);
     }

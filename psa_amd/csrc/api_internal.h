@@ -19,6 +19,12 @@
 //   api_partial.hip  the species-resolved (partial) spectra on that lattice: one projection per species, products of pairs
 //   api_correlation.hip  F(k,t), F_s(k,t), C_L(k,t), C_T(k,t) on that lattice: the spectral calls with padded segments, then
 //                    the cosine back-transform of the summed power
+//   api_realspace.hip  what the real-space entries share: the atom groups and their checks, the box's determinant, inverse
+//                    and served radius, the histogram arguments, the atom-list upload, the rows of the integer reduce
+//                    (hist_reduce.hip; the device side of the geometry: min_image.h)
+//   api_msd.hip      MSD moments and the self van Hove function from unwrapped displacements
+//   api_pair.hip     g(r), its partials and the distinct van Hove function
+//   api_angle.hip    bond-angle distributions and coordination statistics
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
 // k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
 #pragma once
@@ -332,18 +338,36 @@ struct SelfPower {
 using SelfFill = std::function<int(int64_t a0, int64_t na, int64_t vb, int64_t s0, int64_t ns, const float2** d_work)>;
 int self_power_run(psa_ctx* c, const SelfPower& w, const SelfFill& fill);
 
-// ---- api_msd.hip / api_pair.hip: the atom groups of a real-space call
-struct MsdCall {
-    int64_t              T = 0, N = 0, n_a = 0, Ab = 0;
+// ---- api_realspace.hip: what the real-space entries (api_msd.hip, api_pair.hip, api_angle.hip) share.
+// The atom groups (species) of a real-space call
+struct AtomGroups {
+    int64_t              T = 0, N = 0, n_a = 0, Ab = 0;   // Ab: atoms (msd) or origins (pair, angle) of a block
     int32_t              G = 1;
     bool                 listed = false;        // false: all N atoms in order, one group
+    const int*           d_idx = nullptr;       // the atom list on the device once upload_atom_list has run (null: not listed)
     std::vector<int64_t> start;                 // (G + 1) the groups' offsets into the atom list
     std::vector<int64_t> size;                  // (G)
 };
+constexpr int64_t REALSPACE_TARGET_GROUPS = 4096;   // workgroups a launch aims at, where the work allows
+// det a of a 3 x 3 matrix, refused ("<name> is singular") when it vanishes against the entries' scale; its inverse by cofactors
+int  invertible_check(const double* a, const char* name, double* det);
+void inverse3(const double* a, double det, double* out);
 // what those entries refuse about the context (a communicator, no positions), the box and its inverse and the group
-// lists (at most MSD_MAX_GROUPS, disjoint, in bounds); fills everything of p but Ab
+// lists (at most MSD_MAX_GROUPS, disjoint, in bounds); fills everything of p but Ab and d_idx
 int group_list_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
-                     const int64_t* group_start, int32_t n_groups, MsdCall* p);
+                     const int64_t* group_start, int32_t n_groups, AtomGroups* p);
+// the radius `what` = r is within the served one: (1/2 - 2^-12) of the box's least perpendicular width, 1 / |column j of
+// Hinv|, compared with a relative slack of 2^-40 (a caller who divides that radius by n_r and multiplies again is served)
+int served_radius_check(const double* box_inverse, const char* what, double r);
+// the arguments of a histogram over lags: the lags (at most max_lags, in [0, T - 1]), origin_step, the bin width and
+// its float32 reciprocal (returned), the bins (at most max_bins)
+int histogram_args_check(const AtomGroups& p, const int64_t* lags, int64_t n_lags, int max_lags, int64_t origin_step, double dr, int32_t n_r,
+                         int max_bins, float* inv_dr);
+// the atom list into d_rs_idx (nothing when the call lists none); sets p->d_idx
+int upload_atom_list(psa_ctx* c, AtomGroups* p, const int32_t* idx);
+// the rows of a table listed group by group -- group g's entries are first[g] .. first[g + 1] - 1, `per` rows each -- as the
+// integer reduce takes them
+int rows_of_groups(const int32_t* first, int n, int64_t per, HistRows* rows);
 int    check_weights(psa_ctx* c, int64_t N);            // the context's atom weights fit a slot of N atoms
 void   set_geom_weights(const psa_ctx* c, ProjGeom* g);  // ... and go into a launch's geometry
 int    begin_result(psa_ctx* c, int64_t T, int64_t K_total, int64_t k_offset, bool intensity, char** rows);

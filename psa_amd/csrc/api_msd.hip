@@ -12,62 +12,10 @@
 
 namespace psa {
 
-// the checks the real-space entries share (also api_pair.hip): the context, the box and its inverse, the group lists
-int group_list_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
-                     const int64_t* group_start, int32_t n_groups, MsdCall* p) {
-    PSA_REQUIRE(c->comm == nullptr && c->nranks == 1, "%s is not available on a sharded context (%d ranks)", entry, c->nranks);
-    const DataSlot& pos = c->slot[PSA_SLOT_POSITIONS];
-    PSA_REQUIRE(pos.valid, "the positions slot holds no array: %s reads the positions", entry);
-    PSA_REQUIRE(box != nullptr && box_inverse != nullptr, "null box or box_inverse");
-    const double* H = box;
-    const double  det = H[0] * (H[4] * H[8] - H[5] * H[7]) - H[1] * (H[3] * H[8] - H[5] * H[6]) + H[2] * (H[3] * H[7] - H[4] * H[6]);
-    double        scale = 0.0;
-    for (int i = 0; i < 9; ++i) {
-        PSA_REQUIRE(std::isfinite(box[i]) && std::isfinite(box_inverse[i]), "box and box_inverse must be finite");
-        scale = std::max(scale, std::fabs(box[i]));
-    }
-    PSA_REQUIRE(std::isfinite(det) && std::fabs(det) > 1e-12 * scale * scale * scale, "the box is singular (determinant %g)", det);
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double e = 0.0;
-            for (int k = 0; k < 3; ++k) e += box[3 * i + k] * box_inverse[3 * k + j];
-            PSA_REQUIRE(std::fabs(e - (i == j ? 1.0 : 0.0)) < 1e-6, "box_inverse is not the inverse of box: (H Hinv)[%d][%d] = %g", i, j, e);
-        }
-    PSA_REQUIRE(n_groups >= 1 && n_groups <= MSD_MAX_GROUPS, "the number of atom groups is in [1, %d], got %d", MSD_MAX_GROUPS,
-                (int)n_groups);
-    p->T = pos.T, p->N = pos.N, p->G = n_groups;
-    PSA_REQUIRE(p->T >= 1 && p->T < (1ll << 31) && p->N < (1ll << 31), "a trajectory of (%lld, %lld) is more than this entry serves",
-                (long long)p->T, (long long)p->N);
-    if (!idx) {
-        PSA_REQUIRE(n_groups == 1, "idx NULL means one group of all atoms (n_groups must be 1)");
-        p->start = {0, p->N};
-    } else {
-        PSA_REQUIRE(group_start != nullptr, "null group_start");
-        PSA_REQUIRE(group_start[0] == 0, "group_start[0] must be 0, got %lld", (long long)group_start[0]);
-        for (int g = 0; g < n_groups; ++g)
-            PSA_REQUIRE(group_start[g + 1] >= group_start[g], "group_start must be ascending (group %d)", g);
-        PSA_REQUIRE(group_start[n_groups] < (1ll << 31), "too many atoms (%lld)", (long long)group_start[n_groups]);
-        std::vector<uint8_t> seen((size_t)p->N, 0);
-        for (int g = 0; g < n_groups; ++g)
-            for (int64_t i = group_start[g]; i < group_start[g + 1]; ++i) {
-                PSA_REQUIRE(idx[i] >= 0 && idx[i] < p->N, "Atom indices in basis out of bounds.");
-                PSA_REQUIRE(!seen[(size_t)idx[i]], "atom %d is listed twice (group %d): the groups must be disjoint", (int)idx[i], g);
-                seen[(size_t)idx[i]] = 1;
-            }
-        p->listed = true;
-        p->start.assign(group_start, group_start + n_groups + 1);
-    }
-    p->n_a = p->start[(size_t)n_groups];
-    for (int g = 0; g < n_groups; ++g) p->size.push_back(p->start[(size_t)g + 1] - p->start[(size_t)g]);
-    return PSA_OK;
-}
-
 namespace {
 
-constexpr int64_t MSD_TARGET_GROUPS = 4096;     // workgroups a launch aims at, where the work allows
-
 int msd_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
-              const int64_t* group_start, int32_t n_groups, int32_t unwrap, MsdCall* p) {
+              const int64_t* group_start, int32_t n_groups, int32_t unwrap, AtomGroups* p) {
     PSA_TRY(group_list_check(c, entry, box, box_inverse, idx, group_start, n_groups, p));
     PSA_REQUIRE(unwrap == 0 || unwrap == 1, "unwrap is 0 or 1, got %d", (int)unwrap);
     const int64_t W = c->opt_dynamic_work_bytes, per_atom = 24 * p->T;
@@ -78,7 +26,7 @@ int msd_check(psa_ctx* c, const char* entry, const double* box, const double* bo
 }
 
 // the unwrap pass of atoms [a0, a0 + na) of the list into d_msd_u (and d_msd_img)
-int msd_unwrap(psa_ctx* c, const MsdCall& p, const double* box, const double* box_inverse, int64_t a0, int64_t na, bool unwrap,
+int msd_unwrap(psa_ctx* c, const AtomGroups& p, const double* box, const double* box_inverse, int64_t a0, int64_t na, bool unwrap,
                bool images) {
     StageTimer    st(c, PSA_T_GATHER);
     const int64_t n_ft = (p.T + MSD_UNWRAP_FRAMES - 1) / MSD_UNWRAP_FRAMES;
@@ -88,14 +36,14 @@ int msd_unwrap(psa_ctx* c, const MsdCall& p, const double* box, const double* bo
         PSA_TRY(c->d_msd_sums.reserve((size_t)n_ft * (size_t)na * 3 * sizeof(int32_t)));
         PSA_TRY(c->d_msd_offs.reserve((size_t)n_ft * (size_t)na * 3 * sizeof(int32_t)));
     }
-    return launch_msd_unwrap(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), p.listed ? c->d_msd_idx.as<int>() : nullptr, a0, na, box,
-                             box_inverse, unwrap, c->d_msd_sums.as<int>(), c->d_msd_offs.as<int>(), c->d_msd_u.as<double>(),
+    return launch_msd_unwrap(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), p.d_idx, a0, na, box, box_inverse, unwrap,
+                             c->d_msd_sums.as<int>(), c->d_msd_offs.as<int>(), c->d_msd_u.as<double>(),
                              images ? c->d_msd_img.as<int>() : nullptr, p.T, p.N);
 }
 
 // The chunks of the block [a0, a0 + na): every group's part of it cut into runs of at most `ca` atoms, {first atom of the
 // block, one past the last, group, 0}, group by group; first (G + 1): where each group's chunks begin in the table
-std::vector<int32_t> msd_chunks(const MsdCall& p, int64_t a0, int64_t na, int64_t ca, int32_t* first) {
+std::vector<int32_t> msd_chunks(const AtomGroups& p, int64_t a0, int64_t na, int64_t ca, int32_t* first) {
     std::vector<int32_t> ch;
     for (int g = 0; g < p.G; ++g) {
         first[g] = (int32_t)(ch.size() / 4);
@@ -113,25 +61,26 @@ std::vector<int32_t> msd_chunks(const MsdCall& p, int64_t a0, int64_t na, int64_
 
 // origin slabs and atoms per chunk of a launch with `rows` workgroups per (slab, chunk): atoms are split first, then the
 // origin tiles; a chunk holds at most `ca_max` atoms
-void msd_split(const MsdCall& p, int64_t rows, int64_t step, int64_t ca_max, int64_t* n_os, int64_t* ca) {
+void msd_split(const AtomGroups& p, int64_t rows, int64_t step, int64_t ca_max, int64_t* n_os, int64_t* ca) {
     const int64_t n_ot = ((p.T - 1) / step + 1 + msd_origins(step) - 1) / msd_origins(step);
-    const int64_t want = std::max<int64_t>(1, MSD_TARGET_GROUPS / rows);                 // (slab, chunk) pairs
+    const int64_t want = std::max<int64_t>(1, REALSPACE_TARGET_GROUPS / rows);           // (slab, chunk) pairs
     const int64_t chunks = std::min(want, p.Ab);
     *n_os = std::max<int64_t>(1, std::min(n_ot, want / chunks));
     *ca = std::max<int64_t>((p.Ab + chunks - 1) / chunks, (p.Ab + 59999) / 60000);      // the grid's y holds 65535
     *ca = std::max<int64_t>(1, std::min(*ca, ca_max));
 }
 
-int msd_upload_list(psa_ctx* c, const MsdCall& p, const int32_t* idx) {
+// the atom list and the groups' sizes
+int msd_upload_list(psa_ctx* c, AtomGroups* p, const int32_t* idx) {
+    PSA_TRY(upload_atom_list(c, p, idx));
     StageTimer st(c, PSA_T_H2D);
-    if (p.listed) PSA_TRY(upload(c, c->d_msd_idx, idx, (size_t)p.n_a * sizeof(int32_t)));
-    return upload(c, c->d_msd_sizes, p.size.data(), p.size.size() * sizeof(int64_t));
+    return upload(c, c->d_msd_sizes, p->size.data(), p->size.size() * sizeof(int64_t));
 }
 
 int moments_run(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start,
                 int32_t n_groups, int64_t n_lags, int64_t origin_step, int32_t unwrap, double* out_host, size_t out_bytes) {
     PSA_REQUIRE(out_host != nullptr, "null output");
-    MsdCall p;
+    AtomGroups p;
     PSA_TRY(msd_check(c, "psa_displacement_moments", box, box_inverse, idx, group_start, n_groups, unwrap, &p));
     PSA_REQUIRE(n_lags >= 1 && n_lags <= p.T, "n_lags = %lld is outside [1, T = %lld]", (long long)n_lags, (long long)p.T);
     PSA_REQUIRE(origin_step >= 1, "origin_step must be at least 1, got %lld", (long long)origin_step);
@@ -141,10 +90,10 @@ int moments_run(psa_ctx* c, const double* box, const double* box_inverse, const 
         std::memset(out_host, 0, out_bytes);
         return PSA_OK;
     }
-    PSA_TRY(msd_upload_list(c, p, idx));
-    PSA_TRY(c->d_msd_acc.reserve(want));
+    PSA_TRY(msd_upload_list(c, &p, idx));
+    PSA_TRY(c->d_rs_acc.reserve(want));
     PSA_TRY(c->d_msd_out.reserve(want));
-    PSA_HIP_CHECK(hipMemsetAsync(c->d_msd_acc.ptr, 0, want, c->stream));
+    PSA_HIP_CHECK(hipMemsetAsync(c->d_rs_acc.ptr, 0, want, c->stream));
     int64_t n_os = 1, ca = 1;
     msd_split(p, (n_lags + MSD_LAGS - 1) / MSD_LAGS, origin_step, p.Ab, &n_os, &ca);
     for (int64_t a0 = 0; a0 < p.n_a; a0 += p.Ab) {
@@ -154,20 +103,20 @@ int moments_run(psa_ctx* c, const double* box, const double* box_inverse, const 
         const std::vector<int32_t> ch = msd_chunks(p, a0, na, ca, first);
         const int64_t              n_chunks = (int64_t)ch.size() / 4;
         PSA_REQUIRE(n_chunks <= 65535, "a block of %lld atoms is too large: lower PSA_OPT_DYNAMIC_WORK_BYTES", (long long)na);
-        PSA_TRY(upload(c, c->d_msd_chunks, ch.data(), ch.size() * sizeof(int32_t)));
-        PSA_TRY(c->d_msd_part.reserve((size_t)n_chunks * (size_t)n_os * want / (size_t)p.G));
+        PSA_TRY(upload(c, c->d_rs_items, ch.data(), ch.size() * sizeof(int32_t)));
+        PSA_TRY(c->d_rs_part.reserve((size_t)n_chunks * (size_t)n_os * want / (size_t)p.G));
         {
             StageTimer st(c, PSA_T_TRANSPOSE);
-            PSA_TRY(launch_msd_moments(c, c->d_msd_u.as<double>(), c->d_msd_chunks.ptr, n_chunks, c->d_msd_part.as<double>(), p.T, n_lags,
+            PSA_TRY(launch_msd_moments(c, c->d_msd_u.as<double>(), c->d_rs_items.ptr, n_chunks, c->d_rs_part.as<double>(), p.T, n_lags,
                                        origin_step, n_os));
         }
         StageTimer st(c, PSA_T_EPILOGUE);
-        PSA_TRY(launch_msd_moments_reduce(c, c->d_msd_part.as<double>(), first, c->d_msd_acc.as<double>(), n_lags,
+        PSA_TRY(launch_msd_moments_reduce(c, c->d_rs_part.as<double>(), first, c->d_rs_acc.as<double>(), n_lags,
                                           n_os, p.G));
     }
     {
         StageTimer st(c, PSA_T_EPILOGUE);
-        PSA_TRY(launch_msd_moments_finish(c, c->d_msd_acc.as<double>(), c->d_msd_sizes.as<int64_t>(), c->d_msd_out.as<double>(), p.T,
+        PSA_TRY(launch_msd_moments_finish(c, c->d_rs_acc.as<double>(), c->d_msd_sizes.as<int64_t>(), c->d_msd_out.as<double>(), p.T,
                                           n_lags, p.G, origin_step));
     }
     StageTimer st(c, PSA_T_D2H);
@@ -180,16 +129,10 @@ int van_hove_run(psa_ctx* c, const double* box, const double* box_inverse, const
                  int32_t n_groups, const int64_t* lags, int64_t n_vh, int64_t origin_step, int32_t unwrap, double dr, int32_t n_r,
                  uint64_t* out_host, size_t out_bytes) {
     PSA_REQUIRE(out_host != nullptr && lags != nullptr, "null output or lags");
-    MsdCall p;
+    AtomGroups p;
     PSA_TRY(msd_check(c, "psa_van_hove_self", box, box_inverse, idx, group_start, n_groups, unwrap, &p));
-    PSA_REQUIRE(n_vh >= 1 && n_vh <= MSD_MAX_VH_LAGS, "the number of lags is in [1, %d], got %lld", MSD_MAX_VH_LAGS, (long long)n_vh);
-    for (int64_t j = 0; j < n_vh; ++j)
-        PSA_REQUIRE(lags[j] >= 0 && lags[j] <= p.T - 1, "lag %lld is outside [0, T - 1 = %lld]", (long long)lags[j], (long long)(p.T - 1));
-    PSA_REQUIRE(origin_step >= 1, "origin_step must be at least 1, got %lld", (long long)origin_step);
-    PSA_REQUIRE(std::isfinite(dr) && dr > 0.0, "the bin width must be positive and finite, got %g", dr);
-    const float inv_dr = (float)(1.0 / dr);
-    PSA_REQUIRE(std::isfinite(inv_dr) && inv_dr > 0.f, "the bin width %g has no float32 reciprocal", dr);
-    PSA_REQUIRE(n_r >= 1 && n_r <= MSD_MAX_BINS, "the number of bins is in [1, %d], got %d", MSD_MAX_BINS, (int)n_r);
+    float inv_dr;
+    PSA_TRY(histogram_args_check(p, lags, n_vh, MSD_MAX_VH_LAGS, origin_step, dr, n_r, MSD_MAX_BINS, &inv_dr));
     const size_t want = (size_t)n_vh * (size_t)p.G * (size_t)(n_r + 1) * sizeof(uint64_t);
     PSA_REQUIRE(out_bytes == want, "out_bytes is %zu, the (%lld,%d,%d) uint64 result has %zu", out_bytes, (long long)n_vh, (int)p.G,
                 (int)(n_r + 1), want);
@@ -197,10 +140,10 @@ int van_hove_run(psa_ctx* c, const double* box, const double* box_inverse, const
         std::memset(out_host, 0, out_bytes);
         return PSA_OK;
     }
-    PSA_TRY(msd_upload_list(c, p, idx));
+    PSA_TRY(msd_upload_list(c, &p, idx));
     PSA_TRY(upload(c, c->d_msd_lags, lags, (size_t)n_vh * sizeof(int64_t)));
-    PSA_TRY(c->d_msd_acc.reserve(want));
-    PSA_HIP_CHECK(hipMemsetAsync(c->d_msd_acc.ptr, 0, want, c->stream));
+    PSA_TRY(c->d_rs_acc.reserve(want));
+    PSA_HIP_CHECK(hipMemsetAsync(c->d_rs_acc.ptr, 0, want, c->stream));
     // a workgroup's 32-bit counters: its chunk's atoms x the origins of lag 0 stay below 2^32
     const int64_t n_o0 = (p.T - 1) / origin_step + 1;
     int64_t       n_os = 1, ca = 1;
@@ -212,19 +155,20 @@ int van_hove_run(psa_ctx* c, const double* box, const double* box_inverse, const
         const std::vector<int32_t> ch = msd_chunks(p, a0, na, ca, first);
         const int64_t              n_chunks = (int64_t)ch.size() / 4;
         PSA_REQUIRE(n_chunks <= 65535, "a block of %lld atoms is too large: lower PSA_OPT_DYNAMIC_WORK_BYTES", (long long)na);
-        PSA_TRY(upload(c, c->d_msd_chunks, ch.data(), ch.size() * sizeof(int32_t)));
-        PSA_TRY(c->d_msd_part.reserve((size_t)n_chunks * (size_t)n_os * (size_t)n_vh * (size_t)(n_r + 1) * sizeof(uint32_t)));
+        PSA_TRY(upload(c, c->d_rs_items, ch.data(), ch.size() * sizeof(int32_t)));
+        PSA_TRY(c->d_rs_part.reserve((size_t)n_chunks * (size_t)n_os * (size_t)n_vh * (size_t)(n_r + 1) * sizeof(uint32_t)));
         {
             StageTimer st(c, PSA_T_TRANSPOSE);
-            PSA_TRY(launch_msd_hist(c, c->d_msd_u.as<double>(), c->d_msd_chunks.ptr, n_chunks, c->d_msd_lags.as<int64_t>(), n_vh,
-                                    c->d_msd_part.as<unsigned>(), p.T, origin_step, n_os, inv_dr, n_r));
+            PSA_TRY(launch_msd_hist(c, c->d_msd_u.as<double>(), c->d_rs_items.ptr, n_chunks, c->d_msd_lags.as<int64_t>(), n_vh,
+                                    c->d_rs_part.as<unsigned>(), p.T, origin_step, n_os, inv_dr, n_r));
         }
         StageTimer st(c, PSA_T_EPILOGUE);
-        PSA_TRY(launch_msd_hist_reduce(c, c->d_msd_part.as<unsigned>(), first,
-                                       c->d_msd_acc.as<unsigned long long>(), n_vh, n_os, n_r, p.G));
+        HistRows   rows;
+        PSA_TRY(rows_of_groups(first, p.G, n_os, &rows));
+        PSA_TRY(launch_hist_reduce(c, c->d_rs_part.as<unsigned>(), rows, p.G, n_vh, n_r + 1, c->d_rs_acc.as<unsigned long long>()));
     }
     StageTimer st(c, PSA_T_D2H);
-    PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_msd_acc.ptr, want, hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_rs_acc.ptr, want, hipMemcpyDeviceToHost, c->stream));
     PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return PSA_OK;
 }
@@ -235,10 +179,10 @@ int debug_unwrap_run(psa_ctx* c, const double* box, const double* box_inverse, c
     PSA_REQUIRE(out_u != nullptr, "null output");
     PSA_REQUIRE(idx == nullptr || (n_g >= 0 && n_g < (1ll << 31)), "bad number of atoms %lld", (long long)n_g);
     const int64_t start[2] = {0, n_g};
-    MsdCall       p;
+    AtomGroups       p;
     PSA_TRY(msd_check(c, "psa_debug_unwrap", box, box_inverse, idx, start, 1, unwrap, &p));
     if (p.n_a == 0) return PSA_OK;
-    PSA_TRY(msd_upload_list(c, p, idx));
+    PSA_TRY(msd_upload_list(c, &p, idx));
     std::vector<double>  hu;
     std::vector<int32_t> hi;
     for (int64_t a0 = 0; a0 < p.n_a; a0 += p.Ab) {

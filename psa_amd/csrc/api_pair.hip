@@ -14,20 +14,10 @@ namespace psa {
 
 namespace {
 
-static_assert(PAIR_MAX_SPECIES == MSD_MAX_GROUPS, "the species of a pair call are the groups of the displacement calls");
-
-constexpr int64_t PAIR_TARGET_GROUPS = 4096;    // workgroups a launch aims at, where the work allows
 constexpr int64_t PAIR_MAX_RUN = 256;           // most beta-tiles of an item
 
-// 1 / |column j of Hinv|: the box's perpendicular widths; the least of them
-double pair_min_width(const double* inv) {
-    double w = INFINITY;
-    for (int j = 0; j < 3; ++j) w = std::min(w, 1.0 / std::sqrt(inv[j] * inv[j] + inv[3 + j] * inv[3 + j] + inv[6 + j] * inv[6 + j]));
-    return w;
-}
-
 int pair_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
-               const int64_t* group_start, int32_t n_groups, MsdCall* p) {
+               const int64_t* group_start, int32_t n_groups, AtomGroups* p) {
     PSA_TRY(group_list_check(c, entry, box, box_inverse, idx, group_start, n_groups, p));
     const int64_t W = c->opt_dynamic_work_bytes, per_origin = 24 * std::max<int64_t>(p->n_a, 1);
     PSA_REQUIRE(W / per_origin >= 1, "the work budget of %lld bytes (PSA_OPT_DYNAMIC_WORK_BYTES) cannot hold the smallest block: the "
@@ -37,29 +27,30 @@ int pair_check(psa_ctx* c, const char* entry, const double* box, const double* b
     return PSA_OK;
 }
 
-int pair_upload_list(psa_ctx* c, const MsdCall& p, const int32_t* idx) {
-    StageTimer st(c, PSA_T_H2D);
-    return p.listed ? upload(c, c->d_pair_idx, idx, (size_t)p.n_a * sizeof(int32_t)) : PSA_OK;
-}
-
-// The items of a launch over n_ob origins, species pair by species pair; first (S S + 1): where each pair's items begin.
-// sym (tau = 0): alpha <= beta only, alpha = beta the upper triangle of tiles.  An item's samples -- PAIR_TILE alpha-atoms
-// x its beta-atoms x its origins -- stay below 2^32: run x origins per slab <= 65535.
-std::vector<PairItem> pair_items(const MsdCall& p, bool sym, int64_t n_ob, int32_t* first) {
+// The items of a launch over n_ob origins, species pair by species pair; rows: the items the reduce sums into (alpha, beta).
+// sym (tau = 0): items for alpha <= beta only, alpha = beta the upper triangle of tiles -- the items of (min, max) serve
+// both orders, and alpha = beta counts every evaluated pair twice.  An item's samples -- PAIR_TILE alpha-atoms x its
+// beta-atoms x its origins -- stay below 2^32: run x origins per slab <= 65535.
+std::vector<PairItem> pair_items(const AtomGroups& p, bool sym, int64_t n_ob, HistRows* rows) {
     const int S = p.G;
     const auto tiles = [&](int g) { return (p.size[(size_t)g] + PAIR_TILE - 1) / PAIR_TILE; };
     int64_t tile_pairs = 0;
     for (int a = 0; a < S; ++a)
         for (int b = sym ? a : 0; b < S; ++b) tile_pairs += sym && a == b ? tiles(a) * (tiles(a) + 1) / 2 : tiles(a) * tiles(b);
-    const int64_t run = std::max<int64_t>(1, std::min(PAIR_MAX_RUN, tile_pairs / PAIR_TARGET_GROUPS));
-    int64_t       n_os = std::max<int64_t>(1, std::min(n_ob, PAIR_TARGET_GROUPS / std::max<int64_t>(1, tile_pairs / run)));
+    const int64_t run = std::max<int64_t>(1, std::min(PAIR_MAX_RUN, tile_pairs / REALSPACE_TARGET_GROUPS));
+    int64_t       n_os = std::max<int64_t>(1, std::min(n_ob, REALSPACE_TARGET_GROUPS / std::max<int64_t>(1, tile_pairs / run)));
     const int64_t per_slab = 65535 / run;                    // most origins of a slab: per_slab run <= 65535
     n_os = std::max(n_os, (n_ob + per_slab - 1) / per_slab);  // the least n_os with ceil(n_ob / n_os) <= per_slab
     std::vector<PairItem> items;
     for (int a = 0; a < S; ++a)
         for (int b = 0; b < S; ++b) {
-            first[a * S + b] = (int32_t)items.size();
-            if (sym && b < a) continue;
+            const int out = a * S + b, twin = b * S + a;
+            rows->factor[out] = sym && a == b ? 2 : 1;
+            if (sym && b < a) {                              // the items of (beta, alpha), listed before
+                rows->lo[out] = rows->lo[twin], rows->hi[out] = rows->hi[twin];
+                continue;
+            }
+            rows->lo[out] = (int)items.size();
             for (int64_t i = 0; i < tiles(a); ++i)
                 for (int64_t j = sym && a == b ? i : 0; j < tiles(b); j += run)
                     for (int64_t slab = 0; slab < n_os; ++slab) {
@@ -73,29 +64,19 @@ std::vector<PairItem> pair_items(const MsdCall& p, bool sym, int64_t n_ob, int32
                         it.pair = a * S + b;
                         items.push_back(it);
                     }
+            rows->hi[out] = (int)items.size();
         }
-    first[S * S] = (int32_t)items.size();
     return items;
 }
 
 int pair_run(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start, int32_t n_groups,
              const int64_t* lags, int64_t n_vh, int64_t origin_step, double dr, int32_t n_r, uint64_t* out_host, size_t out_bytes) {
     PSA_REQUIRE(out_host != nullptr && lags != nullptr, "null output or lags");
-    MsdCall p;
+    AtomGroups p;
     PSA_TRY(pair_check(c, "psa_pair_histogram", box, box_inverse, idx, group_start, n_groups, &p));
-    PSA_REQUIRE(n_vh >= 1 && n_vh <= PAIR_MAX_LAGS, "the number of lags is in [1, %d], got %lld", PAIR_MAX_LAGS, (long long)n_vh);
-    for (int64_t j = 0; j < n_vh; ++j)
-        PSA_REQUIRE(lags[j] >= 0 && lags[j] <= p.T - 1, "lag %lld is outside [0, T - 1 = %lld]", (long long)lags[j], (long long)(p.T - 1));
-    PSA_REQUIRE(origin_step >= 1, "origin_step must be at least 1, got %lld", (long long)origin_step);
-    PSA_REQUIRE(std::isfinite(dr) && dr > 0.0, "the bin width must be positive and finite, got %g", dr);
-    const float inv_dr = (float)(1.0 / dr);
-    PSA_REQUIRE(std::isfinite(inv_dr) && inv_dr > 0.f, "the bin width %g has no float32 reciprocal", dr);
-    PSA_REQUIRE(n_r >= 1 && n_r <= PAIR_MAX_BINS, "the number of bins is in [1, %d], got %d", PAIR_MAX_BINS, (int)n_r);
-    // the served radius: (1/2 - 2^-12) of the least perpendicular width, compared with a relative slack of 2^-40 (a caller
-    // who divides that radius by n_r and multiplies again is served)
-    const double served = (0.5 - 0x1p-12) * pair_min_width(box_inverse);
-    PSA_REQUIRE((double)n_r * dr <= served * (1.0 + 0x1p-40), "r_max = n_r dr = %.17g is beyond the served radius %.17g: (1/2 - 2^-12) of "
-                "the box's least perpendicular width", (double)n_r * dr, served);
+    float inv_dr;
+    PSA_TRY(histogram_args_check(p, lags, n_vh, PAIR_MAX_LAGS, origin_step, dr, n_r, PAIR_MAX_BINS, &inv_dr));
+    PSA_TRY(served_radius_check(box_inverse, "r_max = n_r dr", (double)n_r * dr));
     const int    S = p.G;
     const size_t per_lag = (size_t)S * (size_t)S * (size_t)(n_r + 1) * sizeof(uint64_t), want = (size_t)n_vh * per_lag;
     PSA_REQUIRE(out_bytes == want, "out_bytes is %zu, the (%lld,%d,%d,%d) uint64 result has %zu", out_bytes, (long long)n_vh, S, S,
@@ -104,41 +85,40 @@ int pair_run(psa_ctx* c, const double* box, const double* box_inverse, const int
         std::memset(out_host, 0, out_bytes);
         return PSA_OK;
     }
-    PSA_TRY(pair_upload_list(c, p, idx));
-    PSA_TRY(c->d_pair_acc.reserve(want));
-    PSA_HIP_CHECK(hipMemsetAsync(c->d_pair_acc.ptr, 0, want, c->stream));
+    PSA_TRY(upload_atom_list(c, &p, idx));
+    PSA_TRY(c->d_rs_acc.reserve(want));
+    PSA_HIP_CHECK(hipMemsetAsync(c->d_rs_acc.ptr, 0, want, c->stream));
     const float* d_pos = c->slot[PSA_SLOT_POSITIONS].buf.as<float>();
-    const int*   d_idx = p.listed ? c->d_pair_idx.as<int>() : nullptr;
     for (int64_t j = 0; j < n_vh; ++j) {
         const int64_t tau = lags[j], n_o = (p.T - 1 - tau) / origin_step + 1;
         const bool    sym = tau == 0;
         const int64_t B = std::min<int64_t>({n_o, p.Ab, 65535});            // origins of a block (the fraction pass's grid holds 65535)
-        int32_t       first[PAIR_MAX_SPECIES * PAIR_MAX_SPECIES + 1];
-        const std::vector<PairItem> items = pair_items(p, sym, B, first);
+        HistRows      rows;
+        const std::vector<PairItem> items = pair_items(p, sym, B, &rows);
         if (items.empty()) continue;
-        PSA_TRY(upload(c, c->d_pair_items, items.data(), items.size() * sizeof(PairItem)));
-        PSA_TRY(c->d_pair_part.reserve(items.size() * (size_t)(n_r + 1) * sizeof(uint32_t)));
+        PSA_TRY(upload(c, c->d_rs_items, items.data(), items.size() * sizeof(PairItem)));
+        PSA_TRY(c->d_rs_part.reserve(items.size() * (size_t)(n_r + 1) * sizeof(uint32_t)));
         PSA_TRY(c->d_pair_c.reserve((size_t)(sym ? 1 : 2) * (size_t)B * 3 * (size_t)p.n_a * sizeof(float)));
         for (int64_t k0 = 0; k0 < n_o; k0 += B) {
             const int64_t nb = std::min(B, n_o - k0);
             float*        cA = c->d_pair_c.as<float>(), *cB = sym ? cA : cA + nb * 3 * p.n_a;
             {
                 StageTimer st(c, PSA_T_GATHER);
-                PSA_TRY(launch_pair_frac(c, d_pos, d_idx, p.n_a, box_inverse, cA, k0 * origin_step, origin_step, nb, p.T, p.N));
-                if (!sym) PSA_TRY(launch_pair_frac(c, d_pos, d_idx, p.n_a, box_inverse, cB, k0 * origin_step + tau, origin_step, nb, p.T, p.N));
+                PSA_TRY(launch_pair_frac(c, d_pos, p.d_idx, p.n_a, box_inverse, cA, k0 * origin_step, origin_step, nb, p.T, p.N));
+                if (!sym) PSA_TRY(launch_pair_frac(c, d_pos, p.d_idx, p.n_a, box_inverse, cB, k0 * origin_step + tau, origin_step, nb, p.T, p.N));
             }
             {
                 StageTimer st(c, PSA_T_TRANSPOSE);
-                PSA_TRY(launch_pair_hist(c, cA, cB, c->d_pair_items.ptr, (int64_t)items.size(), c->d_pair_part.as<unsigned>(), box, p.n_a,
+                PSA_TRY(launch_pair_hist(c, cA, cB, c->d_rs_items.ptr, (int64_t)items.size(), c->d_rs_part.as<unsigned>(), box, p.n_a,
                                          nb, inv_dr, n_r));
             }
             StageTimer st(c, PSA_T_EPILOGUE);
-            PSA_TRY(launch_pair_hist_reduce(c, c->d_pair_part.as<unsigned>(), first,
-                                            c->d_pair_acc.as<unsigned long long>() + (size_t)j * (per_lag / sizeof(uint64_t)), S, n_r, sym));
+            PSA_TRY(launch_hist_reduce(c, c->d_rs_part.as<unsigned>(), rows, S * S, 1, n_r + 1,
+                                       c->d_rs_acc.as<unsigned long long>() + (size_t)j * (per_lag / sizeof(uint64_t))));
         }
     }
     StageTimer st(c, PSA_T_D2H);
-    PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_pair_acc.ptr, want, hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_rs_acc.ptr, want, hipMemcpyDeviceToHost, c->stream));
     PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return PSA_OK;
 }
@@ -147,15 +127,15 @@ int pair_run(psa_ctx* c, const double* box, const double* box_inverse, const int
 int debug_plan_run(const int64_t* sizes, int32_t S, int32_t sym, int64_t n_ob, int64_t* out) {
     PSA_REQUIRE(sizes != nullptr && out != nullptr, "null sizes or output");
     PSA_REQUIRE(S >= 1 && S <= PAIR_MAX_SPECIES && n_ob >= 1 && n_ob <= 65535 && (sym == 0 || sym == 1), "bad plan arguments");
-    MsdCall p;
+    AtomGroups p;
     p.G = S, p.start = {0};
     for (int g = 0; g < S; ++g) {
         PSA_REQUIRE(sizes[g] >= 0 && p.start.back() + sizes[g] < (1ll << 31), "bad species size");
         p.size.push_back(sizes[g]);
         p.start.push_back(p.start.back() + sizes[g]);
     }
-    int32_t                     first[PAIR_MAX_SPECIES * PAIR_MAX_SPECIES + 1];
-    const std::vector<PairItem> items = pair_items(p, sym != 0, n_ob, first);
+    HistRows                    rows;
+    const std::vector<PairItem> items = pair_items(p, sym != 0, n_ob, &rows);
     out[0] = out[1] = out[3] = 0, out[2] = (int64_t)items.size();
     for (const PairItem& it : items) {
         const int64_t origins = it.slab < n_ob ? (n_ob - 1 - it.slab) / it.n_os + 1 : 0;
@@ -170,30 +150,21 @@ int debug_plan_run(const int64_t* sizes, int32_t S, int32_t sym, int64_t n_ob, i
 int debug_fractions_run(psa_ctx* c, const double* box_inverse, const int32_t* idx, int64_t n_g, float* out) {
     PSA_REQUIRE(out != nullptr && box_inverse != nullptr, "null output or box_inverse");
     PSA_REQUIRE(idx == nullptr || (n_g >= 0 && n_g < (1ll << 31)), "bad number of atoms %lld", (long long)n_g);
-    double H[9];                                             // the box of this inverse, for the shared checks
-    {
-        const double* a = box_inverse;
-        const double  det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
-        double        scale = 0.0;
-        for (int i = 0; i < 9; ++i) scale = std::max(scale, std::fabs(a[i]));
-        PSA_REQUIRE(std::isfinite(det) && std::fabs(det) > 1e-12 * scale * scale * scale, "box_inverse is singular (determinant %g)", det);
-        H[0] = (a[4] * a[8] - a[5] * a[7]) / det, H[1] = (a[2] * a[7] - a[1] * a[8]) / det, H[2] = (a[1] * a[5] - a[2] * a[4]) / det;
-        H[3] = (a[5] * a[6] - a[3] * a[8]) / det, H[4] = (a[0] * a[8] - a[2] * a[6]) / det, H[5] = (a[2] * a[3] - a[0] * a[5]) / det;
-        H[6] = (a[3] * a[7] - a[4] * a[6]) / det, H[7] = (a[1] * a[6] - a[0] * a[7]) / det, H[8] = (a[0] * a[4] - a[1] * a[3]) / det;
-    }
+    double H[9], det;                                        // the box of this inverse, for the shared checks
+    PSA_TRY(invertible_check(box_inverse, "box_inverse", &det));
+    inverse3(box_inverse, det, H);
     const int64_t start[2] = {0, n_g};
-    MsdCall       p;
+    AtomGroups       p;
     PSA_TRY(pair_check(c, "psa_debug_pair_fractions", H, box_inverse, idx, start, 1, &p));
     if (p.n_a == 0) return PSA_OK;
-    PSA_TRY(pair_upload_list(c, p, idx));
+    PSA_TRY(upload_atom_list(c, &p, idx));
     const int64_t      Bf = std::min<int64_t>({p.T, 2 * p.Ab, 65535});
     std::vector<float> h;
     PSA_TRY(c->d_pair_c.reserve((size_t)Bf * 3 * (size_t)p.n_a * sizeof(float)));
     for (int64_t f0 = 0; f0 < p.T; f0 += Bf) {
         const int64_t nf = std::min(Bf, p.T - f0);
         const size_t  n = (size_t)nf * 3 * (size_t)p.n_a;
-        PSA_TRY(launch_pair_frac(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), p.listed ? c->d_pair_idx.as<int>() : nullptr, p.n_a,
-                                 box_inverse, c->d_pair_c.as<float>(), f0, 1, nf, p.T, p.N));
+        PSA_TRY(launch_pair_frac(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), p.d_idx, p.n_a, box_inverse, c->d_pair_c.as<float>(), f0, 1, nf, p.T, p.N));
         h.resize(n);
         PSA_HIP_CHECK(hipMemcpyAsync(h.data(), c->d_pair_c.ptr, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         PSA_HIP_CHECK(hipStreamSynchronize(c->stream));

@@ -9,7 +9,7 @@
 //   msd_moments_reduce the partials, in order, added to the float64 accumulator (n_lags, G, 4) that lives across blocks
 //   msd_moments_finish scale by 1 / (N_g n_o(t)) in float64
 //   msd_hist           u64 -> per-workgroup 32-bit histograms of floor(|D| / dr) in LDS -> partials
-//   msd_hist_reduce    the partials summed in 64-bit integers into the accumulator (n_vh, G, n_r + 1)
+//   hist_reduce (hist_reduce.hip)  the partials summed in 64-bit integers into the accumulator (n_vh, G, n_r + 1)
 //
 // Unwrapping.  All of it float64 from the float32 positions.  For t >= 1, with e = r[t,a] - r[t-1,a] (exact in float64)
 //     d_j = fma(e_z, Hinv[2][j], fma(e_y, Hinv[1][j], e_x Hinv[0][j]))      m_j = rint(d_j)      (ties to even)
@@ -42,11 +42,13 @@
 // b_c = float32(u_c[o + tau] - u_c[o_0]) with the same origin tiles, D_c = b_c - a_c -- but read straight from u64, a
 // lane per origin: a call has one lag per workgroup, so a staged value would be read once.  Then
 //     r = __fsqrt_rn(r2),   x = __fmul_rn(r, inv_dr),   bin = x < n_r ? (int)floorf(x) : n_r    (inv_dr = float32(1 / dr))
+// (min_image.h's radial_bin, the one pair.hip bins with)
 // and a 32-bit integer add into the workgroup's histogram in LDS (n_r + 1 counters) -- the one place where this project
 // uses LDS atomics: integer adds commute, so the counts are bit-identical whatever the order.  The host bounds a
 // workgroup's samples below 2^32, the histogram goes to partials with plain stores, the reduce kernel sums in uint64.
 #include <algorithm>
 
+#include "min_image.h"
 #include "psa_ctx.h"
 
 namespace psa {
@@ -286,28 +288,13 @@ msd_hist_kernel(const double* __restrict__ u, const MsdChunk* __restrict__ chunk
                 const int64_t o = o0 + (int64_t)k * step, f = o + tau;     // f <= T - 1
                 const MsdUnit q = msd_unit((float)(ux[f] - bx), (float)(uy[f] - by), (float)(uz[f] - bz), (float)(ux[o] - bx),
                                            (float)(uy[o] - by), (float)(uz[o] - bz));
-                const float   x = __fmul_rn(__fsqrt_rn(q.r2), inv_dr);
-                const int     bin = x < edge ? (int)floorf(x) : n_r;      // (a value that is not finite: the overflow counter)
-                atomicAdd(&hist[bin], 1u);
+                atomicAdd(&hist[radial_bin(q.r2, inv_dr, edge, n_r)], 1u);
             }
         }
     }
     __syncthreads();
     unsigned* dst = part + (((int64_t)blockIdx.y * n_os + slab) * n_vh + j) * (n_r + 1);
     for (int i = threadIdx.x; i <= n_r; i += 256) dst[i] = hist[i];
-}
-
-// acc[lag j][group][n_r + 1] (uint64) += the partials of the group's chunks and slabs
-__global__ void __launch_bounds__(256)
-msd_hist_reduce_kernel(const unsigned* __restrict__ part, const MsdGroupChunks of, unsigned long long* __restrict__ acc, int n_vh,
-                       int G, int n_bins1, int n_os) {
-    const int64_t n = (int64_t)n_vh * G * n_bins1;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int          b = (int)(i % n_bins1), g = (int)(i / n_bins1 % G), j = (int)(i / ((int64_t)n_bins1 * G));
-        unsigned long long sum = acc[i];
-        for (int64_t r = (int64_t)of.first[g] * n_os; r < (int64_t)of.first[g + 1] * n_os; ++r) sum += part[(r * n_vh + j) * n_bins1 + b];
-        acc[i] = sum;
-    }
 }
 
 MsdBox msd_box(const double* box, const double* box_inverse) {
@@ -387,18 +374,6 @@ int launch_msd_hist(psa_ctx* c, const double* d_u, const void* d_chunks, int64_t
     hipLaunchKernelGGL(msd_hist_kernel, dim3((unsigned)(n_vh * n_os), (unsigned)n_chunks), dim3(256), 0, c->stream, d_u,
                        static_cast<const MsdChunk*>(d_chunks), d_lags, d_part, T, (int)n_vh, step, msd_origins(step), (int)n_os, inv_dr,
                        (int)n_r);
-    PSA_HIP_CHECK(hipGetLastError());
-    return PSA_OK;
-}
-
-int launch_msd_hist_reduce(psa_ctx* c, const unsigned* d_part, const int32_t* group_first, unsigned long long* d_acc, int64_t n_vh,
-                           int64_t n_os, int32_t n_r, int32_t G) {
-    if (group_first[G] == 0) return PSA_OK;
-    MsdGroupChunks of = {};
-    for (int g = 0; g <= G; ++g) of.first[g] = group_first[g];
-    const int64_t n = n_vh * G * (n_r + 1);
-    hipLaunchKernelGGL(msd_hist_reduce_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1 << 16)), dim3(256), 0, c->stream, d_part,
-                       of, d_acc, (int)n_vh, (int)G, (int)(n_r + 1), (int)n_os);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;
 }

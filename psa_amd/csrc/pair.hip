@@ -4,9 +4,10 @@
 //
 //   pair_frac          positions -> c (frames of a block, 3, n_a) float32, the centred fractional coordinates
 //   pair_hist          c of the origin frames and of their partner frames -> per-workgroup 32-bit histograms in LDS -> partials
-//   pair_hist_reduce   the partials summed in 64-bit integers into the accumulator (n_vh, S, S, n_r + 1), eight strands per bin
+//   hist_reduce (hist_reduce.hip)  the partials summed in 64-bit integers into the accumulator (n_vh, S, S, n_r + 1)
 //
-// Arithmetic.  Per (frame, atom), float64 from the float32 position r:
+// Arithmetic (the pair chain is min_image.h's min_image and radial_bin, which angle.hip and msd.hip share: this is its one
+// statement).  Per (frame, atom), float64 from the float32 position r:
 //     sigma_j = fma(r_z, Hinv[2][j], fma(r_y, Hinv[1][j], r_x Hinv[0][j]))
 //     c_j     = float32(sigma_j - floor(sigma_j) - 0.5)                          in [-0.5, 0.5]
 // (the prepass; a fractional coordinate formed in float32 would carry 2^-24 |sigma|, a bin's width at |r| of 10^3 boxes).
@@ -39,6 +40,7 @@
 // leaves out b = a (the self part).
 #include <algorithm>
 
+#include "min_image.h"
 #include "psa_ctx.h"
 
 namespace psa {
@@ -47,9 +49,6 @@ namespace {
 
 struct PairInv {
     double inv[9];
-};
-struct PairBox32 {
-    float h[9];
 };
 
 // Grid (atom tiles, frames of the block).  Frame k of the block is f0 + k df.  out[(k 3 + j) n_a + i], i the list position
@@ -68,23 +67,16 @@ pair_frac_kernel(const float* __restrict__ pos, const int* __restrict__ idx, int
 }
 
 // One pair: the bin of |mi(b - a)|
-__device__ inline int pair_bin(float ax, float ay, float az, float bx, float by, float bz, const PairBox32& B, float inv_dr, float edge,
+__device__ inline int pair_bin(float ax, float ay, float az, float bx, float by, float bz, const Box32& B, float inv_dr, float edge,
                                int n_r) {
-    float e0 = __fsub_rn(bx, ax), e1 = __fsub_rn(by, ay), e2 = __fsub_rn(bz, az);
-    e0 = __fsub_rn(e0, rintf(e0)), e1 = __fsub_rn(e1, rintf(e1)), e2 = __fsub_rn(e2, rintf(e2));
-    const float dx = __fmaf_rn(e2, B.h[6], __fmaf_rn(e1, B.h[3], __fmul_rn(e0, B.h[0])));
-    const float dy = __fmaf_rn(e2, B.h[7], __fmaf_rn(e1, B.h[4], __fmul_rn(e0, B.h[1])));
-    const float dz = __fmaf_rn(e2, B.h[8], __fmaf_rn(e1, B.h[5], __fmul_rn(e0, B.h[2])));
-    const float r2 = __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx)));
-    const float x = __fmul_rn(__fsqrt_rn(r2), inv_dr);
-    return x < edge ? (int)floorf(x) : n_r;                               // (a value that is not finite: the overflow counter)
+    return radial_bin(min_image(ax, ay, az, bx, by, bz, B).r2, inv_dr, edge, n_r);
 }
 
 // Grid (items).  cA, cB: (origins of the block, 3, n_a) float32 at the origin frames and at their partners (tau = 0: the
 // same buffer).  part[item][n_r + 1] uint32
 __global__ void __launch_bounds__(PAIR_TILE)
 pair_hist_kernel(const float* __restrict__ cA, const float* __restrict__ cB, const PairItem* __restrict__ items,
-                 unsigned* __restrict__ part, const PairBox32 B, int n_a, int n_ob, float inv_dr, int n_r) {
+                 unsigned* __restrict__ part, const Box32 B, int n_a, int n_ob, float inv_dr, int n_r) {
     __shared__ unsigned hist[PAIR_MAX_BINS + 1];
     __shared__ __attribute__((aligned(16))) float sb[3][PAIR_TILE];
     const PairItem it = items[blockIdx.x];
@@ -129,33 +121,6 @@ pair_hist_kernel(const float* __restrict__ cA, const float* __restrict__ cB, con
     for (int i = lane; i <= n_r; i += PAIR_TILE) dst[i] = hist[i];
 }
 
-// the items of species pair p = alpha S + beta are first[p] .. first[p + 1] - 1 of the table (the host lists them pair by pair)
-struct PairFirst {
-    int first[PAIR_MAX_SPECIES * PAIR_MAX_SPECIES + 1];
-};
-
-// Grid (tiles of PAIR_REDUCE_BINS bins, S S ordered species pairs).  acc[alpha][beta][n_r + 1] (uint64) += the partials of the
-// pair's items: a lane per bin, PAIR_REDUCE_STRANDS strands of lanes each on every PAIR_REDUCE_STRANDS-th item, their
-// 64-bit sums added through LDS (integer adds: any order, the same bits).  sym (tau = 0): the items of (min, max) serve both
-// orders, and alpha = beta counts every evaluated pair twice
-constexpr int PAIR_REDUCE_BINS = 32, PAIR_REDUCE_STRANDS = 8;
-__global__ void __launch_bounds__(PAIR_REDUCE_BINS * PAIR_REDUCE_STRANDS)
-pair_hist_reduce_kernel(const unsigned* __restrict__ part, const PairFirst of, unsigned long long* __restrict__ acc, int S, int n_bins1,
-                        int sym) {
-    __shared__ unsigned long long strands[PAIR_REDUCE_STRANDS][PAIR_REDUCE_BINS];
-    const int lane = threadIdx.x % PAIR_REDUCE_BINS, strand = threadIdx.x / PAIR_REDUCE_BINS;
-    const int b = blockIdx.x * PAIR_REDUCE_BINS + lane, al = blockIdx.y / S, be = blockIdx.y - al * S;
-    const int p = sym ? min(al, be) * S + max(al, be) : al * S + be;
-    unsigned long long sum = 0;
-    if (b < n_bins1)
-        for (int64_t r = of.first[p] + strand; r < of.first[p + 1]; r += PAIR_REDUCE_STRANDS) sum += part[r * n_bins1 + b];
-    strands[strand][lane] = sum;
-    __syncthreads();
-    if (strand || b >= n_bins1) return;
-    for (int w = 1; w < PAIR_REDUCE_STRANDS; ++w) sum += strands[w][lane];
-    acc[(int64_t)blockIdx.y * n_bins1 + b] += sym && al == be ? 2 * sum : sum;
-}
-
 }  // namespace
 
 int launch_pair_frac(psa_ctx* c, const float* d_pos, const int* d_idx, int64_t n_a, const double* box_inverse, float* d_out, int64_t f0,
@@ -177,21 +142,8 @@ int launch_pair_hist(psa_ctx* c, const float* d_cA, const float* d_cB, const voi
     if (n_items == 0) return PSA_OK;
     PSA_REQUIRE(n_items < (1ll << 31) && n_a < (1ll << 31) && n_ob >= 1 && n_ob < (1ll << 31) && n_r >= 1 && n_r <= PAIR_MAX_BINS,
                 "pair pass outside its grid");
-    PairBox32 B;
-    for (int i = 0; i < 9; ++i) B.h[i] = (float)box[i];
     hipLaunchKernelGGL(pair_hist_kernel, dim3((unsigned)n_items), dim3(PAIR_TILE), 0, c->stream, d_cA, d_cB,
-                       static_cast<const PairItem*>(d_items), d_part, B, (int)n_a, (int)n_ob, inv_dr, (int)n_r);
-    PSA_HIP_CHECK(hipGetLastError());
-    return PSA_OK;
-}
-
-int launch_pair_hist_reduce(psa_ctx* c, const unsigned* d_part, const int32_t* pair_first, unsigned long long* d_acc, int32_t S,
-                            int32_t n_r, bool sym) {
-    if (pair_first[S * S] == 0) return PSA_OK;
-    PairFirst of = {};
-    for (int p = 0; p <= S * S; ++p) of.first[p] = pair_first[p];
-    hipLaunchKernelGGL(pair_hist_reduce_kernel, dim3((unsigned)((n_r + 1 + PAIR_REDUCE_BINS - 1) / PAIR_REDUCE_BINS), (unsigned)(S * S)),
-                       dim3(PAIR_REDUCE_BINS * PAIR_REDUCE_STRANDS), 0, c->stream, d_part, of, d_acc, (int)S, (int)(n_r + 1), sym ? 1 : 0);
+                       static_cast<const PairItem*>(d_items), d_part, Box32(box), (int)n_a, (int)n_ob, inv_dr, (int)n_r);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;
 }

@@ -328,24 +328,25 @@ struct psa_ctx {
     // and the float32 result (1 or 3, n_lags, K or n_bins).  All kept between calls.
     psa::DevBuf  d_corr_tab, d_corr_factor, d_corr_scale, d_corr_in, d_corr_out;
 
+    // real-space structure (api_realspace.hip: what api_msd.hip, api_pair.hip and api_angle.hip share).  One set that every
+    // call of the three families fills before it reads it and none keeps for the next: the atom list, the item or chunk
+    // table, the workgroups' partials (uint32 histograms; float64 moments) and the accumulator that lives across the
+    // blocks and lags of a call (zeroed by the call).
+    psa::DevBuf  d_rs_idx, d_rs_items, d_rs_part, d_rs_acc;
+
     // real-space self dynamics (psa_displacement_moments, psa_van_hove_self, psa_debug_unwrap; api_msd.hip): the unwrapped
     // displacements u64 (atoms of a block, 3, T) float64, held to opt_dynamic_work_bytes; outside it the debug entry's
-    // image counts, the unwrap pass's tile sums and offsets, the atom list, the chunk table, the groups' sizes, the van
-    // Hove lags, the chunk partials, the accumulator that lives across blocks and the scaled moments.  All kept between calls.
-    psa::DevBuf  d_msd_u, d_msd_img, d_msd_sums, d_msd_offs, d_msd_idx, d_msd_chunks, d_msd_sizes, d_msd_lags, d_msd_part,
-                 d_msd_acc, d_msd_out;
+    // image counts, the unwrap pass's tile sums and offsets, the groups' sizes, the van Hove lags and the scaled moments.
+    psa::DevBuf  d_msd_u, d_msd_img, d_msd_sums, d_msd_offs, d_msd_sizes, d_msd_lags, d_msd_out;
 
     // pair distributions (psa_pair_histogram, psa_debug_pair_fractions; api_pair.hip): the centred fractional coordinates
-    // of a block of origin frames and of their partner frames (2, origins, 3, n_a) float32, held to opt_dynamic_work_bytes;
-    // outside it the atom list, the item table, the items' partial histograms and the accumulator that lives across
-    // blocks and lags.  All kept between calls.
-    psa::DevBuf  d_pair_c, d_pair_idx, d_pair_items, d_pair_part, d_pair_acc;
+    // of a block of origin frames and of their partner frames (2, origins, 3, n_a) float32, held to opt_dynamic_work_bytes.
+    psa::DevBuf  d_pair_c;
 
     // bond angles and coordination (psa_angle_histogram, psa_debug_neighbour_lists; api_angle.hip): per origin of a block
     // the centred fractional coordinates (3, n_a) float32, the neighbour counts (n_a) int32 and the neighbour lists
-    // (n_a, 64, 4) float32 -- 1040 n_a bytes, held to opt_dynamic_work_bytes; outside it the atom list, the item table,
-    // the bin edges, the items' partial histograms and the accumulator that lives across blocks.  All kept between calls.
-    psa::DevBuf  d_angle_work, d_angle_idx, d_angle_items, d_angle_edges, d_angle_part, d_angle_acc;
+    // (n_a, 64, 4) float32 -- 1040 n_a bytes, held to opt_dynamic_work_bytes; outside it the bin edges.
+    psa::DevBuf  d_angle_work, d_angle_edges;
 
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
@@ -607,11 +608,19 @@ int launch_msd_moments_reduce(psa_ctx* c, const double* d_part, const int32_t* g
 int launch_msd_moments_finish(psa_ctx* c, const double* d_acc, const int64_t* d_group_size, double* d_out, int64_t T, int64_t n_lags,
                               int32_t G, int64_t step);
 // the histogram kernel writes d_part (n_chunks, n_os, n_vh, n_r + 1) uint32 -- a chunk's atoms x the origins of a lag stay
-// below 2^32 (the caller's chunk rule) --, the reduce adds them to acc (n_vh, G, n_r + 1) uint64
+// below 2^32 (the caller's chunk rule) --, launch_hist_reduce adds them to acc (n_vh, G, n_r + 1) uint64
 int launch_msd_hist(psa_ctx* c, const double* d_u, const void* d_chunks, int64_t n_chunks, const int64_t* d_lags, int64_t n_vh,
                     unsigned* d_part, int64_t T, int64_t step, int64_t n_os, float inv_dr, int32_t n_r);
-int launch_msd_hist_reduce(psa_ctx* c, const unsigned* d_part, const int32_t* group_first, unsigned long long* d_acc, int64_t n_vh,
-                           int64_t n_os, int32_t n_r, int32_t G);
+// --- hist_reduce.hip (the integer reduce of the three histogram families).  The rows of the partials that output row g
+// sums, [lo[g], hi[g]), and what it multiplies the sum by: resolved by the host, passed by value
+constexpr int HIST_REDUCE_MAX_ROWS = 64;   // most output rows of a launch: the ordered pairs of PAIR_MAX_SPECIES species
+struct HistRows {
+    int lo[HIST_REDUCE_MAX_ROWS], hi[HIST_REDUCE_MAX_ROWS], factor[HIST_REDUCE_MAX_ROWS];
+};
+// acc[(j n + g) cols + col] (uint64) += factor[g] sum_r part[(r n_outer + j) cols + col] (uint32), r in [lo[g], hi[g]), for
+// g < n, j < n_outer, col < cols
+int launch_hist_reduce(psa_ctx* c, const unsigned* d_part, const HistRows& rows, int32_t n, int64_t n_outer, int64_t cols,
+                       unsigned long long* d_acc);
 // --- pair.hip (psa_pair_histogram, psa_debug_pair_fractions: the histogram of minimum-image pair distances between two
 // species over time origins; the arithmetic and the tiling are in its header)
 constexpr int PAIR_TILE = 256;         // alpha-atoms of a workgroup, one per lane, and beta-atoms of a staged tile
@@ -628,12 +637,9 @@ int launch_pair_frac(psa_ctx* c, const float* d_pos, const int* d_idx, int64_t n
                      int64_t df, int64_t n_frames, int64_t T, int64_t N);
 // d_cA, d_cB (n_ob, 3, n_a): the fractions at the block's origins and at their partner frames; d_items: n_items PairItem,
 // listed species pair by species pair; d_part (n_items, n_r + 1) uint32 -- an item's samples stay below 2^32 (the caller's
-// rule).  The reduce adds to acc (S, S, n_r + 1) uint64; pair_first (S S + 1, host): where each pair's items begin;
-// sym: the items of (alpha <= beta) serve both orders (tau = 0)
+// rule); launch_hist_reduce adds them to acc (S, S, n_r + 1) uint64
 int launch_pair_hist(psa_ctx* c, const float* d_cA, const float* d_cB, const void* d_items, int64_t n_items, unsigned* d_part,
                      const double* box, int64_t n_a, int64_t n_ob, float inv_dr, int32_t n_r);
-int launch_pair_hist_reduce(psa_ctx* c, const unsigned* d_part, const int32_t* pair_first, unsigned long long* d_acc, int32_t S,
-                            int32_t n_r, bool sym);
 // --- angle.hip (psa_angle_histogram, psa_debug_neighbour_lists: the neighbour shell of every atom, the angles between
 // pairs of neighbours and the coordination numbers; the arithmetic and the tiling are in its header)
 constexpr int ANGLE_MAX_NEIGHBOURS = 64;   // most neighbours a centre holds, all species together
@@ -662,12 +668,9 @@ inline int64_t angle_row_words(int S, int n_theta) {
 int launch_angle_neighbours(psa_ctx* c, const float* d_c, int* d_count, void* d_list, const AngleSpecies& sp, const double* box,
                             int64_t n_a, int64_t n_ob);
 // d_items: n_items AngleItem listed species by species; d_part (n_items, angle_row_words) uint32 -- an item's samples stay
-// below 2^32 (the caller's rule); d_edges (n_theta + 1) float32.  The reduce adds to acc (S, angle_row_words) uint64;
-// item_first (S + 1, host): where each species' items begin
+// below 2^32 (the caller's rule); d_edges (n_theta + 1) float32; launch_hist_reduce adds them to acc (S, angle_row_words) uint64
 int launch_angle_hist(psa_ctx* c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items, const float* d_edges,
                       unsigned* d_part, int32_t S, int64_t n_a, int64_t n_ob, int32_t n_theta);
-int launch_angle_reduce(psa_ctx* c, const unsigned* d_part, const int32_t* item_first, unsigned long long* d_acc, int32_t S,
-                        int32_t n_theta);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 

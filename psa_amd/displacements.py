@@ -36,6 +36,8 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
+from .pairs import _divide, _shell_volumes
+
 
 def origin_counts(n_frames: int, n_lags: int, origin_step: int = 1) -> np.ndarray:
     """n_o(t) = (T - 1 - t) // origin_step + 1 for t = 0 .. n_lags - 1, int64"""
@@ -48,6 +50,38 @@ def check_origin_step(origin_step) -> int:
     if isinstance(origin_step, bool) or not isinstance(origin_step, (int, np.integer)) or int(origin_step) < 1:
         raise ValueError(f"origin_step must be an integer of at least 1, got {origin_step!r}")
     return int(origin_step)
+
+
+def check_count(name: str, value, cap: int) -> int:
+    """`value` as an int; ValueError unless it is an integer in [1, cap]"""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= cap:
+        raise ValueError(f"{name} must be an integer in [1, {cap}], got {value!r}")
+    return int(value)
+
+
+def check_lag_frames(lag_frames, cap: int, n_frames: int) -> np.ndarray:
+    """`lag_frames` (a scalar or a list) as int64 (n_vh,); ValueError unless they are 1 to `cap` integers in [0, T - 1]"""
+    tau = np.asarray(lag_frames)
+    if tau.ndim == 0:
+        tau = tau.reshape(1)
+    if tau.ndim != 1 or (tau.size and not (np.issubdtype(tau.dtype, np.integer) or np.all(tau == np.rint(tau)))):
+        raise ValueError("lag_frames must be a list of integers")
+    tau = tau.astype(np.int64)
+    if not 1 <= tau.size <= cap:
+        raise ValueError(f"between 1 and {cap} lags are served, got {tau.size}")
+    if n_frames and (np.any(tau < 0) or np.any(tau > n_frames - 1)):
+        raise ValueError(f"lag_frames must lie in [0, T - 1 = {n_frames - 1}]")
+    return tau
+
+
+def radial_bins(r_max, n_r: int) -> Tuple[float, np.ndarray, np.ndarray]:
+    """(dr = r_max / n_r, the n_r + 1 edges, the n_r centres) of a radial histogram; ValueError unless r_max is positive
+    and finite"""
+    if not (np.isfinite(r_max) and float(r_max) > 0.0):
+        raise ValueError(f"r_max must be positive and finite, got {r_max!r}")
+    dr = float(r_max) / n_r
+    edges = dr * np.arange(n_r + 1, dtype=np.float64)
+    return dr, edges, 0.5 * (edges[1:] + edges[:-1])
 
 
 def alpha2(msd: np.ndarray, fourth: np.ndarray) -> np.ndarray:
@@ -103,19 +137,16 @@ class VanHoveSelf:
     groups: List[np.ndarray]
     dt_ps: Optional[float] = None
 
-    def _per_sample(self, width: np.ndarray) -> np.ndarray:
-        s = np.asarray(self.samples, np.float64)[:, :, None]
-        out = np.zeros(self.counts.shape, np.float64)
-        np.divide(np.asarray(self.counts, np.float64), s * width, out=out, where=s > 0)
-        return out
+    def _per_atom(self) -> np.ndarray:
+        """N_g n_o, shaped to divide counts"""
+        return np.asarray(self.samples, np.float64)[:, :, None]
 
     @property
     def radial_density(self) -> np.ndarray:
         """counts / (samples dr) = 4 pi r^2 G_s(r,t): sum_i radial_density dr = 1 - overflow / samples"""
-        return self._per_sample(np.diff(self.r_edges)[None, None, :])
+        return _divide(self.counts, self._per_atom() * np.diff(self.r_edges)[None, None, :])
 
     @property
     def g_s(self) -> np.ndarray:
         """counts / (samples (4 pi / 3)(r_hi^3 - r_lo^3)) = G_s(r,t)"""
-        e = np.asarray(self.r_edges, np.float64)
-        return self._per_sample((4.0 * np.pi / 3.0) * (e[1:] ** 3 - e[:-1] ** 3)[None, None, :])
+        return _divide(self.counts, self._per_atom() * _shell_volumes(self.r_edges)[None, None, :])

@@ -10,7 +10,7 @@ import pytest
 from kernel_build import SRC, device_compile
 from psa_amd import _hip
 
-KERNELS = ("angle_neighbours_kernel", "angle_hist_kernel", "angle_reduce_kernel")
+KERNELS = ("angle_neighbours_kernel", "angle_hist_kernel")   # the integer reduce: test_hist_reduce_resources.py
 
 
 def test_makefile_lists_the_sources():

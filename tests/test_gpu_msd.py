@@ -320,6 +320,14 @@ def test_blocking_and_reproducibility(engine):
         assert np.all(np.abs(a - b) <= np.spacing(np.maximum(np.abs(a), np.abs(b))))
         assert np.all(np.abs(cut - whole) <= 64 * 2.0 ** -53 * np.abs(whole))
         assert np.array_equal(counts, engine.van_hove_self(w["box"], lags, 0.25, 64, listing))
+        # the integer reduce (blocks whose groups hold fewer chunks than its eight strands, or none; 2, 34 and 65 columns;
+        # five lags x three groups): the three groups -- the middle one empty -- are, group by group, the three
+        # one-group calls, and sum_i counts + overflow = samples
+        n_r = {1: 1, 5: 33, 11: 64}[atoms]
+        three = engine.van_hove_self(w["box"], lags, 0.25, n_r, listing)
+        for g, members in enumerate(listing):
+            assert np.array_equal(three[:, g:g + 1], engine.van_hove_self(w["box"], lags, 0.25, n_r, [members])), (atoms, g)
+        assert np.array_equal(three.sum(axis=2), np.array([T - t for t in lags], np.uint64)[:, None] * np.array([12, 0, 23], np.uint64))
 
 
 def test_calculator_methods_and_draws(engine):

@@ -13,7 +13,7 @@ from psa_amd import _hip
 
 LDS_PER_CU = 160 * 1024
 KERNELS = ("msd_unwrap_count_kernel", "msd_unwrap_scan_kernel", "msd_unwrap_write_kernel", "msd_moments_kernel",
-           "msd_moments_reduce_kernel", "msd_moments_finish_kernel", "msd_hist_kernel", "msd_hist_reduce_kernel")
+           "msd_moments_reduce_kernel", "msd_moments_finish_kernel", "msd_hist_kernel")          # the integer reduce: test_hist_reduce_resources.py
 
 
 def test_makefile_lists_the_sources():

@@ -11,7 +11,7 @@ from kernel_build import SRC, device_compile
 from psa_amd import _hip
 
 LDS_PER_CU = 160 * 1024
-KERNELS = ("pair_frac_kernel", "pair_hist_kernel", "pair_hist_reduce_kernel")
+KERNELS = ("pair_frac_kernel", "pair_hist_kernel")          # the integer reduce: test_hist_reduce_resources.py
 
 
 def test_makefile_lists_the_sources():
