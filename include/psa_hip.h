@@ -810,6 +810,60 @@ int psa_angle_histogram(psa_ctx* ctx, const double* box /* 9 */, const double* b
                         int32_t n_theta, uint64_t* angles /* (S, P, n_theta + 1) */, size_t angles_bytes,
                         uint64_t* coord /* (S, S, 65) */, size_t coord_bytes, uint64_t* truncated /* S */);
 
+/* Steinhardt bond-orientational order parameters q_l of every atom's neighbour shell at every time origin: per species and
+ * order l the histogram of q_l, as integer counts, and optionally q_l^2 of every atom as an exact integer.
+ * Inputs.  The positions slot, H = box with its inverse, S <= 8 disjoint species, r_cut (S, S) and origin_step exactly as
+ * for psa_angle_histogram, under the same checks and refusals.  ls: n_ls orders, strictly ascending integers in [1, 12],
+ * 1 <= n_ls <= 8.  n_q in [1, 1024].
+ * Neighbours and capacity.  The neighbours of a centre are bit for bit those of psa_angle_histogram, of all species
+ * together (a pair of species bonds where r_cut[alpha][beta] > 0); n is their number.  A centre a in alpha at an origin is
+ * left out of the histograms, all or nothing, and counted once, in the first of
+ *     truncated[alpha]   it has more than 64 neighbours
+ *     isolated[alpha]    it has n = 0 neighbours
+ *     undefined[alpha]   it has a pair of legs whose cosine is not a number (a coincident neighbour, r2 = 0)
+ * that applies: sum_i hist[alpha,j,i] + truncated[alpha] + isolated[alpha] + undefined[alpha] = n_o N_alpha exactly for every j.
+ * Definition.  q_l(a)^2 = 4 pi / (2 l + 1) sum_m |1/n sum_b Y_lm(d_b / |d_b|)|^2 over the n legs d_b of a, which by the
+ * addition theorem of the spherical harmonics is 1/n^2 (n + 2 sum_{b<c} P_l(cos theta_bc)), theta_bc the angle between the
+ * legs b and c.  It is evaluated in that form.
+ * Per unordered pair {b, c} of legs, float32, every operation rounded once:
+ *     dot = fma(d_z(b), d_z(c), fma(d_y(b), d_y(c), d_x(b) d_x(c)));   q = r2(b) r2(c);   cos = dot / sqrt(q)
+ * clamped to [-1, 1] -- the chain of psa_angle_histogram, from the same stored d and r2 -- and then
+ *     P_0 = 1;   P_1 = cos;   P_{k+1} = __fmaf_rn(A_k, __fmul_rn(cos, P_k), -__fmul_rn(B_k, P_{k-1})),   k = 1 .. max(ls) - 1
+ *     A_k = float32((2 k + 1) / (k + 1)),   B_k = float32(k / (k + 1))   (the quotients formed in float64, rounded once)
+ *     t_l = __float2ll_rn(__fmul_rn(P_l, 2^24))
+ * The scaling is exact; the rounding to an integer loses at most 2^-25 in P_l.  Every step is symmetric in b <-> c bit for
+ * bit.
+ * Per centre, 64-bit integers:  X_l = n 2^24 + 2 sum_{b<c} t_l(b, c), clamped to [0, n^2 2^24];  q_l^2 = X_l / (n^2 2^24).
+ * Integer adds commute, so X_l depends on neither the order of the list, the blocking, the budget nor the order of the
+ * atoms inside a species.
+ * Bin.  n_q uniform bins in q over [0, 1], found with integers only: the largest i in [0, n_q - 1] with
+ * i^2 n^2 2^24 <= X_l n_q^2 (both sides stay below 2^57; q = 1 is in the last bin).  No floating-point root and no
+ * floating-point comparison after t_l.
+ * Outputs.  hist (S, n_ls, n_q) uint64; truncated, isolated, undefined (S) uint64; optionally per atom (either pointer may
+ * be NULL) x (n_o, n_a, n_ls) int64, the clamped X_l, -1 for a centre that is left out, and n (n_o, n_a) int32, the true
+ * neighbour count (beyond 64 too) -- n_a the listed atoms in list order.
+ * As evaluated (order.hip): the fraction pass and the neighbour pass of psa_angle_histogram; an order pass in which a
+ * wavefront reads a centre's list once, its lanes take the pairs and add t_l into 64-bit integers, a 64-bit wave
+ * reduction, and one lane per order bins with a 32-bit integer add in LDS -- an item's samples stay below 2^32 --, written
+ * to partials with plain stores and summed in 64-bit integers.  No global atomics, no float atomics; two identical calls,
+ * any budget and any order of the atoms inside a species give the same bits.
+ * Budget (PSA_OPT_DYNAMIC_WORK_BYTES): per origin of a block 1040 n_a bytes as for psa_angle_histogram, plus 8 n_ls n_a
+ * when x is asked for; every block's x and n are copied to the caller's arrays block by block; a budget below one origin
+ * is refused and the refusal names the bytes needed.
+ * PSA_EINVAL: everything psa_angle_histogram refuses about the context, the box, the species, r_cut, origin_step and the
+ * budget; ls null, n_ls outside [1, 8], an order outside [1, 12] or not strictly ascending; n_q outside [1, 1024];
+ * hist_bytes not exact; a null hist, truncated, isolated or undefined.
+ * Not here: the third-order invariants w_l and the neighbour-averaged q_l of Lechner and Dellago (both need the q_lm
+ * vectors themselves), Voronoi or solid-angle-weighted neighbours.
+ * Only the positions slot is read.  Atom weights and segments set on the context are ignored, not refused; every result
+ * and plan of the other entry points is left as it is.  Stage times: [0] the table's upload, [5] the fraction pass,
+ * [6] the neighbour pass, [1] the order pass, [4] reduce, [7] device->host. */
+int psa_bond_order(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                   const int64_t* group_start /* S+1 */, int32_t n_groups, const double* r_cut /* S*S */, int64_t origin_step,
+                   const int32_t* ls /* n_ls */, int32_t n_ls, int32_t n_q, uint64_t* hist /* (S, n_ls, n_q) */, size_t hist_bytes,
+                   uint64_t* truncated /* S */, uint64_t* isolated /* S */, uint64_t* undefined /* S */,
+                   int64_t* x /* (n_o, n_a, n_ls) or NULL */, int32_t* n /* (n_o, n_a) or NULL */);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is

@@ -80,6 +80,11 @@ PAIR_MAX_SPECIES = 8   # most species of a pair call
 # the caps of the angle kernels (psa_amd/csrc/angle.hip)
 ANGLE_MAX_NEIGHBOURS = 64   # most neighbours a centre holds, all species together
 ANGLE_MAX_BINS = 1024       # most bins of an angle histogram
+# the caps of the order kernel (psa_amd/csrc/order.hip)
+ORDER_MAX_L = 12        # the largest order l of a Steinhardt parameter q_l
+ORDER_MAX_LS = 8        # most orders of a call
+ORDER_MAX_BINS = 1024   # most bins of a q histogram
+ORDER_SHIFT = 24        # X_l counts units of 2^-24: q_l^2 = X_l / (n^2 2^24)
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -176,6 +181,9 @@ SIGNATURES = {
                                       _u64p]),
     "psa_debug_neighbour_lists": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32,
                                             _f64p, C.c_int64, _i32p, _i32p]),
+    "psa_bond_order": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p, C.c_int64,
+                                 _i32p, C.c_int32, C.c_int32, _u64p, C.c_size_t, _u64p, _u64p, _u64p,
+                                 _i64p, _i32p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, _f64p,
                                    _f64p, _f32p, _f32p, _f32p]),
@@ -1135,6 +1143,33 @@ class Engine:
                                                    rc.ctypes.data_as(_f64p), int(frame), count.ctypes.data_as(_i32p),
                                                    lst.ctypes.data_as(_i32p)), "psa_debug_neighbour_lists")
         return count[:n_a], lst[:n_a]
+
+    def bond_order(self, box, r_cut, ls, n_q: int, groups=None, origin_step: int = 1, per_atom: bool = False, box_inverse=None):
+        """The Steinhardt order parameters q_l as counts (psa_bond_order): (hist (S, n_l, n_q) uint64, truncated, isolated,
+        undefined (S,) uint64, x, n).  The neighbours are those of `angle_histogram` (`r_cut` a scalar or symmetric (S, S), 0:
+        no bond); hist[alpha, j, i] counts the (centre of species alpha, origin) whose q of order ls[j] lies in bin i of
+        `n_q` uniform bins over [0, 1]; a centre with more than 64 neighbours, with none, or with a coincident neighbour is
+        left out and counted in truncated, isolated or undefined.  `ls`: strictly ascending orders in [1, 12], at most 8.
+        With `per_atom`: x (n_o, n_a, n_l) int64, q_l^2 = x / (n^2 2^24) exactly as binned, -1 where the centre is left out,
+        and n (n_o, n_a) int32 the true neighbour counts, in list order; else None, None.  `box`, `groups`, `origin_step`
+        as for `pair_histogram`.  Only positions are read, as stored."""
+        T, N = self.shape(SLOT_POSITIONS)
+        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
+        rc = self._cutoffs(r_cut, G)
+        orders = np.ascontiguousarray(ls, np.int32).ravel()
+        held = orders if orders.size else np.zeros(1, np.int32)
+        n_a = N if groups is None else int(start[-1])
+        n_o = (T - 1) // max(int(origin_step), 1) + 1 if T else 0
+        hist = np.empty((G, orders.size, max(int(n_q), 0)), np.uint64)
+        trunc, iso, undef = (np.empty(G, np.uint64) for _ in range(3))
+        x = pinned_empty((n_o, n_a, orders.size), np.int64) if per_atom else None       # (every cell is written by the call)
+        n = pinned_empty((n_o, n_a), np.int32) if per_atom else None
+        _check(self._lib.psa_bond_order(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G,
+                                        rc.ctypes.data_as(_f64p), int(origin_step), held.ctypes.data_as(_i32p), orders.size, int(n_q),
+                                        hist.ctypes.data_as(_u64p), hist.nbytes, trunc.ctypes.data_as(_u64p), iso.ctypes.data_as(_u64p),
+                                        undef.ctypes.data_as(_u64p), None if x is None else x.ctypes.data_as(_i64p),
+                                        None if n is None else n.ctypes.data_as(_i32p)), "psa_bond_order")
+        return hist, trunc, iso, undef, x, n
 
     def debug_correlation_transform(self, power, L: int, n_seg: int, n_lags: int, as_float32: bool = False) -> np.ndarray:
         """The back-transform of the time correlations alone (psa_debug_correlation_transform): `power` (fields, P, cols)

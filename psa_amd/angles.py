@@ -22,8 +22,8 @@ The counts are exact integers:
     happens, since it means r_cut reaches far beyond the first shell.
   * The cut-offs are held to the served radius of the pair histograms, `max_pair_radius(box)`.
   * With one scalar cut-off the neighbours are bit for bit the pairs `calculate_rdf` counts below r_cut.
-  * Not here: cell lists for r_cut much smaller than the box, bond-length-resolved angle maps, Steinhardt order
-    parameters, ring statistics, time-lagged neighbour persistence, `max_atoms` sampling, sharding.
+  * Not here: cell lists for r_cut much smaller than the box, bond-length-resolved angle maps, ring statistics (the
+    Steinhardt order parameters of the same shells: psa_amd/order.py), time-lagged neighbour persistence, `max_atoms` sampling, sharding.
 
 This module is host code only: the result type.  `SEDCalculator.calculate_bond_angles` runs the kernels
 (psa_amd/csrc/angle.hip).

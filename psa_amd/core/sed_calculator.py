@@ -37,8 +37,9 @@ from ..covariance import ModeVectors, mode_vectors, spectral_weights
 from ..displacements import (MeanSquareDisplacement, VanHoveSelf, alpha2, check_count, check_lag_frames, check_origin_step,
                              origin_counts, radial_bins)
 from ..dynamic import DynamicSpectra
-from .. import angles
+from .. import angles, order
 from ..angles import BondAngleDistribution
+from ..order import BondOrder
 from ..pairs import RadialDistribution, VanHoveDistinct, max_pair_radius
 from .. import lattice
 from ..lattice import PowderSpectra
@@ -970,6 +971,17 @@ class SEDCalculator:
         Returns a `psa_amd.BondAngleDistribution` with `density`, `triplet(centre, b, c)`, `coordination_fraction` and
         `mean_coordination`."""
         n_theta = check_count("n_theta", n_theta, _hip.ANGLE_MAX_BINS)
+        rc, step, groups = self._shell_inputs(r_cut, basis_atom_indices, basis_atom_types, origin_step, "the bond-angle distribution")
+        if groups is None:
+            return angles.distribution(np.zeros((1, 1, n_theta + 1), np.uint64), np.zeros((1, 1, _hip.ANGLE_MAX_NEIGHBOURS + 1), np.uint64),
+                                       np.zeros(1, np.uint64), n_theta, 0, [np.zeros(0, int)])
+        out, coord, truncated = self._displacement_run(lambda eng, box: eng.angle_histogram(box, rc, n_theta, groups, step))
+        self._refuse_truncated(truncated)
+        return angles.distribution(out, coord, truncated, n_theta, (self.traj.n_frames - 1) // step + 1, groups)
+
+    def _shell_inputs(self, r_cut, basis_atom_indices, basis_atom_types, origin_step, what):
+        """(r_cut as an array, origin_step, the species' atom-index arrays or None -- warned: 0 frames or 0 atoms) of a call
+        on the neighbour shells (`calculate_bond_angles`, `calculate_bond_order`), after its refusals"""
         rc = np.asarray(r_cut, np.float64)
         if rc.ndim not in (0, 2) or not np.all(np.isfinite(rc)) or np.any(rc < 0.0):
             raise ValueError("r_cut must be a scalar or an (S, S) matrix of finite values that are not negative")
@@ -977,21 +989,55 @@ class SEDCalculator:
         if rc.size and float(rc.max()) > served:
             raise ValueError(f"r_cut = {float(rc.max())!r} is beyond the served radius {served!r} (psa_amd.max_pair_radius): "
                              "(1/2 - 2^-12) of the box's least perpendicular width")
-        what = "the bond-angle distribution"
         step, groups = self._displacement_groups(basis_atom_indices, basis_atom_types, origin_step, True, None, 0, what)
         if groups is None:
             logger.warning(f"Cannot calculate {what}: 0 frames or 0 atoms.")
-            return angles.distribution(np.zeros((1, 1, n_theta + 1), np.uint64), np.zeros((1, 1, _hip.ANGLE_MAX_NEIGHBOURS + 1), np.uint64),
-                                       np.zeros(1, np.uint64), n_theta, 0, [np.zeros(0, int)])
+            return rc, step, None
         S = len(groups)
         if rc.ndim == 2 and (rc.shape != (S, S) or not np.array_equal(rc, rc.T)):
             raise ValueError(f"r_cut must be a scalar or a symmetric ({S}, {S}) matrix, got shape {rc.shape}")
-        out, coord, truncated = self._displacement_run(lambda eng, box: eng.angle_histogram(box, rc, n_theta, groups, step))
+        return rc, step, groups
+
+    @staticmethod
+    def _refuse_truncated(truncated):
         if truncated.any():
             bad = ", ".join(f"species {a}: {int(truncated[a])}" for a in np.flatnonzero(truncated))
             raise ValueError(f"centres with more than {_hip.ANGLE_MAX_NEIGHBOURS} neighbours were left out ({bad} (centre, frame) "
                              "samples): r_cut reaches beyond the first shells, choose a smaller r_cut")
-        return angles.distribution(out, coord, truncated, n_theta, (self.traj.n_frames - 1) // step + 1, groups)
+
+    # ------------------------------------------------------------------ Steinhardt bond-orientational order parameters
+    def calculate_bond_order(self, r_cut, ls=(4, 6), n_q: int = 200,
+                             basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                             basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                             origin_step: int = 1, per_atom: bool = False) -> BondOrder:
+        """The Steinhardt bond-orientational order parameters q_l of every atom's neighbour shell (not in the reference;
+        definition in psa_amd/order.py), computed on the GPU from the positions resident in HBM.  The neighbours are those
+        of `calculate_bond_angles` -- `r_cut` a scalar or a symmetric (S, S) matrix, 0 meaning "no bond between these
+        species", no entry beyond `psa_amd.max_pair_radius(box)` -- of all species together.  Over the frames 0,
+        origin_step, ... q_l of every centre is counted per species and order in `n_q` <= 1024 uniform bins over [0, 1];
+        `ls`: at most 8 strictly ascending orders in [1, 12].  Integer counts, the same bits for any budget and atom
+        order; positions as stored, nothing unwrapped.  `per_atom=True` adds `q_atoms` (n_o, n_a, n_l), `neighbours` and
+        `mean` -- the (q_4, q_6) scatter that tells fcc, hcp, bcc and icosahedral shells apart.
+
+        Species are resolved like those of `calculate_bond_angles` (disjoint, at most 8).  A centre with no neighbour or
+        with a coincident one is counted in `isolated` or `undefined`; where a centre has more than 64 neighbours the
+        call raises ValueError naming the species: choose a smaller `r_cut` (`Engine.bond_order` returns the numbers
+        instead).  A sharded calculator refuses (NotImplementedError).  Returns a `psa_amd.BondOrder`."""
+        n_q = check_count("n_q", n_q, _hip.ORDER_MAX_BINS)
+        orders = np.asarray(ls)
+        if (orders.ndim != 1 or not 1 <= orders.size <= _hip.ORDER_MAX_LS or orders.dtype.kind not in "iu"
+                or orders.min() < 1 or orders.max() > _hip.ORDER_MAX_L or np.any(np.diff(orders) <= 0)):
+            raise ValueError(f"ls must be 1 to {_hip.ORDER_MAX_LS} strictly ascending integers in [1, {_hip.ORDER_MAX_L}], got {ls!r}")
+        if not isinstance(per_atom, (bool, np.bool_)):
+            raise TypeError(f"per_atom must be a bool, got {type(per_atom).__name__}")
+        rc, step, groups = self._shell_inputs(r_cut, basis_atom_indices, basis_atom_types, origin_step, "the bond order parameters")
+        if groups is None:
+            zero = np.zeros(1, np.uint64)
+            return order.result(np.zeros((1, orders.size, n_q), np.uint64), zero, zero.copy(), zero.copy(), None, None, orders, n_q, 0,
+                                [np.zeros(0, int)])
+        out = self._displacement_run(lambda eng, box: eng.bond_order(box, rc, orders, n_q, groups, step, bool(per_atom)))
+        self._refuse_truncated(out[1])
+        return order.result(*out, orders, n_q, (self.traj.n_frames - 1) // step + 1, groups)
 
     # ------------------------------------------------------------------ partial (species-resolved) spectra on that lattice
     def _partial_species(self, basis_atom_indices, basis_atom_types, weights):

@@ -1,6 +1,6 @@
-// psa_angle_histogram, psa_debug_neighbour_lists: the bond-angle distributions of species triplets and the coordination
-// statistics of species pairs over time origins (definition: include/psa_hip.h; kernels: angle.hip, and pair.hip's
-// fraction pass).  Only the positions slot is read; atom weights and segments set on the context are ignored; nothing of
+// psa_angle_histogram, psa_debug_neighbour_lists, psa_bond_order: the bond-angle distributions of species triplets, the
+// coordination statistics of species pairs and the Steinhardt order parameters of the neighbour shells over time origins
+// (definition: include/psa_hip.h; kernels: angle.hip, order.hip, and pair.hip's fraction pass).  Only the positions slot is read; atom weights and segments set on the context are ignored; nothing of
 // the other entry points' state is touched.
 //
 // Budget (PSA_OPT_DYNAMIC_WORK_BYTES = W): per origin of a block the centred fractional coordinates of the listed atoms
@@ -8,6 +8,10 @@
 // whole number of origins, W / (1040 n_a) of them, and a budget below one origin is refused.  The item table, the bin
 // edges, the partials, the accumulator and the result lie outside it.  Per block: the fraction pass, the neighbour pass,
 // the angle pass over the items, the reduce into the accumulator that lives across blocks.
+//
+// psa_bond_order (kernel: order.hip) is the same call with the order pass in place of the angle pass: the same checks, work
+// buffer, items and reduce; with per-atom output the block's X (8 n_l n_a bytes per origin) lies behind the counts, inside
+// the budget, and every block's X and counts are copied to the caller's arrays before the next block overwrites them.
 #include "api_internal.h"
 
 namespace psa {
@@ -22,9 +26,10 @@ static_assert((uint64_t)ANGLE_ITEM_CENTRES * ANGLE_MAX_SLAB * (ANGLE_MAX_NEIGHBO
               "an item's samples fit 32 bits");
 constexpr int64_t ANGLE_ORIGIN_BYTES = 12 + 4 + 16 * ANGLE_MAX_NEIGHBOURS;   // per atom and origin
 
-// the shared checks, the cut-offs and the budget; fills p (Ab: origins of a block) and sp
+// the shared checks, the cut-offs and the budget (extra: bytes per atom and origin behind the counts); fills p (Ab: origins
+// of a block) and sp
 int angle_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
-                const int64_t* group_start, int32_t n_groups, const double* r_cut, AtomGroups* p, AngleSpecies* sp) {
+                const int64_t* group_start, int32_t n_groups, const double* r_cut, AtomGroups* p, AngleSpecies* sp, int64_t extra = 0) {
     PSA_TRY(group_list_check(c, entry, box, box_inverse, idx, group_start, n_groups, p));
     PSA_REQUIRE(r_cut != nullptr, "null r_cut");
     const int    S = p->G;
@@ -46,7 +51,7 @@ int angle_check(psa_ctx* c, const char* entry, const double* box, const double* 
                 (long long)p->n_a);
     for (int g = 0; g <= S; ++g) sp->start[g] = (int)p->start[(size_t)g];
     for (int g = 0; g < S; ++g) sp->tile_first[g + 1] = sp->tile_first[g] + (int)((p->size[(size_t)g] + ANGLE_CENTRES - 1) / ANGLE_CENTRES);
-    const int64_t W = c->opt_dynamic_work_bytes, per_origin = ANGLE_ORIGIN_BYTES * std::max<int64_t>(p->n_a, 1);
+    const int64_t W = c->opt_dynamic_work_bytes, per_origin = (ANGLE_ORIGIN_BYTES + extra) * std::max<int64_t>(p->n_a, 1);
     PSA_REQUIRE(W / per_origin >= 1, "the work budget of %lld bytes (PSA_OPT_DYNAMIC_WORK_BYTES) cannot hold the smallest block: the "
                 "fractional coordinates, neighbour counts and neighbour lists of %lld atoms at one origin need %lld bytes", (long long)W,
                 (long long)p->n_a, (long long)per_origin);
@@ -54,19 +59,22 @@ int angle_check(psa_ctx* c, const char* entry, const double* box, const double* 
     return PSA_OK;
 }
 
-// the work buffer of a block of B origins: the lists first (16-byte entries), then c, then the counts
+// the work buffer of a block of B origins: the lists first (16-byte entries), then c, then the counts, then `extra` bytes
+// per atom and origin (a multiple of 8: psa_bond_order's X)
 struct AngleWork {
-    float4* list;
-    float*  c;
-    int*    count;
+    float4*    list;
+    float*     c;
+    int*       count;
+    long long* x;
 };
-int angle_work(psa_ctx* c, int64_t n_a, int64_t B, AngleWork* w) {
+int angle_work(psa_ctx* c, int64_t n_a, int64_t B, AngleWork* w, int64_t extra = 0) {
     const size_t rows = (size_t)B * (size_t)n_a;
-    PSA_TRY(c->d_angle_work.reserve(rows * (size_t)ANGLE_ORIGIN_BYTES));
+    PSA_TRY(c->d_angle_work.reserve(rows * (size_t)(ANGLE_ORIGIN_BYTES + extra)));
     char* base = static_cast<char*>(c->d_angle_work.ptr);
     w->list = reinterpret_cast<float4*>(base);
     w->c = reinterpret_cast<float*>(base + rows * 16 * ANGLE_MAX_NEIGHBOURS);
     w->count = reinterpret_cast<int*>(base + rows * (16 * ANGLE_MAX_NEIGHBOURS + 12));
+    w->x = extra ? reinterpret_cast<long long*>(base + rows * (size_t)ANGLE_ORIGIN_BYTES) : nullptr;
     return PSA_OK;
 }
 
@@ -89,6 +97,58 @@ std::vector<AngleItem> angle_items(const AtomGroups& p, int64_t n_ob, int64_t ro
     return items;
 }
 
+// What a call on the neighbour shells runs after its checks (angle_run, order_run): the item table over the origins of a
+// block, the uploads of the atom list and the table, the accumulator (S, row) zeroed; per block the fraction pass, the
+// neighbour pass, the caller's `pass` over the items into the partials, the reduce, and `after` where the caller has
+// something to take out of the block before the next one overwrites it; at the end the accumulator on the host.
+// extra: bytes per atom and origin behind the counts (AngleWork::x)
+using ShellPass = std::function<int(const AngleWork& w, int64_t n_items, int64_t k0, int64_t nb)>;
+int shell_run(psa_ctx* c, AtomGroups& p, const AngleSpecies& sp, const int32_t* idx, const double* box, const double* box_inverse,
+              int64_t origin_step, int64_t row, int64_t extra, const ShellPass& pass, const ShellPass& after, std::vector<uint64_t>* acc) {
+    const int     S = p.G;
+    const int64_t n_o = (p.T - 1) / origin_step + 1, B = std::min<int64_t>({n_o, p.Ab, 65535});
+    int32_t                      first[PAIR_MAX_SPECIES + 1];
+    const std::vector<AngleItem> items = angle_items(p, B, row, first);
+    AngleWork                    w;
+    HistRows                     rows;
+    PSA_TRY(rows_of_groups(first, S, 1, &rows));
+    PSA_TRY(upload_atom_list(c, &p, idx));
+    {
+        StageTimer st(c, PSA_T_H2D);
+        PSA_TRY(upload(c, c->d_rs_items, items.data(), items.size() * sizeof(AngleItem)));
+    }
+    PSA_TRY(c->d_rs_part.reserve(items.size() * (size_t)row * sizeof(uint32_t)));
+    PSA_TRY(c->d_rs_acc.reserve((size_t)S * (size_t)row * sizeof(uint64_t)));
+    PSA_HIP_CHECK(hipMemsetAsync(c->d_rs_acc.ptr, 0, (size_t)S * (size_t)row * sizeof(uint64_t), c->stream));
+    PSA_TRY(angle_work(c, p.n_a, B, &w, extra));
+    const float* d_pos = c->slot[PSA_SLOT_POSITIONS].buf.as<float>();
+    for (int64_t k0 = 0; k0 < n_o; k0 += B) {
+        const int64_t nb = std::min(B, n_o - k0);
+        {
+            StageTimer st(c, PSA_T_GATHER);
+            PSA_TRY(launch_pair_frac(c, d_pos, p.d_idx, p.n_a, box_inverse, w.c, k0 * origin_step, origin_step, nb, p.T, p.N));
+        }
+        {
+            StageTimer st(c, PSA_T_TRANSPOSE);
+            PSA_TRY(launch_angle_neighbours(c, w.c, w.count, w.list, sp, box, p.n_a, nb));
+        }
+        {
+            StageTimer st(c, PSA_T_PHASE);
+            PSA_TRY(pass(w, (int64_t)items.size(), k0, nb));
+        }
+        {
+            StageTimer st(c, PSA_T_EPILOGUE);
+            PSA_TRY(launch_hist_reduce(c, c->d_rs_part.as<unsigned>(), rows, S, 1, row, c->d_rs_acc.as<unsigned long long>()));
+        }
+        if (after) PSA_TRY(after(w, (int64_t)items.size(), k0, nb));
+    }
+    acc->resize((size_t)S * (size_t)row);
+    StageTimer st(c, PSA_T_D2H);
+    PSA_HIP_CHECK(hipMemcpyAsync(acc->data(), c->d_rs_acc.ptr, acc->size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return PSA_OK;
+}
+
 int angle_run(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start, int32_t n_groups,
               const double* r_cut, int64_t origin_step, int32_t n_theta, uint64_t* angles, size_t angles_bytes, uint64_t* coord,
               size_t coord_bytes, uint64_t* truncated) {
@@ -106,55 +166,75 @@ int angle_run(psa_ctx* c, const double* box, const double* box_inverse, const in
     std::memset(coord, 0, want_c);
     std::memset(truncated, 0, (size_t)S * sizeof(uint64_t));
     if (p.n_a == 0) return PSA_OK;                           // every species empty: zeros
-    const int64_t n_o = (p.T - 1) / origin_step + 1, B = std::min<int64_t>({n_o, p.Ab, 65535}), row = angle_row_words(S, n_theta);
+    const int64_t      row = angle_row_words(S, n_theta);
     std::vector<float> edges((size_t)n1);
     for (int i = 0; i < n1; ++i) edges[(size_t)i] = (float)std::cos((double)i * M_PI / (double)n_theta);
     edges[0] = 1.f, edges[(size_t)n_theta] = -1.f;
-    int32_t                      first[PAIR_MAX_SPECIES + 1];
-    const std::vector<AngleItem> items = angle_items(p, B, row, first);
-    AngleWork                    w;
-    HistRows                     rows;
-    PSA_TRY(rows_of_groups(first, S, 1, &rows));
-    PSA_TRY(upload_atom_list(c, &p, idx));
     {
         StageTimer st(c, PSA_T_H2D);
         PSA_TRY(upload(c, c->d_angle_edges, edges.data(), edges.size() * sizeof(float)));
-        PSA_TRY(upload(c, c->d_rs_items, items.data(), items.size() * sizeof(AngleItem)));
     }
-    PSA_TRY(c->d_rs_part.reserve(items.size() * (size_t)row * sizeof(uint32_t)));
-    PSA_TRY(c->d_rs_acc.reserve((size_t)S * (size_t)row * sizeof(uint64_t)));
-    PSA_HIP_CHECK(hipMemsetAsync(c->d_rs_acc.ptr, 0, (size_t)S * (size_t)row * sizeof(uint64_t), c->stream));
-    PSA_TRY(angle_work(c, p.n_a, B, &w));
-    const float* d_pos = c->slot[PSA_SLOT_POSITIONS].buf.as<float>();
-    for (int64_t k0 = 0; k0 < n_o; k0 += B) {
-        const int64_t nb = std::min(B, n_o - k0);
-        {
-            StageTimer st(c, PSA_T_GATHER);
-            PSA_TRY(launch_pair_frac(c, d_pos, p.d_idx, p.n_a, box_inverse, w.c, k0 * origin_step, origin_step, nb, p.T, p.N));
-        }
-        {
-            StageTimer st(c, PSA_T_TRANSPOSE);
-            PSA_TRY(launch_angle_neighbours(c, w.c, w.count, w.list, sp, box, p.n_a, nb));
-        }
-        {
-            StageTimer st(c, PSA_T_PHASE);
-            PSA_TRY(launch_angle_hist(c, w.count, w.list, c->d_rs_items.ptr, (int64_t)items.size(), c->d_angle_edges.as<float>(),
-                                      c->d_rs_part.as<unsigned>(), S, p.n_a, nb, n_theta));
-        }
-        StageTimer st(c, PSA_T_EPILOGUE);
-        PSA_TRY(launch_hist_reduce(c, c->d_rs_part.as<unsigned>(), rows, S, 1, row, c->d_rs_acc.as<unsigned long long>()));
-    }
-    std::vector<uint64_t> acc((size_t)S * (size_t)row);
-    {
-        StageTimer st(c, PSA_T_D2H);
-        PSA_HIP_CHECK(hipMemcpyAsync(acc.data(), c->d_rs_acc.ptr, acc.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
-    }
+    std::vector<uint64_t> acc;
+    PSA_TRY(shell_run(c, p, sp, idx, box, box_inverse, origin_step, row, 0, [&](const AngleWork& w, int64_t n_items, int64_t, int64_t nb) -> int {
+        return launch_angle_hist(c, w.count, w.list, c->d_rs_items.ptr, n_items, c->d_angle_edges.as<float>(), c->d_rs_part.as<unsigned>(), S,
+                                 p.n_a, nb, n_theta);
+    }, nullptr, &acc));
     for (int a = 0; a < S; ++a) {
         const uint64_t* r = acc.data() + (size_t)a * (size_t)row;
         std::memcpy(angles + (size_t)a * (size_t)P * (size_t)n1, r, (size_t)P * (size_t)n1 * sizeof(uint64_t));
         std::memcpy(coord + (size_t)a * (size_t)S * (size_t)NC, r + (size_t)P * (size_t)n1, (size_t)S * (size_t)NC * sizeof(uint64_t));
         truncated[a] = r[(size_t)row - 1];
+    }
+    return PSA_OK;
+}
+
+// an item's samples of the order pass, 64 centres x the origins of a block x n_l, fit 32 bits whatever the slabs
+static_assert((uint64_t)ANGLE_ITEM_CENTRES * 65535 * ORDER_MAX_LS < (1ull << 32), "an item's samples fit 32 bits");
+
+int order_run(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start, int32_t n_groups,
+              const double* r_cut, int64_t origin_step, const int32_t* ls, int32_t n_ls, int32_t n_q, uint64_t* hist, size_t hist_bytes,
+              uint64_t* truncated, uint64_t* isolated, uint64_t* undefined, int64_t* x, int32_t* n) {
+    PSA_REQUIRE(hist != nullptr && truncated != nullptr && isolated != nullptr && undefined != nullptr, "null output");
+    PSA_REQUIRE(ls != nullptr, "null ls");
+    PSA_REQUIRE(n_ls >= 1 && n_ls <= ORDER_MAX_LS, "the number of orders is in [1, %d], got %d", ORDER_MAX_LS, (int)n_ls);
+    OrderLs o{(int)n_ls, (int)ls[n_ls - 1], 0u};
+    for (int j = 0; j < n_ls; ++j) {
+        PSA_REQUIRE(ls[j] >= 1 && ls[j] <= ORDER_MAX_L, "ls[%d] = %d is outside [1, %d]", j, (int)ls[j], ORDER_MAX_L);
+        PSA_REQUIRE(j == 0 || ls[j] > ls[j - 1], "ls must be strictly ascending: ls[%d] = %d after %d", j, (int)ls[j], (int)ls[j ? j - 1 : 0]);
+        o.mask |= 1u << ls[j];
+    }
+    const int64_t extra = x != nullptr ? 8 * (int64_t)n_ls : 0;
+    AtomGroups    p;
+    AngleSpecies  sp;
+    PSA_TRY(angle_check(c, "psa_bond_order", box, box_inverse, idx, group_start, n_groups, r_cut, &p, &sp, extra));
+    PSA_REQUIRE(origin_step >= 1, "origin_step must be at least 1, got %lld", (long long)origin_step);
+    PSA_REQUIRE(n_q >= 1 && n_q <= ORDER_MAX_BINS, "the number of bins is in [1, %d], got %d", ORDER_MAX_BINS, (int)n_q);
+    const int    S = p.G;
+    const size_t bins = (size_t)n_ls * (size_t)n_q, want = (size_t)S * bins * sizeof(uint64_t);
+    PSA_REQUIRE(hist_bytes == want, "hist_bytes is %zu, the (%d,%d,%d) uint64 result has %zu", hist_bytes, S, (int)n_ls, (int)n_q, want);
+    std::memset(hist, 0, want);
+    for (uint64_t* out : {truncated, isolated, undefined}) std::memset(out, 0, (size_t)S * sizeof(uint64_t));
+    if (p.n_a == 0) return PSA_OK;                           // every species empty: zeros
+    const int64_t         row = order_row_words(n_ls, n_q);
+    std::vector<uint64_t> acc;
+    const ShellPass       order_pass = [&](const AngleWork& w, int64_t n_items, int64_t, int64_t nb) -> int {
+        return launch_order_hist(c, w.count, w.list, c->d_rs_items.ptr, n_items, c->d_rs_part.as<unsigned>(), w.x, o, p.n_a, nb, n_q);
+    };
+    // the block's per-atom rows to the caller's arrays
+    const ShellPass per_atom = [&](const AngleWork& w, int64_t, int64_t k0, int64_t nb) -> int {
+        StageTimer   st(c, PSA_T_D2H);
+        const size_t at = (size_t)k0 * (size_t)p.n_a, cells = (size_t)nb * (size_t)p.n_a;
+        if (x != nullptr)
+            PSA_HIP_CHECK(hipMemcpyAsync(x + at * (size_t)n_ls, w.x, cells * (size_t)n_ls * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        if (n != nullptr) PSA_HIP_CHECK(hipMemcpyAsync(n + at, w.count, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        return PSA_OK;
+    };
+    PSA_TRY(shell_run(c, p, sp, idx, box, box_inverse, origin_step, row, extra, order_pass, x != nullptr || n != nullptr ? per_atom : ShellPass(),
+                      &acc));
+    for (int a = 0; a < S; ++a) {
+        const uint64_t* r = acc.data() + (size_t)a * (size_t)row;
+        std::memcpy(hist + (size_t)a * bins, r, bins * sizeof(uint64_t));
+        truncated[a] = r[bins], isolated[a] = r[bins + 1], undefined[a] = r[bins + 2];
     }
     return PSA_OK;
 }
@@ -201,6 +281,15 @@ int psa_angle_histogram(psa_ctx* c, const double* box, const double* box_inverse
     Guard guard(c);
     return synchronised(c, angle_run(c, box, box_inverse, idx, group_start, n_groups, r_cut, origin_step, n_theta, angles, angles_bytes, coord,
                                      coord_bytes, truncated), "psa_angle_histogram");
+}
+
+int psa_bond_order(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start,
+                   int32_t n_groups, const double* r_cut, int64_t origin_step, const int32_t* ls, int32_t n_ls, int32_t n_q, uint64_t* hist,
+                   size_t hist_bytes, uint64_t* truncated, uint64_t* isolated, uint64_t* undefined, int64_t* x, int32_t* n) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    return synchronised(c, order_run(c, box, box_inverse, idx, group_start, n_groups, r_cut, origin_step, ls, n_ls, n_q, hist, hist_bytes,
+                                     truncated, isolated, undefined, x, n), "psa_bond_order");
 }
 
 int psa_debug_neighbour_lists(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start,

@@ -24,7 +24,7 @@
 //                    (hist_reduce.hip; the device side of the geometry: min_image.h)
 //   api_msd.hip      MSD moments and the self van Hove function from unwrapped displacements
 //   api_pair.hip     g(r), its partials and the distinct van Hove function
-//   api_angle.hip    bond-angle distributions and coordination statistics
+//   api_angle.hip    bond-angle distributions, coordination statistics and the Steinhardt order parameters q_l
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
 // k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
 #pragma once

@@ -345,7 +345,8 @@ struct psa_ctx {
 
     // bond angles and coordination (psa_angle_histogram, psa_debug_neighbour_lists; api_angle.hip): per origin of a block
     // the centred fractional coordinates (3, n_a) float32, the neighbour counts (n_a) int32 and the neighbour lists
-    // (n_a, 64, 4) float32 -- 1040 n_a bytes, held to opt_dynamic_work_bytes; outside it the bin edges.
+    // (n_a, 64, 4) float32 -- 1040 n_a bytes, held to opt_dynamic_work_bytes; outside it the bin edges.  psa_bond_order
+    // uses the same buffer, with its per-atom X (n_a, n_l) int64 behind the counts where the caller asks for them.
     psa::DevBuf  d_angle_work, d_angle_edges;
 
     psa::TimingState timing;
@@ -671,6 +672,25 @@ int launch_angle_neighbours(psa_ctx* c, const float* d_c, int* d_count, void* d_
 // below 2^32 (the caller's rule); d_edges (n_theta + 1) float32; launch_hist_reduce adds them to acc (S, angle_row_words) uint64
 int launch_angle_hist(psa_ctx* c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items, const float* d_edges,
                       unsigned* d_part, int32_t S, int64_t n_a, int64_t n_ob, int32_t n_theta);
+// --- order.hip (psa_bond_order: the Steinhardt order parameters q_l of every atom's neighbour shell from the lists of the
+// neighbour pass above, by the addition theorem; the arithmetic and the tiling are in its header)
+constexpr int ORDER_MAX_L = 12;            // the largest order l
+constexpr int ORDER_MAX_LS = 8;            // most orders of a call
+constexpr int ORDER_MAX_BINS = 1024;       // most bins of a q histogram
+constexpr int ORDER_SHIFT = 24;            // P_l is rounded to a multiple of 2^-24
+// the orders of a call as the kernel takes them: bit l of mask is set for every l asked for (ascending: the j-th set bit
+// is column j)
+struct OrderLs {
+    int n_l, l_max;
+    unsigned mask;
+};
+// columns of a partial row and of a species' accumulator row: n_l n_q bins, then the truncated, the isolated and the
+// undefined centres
+inline int64_t order_row_words(int n_l, int n_q) { return (int64_t)n_l * n_q + 3; }
+// d_count, d_list, d_items as for launch_angle_hist; d_part (n_items, order_row_words) uint32; d_x (n_ob, n_a, n_l) int64 or
+// null: per centre the clamped X_l, -1 where the centre is left out
+int launch_order_hist(psa_ctx* c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items, unsigned* d_part,
+                      long long* d_x, const OrderLs& ls, int64_t n_a, int64_t n_ob, int32_t n_q);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 

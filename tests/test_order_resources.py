@@ -1,0 +1,43 @@
+"""The bond-order kernel (psa_amd/csrc/order.hip) as the compiler builds it for gfx950 (hipcc cross-compiles here), from the
+compiler's resource remarks and the assembly: exactly one kernel, no scratch and no spilled registers, within 128
+registers; no global, flat or buffer atomic, no float LDS atomic, no 64-bit LDS atomic, and the 32-bit integer LDS add that
+counts; the Makefile lists the sources."""
+import re
+
+import pytest
+
+from kernel_build import SRC, device_compile
+
+
+def test_makefile_lists_the_sources():
+    mk = (SRC / "Makefile").read_text()
+    srcs = next(ln for ln in mk.splitlines() if ln.startswith("SRCS"))
+    assert " order.hip" in srcs and " api_angle.hip" in srcs              # the host entry stands beside angle_run
+    assert re.search(r"for f in [^;]*\border\b[^;]*; do", mk)                 # the asm list
+    assert all((SRC / f).is_file() for f in srcs.split(":=")[1].split())
+    assert (SRC / "order.hip").read_text().count("__global__") == 1
+
+
+@pytest.fixture(scope="module")
+def compiled():
+    c = device_compile("order.hip")
+    print(c.usage)
+    return c.usage, c.asm
+
+
+def test_order_kernel_resources(compiled):
+    usage, asm = compiled
+    assert len(usage) == 1 and "order_hist_kernel" in next(iter(usage))
+    u = next(iter(usage.values()))
+    assert u["ScratchSize [bytes/lane]"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, u
+    assert u["VGPRs"] + u["AGPRs"] <= 128, u
+    assert "scratch_" not in asm
+
+
+def test_atomics(compiled):
+    usage, asm = compiled
+    assert "global_atomic" not in asm and "flat_atomic" not in asm and "buffer_atomic" not in asm
+    assert not re.search(r"ds_\w*(add|sub|min|max)\w*_f(16|32|64)|ds_pk_add", asm)   # no float LDS atomic
+    assert "cmpswap" not in asm and "cmpst" not in asm
+    assert asm.count("ds_add_u32") >= 1 and "ds_add_rtn" not in asm and "ds_add_u64" not in asm
+    assert not re.search(r"ds_(add|sub|inc|dec|min|max|and|or|xor)\w*_(u|i|b)64", asm)   # no 64-bit LDS atomic of any kind
