@@ -793,6 +793,16 @@ class Engine:
         keep = ii if ii.size else np.zeros(1, np.int32)
         return inv, n, keep, keep.ctypes.data_as(_i32p), int(ii.size)
 
+    @staticmethod
+    def _bins_args(bin_of, K):
+        """(`bin_of` (K,) int32 or None -- the per-vector form --, its pointer)"""
+        if bin_of is None:
+            return None, None
+        bins = np.ascontiguousarray(bin_of, np.int32).ravel()
+        if bins.size != K:
+            raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
+        return bins, bins.ctypes.data_as(_i32p)
+
     def lattice_spectra(self, box_inverse, indices, bin_of=None, n_bins=0, idx=None, currents: bool = True) -> np.ndarray:
         """Dynamic spectra on the box's reciprocal lattice (psa_lattice_spectra): k = n.G with integer `indices` (K, 3),
         `box_inverse` the float64 inverse of the box matrix (rows = box vectors).  `bin_of` None: per vector, (3, L, K)
@@ -803,12 +813,10 @@ class Engine:
         L = self.segment_length or T
         inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
         K = n.shape[0]
-        bins = None if bin_of is None else np.ascontiguousarray(bin_of, np.int32).ravel()
-        if bins is not None and bins.size != K:
-            raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
+        bins, bp = self._bins_args(bin_of, K)
         out = np.empty((3 if currents else 1, L, K if bins is None else int(n_bins)), np.float32)
         _check(self._lib.psa_lattice_spectra(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
-                                             None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g,
+                                             bp, int(n_bins), ip, n_g,
                                              1 if currents else 0, _f32(out), out.nbytes), "psa_lattice_spectra")
         return out
 
@@ -832,12 +840,10 @@ class Engine:
         L = self.segment_length or T
         inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
         K = n.shape[0]
-        bins = None if bin_of is None else np.ascontiguousarray(bin_of, np.int32).ravel()
-        if bins is not None and bins.size != K:
-            raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
+        bins, bp = self._bins_args(bin_of, K)
         out = np.empty((L, K if bins is None else int(n_bins)), np.float32)
         _check(self._lib.psa_self_spectra(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
-                                          None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g, _f32(out),
+                                          bp, int(n_bins), ip, n_g, _f32(out),
                                           out.nbytes), "psa_self_spectra")
         return out
 
@@ -904,12 +910,10 @@ class Engine:
         inv, n, _, _, _ = self._lattice_args(box_inverse, indices, None)
         idx, off, S = self._species_args(species)
         K = n.shape[0]
-        bins = None if bin_of is None else np.ascontiguousarray(bin_of, np.int32).ravel()
-        if bins is not None and bins.size != K:
-            raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
+        bins, bp = self._bins_args(bin_of, K)
         out = np.empty((3 if currents else 1, S * (S + 1) // 2, L, K if bins is None else int(n_bins)), np.float32)
         _check(self._lib.psa_partial_spectra(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
-                                             None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins),
+                                             bp, int(n_bins),
                                              idx.ctypes.data_as(_i32p), off.ctypes.data_as(_i64p), S, 1 if currents else 0,
                                              _f32(out), out.nbytes), "psa_partial_spectra")
         return out
@@ -974,12 +978,10 @@ class Engine:
         `lattice_spectra`."""
         inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
         K = n.shape[0]
-        bins = None if bin_of is None else np.ascontiguousarray(bin_of, np.int32).ravel()
-        if bins is not None and bins.size != K:
-            raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
+        bins, bp = self._bins_args(bin_of, K)
         out = np.empty((3 if currents else 1, max(int(n_lags), 0), K if bins is None else int(n_bins)), np.float32)
         _check(self._lib.psa_lattice_correlations(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
-                                                  None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g,
+                                                  bp, int(n_bins), ip, n_g,
                                                   1 if currents else 0, int(n_lags), _f32(out), out.nbytes),
                "psa_lattice_correlations")
         return out
@@ -990,12 +992,10 @@ class Engine:
         form, (n_lags, n_bins).  Everything else as for `self_spectra`."""
         inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
         K = n.shape[0]
-        bins = None if bin_of is None else np.ascontiguousarray(bin_of, np.int32).ravel()
-        if bins is not None and bins.size != K:
-            raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
+        bins, bp = self._bins_args(bin_of, K)
         out = np.empty((max(int(n_lags), 0), K if bins is None else int(n_bins)), np.float32)
         _check(self._lib.psa_self_correlations(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
-                                               None if bins is None else bins.ctypes.data_as(_i32p), int(n_bins), ip, n_g,
+                                               bp, int(n_bins), ip, n_g,
                                                int(n_lags), _f32(out), out.nbytes), "psa_self_correlations")
         return out
 

@@ -277,12 +277,9 @@ int psa_destroy(psa_ctx* c) {
                           &c->d_qrows, &c->d_stage, &c->d_bin, &c->d_upload_max, &c->d_zeros, &c->d_kmap, &c->d_cols, &c->d_inten,
                           &c->d_vdos_work, &c->d_vdos_pairs, &c->d_vdos_off, &c->d_vdos_mean, &c->d_vdos_part, &c->d_vdos_acc,
                           &c->d_vdos_out, &c->d_modes_work, &c->d_modes_coef, &c->d_modes_out, &c->d_cov_slab, &c->d_cov_g, &c->d_cov_out, &c->d_peaks_spec, &c->d_peaks_bands,
-                          &c->d_peaks_part, &c->d_peaks_fit, &c->d_peaks_info, &c->d_dyn_q, &c->d_dyn_kappa, &c->d_dyn_khat, &c->d_dyn_idx,
-                          &c->d_dyn_out, &c->d_lat_q, &c->d_lat_tiles, &c->d_lat_ent, &c->d_lat_slot, &c->d_lat_dest, &c->d_lat_khat,
-                          &c->d_lat_idx, &c->d_lat_bins, &c->d_lat_scale, &c->d_lat_acc, &c->d_lat_out, &c->d_self_work, &c->d_self_tiles,
-                          &c->d_self_ent, &c->d_self_slot, &c->d_self_idx, &c->d_self_groups, &c->d_self_scale, &c->d_self_part, &c->d_self_acc,
-                          &c->d_self_out, &c->d_par_q, &c->d_par_tiles, &c->d_par_ent, &c->d_par_slot, &c->d_par_dest, &c->d_par_khat,
-                          &c->d_par_idx, &c->d_par_bins, &c->d_par_scale, &c->d_par_acc, &c->d_par_out, &c->d_corr_tab, &c->d_corr_factor,
+                          &c->d_peaks_part, &c->d_peaks_fit, &c->d_peaks_info, &c->d_rc_work, &c->d_rc_kappa, &c->d_rc_khat, &c->d_rc_idx,
+                          &c->d_rc_tiles, &c->d_rc_ent, &c->d_rc_slot, &c->d_rc_dest, &c->d_rc_bins, &c->d_rc_scale, &c->d_rc_acc,
+                          &c->d_rc_out, &c->d_rc_groups, &c->d_rc_part, &c->d_corr_tab, &c->d_corr_factor,
                           &c->d_corr_scale, &c->d_corr_in, &c->d_corr_out, &c->d_rs_idx, &c->d_rs_items, &c->d_rs_part, &c->d_rs_acc, &c->d_msd_u,
                           &c->d_msd_img, &c->d_msd_sums, &c->d_msd_offs, &c->d_msd_sizes, &c->d_msd_lags, &c->d_msd_out, &c->d_pair_c,
                           &c->d_angle_work, &c->d_angle_edges})

@@ -1,8 +1,9 @@
 // psa_lattice_correlations, psa_self_correlations: the intermediate scattering function F(k,t), its self part F_s(k,t) and
 // the current correlations C_L(k,t), C_T(k,t) on the reciprocal lattice of the box, per vector or averaged over shells of
 // |k| (definition: include/psa_hip.h; kernels: correlation.hip).  Each is its spectral twin's call -- psa_lattice_spectra
-// (api_lattice.hip), psa_self_spectra (api_self.hip): the same checks, plan, projection or series kernel, rocFFT and power
-// passes, through the same helpers -- with three differences:
+// (api_lattice.hip) through the one run body (api_reciprocal.hip: spectra_run with n_lags set), psa_self_spectra
+// (api_self.hip) through the same helpers: the same checks, plan, projection or series kernel, rocFFT and power passes --
+// with three differences, of which this file adds the last:
 //   the rows    every segment is zero-padded to P = the smallest power of two >= L + n_lags - 1 frames before its FFT
 //               (correlation_length); the budget rules count P where the spectra count L;
 //   the power   is left unscaled where it is summed: the per-vector pass's float32 (1 or 3, P, K) with the scale 1, the
@@ -63,53 +64,22 @@ int lattice_correlations_run(psa_ctx* c, const double* box_inverse, const int32_
     LatCall p;
     PSA_TRY(lattice_check(c, "psa_lattice_correlations", box_inverse, indices, K, bin_of, n_bins, idx, n_g, currents, n_lags, &p));
     const DynCall& d = p.d;
-    const int64_t  L = d.L, P = d.P, T = d.T, rows = currents ? 3 : 1, cols = p.shell ? n_bins : K;
-    const size_t   want = (size_t)rows * (size_t)n_lags * (size_t)cols * sizeof(float);
-    PSA_REQUIRE(out_bytes == want, "out_bytes is %zu, the (%lld,%lld,%lld) float32 result has %zu", out_bytes, (long long)rows,
-                (long long)n_lags, (long long)cols, want);
-    if (d.n_g == 0) {                                        // an empty atom set: zeros
-        std::memset(out_host, 0, out_bytes);
-        return PSA_OK;
-    }
-    PSA_TRY(lattice_upload(c, p, idx));
-    PSA_TRY(c->d_lat_q.reserve((size_t)d.kb * (size_t)d.per_k));
-    PSA_TRY(c->d_seg.reserve((size_t)d.bk * (size_t)d.bs * (size_t)d.unit));
-    const size_t power = (size_t)rows * (size_t)P * (size_t)cols;
-    double*      d_acc = nullptr;
-    if (p.shell) PSA_TRY(lattice_shell_begin(c, power * sizeof(double), &d_acc));
-    else PSA_TRY(c->d_lat_out.reserve(power * sizeof(float)));
-
-    float2*   d_q = c->d_lat_q.as<float2>();
-    float2*   d_seg = c->d_seg.as<float2>();
-    PowerPass pass;
-    pass.NC = d.NC, pass.L = P, pass.n_seg = d.n_seg, pass.K = K, pass.scale = 1.f;
-    pass.d_khat = c->d_lat_khat.as<float>(), pass.d_out = c->d_lat_out.as<float>();
-    if (p.shell) pass.d_bins = c->d_lat_bins.as<int>(), pass.d_acc = d_acc, pass.n_bins = n_bins;
-    int64_t   block = 0;
-    for (int64_t k0 = 0; k0 < K; k0 += d.kb, ++block) {
-        const int64_t nk = std::min(d.kb, K - k0);
-        PSA_TRY(lattice_project(c, p, idx, block, d_q));
-        PSA_TRY(power_block(c, pass, k0, nk, d.bk, d.bs, [&](int64_t k1, int64_t nb, int64_t s0, int64_t ns, const float2** where) -> int {
-            {
-                StageTimer st(c, PSA_T_GATHER);
-                PSA_TRY(launch_correlation_pad(c, d_q + (size_t)k1 * (size_t)d.NC * (size_t)T, d_seg, T, L, P, d.H, s0, ns, nb * d.NC));
-            }
-            StageTimer st(c, PSA_T_FFT);
-            PSA_TRY(run_fft(c, d_seg, P, (int64_t)d.NC * nb * ns));
-            *where = d_seg;
-            return PSA_OK;
-        }));
-    }
-    if (p.shell) {
-        // the shell pass adds X_n[o] + X_n[(P - o) mod P] of a bin's n_half vectors: the mean over the full sphere
-        std::vector<double> col_scale((size_t)n_bins, 0.0);
-        for (int64_t b = 0; b < n_bins; ++b)
-            if (p.count[(size_t)b]) col_scale[(size_t)b] = 1.0 / (2.0 * (double)p.count[(size_t)b]);
-        PSA_TRY(correlation_finish(c, d_acc, rows, P, cols, L, d.n_seg, n_lags, col_scale.data()));
-    } else {
-        PSA_TRY(correlation_finish(c, c->d_lat_out.as<float>(), rows, P, cols, L, d.n_seg, n_lags, nullptr));
-    }
-    return correlation_fetch(c, out_host, want);
+    const int64_t  rows = currents ? 3 : 1, cols = p.shell ? n_bins : K;
+    SpectraRun     a;
+    a.src = lattice_source(c, p, idx), a.n_bins = p.n_bins, a.out_host = out_host, a.out_bytes = out_bytes;
+    a.finish = [&](const float* d_power, const double* d_acc) -> int {
+        if (p.shell) {
+            // the shell pass adds X_n[o] + X_n[(P - o) mod P] of a bin's n_half vectors: the mean over the full sphere
+            std::vector<double> col_scale((size_t)n_bins, 0.0);
+            for (int64_t b = 0; b < n_bins; ++b)
+                if (p.count[(size_t)b]) col_scale[(size_t)b] = 1.0 / (2.0 * (double)p.count[(size_t)b]);
+            PSA_TRY(correlation_finish(c, d_acc, rows, d.P, cols, d.L, d.n_seg, n_lags, col_scale.data()));
+        } else {
+            PSA_TRY(correlation_finish(c, d_power, rows, d.P, cols, d.L, d.n_seg, n_lags, nullptr));
+        }
+        return correlation_fetch(c, out_host, out_bytes);
+    };
+    return spectra_run(c, d, a);
 }
 
 int self_correlations_run(psa_ctx* c, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t n_bins,
@@ -118,7 +88,7 @@ int self_correlations_run(psa_ctx* c, const double* box_inverse, const int32_t* 
     PSA_REQUIRE(n_lags >= 1, "n_lags = %lld: at least one lag (1 <= n_lags <= L)", (long long)n_lags);
     SelfCall p;
     PSA_TRY(self_check(c, "psa_self_correlations", box_inverse, indices, K, bin_of, n_bins, idx, n_g, true, n_lags, &p));
-    const int64_t L = p.L, P = p.P, cols = p.cols;
+    const int64_t L = p.d.L, P = p.d.P, cols = p.cols;
     const size_t  want = (size_t)n_lags * (size_t)cols * sizeof(float);
     PSA_REQUIRE(out_bytes == want, "out_bytes is %zu, the (%lld,%lld) float32 result has %zu", out_bytes, (long long)n_lags,
                 (long long)cols, want);
@@ -127,21 +97,17 @@ int self_correlations_run(psa_ctx* c, const double* box_inverse, const int32_t* 
         return PSA_OK;
     }
     PSA_TRY(self_upload(c, p, idx, true));
-    const int64_t Ab = p.at * SELF_ATOMS, nv_max = std::min(K, p.vt * p.kt_max);
-    PSA_TRY(c->d_self_work.reserve((size_t)std::min(Ab, p.d.n_g) * (size_t)nv_max * (size_t)p.bs * (size_t)P * sizeof(float2)));
-    float2* d_work = c->d_self_work.as<float2>();
-    std::vector<int64_t> vcut;                               // a vector block is a run of vt tiles
-    for (int64_t t0 = 0; t0 < p.n_tiles; t0 += p.vt) vcut.push_back(p.tile[(size_t)(2 * t0 + 1)]);
-    vcut.push_back(K);
-    SelfPower w;
-    w.L = P, w.n_seg = p.n_seg, w.n_atoms = p.d.n_g, w.cols = cols, w.n_groups = p.n_groups, w.groups = p.groups.data();
-    w.mirror = false, w.finish = false, w.Ab = Ab, w.bs = p.bs, w.vcut = &vcut;
+    std::vector<int64_t> vcut;
+    SelfPower            w;
+    PSA_TRY(self_blocks(c, p, &vcut, &w));
+    w.mirror = false, w.finish = false;
+    float2* d_work = c->d_rc_work.as<float2>();
     PSA_TRY(self_power_run(c, w, [&](int64_t a0, int64_t na, int64_t vb, int64_t s0, int64_t ns, const float2** where) -> int {
         const int64_t t0 = vb * p.vt, nt = std::min(p.vt, p.n_tiles - t0), nv = vcut[(size_t)vb + 1] - vcut[(size_t)vb];
         PSA_TRY(self_series(c, p, idx, a0, na, t0, nt, s0, ns, d_work));          // the heads, rows of pitch P
         {
             StageTimer st(c, PSA_T_GATHER);
-            PSA_TRY(launch_correlation_pad(c, nullptr, d_work, p.d.T, L, P, p.H, s0, ns, na * nv));   // the tails
+            PSA_TRY(launch_correlation_pad(c, nullptr, d_work, p.d.T, L, P, p.d.H, s0, ns, na * nv));   // the tails
         }
         StageTimer st(c, PSA_T_FFT);
         PSA_TRY(run_fft(c, d_work, P, na * nv * ns));
@@ -154,7 +120,7 @@ int self_correlations_run(psa_ctx* c, const double* box_inverse, const int32_t* 
         for (int64_t b = 0; b < n_bins; ++b)
             if (p.count[(size_t)b]) col_scale[(size_t)b] = 1.0 / (double)p.count[(size_t)b];
     }
-    PSA_TRY(correlation_finish(c, c->d_self_acc.as<double>(), 1, P, cols, L, p.n_seg, n_lags, p.shell ? col_scale.data() : nullptr));
+    PSA_TRY(correlation_finish(c, c->d_rc_acc.as<double>(), 1, P, cols, L, p.d.n_seg, n_lags, p.shell ? col_scale.data() : nullptr));
     return correlation_fetch(c, out_host, want);
 }
 

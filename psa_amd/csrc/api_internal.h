@@ -13,6 +13,8 @@
 //                    the Welch segment average between projection and contraction
 //   api_covariance.hip  the spectral covariance of the B site groups' spectra: the frequency-weighted sum of their outer products
 //   api_peaks.hip    Lorentzian peak fits of spectrum columns: an uploaded spectrum, or the mode spectra where they lie
+//   api_reciprocal.hip  what the reciprocal-space entries below share: segments and block rule, the one run body
+//                    (projection, window or padding, rocFFT, power pass, finish), the debug loops, bins, the shell pair
 //   api_dynamic.hip  the dynamic structure factor and the current correlations: the phase of every frame's own positions
 //   api_lattice.hip  the same spectra on the box's reciprocal lattice, per vector or averaged over shells of |k|
 //   api_self.hip     the self (incoherent) part on that lattice: per-atom series, their power summed over the atoms
@@ -227,8 +229,10 @@ struct PeakArgs {
 };
 int check_peak_args(const psa_peak_opts* opts, PeakArgs* a);
 int peaks_run(psa_ctx* c, const float* d_spec, const PeakArgs& a);
-// api_dynamic.hip: the shape of a psa_dynamic_spectra call, shared with psa_lattice_spectra (api_lattice.hip): the checks
-// of the slots, the atom set and the weights, then the context's segments and the block rule of the budget
+// ---- api_reciprocal.hip: what the reciprocal-space entries (api_dynamic.hip, api_lattice.hip, api_partial.hip, api_self.hip,
+// api_correlation.hip) share.  Their device buffers are the one set d_rc_* (psa_ctx.h).
+// The shape of such a call: the checks of the slots, the atom set and the weights (dynamic_inputs), the context's segments
+// (segment_shape), the block rule of the budget (dynamic_plan)
 struct DynCall {
     int64_t T = 0, N = 0, K = 0, n_g = 0;
     int     NC = 1, slices = 1;
@@ -242,14 +246,15 @@ struct DynCall {
     std::vector<float> kappa, khat;      // (K, 6) k / 2 pi as hi xyz, lo xyz; (K, 3) k / |k|
 };
 int dynamic_inputs(psa_ctx* c, const char* entry, int64_t K, const int32_t* idx, int64_t n_g, int32_t currents, DynCall* d);
+// cut, L, H, n_seg and P of a call over d->T frames with d->n_lags lags; `segments` false: one boxcar segment of T frames,
+// whatever the context holds
+int segment_shape(const psa_ctx* c, bool segments, DynCall* d);
 int dynamic_plan(psa_ctx* c, DynCall* d);
-int correlation_length(const psa_ctx* c, bool cut, int64_t L, int64_t n_lags, int64_t* P);
-// The power part of a dynamic or lattice call, shared by the run and by the debug entries (psa_debug_dynamic_power,
-// psa_debug_lattice_shell), which differ only in where the transformed segments come from.  PowerPass: what every launch of
-// the pass gets; d_bins set: the shell pass into d_acc, else dynamic.hip's power pass into d_out; n_species > 0: the pair
-// passes of partial.hip (psa_partial_spectra, psa_debug_partial_power) on (nb, n_species, NC, ns, L).  power_block: vectors
-// [k0, k0 + nk) of the processing order in sub-blocks of bk vectors x bs segments; `fill` leaves the transformed segments
-// (nb, NC, ns, L) of vectors k0 + k1 .. and segments s0 .. on the device and says where.
+// The power part of a call, shared by the run and by the debug power entries, which differ only in where the transformed
+// segments come from.  PowerPass: what every launch of the pass gets; d_bins set: the shell pass into d_acc, else
+// dynamic.hip's power pass into d_out; n_species > 0: the pair passes of partial.hip on (nb, n_species, NC, ns, L).
+// power_block: vectors [k0, k0 + nk) of the processing order in sub-blocks of bk vectors x bs segments; `fill` leaves the
+// transformed segments (nb, NC, ns, L) of vectors k0 + k1 .. and segments s0 .. on the device and says where.
 struct PowerPass {
     int          NC = 1;
     int          n_species = 0;          // 0: one series set per vector, moduli; else that many, products of pairs
@@ -263,46 +268,103 @@ struct PowerPass {
 };
 using SegFill = std::function<int(int64_t k1, int64_t nb, int64_t s0, int64_t ns, const float2** d_seg)>;
 int  power_block(psa_ctx* c, const PowerPass& p, int64_t k0, int64_t nk, int64_t bk, int64_t bs, const SegFill& fill);
+// How a family fills q: the call's uploads (booked under PSA_T_H2D by the family), and block `block` of the call --
+// vectors [k0, k0 + nk) of the processing order -- over all frames into d_q (nk, n_species NC, T)
+struct BlockSource {
+    std::function<int()>                                                     upload;
+    std::function<int(int64_t block, int64_t k0, int64_t nk, float2* d_q)> project;
+};
+// The one run body of psa_dynamic_spectra, psa_lattice_spectra, psa_partial_spectra and psa_lattice_correlations after
+// their checks (d planned): the out_bytes refusal, zeros for an empty atom set, the uploads and reservations, per block the
+// projection, then per sub-block the window (with segments; else q in place) or -- d.n_lags set -- the zero-padding to
+// d.P frames, the rocFFT and the power pass; at the end the shell form's finish pass and the copy home, or `finish`.
+struct SpectraRun {
+    BlockSource src;
+    bool        pairs = false;           // products of pairs of the d.n_species species (partial.hip) where else moduli
+    int64_t     n_bins = 0;              // > 0: the shell form
+    // set: what ends a time-correlation call, handed the unscaled power where it lies (float32 per vector, float64 per shell)
+    std::function<int(const float* d_power, const double* d_acc)> finish;
+    float*      out_host = nullptr;
+    size_t      out_bytes = 0;
+};
+int spectra_run(psa_ctx* c, const DynCall& d, const SpectraRun& a);
+// the projection alone, block by block under the same rule: q (K, n_species NC, T) before any FFT
+int debug_project_run(psa_ctx* c, const DynCall& d, const BlockSource& src, void* out_host);
+// The power pass alone on transformed segments (K, series, n_seg, L) of the caller's, cut into sub-blocks of k_block
+// vectors x seg_block segments (0: all): psa_debug_dynamic_power, psa_debug_lattice_shell, psa_debug_partial_power.
+// bin_of null: the per-vector form with `scale`; else the shell form, the vectors sorted by bin, with the bins' scales
+// 1 / (2 n_b norm).  debug_power_check: the refusals they share, and bk, bs; debug_power_run: the rest, with k / |k| in the
+// order of the vectors (read with currents only)
+struct DebugPower {
+    const void*    seg_host = nullptr;
+    const int32_t* bin_of = nullptr;
+    int64_t        K = 0, n_bins = 0;
+    int            n_species = 0;        // as PowerPass
+    int32_t        currents = 0;
+    int64_t        n_seg = 0, L = 0, k_block = 0, seg_block = 0;
+    double         norm = 1.0;
+    float          scale = 0.f;
+    float*         out_host = nullptr;
+    int64_t        bk = 0, bs = 0;
+};
+int debug_power_check(DebugPower* a);
+int debug_power_run(psa_ctx* c, const DebugPower& a, const float* khat);
 // rows [r0, r0 + nr) x segments [s0, s0 + ns) of host segments (rows, n_seg, L), packed as (nr, ns, L) and uploaded to b
 int  upload_segments(psa_ctx* c, DevBuf& b, const void* host, int64_t r0, int64_t nr, int64_t n_seg, int64_t s0, int64_t ns, int64_t L);
-// api_lattice.hip: what psa_lattice_spectra shares with psa_self_spectra (api_self.hip): the refusals that concern the box
-// and the vector list; Hinv as float32 hi + lo; the processing order (bin_of: by (bin, n); else every run of kb vectors by n);
-// one tile's entry list (appended to ent) and per vector the three entries it reads -- returns the tile's R
-int  lattice_inputs(const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t n_bins);
-void lattice_box_parts(const double* B, float* hi, float* lo);
-void lattice_order(const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t kb, std::vector<int64_t>* order);
-int  lattice_tile_entries(const int32_t* indices, const int64_t* members, int64_t nt, std::vector<uint16_t>* ent, uint32_t* slot);
+// vectors per bin; the same of a list that comes sorted by bin, with the refusals of such a list
+void bin_counts(const int32_t* bin_of, int64_t K, int64_t n_bins, std::vector<int64_t>* count);
+int  sorted_bin_counts(const int32_t* bin_of, int64_t K, int64_t n_bins, std::vector<int64_t>* count);
 // where each bin's vectors begin in an order sorted by bin (n_bins + 1) and the bins' scales 1 / (2 n_half n_seg U L^2), an
 // empty bin: 0 (count: vectors per bin)
 void lattice_bins(const std::vector<int64_t>& count, double n_seg, double U, double L, std::vector<int32_t>* bin_start,
                   std::vector<double>* scale);
-// a psa_lattice_spectra call and its pieces, shared with psa_lattice_correlations (api_correlation.hip; n_lags > 0: its
-// padded plan): every refusal, the plan and the block rule; the plan's uploads; the shell form's float64 accumulator,
-// zeroed; block b of the plan over all frames into d_q (nk, NC, T)
+// the shell form's float64 accumulator d_rc_acc, zeroed; its last launch: the n sums times the bins' scales (d_rc_scale)
+// in float64, one rounding into d_out
+int  shell_begin(psa_ctx* c, size_t bytes, double** d_acc);
+int  shell_finish(psa_ctx* c, int64_t n, int64_t n_bins, float* d_out);
+
+// api_lattice.hip: what the lattice families share: the refusals that concern the box and the vector list; Hinv as float32
+// hi + lo; the processing order (bin_of: by (bin, n); else every run of kb vectors by n); one tile's entry list (appended to
+// ent) and per vector the three entries it reads -- returns the tile's R
+int  lattice_inputs(const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t n_bins);
+void lattice_box_parts(const double* B, float* hi, float* lo);
+void lattice_order(const int32_t* indices, int64_t K, const int32_t* bin_of, int64_t kb, std::vector<int64_t>* order);
+int  lattice_tile_entries(const int32_t* indices, const int64_t* members, int64_t nt, std::vector<uint16_t>* ent, uint32_t* slot);
+// a psa_lattice_spectra call and its pieces, shared with psa_partial_spectra (api_partial.hip) and psa_lattice_correlations
+// (api_correlation.hip; n_lags > 0: its padded plan)
 struct LatCall {
     DynCall  d;                                      // sizes, segments, block rule (kappa unused; khat in row order)
     bool     shell = false;
     int64_t  n_bins = 0;
     float    box_hi[9], box_lo[9];
     std::vector<int64_t>  block_tile0;               // first tile of block b (n_blocks + 1)
-    std::vector<int32_t>  tile_off, dest;            // (n_tiles + 1); (n_tiles LAT_KS)
+    std::vector<int32_t>  tile_off, dest;            // (n_tiles + 1); (n_tiles LAT_KS): a vector's row of q, or -1
     std::vector<uint16_t> ent;
     std::vector<uint32_t> slot;                      // (n_tiles LAT_KS)
     std::vector<int64_t>  count;                     // (n_bins) vectors per bin
     std::vector<int32_t>  bin_start;                 // (n_bins + 1) in the processing order
     std::vector<double>   scale;                     // (n_bins) 1 / (2 n_half n_seg U L^2); an empty bin: 0
 };
+// the plan of a call whose d is planned: box parts, the processing order, k / |k| in row order, blocks, tiles, entries and
+// the row table -- it holds row_mult x a vector's row: 1, or the species of a partial call --, the bins' counts, offsets
+// and scales
+int lattice_plan(const psa_ctx* c, const double* box_inverse, const int32_t* indices, const int32_t* bin_of, int64_t n_bins,
+                 int64_t row_mult, LatCall* p);
+// every refusal of a lattice call, the block rule and the plan
 int lattice_check(psa_ctx* c, const char* entry, const double* box_inverse, const int32_t* indices, int64_t K, const int32_t* bin_of,
                   int64_t n_bins, const int32_t* idx, int64_t n_g, int32_t currents, int64_t n_lags, LatCall* p);
+// the plan's uploads (idx null: no atom list)
 int lattice_upload(psa_ctx* c, const LatCall& p, const int32_t* idx);
-int lattice_shell_begin(psa_ctx* c, size_t bytes, double** d_acc);
-int lattice_project(psa_ctx* c, const LatCall& p, const int32_t* idx, int64_t block, float2* d_q);
+// block b of the plan over all frames into d_q, for one species: the atoms [a0, a0 + n_g) of the uploaded list (`listed`
+// false: all atoms in order); an empty species still gets its launch, which writes its zeros
+int lattice_project(psa_ctx* c, const LatCall& p, bool listed, int64_t a0, int64_t n_g, int64_t block, float2* d_q);
+// the one-species source (p and idx outlive it)
+BlockSource lattice_source(psa_ctx* c, const LatCall& p, const int32_t* idx);
 // api_self.hip: a psa_self_spectra call and its pieces, shared with psa_self_correlations in the same way
 struct SelfCall {
-    DynCall  d;                                      // T, N, K, n_g (the rest unused)
-    bool     cut = false, shell = false;
-    int64_t  L = 0, H = 0, n_seg = 0, cols = 0;
-    int64_t  P = 0;                                  // the rows of the work buffer and the FFT: L, or the padded length
+    DynCall  d;                                      // T, N, K, n_g; cut, L, H, n_seg, P (the rest unused)
+    bool     shell = false;
+    int64_t  cols = 0;
     float    box_hi[9], box_lo[9];
     std::vector<int64_t>  order;                     // the processing order: places in the caller's list
     std::vector<int32_t>  tile;                      // (2 (n_tiles + 1)): per tile its offset into ent, its first vector
@@ -325,7 +387,7 @@ int self_series(psa_ctx* c, const SelfCall& p, const int32_t* idx, int64_t a0, i
 // The power part of a self call, shared by self_run, psa_debug_self_power and psa_self_correlations, which differ only in
 // where the transformed series come from: the float64 accumulator (L, cols), zeroed; per block of Ab atoms x the vectors
 // [vcut[b], vcut[b + 1]) of the processing order x bs segments the columns the block touches, the chunk rule, the power and
-// reduce launches; with `finish` the finish pass into d_self_out (else the sums stay in d_self_acc).  The groups table
+// reduce launches; with `finish` the finish pass into d_rc_out (else the sums stay in d_rc_acc).  The groups table
 // (2 (n_groups + 1)) and the columns' scales are on the device already.  `fill` leaves the transformed block
 // (na, nv, ns, L) on the device and says where.
 struct SelfPower {
@@ -337,6 +399,9 @@ struct SelfPower {
 };
 using SelfFill = std::function<int(int64_t a0, int64_t na, int64_t vb, int64_t s0, int64_t ns, const float2** d_work)>;
 int self_power_run(psa_ctx* c, const SelfPower& w, const SelfFill& fill);
+// the blocks of a checked call, for self_run and psa_self_correlations: the vector blocks (runs of vt tiles) into vcut, the
+// work buffer of one block with rows of d.P frames reserved, and everything of w but mirror and finish
+int self_blocks(psa_ctx* c, const SelfCall& p, std::vector<int64_t>* vcut, SelfPower* w);
 
 // ---- api_realspace.hip: what the real-space entries (api_msd.hip, api_pair.hip, api_angle.hip) share.
 // The atom groups (species) of a real-space call

@@ -10,10 +10,11 @@
 // vector the three entries it reads (lattice_tile_entries, shared with api_lattice.hip).  A column of the result is a
 // "group" of consecutive vectors of that order: one vector and its place in the caller's list, or a shell.
 //
-// Budget (PSA_OPT_DYNAMIC_WORK_BYTES = W; the accumulator, the partial sums and the result are outside, like d_dyn_out).
+// Budget (PSA_OPT_DYNAMIC_WORK_BYTES = W; the accumulator, the partial sums and the result are outside).
 // A block is a whole number of atom tiles x vector tiles x segments and is counted in units of SELF_ATOMS atoms x the
 // largest tile's vectors x one segment, 8 L bytes per series: segments shrink first, then vector tiles, then atom tiles,
-// and a budget below one unit is refused.
+// and a budget below one unit is refused.  Shared with the other reciprocal-space entries (api_reciprocal.hip): the checks of
+// the slots and the atom set, the segments (segment_shape), the bins and the buffer set d_rc_*.
 #include "api_internal.h"
 
 namespace psa {
@@ -26,14 +27,10 @@ int self_check(psa_ctx* c, const char* entry, const double* box_inverse, const i
     PSA_TRY(dynamic_inputs(c, entry, K, idx, n_g, 0, &d));
     PSA_TRY(lattice_inputs(box_inverse, indices, K, bin_of, n_bins));
     PSA_REQUIRE(K < (1ll << 30), "too many vectors (%lld)", (long long)K);
-    const int64_t T = d.T;
     p->shell = bin_of != nullptr;
     p->cols = p->shell ? n_bins : K;
-    p->cut = segments && c->seg_L != 0;
-    p->L = p->cut ? c->seg_L : T, p->H = p->cut ? c->seg_hop : T;
-    PSA_REQUIRE(p->L <= T, "segment length %lld exceeds the trajectory's %lld frames", (long long)p->L, (long long)T);
-    p->n_seg = 1 + (T - p->L) / p->H;
-    PSA_TRY(correlation_length(c, p->cut, p->L, n_lags, &p->P));
+    d.n_lags = n_lags;
+    PSA_TRY(segment_shape(c, segments, &d));
     lattice_box_parts(box_inverse, p->box_hi, p->box_lo);
     lattice_order(indices, K, bin_of, K, &p->order);
 
@@ -61,17 +58,14 @@ int self_check(psa_ctx* c, const char* entry, const double* box_inverse, const i
     p->n_tiles = (int64_t)p->tile.size() / 2 - 1;
 
     // columns
-    const double U = p->cut ? c->seg_U : 1.0, norm = (double)p->n_seg * U * (double)p->L * (double)p->L;
+    const double U = d.cut ? c->seg_U : 1.0, norm = (double)d.n_seg * U * (double)d.L * (double)d.L;
     if (p->shell) {
-        std::vector<int64_t>& count = p->count;
-        count.assign((size_t)n_bins, 0);
-        for (int64_t k = 0; k < K; ++k) ++count[(size_t)bin_of[k]];
-        p->scale.assign((size_t)n_bins, 0.0);
-        int64_t first = 0;
-        for (int64_t b = 0; b < n_bins; first += count[(size_t)b], ++b) {
-            p->groups.push_back((int32_t)first);
+        std::vector<int32_t> bin_start;
+        bin_counts(bin_of, K, n_bins, &p->count);
+        lattice_bins(p->count, norm, 1.0, 1.0, &bin_start, &p->scale);   // 1 / (2 n_half norm)
+        for (int64_t b = 0; b < n_bins; ++b) {
+            p->groups.push_back(bin_start[(size_t)b]);
             p->groups.push_back((int32_t)b);
-            if (count[(size_t)b]) p->scale[(size_t)b] = 1.0 / (2.0 * (double)count[(size_t)b] * norm);
         }
     } else {
         p->scale.assign((size_t)K, 1.0 / norm);
@@ -86,15 +80,15 @@ int self_check(psa_ctx* c, const char* entry, const double* box_inverse, const i
 
     // the block rule
     const int64_t W = c->opt_dynamic_work_bytes;
-    const int64_t unit = (int64_t)SELF_ATOMS * p->kt_max * p->P * (int64_t)sizeof(float2);
+    const int64_t unit = (int64_t)SELF_ATOMS * p->kt_max * d.P * (int64_t)sizeof(float2);
     const int64_t units = W / unit;
     PSA_REQUIRE(units >= 1, "the work budget of %lld bytes (PSA_OPT_DYNAMIC_WORK_BYTES) cannot hold the smallest block: %d atoms x "
                 "%lld vectors x one segment of %lld frames need %lld bytes", (long long)W, SELF_ATOMS, (long long)p->kt_max,
-                (long long)p->P, (long long)unit);
+                (long long)d.P, (long long)unit);
     const int64_t n_at = (d.n_g + SELF_ATOMS - 1) / SELF_ATOMS;
     p->at = std::max<int64_t>(1, std::min<int64_t>({n_at, units, 65535}));
     p->vt = std::min<int64_t>({p->n_tiles, units / p->at, 65535});
-    p->bs = std::min<int64_t>(p->n_seg, units / (p->at * p->vt));
+    p->bs = std::min<int64_t>(d.n_seg, units / (p->at * p->vt));
     // (the batch of the FFT and the rows of the passes in 31 bits)
     const int64_t series = p->at * SELF_ATOMS * std::min(K, p->vt * p->kt_max);
     PSA_REQUIRE(series < (1ll << 31), "a block of %lld series is too large: lower PSA_OPT_DYNAMIC_WORK_BYTES", (long long)series);
@@ -104,13 +98,13 @@ int self_check(psa_ctx* c, const char* entry, const double* box_inverse, const i
 
 int self_upload(psa_ctx* c, const SelfCall& p, const int32_t* idx, bool columns) {
     StageTimer st(c, PSA_T_H2D);
-    PSA_TRY(upload(c, c->d_self_tiles, p.tile.data(), p.tile.size() * sizeof(int32_t)));
-    PSA_TRY(upload(c, c->d_self_ent, p.ent.data(), p.ent.size() * sizeof(uint16_t)));
-    PSA_TRY(upload(c, c->d_self_slot, p.slot.data(), p.slot.size() * sizeof(uint32_t)));
-    if (idx) PSA_TRY(upload(c, c->d_self_idx, idx, (size_t)p.d.n_g * sizeof(int32_t)));
+    PSA_TRY(upload(c, c->d_rc_tiles, p.tile.data(), p.tile.size() * sizeof(int32_t)));
+    PSA_TRY(upload(c, c->d_rc_ent, p.ent.data(), p.ent.size() * sizeof(uint16_t)));
+    PSA_TRY(upload(c, c->d_rc_slot, p.slot.data(), p.slot.size() * sizeof(uint32_t)));
+    if (idx) PSA_TRY(upload(c, c->d_rc_idx, idx, (size_t)p.d.n_g * sizeof(int32_t)));
     if (columns) {
-        PSA_TRY(upload(c, c->d_self_groups, p.groups.data(), p.groups.size() * sizeof(int32_t)));
-        PSA_TRY(upload(c, c->d_self_scale, p.scale.data(), p.scale.size() * sizeof(double)));
+        PSA_TRY(upload(c, c->d_rc_groups, p.groups.data(), p.groups.size() * sizeof(int32_t)));
+        PSA_TRY(upload(c, c->d_rc_scale, p.scale.data(), p.scale.size() * sizeof(double)));
     }
     return PSA_OK;
 }
@@ -120,20 +114,21 @@ int self_series(psa_ctx* c, const SelfCall& p, const int32_t* idx, int64_t a0, i
     StageTimer    st(c, PSA_T_TRANSPOSE);
     const int64_t v0 = p.tile[(size_t)(2 * t0 + 1)], nv = p.tile[(size_t)(2 * (t0 + nt) + 1)] - v0;
     return launch_self_series(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), c->weights_N ? c->d_weights.as<float>() : nullptr,
-                              idx ? c->d_self_idx.as<int>() : nullptr, a0, p.box_hi, p.box_lo, c->d_self_tiles.as<int>(),
-                              c->d_self_ent.as<unsigned short>(), c->d_self_slot.as<unsigned>(),
-                              p.cut ? c->d_seg_window.as<float>() : nullptr, d_work, p.d.T, p.d.N, na, t0, nt, v0, nv, p.L, p.H, s0, ns, p.P);
+                              idx ? c->d_rc_idx.as<int>() : nullptr, a0, p.box_hi, p.box_lo, c->d_rc_tiles.as<int>(),
+                              c->d_rc_ent.as<unsigned short>(), c->d_rc_slot.as<unsigned>(),
+                              p.d.cut ? c->d_seg_window.as<float>() : nullptr, d_work, p.d.T, p.d.N, na, t0, nt, v0, nv, p.d.L, p.d.H, s0,
+                              ns, p.d.P);
 }
 
 int self_power_run(psa_ctx* c, const SelfPower& w, const SelfFill& fill) {
     const int64_t L = w.L, cols = w.cols;
     const size_t  want = (size_t)L * (size_t)cols * sizeof(float);
-    PSA_TRY(c->d_self_acc.reserve(want * 2));
-    PSA_TRY(c->d_self_out.reserve(want));
-    double* d_acc = c->d_self_acc.as<double>();
+    PSA_TRY(c->d_rc_acc.reserve(want * 2));
+    PSA_TRY(c->d_rc_out.reserve(want));
+    double* d_acc = c->d_rc_acc.as<double>();
     PSA_HIP_CHECK(hipMemsetAsync(d_acc, 0, want * 2, c->stream));
 
-    const int*     d_groups = c->d_self_groups.as<int>();
+    const int*     d_groups = c->d_rc_groups.as<int>();
     const int64_t  n_ot = std::min<int64_t>((L + 255) / 256, 1 << 12);
     std::vector<int32_t> starts((size_t)w.n_groups + 1);
     for (int64_t g = 0; g <= w.n_groups; ++g) starts[(size_t)g] = w.groups[(size_t)(2 * g)];
@@ -149,20 +144,31 @@ int self_power_run(psa_ctx* c, const SelfPower& w, const SelfFill& fill) {
             // chunks whose float64 partial sums are added in order
             const int64_t n_chunks = w.n_chunks ? w.n_chunks
                                                 : std::max<int64_t>(1, std::min<int64_t>({64, (2048 + n_ot * ng - 1) / (n_ot * ng), na}));
-            PSA_TRY(c->d_self_part.reserve((size_t)n_chunks * (size_t)ng * (size_t)L * sizeof(double)));
+            PSA_TRY(c->d_rc_part.reserve((size_t)n_chunks * (size_t)ng * (size_t)L * sizeof(double)));
             for (int64_t s0 = 0; s0 < w.n_seg; s0 += w.bs) {
                 const int64_t ns = std::min(w.bs, w.n_seg - s0);
                 const float2* d_work = nullptr;
                 PSA_TRY(fill(a0, na, (int64_t)vb, s0, ns, &d_work));
                 StageTimer st(c, PSA_T_EPILOGUE);
-                PSA_TRY(launch_self_power(c, d_work, d_groups, c->d_self_part.as<double>(), d_acc, L, ns, na, v0, nv, g_first, ng, cols,
+                PSA_TRY(launch_self_power(c, d_work, d_groups, c->d_rc_part.as<double>(), d_acc, L, ns, na, v0, nv, g_first, ng, cols,
                                           n_chunks, w.mirror));
             }
         }
     }
     if (!w.finish) return PSA_OK;
     StageTimer st(c, PSA_T_EPILOGUE);
-    return launch_lattice_finish(c, d_acc, c->d_self_scale.as<double>(), c->d_self_out.as<float>(), L * cols, cols);
+    return launch_lattice_finish(c, d_acc, c->d_rc_scale.as<double>(), c->d_rc_out.as<float>(), L * cols, cols);
+}
+
+int self_blocks(psa_ctx* c, const SelfCall& p, std::vector<int64_t>* vcut, SelfPower* w) {
+    const int64_t K = p.d.K, Ab = p.at * SELF_ATOMS, nv_max = std::min(K, p.vt * p.kt_max);
+    PSA_TRY(c->d_rc_work.reserve((size_t)std::min(Ab, p.d.n_g) * (size_t)nv_max * (size_t)p.bs * (size_t)p.d.P * sizeof(float2)));
+    vcut->clear();                                           // a vector block is a run of vt tiles
+    for (int64_t t0 = 0; t0 < p.n_tiles; t0 += p.vt) vcut->push_back(p.tile[(size_t)(2 * t0 + 1)]);
+    vcut->push_back(K);
+    w->L = p.d.P, w->n_seg = p.d.n_seg, w->n_atoms = p.d.n_g, w->cols = p.cols, w->n_groups = p.n_groups, w->groups = p.groups.data();
+    w->Ab = Ab, w->bs = p.bs, w->vcut = vcut;
+    return PSA_OK;
 }
 
 namespace {
@@ -172,7 +178,7 @@ int self_run(psa_ctx* c, const double* box_inverse, const int32_t* indices, int6
     PSA_REQUIRE(out_host != nullptr, "null output");
     SelfCall p;
     PSA_TRY(self_check(c, "psa_self_spectra", box_inverse, indices, K, bin_of, n_bins, idx, n_g, true, 0, &p));
-    const int64_t L = p.L, cols = p.cols;
+    const int64_t L = p.d.L, cols = p.cols;
     const size_t  want = (size_t)L * (size_t)cols * sizeof(float);
     PSA_REQUIRE(out_bytes == want, "out_bytes is %zu, the (%lld,%lld) float32 result has %zu", out_bytes, (long long)L, (long long)cols,
                 want);
@@ -181,16 +187,11 @@ int self_run(psa_ctx* c, const double* box_inverse, const int32_t* indices, int6
         return PSA_OK;
     }
     PSA_TRY(self_upload(c, p, idx, true));
-    const int64_t Ab = p.at * SELF_ATOMS, nv_max = std::min(K, p.vt * p.kt_max);
-    PSA_TRY(c->d_self_work.reserve((size_t)std::min(Ab, p.d.n_g) * (size_t)nv_max * (size_t)p.bs * (size_t)L * sizeof(float2)));
-    float2* d_work = c->d_self_work.as<float2>();
-    // a vector block is a run of vt tiles
     std::vector<int64_t> vcut;
-    for (int64_t t0 = 0; t0 < p.n_tiles; t0 += p.vt) vcut.push_back(p.tile[(size_t)(2 * t0 + 1)]);
-    vcut.push_back(K);
-    SelfPower w;
-    w.L = L, w.n_seg = p.n_seg, w.n_atoms = p.d.n_g, w.cols = cols, w.n_groups = p.n_groups, w.groups = p.groups.data();
-    w.mirror = p.shell, w.Ab = Ab, w.bs = p.bs, w.vcut = &vcut;
+    SelfPower            w;
+    PSA_TRY(self_blocks(c, p, &vcut, &w));
+    w.mirror = p.shell;
+    float2* d_work = c->d_rc_work.as<float2>();
     PSA_TRY(self_power_run(c, w, [&](int64_t a0, int64_t na, int64_t vb, int64_t s0, int64_t ns, const float2** where) -> int {
         const int64_t t0 = vb * p.vt, nt = std::min(p.vt, p.n_tiles - t0);
         PSA_TRY(self_series(c, p, idx, a0, na, t0, nt, s0, ns, d_work));
@@ -200,7 +201,7 @@ int self_run(psa_ctx* c, const double* box_inverse, const int32_t* indices, int6
         return PSA_OK;
     }));
     StageTimer st(c, PSA_T_D2H);
-    PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_self_out.ptr, want, hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_rc_out.ptr, want, hipMemcpyDeviceToHost, c->stream));
     PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return PSA_OK;
 }
@@ -216,16 +217,16 @@ int self_debug_series(psa_ctx* c, const double* box_inverse, const int32_t* indi
     PSA_TRY(self_upload(c, p, idx, false));
     const int64_t T = p.d.T, Ab = p.at * SELF_ATOMS, nv_max = std::min(K, p.vt * p.kt_max);
     const size_t  row = (size_t)T * sizeof(float2);
-    PSA_TRY(c->d_self_work.reserve((size_t)std::min(Ab, p.d.n_g) * (size_t)nv_max * row));
+    PSA_TRY(c->d_rc_work.reserve((size_t)std::min(Ab, p.d.n_g) * (size_t)nv_max * row));
     std::vector<char> host;
     for (int64_t a0 = 0; a0 < p.d.n_g; a0 += Ab) {
         const int64_t na = std::min(Ab, p.d.n_g - a0);
         for (int64_t t0 = 0; t0 < p.n_tiles; t0 += p.vt) {
             const int64_t nt = std::min(p.vt, p.n_tiles - t0);
             const int64_t v0 = p.tile[(size_t)(2 * t0 + 1)], nv = p.tile[(size_t)(2 * (t0 + nt) + 1)] - v0;
-            PSA_TRY(self_series(c, p, idx, a0, na, t0, nt, 0, 1, c->d_self_work.as<float2>()));
+            PSA_TRY(self_series(c, p, idx, a0, na, t0, nt, 0, 1, c->d_rc_work.as<float2>()));
             host.resize((size_t)na * (size_t)nv * row);
-            PSA_HIP_CHECK(hipMemcpyAsync(host.data(), c->d_self_work.ptr, host.size(), hipMemcpyDeviceToHost, c->stream));
+            PSA_HIP_CHECK(hipMemcpyAsync(host.data(), c->d_rc_work.ptr, host.size(), hipMemcpyDeviceToHost, c->stream));
             PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
             for (int64_t a = 0; a < na; ++a)
                 for (int64_t k = 0; k < nv; ++k)
@@ -268,8 +269,8 @@ int self_debug_power(psa_ctx* c, const void* work_host, int64_t na, int64_t nv, 
     PSA_REQUIRE((double)Ab * (double)bv * (double)bs * (double)L < (double)(1ll << 28),
                 "a block of %lld x %lld x %lld x %lld elements is more than this entry serves", (long long)Ab, (long long)bv, (long long)bs,
                 (long long)L);
-    PSA_TRY(upload(c, c->d_self_groups, groups, (size_t)(2 * (n_groups + 1)) * sizeof(int32_t)));
-    PSA_TRY(upload(c, c->d_self_scale, scale, (size_t)cols * sizeof(double)));
+    PSA_TRY(upload(c, c->d_rc_groups, groups, (size_t)(2 * (n_groups + 1)) * sizeof(int32_t)));
+    PSA_TRY(upload(c, c->d_rc_scale, scale, (size_t)cols * sizeof(double)));
     std::vector<int64_t> vcut;
     for (int64_t v0 = 0; v0 < nv; v0 += bv) vcut.push_back(v0);
     vcut.push_back(nv);
@@ -287,13 +288,13 @@ int self_debug_power(psa_ctx* c, const void* work_host, int64_t na, int64_t nv, 
                 std::memcpy(part.data() + ((size_t)a * (size_t)nvb + (size_t)v) * (size_t)ns * (size_t)L,
                             S + (((size_t)(a0 + a) * (size_t)nv + (size_t)(v0 + v)) * (size_t)n_seg + (size_t)s0) * (size_t)L,
                             (size_t)ns * (size_t)L * sizeof(float2));
-        PSA_TRY(upload(c, c->d_self_work, part.data(), part.size() * sizeof(float2)));
+        PSA_TRY(upload(c, c->d_rc_work, part.data(), part.size() * sizeof(float2)));
         PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
-        *where = c->d_self_work.as<float2>();
+        *where = c->d_rc_work.as<float2>();
         return PSA_OK;
     }));
     const size_t want = (size_t)L * (size_t)cols * sizeof(float);
-    PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_self_out.ptr, want, hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipMemcpyAsync(out_host, c->d_rc_out.ptr, want, hipMemcpyDeviceToHost, c->stream));
     PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return PSA_OK;
 }

@@ -294,36 +294,27 @@ struct psa_ctx {
     // the row slices' partial maxima (value, bin, non-finite flag) and the results.  All kept between calls.
     psa::DevBuf  d_peaks_spec, d_peaks_bands, d_peaks_part, d_peaks_fit, d_peaks_info;
 
-    // dynamic structure factor and current correlations (psa_dynamic_spectra; api_dynamic.hip): the frame-dependent
-    // projections q (kb, NC, T) of one block of k-vectors, held -- together with the segment buffer d_seg -- to
-    // opt_dynamic_work_bytes (PSA_OPT_DYNAMIC_WORK_BYTES); kappa = k / 2 pi as float32 hi and lo parts (K, 6), the unit
-    // vectors k / |k| (K, 3), the atom list, the (1 or 3, L, K) float32 result.  All kept between calls.
-    psa::DevBuf  d_dyn_q, d_dyn_kappa, d_dyn_khat, d_dyn_idx, d_dyn_out;
+    // reciprocal-space spectra and time correlations (api_reciprocal.hip: what api_dynamic.hip, api_lattice.hip,
+    // api_partial.hip, api_self.hip and api_correlation.hip share).  One set that every call of those families fills before
+    // it reads it and none keeps for the next:
+    //   work    the projections q of one block of k-vectors -- (kb, NC, T); the partial spectra's (kb, S, NC, T) --, or the
+    //           self part's series of one block (atoms, vectors, segments, P); held, together with the segment buffer d_seg,
+    //           to opt_dynamic_work_bytes (PSA_OPT_DYNAMIC_WORK_BYTES).  Everything below is outside that budget
+    //   kappa   k / 2 pi as float32 hi and lo parts (K, 6) (psa_dynamic_spectra alone)
+    //   khat    the unit vectors k / |k| (K, 3) in the order of the rows of q
+    //   idx     the atom list; the partial spectra's species lists, concatenated
+    //   tiles, ent, slot, dest    the plan of a lattice call: tile offsets, the tiles' entries, per vector its three
+    //           entries and (dest) its row of q -- S row for S species; the self part's tiles hold two offsets each
+    //   bins, scale    the shell form's bin offsets; the columns' scales in float64
+    //   acc, out       the float64 accumulator that lives across the blocks of a call (zeroed by the call) and the float32
+    //           result; the per-vector time correlations leave their float32 power in out
+    //   groups, part   the self part's columns (first vector, column) and its chunks' float64 partial sums
+    psa::DevBuf  d_rc_work, d_rc_kappa, d_rc_khat, d_rc_idx, d_rc_tiles, d_rc_ent, d_rc_slot, d_rc_dest, d_rc_bins, d_rc_scale,
+                 d_rc_acc, d_rc_out, d_rc_groups, d_rc_part;
     int64_t      opt_dynamic_work_bytes = (int64_t)4 << 30;
 
-    // spectra on the box's reciprocal lattice (psa_lattice_spectra; api_lattice.hip), under the same budget: the
-    // projections q of one block; the plan of the call -- tile offsets, the tiles' entries, per vector its three entries
-    // and its row of q --; k / |k|, the atom list; the shell form's bin offsets, scales and float64 accumulator
-    // (1 or 3, L, n_bins); the float32 result.  All kept between calls.
-    psa::DevBuf  d_lat_q, d_lat_tiles, d_lat_ent, d_lat_slot, d_lat_dest, d_lat_khat, d_lat_idx, d_lat_bins, d_lat_scale,
-                 d_lat_acc, d_lat_out;
-
-    // the self part on the box's reciprocal lattice (psa_self_spectra; api_self.hip), under the same budget: the series of
-    // one block (atoms, vectors, segments, L); the plan -- tile offsets into the entries and into the vectors, the entries,
-    // per vector its three entries --; the atom list; per output column its first vector and its column; the scales; the
-    // chunks' float64 partial sums and the float64 accumulator (L, K or n_bins); the float32 result.  All kept between calls.
-    psa::DevBuf  d_self_work, d_self_tiles, d_self_ent, d_self_slot, d_self_idx, d_self_groups, d_self_scale, d_self_part,
-                 d_self_acc, d_self_out;
-
-    // the species-resolved (partial) spectra on that lattice (psa_partial_spectra; api_partial.hip), under the same budget:
-    // the projections q (kb, S, NC, T) of one block; the plan as for psa_lattice_spectra, its rows of q counted in vectors
-    // (the table holds S row); k / |k|; the species' atom lists, concatenated; the shell form's bin offsets, scales and
-    // float64 accumulator (1 or 3, P, L, n_bins); the float32 result (1 or 3, P, L, K or n_bins).  All kept between calls.
-    psa::DevBuf  d_par_q, d_par_tiles, d_par_ent, d_par_slot, d_par_dest, d_par_khat, d_par_idx, d_par_bins, d_par_scale,
-                 d_par_acc, d_par_out;
-
     // time correlations on that lattice (psa_lattice_correlations, psa_self_correlations; api_correlation.hip): they run
-    // the spectral calls' buffers with zero-padded rows of P >= L + n_lags - 1 and add the back-transform's cosine table
+    // the set above with zero-padded rows of P >= L + n_lags - 1 and add the back-transform's cosine table
     // (P float64), the lag factors (n_lags float64), the columns' scales (cols float64), the debug entry's uploaded power
     // and the float32 result (1 or 3, n_lags, K or n_bins).  All kept between calls.
     psa::DevBuf  d_corr_tab, d_corr_factor, d_corr_scale, d_corr_in, d_corr_out;
