@@ -740,14 +740,19 @@ class Engine:
         return np.ascontiguousarray(out.transpose(2, 0, 1))
 
     @staticmethod
-    def _dynamic_args(k_vectors, idx):
-        """(k-vectors (K, 3) float32, index array or None, its pointer, n_g); an empty set keeps a valid pointer"""
-        kv = _as_f32(np.asarray(k_vectors, np.float32).reshape(-1, 3), (3,))
+    def _index_args(idx):
+        """(index array int32 or None -- to be kept alive over the call --, its pointer, n) of an index array or None; an
+        empty set keeps a valid pointer (one dummy element)"""
         if idx is None:
-            return kv, None, None, 0
+            return None, None, 0
         ii = np.ascontiguousarray(idx, np.int32).ravel()
         keep = ii if ii.size else np.zeros(1, np.int32)
-        return kv, keep, keep.ctypes.data_as(_i32p), int(ii.size)
+        return keep, keep.ctypes.data_as(_i32p), int(ii.size)
+
+    @staticmethod
+    def _dynamic_args(k_vectors, idx):
+        """(k-vectors (K, 3) float32, index array or None, its pointer, n_g)"""
+        return (_as_f32(np.asarray(k_vectors, np.float32).reshape(-1, 3), (3,)),) + Engine._index_args(idx)
 
     def dynamic_spectra(self, k_vectors, idx=None, currents: bool = True) -> np.ndarray:
         """Dynamic spectra of the resident positions (and velocities) slots (psa_dynamic_spectra): (3, L, K) float32 --
@@ -780,18 +785,20 @@ class Engine:
         _check(self._lib.psa_debug_dynamic_sincos(self._h, _f32(x), x.size, _f32(out)), "psa_debug_dynamic_sincos")
         return out
 
-    @staticmethod
-    def _lattice_args(box_inverse, indices, idx):
-        """(Hinv (3, 3) float64, indices (K, 3) int32, index array or None, its pointer, n_g)"""
+    def _lattice_args(self, box_inverse, indices, idx=None, species=None):
+        """The front half of a call on the box's lattice: (K, the leading arguments (handle, Hinv (3, 3) float64, indices
+        (K, 3) int32, K), the atom arguments -- (pointer, n_g) of the index array `idx`, or (atoms, offsets, S) of
+        `species` --, the arrays behind the pointers, to be kept alive over the call)"""
         inv = np.ascontiguousarray(box_inverse, np.float64)
         if inv.shape != (3, 3):
             raise ValueError(f"box_inverse must be (3, 3), got {inv.shape}")
         n = np.ascontiguousarray(np.asarray(indices, np.int32).reshape(-1, 3))
-        if idx is None:
-            return inv, n, None, None, 0
-        ii = np.ascontiguousarray(idx, np.int32).ravel()
-        keep = ii if ii.size else np.zeros(1, np.int32)
-        return inv, n, keep, keep.ctypes.data_as(_i32p), int(ii.size)
+        if species is None:
+            keep, *atoms = self._index_args(idx)
+        else:
+            flat, off, S = self._species_args(species)
+            keep, atoms = (flat, off), (flat.ctypes.data_as(_i32p), off.ctypes.data_as(_i64p), S)
+        return n.shape[0], (self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), n.shape[0]), tuple(atoms), (inv, n, keep)
 
     @staticmethod
     def _bins_args(bin_of, K):
@@ -803,6 +810,17 @@ class Engine:
             raise ValueError(f"bin_of has {bins.size} entries for {K} vectors")
         return bins, bins.ctypes.data_as(_i32p)
 
+    def _lattice_call(self, entry, lead, rows, box_inverse, indices, bin_of, n_bins, *middle, idx=None, species=None):
+        """One call of a spectra or correlations entry on the box's lattice: the arguments are the front half of
+        `_lattice_args`, (`bin_of`, `n_bins`), the atom arguments, `middle`, (out, its bytes); out is `lead` (+ the pairs of `species`) + (rows, K -- with `bin_of`: n_bins) float32."""
+        K, front, atoms, alive = self._lattice_args(box_inverse, indices, idx, species)
+        bins, bp = self._bins_args(bin_of, K)
+        if species is not None:
+            lead += (atoms[2] * (atoms[2] + 1) // 2,)
+        out = np.empty(lead + (rows, K if bins is None else int(n_bins)), np.float32)
+        _check(getattr(self._lib, entry)(*front, bp, int(n_bins), *atoms, *middle, _f32(out), out.nbytes), entry)
+        return out
+
     def lattice_spectra(self, box_inverse, indices, bin_of=None, n_bins=0, idx=None, currents: bool = True) -> np.ndarray:
         """Dynamic spectra on the box's reciprocal lattice (psa_lattice_spectra): k = n.G with integer `indices` (K, 3),
         `box_inverse` the float64 inverse of the box matrix (rows = box vectors).  `bin_of` None: per vector, (3, L, K)
@@ -810,24 +828,16 @@ class Engine:
         the shell form, (3 or 1, L, n_bins), every vector a half-space member standing for itself and its partner -n.
         Atom set, weights and segments as for `dynamic_spectra`."""
         T, _ = self.shape(SLOT_POSITIONS)
-        L = self.segment_length or T
-        inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
-        K = n.shape[0]
-        bins, bp = self._bins_args(bin_of, K)
-        out = np.empty((3 if currents else 1, L, K if bins is None else int(n_bins)), np.float32)
-        _check(self._lib.psa_lattice_spectra(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
-                                             bp, int(n_bins), ip, n_g,
-                                             1 if currents else 0, _f32(out), out.nbytes), "psa_lattice_spectra")
-        return out
+        return self._lattice_call("psa_lattice_spectra", (3 if currents else 1,), self.segment_length or T, box_inverse, indices,
+                                  bin_of, n_bins, 1 if currents else 0, idx=idx)
 
     def debug_lattice_project(self, box_inverse, indices, idx=None, currents: bool = True) -> np.ndarray:
         """The projection kernel of `lattice_spectra` alone: q (K, NC, T) complex64 before the window and the FFT, NC = 4
         with currents (density, j_x, j_y, j_z), else 1."""
         T, _ = self.shape(SLOT_POSITIONS)
-        inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
-        out = np.empty((n.shape[0], 4 if currents else 1, T), np.complex64)
-        _check(self._lib.psa_debug_lattice_project(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p),
-                                                   n.shape[0], ip, n_g, 1 if currents else 0, out.ctypes.data_as(C.c_void_p)),
+        K, front, atoms, alive = self._lattice_args(box_inverse, indices, idx)
+        out = np.empty((K, 4 if currents else 1, T), np.complex64)
+        _check(self._lib.psa_debug_lattice_project(*front, *atoms, 1 if currents else 0, out.ctypes.data_as(C.c_void_p)),
                "psa_debug_lattice_project")
         return out
 
@@ -837,24 +847,15 @@ class Engine:
         `bin_of` (K,) with `n_bins`: the shell form, (L, n_bins), every vector a half-space member standing for itself and
         its partner -n.  Arguments, atom set, weights and segments as for `lattice_spectra`; only positions are read."""
         T, _ = self.shape(SLOT_POSITIONS)
-        L = self.segment_length or T
-        inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
-        K = n.shape[0]
-        bins, bp = self._bins_args(bin_of, K)
-        out = np.empty((L, K if bins is None else int(n_bins)), np.float32)
-        _check(self._lib.psa_self_spectra(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
-                                          bp, int(n_bins), ip, n_g, _f32(out),
-                                          out.nbytes), "psa_self_spectra")
-        return out
+        return self._lattice_call("psa_self_spectra", (), self.segment_length or T, box_inverse, indices, bin_of, n_bins, idx=idx)
 
     def debug_self_series(self, box_inverse, indices, idx=None) -> np.ndarray:
         """The series kernel of `self_spectra` alone: z (n_g, K, T) complex64 before the window and the FFT, atoms in the
         order of the set, vectors in the caller's order."""
         T, N = self.shape(SLOT_POSITIONS)
-        inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
-        out = np.empty((N if idx is None else n_g, n.shape[0], T), np.complex64)
-        _check(self._lib.psa_debug_self_series(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p),
-                                               n.shape[0], ip, n_g, out.ctypes.data_as(C.c_void_p)), "psa_debug_self_series")
+        K, front, atoms, alive = self._lattice_args(box_inverse, indices, idx)
+        out = np.empty((N if idx is None else atoms[1], K, T), np.complex64)
+        _check(self._lib.psa_debug_self_series(*front, *atoms, out.ctypes.data_as(C.c_void_p)), "psa_debug_self_series")
         return out
 
     def debug_dynamic_power(self, segments, k_vectors, scale: float = 1.0, k_block: int = 0, seg_block: int = 0) -> np.ndarray:
@@ -906,28 +907,16 @@ class Engine:
         F^a conj F^b -- or (1, P, L, K) with `currents=False`; `bin_of` (K,) with `n_bins`: the shell form,
         (3 or 1, P, L, n_bins).  Box, vectors, weights and segments as for `lattice_spectra`."""
         T, _ = self.shape(SLOT_POSITIONS)
-        L = self.segment_length or T
-        inv, n, _, _, _ = self._lattice_args(box_inverse, indices, None)
-        idx, off, S = self._species_args(species)
-        K = n.shape[0]
-        bins, bp = self._bins_args(bin_of, K)
-        out = np.empty((3 if currents else 1, S * (S + 1) // 2, L, K if bins is None else int(n_bins)), np.float32)
-        _check(self._lib.psa_partial_spectra(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
-                                             bp, int(n_bins),
-                                             idx.ctypes.data_as(_i32p), off.ctypes.data_as(_i64p), S, 1 if currents else 0,
-                                             _f32(out), out.nbytes), "psa_partial_spectra")
-        return out
+        return self._lattice_call("psa_partial_spectra", (3 if currents else 1,), self.segment_length or T, box_inverse, indices,
+                                  bin_of, n_bins, 1 if currents else 0, species=species)
 
     def debug_partial_project(self, box_inverse, indices, species, currents: bool = True) -> np.ndarray:
         """The projections of `partial_spectra` alone: q (K, S, NC, T) complex64 before the window and the FFT, NC = 4 with
         currents (density, j_x, j_y, j_z), else 1."""
         T, _ = self.shape(SLOT_POSITIONS)
-        inv, n, _, _, _ = self._lattice_args(box_inverse, indices, None)
-        idx, off, S = self._species_args(species)
-        out = np.empty((n.shape[0], S, 4 if currents else 1, T), np.complex64)
-        _check(self._lib.psa_debug_partial_project(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p),
-                                                   n.shape[0], idx.ctypes.data_as(_i32p), off.ctypes.data_as(_i64p), S,
-                                                   1 if currents else 0, out.ctypes.data_as(C.c_void_p)),
+        K, front, atoms, alive = self._lattice_args(box_inverse, indices, species=species)
+        out = np.empty((K, atoms[2], 4 if currents else 1, T), np.complex64)
+        _check(self._lib.psa_debug_partial_project(*front, *atoms, 1 if currents else 0, out.ctypes.data_as(C.c_void_p)),
                "psa_debug_partial_project")
         return out
 
@@ -976,28 +965,15 @@ class Engine:
         correlation of every (boxcar) segment at lags 0 .. n_lags - 1.  (3, n_lags, K) float32, or (1, n_lags, K) with
         `currents=False`; with `bin_of` and `n_bins` the shell form, (3 or 1, n_lags, n_bins).  Everything else as for
         `lattice_spectra`."""
-        inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
-        K = n.shape[0]
-        bins, bp = self._bins_args(bin_of, K)
-        out = np.empty((3 if currents else 1, max(int(n_lags), 0), K if bins is None else int(n_bins)), np.float32)
-        _check(self._lib.psa_lattice_correlations(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
-                                                  bp, int(n_bins), ip, n_g,
-                                                  1 if currents else 0, int(n_lags), _f32(out), out.nbytes),
-               "psa_lattice_correlations")
-        return out
+        return self._lattice_call("psa_lattice_correlations", (3 if currents else 1,), max(int(n_lags), 0), box_inverse, indices,
+                                  bin_of, n_bins, 1 if currents else 0, int(n_lags), idx=idx)
 
     def self_correlations(self, box_inverse, indices, n_lags: int, bin_of=None, n_bins=0, idx=None) -> np.ndarray:
         """F_s(k,t) on the box's reciprocal lattice (psa_self_correlations): per atom the time correlation of
         z = w_a exp(2 pi i n.s_a(t)), summed over the atoms.  (n_lags, K) float32, or with `bin_of` and `n_bins` the shell
         form, (n_lags, n_bins).  Everything else as for `self_spectra`."""
-        inv, n, keep, ip, n_g = self._lattice_args(box_inverse, indices, idx)
-        K = n.shape[0]
-        bins, bp = self._bins_args(bin_of, K)
-        out = np.empty((max(int(n_lags), 0), K if bins is None else int(n_bins)), np.float32)
-        _check(self._lib.psa_self_correlations(self._h, inv.ctypes.data_as(_f64p), n.ctypes.data_as(_i32p), K,
-                                               bp, int(n_bins), ip, n_g,
-                                               int(n_lags), _f32(out), out.nbytes), "psa_self_correlations")
-        return out
+        return self._lattice_call("psa_self_correlations", (), max(int(n_lags), 0), box_inverse, indices, bin_of, n_bins,
+                                  int(n_lags), idx=idx)
 
     @staticmethod
     def _displacement_args(box, box_inverse, groups):
@@ -1018,9 +994,8 @@ class Engine:
         lists = [np.asarray(g, np.int32).ravel() for g in groups]
         start = np.zeros(len(lists) + 1, np.int64)
         start[1:] = np.cumsum([g.size for g in lists])
-        flat = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.int32), np.int32)
-        keep = flat if flat.size else np.zeros(1, np.int32)
-        return H, inv, keep, keep.ctypes.data_as(_i32p), start, start.ctypes.data_as(_i64p), len(lists)
+        keep, ip, _ = Engine._index_args(np.concatenate(lists) if lists else np.zeros(0, np.int32))
+        return H, inv, keep, ip, start, start.ctypes.data_as(_i64p), len(lists)
 
     def displacement_moments(self, box, n_lags: int, groups=None, origin_step: int = 1, unwrap: bool = True,
                              box_inverse=None) -> np.ndarray:

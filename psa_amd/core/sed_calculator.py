@@ -497,7 +497,7 @@ class SEDCalculator:
         lon, tra = (out[1], out[2]) if currents else (None, None)
         return DynamicSpectra(out[0], lon, tra, freqs, k_points_mags, k_vectors_3d, atoms, norm, self.dt_ps)
 
-    # what calculate_dynamic_spectra, calculate_lattice_spectra and calculate_powder_spectra share: the checks of the
+    # what calculate_dynamic_spectra and `_reciprocal` (the ten methods on the box's lattice) share: the checks of the
     # weights, the segments and the sharding; the lengths; the empty inputs; the atom set, the residency and the call
     def _dynamic_arguments(self, atom_weights, segments, what):
         weights = None if atom_weights is None else check_atom_weights(atom_weights, self.traj.n_atoms)
@@ -520,21 +520,28 @@ class SEDCalculator:
             return True
         return False
 
-    def _dynamic_run(self, basis_atom_indices, basis_atom_types, weights, segments, currents, call, max_atoms=None, seed=0):
+    def _dynamic_run(self, basis_atom_indices, basis_atom_types, weights, segments, currents, call, max_atoms=None, seed=0,
+                     species=False):
         """(what `call(engine, atom list or None)` returns, the atom-index array, sum_a w_a^2 over it); `max_atoms`: that
-        many atoms of the resolved set, drawn by `seed` (the self spectra)"""
-        groups = self._resolve_groups(basis_atom_indices, basis_atom_types, "coherent")
-        atoms = np.unique(np.concatenate(groups)).astype(int) if len(groups) > 1 else groups[0]
-        atoms = draw_atoms(atoms, max_atoms, seed)
-        w2 = np.ones(self.traj.n_atoms, np.float64) if weights is None else weights.astype(np.float64) ** 2
+        many atoms of the resolved set, drawn by `seed` (the self spectra).  `species`: the partial spectra -- `call`
+        gets the species' atom lists, and they and their norms are returned"""
+        if species:
+            atoms, norm = self._partial_species(basis_atom_indices, basis_atom_types, weights)
+            listed = atoms
+        else:
+            groups = self._resolve_groups(basis_atom_indices, basis_atom_types, "coherent")
+            atoms = np.unique(np.concatenate(groups)).astype(int) if len(groups) > 1 else groups[0]
+            atoms = np.asarray(draw_atoms(atoms, max_atoms, seed))
+            w2 = np.ones(self.traj.n_atoms, np.float64) if weights is None else weights.astype(np.float64) ** 2
+            norm = float(np.sum(w2[atoms]))
+            listed = self._device_groups([atoms])    # None: all atoms in order
+            listed = None if listed is None else listed[0]
         eng = self.engine
         with self._engine_state(weights, segments):  # (segments before the upload: its FFT primer then builds length L)
             eng.ensure_resident(_hip.SLOT_POSITIONS, self.traj.positions)
             if currents:
                 eng.ensure_resident(_hip.SLOT_VELOCITIES, self.traj.velocities)
-            listed = self._device_groups([atoms])    # None: all atoms in order
-            out = call(eng, None if listed is None else listed[0])
-        return out, np.asarray(atoms), float(np.sum(w2[atoms]))
+            return call(eng, listed), atoms, norm
 
     # ------------------------------------------------------------------ spectra on the box's reciprocal lattice
     def _lattice_indices(self, indices):
@@ -547,6 +554,76 @@ class SEDCalculator:
         if n.size and int(np.max(np.abs(n))) > _hip.LAT_MAX_INDEX:
             raise ValueError(f"indices up to |n_j| = {_hip.LAT_MAX_INDEX} are served, got {int(np.max(np.abs(n)))}")
         return n.astype(np.int32)
+
+    # the two sources of vectors: (box inverse, indices (K, 3), bin of each or None, n_bins, the result's fields about them)
+    def _lattice_vectors(self, indices):
+        n = self._lattice_indices(indices)
+        inv = lattice.box_inverse(self.traj.box_matrix)
+        k = lattice.lattice_k(n, inv)
+        return inv, n, None, 0, dict(k_points=np.linalg.norm(k, axis=1), k_vectors=k)
+
+    def _powder_shells(self, q_edges, max_per_bin, seed):
+        """the half space of every shell, its bins and the draw"""
+        edges = np.asarray(q_edges, np.float64).ravel()
+        lattice.shell_bins(np.zeros(0), edges, max_per_bin=max_per_bin)     # ValueError for bad edges or a bad cap
+        n_bins = edges.size - 1
+        inv = lattice.box_inverse(self.traj.box_matrix)
+        reach = lattice.index_reach(self.traj.box_matrix, edges[-1])
+        if np.max(reach) > _hip.LAT_MAX_INDEX:
+            raise ValueError(f"indices up to |n_j| = {_hip.LAT_MAX_INDEX} are served: q_edges reach |n_j| = {int(np.max(reach))}")
+        n_all, _, q_all = lattice.commensurate_vectors(self.traj.box_matrix, edges[-1], edges[0], half_space=True)
+        bins, selected, available, used = lattice.shell_bins(q_all, edges, max_per_bin=max_per_bin, seed=seed)
+        n, b, q = n_all[selected], bins[selected], q_all[selected]
+        q_mean = np.full(n_bins, np.nan)
+        np.divide(np.bincount(b, weights=q, minlength=n_bins), used, out=q_mean, where=used > 0)
+        return inv, n, b, n_bins, dict(q=q_mean, q_edges=edges, counts=2 * used, available=2 * available, indices=n, bin_index=b)
+
+    def _reciprocal(self, name, kind, family, source, basis_atom_indices, basis_atom_types, atom_weights, segments, *,
+                    currents=False, lags=None, max_atoms=None, seed=0):
+        """The one body of the ten methods on the box's reciprocal lattice.  `name`: the method's, as its messages spell
+        it; `kind`: "spectra" or "correlations" (`lags`); `family`: "coherent" (1 or 3 fields by `currents`), "self"
+        (density alone, `max_atoms` of the atoms drawn by `seed`) or "partial" (species, a pair axis); `source()`: the
+        vectors, `_lattice_vectors` or `_powder_shells`.  The refusals come in the order of the statements below -- the
+        order users see -- and all of them before the engine is touched."""
+        weights = self._dynamic_arguments(atom_weights, segments, f"the {name}")   # weights, type of segments, sharded
+        if kind == "spectra":
+            vectors = source()                               # shape, integers, reach; edges, max_per_bin; the box
+            rows, freqs = self._dynamic_lengths(segments)    # L > T
+            axis = dict(freqs=freqs)
+        else:
+            check_boxcar(segments)                           # a tapered window
+            L, _ = self._dynamic_lengths(segments)           # L > T
+            rows = check_lags(lags, L) if L else 0          # no frames: nothing to correlate, whatever `lags`
+            n_seg = 1 if segments is None else segments.count(self.traj.n_frames)
+            axis = dict(times=np.arange(rows) * float(self.dt_ps), origins=n_seg * (L - np.arange(rows, dtype=np.int64)))
+            vectors = source()                               # (as above)
+        inv, n, bin_of, n_bins, about = vectors
+        if family == "self":
+            check_max_atoms(max_atoms)
+        if self._dynamic_nothing(n.shape[0], name):
+            pair_axis, atoms, norm = ((1,), [np.zeros(0, int)], np.zeros(1)) if family == "partial" else ((), np.zeros(0, int), 0.0)
+            out = np.zeros((3 if currents else 1,) + pair_axis + (rows, n.shape[0] if bin_of is None else n_bins), np.float32)
+        else:
+            lag = () if kind == "spectra" else (rows,)
+
+            def call(eng, listed):
+                if family == "partial":
+                    return eng.partial_spectra(inv, n, listed, bin_of, n_bins, currents)
+                if family == "self":
+                    entry = eng.self_spectra if kind == "spectra" else eng.self_correlations
+                    return entry(inv, n, *lag, bin_of, n_bins, listed)[None]
+                entry = eng.lattice_spectra if kind == "spectra" else eng.lattice_correlations
+                return entry(inv, n, *lag, bin_of, n_bins, listed, currents)
+            out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, currents, call,
+                                                 max_atoms, seed, species=family == "partial")
+        head = (out[0],) + ((out[1], out[2]) if currents else (None, None))
+        if family == "partial":
+            tail = dict(pairs=pair_table(len(atoms)), groups=atoms, weight_norms=norm, **axis, **about, dt_ps=self.dt_ps)
+            return PartialSpectra(*head, **tail) if bin_of is None else PowderPartialSpectra(*head, **tail)
+        tail = dict(atoms=atoms, weight_norm=norm, **axis, **about, dt_ps=self.dt_ps)
+        if kind == "spectra":
+            return DynamicSpectra(*head, **tail) if bin_of is None else PowderSpectra(*head, **tail)
+        return TimeCorrelations(*head, **tail) if bin_of is None else PowderTimeCorrelations(*head, **tail)
 
     def calculate_lattice_spectra(self, indices: np.ndarray,
                                   basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
@@ -562,20 +639,8 @@ class SEDCalculator:
         Atom set, `atom_weights`, `segments`, `currents`, residency, the empty inputs and the sharded refusal are those
         of `calculate_dynamic_spectra`.  Returns a `psa_amd.DynamicSpectra` whose `k_vectors` are n.G in float64 and
         `k_points` their lengths."""
-        weights = self._dynamic_arguments(atom_weights, segments, "the lattice spectra")
-        n = self._lattice_indices(indices)
-        inv = lattice.box_inverse(self.traj.box_matrix)
-        k = lattice.lattice_k(n, inv)
-        mags = np.linalg.norm(k, axis=1)
-        L, freqs = self._dynamic_lengths(segments)
-        if self._dynamic_nothing(n.shape[0], "lattice spectra"):
-            zero = np.zeros((L, n.shape[0]), np.float32)
-            return DynamicSpectra(zero, zero.copy() if currents else None, zero.copy() if currents else None, freqs,
-                                  mags, k, np.zeros(0, int), 0.0, self.dt_ps)
-        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, currents,
-                                             lambda eng, listed: eng.lattice_spectra(inv, n, None, 0, listed, currents))
-        lon, tra = (out[1], out[2]) if currents else (None, None)
-        return DynamicSpectra(out[0], lon, tra, freqs, mags, k, atoms, norm, self.dt_ps)
+        return self._reciprocal("lattice spectra", "spectra", "coherent", lambda: self._lattice_vectors(indices),
+                                basis_atom_indices, basis_atom_types, atom_weights, segments, currents=currents)
 
     def calculate_powder_spectra(self, q_edges: np.ndarray,
                                  basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
@@ -591,38 +656,8 @@ class SEDCalculator:
 
         Atom set, `atom_weights`, `segments`, `currents`, residency, the empty inputs and the sharded refusal are those
         of `calculate_dynamic_spectra`.  Returns a `psa_amd.PowderSpectra` with (L, n_bins) float32 fields."""
-        weights = self._dynamic_arguments(atom_weights, segments, "the powder spectra")
-        shells = self._powder_shells(q_edges, max_per_bin, seed)
-        L, freqs = self._dynamic_lengths(segments)
-
-        def result(out, atoms, norm):
-            lon, tra = (out[1], out[2]) if currents else (None, None)
-            return self._powder_result(shells, out[0], lon, tra, freqs, atoms, norm)
-        n, b, n_bins, inv = shells["indices"], shells["bins"], shells["n_bins"], shells["inverse"]
-        if self._dynamic_nothing(n.shape[0], "powder spectra"):
-            return result(np.zeros((3 if currents else 1, L, n_bins), np.float32), np.zeros(0, int), 0.0)
-        return result(*self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, currents,
-                                         lambda eng, listed: eng.lattice_spectra(inv, n, b, n_bins, listed, currents)))
-
-    # what the two powder methods share: the half space of every shell, its bins and the draw; the result
-    def _powder_shells(self, q_edges, max_per_bin, seed):
-        edges = np.asarray(q_edges, np.float64).ravel()
-        lattice.shell_bins(np.zeros(0), edges, max_per_bin=max_per_bin)     # ValueError for bad edges or a bad cap
-        n_bins = edges.size - 1
-        inv = lattice.box_inverse(self.traj.box_matrix)
-        reach = lattice.index_reach(self.traj.box_matrix, edges[-1])
-        if np.max(reach) > _hip.LAT_MAX_INDEX:
-            raise ValueError(f"indices up to |n_j| = {_hip.LAT_MAX_INDEX} are served: q_edges reach |n_j| = {int(np.max(reach))}")
-        n_all, _, q_all = lattice.commensurate_vectors(self.traj.box_matrix, edges[-1], edges[0], half_space=True)
-        bins, selected, available, used = lattice.shell_bins(q_all, edges, max_per_bin=max_per_bin, seed=seed)
-        n, b, q = n_all[selected], bins[selected], q_all[selected]
-        q_mean = np.full(n_bins, np.nan)
-        np.divide(np.bincount(b, weights=q, minlength=n_bins), used, out=q_mean, where=used > 0)
-        return dict(edges=edges, n_bins=n_bins, inverse=inv, indices=n, bins=b, q=q_mean, used=used, available=available)
-
-    def _powder_result(self, shells, density, longitudinal, transverse, freqs, atoms, norm):
-        return PowderSpectra(density, longitudinal, transverse, shells["q"], shells["edges"], 2 * shells["used"],
-                             2 * shells["available"], shells["indices"], shells["bins"], freqs, atoms, norm, self.dt_ps)
+        return self._reciprocal("powder spectra", "spectra", "coherent", lambda: self._powder_shells(q_edges, max_per_bin, seed),
+                                basis_atom_indices, basis_atom_types, atom_weights, segments, currents=currents)
 
     # ------------------------------------------------------------------ the self (incoherent) part on that lattice
     def calculate_self_spectra(self, indices: np.ndarray,
@@ -640,18 +675,8 @@ class SEDCalculator:
         the result then describe the atoms used.  Only the positions are made resident.  Atom set, `atom_weights`,
         `segments`, the empty inputs and the sharded refusal are those of `calculate_lattice_spectra`.  Returns a
         `psa_amd.DynamicSpectra` whose two current fields are None."""
-        weights = self._dynamic_arguments(atom_weights, segments, "the self spectra")
-        n = self._lattice_indices(indices)
-        inv = lattice.box_inverse(self.traj.box_matrix)
-        k = lattice.lattice_k(n, inv)
-        mags = np.linalg.norm(k, axis=1)
-        L, freqs = self._dynamic_lengths(segments)
-        check_max_atoms(max_atoms)
-        if self._dynamic_nothing(n.shape[0], "self spectra"):
-            return DynamicSpectra(np.zeros((L, n.shape[0]), np.float32), None, None, freqs, mags, k, np.zeros(0, int), 0.0, self.dt_ps)
-        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, False,
-                                             lambda eng, listed: eng.self_spectra(inv, n, None, 0, listed), max_atoms, seed)
-        return DynamicSpectra(out, None, None, freqs, mags, k, atoms, norm, self.dt_ps)
+        return self._reciprocal("self spectra", "spectra", "self", lambda: self._lattice_vectors(indices),
+                                basis_atom_indices, basis_atom_types, atom_weights, segments, max_atoms=max_atoms, seed=seed)
 
     def calculate_powder_self_spectra(self, q_edges: np.ndarray,
                                       basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
@@ -664,31 +689,10 @@ class SEDCalculator:
         `max_per_bin`, counts and the empty shell are those of `calculate_powder_spectra`; `max_atoms` and everything
         else those of `calculate_self_spectra` (`seed` serves both draws).  Returns a `psa_amd.PowderSpectra` whose two
         current fields are None."""
-        weights = self._dynamic_arguments(atom_weights, segments, "the powder self spectra")
-        shells = self._powder_shells(q_edges, max_per_bin, seed)
-        L, freqs = self._dynamic_lengths(segments)
-        check_max_atoms(max_atoms)
-        n, b, n_bins, inv = shells["indices"], shells["bins"], shells["n_bins"], shells["inverse"]
-        if self._dynamic_nothing(n.shape[0], "powder self spectra"):
-            return self._powder_result(shells, np.zeros((L, n_bins), np.float32), None, None, freqs, np.zeros(0, int), 0.0)
-        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, False,
-                                             lambda eng, listed: eng.self_spectra(inv, n, b, n_bins, listed), max_atoms, seed)
-        return self._powder_result(shells, out, None, None, freqs, atoms, norm)
+        return self._reciprocal("powder self spectra", "spectra", "self", lambda: self._powder_shells(q_edges, max_per_bin, seed),
+                                basis_atom_indices, basis_atom_types, atom_weights, segments, max_atoms=max_atoms, seed=seed)
 
     # ------------------------------------------------------------------ time correlations on that lattice
-    def _correlation_arguments(self, atom_weights, segments, lags, what):
-        """(weights, n_lags, times, origins) of a time-correlation call, after the refusals of `_dynamic_arguments`, of a
-        tapered window and of `lags` outside [1, L] -- all before anything is uploaded"""
-        weights = self._dynamic_arguments(atom_weights, segments, what)
-        check_boxcar(segments)
-        L, _ = self._dynamic_lengths(segments)
-        n_t = self.traj.n_frames
-        if L == 0:                                       # no frames: nothing to correlate, whatever `lags`
-            return weights, 0, np.zeros(0, np.float64), np.zeros(0, np.int64)
-        n_lags = check_lags(lags, L)
-        n_seg = 1 if segments is None else segments.count(n_t)
-        return weights, n_lags, np.arange(n_lags) * float(self.dt_ps), n_seg * (L - np.arange(n_lags, dtype=np.int64))
-
     def calculate_lattice_correlations(self, indices: np.ndarray,
                                        basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
                                        basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
@@ -703,19 +707,8 @@ class SEDCalculator:
 
         Vectors, atom set, `atom_weights`, `currents`, residency, the empty inputs and the sharded refusal are those of
         `calculate_lattice_spectra`.  Returns a `psa_amd.TimeCorrelations` with (n_lags, K) float32 fields."""
-        weights, n_lags, times, origins = self._correlation_arguments(atom_weights, segments, lags, "the lattice correlations")
-        n = self._lattice_indices(indices)
-        inv = lattice.box_inverse(self.traj.box_matrix)
-        k = lattice.lattice_k(n, inv)
-        mags = np.linalg.norm(k, axis=1)
-        if self._dynamic_nothing(n.shape[0], "lattice correlations"):
-            zero = np.zeros((n_lags, n.shape[0]), np.float32)
-            return TimeCorrelations(zero, zero.copy() if currents else None, zero.copy() if currents else None, times, origins,
-                                    mags, k, np.zeros(0, int), 0.0, self.dt_ps)
-        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, currents,
-                                             lambda eng, listed: eng.lattice_correlations(inv, n, n_lags, None, 0, listed, currents))
-        lon, tra = (out[1], out[2]) if currents else (None, None)
-        return TimeCorrelations(out[0], lon, tra, times, origins, mags, k, atoms, norm, self.dt_ps)
+        return self._reciprocal("lattice correlations", "correlations", "coherent", lambda: self._lattice_vectors(indices),
+                                basis_atom_indices, basis_atom_types, atom_weights, segments, currents=currents, lags=lags)
 
     def calculate_powder_correlations(self, q_edges: np.ndarray,
                                       basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
@@ -728,22 +721,9 @@ class SEDCalculator:
         mean over the full sphere is real and the half-space members alone give it.  Shells, `max_per_bin`, `seed`,
         counts and the empty shell are those of `calculate_powder_spectra`; `lags`, `segments` and everything else those
         of `calculate_lattice_correlations`.  Returns a `psa_amd.PowderTimeCorrelations` with (n_lags, n_bins) fields."""
-        weights, n_lags, times, origins = self._correlation_arguments(atom_weights, segments, lags, "the powder correlations")
-        shells = self._powder_shells(q_edges, max_per_bin, seed)
-
-        def result(out, atoms, norm):
-            lon, tra = (out[1], out[2]) if currents else (None, None)
-            return self._powder_correlations(shells, out[0], lon, tra, times, origins, atoms, norm)
-        n, b, n_bins, inv = shells["indices"], shells["bins"], shells["n_bins"], shells["inverse"]
-        if self._dynamic_nothing(n.shape[0], "powder correlations"):
-            return result(np.zeros((3 if currents else 1, n_lags, n_bins), np.float32), np.zeros(0, int), 0.0)
-        return result(*self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, currents,
-                                         lambda eng, listed: eng.lattice_correlations(inv, n, n_lags, b, n_bins, listed, currents)))
-
-    def _powder_correlations(self, shells, density, longitudinal, transverse, times, origins, atoms, norm):
-        return PowderTimeCorrelations(density, longitudinal, transverse, times, origins, shells["q"], shells["edges"],
-                                      2 * shells["used"], 2 * shells["available"], shells["indices"], shells["bins"], atoms, norm,
-                                      self.dt_ps)
+        return self._reciprocal("powder correlations", "correlations", "coherent",
+                                lambda: self._powder_shells(q_edges, max_per_bin, seed), basis_atom_indices, basis_atom_types,
+                                atom_weights, segments, currents=currents, lags=lags)
 
     def calculate_self_correlations(self, indices: np.ndarray,
                                     basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
@@ -756,19 +736,9 @@ class SEDCalculator:
         over the atoms -- F_s(n, 0) = sum_a w_a^2 --, correct on wrapped coordinates as stored.  `lags` and `segments` as
         for `calculate_lattice_correlations`; vectors, atom set, `atom_weights`, `max_atoms`, `seed` and everything else
         as for `calculate_self_spectra`.  Returns a `psa_amd.TimeCorrelations` whose two current fields are None."""
-        weights, n_lags, times, origins = self._correlation_arguments(atom_weights, segments, lags, "the self correlations")
-        n = self._lattice_indices(indices)
-        inv = lattice.box_inverse(self.traj.box_matrix)
-        k = lattice.lattice_k(n, inv)
-        mags = np.linalg.norm(k, axis=1)
-        check_max_atoms(max_atoms)
-        if self._dynamic_nothing(n.shape[0], "self correlations"):
-            return TimeCorrelations(np.zeros((n_lags, n.shape[0]), np.float32), None, None, times, origins, mags, k,
-                                    np.zeros(0, int), 0.0, self.dt_ps)
-        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, False,
-                                             lambda eng, listed: eng.self_correlations(inv, n, n_lags, None, 0, listed),
-                                             max_atoms, seed)
-        return TimeCorrelations(out, None, None, times, origins, mags, k, atoms, norm, self.dt_ps)
+        return self._reciprocal("self correlations", "correlations", "self", lambda: self._lattice_vectors(indices),
+                                basis_atom_indices, basis_atom_types, atom_weights, segments, lags=lags, max_atoms=max_atoms,
+                                seed=seed)
 
     def calculate_powder_self_correlations(self, q_edges: np.ndarray,
                                            basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
@@ -780,17 +750,9 @@ class SEDCalculator:
         lattice in each shell.  Shells, `max_per_bin`, counts and the empty shell are those of
         `calculate_powder_spectra`; everything else as for `calculate_self_correlations` (`seed` serves both draws).
         Returns a `psa_amd.PowderTimeCorrelations` whose two current fields are None."""
-        weights, n_lags, times, origins = self._correlation_arguments(atom_weights, segments, lags, "the powder self correlations")
-        shells = self._powder_shells(q_edges, max_per_bin, seed)
-        check_max_atoms(max_atoms)
-        n, b, n_bins, inv = shells["indices"], shells["bins"], shells["n_bins"], shells["inverse"]
-        if self._dynamic_nothing(n.shape[0], "powder self correlations"):
-            return self._powder_correlations(shells, np.zeros((n_lags, n_bins), np.float32), None, None, times, origins,
-                                             np.zeros(0, int), 0.0)
-        out, atoms, norm = self._dynamic_run(basis_atom_indices, basis_atom_types, weights, segments, False,
-                                             lambda eng, listed: eng.self_correlations(inv, n, n_lags, b, n_bins, listed),
-                                             max_atoms, seed)
-        return self._powder_correlations(shells, out, None, None, times, origins, atoms, norm)
+        return self._reciprocal("powder self correlations", "correlations", "self",
+                                lambda: self._powder_shells(q_edges, max_per_bin, seed), basis_atom_indices, basis_atom_types,
+                                atom_weights, segments, lags=lags, max_atoms=max_atoms, seed=seed)
 
     # ------------------------------------------------------------------ displacements in real space
     def _displacement_groups(self, basis_atom_indices, basis_atom_types, origin_step, unwrap, max_atoms, seed, what):
@@ -1051,14 +1013,6 @@ class SEDCalculator:
         w2 = np.ones(self.traj.n_atoms, np.float64) if weights is None else weights.astype(np.float64) ** 2
         return [np.asarray(g) for g in groups], np.array([float(np.sum(w2[g])) for g in groups])
 
-    def _partial_run(self, groups, weights, segments, currents, call):
-        eng = self.engine
-        with self._engine_state(weights, segments):  # (segments before the upload: its FFT primer then builds length L)
-            eng.ensure_resident(_hip.SLOT_POSITIONS, self.traj.positions)
-            if currents:
-                eng.ensure_resident(_hip.SLOT_VELOCITIES, self.traj.velocities)
-            return call(eng)
-
     def calculate_partial_spectra(self, indices: np.ndarray,
                                   basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
                                   basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
@@ -1074,21 +1028,8 @@ class SEDCalculator:
         gives all atoms as one.  They must be disjoint and at most 8 (ValueError).  Vectors, `atom_weights`, `segments`,
         `currents`, residency, the empty inputs and the sharded refusal are those of `calculate_lattice_spectra`.
         Returns a `psa_amd.PartialSpectra` with (P, L, K) float32 fields, P = S (S + 1) / 2."""
-        weights = self._dynamic_arguments(atom_weights, segments, "the partial spectra")
-        n = self._lattice_indices(indices)
-        inv = lattice.box_inverse(self.traj.box_matrix)
-        k = lattice.lattice_k(n, inv)
-        mags = np.linalg.norm(k, axis=1)
-        L, freqs = self._dynamic_lengths(segments)
-
-        def result(out, groups, norms):
-            lon, tra = (out[1], out[2]) if currents else (None, None)
-            return PartialSpectra(out[0], lon, tra, pair_table(len(groups)), groups, norms, freqs, mags, k, self.dt_ps)
-        if self._dynamic_nothing(n.shape[0], "partial spectra"):
-            return result(np.zeros((3 if currents else 1, 1, L, n.shape[0]), np.float32), [np.zeros(0, int)], np.zeros(1))
-        groups, norms = self._partial_species(basis_atom_indices, basis_atom_types, weights)
-        return result(self._partial_run(groups, weights, segments, currents,
-                                        lambda eng: eng.partial_spectra(inv, n, groups, None, 0, currents)), groups, norms)
+        return self._reciprocal("partial spectra", "spectra", "partial", lambda: self._lattice_vectors(indices),
+                                basis_atom_indices, basis_atom_types, atom_weights, segments, currents=currents)
 
     def calculate_powder_partial_spectra(self, q_edges: np.ndarray,
                                          basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
@@ -1101,20 +1042,9 @@ class SEDCalculator:
         q_edges[b] <= |k| < q_edges[b + 1], the shells summed on the GPU in float64.  Shells, `max_per_bin`, `seed`,
         counts and the empty shell are those of `calculate_powder_spectra`; species and everything else those of
         `calculate_partial_spectra`.  Returns a `psa_amd.PowderPartialSpectra` with (P, L, n_bins) float32 fields."""
-        weights = self._dynamic_arguments(atom_weights, segments, "the powder partial spectra")
-        shells = self._powder_shells(q_edges, max_per_bin, seed)
-        L, freqs = self._dynamic_lengths(segments)
-        n, b, n_bins, inv = shells["indices"], shells["bins"], shells["n_bins"], shells["inverse"]
-
-        def result(out, groups, norms):
-            lon, tra = (out[1], out[2]) if currents else (None, None)
-            return PowderPartialSpectra(out[0], lon, tra, pair_table(len(groups)), groups, norms, shells["q"], shells["edges"],
-                                        2 * shells["used"], 2 * shells["available"], n, b, freqs, self.dt_ps)
-        if self._dynamic_nothing(n.shape[0], "powder partial spectra"):
-            return result(np.zeros((3 if currents else 1, 1, L, n_bins), np.float32), [np.zeros(0, int)], np.zeros(1))
-        groups, norms = self._partial_species(basis_atom_indices, basis_atom_types, weights)
-        return result(self._partial_run(groups, weights, segments, currents,
-                                        lambda eng: eng.partial_spectra(inv, n, groups, b, n_bins, currents)), groups, norms)
+        return self._reciprocal("powder partial spectra", "spectra", "partial",
+                                lambda: self._powder_shells(q_edges, max_per_bin, seed), basis_atom_indices, basis_atom_types,
+                                atom_weights, segments, currents=currents)
 
     # ------------------------------------------------------------------ mode projection
     def calculate_mode_sed(self, k_points_mags: np.ndarray, k_vectors_3d: np.ndarray, eigenvectors: np.ndarray,

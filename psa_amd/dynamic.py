@@ -40,6 +40,15 @@ from typing import Optional
 import numpy as np
 
 
+def time_step(dt_ps, freqs, L):
+    """the time step behind a spectrum of L bins: `dt_ps`, or 1 / (L freqs[1]) where that is None (ValueError for L = 1)"""
+    if dt_ps is not None:
+        return dt_ps
+    if L < 2:
+        raise ValueError("structure_factor needs dt_ps: the frequencies of a one-bin spectrum hold no time step")
+    return 1.0 / (L * abs(float(freqs[1])))
+
+
 @dataclass
 class DynamicSpectra:
     """Result of `SEDCalculator.calculate_dynamic_spectra`: `density`, `longitudinal`, `transverse` (L, K) float32 per
@@ -61,9 +70,4 @@ class DynamicSpectra:
         """(L, K) float64: S(k, omega) = density L dt / sum_a w_a^2; dt is `dt_ps`, or 1 / (L freqs[1]) where that is
         None (ValueError for L = 1, whose `freqs` hold no time step)"""
         L = self.density.shape[0]
-        dt = self.dt_ps
-        if dt is None:
-            if L < 2:
-                raise ValueError("structure_factor needs dt_ps: the frequencies of a one-bin spectrum hold no time step")
-            dt = 1.0 / (L * abs(float(self.freqs[1])))
-        return self.density.astype(np.float64) * (L * dt / self.weight_norm)
+        return self.density.astype(np.float64) * (L * time_step(self.dt_ps, self.freqs, L) / self.weight_norm)

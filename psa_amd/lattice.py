@@ -37,6 +37,8 @@ from typing import Optional
 
 import numpy as np
 
+from .dynamic import time_step
+
 
 def box_inverse(box_matrix) -> np.ndarray:
     """Hinv (3, 3) float64 of the box matrix (rows = box vectors), its float32 entries taken as exact; ValueError for a
@@ -145,9 +147,4 @@ class PowderSpectra:
         """(L, n_bins) float64: S(Q, omega) = density L dt / sum_a w_a^2; dt is `dt_ps`, or 1 / (L freqs[1]) where that
         is None (ValueError for L = 1, whose `freqs` hold no time step)"""
         L = self.density.shape[0]
-        dt = self.dt_ps
-        if dt is None:
-            if L < 2:
-                raise ValueError("structure_factor needs dt_ps: the frequencies of a one-bin spectrum hold no time step")
-            dt = 1.0 / (L * abs(float(self.freqs[1])))
-        return self.density.astype(np.float64) * (L * dt / self.weight_norm)
+        return self.density.astype(np.float64) * (L * time_step(self.dt_ps, self.freqs, L) / self.weight_norm)

@@ -32,6 +32,8 @@ from typing import List, Optional
 
 import numpy as np
 
+from .dynamic import time_step
+
 MAX_SPECIES = 8                        # psa_amd._hip.PARTIAL_MAX_SPECIES: 36 pairs
 
 
@@ -52,14 +54,6 @@ def pair_row(a: int, b: int, n_species: int) -> int:
     return a * S - a * (a - 1) // 2 + (b - a)
 
 
-def _time_step(dt_ps, freqs, L):
-    if dt_ps is not None:
-        return dt_ps
-    if L < 2:
-        raise ValueError("structure_factor needs dt_ps: the frequencies of a one-bin spectrum hold no time step")
-    return 1.0 / (L * abs(float(freqs[1])))
-
-
 class _Partials:
     """what the two result types derive from their (P, L, columns) fields"""
 
@@ -76,7 +70,7 @@ class _Partials:
         """(P, L, columns) float64, Ashcroft-Langreth: S_ab = density_ab L dt / sqrt(W_a W_b), W = `weight_norms`; dt is
         `dt_ps`, or 1 / (L freqs[1]) where that is None (ValueError for L = 1).  A pair with an empty species: zeros."""
         L = self.density.shape[1]
-        dt = _time_step(self.dt_ps, self.freqs, L)
+        dt = time_step(self.dt_ps, self.freqs, L)
         W = np.asarray(self.weight_norms, np.float64)
         norm = np.sqrt(W[self.pairs[:, 0]] * W[self.pairs[:, 1]])
         factor = np.divide(L * dt, norm, out=np.zeros_like(norm), where=norm > 0)
