@@ -1,12 +1,14 @@
 """The vibrational density of states on the GPU (psa_vdos, `calculate_vdos`): parity with the float64 restatement
 (tests/vdos64.py) over modes, segment shapes and windows; the single-atom identity with the SED path; the planted mode;
 Parseval; index-list and empty groups; float64 accumulation over 32768 atoms; invariance under the blocking and
-determinism; no leak into later SED calls; ABI errors."""
+determinism; no leak into later SED calls; ABI errors.  Beside rel_max the parity tests hold every element to the bound
+of tests/vdos_cases.py (its edges are in tests/test_gpu_vdos_perelement.py)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import vdos_cases as V
 from conftest import rel_max
 
 pytestmark = pytest.mark.gpu
@@ -79,8 +81,10 @@ def test_parity_float64(engine, syn, mode, shape, window):
     assert got.dos.shape == (L // 2 + 1, G, 3) and got.dos.dtype == np.float32 and len(got.groups) == G
     assert np.array_equal(got.freqs, np.fft.rfftfreq(L, d=calc.dt_ps))
     err = rel_max(got.dos, ref)
-    print(f"{mode} L={L} H={H} {window}: rel_max {err:.3e}")
+    ratio = V.check(got.dos, window=seg.window_array(), L=L, H=H, ref=ref, **ref_kw)
+    print(f"{mode} L={L} H={H} {window}: rel_max {err:.3e}, {ratio:.3f} x bound")
     assert err <= 1e-5
+    assert ratio <= 1.0
     assert engine.segment_length == 0
 
 
@@ -90,9 +94,11 @@ def test_full_length_without_segments(engine, syn):
     for mode in MODES:
         calc, kw, ref_kw = _mode(syn, mode)
         got = calc.calculate_vdos(**kw)
-        err = rel_max(got.dos, vdos64(**ref_kw))
-        print(f"{mode} full length: rel_max {err:.3e}")
+        ref = vdos64(**ref_kw)
+        err, ratio = rel_max(got.dos, ref), V.check(got.dos, ref=ref, **ref_kw)
+        print(f"{mode} full length: rel_max {err:.3e}, {ratio:.3f} x bound")
         assert got.dos.shape[0] == 129 and err <= 1e-5
+        assert ratio <= 1.0
 
 
 @pytest.mark.parametrize("weighted", [False, True])
@@ -152,6 +158,9 @@ def test_index_list_groups(engine, syn):
             err = rel_max(got[:, gi, :], ref[:, gi, :])
             print(f"group {gi} segments {seg is not None}: rel_max {err:.3e}")
             assert err <= 1e-5
+        ratio = V.check(got, tr.velocities, groups, ref=ref, **kw)
+        print(f"segments {seg is not None}: {ratio:.3f} x bound")
+        assert ratio <= 1.0
     in_order = engine.vdos(_hip.SLOT_VELOCITIES, None, [np.sort(groups[0]), groups[1], groups[2]])
     assert np.array_equal(in_order, engine.vdos(_hip.SLOT_VELOCITIES, None, groups))     # the order inside a group is free
 
@@ -159,7 +168,7 @@ def test_index_list_groups(engine, syn):
 def test_blocking_invariance_and_determinism(engine, syn):
     """a work budget that forces several atom blocks and several segment blocks gives the default-budget result"""
     from psa_amd import Segments, _hip
-    calc = syn["calcs"][False]
+    calc, tr = syn["calcs"][False], syn["traj"]
     seg = Segments(64, 32)                                   # 7 segments; 256 atom pairs = 8 tiles; one unit = 768 L bytes
     kw = dict(basis_atom_types=[1, 2], segments=seg)
     # groups of 45 and 111 atoms: 23 + 56 pairs, so the first tile of 32 pairs holds rows of both groups
@@ -168,6 +177,11 @@ def test_blocking_invariance_and_determinism(engine, syn):
     try:
         whole, whole_odd = calc.calculate_vdos(**kw).dos, calc.calculate_vdos(**kw_odd).dos
         assert np.array_equal(whole, calc.calculate_vdos(**kw).dos)
+        for dos, groups in ((whole, [np.flatnonzero(tr.types == t) for t in (1, 2)]),
+                            (whole_odd, [np.arange(0, 90, 2), np.arange(1, 223, 2)])):
+            ratio = V.check(dos, tr.velocities, groups, seg.window_array(), seg.length, seg.hop)
+            print(f"default budget, groups of {[len(g) for g in groups]}: {ratio:.3f} x bound")
+            assert ratio <= 1.0
         for budget in (3 * unit, 14 * unit + 5, 20 * unit):  # 8 x 3 blocks of (1 tile, 3 segments); 4 x 1 of (2, 7); 4 x 1
             engine.set_option(_hip.OPT_VDOS_WORK_BYTES, budget)
             for k, ref in ((kw, whole), (kw_odd, whole_odd)):
@@ -258,7 +272,9 @@ def test_accumulation_over_32768_atoms(engine, syn):
         got = calc.calculate_vdos(segments=Segments(64, 64, "boxcar"))
         ref = vdos64(tr.velocities, [None], np.ones(64), 64, 64)
         err = rel_max(got.dos, ref)
-        print(f"N = 32768, T = 64: rel_max {err:.3e}")
+        ratio = V.check(got.dos, tr.velocities, [None], np.ones(64), 64, 64, ref=ref)
+        print(f"N = 32768, T = 64: rel_max {err:.3e}, {ratio:.3f} x bound")
         assert got.dos.shape == (33, 1, 3) and err <= 1e-5
+        assert ratio <= 1.0
     finally:
         engine.invalidate()
