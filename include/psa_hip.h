@@ -121,10 +121,10 @@ int         psa_set_k1(psa_ctx* ctx, int selector);     /* PSA_K1_* */
  *                             32-row blocks of shorter lists).  Same arithmetic, same results; the loader
  *                             form measured 2-3 % faster on every shape (round 3). */
 #define PSA_OPT_K1_LOADER_WAVES 6
-/*   PSA_OPT_K1_WIDE       [0] 1 = lists of more than 64 k-vectors are projected in 256-row M blocks
+/*   PSA_OPT_K1_WIDE       [1] lists of more than 64 k-vectors are projected in 256-row M blocks
  *                             (k1_planes_wide.hip: eight wavefronts, a ring of 1-KiB units, 28 KiB of LDS-DMA
  *                             per 128 rows and stage instead of 40).  Same arithmetic; the float32 fold
- *                             comes every 10 stages instead of every 8. */
+ *                             comes every 10 stages instead of every 8.  0 = the 128-row blocks for them too. */
 #define PSA_OPT_K1_WIDE         7
 /*   PSA_OPT_K1_LOWRANK    [1] k-lists on one line (k-paths) are projected as 64 node rows of exact phases
  *                             (the 128-row planes kernel), one float16 product of the difference to the
@@ -164,6 +164,10 @@ int         psa_set_k1(psa_ctx* ctx, int selector);     /* PSA_K1_* */
  *                             the D pass.  Same arithmetic, bit-identical results; 0 = always the two passes.  psa_k1_lowrank_pair_launches counts the launches it served. */
 #define PSA_OPT_K1_LOWRANK_PAIR 15   /* 14 is not assigned: psa_set_option refuses it as unknown */
 int         psa_set_option(psa_ctx* ctx, int option, int64_t value);
+/* The table those options live in (api_core.hip), row by row: the option's id, the default a new context starts it at
+ * (before psa_create reads the environment) and its name as spelled above; any of the three may be null.  PSA_EINVAL past
+ * the last row.  No context, no GPU. */
+int         psa_option_info(int index, int32_t* option, int64_t* default_value, const char** name);
 /* device name / CU count / HBM bytes of the context's GPU */
 int         psa_device_info(psa_ctx* ctx, char* name, int name_len,
                             int* compute_units, int64_t* hbm_bytes);
@@ -922,6 +926,9 @@ int psa_k1_lowrank_pair_launches(psa_ctx* ctx, int64_t* launches);
  * stages, padding included; index[512 * 32 n_stage] (may be null) = the float16 element index of (row m, atom a) at
  * m * 32 n_stage + a.  No context, no GPU. */
 int psa_lowrank_pair_image(int32_t n_stage, int64_t* index, int64_t* bytes);
+/* Device allocations the library's contexts hold at this moment, process-wide: how many and their bytes.  A destroyed
+ * context leaves none behind.  No context, no GPU. */
+int psa_debug_device_buffers(int64_t* count, int64_t* bytes);
 /* host wall clock (ms) of work that is done once and then cached, summed since the last call:
  * [0] rocFFT plan builds (run-time compiled per (T, batch))  [1] largest-magnitude passes
  * [2] split-plane builds  [3] trajectory uploads (psa_data_upload / psa_sed_project_upload) */

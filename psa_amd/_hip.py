@@ -199,6 +199,8 @@ SIGNATURES = {
     "psa_k1_lowrank_pair_launches": (C.c_int, [_ctx, _i64p]),
     "psa_lowrank_pair_image": (C.c_int, [C.c_int32, _i64p, _i64p]),
     "psa_oneoff_stats": (C.c_int, [_ctx, _f64p]),
+    "psa_option_info": (C.c_int, [C.c_int, C.POINTER(C.c_int32), _i64p, C.POINTER(C.c_char_p)]),
+    "psa_debug_device_buffers": (C.c_int, [_i64p, _i64p]),
     "psa_debug_phase_table": (C.c_int, [_ctx, _f32p, _f32p, C.c_int64, _i32p, C.c_int64,
                                         C.c_int64, C.c_void_p]),
     "psa_debug_project_only": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p,
@@ -289,6 +291,24 @@ def device_count() -> int:
     n = C.c_int(0)
     _check(load_library().psa_device_count(C.byref(n)), "psa_device_count")
     return n.value
+
+
+def option_table():
+    """[(id, name, default)] of every option of psa_set_option, from the library's own table (psa_option_info; host
+    only): the one source of the defaults."""
+    lib, rows = load_library(), []
+    opt, default, name = C.c_int32(0), C.c_int64(0), C.c_char_p()
+    while lib.psa_option_info(len(rows), C.byref(opt), C.byref(default), C.byref(name)) == 0:
+        rows.append((opt.value, name.value.decode(), default.value))
+    return rows
+
+
+def device_buffers():
+    """(count, bytes) of the device allocations the library's contexts hold right now, process-wide
+    (psa_debug_device_buffers; host only).  A closed Engine leaves none behind."""
+    n, b = C.c_int64(0), C.c_int64(0)
+    _check(load_library().psa_debug_device_buffers(C.byref(n), C.byref(b)), "psa_debug_device_buffers")
+    return n.value, b.value
 
 
 def k_pairs(k_vectors):
@@ -593,6 +613,12 @@ class Engine:
 
     def set_option(self, option: int, value: int):
         _check(self._lib.psa_set_option(self._h, option, int(value)), "psa_set_option")
+
+    def reset_options(self):
+        """Every option back to its default in the library's table (option_table).  The environment overrides that
+        psa_create reads (PSA_K1_LOWRANK, PSA_K1_LOWRANK_MIN_K) are ignored: the table's values are set."""
+        for option, _, default in option_table():
+            self.set_option(option, default)
 
     def plane_cache(self):
         """(number of cached split-plane sets, their bytes)"""

@@ -4,6 +4,7 @@
 
 #include <unistd.h>
 
+#include <atomic>
 #include <filesystem>
 
 namespace psa {
@@ -20,10 +21,15 @@ void set_error(const char* fmt, ...) {
     g_error = buf;
 }
 
+// live DevBuf allocations of the process (psa_debug_device_buffers): a move hands one over and changes neither
+static std::atomic<int64_t> g_devbuf_count{0}, g_devbuf_bytes{0};
+
 int DevBuf::reserve(size_t bytes) {
     if (bytes <= cap) return PSA_OK;
     if (ptr) {
         PSA_HIP_CHECK(hipFree(ptr));
+        g_devbuf_count -= 1;
+        g_devbuf_bytes -= (int64_t)cap;
         ptr = nullptr;
         cap = 0;
     }
@@ -34,13 +40,24 @@ int DevBuf::reserve(size_t bytes) {
         return PSA_ENOMEM;
     }
     cap = bytes;
+    g_devbuf_count += 1;
+    g_devbuf_bytes += (int64_t)bytes;
     return PSA_OK;
 }
 
 void DevBuf::release() {
-    if (ptr) (void)hipFree(ptr);
+    if (ptr) {
+        (void)hipFree(ptr);
+        g_devbuf_count -= 1;
+        g_devbuf_bytes -= (int64_t)cap;
+    }
     ptr = nullptr;
     cap = 0;
+}
+
+FftPlan::~FftPlan() {
+    if (info) (void)rocfft_execution_info_destroy(info);
+    if (plan) (void)rocfft_plan_destroy(plan);
 }
 
 int enter(psa_ctx* c) {
@@ -102,13 +119,7 @@ static void join_primer(psa_ctx* c) {
     HostTimer ht(&c->oneoff_ms[0]);                    // whatever of the build is still outstanding
     c->fft_primer.join();
     if (c->primed.plan) {
-        auto key = std::make_pair(c->primed_T, (int64_t)3);
-        if (c->plans.find(key) == c->plans.end()) {
-            c->plans.emplace(key, c->primed);
-        } else {
-            (void)rocfft_execution_info_destroy(c->primed.info);
-            (void)rocfft_plan_destroy(c->primed.plan);
-        }
+        c->plans.try_emplace(std::make_pair(c->primed_T, (int64_t)3), std::move(c->primed));   // (a key that is there stays)
         c->primed = FftPlan{};
     }
 }
@@ -121,7 +132,7 @@ void prime_fft(psa_ctx* c, int64_t T) {
     c->fft_primer = std::thread([c, T] {
         (void)hipSetDevice(c->device);
         FftPlan p;
-        if (create_plan(c, T, 3, &p) == PSA_OK) c->primed = p;
+        if (create_plan(c, T, 3, &p) == PSA_OK) c->primed = std::move(p);
     });
 }
 
@@ -133,7 +144,7 @@ int get_plan(psa_ctx* c, int64_t T, int64_t batch, FftPlan** out) {
         HostTimer ht(&c->oneoff_ms[0]);
         FftPlan   p;
         PSA_TRY(create_plan(c, T, batch, &p));
-        it = c->plans.emplace(key, p).first;
+        it = c->plans.emplace(key, std::move(p)).first;
     }
     *out = &it->second;
     return PSA_OK;
@@ -172,7 +183,59 @@ int validate_groups(int64_t N, const int32_t* group_idx, const int64_t* group_of
     return PSA_OK;
 }
 
+// ---- the options: the one place that says which exist, what they are called and what they start at -----------------
+// (include/psa_hip.h documents them; psa_option_info hands the table to Python and to tests/test_options_host.py)
+constexpr int64_t OPT_FLAG = -1;                       // Option::min of an on / off option: stored as value != 0
+struct Option {
+    int              id;
+    const char*      name;
+    int64_t psa_ctx::*field;
+    int64_t          def;
+    int64_t          min;                              // least value accepted, or OPT_FLAG
+};
+#define PSA_OPTION(id, field, def, min) {id, #id, &psa_ctx::field, def, min}
+constexpr Option OPTIONS[] = {
+    PSA_OPTION(PSA_OPT_PLANES, opt_planes, 1, OPT_FLAG),
+    PSA_OPTION(PSA_OPT_PLANES_BUDGET, opt_planes_budget, 0, 0),
+    PSA_OPTION(PSA_OPT_PLANES_EAGER, opt_planes_eager, 0, OPT_FLAG),
+    PSA_OPTION(PSA_OPT_PLANES_MIN_K, opt_planes_min_k, 17, 1),
+    PSA_OPTION(PSA_OPT_FOLD_PAIRS, opt_fold_pairs, 1, OPT_FLAG),
+    PSA_OPTION(PSA_OPT_FFT_PRIME, opt_fft_prime, 1, OPT_FLAG),
+    PSA_OPTION(PSA_OPT_K1_LOADER_WAVES, opt_k1_loader_waves, 1, OPT_FLAG),
+    PSA_OPTION(PSA_OPT_K1_WIDE, opt_k1_wide, 1, OPT_FLAG),
+    PSA_OPTION(PSA_OPT_K1_LOWRANK, opt_k1_lowrank, 1, OPT_FLAG),
+    PSA_OPTION(PSA_OPT_K1_LOWRANK_MIN_K, opt_k1_lowrank_min_k, 256, 1),
+    PSA_OPTION(PSA_OPT_K1_LOWRANK_MIN_LOCAL, opt_k1_lowrank_min_local, 128, 1),
+    PSA_OPTION(PSA_OPT_VDOS_WORK_BYTES, opt_vdos_work_bytes, (int64_t)1 << 30, 1),
+    PSA_OPTION(PSA_OPT_MODES_WORK_BYTES, opt_modes_work_bytes, (int64_t)4 << 30, 1),
+    PSA_OPTION(PSA_OPT_DYNAMIC_WORK_BYTES, opt_dynamic_work_bytes, (int64_t)4 << 30, 1),
+    PSA_OPTION(PSA_OPT_K1_LOWRANK_PAIR, opt_k1_lowrank_pair, 1, OPT_FLAG),
+};
+#undef PSA_OPTION
+
 }  // namespace psa
+
+psa_ctx::psa_ctx() {
+    for (const psa::Option& o : psa::OPTIONS) this->*o.field = o.def;
+}
+
+// What the members do not free themselves, once nothing can be in flight: the caller has set the device; the stream is
+// drained and the primer joined before anything is closed.  The buffers, the plane sets and the rocFFT plans go after
+// this body, as members: the stream they were used on is idle by then.
+psa_ctx::~psa_ctx() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (fft_primer.joinable()) fft_primer.join();
+    if (comm) (void)ncclCommDestroy(comm);
+    for (auto& p : timing.pending) {
+        (void)hipEventDestroy(p.e0);
+        (void)hipEventDestroy(p.e1);
+    }
+    for (auto ev : timing.pool) (void)hipEventDestroy(ev);
+    psa::stager_release(this);
+    if (d2h_stream) (void)hipStreamDestroy(d2h_stream);
+    if (d2h_ready) (void)hipEventDestroy(d2h_ready);
+    if (stream) (void)hipStreamDestroy(stream);
+}
 
 using namespace psa;
 
@@ -229,7 +292,7 @@ int psa_create(int device, psa_ctx** out) {
         }
         (void)rocfft_setup();
     });
-    psa_ctx* c = new psa_ctx();
+    psa_ctx* c = new psa_ctx();                        // (the options at the table's defaults)
     c->device = device;
     c->compute_units = prop.multiProcessorCount;
     // A/B switches of the low-rank route, read once here (psa_set_option overrides them)
@@ -247,46 +310,16 @@ int psa_create(int device, psa_ctx** out) {
 
 int psa_destroy(psa_ctx* c) {
     if (!c) return PSA_OK;
-    {
-        Guard g(c);
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-        if (c->fft_primer.joinable()) c->fft_primer.join();
-        if (c->primed.plan) {
-            (void)rocfft_execution_info_destroy(c->primed.info);
-            (void)rocfft_plan_destroy(c->primed.plan);
-        }
-        if (c->comm) (void)ncclCommDestroy(c->comm);
-        for (auto& kv : c->plans) {
-            (void)rocfft_execution_info_destroy(kv.second.info);
-            (void)rocfft_plan_destroy(kv.second.plan);
-        }
-        for (auto& p : c->timing.pending) {
-            (void)hipEventDestroy(p.e0);
-            (void)hipEventDestroy(p.e1);
-        }
-        for (auto ev : c->timing.pool) (void)hipEventDestroy(ev);
-        for (auto& s : c->slot) s.buf.release();
-        for (auto& ps : c->planes) ps->buf.release();
-        c->planes.clear();
-        stager_release(c);
-        if (c->d2h_stream) (void)hipStreamDestroy(c->d2h_stream);
-        if (c->d2h_ready) (void)hipEventDestroy(c->d2h_ready);
-        for (DevBuf* b : {&c->d_kvec, &c->d_mean_all, &c->d_idx, &c->d_mean_g, &c->d_phase, &c->d_qwork,
-                          &c->d_fft_work, &c->d_tables, &c->d_absmax, &c->d_slab, &c->d_out, &c->d_aux, &c->d_sync,
-                          &c->d_qrows, &c->d_stage, &c->d_bin, &c->d_upload_max, &c->d_zeros, &c->d_kmap, &c->d_cols, &c->d_inten,
-                          &c->d_vdos_work, &c->d_vdos_pairs, &c->d_vdos_off, &c->d_vdos_mean, &c->d_vdos_part, &c->d_vdos_acc,
-                          &c->d_vdos_out, &c->d_modes_work, &c->d_modes_coef, &c->d_modes_out, &c->d_cov_slab, &c->d_cov_g, &c->d_cov_out, &c->d_peaks_spec, &c->d_peaks_bands,
-                          &c->d_peaks_part, &c->d_peaks_fit, &c->d_peaks_info, &c->d_rc_work, &c->d_rc_kappa, &c->d_rc_khat, &c->d_rc_idx,
-                          &c->d_rc_tiles, &c->d_rc_ent, &c->d_rc_slot, &c->d_rc_dest, &c->d_rc_bins, &c->d_rc_scale, &c->d_rc_acc,
-                          &c->d_rc_out, &c->d_rc_groups, &c->d_rc_part, &c->d_corr_tab, &c->d_corr_factor,
-                          &c->d_corr_scale, &c->d_corr_in, &c->d_corr_out, &c->d_rs_idx, &c->d_rs_items, &c->d_rs_part, &c->d_rs_acc, &c->d_msd_u,
-                          &c->d_msd_img, &c->d_msd_sums, &c->d_msd_offs, &c->d_msd_sizes, &c->d_msd_lags, &c->d_msd_out, &c->d_pair_c,
-                          &c->d_angle_work, &c->d_angle_edges})
-            b->release();
-        (void)hipStreamDestroy(c->stream);
-    }
+    { Guard g(c); }                                    // a call in flight on another thread ends first
+    (void)hipSetDevice(c->device);
     delete c;
+    return PSA_OK;
+}
+
+int psa_debug_device_buffers(int64_t* count, int64_t* bytes) {
+    PSA_REQUIRE(count != nullptr && bytes != nullptr, "null argument");
+    *count = g_devbuf_count.load();
+    *bytes = g_devbuf_bytes.load();
     return PSA_OK;
 }
 
@@ -310,59 +343,32 @@ int psa_set_k1(psa_ctx* c, int selector) {
 int psa_set_option(psa_ctx* c, int option, int64_t value) {
     PSA_TRY(enter(c));
     Guard g(c);
-    switch (option) {
-        case PSA_OPT_PLANES:
-            c->opt_planes = value != 0;
-            if (!c->opt_planes) {
-                PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
-                for (auto& ps : c->planes) ps->buf.release();
-                c->planes.clear();
-            }
-            return PSA_OK;
-        case PSA_OPT_PLANES_BUDGET:
-            PSA_REQUIRE(value >= 0, "negative plane budget");
-            c->opt_planes_budget = value;
-            return PSA_OK;
-        case PSA_OPT_PLANES_EAGER: c->opt_planes_eager = value != 0; return PSA_OK;
-        case PSA_OPT_PLANES_MIN_K:
-            PSA_REQUIRE(value >= 1, "PSA_OPT_PLANES_MIN_K must be >= 1");
-            c->opt_planes_min_k = value;
-            return PSA_OK;
-        case PSA_OPT_FOLD_PAIRS: c->opt_fold_pairs = value != 0; return PSA_OK;
-        case PSA_OPT_FFT_PRIME: c->opt_fft_prime = value != 0; return PSA_OK;
-        case PSA_OPT_K1_LOADER_WAVES: c->opt_k1_loader_waves = value != 0; return PSA_OK;
-        case PSA_OPT_K1_WIDE: c->opt_k1_wide = value != 0; return PSA_OK;
-        case PSA_OPT_K1_LOWRANK:
-            c->opt_k1_lowrank = value != 0;
-            if (!c->opt_k1_lowrank) {
-                PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
-                for (psa::DevBuf* b : {&c->d_lr_diff, &c->d_lr_qn, &c->d_lr_L, &c->d_lr_phi, &c->d_lr_f64}) b->release();
-            }
-            return PSA_OK;
-        case PSA_OPT_K1_LOWRANK_PAIR: c->opt_k1_lowrank_pair = value != 0; return PSA_OK;
-        case PSA_OPT_K1_LOWRANK_MIN_LOCAL:
-            PSA_REQUIRE(value >= 1, "PSA_OPT_K1_LOWRANK_MIN_LOCAL must be >= 1");
-            c->opt_k1_lowrank_min_local = value;
-            return PSA_OK;
-        case PSA_OPT_K1_LOWRANK_MIN_K:
-            PSA_REQUIRE(value >= 1, "PSA_OPT_K1_LOWRANK_MIN_K must be >= 1");
-            c->opt_k1_lowrank_min_k = value;
-            return PSA_OK;
-        case PSA_OPT_VDOS_WORK_BYTES:
-            PSA_REQUIRE(value >= 1, "PSA_OPT_VDOS_WORK_BYTES must be >= 1");
-            c->opt_vdos_work_bytes = value;
-            return PSA_OK;
-        case PSA_OPT_MODES_WORK_BYTES:
-            PSA_REQUIRE(value >= 1, "PSA_OPT_MODES_WORK_BYTES must be >= 1");
-            c->opt_modes_work_bytes = value;
-            return PSA_OK;
-        case PSA_OPT_DYNAMIC_WORK_BYTES:
-            PSA_REQUIRE(value >= 1, "PSA_OPT_DYNAMIC_WORK_BYTES must be >= 1");
-            c->opt_dynamic_work_bytes = value;
-            return PSA_OK;
+    for (const Option& o : OPTIONS) {
+        if (o.id != option) continue;
+        if (o.min == OPT_FLAG) value = value != 0;
+        else if (o.min == 0) PSA_REQUIRE(value >= 0, "negative plane budget");
+        else PSA_REQUIRE(value >= o.min, "%s must be >= %lld", o.name, (long long)o.min);
+        c->*o.field = value;
+        // switched off: what the option kept on the device goes
+        if (option == PSA_OPT_PLANES && !value) {
+            PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+            c->planes.clear();
+        } else if (option == PSA_OPT_K1_LOWRANK && !value) {
+            PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+            for (DevBuf* b : {&c->d_lr_diff, &c->d_lr_qn, &c->d_lr_L, &c->d_lr_phi, &c->d_lr_f64}) b->release();
+        }
+        return PSA_OK;
     }
     set_error("unknown option %d", option);
     return PSA_EINVAL;
+}
+
+int psa_option_info(int index, int32_t* option, int64_t* default_value, const char** name) {
+    PSA_REQUIRE(index >= 0 && index < (int)std::size(OPTIONS), "no option at index %d", index);
+    if (option) *option = OPTIONS[index].id;
+    if (default_value) *default_value = OPTIONS[index].def;
+    if (name) *name = OPTIONS[index].name;
+    return PSA_OK;
 }
 
 int psa_device_info(psa_ctx* c, char* name, int name_len, int* compute_units, int64_t* hbm_bytes) {

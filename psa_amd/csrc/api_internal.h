@@ -84,7 +84,12 @@ struct StageTimer {
             ok = true;
     }
     ~StageTimer() {
-        if (ok && hipEventRecord(e1, c->stream) == hipSuccess) ts.pending.push_back({stage, e0, e1});
+        if (ok && hipEventRecord(e1, c->stream) == hipSuccess) {
+            ts.pending.push_back({stage, e0, e1});
+            return;
+        }
+        for (hipEvent_t ev : {e0, e1})                    // not booked: the events go back to the pool
+            if (ev) ts.pool.push_back(ev);
     }
 };
 

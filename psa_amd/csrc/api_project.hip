@@ -96,9 +96,7 @@ void drop_stale_planes(psa_ctx* c) {
     v.erase(std::remove_if(v.begin(), v.end(),
                            [&](const std::unique_ptr<PlaneSet>& ps) {
                                const DataSlot& s = c->slot[ps->slot];
-                               if (s.valid && s.generation == ps->generation) return false;
-                               ps->buf.release();
-                               return true;
+                               return !(s.valid && s.generation == ps->generation);
                            }),
             v.end());
 }
@@ -111,7 +109,6 @@ bool evict_one_plane_set(psa_ctx* c) {
             (victim < 0 || c->planes[i]->last_use < c->planes[victim]->last_use))
             victim = (int)i;
     if (victim < 0) return false;
-    c->planes[victim]->buf.release();
     c->planes.erase(c->planes.begin() + victim);
     return true;
 }
@@ -832,9 +829,12 @@ struct Timeline {
             float ms = -1.f;
             (void)hipEventElapsedTime(&ms, e0, m.ev);
             std::fprintf(stderr, "[psa timeline] %-22s %5d %10.3f %10.3f\n", m.what, m.block, ms, m.host_ms);
-            (void)hipEventDestroy(m.ev);
         }
         std::fprintf(stderr, "[psa timeline] %-22s %5s %10s %10.3f\n", "return", "", "", t_end);
+    }
+    ~Timeline() {                                                 // whichever way the call ends
+        for (auto& m : marks)
+            if (m.ev) (void)hipEventDestroy(m.ev);
         if (e0) (void)hipEventDestroy(e0);
     }
 };

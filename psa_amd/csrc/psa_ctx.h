@@ -66,19 +66,42 @@ void set_error(const char* fmt, ...);
         if (rc_ != PSA_OK) return rc_;                                                   \
     } while (0)
 
-// grow-only device allocation
+// grow-only device allocation, freed with its owner (release: the early free).  Every live one is counted, process-wide
+// (psa_debug_device_buffers)
 struct DevBuf {
     void*  ptr = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : ptr(std::exchange(o.ptr, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            ptr = std::exchange(o.ptr, nullptr);
+            cap = std::exchange(o.cap, 0);
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int reserve(size_t bytes);
     void release();
     template <class T> T* as() const { return static_cast<T*>(ptr); }
 };
 
+// a rocFFT plan and its execution info, destroyed (info, then plan) with their owner
 struct FftPlan {
     rocfft_plan           plan = nullptr;
     rocfft_execution_info info = nullptr;
     size_t                work_bytes = 0;
+    FftPlan() = default;
+    FftPlan(FftPlan&& o) noexcept
+        : plan(std::exchange(o.plan, nullptr)), info(std::exchange(o.info, nullptr)), work_bytes(std::exchange(o.work_bytes, 0)) {}
+    FftPlan& operator=(FftPlan&& o) noexcept {
+        std::swap(plan, o.plan);
+        std::swap(info, o.info);
+        std::swap(work_bytes, o.work_bytes);
+        return *this;
+    }
+    ~FftPlan();
 };
 
 struct DataSlot {
@@ -186,7 +209,14 @@ struct Stager {
 enum { PSA_T_H2D = 0, PSA_T_PHASE, PSA_T_PROJECT, PSA_T_FFT, PSA_T_EPILOGUE, PSA_T_GATHER,
        PSA_T_TRANSPOSE, PSA_T_D2H, PSA_T_COUNT };
 
+// Everything the context opens it owns: the buffers and the rocFFT plans free themselves as members, ~psa_ctx
+// (api_core.hip) closes the rest first, in the order it documents.
 struct psa_ctx {
+    psa_ctx();                  // the options' defaults, from the table
+    ~psa_ctx();
+    psa_ctx(const psa_ctx&) = delete;
+    psa_ctx& operator=(const psa_ctx&) = delete;
+
     int         device = 0;
     hipStream_t stream = nullptr;
     std::mutex  mu;
@@ -213,7 +243,7 @@ struct psa_ctx {
     std::vector<std::unique_ptr<psa::PlaneSet>> planes;
     std::vector<uint64_t> seen_groups;        // hashes of index-list groups projected once already
     uint64_t plane_tick = 0, plane_call_mark = 0;   // sets touched since the mark belong to the call in progress
-    int64_t  opt_planes = 1, opt_planes_budget = 0, opt_planes_eager = 0, opt_planes_min_k = 17;
+    int64_t  opt_planes, opt_planes_budget, opt_planes_eager, opt_planes_min_k;   // the options: defaults from the table (api_core.hip)
     psa::Stager stager;
     hipStream_t d2h_stream = nullptr;         // result blocks leave while the next block is projected
     hipEvent_t  d2h_ready = nullptr;
@@ -232,7 +262,7 @@ struct psa_ctx {
     int64_t              out_K = 0;
     std::vector<int32_t> kmap;
     psa::DevBuf          d_kmap, d_cols;
-    int64_t              opt_fold_pairs = 1;
+    int64_t              opt_fold_pairs;
     psa::DevBuf          d_inten;                 // (T,out_K) f32: sum_c |d_out|^2 of a finalized complex result
     bool                 inten_valid = false;
     bool    slab_valid = false, out_valid = false;
@@ -245,14 +275,14 @@ struct psa_ctx {
     std::thread  fft_primer;
     psa::FftPlan primed;
     int64_t      primed_T = 0;
-    int64_t      opt_fft_prime = 1;
-    int64_t      opt_k1_wide = 1;               // PSA_OPT_K1_WIDE: 256-row M blocks (k1_planes_wide.hip) where the k-list fills them (k1_planes_block_rows)
-    int64_t      opt_k1_loader_waves = 1;       // PSA_OPT_K1_LOADER_WAVES: 128-row M blocks through k1_planes_lw.hip
-    int64_t      opt_k1_lowrank = 1;            // PSA_OPT_K1_LOWRANK: k-paths through the node rows + D pass (api_lowrank.hip)
-    int64_t      opt_k1_lowrank_min_k = 256;    // PSA_OPT_K1_LOWRANK_MIN_K: shortest whole k-list it serves
-    int64_t      opt_k1_lowrank_min_local = 128; // PSA_OPT_K1_LOWRANK_MIN_LOCAL: shortest part of it one launch serves
+    int64_t      opt_fft_prime;
+    int64_t      opt_k1_wide;                   // PSA_OPT_K1_WIDE: 256-row M blocks (k1_planes_wide.hip) where the k-list fills them (k1_planes_block_rows)
+    int64_t      opt_k1_loader_waves;           // PSA_OPT_K1_LOADER_WAVES: 128-row M blocks through k1_planes_lw.hip
+    int64_t      opt_k1_lowrank;                // PSA_OPT_K1_LOWRANK: k-paths through the node rows + D pass (api_lowrank.hip)
+    int64_t      opt_k1_lowrank_min_k;          // PSA_OPT_K1_LOWRANK_MIN_K: shortest whole k-list it serves
+    int64_t      opt_k1_lowrank_min_local;       // PSA_OPT_K1_LOWRANK_MIN_LOCAL: shortest part of it one launch serves
     int64_t      lowrank_launches = 0;          // projection launches that took the route (psa_k1_lowrank_launches)
-    int64_t      opt_k1_lowrank_pair = 1;       // PSA_OPT_K1_LOWRANK_PAIR: lists with one 512-row D block through k1_lowrank_pair.hip
+    int64_t      opt_k1_lowrank_pair;           // PSA_OPT_K1_LOWRANK_PAIR: lists with one 512-row D block through k1_lowrank_pair.hip
     int64_t      lowrank_pair_launches = 0;     // ... of which the pair launch served (psa_k1_lowrank_pair_launches)
     // its D image, node projections, the combine's L and phi, fp64 inputs (the node table goes into d_phase);
     // released when the route is switched off
@@ -275,7 +305,7 @@ struct psa_ctx {
     // to opt_vdos_work_bytes (PSA_OPT_VDOS_WORK_BYTES); the pair list, the groups' pair offsets, the mean, the chunk
     // partials, the float64 accumulator and the float32 result.  All kept between calls.
     psa::DevBuf  d_vdos_work, d_vdos_pairs, d_vdos_off, d_vdos_mean, d_vdos_part, d_vdos_acc, d_vdos_out;
-    int64_t      opt_vdos_work_bytes = (int64_t)1 << 30;
+    int64_t      opt_vdos_work_bytes;
 
     // mode-projected SED (psa_sed_modes, psa_sed_modes_welch; api_modes.hip): the stacked spectra (B, kb, 3, T) of one
     // block of k-vectors, held to opt_modes_work_bytes (PSA_OPT_MODES_WORK_BYTES); the packed coefficient table
@@ -283,7 +313,7 @@ struct psa_ctx {
     // (B, bk, 3, bs, L) of a sub-block, q and d_seg together within the budget.
     // All kept between calls.
     psa::DevBuf  d_modes_work, d_modes_coef, d_modes_out;
-    int64_t      opt_modes_work_bytes = (int64_t)4 << 30;
+    int64_t      opt_modes_work_bytes;
 
     // spectral covariance (psa_sed_covariance; api_covariance.hip): the stacked spectra lie in d_modes_work, under the same
     // budget as the partial slabs [k][chunk][slot][pair][part][256] of a block; the weight table (n_w, T); the (n_w, K, 3B, 3B)
@@ -311,7 +341,7 @@ struct psa_ctx {
     //   groups, part   the self part's columns (first vector, column) and its chunks' float64 partial sums
     psa::DevBuf  d_rc_work, d_rc_kappa, d_rc_khat, d_rc_idx, d_rc_tiles, d_rc_ent, d_rc_slot, d_rc_dest, d_rc_bins, d_rc_scale,
                  d_rc_acc, d_rc_out, d_rc_groups, d_rc_part;
-    int64_t      opt_dynamic_work_bytes = (int64_t)4 << 30;
+    int64_t      opt_dynamic_work_bytes;
 
     // time correlations on that lattice (psa_lattice_correlations, psa_self_correlations; api_correlation.hip): they run
     // the set above with zero-padded rows of P >= L + n_lags - 1 and add the back-transform's cosine table

@@ -17,6 +17,7 @@ import angle64 as A
 import angle_cases as Q
 import pair64 as R
 import pair_cases as P
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -25,19 +26,11 @@ TILE = 256
 PER_ORIGIN = 1040                                                          # work bytes per atom and origin
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, 4 << 30)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-    engine.set_k1(_hip.K1_AUTO)
-
-
 @pytest.fixture(autouse=True)
 def _clean(engine):
-    _defaults(engine)
+    reset(engine)
     yield
-    _defaults(engine)
+    reset(engine)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -261,7 +254,7 @@ def test_permutations_budgets_and_repeats(engine):
         engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, PER_ORIGIN * n * origins + 5)
         assert _equal(whole, engine.angle_histogram(Q.TRICLINIC, rc, 180, listing))
     # one species of all atoms is the sum over the two, with one cut-off
-    _defaults(engine)
+    reset(engine)
     two = engine.angle_histogram(Q.TRICLINIC, 4.1, 180, listing)
     one = engine.angle_histogram(Q.TRICLINIC, 4.1, 180)
     assert np.array_equal(one[0][0, 0], two[0].sum(axis=(0, 1))) and one[2][0] == two[2].sum() == 0
@@ -305,7 +298,7 @@ def test_many_tiles(engine):
     assert _equal(two, engine.angle_histogram(Q.TRICLINIC, r_cut, 45, [rng.permutation(g) for g in listing]))
     engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, PER_ORIGIN * n + 3)     # one origin per block
     assert _equal(two, engine.angle_histogram(Q.TRICLINIC, r_cut, 45, listing))
-    _defaults(engine)
+    reset(engine)
     # 300 centres spread over all tiles against every 8th of the rest: the reference's sets, and the same pairs in the full call
     pick = np.sort(order[:300])
     rest = np.setdiff1d(np.arange(n), pick).astype(np.int32)

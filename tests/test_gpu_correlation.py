@@ -16,6 +16,7 @@ import correlation64 as R
 import correlation_cases as CC
 import lattice64 as L64
 import self_cases as S
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -26,19 +27,11 @@ N0 = np.array([2, -1, 3], np.int32)
 FIELDS = ("density", "longitudinal", "transverse")
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, 4 << 30)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-    engine.set_k1(_hip.K1_AUTO)
-
-
 @pytest.fixture(autouse=True)
 def _clean(engine):
-    _defaults(engine)
+    reset(engine)
     yield
-    _defaults(engine)
+    reset(engine)
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -15,20 +15,12 @@ import numpy as np
 import pytest
 
 from conftest import rel_max
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
 B_SITES = 8
 MASSES = {1: 1.0, 2: 207.0}
-
-
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_MODES_WORK_BYTES, 4 << 30)
-    engine.set_option(_hip.OPT_K1_LOWRANK, 1)
-    engine.set_option(_hip.OPT_PLANES_EAGER, 0)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
 
 
 # ------------------------------------------------------------------------------------------------- 1. exact data
@@ -120,9 +112,9 @@ def syn(engine):
         out[T] = dict(traj=tr, calcs=calcs, groups=site_groups(np.arange(tr.n_atoms) % B_SITES), mean=O.mean_positions(tr.positions),
                       weights=mass_weights(tr.types, MASSES),
                       klists={"path": path, "scattered": (np.linalg.norm(scattered, axis=1).astype(np.float32), scattered)})
-    _defaults(engine)
+    reset(engine)
     yield out
-    _defaults(engine)
+    reset(engine)
     engine.invalidate()
 
 
@@ -277,7 +269,7 @@ def test_planted_modes_are_recovered(engine):
                 assert sin <= 2 * dist / gap + 1e-6
         print(f"frequencies against mode_vectors(cov64): max difference {np.max(np.abs(mv.frequency - ref.frequency)) / df:.2e} df")
     finally:
-        _defaults(engine)
+        reset(engine)
         engine.invalidate()
 
 
@@ -308,7 +300,7 @@ def test_blocking_determinism_and_isolation(engine, syn):
         with pytest.raises(_hip.PsaHipError, match=str(per_k)):
             run()
     finally:
-        _defaults(engine)
+        reset(engine)
     # the SED entry points and the mode projection give the bits they gave before the covariance calls
     assert np.array_equal(calc.calculate(mags, vecs).sed.view(np.uint8), sed0.view(np.uint8))
     assert np.array_equal(calc.calculate_mode_sed(mags, vecs, e, groups).sed.view(np.uint32), phi0.view(np.uint32))

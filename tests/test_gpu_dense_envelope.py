@@ -23,6 +23,7 @@ import pytest
 import dense_cases as D
 from conftest import rel_max
 from ref64 import gamma, intensity64, project64, row_rel, scale_B, sed64
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -59,21 +60,12 @@ def _select(engine, form, K):
         engine.set_option(opt, val)
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_k1(_hip.K1_AUTO)
-    for opt, val in ((_hip.OPT_PLANES, 1), (_hip.OPT_PLANES_EAGER, 0), (_hip.OPT_PLANES_MIN_K, 17), (_hip.OPT_K1_WIDE, 1),
-                     (_hip.OPT_K1_LOADER_WAVES, 1)):
-        engine.set_option(opt, val)
-    engine.set_atom_weights(None)
-
-
 @pytest.fixture
 def forced(engine):
     try:
         yield engine
     finally:
-        _defaults(engine)
+        reset(engine)
         for slot in (0, 1):
             engine.release(slot)
         engine.invalidate()

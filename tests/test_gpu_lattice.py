@@ -19,25 +19,18 @@ import dynamic_cases
 import lattice64 as L64
 import lattice_cases as C
 from conftest import rel_max
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
 BOXES = {"cubic": C.CUBIC, "triclinic": C.TRICLINIC}
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, 4 << 30)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-    engine.set_k1(_hip.K1_AUTO)
-
-
 @pytest.fixture(autouse=True)
 def _clean(engine):
-    _defaults(engine)
+    reset(engine)
     yield
-    _defaults(engine)
+    reset(engine)
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -5,16 +5,9 @@ import numpy as np
 import pytest
 
 from conftest import rel_max
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
-
-
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_K1_LOWRANK, 1)
-    engine.set_option(_hip.OPT_K1_LOWRANK_MIN_K, 256)
-    engine.set_option(_hip.OPT_K1_LOWRANK_MIN_LOCAL, 128)
-    engine.set_option(_hip.OPT_PLANES_EAGER, 0)
 
 
 @pytest.fixture(scope="module")
@@ -29,7 +22,7 @@ def c3(engine):
                                     np.zeros(3, np.float32), spec.dt_ps), *spec.cells)
     _, vecs = calc.get_k_path(req["direction"], req["bz_coverage"], req["n_k"])
     yield dict(spec=spec, r0=r0, types=types, vecs=np.asarray(vecs, np.float32))
-    _defaults(engine)
+    reset(engine)
     engine.release(_hip.SLOT_VELOCITIES)
 
 
@@ -68,7 +61,7 @@ def test_config3_lowrank_against_dense_and_split(engine, c3):
     assert n == 0
     np.testing.assert_allclose(np.sum(np.abs(got) ** 2, axis=-1), inten_dense, rtol=1e-6, atol=0)
     assert rel_max(got, whole) <= 1e-6
-    _defaults(engine)
+    reset(engine)
 
 
 def test_config3_incoherent_two_groups(engine, c3):
@@ -87,7 +80,7 @@ def test_config3_incoherent_two_groups(engine, c3):
     err = rel_max(out[1], out[0])
     print(f"incoherent lowrank vs dense rel_max {err:.3e}")
     assert err <= 2e-6
-    _defaults(engine)
+    reset(engine)
 
 
 @pytest.mark.parametrize("case", ["all_atoms", "index_dups", "displacements"])
@@ -130,5 +123,5 @@ def test_odd_shapes_against_dense(engine, case):
         print(f"{case}: route taken {taken[1]}, lowrank vs dense rel_max {err:.3e}")
         assert err <= 1e-6
     finally:
-        _defaults(engine)
+        reset(engine)
         engine.release(slot)

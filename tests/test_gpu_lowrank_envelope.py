@@ -16,6 +16,7 @@ import pytest
 from conftest import rel_max
 from lowrank_cases import D_LIMIT, DIRECTIONS, LIMITS, N_ATOMS, geometry, mass_weights
 from ref64 import intensity64, row_rel, sed64
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -30,21 +31,13 @@ def _force(engine):
         engine.set_option(opt, val)
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    for opt, val in ((_hip.OPT_K1_LOWRANK, 1), (_hip.OPT_K1_LOWRANK_MIN_K, 256), (_hip.OPT_K1_LOWRANK_MIN_LOCAL, 128),
-                     (_hip.OPT_PLANES_EAGER, 0), (_hip.OPT_PLANES_MIN_K, 17)):
-        engine.set_option(opt, val)
-    engine.set_atom_weights(None)
-
-
 @pytest.fixture
 def forced(engine):
     _force(engine)
     try:
         yield engine
     finally:
-        _defaults(engine)
+        reset(engine)
         engine.release(SLOT)
 
 

@@ -21,7 +21,8 @@ import numpy as np
 import pytest
 
 import lowrank_env_cases as E
-from test_gpu_lowrank_envelope import _defaults, _force
+from engine_state import reset
+from test_gpu_lowrank_envelope import _force
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +41,7 @@ def forced(engine):
         yield engine
     finally:
         engine.set_option(_hip.OPT_K1_LOWRANK_PAIR, 1)
-        _defaults(engine)
+        reset(engine)
         for slot in (0, 1):
             engine.release(slot)
         engine.invalidate()

@@ -27,7 +27,8 @@ import pytest
 import lowrank_env_cases as E
 from lowrank_cases import D_LIMIT
 from ref64 import gamma, project64, scale_B
-from test_gpu_lowrank_envelope import _defaults, _force
+from engine_state import reset
+from test_gpu_lowrank_envelope import _force
 
 pytestmark = pytest.mark.gpu
 
@@ -47,7 +48,7 @@ def forced(engine):
     try:
         yield engine
     finally:
-        _defaults(engine)
+        reset(engine)
         for slot in (0, 1):
             engine.release(slot)
         engine.invalidate()

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_max
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -32,15 +33,6 @@ def _trajectory(cells=(4, 4, 4), T=256, seed=3):
                       np.zeros(3, np.float32), spec.dt_ps), spec.cells
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_MODES_WORK_BYTES, 4 << 30)
-    engine.set_option(_hip.OPT_K1_LOWRANK, 1)
-    engine.set_option(_hip.OPT_PLANES_EAGER, 0)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-
-
 @pytest.fixture(scope="module")
 def syn(engine):
     from oracle import psa_oracle as O
@@ -55,9 +47,9 @@ def syn(engine):
         out[T] = dict(traj=tr, calcs=calcs, groups=site_groups(np.arange(tr.n_atoms) % B_SITES), mean=O.mean_positions(tr.positions),
                       weights=mass_weights(tr.types, MASSES),
                       klists={"path": path, "scattered": (np.linalg.norm(scattered, axis=1).astype(np.float32), scattered)})
-    _defaults(engine)
+    reset(engine)
     yield out
-    _defaults(engine)
+    reset(engine)
     engine.invalidate()
 
 
@@ -230,7 +222,7 @@ def test_lowrank_route_on_a_k_path(engine, syn):
         assert taken == B_SITES
         assert err <= 1e-5 and err_d <= 1e-5
     finally:
-        _defaults(engine)
+        reset(engine)
 
 
 # ------------------------------------------------------------------------------------------------- 4. blocking, isolation
@@ -263,7 +255,7 @@ def test_blocking_determinism_and_budget(engine, syn):
         with pytest.raises(_hip.PsaHipError, match=str(per_k)):
             calc.calculate_mode_sed(mags, vecs, eig, groups)
     finally:
-        _defaults(engine)
+        reset(engine)
     assert np.array_equal(calc.calculate_mode_sed(mags, vecs, eig, groups).sed.view(np.uint32), got["one block"][0].view(np.uint32))
 
 
@@ -366,7 +358,7 @@ def test_abi_errors(engine, syn):
     try:
         assert str(24 * 2 * T).encode() in refused("budget below one k-vector")
     finally:
-        _defaults(engine)
+        reset(engine)
     out = np.zeros((T, K, M), np.float32)                                     # the context is usable afterwards
     rc, _ = call(out=out)
     assert rc == 0

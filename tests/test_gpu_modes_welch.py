@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_max
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -35,15 +36,6 @@ def _trajectory(cells=(4, 4, 4), T=256, seed=3):
                       np.zeros(3, np.float32), spec.dt_ps), spec.cells
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_MODES_WORK_BYTES, 4 << 30)
-    engine.set_option(_hip.OPT_K1_LOWRANK, 1)
-    engine.set_option(_hip.OPT_PLANES_EAGER, 0)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-
-
 @pytest.fixture(scope="module")
 def syn(engine):
     from oracle import psa_oracle as O
@@ -58,9 +50,9 @@ def syn(engine):
         out[T] = dict(traj=tr, calcs=calcs, groups=site_groups(np.arange(tr.n_atoms) % B_SITES), mean=O.mean_positions(tr.positions),
                       weights=mass_weights(tr.types, MASSES),
                       klists={"path": path, "scattered": (np.linalg.norm(scattered, axis=1).astype(np.float32), scattered)})
-    _defaults(engine)
+    reset(engine)
     yield out
-    _defaults(engine)
+    reset(engine)
     engine.invalidate()
 
 
@@ -277,7 +269,7 @@ def test_blocking_determinism_and_budget(engine, syn):
             calc.calculate_mode_sed(mags, vecs, eig, groups, segments=seg)
         assert engine.segment_length == 0
     finally:
-        _defaults(engine)
+        reset(engine)
     assert _bits(calc.calculate_mode_sed(mags, vecs, eig, groups, segments=seg).sed) == _bits(got["one block"][0])
 
 
@@ -302,7 +294,7 @@ def test_lowrank_route_on_a_k_path(engine, syn):
         assert taken == B_SITES
         assert err <= 1e-5
     finally:
-        _defaults(engine)
+        reset(engine)
 
 
 # ------------------------------------------------------------------------------------------------- 5. fits
@@ -474,7 +466,7 @@ def test_abi_errors(engine, syn):
         groups = [np.array([0, 1]), np.array([2, 3])]
         assert rel_max(out, W64.mode_welch64(tr.velocities, s["mean"], vecs, groups, good_eig, seg)[0]) <= 1e-5
     finally:
-        _defaults(engine)
+        reset(engine)
     # the debug entry's own argument check
     S, e = W64.kernel_case(1, 3, 16, 3, 1)
     o = np.zeros((16, 3, 3), np.float32)

@@ -14,6 +14,7 @@ import pytest
 
 import msd64 as R
 import msd_cases as M
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -21,19 +22,11 @@ BOXES = {"cubic": M.CUBIC, "triclinic": M.TRICLINIC}
 T = 250
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, 4 << 30)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-    engine.set_k1(_hip.K1_AUTO)
-
-
 @pytest.fixture(autouse=True)
 def _clean(engine):
-    _defaults(engine)
+    reset(engine)
     yield
-    _defaults(engine)
+    reset(engine)
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -19,6 +19,7 @@ import order64 as O
 import order_cases as C
 import pair64 as R
 import pair_cases as P
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -27,19 +28,11 @@ PER_ORIGIN = 1040                                                          # wor
 EIGHT = (1, 2, 3, 5, 7, 8, 10, 12)
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, 4 << 30)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-    engine.set_k1(_hip.K1_AUTO)
-
-
 @pytest.fixture(autouse=True)
 def _clean(engine):
-    _defaults(engine)
+    reset(engine)
     yield
-    _defaults(engine)
+    reset(engine)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -224,7 +217,7 @@ def test_budgets_blocks_permutations_and_repeats(engine):
         assert _equal(whole, engine.bond_order(box, rc, EIGHT, 200, listing, per_atom=True)), origins
         engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, PER_ORIGIN * n * origins + 5)
         assert _equal(whole[:4], engine.bond_order(box, rc, EIGHT, 200, listing)[:4]), origins
-    _defaults(engine)
+    reset(engine)
     rng = np.random.default_rng(8)
     perms = [rng.permutation(len(g)) for g in listing]
     moved = engine.bond_order(box, rc, EIGHT, 200, [g[p] for g, p in zip(listing, perms)], per_atom=True)

@@ -14,6 +14,7 @@ import pytest
 
 import pair64 as R
 import pair_cases as P
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -21,19 +22,11 @@ BOXES = {"cubic": P.CUBIC, "triclinic": P.TRICLINIC}
 TILE = P.TILE
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, 4 << 30)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-    engine.set_k1(_hip.K1_AUTO)
-
-
 @pytest.fixture(autouse=True)
 def _clean(engine):
-    _defaults(engine)
+    reset(engine)
     yield
-    _defaults(engine)
+    reset(engine)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -214,7 +207,7 @@ def test_permutations_budgets_and_repeats(engine):
         engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, 24 * n * origins + 5)
         assert np.array_equal(whole, engine.pair_histogram(P.TRICLINIC, lags, dr, 64, listing))
     # one species of all atoms is the sum over the two
-    _defaults(engine)
+    reset(engine)
     one = engine.pair_histogram(P.TRICLINIC, lags, dr, 64)
     assert np.array_equal(one[:, 0, 0], whole.sum(axis=(1, 2)))
 
@@ -250,7 +243,7 @@ def test_runs_of_beta_tiles(engine):
     pick = np.sort(order[:300])
     rest = np.setdiff1d(np.arange(n), pick).astype(np.int32)
     got = engine.pair_histogram(P.TRICLINIC, [1], dr, n_r, [pick.astype(np.int32), rest]).astype(np.int64)
-    _defaults(engine)
+    reset(engine)
     ref, allowed, borderline, total = P.reference(pos, P.TRICLINIC, [pick, rest[::40]], [1], 1, dr, n_r)
     sub = engine.pair_histogram(P.TRICLINIC, [1], dr, n_r, [pick.astype(np.int32), rest[::40]]).astype(np.int64)
     assert borderline <= P.cap(n_r) * total and np.all(np.abs(sub - ref) <= allowed)

@@ -15,6 +15,7 @@ import partial64 as R
 import partial_cases as C
 import power64
 import power_cases as P
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -22,19 +23,11 @@ BOXES = {"cubic": LC.CUBIC, "triclinic": LC.TRICLINIC}
 FIELDS = ("density", "longitudinal", "transverse")
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, 4 << 30)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-    engine.set_k1(_hip.K1_AUTO)
-
-
 @pytest.fixture(autouse=True)
 def _clean(engine):
-    _defaults(engine)
+    reset(engine)
     yield
-    _defaults(engine)
+    reset(engine)
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import fit64 as F64
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -233,11 +234,6 @@ def _trajectory(cells=(4, 4, 4), T=256, seed=3):
                       np.zeros(3, np.float32), spec.dt_ps), spec.cells
 
 
-def _defaults(engine):
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-
-
 @pytest.fixture(scope="module")
 def syn(engine):
     import modes64 as M64
@@ -250,9 +246,9 @@ def syn(engine):
         out[T] = dict(traj=tr, calc=calc, groups=site_groups(np.arange(tr.n_atoms) % B_SITES), mags=mags, vecs=vecs,
                       eig=M64.random_unitary(np.random.default_rng(5), len(vecs), B_SITES, 5),
                       weights=mass_weights(tr.types, {1: 1.0, 2: 207.0}))
-    _defaults(engine)
+    reset(engine)
     yield out
-    _defaults(engine)
+    reset(engine)
     engine.invalidate()
 
 

@@ -14,25 +14,18 @@ import pytest
 import lattice_cases as C
 import power64 as R
 import power_cases as P
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
 ROWS = ("density", "longitudinal", "transverse")
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, 4 << 30)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-    engine.set_k1(_hip.K1_AUTO)
-
-
 @pytest.fixture(autouse=True)
 def _clean(engine):
-    _defaults(engine)
+    reset(engine)
     yield
-    _defaults(engine)
+    reset(engine)
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -10,6 +10,7 @@ import pytest
 import lattice64 as L64
 import lattice_cases as LC
 import partial_cases as C
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -17,18 +18,11 @@ EDGES = np.array([0.05, 0.2, 0.45, 0.65, 0.85, 1.0, 1.15])
 SMALL = 256 << 10       # bytes: 28 vectors of q with currents (8 KiB each), 14 of two species; one or two units of the self part
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, 4 << 30)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-
-
 @pytest.fixture(autouse=True)
 def _clean(engine):
-    _defaults(engine)
+    reset(engine)
     yield
-    _defaults(engine)
+    reset(engine)
 
 
 @pytest.fixture(scope="module", autouse=True)

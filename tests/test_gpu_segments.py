@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_max
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -22,24 +23,14 @@ def _trajectory(cells=(4, 4, 4), T=256, seed=3):
                       np.zeros(3, np.float32), spec.dt_ps), spec.cells
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_k1(_hip.K1_AUTO)
-    for opt, val in ((_hip.OPT_PLANES, 1), (_hip.OPT_PLANES_EAGER, 0), (_hip.OPT_K1_LOWRANK, 1), (_hip.OPT_K1_LOWRANK_MIN_K, 256),
-                     (_hip.OPT_K1_LOWRANK_MIN_LOCAL, 128), (_hip.OPT_FOLD_PAIRS, 1), (_hip.OPT_K1_WIDE, 1)):
-        engine.set_option(opt, val)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-
-
 @pytest.fixture(scope="module")
 def syn(engine):
     from psa_amd import SEDCalculator
     tr, cells = _trajectory()
     calcs = {disp: SEDCalculator(tr, *cells, use_displacements=disp).attach(engine=engine) for disp in (False, True)}
-    _defaults(engine)
+    reset(engine)
     yield dict(traj=tr, calcs=calcs)
-    _defaults(engine)
+    reset(engine)
     engine.invalidate()
 
 
@@ -131,7 +122,7 @@ def test_folded_pairs(engine, syn):
             assert folded.sed.shape == flat.sed.shape == (64, 36)
             assert rel_max(folded.sed, flat.sed) <= 1e-6
     finally:
-        _defaults(engine)
+        reset(engine)
 
 
 def test_lowrank_route(engine, syn):
@@ -149,7 +140,7 @@ def test_lowrank_route(engine, syn):
         ref = welch_intensity64(data, mean, vecs, groups, seg.window_array(), 64, 32)
         assert rel_max(got.sed, ref) <= 1e-5
     finally:
-        _defaults(engine)
+        reset(engine)
 
 
 def test_first_call_and_no_leak(engine, syn):

@@ -17,6 +17,7 @@ import lattice64 as L64
 import self64
 import self_cases as S
 from conftest import rel_max
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -27,19 +28,11 @@ SEGMENTS = {"none": None, "hann_64_32": (64, 32, "hann"), "boxcar_64_64": (64, 6
 N0 = np.array([2, -1, 3], np.int32)
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, 4 << 30)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-    engine.set_k1(_hip.K1_AUTO)
-
-
 @pytest.fixture(autouse=True)
 def _clean(engine):
-    _defaults(engine)
+    reset(engine)
     yield
-    _defaults(engine)
+    reset(engine)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -295,13 +288,13 @@ def test_blockings_repeat_max_atoms(engine, walk):
     ulp = np.spacing(np.maximum(np.abs(per_one), np.abs(per_cut)))
     print(f"per vector, two blockings: largest difference {np.max(np.abs(per_one - per_cut) / ulp):.2f} ulp")
     assert np.all(np.abs(per_one - per_cut) <= ulp)
-    _defaults(engine)
+    reset(engine)
     # an empty atom set gives zeros
     engine.set_segments(s)
     assert not engine.self_spectra(inv, half, bins, 6, np.zeros(0, np.int32)).any()
     assert not engine.self_spectra(inv, half, None, 0, np.zeros(0, np.int32)).any()
     assert engine.debug_self_series(inv, half, np.zeros(0, np.int32)).shape == (0, half.shape[0], T)
-    _defaults(engine)
+    reset(engine)
     # max_atoms
     calc = _calculator(engine, walk["pos"], walk["box"])
     some = calc.calculate_self_spectra(walk["full"], atom_weights=walk["w"], segments=s, max_atoms=40, seed=0)

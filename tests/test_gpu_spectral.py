@@ -29,28 +29,18 @@ from conftest import rel_max
 from ref64 import intensity64, project64, row_rel, scale_B, sed64
 from test_gpu_dense_envelope import TOL, TOL_ROW
 from welch64 import welch_intensity64
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_k1(_hip.K1_AUTO)
-    for opt, val in ((_hip.OPT_PLANES, 1), (_hip.OPT_PLANES_EAGER, 0), (_hip.OPT_PLANES_MIN_K, 17), (_hip.OPT_K1_LOWRANK, 1),
-                     (_hip.OPT_K1_LOWRANK_MIN_K, 256), (_hip.OPT_K1_LOWRANK_MIN_LOCAL, 128), (_hip.OPT_FOLD_PAIRS, 1),
-                     (_hip.OPT_K1_WIDE, 1), (_hip.OPT_K1_LOADER_WAVES, 1)):
-        engine.set_option(opt, val)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-
-
 @pytest.fixture
 def eng(engine):
-    _defaults(engine)
+    reset(engine)
     try:
         yield engine
     finally:
-        _defaults(engine)
+        reset(engine)
         for slot in (0, 1):
             engine.release(slot)
         engine.invalidate()

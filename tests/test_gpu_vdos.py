@@ -10,6 +10,7 @@ import pytest
 
 import vdos_cases as V
 from conftest import rel_max
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -26,21 +27,14 @@ def _trajectory(cells=(4, 4, 4), T=256, seed=3):
                       np.zeros(3, np.float32), spec.dt_ps), spec.cells
 
 
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_VDOS_WORK_BYTES, 1 << 30)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
-
-
 @pytest.fixture(scope="module")
 def syn(engine):
     from psa_amd import SEDCalculator
     tr, cells = _trajectory()
     calcs = {disp: SEDCalculator(tr, *cells, use_displacements=disp).attach(engine=engine) for disp in (False, True)}
-    _defaults(engine)
+    reset(engine)
     yield dict(traj=tr, calcs=calcs)
-    _defaults(engine)
+    reset(engine)
     engine.invalidate()
 
 
@@ -194,7 +188,7 @@ def test_blocking_invariance_and_determinism(engine, syn):
         with pytest.raises(_hip.PsaHipError, match=str(unit)):
             calc.calculate_vdos(**kw)
     finally:
-        _defaults(engine)
+        reset(engine)
     assert np.array_equal(whole, calc.calculate_vdos(**kw).dos)
 
 

@@ -26,24 +26,18 @@ import pytest
 
 import vdos_cases as V
 from conftest import rel_max
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
-
-
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_option(_hip.OPT_VDOS_WORK_BYTES, V.DEFAULT_BUDGET)
-    engine.set_atom_weights(None)
-    engine.set_segments(None)
 
 
 @pytest.fixture(scope="module")
 def worst(engine):
     """axis -> [worst ratio, worst rel_max]; printed when the module is done"""
     table = {}
-    _defaults(engine)
+    reset(engine)
     yield table
-    _defaults(engine)
+    reset(engine)
     for slot in (0, 1):
         engine.release(slot)
     engine.invalidate()
@@ -63,7 +57,7 @@ def _run(engine, inp, budget):
         groups = None if inp["groups"][0] is None else inp["groups"]
         return engine.vdos(slot, inp["mean"], groups, _hip.F_DISPLACEMENTS if disp else 0)
     finally:
-        _defaults(engine)
+        reset(engine)
 
 
 def _check(engine, worst, axis, name):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import make_calculator, rel_max
+from engine_state import reset
 
 pytestmark = pytest.mark.gpu
 
@@ -29,17 +30,8 @@ def syn(engine):
     tr, cells = _trajectory()
     calcs = {disp: SEDCalculator(tr, *cells, use_displacements=disp).attach(engine=engine) for disp in (False, True)}
     yield dict(traj=tr, calcs=calcs)
-    _defaults(engine)
+    reset(engine)
     engine.invalidate()
-
-
-def _defaults(engine):
-    from psa_amd import _hip
-    engine.set_k1(_hip.K1_AUTO)
-    for opt, val in ((_hip.OPT_PLANES, 1), (_hip.OPT_PLANES_EAGER, 0), (_hip.OPT_K1_LOWRANK, 1), (_hip.OPT_K1_LOWRANK_MIN_K, 256),
-                     (_hip.OPT_K1_LOWRANK_MIN_LOCAL, 128), (_hip.OPT_FOLD_PAIRS, 1), (_hip.OPT_K1_WIDE, 1)):
-        engine.set_option(opt, val)
-    engine.set_atom_weights(None)
 
 
 MODES = {"coherent": ({}, False), "incoherent": (dict(basis_atom_types=[1, 2], summation_mode="incoherent"), False),
@@ -61,7 +53,7 @@ FAMILIES = {
 
 def _configure(engine, opts, k1):
     from psa_amd import _hip
-    _defaults(engine)
+    reset(engine)
     engine.set_option(_hip.OPT_PLANES, opts.get("planes", 1))
     engine.set_option(_hip.OPT_PLANES_EAGER, 1)
     engine.set_option(_hip.OPT_K1_LOWRANK, opts.get("lowrank", 1))
@@ -130,7 +122,7 @@ def test_exact_identities(engine, syn, family, mode):
         assert np.array_equal(_bits(again), _bits(ref))
         assert float(np.max(ref_i)) > 0.0
     finally:
-        _defaults(engine)
+        reset(engine)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -199,7 +191,7 @@ def test_parity_dense_and_lowrank(engine, syn, kind, mode):
             assert err <= 1e-5
         assert rel_max(got[1], got[0]) <= 1e-6
     finally:
-        _defaults(engine)
+        reset(engine)
 
 
 @pytest.mark.parametrize("name", ["a", "b", "c"])
@@ -228,7 +220,7 @@ def test_paths_agree(engine, syn):
     w = _weights("mass", traj)
     T, N = traj.n_frames, traj.n_atoms
     try:
-        _defaults(engine)
+        reset(engine)
         # Gamma-symmetric grid: folded against every vector projected
         _, gvecs, shape = calc.get_k_grid("xy", (-1.5, 1.5), (-1.0, 1.0), 6, 6, 0.0)
         none = np.array([], np.float32)
@@ -277,7 +269,7 @@ def test_paths_agree(engine, syn):
         unweighted = engine.debug_project_only(_hip.SLOT_VELOCITIES, mean, vecs)
         assert rel_max(whole, unweighted) > 1e-2                           # (the weights did something)
     finally:
-        _defaults(engine)
+        reset(engine)
 
 
 def test_errors_leave_the_context_usable(engine, syn):
@@ -285,7 +277,7 @@ def test_errors_leave_the_context_usable(engine, syn):
     calc, traj = syn["calcs"][False], syn["traj"]
     N = traj.n_atoms
     mags, vecs = calc.get_k_path("100", 1.0, 24)
-    _defaults(engine)
+    reset(engine)
     ref = calc.calculate(mags, vecs)
     bad = np.ones(N, np.float32)
     bad[3] = np.nan
