@@ -929,6 +929,26 @@ int psa_lowrank_pair_image(int32_t n_stage, int64_t* index, int64_t* bytes);
 /* Device allocations the library's contexts hold at this moment, process-wide: how many and their bytes.  A destroyed
  * context leaves none behind.  No context, no GPU. */
 int psa_debug_device_buffers(int64_t* count, int64_t* bytes);
+/* The table of the context's device buffers (api_core.hip), row by row: the member's name and what its bytes are read
+ * as; either may be null.  PSA_EINVAL past the last row.  No context, no GPU.
+ *   PSA_SCRATCH_REAL   only as float, float16, complex, double or counters that are only added to
+ *   PSA_SCRATCH_INDEX  in part as an index, an offset, an address or a loop bound
+ *   PSA_SCRATCH_STATE  it carries something a later call is promised: atom weights, the segment window, a cached table */
+#define PSA_SCRATCH_REAL 0
+#define PSA_SCRATCH_INDEX 1
+#define PSA_SCRATCH_STATE 2
+int psa_debug_scratch_info(int index, const char** name, int32_t* cls);
+/* Shows that no result depends on what scratch memory held before.  Drains the context's streams, then sets every byte of
+ * every REAL buffer's whole capacity to `byte` (0 .. 255; 0xFF is a NaN in float16, float32 and float64) and every byte
+ * of every INDEX buffer to 0, whatever `byte` is: a pattern never reaches anything a kernel turns into an address or a
+ * trip count.  STATE buffers, the data slots and the plane sets that exist are left alone.  The result resident on the
+ * device is dropped with its buffers: psa_sed_finalize and psa_result_* answer as after psa_create.  buffers, bytes (may
+ * be null): how many buffers were filled and their bytes.  The call also ARMS the context: until byte = -1 disarms it
+ * (and fills nothing), every REAL or INDEX buffer the context allocates or grows, and every plane set it builds, is
+ * filled the same way before its first use.  Between a call that begins a sequence (psa_sed_project, psa_sed_fs_project)
+ * and the one that ends it, the sequence's intermediate results go the same way.  Not for production: a context that
+ * was never armed pays one pointer test per reservation. */
+int psa_debug_scratch_fill(psa_ctx* ctx, int byte, int64_t* buffers, int64_t* bytes);
 /* host wall clock (ms) of work that is done once and then cached, summed since the last call:
  * [0] rocFFT plan builds (run-time compiled per (T, batch))  [1] largest-magnitude passes
  * [2] split-plane builds  [3] trajectory uploads (psa_data_upload / psa_sed_project_upload) */

@@ -201,6 +201,8 @@ SIGNATURES = {
     "psa_oneoff_stats": (C.c_int, [_ctx, _f64p]),
     "psa_option_info": (C.c_int, [C.c_int, C.POINTER(C.c_int32), _i64p, C.POINTER(C.c_char_p)]),
     "psa_debug_device_buffers": (C.c_int, [_i64p, _i64p]),
+    "psa_debug_scratch_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
+    "psa_debug_scratch_fill": (C.c_int, [_ctx, C.c_int, _i64p, _i64p]),
     "psa_debug_phase_table": (C.c_int, [_ctx, _f32p, _f32p, C.c_int64, _i32p, C.c_int64,
                                         C.c_int64, C.c_void_p]),
     "psa_debug_project_only": (C.c_int, [_ctx, C.c_int, _f32p, _f32p, C.c_int64, _i32p,
@@ -309,6 +311,19 @@ def device_buffers():
     n, b = C.c_int64(0), C.c_int64(0)
     _check(load_library().psa_debug_device_buffers(C.byref(n), C.byref(b)), "psa_debug_device_buffers")
     return n.value, b.value
+
+
+SCRATCH_CLASSES = ("real", "index", "state")
+
+
+def scratch_table():
+    """[(name, class)] of every device buffer of a context, class one of SCRATCH_CLASSES, from the library's own table
+    (psa_debug_scratch_info; host only)."""
+    lib, rows = load_library(), []
+    name, cls = C.c_char_p(), C.c_int32(0)
+    while lib.psa_debug_scratch_info(len(rows), C.byref(name), C.byref(cls)) == 0:
+        rows.append((name.value.decode(), SCRATCH_CLASSES[cls.value]))
+    return rows
 
 
 def k_pairs(k_vectors):
@@ -619,6 +634,15 @@ class Engine:
         psa_create reads (PSA_K1_LOWRANK, PSA_K1_LOWRANK_MIN_K) are ignored: the table's values are set."""
         for option, _, default in option_table():
             self.set_option(option, default)
+
+    def scratch_fill(self, byte: int):
+        """(buffers, bytes) filled: every byte of the context's real scratch buffers set to `byte`, of its index buffers to
+        0, and the context armed so that new allocations and plane sets come filled the same way (psa_debug_scratch_fill);
+        byte = -1 disarms.  The result resident on the device is dropped.  A correct call after it returns what it returned
+        before."""
+        n, b = C.c_int64(0), C.c_int64(0)
+        _check(self._lib.psa_debug_scratch_fill(self._h, int(byte), C.byref(n), C.byref(b)), "psa_debug_scratch_fill")
+        return n.value, b.value
 
     def plane_cache(self):
         """(number of cached split-plane sets, their bytes)"""

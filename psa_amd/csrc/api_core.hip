@@ -42,6 +42,10 @@ int DevBuf::reserve(size_t bytes) {
     cap = bytes;
     g_devbuf_count += 1;
     g_devbuf_bytes += (int64_t)bytes;
+    if (fill) {                                        // armed (psa_debug_scratch_fill): no byte comes as the allocator left it
+        PSA_HIP_CHECK(hipMemset(ptr, *fill, cap));
+        PSA_HIP_CHECK(hipDeviceSynchronize());
+    }
     return PSA_OK;
 }
 
@@ -213,6 +217,56 @@ constexpr Option OPTIONS[] = {
 };
 #undef PSA_OPTION
 
+// ---- the context's device buffers: the one place that says which exist and what their bytes are read as ------------
+// (psa_debug_scratch_info hands the table to Python and to tests/test_scratch_table_host.py, which holds it against the
+// DevBuf members of psa_ctx; psa_debug_scratch_fill walks it.  DESIGN.md says what every state buffer carries.)
+//   real   every byte is read only as a float, float16, complex, double or a counter that is only added to: a pattern in it
+//          can change a number, never an address
+//   index  some part of it is read as an index, an offset, an address or a loop bound: it is only ever filled with zeros
+//   state  it carries something from one call to a later one that the ABI promises: never filled
+struct Scratch {
+    const char*      name;
+    DevBuf psa_ctx::*member;
+    int              cls;
+};
+#define PSA_SCRATCH(member, cls) {#member, &psa_ctx::member, PSA_SCRATCH_##cls}
+constexpr Scratch SCRATCH[] = {
+    PSA_SCRATCH(d_kvec, REAL), PSA_SCRATCH(d_mean_all, REAL), PSA_SCRATCH(d_idx, INDEX), PSA_SCRATCH(d_mean_g, REAL),
+    PSA_SCRATCH(d_phase, REAL), PSA_SCRATCH(d_qwork, REAL), PSA_SCRATCH(d_fft_work, REAL),
+    PSA_SCRATCH(d_tables, INDEX),                          // (the synthetic fill's table holds component numbers)
+    PSA_SCRATCH(d_absmax, REAL), PSA_SCRATCH(d_upload_max, REAL), PSA_SCRATCH(d_zeros, STATE),
+    PSA_SCRATCH(d_qrows, REAL), PSA_SCRATCH(d_stage, REAL), PSA_SCRATCH(d_bin, REAL),
+    PSA_SCRATCH(d_slab, REAL), PSA_SCRATCH(d_out, REAL), PSA_SCRATCH(d_aux, REAL),
+    PSA_SCRATCH(d_kmap, INDEX), PSA_SCRATCH(d_cols, INDEX), PSA_SCRATCH(d_inten, REAL),
+    PSA_SCRATCH(d_lr_diff, REAL), PSA_SCRATCH(d_lr_qn, REAL), PSA_SCRATCH(d_lr_L, REAL), PSA_SCRATCH(d_lr_phi, REAL),
+    PSA_SCRATCH(d_lr_f64, REAL),
+    PSA_SCRATCH(d_weights, STATE), PSA_SCRATCH(d_seg_window, STATE), PSA_SCRATCH(d_seg, REAL),
+    PSA_SCRATCH(d_vdos_work, REAL), PSA_SCRATCH(d_vdos_pairs, INDEX), PSA_SCRATCH(d_vdos_off, INDEX), PSA_SCRATCH(d_vdos_mean, REAL),
+    PSA_SCRATCH(d_vdos_part, REAL), PSA_SCRATCH(d_vdos_acc, REAL), PSA_SCRATCH(d_vdos_out, REAL),
+    PSA_SCRATCH(d_modes_work, REAL), PSA_SCRATCH(d_modes_coef, REAL), PSA_SCRATCH(d_modes_out, REAL),
+    PSA_SCRATCH(d_cov_slab, REAL), PSA_SCRATCH(d_cov_g, REAL), PSA_SCRATCH(d_cov_out, REAL),
+    PSA_SCRATCH(d_peaks_spec, REAL), PSA_SCRATCH(d_peaks_bands, INDEX),
+    PSA_SCRATCH(d_peaks_part, INDEX),                      // (the partial maxima come with their bins)
+    PSA_SCRATCH(d_peaks_fit, REAL), PSA_SCRATCH(d_peaks_info, REAL),
+    PSA_SCRATCH(d_rc_work, REAL), PSA_SCRATCH(d_rc_kappa, REAL), PSA_SCRATCH(d_rc_khat, REAL), PSA_SCRATCH(d_rc_idx, INDEX),
+    PSA_SCRATCH(d_rc_tiles, INDEX), PSA_SCRATCH(d_rc_ent, INDEX), PSA_SCRATCH(d_rc_slot, INDEX), PSA_SCRATCH(d_rc_dest, INDEX),
+    PSA_SCRATCH(d_rc_bins, INDEX), PSA_SCRATCH(d_rc_scale, REAL), PSA_SCRATCH(d_rc_acc, REAL), PSA_SCRATCH(d_rc_out, REAL),
+    PSA_SCRATCH(d_rc_groups, INDEX), PSA_SCRATCH(d_rc_part, REAL),
+    PSA_SCRATCH(d_corr_tab, REAL), PSA_SCRATCH(d_corr_factor, REAL), PSA_SCRATCH(d_corr_scale, REAL), PSA_SCRATCH(d_corr_in, REAL),
+    PSA_SCRATCH(d_corr_out, REAL),
+    PSA_SCRATCH(d_rs_idx, INDEX), PSA_SCRATCH(d_rs_items, INDEX), PSA_SCRATCH(d_rs_part, REAL), PSA_SCRATCH(d_rs_acc, REAL),
+    PSA_SCRATCH(d_msd_u, REAL), PSA_SCRATCH(d_msd_img, REAL), PSA_SCRATCH(d_msd_sums, REAL), PSA_SCRATCH(d_msd_offs, REAL),
+    PSA_SCRATCH(d_msd_sizes, REAL),
+    PSA_SCRATCH(d_msd_lags, INDEX),                        // (a lag is a frame offset)
+    PSA_SCRATCH(d_msd_out, REAL),
+    PSA_SCRATCH(d_pair_c, REAL),
+    PSA_SCRATCH(d_angle_work, INDEX),                      // (the neighbour counts lie beside the lists)
+    PSA_SCRATCH(d_angle_edges, REAL),
+    PSA_SCRATCH(d_sync, REAL),
+};
+#undef PSA_SCRATCH
+static const int SCRATCH_ZERO = 0;                     // what an armed index buffer is filled with, whatever the byte
+
 }  // namespace psa
 
 psa_ctx::psa_ctx() {
@@ -320,6 +374,38 @@ int psa_debug_device_buffers(int64_t* count, int64_t* bytes) {
     PSA_REQUIRE(count != nullptr && bytes != nullptr, "null argument");
     *count = g_devbuf_count.load();
     *bytes = g_devbuf_bytes.load();
+    return PSA_OK;
+}
+
+int psa_debug_scratch_info(int index, const char** name, int32_t* cls) {
+    PSA_REQUIRE(index >= 0 && index < (int)std::size(SCRATCH), "no device buffer at index %d", index);
+    if (name) *name = SCRATCH[index].name;
+    if (cls) *cls = SCRATCH[index].cls;
+    return PSA_OK;
+}
+
+int psa_debug_scratch_fill(psa_ctx* c, int byte, int64_t* buffers, int64_t* bytes) {
+    PSA_TRY(enter(c));
+    PSA_REQUIRE(byte >= -1 && byte <= 255, "the fill byte is 0 .. 255, or -1 to disarm");
+    Guard g(c);
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (c->d2h_stream) PSA_HIP_CHECK(hipStreamSynchronize(c->d2h_stream));
+    if (c->stager.copy_stream) PSA_HIP_CHECK(hipStreamSynchronize(c->stager.copy_stream));
+    int64_t n = 0, total = 0;
+    c->scratch_byte = byte;
+    for (const Scratch& s : SCRATCH) {
+        DevBuf& b = c->*s.member;
+        b.fill = byte < 0 || s.cls == PSA_SCRATCH_STATE ? nullptr : s.cls == PSA_SCRATCH_REAL ? &c->scratch_byte : &SCRATCH_ZERO;
+        if (!b.fill || !b.ptr) continue;
+        PSA_HIP_CHECK(hipMemsetAsync(b.ptr, *b.fill, b.cap, c->stream));
+        n += 1;
+        total += (int64_t)b.cap;
+    }
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    // the result went with d_slab, d_out and d_inten: a later psa_result_* or finalize finds what it finds after psa_create
+    if (byte >= 0) c->slab_valid = c->out_valid = c->inten_valid = false;
+    if (buffers) *buffers = n;
+    if (bytes) *bytes = total;
     return PSA_OK;
 }
 

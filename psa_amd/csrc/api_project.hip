@@ -173,6 +173,7 @@ int get_planes(psa_ctx* c, const GroupView& v, int64_t K_local, const float* mea
         PSA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     }
     auto ps = std::make_unique<PlaneSet>();
+    if (c->scratch_byte >= 0) ps->buf.fill = &c->scratch_byte;   // armed (psa_debug_scratch_fill)
     if (ps->buf.reserve(bytes) != PSA_OK) {
         (void)hipGetLastError();
         return PSA_OK;

@@ -67,10 +67,12 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 // grow-only device allocation, freed with its owner (release: the early free).  Every live one is counted, process-wide
-// (psa_debug_device_buffers)
+// (psa_debug_device_buffers).  fill: null, or -- while psa_debug_scratch_fill has the owner armed -- the byte every new
+// allocation is set to over its whole capacity before its first use; it belongs to the member, a move leaves it behind
 struct DevBuf {
     void*  ptr = nullptr;
     size_t cap = 0;
+    const int* fill = nullptr;
     DevBuf() = default;
     DevBuf(DevBuf&& o) noexcept : ptr(std::exchange(o.ptr, nullptr)), cap(std::exchange(o.cap, 0)) {}
     DevBuf& operator=(DevBuf&& o) noexcept {
@@ -374,6 +376,10 @@ struct psa_ctx {
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
                                           // plane builds, trajectory uploads (psa_oneoff_stats)
     psa::DevBuf      d_sync;     // one float for the RCCL barrier
+
+    // psa_debug_scratch_fill: the byte the real buffers of the table SCRATCH (api_core.hip) and new plane sets are filled
+    // with while the context is armed; -1: not armed
+    int scratch_byte = -1;
 
     ncclComm_t comm = nullptr;
     int        rank = 0, nranks = 1;
