@@ -81,6 +81,13 @@ int         psa_create(int device, psa_ctx** out);
 int         psa_destroy(psa_ctx* ctx);
 int         psa_synchronize(psa_ctx* ctx);
 int         psa_set_k1(psa_ctx* ctx, int selector);     /* PSA_K1_* */
+/* The low-rank k-path route's fold (on in a new context): the product of the node table's lo piece with the hi plane is not
+ * multiplied per node row; by the combine's linearity it equals E v_hi with E = phi L W_lo, a table as small as D, and the D
+ * image holds D + E rounded once to float16.  Node rows keep two products instead of three (k1_lowrank_fold.hip for lists the
+ * pair launch serves, else the two-product node pass and the D pass on the folded image).  Results move within the route's
+ * per-element bound; on = 0: the route as it was, bit for bit.  A switch of its own like psa_set_k1, not a row of the option
+ * table below. */
+int         psa_set_k1_lowrank_fold(psa_ctx* ctx, int on);
 /* Tunables of the product path (defaults in brackets):
  *   PSA_OPT_PLANES        [1] keep, per atom group, the group's data scaled, split into its two
  *                             float16 pieces and laid out in MFMA-fragment order ("split planes",
@@ -882,8 +889,8 @@ int psa_k_pairs(const float* k_vectors, int64_t K, int32_t* kmap /* K */,
 int psa_sed_set_kmap(psa_ctx* ctx, const int32_t* kmap, int64_t K_out);
 
 /* The low-rank plan of a k-list for one atom group (api_lowrank.hip) as a host-only service for tests:
- * *ok = 1 when the route serves; geo[12] = u (3), k0 (3), x_c, h_x, interval width, interval id, bound on
- * |D|, scale of D; kappa[64] the nodes, L[K * 64] the combine's real Lagrange weights and phi[K * 2] its complex64
+ * *ok = 1 when the route serves; geo[14] = u (3), k0 (3), x_c, h_x, interval width, interval id, bound on
+ * |D|, scale of D, bound on |E| and scale of the folded image D + E (psa_set_k1_lowrank_fold); kappa[64] the nodes, L[K * 64] the combine's real Lagrange weights and phi[K * 2] its complex64
  * row phases, C[K * 64 * 2] complex64 their product phi[j] L[j, l] rounded once from fp64: the reference the two
  * factors are checked against, which no kernel reads (any may be null).  No context, no GPU. */
 int psa_lowrank_plan(const float* k_vectors, int64_t K, const float* mean_pos_all, int64_t N, const int32_t* idx,
@@ -926,6 +933,9 @@ int psa_k1_lowrank_pair_launches(psa_ctx* ctx, int64_t* launches);
  * stages, padding included; index[512 * 32 n_stage] (may be null) = the float16 element index of (row m, atom a) at
  * m * 32 n_stage + a.  No context, no GPU. */
 int psa_lowrank_pair_image(int32_t n_stage, int64_t* index, int64_t* bytes);
+/* The same for the folded D image of the folded pair launch (k1_lowrank_fold.h, psa_set_k1_lowrank_fold): rows 0..127 in
+ * role A's part, rows 128..511 in role B's.  No context, no GPU. */
+int psa_lowrank_fold_image(int32_t n_stage, int64_t* index, int64_t* bytes);
 /* Device allocations the library's contexts hold at this moment, process-wide: how many and their bytes.  A destroyed
  * context leaves none behind.  No context, no GPU. */
 int psa_debug_device_buffers(int64_t* count, int64_t* bytes);

@@ -106,6 +106,7 @@ SIGNATURES = {
     "psa_destroy": (C.c_int, [_ctx]),
     "psa_synchronize": (C.c_int, [_ctx]),
     "psa_set_k1": (C.c_int, [_ctx, C.c_int]),
+    "psa_set_k1_lowrank_fold": (C.c_int, [_ctx, C.c_int]),
     "psa_set_option": (C.c_int, [_ctx, C.c_int, C.c_int64]),
     "psa_device_info": (C.c_int, [_ctx, C.c_char_p, C.c_int, C.POINTER(C.c_int), _i64p]),
     "psa_data_upload": (C.c_int, [_ctx, C.c_int, _f32p, C.c_int64, C.c_int64]),
@@ -198,6 +199,7 @@ SIGNATURES = {
     "psa_k1_lowrank_launches": (C.c_int, [_ctx, _i64p]),
     "psa_k1_lowrank_pair_launches": (C.c_int, [_ctx, _i64p]),
     "psa_lowrank_pair_image": (C.c_int, [C.c_int32, _i64p, _i64p]),
+    "psa_lowrank_fold_image": (C.c_int, [C.c_int32, _i64p, _i64p]),
     "psa_oneoff_stats": (C.c_int, [_ctx, _f64p]),
     "psa_option_info": (C.c_int, [C.c_int, C.POINTER(C.c_int32), _i64p, C.POINTER(C.c_char_p)]),
     "psa_debug_device_buffers": (C.c_int, [_i64p, _i64p]),
@@ -339,14 +341,15 @@ def k_pairs(k_vectors):
 
 def lowrank_plan(k_vectors, mean_pos_all, idx=None):
     """The low-rank plan of a k-list for one atom group (psa_lowrank_plan; host only): None when the list stays on
-    the dense kernels, else a dict with u, k0, x_c, h_x, width, interval, d_bound, dscale, kappa (64,) and
-    C (K, 64) complex64, and C's two factors L (K, 64) float32 and phi (K,) complex64."""
+    the dense kernels, else a dict with u, k0, x_c, h_x, width, interval, d_bound, dscale, e_bound, dscale_fold (the
+    bound on |E| and the scale of the folded image D + E, Engine.set_lowrank_fold), kappa (64,) and C (K, 64) complex64, and
+    C's two factors L (K, 64) float32 and phi (K,) complex64."""
     kv = _as_f32(k_vectors, (3,))
     mean = _as_f32(mean_pos_all, (3,))
     K, N = kv.shape[0], mean.shape[0]
     ix = None if idx is None else np.ascontiguousarray(idx, np.int32)
     n_g = N if ix is None else ix.size
-    ok, geo = C.c_int32(0), np.zeros(12, np.float64)
+    ok, geo = C.c_int32(0), np.zeros(14, np.float64)
     kappa, cm = np.zeros(64, np.float64), np.zeros((K, 64), np.complex64)
     lw, phi = np.zeros((K, 64), np.float32), np.zeros(K, np.complex64)
     _check(load_library().psa_lowrank_plan(_f32(kv), K, _f32(mean), N, None if ix is None else ix.ctypes.data_as(_i32p), n_g,
@@ -355,7 +358,8 @@ def lowrank_plan(k_vectors, mean_pos_all, idx=None):
     if not ok.value:
         return None
     return {"u": geo[0:3].copy(), "k0": geo[3:6].copy(), "x_c": geo[6], "h_x": geo[7], "width": geo[8],
-            "interval": int(geo[9]), "d_bound": geo[10], "dscale": geo[11], "kappa": kappa, "C": cm, "L": lw, "phi": phi}
+            "interval": int(geo[9]), "d_bound": geo[10], "dscale": geo[11], "e_bound": geo[12],
+            "dscale_fold": geo[13], "kappa": kappa, "C": cm, "L": lw, "phi": phi}
 
 
 def lowrank_pair_image(n_stage: int):
@@ -364,6 +368,14 @@ def lowrank_pair_image(n_stage: int):
     bytes, padding stages included."""
     index, nbytes = np.zeros((512, 32 * int(n_stage)), np.int64), C.c_int64(0)
     _check(load_library().psa_lowrank_pair_image(int(n_stage), index.ctypes.data_as(_i64p), C.byref(nbytes)), "psa_lowrank_pair_image")
+    return index, nbytes.value
+
+
+def lowrank_fold_image(n_stage: int):
+    """The folded D image of the low-rank route's folded pair launch (psa_lowrank_fold_image; host only) for n_stage
+    32-atom stages: (index, nbytes) as lowrank_pair_image, rows 0..127 in role A's part and rows 128..511 in role B's."""
+    index, nbytes = np.zeros((512, 32 * int(n_stage)), np.int64), C.c_int64(0)
+    _check(load_library().psa_lowrank_fold_image(int(n_stage), index.ctypes.data_as(_i64p), C.byref(nbytes)), "psa_lowrank_fold_image")
     return index, nbytes.value
 
 
@@ -525,6 +537,11 @@ class Engine:
     def set_k1(self, selector: int):
         _check(self._lib.psa_set_k1(self._h, selector), "psa_set_k1")
 
+    def set_lowrank_fold(self, on: bool):
+        """The low-rank k-path route with the node table's lo piece folded into the D image (psa_set_k1_lowrank_fold; on in a
+        new context).  False: the route as it was, bit for bit."""
+        _check(self._lib.psa_set_k1_lowrank_fold(self._h, int(bool(on))), "psa_set_k1_lowrank_fold")
+
     def device_info(self) -> dict:
         name = C.create_string_buffer(256)
         cu, mem = C.c_int(0), C.c_int64(0)
@@ -634,6 +651,7 @@ class Engine:
         psa_create reads (PSA_K1_LOWRANK, PSA_K1_LOWRANK_MIN_K) are ignored: the table's values are set."""
         for option, _, default in option_table():
             self.set_option(option, default)
+        self.set_lowrank_fold(True)                  # a switch of its own beside the table: back to a new context's state too
 
     def scratch_fill(self, byte: int):
         """(buffers, bytes) filled: every byte of the context's real scratch buffers set to `byte`, of its index buffers to

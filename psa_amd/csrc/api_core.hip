@@ -426,6 +426,13 @@ int psa_set_k1(psa_ctx* c, int selector) {
     return PSA_OK;
 }
 
+int psa_set_k1_lowrank_fold(psa_ctx* c, int on) {
+    PSA_TRY(enter(c));
+    Guard g(c);
+    c->k1_lowrank_fold = on != 0;
+    return PSA_OK;
+}
+
 int psa_set_option(psa_ctx* c, int option, int64_t value) {
     PSA_TRY(enter(c));
     Guard g(c);

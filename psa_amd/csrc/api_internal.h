@@ -176,7 +176,10 @@ struct LowRankPlan {
     double              kappa[LOWRANK_NODES] = {};            // the nodes
     double              d_bound = 0;                          // bound on |P_ref - P_line|
     float               dscale = 0.f;                         // power of two the D image carries
-    std::vector<double> kline;                                // (K, 3) the k-vectors projected on the line
+    double              e_bound = 0;                          // bound on |E|, the node table's lo piece through the combine:
+                                                              // max_j rot_j Lam_j 2^-12 from the float32 L and phi
+    float               dscale_fold = 0.f;                    // power of two the folded image D + E carries
+    std::vector<double> kline;                               // (K, 3) the k-vectors projected on the line
     std::vector<float>  L;                                    // (K, 64) the combine's real Lagrange weights L_l(kappa_j)
     std::vector<float>  phi;                                  // (K) complex64, the combine's row phases exp(i kappa_j x_c)
 };

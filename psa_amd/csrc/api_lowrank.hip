@@ -25,6 +25,7 @@
 // kernels.  A list that crosses Gamma declines as a whole while a part of it on one side may take the route, so
 // for such lists splitting can move rows by the ~1e-7 that separates the two routes.
 #include "api_internal.h"
+#include "k1_lowrank_fold.h"
 #include "k1_lowrank_pair.h"
 
 namespace psa {
@@ -190,6 +191,16 @@ int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, co
     }
     // ---- scale of D: the bound lands at or below 2^14 (float16 maximum 65504)
     p->dscale = std::ldexp(1.0f, 14 - (int)std::ceil(std::log2(p->d_bound)));
+    // ---- the folded image D + E (psa_set_k1_lowrank_fold): E[j, a] = phi_j sum_l L[j, l] W_lo[l, a], |W_lo| <= 2^-12 per
+    // part (the residual of a float16 piece of a value <= 1), so a part of E is at most rot_j Lam_j 2^-12 with
+    // rot_j = |Re phi_j| + |Im phi_j|, Lam_j = sum_l |L[j, l]| of the float32 tables the device reads
+    for (int64_t j = 0; j < K; ++j) {
+        double lam = 0.0;
+        for (int l = 0; l < LOWRANK_NODES; ++l) lam += std::fabs((double)p->L[(size_t)j * LOWRANK_NODES + l]);
+        const double rot = std::fabs((double)p->phi[(size_t)j * 2]) + std::fabs((double)p->phi[(size_t)j * 2 + 1]);
+        p->e_bound = std::max(p->e_bound, rot * lam * 0x1p-12);
+    }
+    p->dscale_fold = std::ldexp(1.0f, 14 - (int)std::ceil(std::log2(p->d_bound + p->e_bound)));
     p->ok = true;
     return PSA_OK;
 }
@@ -219,9 +230,11 @@ int prepare_lowrank(psa_ctx* c, const GroupView& v, const ProjectArgs& list, int
     PSA_TRY(upload(c, c->d_lr_phi, p.phi.data(), p.phi.size() * sizeof(float)));
     PSA_TRY(c->d_lr_qn.reserve((size_t)LOWRANK_NODES * 3 * (size_t)c->slot[v.slot].T * sizeof(float2)));
     g->lowrank = true;
-    g->dscale = p.dscale;
+    g->lr_fold = c->k1_lowrank_fold;                                   // D' = D + E in the image, two products per node row
+    g->dscale = g->lr_fold ? p.dscale_fold : p.dscale;
     g->M_pad_d = (int)((2 * nk + 511) / 512 * 512);
     g->lr_pair = c->opt_k1_lowrank_pair && g->M_pad_d == LRP_ROWS;     // one D block: node rows and D rows in one launch
+    static_assert(LRF_ROWS == LRP_ROWS, "the folded pair launch serves the lists the pair launch serves");
     return PSA_OK;
 }
 
@@ -239,7 +252,8 @@ int psa_lowrank_plan(const float* k_vectors, int64_t K, const float* mean_pos_al
     LowRankPlan p;
     PSA_TRY(plan_lowrank(k_vectors, K, mean_pos_all, N, idx, n_g, &p, C));
     *ok = p.ok;
-    const double g[12] = {p.u[0], p.u[1], p.u[2], p.k0[0], p.k0[1], p.k0[2], p.x_c, p.h_x, p.width, (double)p.interval, p.d_bound, p.dscale};
+    const double g[14] = {p.u[0],  p.u[1],    p.u[2],           p.k0[0],   p.k0[1],  p.k0[2],   p.x_c,
+                          p.h_x,   p.width,   (double)p.interval, p.d_bound, p.dscale, p.e_bound, p.dscale_fold};
     std::memcpy(geo, g, sizeof(g));
     if (p.ok && kappa) std::memcpy(kappa, p.kappa, sizeof(p.kappa));
     if (p.ok && L) std::memcpy(L, p.L.data(), p.L.size() * sizeof(float));
@@ -253,6 +267,15 @@ int psa_lowrank_pair_image(int32_t n_stage, int64_t* index, int64_t* bytes) {
     if (index)
         for (int m = 0; m < LRP_ROWS; ++m)
             for (int a = 0; a < n_stage * K1_BA; ++a) index[(size_t)m * n_stage * K1_BA + a] = (int64_t)pd16_pair_index(m, a, n_stage);
+    return PSA_OK;
+}
+
+int psa_lowrank_fold_image(int32_t n_stage, int64_t* index, int64_t* bytes) {
+    PSA_REQUIRE(n_stage >= 1 && n_stage < (1 << 20) && bytes, "bad argument");
+    *bytes = (int64_t)pd16_fold_table_bytes(n_stage);
+    if (index)
+        for (int m = 0; m < LRF_ROWS; ++m)
+            for (int a = 0; a < n_stage * K1_BA; ++a) index[(size_t)m * n_stage * K1_BA + a] = (int64_t)pd16_fold_index(m, a, n_stage);
     return PSA_OK;
 }
 

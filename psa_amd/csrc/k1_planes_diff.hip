@@ -25,6 +25,7 @@
 #include <utility>
 
 #include "k1_f16.h"
+#include "k1_lowrank_fold.h"
 #include "k1_lowrank_pair.h"
 
 namespace psa {
@@ -197,6 +198,21 @@ int launch_k1_planes_diff(psa_ctx* c, const void* d_planes, const void* d_diff, 
 // ---------------------------------------------------------------------------------------------
 // Tables
 // ---------------------------------------------------------------------------------------------
+// The parts of D[k, a] for group atom a: cs = P_ref (cos, sin), ce / se = P_line in fp64, wa = the atom's weight (1 without)
+__device__ __forceinline__ void diff_parts(const float* __restrict__ kvec, const double* __restrict__ kline,
+                                           const float* __restrict__ mean_all, const int* __restrict__ idx,
+                                           const float* __restrict__ w, float wnorm, int k, int a, float (&cs)[2], double& ce,
+                                           double& se, double& wa) {
+    const int   src = idx ? idx[a] : a;
+    const float rx = mean_all[3 * (size_t)src + 0], ry = mean_all[3 * (size_t)src + 1], rz = mean_all[3 * (size_t)src + 2];
+    const float kx = kvec[3 * k + 0], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
+    const float arg = __fmaf_rn(kz, rz, __fmaf_rn(ky, ry, __fmul_rn(kx, rx)));
+    sincosf(arg, &cs[1], &cs[0]);
+    const double th = kline[3 * k + 0] * (double)rx + kline[3 * k + 1] * (double)ry + kline[3 * k + 2] * (double)rz;
+    sincos(th, &se, &ce);
+    wa = w ? (double)(w[src] * wnorm) : 1.0;
+}
+
 // D[j, a] = (P_ref - P_line) * dscale, one float16 piece.  P_ref exactly as phase_table_f16_kernel (k1_pair.hip)
 // computes it -- the same float32 FMA chain and sincosf, under the same compiler flags --, P_line from the k-vector
 // projected on the plan's line, kline[3 j..], in fp64.  Rows past 2K and atoms past n_g are zero.
@@ -212,7 +228,7 @@ diff_table_kernel(const float* __restrict__ kvec, const double* __restrict__ kli
     const int k = blockIdx.x;
     if (a >= A_pad) return;
     float d[2] = {0.f, 0.f};
-    if (k < K && a < n_g) {
+    if (k < K && a < n_g) {      // (diff_parts, written out: through the helper the compiler orders this kernel's instructions differently)
         const int   src = idx ? idx[a] : a;
         const float rx = mean_all[3 * (size_t)src + 0], ry = mean_all[3 * (size_t)src + 1], rz = mean_all[3 * (size_t)src + 2];
         const float kx = kvec[3 * k + 0], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
@@ -261,6 +277,81 @@ node_table_kernel(const double* __restrict__ geo, const double* __restrict__ kap
         Pb[pf16_tile_index(0, 2 * l + ri, a, 128, n_stage)] = lead;
         Pb[pf16_tile_index(1, 2 * l + ri, a, 128, n_stage)] = (_Float16)(float)(x - (double)lead);
     }
+}
+
+// The FOLDED D image (psa_set_k1_lowrank_fold): D'[j, a] = (D[j, a] + E[j, a]) dscale, rounded once to float32 and then to
+// one float16 piece like D.  D as above, in fp64.  E[j, a] = phi_j sum_l L[j, l] W_lo[l, a] / 2^14 is what the combine
+// makes of the node rows' product W_lo v_hi, which the folded node rows leave out (k1_lowrank_fold.hip): W_lo are the
+// float16 lo pieces AS THEY STAND in the node table image Pn (node_table_kernel, which therefore runs first; they carry
+// the weights already), L and phi the plan's float32 tables that the combine reads.  One fixed order per element: float32
+// FMAs over l = 0..63, real and imaginary sums on their own, then phase_add's two operations per part
+// (lowrank_combine.hip) -- a row's bits depend on k_j, the node interval and the group alone, however rows and atoms are
+// tiled.  |E| <= rot_j Lam_j 2^-12 (the plan's e_bound), so dscale is the plan's dscale_fold.
+// A thread holds one atom's 128 lo pieces and walks FOLD_JB rows; L and phi are uniform reads.  (32 rows per thread, and the
+// two sums as one packed FMA, measured no faster: 0.12 and 0.11 ms against 0.11 at configuration 3.)
+// FOLD: the folded pair launch's image (pd16_fold_index, k1_lowrank_fold.h) instead of the D pass's.
+constexpr int FOLD_JB = 16;
+template <bool FOLD>
+__global__ void __launch_bounds__(256)
+diff_fold_table_kernel(const float* __restrict__ kvec, const double* __restrict__ kline, const float* __restrict__ mean_all,
+                       const int* __restrict__ idx, const float* __restrict__ w, float wnorm, const _Float16* __restrict__ Pn,
+                       const float* __restrict__ L, const float2* __restrict__ phi, _Float16* __restrict__ Db, int K, int n_g,
+                       int A_pad, float dscale) {
+    const int a = blockIdx.y * 256 + threadIdx.x;
+    const int k0 = blockIdx.x * FOLD_JB;
+    if (a >= A_pad) return;
+    const int n_stage = A_pad / K1_BA;
+    _Float16  wl[2 * LOWRANK_NODES];
+#pragma unroll
+    for (int m = 0; m < 2 * LOWRANK_NODES; ++m) wl[m] = Pn[pf16_tile_index(1, m, a, 2 * LOWRANK_NODES, n_stage)];
+    for (int k = k0; k < k0 + FOLD_JB; ++k) {
+        float d[2] = {0.f, 0.f};
+        if (k < K && a < n_g) {
+            const float* Lk = L + (size_t)k * LOWRANK_NODES;
+            float        sr = 0.f, si = 0.f;
+#pragma unroll
+            for (int l = 0; l < LOWRANK_NODES; ++l) {
+                sr = __fmaf_rn(Lk[l], (float)wl[2 * l], sr);
+                si = __fmaf_rn(Lk[l], (float)wl[2 * l + 1], si);
+            }
+            const float2 ph = phi[k];
+            const float  er = __fmaf_rn(-ph.y, si, __fmul_rn(ph.x, sr)), ei = __fmaf_rn(ph.y, sr, __fmul_rn(ph.x, si));
+            float        cs[2];
+            double       se, ce, wa;
+            diff_parts(kvec, kline, mean_all, idx, w, wnorm, k, a, cs, ce, se, wa);
+            constexpr double inv_p = 1.0 / (double)F16x2::P_SCALE;
+            d[0] = (float)((((double)cs[0] - ce) * wa + (double)er * inv_p) * (double)dscale);
+            d[1] = (float)((((double)cs[1] - se) * wa + (double)ei * inv_p) * (double)dscale);
+        }
+        Db[FOLD ? pd16_fold_index(2 * k, a, n_stage) : pd16_index(2 * k, a, n_stage)] = (_Float16)d[0];
+        Db[FOLD ? pd16_fold_index(2 * k + 1, a, n_stage) : pd16_index(2 * k + 1, a, n_stage)] = (_Float16)d[1];
+    }
+}
+
+// the same tables for the folded route: the node table first, then the folded D image from it (d_L, d_phi: the plan's)
+int launch_lowrank_tables_fold(psa_ctx* c, const float* d_kvec, const double* d_kline, const double* d_geo, const double* d_kappa,
+                               const float* d_mean_all, const int* d_idx, const float* d_L, const float2* d_phi, void* d_diff,
+                               void* d_nodes, const ProjGeom& g, int M_pad_d, float dscale, bool pair) {
+    PSA_REQUIRE(M_pad_d % D_M_BLK == 0 && M_pad_d >= 2 * g.K && g.A_pad % K1_BA == 0, "bad low-rank table geometry");
+    PSA_REQUIRE(!pair || M_pad_d == LRF_ROWS, "the folded pair launch's image is one 512-row block");
+    static_assert((D_M_BLK / 2) % FOLD_JB == 0, "whole blocks of rows");
+    hipLaunchKernelGGL(node_table_kernel, dim3(LOWRANK_NODES, (g.A_pad + 255) / 256), dim3(256), 0, c->stream, d_geo, d_kappa, d_mean_all,
+                       d_idx, g.weights, 1.f / g.wscale, (_Float16*)d_nodes, g.n_g, g.A_pad);
+    PSA_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(pair ? diff_fold_table_kernel<true> : diff_fold_table_kernel<false>,
+                       dim3(M_pad_d / 2 / FOLD_JB, (g.A_pad + 255) / 256), dim3(256), 0, c->stream, d_kvec, d_kline, d_mean_all, d_idx,
+                       g.weights, 1.f / g.wscale, (const _Float16*)d_nodes, d_L, d_phi, (_Float16*)d_diff, g.K, g.n_g, g.A_pad, dscale);
+    PSA_HIP_CHECK(hipGetLastError());
+    if (pair) {      // each role's part ends with its own padding stages
+        const size_t n_stage = (size_t)g.A_pad / K1_BA, a_pad = LRF_PAD_STAGES * LRF_A_UNITS * 1024, b_pad = LRF_PAD_STAGES * LRF_B_UNITS * 1024;
+        static_assert(LRF_ROWS == D_M_BLK, "the fold image has the size of one D block");
+        PSA_HIP_CHECK(hipMemsetAsync((char*)d_diff + n_stage * LRF_A_UNITS * 1024, 0, a_pad, c->stream));
+        PSA_HIP_CHECK(hipMemsetAsync((char*)d_diff + pd16_fold_table_bytes((int)n_stage) - b_pad, 0, b_pad, c->stream));
+    } else {
+        PSA_HIP_CHECK(hipMemsetAsync((char*)d_diff + (size_t)M_pad_d * g.A_pad * 2, 0,
+                                     pd16_table_bytes(M_pad_d, g.A_pad) - (size_t)M_pad_d * g.A_pad * 2, c->stream));
+    }
+    return PSA_OK;
 }
 
 int launch_lowrank_tables(psa_ctx* c, const float* d_kvec, const double* d_kline, const double* d_geo, const double* d_kappa,

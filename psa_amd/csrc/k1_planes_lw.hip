@@ -28,7 +28,11 @@
 
 namespace psa {
 
-template <bool NT_V>
+// TWO: the low-rank route's folded node rows (psa_set_k1_lowrank_fold, launch_k1_planes_lw2): the product of the
+// table's lo piece with the hi plane has moved into the folded D image (k1_planes_diff.hip), so a chain is
+// mma(a[0], b[1]), mma(a[0], b[0]) and the table's lo piece -- the second 8 KiB of each 16-KiB stage -- is neither
+// fetched nor read.  The ring keeps its slots.
+template <bool NT_V, bool TWO = false>
 __global__ void __launch_bounds__(768, 3)
 k1_planes_lw_kernel(const _Float16* __restrict__ planes, const _Float16* __restrict__ Pb, float2* __restrict__ Q,
                     int64_t T, int64_t q_stride, int n_fg, int n_stage, int K, int n_mblk, int n_tblk, float qscale) {
@@ -38,7 +42,7 @@ k1_planes_lw_kernel(const _Float16* __restrict__ planes, const _Float16* __restr
     constexpr int P_STAGE_BYTES = pf16_stage_bytes(M_BLK);                  // 16 KiB
     constexpr int V_GROUP_BYTES = PL_STAGE_BYTES;                           // 6 KiB
     constexpr int STAGE_BYTES = P_STAGE_BYTES + 4 * V_GROUP_BYTES;          // 40 KiB
-    constexpr int BATCH = 10;                                               // LDS-DMA instructions per loader and stage
+    constexpr int BATCH = TWO ? 8 : 10;                                     // LDS-DMA instructions per loader and stage
     static_assert(RING * STAGE_BYTES == 160 * 1024, "the ring is all of LDS");
     __shared__ __attribute__((aligned(16))) unsigned char smem[RING * STAGE_BYTES];
     const unsigned lds0 = (unsigned)(size_t)(lds_u8*)smem;
@@ -61,7 +65,10 @@ k1_planes_lw_kernel(const _Float16* __restrict__ planes, const _Float16* __restr
         // padding behind the buffers) and never read -- as in k1_planes_kernel
         auto dma_stage = [&](int slot) {
             const unsigned dst = lds0 + slot * STAGE_BYTES;
-            lds_dma16_group<4>(p_next, p_voff, dst + 4096 * j);
+            if constexpr (TWO)          // the hi piece's 8 KiB in quarters of 2
+                lds_dma16_group<2>(p_next, 2048 * j + 16 * lane, dst + 2048 * j);
+            else
+                lds_dma16_group<4>(p_next, p_voff, dst + 4096 * j);
             lds_dma16_group<3, NT_V>(v_next, v_voff, dst + P_STAGE_BYTES + j * V_GROUP_BYTES);
             lds_dma16_group<3, NT_V>(v_next, v_voff + 3072, dst + P_STAGE_BYTES + j * V_GROUP_BYTES + 3072);
             p_next += P_STAGE_BYTES;
@@ -97,7 +104,7 @@ k1_planes_lw_kernel(const _Float16* __restrict__ planes, const _Float16* __restr
     auto  read_a_tile = [&](int mt, int slot) {
         const unsigned base = p_lane + slot * STAGE_BYTES;
 #pragma unroll
-        for (int p = 0; p < NP; ++p)
+        for (int p = 0; p < (TWO ? 1 : NP); ++p)
             a[p][mt] = *reinterpret_cast<lds_cv8*>((const lds_u8*)(size_t)(base + (p * M_BLK + mt * 16) * 64));
     };
     auto read_b = [&](int buf, int slot, int c) {
@@ -135,9 +142,14 @@ k1_planes_lw_kernel(const _Float16* __restrict__ planes, const _Float16* __restr
                 read_b(cur ^ 1, slot1, 0);
 #pragma unroll
             for (int mt = 0; mt < MT16; ++mt) {
-                f32x4 ch = PR::mma(a[1][mt], bb[cur][0], restart ? f32x4{0.f, 0.f, 0.f, 0.f} : hi[mt][c]);
-                ch = PR::mma(a[0][mt], bb[cur][1], ch);
-                hi[mt][c] = PR::mma(a[0][mt], bb[cur][0], ch);
+                if constexpr (TWO) {
+                    const f32x4 ch = PR::mma(a[0][mt], bb[cur][1], restart ? f32x4{0.f, 0.f, 0.f, 0.f} : hi[mt][c]);
+                    hi[mt][c] = PR::mma(a[0][mt], bb[cur][0], ch);
+                } else {
+                    f32x4 ch = PR::mma(a[1][mt], bb[cur][0], restart ? f32x4{0.f, 0.f, 0.f, 0.f} : hi[mt][c]);
+                    ch = PR::mma(a[0][mt], bb[cur][1], ch);
+                    hi[mt][c] = PR::mma(a[0][mt], bb[cur][0], ch);
+                }
                 if (c == 2) read_a_tile(mt, slot1);        // behind the tile's last MFMAs of this stage
             }
         }
@@ -159,6 +171,13 @@ k1_planes_lw_kernel(const _Float16* __restrict__ planes, const _Float16* __restr
 int launch_k1_planes_lw(psa_ctx* c, const void* d_planes, const void* d_phase, float2* d_q, const ProjGeom& g, int64_t n_fg) {
     PSA_REQUIRE(g.m_blk == 128 && g.M_pad % 128 == 0, "loader-wave planes kernel: 128-row M blocks only");
     return launch_planes_family(c, k1_planes_lw_kernel<true>, k1_planes_lw_kernel<false>, 128, 768, "planes kernel", 2 * K1_BA,
+                                F16x2::P_SCALE, d_planes, d_phase, d_q, g, n_fg);
+}
+
+// the low-rank route's folded node rows: two products per row tile, the table's hi piece only
+int launch_k1_planes_lw2(psa_ctx* c, const void* d_planes, const void* d_phase, float2* d_q, const ProjGeom& g, int64_t n_fg) {
+    PSA_REQUIRE(g.m_blk == 128 && g.M_pad % 128 == 0, "loader-wave planes kernel: 128-row M blocks only");
+    return launch_planes_family(c, k1_planes_lw_kernel<true, true>, k1_planes_lw_kernel<false, true>, 128, 768, "planes kernel", 2 * K1_BA,
                                 F16x2::P_SCALE, d_planes, d_phase, d_q, g, n_fg);
 }
 

@@ -169,6 +169,8 @@ struct ProjGeom {
     int     M_pad_d = 0;      // lowrank: rows of the D image (2K rounded up to 512)
     float   dscale = 0.f;     // lowrank: power of two the D image carries
     bool    lr_pair = false;  // lowrank: node rows and D rows in one launch (k1_lowrank_pair.hip; PSA_OPT_K1_LOWRANK_PAIR)
+    bool    lr_fold = false;  // lowrank: the node table's lo piece folded into the D image, two-product node rows (psa_set_k1_lowrank_fold;
+                              // dscale is then the plan's dscale_fold)
     // per-atom weights (psa_set_atom_weights), folded into the phase table: (N_tot) float32 on the device, indexed like
     // the mean positions; nullptr = none.  The float16 tables hold w 2^-e and their launches multiply qscale by
     // wscale = 2^e (the float32 and bf16 tables hold w itself)
@@ -286,6 +288,7 @@ struct psa_ctx {
     int64_t      lowrank_launches = 0;          // projection launches that took the route (psa_k1_lowrank_launches)
     int64_t      opt_k1_lowrank_pair;           // PSA_OPT_K1_LOWRANK_PAIR: lists with one 512-row D block through k1_lowrank_pair.hip
     int64_t      lowrank_pair_launches = 0;     // ... of which the pair launch served (psa_k1_lowrank_pair_launches)
+    bool         k1_lowrank_fold = true;        // psa_set_k1_lowrank_fold: D' = D + E in the D image, two products per node row (k1_lowrank_fold.hip)
     // its D image, node projections, the combine's L and phi, fp64 inputs (the node table goes into d_phase);
     // released when the route is switched off
     psa::DevBuf  d_lr_diff, d_lr_qn, d_lr_L, d_lr_phi, d_lr_f64;
@@ -438,6 +441,9 @@ int    launch_k1_planes(psa_ctx* c, const void* d_planes, const void* d_phase, f
 // --- k1_planes_lw.hip (the same with dedicated loader wavefronts; 128-row M blocks)
 int    launch_k1_planes_lw(psa_ctx* c, const void* d_planes, const void* d_phase, float2* d_q, const ProjGeom& g,
                            int64_t n_fg);
+// (the low-rank route's folded node rows: two products per row tile, the node table's hi piece only)
+int    launch_k1_planes_lw2(psa_ctx* c, const void* d_planes, const void* d_phase, float2* d_q, const ProjGeom& g,
+                            int64_t n_fg);
 
 // --- k1_planes_wide.hip (256-row M blocks: k-lists of more than 64 vectors under PSA_OPT_K1_WIDE)
 int    launch_k1_planes_wide(psa_ctx* c, const void* d_planes, const void* d_phase, float2* d_q, const ProjGeom& g,
@@ -450,10 +456,19 @@ int    launch_lowrank_tables(psa_ctx* c, const float* d_kvec, const double* d_kl
                              float dscale, bool pair);
 int    launch_k1_planes_diff(psa_ctx* c, const void* d_planes, const void* d_diff, float2* d_q, const ProjGeom& g, int64_t n_fg,
                              float dscale);
+// (psa_set_k1_lowrank_fold: the node table, then the folded image D' = D + E built from its lo pieces; pair: in the layout of
+// k1_lowrank_fold.h)
+int    launch_lowrank_tables_fold(psa_ctx* c, const float* d_kvec, const double* d_kline, const double* d_geo, const double* d_kappa,
+                                  const float* d_mean_all, const int* d_idx, const float* d_L, const float2* d_phi, void* d_diff,
+                                  void* d_nodes, const ProjGeom& g, int M_pad_d, float dscale, bool pair);
 
 // --- k1_lowrank_pair.hip (the route's node rows and D rows as one launch of balanced row pairs: one 512-row D block;
 // the D image in the pair layout, launch_lowrank_tables with pair = true)
 int    launch_k1_lowrank_pair(psa_ctx* c, const void* d_planes, const void* d_nodes, const void* d_diff, float2* d_qn, float2* d_q,
+                              const ProjGeom& g, int64_t n_fg, float dscale);
+
+// --- k1_lowrank_fold.hip (the same launch on the folded tables: two-product node rows + D' rows 0..127 / D' rows 128..511)
+int    launch_k1_lowrank_fold(psa_ctx* c, const void* d_planes, const void* d_nodes, const void* d_diff, float2* d_qn, float2* d_q,
                               const ProjGeom& g, int64_t n_fg, float dscale);
 
 // --- lowrank_combine.hip (the route's combine: real weights + one phase per element)
