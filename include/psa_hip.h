@@ -864,8 +864,8 @@ int psa_angle_histogram(psa_ctx* ctx, const double* box /* 9 */, const double* b
  * PSA_EINVAL: everything psa_angle_histogram refuses about the context, the box, the species, r_cut, origin_step and the
  * budget; ls null, n_ls outside [1, 8], an order outside [1, 12] or not strictly ascending; n_q outside [1, 1024];
  * hist_bytes not exact; a null hist, truncated, isolated or undefined.
- * Not here: the third-order invariants w_l and the neighbour-averaged q_l of Lechner and Dellago (both need the q_lm
- * vectors themselves), Voronoi or solid-angle-weighted neighbours.
+ * Not here: odd l in psa_local_order, the q_lm of other neighbour definitions, Voronoi or solid-angle-weighted neighbours,
+ * cluster analysis of the solid-like bonds, cell lists (w_l, the neighbour-averaged q_l and the bonds: psa_local_order).
  * Only the positions slot is read.  Atom weights and segments set on the context are ignored, not refused; every result
  * and plan of the other entry points is left as it is.  Stage times: [0] the table's upload, [5] the fraction pass,
  * [6] the neighbour pass, [1] the order pass, [4] reduce, [7] device->host. */
@@ -874,6 +874,83 @@ int psa_bond_order(psa_ctx* ctx, const double* box /* 9 */, const double* box_in
                    const int32_t* ls /* n_ls */, int32_t n_ls, int32_t n_q, uint64_t* hist /* (S, n_ls, n_q) */, size_t hist_bytes,
                    uint64_t* truncated /* S */, uint64_t* isolated /* S */, uint64_t* undefined /* S */,
                    int64_t* x /* (n_o, n_a, n_ls) or NULL */, int32_t* n /* (n_o, n_a) or NULL */);
+
+/* Local order from the vectors q_lm of every atom's neighbour shell at every time origin: the neighbour-averaged q-bar_l of
+ * Lechner and Dellago, the third-order invariants w_l and w-bar_l, and the solid-like bonds of ten Wolde, Ruiz-Montero and
+ * Frenkel, as integer counts and optionally per atom.
+ * Inputs.  The positions slot, H = box with its inverse, S <= 8 disjoint species, r_cut (S, S) and origin_step exactly as
+ * for psa_angle_histogram, under the same checks and refusals.  The neighbours of a centre are bit for bit those of
+ * psa_bond_order: all species together, at most 64, n of them with the legs d_b; the relation is symmetric bit for bit (the
+ * minimum-image chain is odd in e).
+ * Orders.  ls: n_ls strictly ascending EVEN orders in [2, 12], 1 <= n_ls <= 4.  For odd l the 3j symbol (l l l; m1 m2 m3)
+ * is antisymmetric under an exchange of two columns, so W_l vanishes identically: an odd order is refused.
+ * The vector.  With Yt_lm = sqrt(4 pi / (2 l + 1)) Y_lm (|Yt_lm| <= 1), Condon-Shortley phase included:
+ *     Q_lm(a) = sum_b t_lm(b),   t = __double2ll_rn(Yt_lm(d_b / |d_b|) 2^40) for the real and the imaginary part, m = 0 .. l
+ *     Q_{l,-m} = (-1)^m conj Q_lm;   q_lm = (Q_lm 2^-40) / n
+ * 64-bit integers (64 x 2^40 fits), and integer adds commute: Q is the same bits for any blocking, budget and atom order.
+ * The harmonics, float64, without trigonometry and without a pole; every operation rounded once, none contracted
+ * (__dmul_rn, __dadd_rn, __ddiv_rn, __dsqrt_rn only):
+ *     x, y, z = (double) d_x, d_y, d_z (exact);   r = sqrt(z z + (y y + x x));   u = (x / r, y / r, z / r)
+ *     c_0 = 1;  c_m = c_{m-1} (u_x + i u_y):   re' = re u_x + (-(im u_y)),   im' = re u_y + im u_x
+ *     Pi_mm = (2 m - 1)!! (exact);   Pi_{m+1,m} = (2 m + 1)!! u_z;
+ *     Pi_lm = ((2 l - 1) (u_z Pi_{l-1,m}) + (-((l + m - 1) Pi_{l-2,m}))) / (l - m)
+ *     Yt_lm = ((N_lm Pi_lm) re(c_m), (N_lm Pi_lm) im(c_m)), each then times 2^40 and rounded to the nearest integer
+ *     N_lm = (-1)^m sqrt(1 / prod_{k = l-m+1 .. l+m} k), float64 on the host, the product taken in ascending k
+ * A leg of length 0 makes the centre undefined (also a centre's only leg, which psa_bond_order still counts).
+ * Lechner-Dellago average, float64:  q-bar_lm(a) = (q_lm(a) + sum_{b in N(a)} q_lm(b)) / (n + 1), the sum taken in list
+ * order starting from q_lm(a), every q_lm(b) = (Q_lm(b) 2^-40) / n_b formed first.  qbar2 = sum_{m=-l..l} |q-bar_lm|^2 =
+ * q-bar_l^2, formed as sum_{m=0..l} c_m (re re + im im) in ascending m, c_0 = 1, c_m = 2.  Its bin of n_q uniform bins in
+ * q-bar over [0, 1]: the largest i < n_q with (double)(i i) <= __dmul_rn(qbar2, (double)(n_q n_q)), by bisection; no root.
+ * Third-order invariants.  W_l(v) = sum_{m1+m2+m3=0} (l l l; m1 m2 m3) Re(v_m1 v_m2 v_m3), w_l(v) = W_l(v) / S^{3/2},
+ * S = sum_m |v_m|^2 as above; evaluated as W / (S sqrt(S)).  w = w_l(Q(a) 2^-40) (scale invariant: no n) and wbar =
+ * w_l(q-bar(a)), the w-bar_l of Lechner and Dellago.  w3j: the caller's table, per order the dense block (2 l + 1)^2 of
+ * (l l l; m1 m2 -m1-m2) at [(m1 + l) (2 l + 1) + m2 + l], 0 where |m1 + m2| > l, the blocks concatenated in the order of ls
+ * (w3j_count values); the terms of a block are dealt to 64 partial sums in strides of 64 and those added pairwise by a
+ * butterfly (partners 32, 16, 8, 4, 2, 1 apart), an order that depends on the table alone.  Bin of n_w uniform bins over [-w_range, w_range]:
+ * u = __dmul_rn(__dadd_rn(w, w_range), n_w / (2 w_range)); i = floor(u) where 0 <= u < n_w, else the value counts as
+ * outside.  Where S is exactly 0 the value is undefined (NaN per atom).  w_l of a shell whose q_l is nearly 0 is noise.
+ * Solid-like bonds, for the order solid_l among ls and 0 < solid_threshold <= 1:  D = Re sum_{m=-l..l} Q_lm(a) conj Q_lm(b),
+ * A = sum_m |Q_lm(a)|^2, B = sum_m |Q_lm(b)|^2, float64 from the integers times 2^-40, sums over m = 0 .. l with the
+ * weights c_m as above.  The bond a-b is solid-like when D > 0 and D D > thr^2 (A B): no root, no division, symmetric in
+ * a <-> b bit for bit.  xi(a) = the number of such bonds, 0 .. 64.
+ * Left out, all or nothing per (origin, centre), counted once in the first that applies: truncated (more than 64
+ * neighbours), isolated (none), undefined (a leg of length 0), incomplete (a neighbour that is truncated or undefined).
+ * Outputs.  hist (S, R) uint64, a species' row R = n_ls n_q + 2 n_ls n_w + 65 + 4 + 4 n_ls:
+ *     qbar[n_ls][n_q], w[n_ls][n_w], wbar[n_ls][n_w], connections[65], truncated, isolated, undefined, incomplete,
+ *     w_outside[n_ls], w_undefined[n_ls], wbar_outside[n_ls], wbar_undefined[n_ls]
+ * For every order sum_i qbar[j][i] + the four counters = sum_i connections[i] + the four = n_o N_alpha; for w and wbar the
+ * same with that histogram's outside and undefined added.  Optionally per atom, in list order (any may be NULL): qbar2, w,
+ * wbar (n_o, n_a, n_ls) float64, NaN where the centre is left out (w, wbar: or undefined); connections (n_o, n_a) int32,
+ * -1 where left out; n (n_o, n_a) int32 the true neighbour count.
+ * As evaluated (qlm.hip): the fraction pass and the neighbour pass of psa_angle_histogram; a pass in which a wavefront takes
+ * a centre, lane b the leg b, and a 64-bit integer wave reduction leaves Q_lm in a table (n_a, sum (l + 1), 2) int64 per
+ * origin; a second pass over the same items in which a wavefront gathers its neighbours' rows of that table and counts with
+ * 32-bit integer adds in LDS, written to partials with plain stores and summed in 64-bit integers.  No global atomics, no
+ * float atomics; two identical calls and any budget give the same bits; a permutation of the atoms inside a species leaves
+ * Q the same bits and moves the float64 values by the roundings of the reordered sums.
+ * Budget (PSA_OPT_DYNAMIC_WORK_BYTES): per origin of a block 1040 n_a bytes as for psa_angle_histogram, plus 16 sum (l + 1)
+ * n_a for the table, plus (24 n_ls + 8) n_a when any of qbar2, w, wbar, connections is asked for.
+ * PSA_EINVAL: everything psa_angle_histogram refuses about the context, the box, the species, r_cut, origin_step and the
+ * budget; ls null, n_ls outside [1, 4], an order outside [2, 12], odd, or not strictly ascending; n_q or n_w outside
+ * [1, 1024]; w_range not finite or <= 0; solid_l not among ls; solid_threshold outside (0, 1]; w3j null, w3j_count not the
+ * blocks' size, an entry not finite or beyond 1 in modulus; hist_bytes not exact; a null hist.
+ * Only the positions slot is read; every result and plan of the other entry points is left as it is.  Stage times: [0] the
+ * tables' upload, [5] the fraction pass, [6] the neighbour pass, [1] the two passes, [2] of these the second, [4] reduce,
+ * [7] device->host. */
+int psa_local_order(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                    const int64_t* group_start /* S+1 */, int32_t n_groups, const double* r_cut /* S*S */, int64_t origin_step,
+                    const int32_t* ls /* n_ls */, int32_t n_ls, int32_t n_q, int32_t n_w, double w_range, int32_t solid_l,
+                    double solid_threshold, const double* w3j /* w3j_count */, int64_t w3j_count, uint64_t* hist /* (S, R) */,
+                    size_t hist_bytes, double* qbar2 /* (n_o, n_a, n_ls) or NULL */, double* w /* the same */,
+                    double* wbar /* the same */, int32_t* connections /* (n_o, n_a) or NULL */, int32_t* n /* (n_o, n_a) or NULL */);
+
+/* The first pass of psa_local_order alone at one frame: q (n_a, sum (l + 1), 2) int64, Q_lm of every listed atom, the
+ * orders' columns m = 0 .. l one after the other, (re, im).  A centre that is truncated, isolated or undefined has zeros,
+ * and -1 in Im Q of its first column (0 for every other centre: Y_l0 is real).  Refusals as for psa_local_order and
+ * psa_debug_neighbour_lists. */
+int psa_debug_qlm(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                  const int64_t* group_start /* S+1 */, int32_t n_groups, const double* r_cut /* S*S */, int64_t frame,
+                  const int32_t* ls /* n_ls */, int32_t n_ls, int64_t* q /* (n_a, sum (l + 1), 2) */);
 
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting

@@ -85,6 +85,10 @@ ORDER_MAX_L = 12        # the largest order l of a Steinhardt parameter q_l
 ORDER_MAX_LS = 8        # most orders of a call
 ORDER_MAX_BINS = 1024   # most bins of a q histogram
 ORDER_SHIFT = 24        # X_l counts units of 2^-24: q_l^2 = X_l / (n^2 2^24)
+# the caps of the local order kernels (psa_amd/csrc/qlm.hip)
+LOCAL_MAX_LS = 4        # most orders of a call, even ones in [2, ORDER_MAX_L]
+LOCAL_MAX_BINS = 1024   # most bins of a q-bar histogram and of a w histogram
+LOCAL_SHIFT = 40        # Q_lm counts units of 2^-40
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -185,6 +189,11 @@ SIGNATURES = {
     "psa_bond_order": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p, C.c_int64,
                                  _i32p, C.c_int32, C.c_int32, _u64p, C.c_size_t, _u64p, _u64p, _u64p,
                                  _i64p, _i32p]),
+    "psa_local_order": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p, C.c_int64,
+                                  _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double,
+                                  _f64p, C.c_int64, _u64p, C.c_size_t, _f64p, _f64p, _f64p, _i32p, _i32p]),
+    "psa_debug_qlm": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p, C.c_int64,
+                                _i32p, C.c_int32, _i64p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, _f64p,
                                    _f64p, _f32p, _f32p, _f32p]),
@@ -1213,6 +1222,56 @@ class Engine:
                                         undef.ctypes.data_as(_u64p), None if x is None else x.ctypes.data_as(_i64p),
                                         None if n is None else n.ctypes.data_as(_i32p)), "psa_bond_order")
         return hist, trunc, iso, undef, x, n
+
+    def local_order(self, box, r_cut, ls, n_q: int, n_w: int, w3j, groups=None, origin_step: int = 1, w_range: float = 0.2,
+                    solid_l: int = 6, solid_threshold: float = 0.7, per_atom: bool = False, box_inverse=None):
+        """The neighbour-averaged q-bar_l, the third-order invariants w_l, w-bar_l and the solid-like bonds as counts
+        (psa_local_order): (hist (S, R) uint64, qbar2, w, wbar, connections, n).  The neighbours are those of `bond_order`;
+        `ls`: at most 4 strictly ascending even orders in [2, 12]; `w3j` the 3j symbols of the orders, per order the dense
+        (2 l + 1, 2 l + 1) block of (l l l; m1 m2 -m1-m2), concatenated (`psa_amd.wigner_3j_table`).  A species' row of `hist`
+        holds qbar (n_l, n_q), w (n_l, n_w), wbar (n_l, n_w), connections (65), truncated, isolated, undefined, incomplete,
+        w_outside, w_undefined, wbar_outside, wbar_undefined (n_l each): `psa_amd.local_order.split_row` takes it apart.  With
+        `per_atom`: qbar2, w, wbar (n_o, n_a, n_l) float64 (NaN: left out or undefined), connections (n_o, n_a) int32 (-1: left
+        out) and n (n_o, n_a) int32 the true neighbour counts, in list order; else None.  `box`, `groups`, `origin_step` as
+        for `pair_histogram`.  Only positions are read, as stored."""
+        T, N = self.shape(SLOT_POSITIONS)
+        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
+        rc = self._cutoffs(r_cut, G)
+        orders = np.ascontiguousarray(ls, np.int32).ravel()
+        held = orders if orders.size else np.zeros(1, np.int32)
+        table = np.ascontiguousarray(w3j, np.float64).ravel()
+        held_3j = table if table.size else np.zeros(1, np.float64)
+        n_a = N if groups is None else int(start[-1])
+        n_o = (T - 1) // max(int(origin_step), 1) + 1 if T else 0
+        n_l = orders.size
+        row = n_l * max(int(n_q), 0) + 2 * n_l * max(int(n_w), 0) + ANGLE_MAX_NEIGHBOURS + 1 + 4 + 4 * n_l
+        hist = np.empty((G, row), np.uint64)
+        vals = [pinned_empty((n_o, n_a, n_l), np.float64) if per_atom else None for _ in range(3)]     # (every cell is written by the call)
+        xi, n = ((pinned_empty((n_o, n_a), np.int32) if per_atom else None) for _ in range(2))
+        f64 = lambda a: None if a is None else a.ctypes.data_as(_f64p)                                 # noqa: E731
+        i32 = lambda a: None if a is None else a.ctypes.data_as(_i32p)                                 # noqa: E731
+        _check(self._lib.psa_local_order(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G,
+                                         rc.ctypes.data_as(_f64p), int(origin_step), held.ctypes.data_as(_i32p), n_l, int(n_q), int(n_w),
+                                         float(w_range), int(solid_l), float(solid_threshold), held_3j.ctypes.data_as(_f64p), table.size,
+                                         hist.ctypes.data_as(_u64p), hist.nbytes, f64(vals[0]), f64(vals[1]), f64(vals[2]), i32(xi), i32(n)),
+               "psa_local_order")
+        return hist, vals[0], vals[1], vals[2], xi, n
+
+    def debug_qlm(self, box, r_cut, frame: int, ls, groups=None, box_inverse=None) -> np.ndarray:
+        """The first pass of `local_order` alone at one frame (psa_debug_qlm): Q (n_a, sum (l + 1), 2) int64, the vectors
+        Q_lm = sum_b round(Yt_lm(d_b) 2^40), m = 0 .. l, (re, im), of every listed atom; a centre that is truncated, isolated
+        or undefined has zeros and -1 in Im Q of its first column."""
+        T, N = self.shape(SLOT_POSITIONS)
+        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
+        rc = self._cutoffs(r_cut, G)
+        orders = np.ascontiguousarray(ls, np.int32).ravel()
+        held = orders if orders.size else np.zeros(1, np.int32)
+        n_a = N if groups is None else int(start[-1])
+        cols = int((orders.astype(np.int64) + 1).sum())
+        q = np.zeros((max(n_a, 1), max(cols, 1), 2), np.int64)
+        _check(self._lib.psa_debug_qlm(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G, rc.ctypes.data_as(_f64p),
+                                       int(frame), held.ctypes.data_as(_i32p), orders.size, q.ctypes.data_as(_i64p)), "psa_debug_qlm")
+        return q[:n_a, :cols]
 
     def debug_correlation_transform(self, power, L: int, n_seg: int, n_lags: int, as_float32: bool = False) -> np.ndarray:
         """The back-transform of the time correlations alone (psa_debug_correlation_transform): `power` (fields, P, cols)

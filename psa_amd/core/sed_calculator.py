@@ -37,9 +37,10 @@ from ..covariance import ModeVectors, mode_vectors, spectral_weights
 from ..displacements import (MeanSquareDisplacement, VanHoveSelf, alpha2, check_count, check_lag_frames, check_origin_step,
                              origin_counts, radial_bins)
 from ..dynamic import DynamicSpectra
-from .. import angles, order
+from .. import angles, local_order, order
 from ..angles import BondAngleDistribution
 from ..order import BondOrder
+from ..local_order import LocalOrder
 from ..pairs import RadialDistribution, VanHoveDistinct, max_pair_radius
 from .. import lattice
 from ..lattice import PowderSpectra
@@ -1000,6 +1001,55 @@ class SEDCalculator:
         out = self._displacement_run(lambda eng, box: eng.bond_order(box, rc, orders, n_q, groups, step, bool(per_atom)))
         self._refuse_truncated(out[1])
         return order.result(*out, orders, n_q, (self.traj.n_frames - 1) // step + 1, groups)
+
+    # ------------------------------------------------------------------ neighbour-averaged q_l, w_l and solid-like bonds
+    def calculate_local_order(self, r_cut, ls=(4, 6), n_q: int = 200, n_w: int = 200,
+                              basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                              basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                              origin_step: int = 1, w_range: float = 0.2, solid_l: int = 6, solid_threshold: float = 0.7,
+                              per_atom: bool = False) -> LocalOrder:
+        """The neighbour-averaged q-bar_l of Lechner and Dellago, the third-order invariants w_l and w-bar_l, and the
+        solid-like bonds of ten Wolde, Ruiz-Montero and Frenkel (not in the reference; definition in
+        psa_amd/local_order.py), computed on the GPU from the positions resident in HBM.  The neighbours, `r_cut`, the
+        species and `origin_step` are those of `calculate_bond_order`.  `ls`: at most 4 strictly ascending even orders in
+        [2, 12] (W_l of an odd l vanishes identically).  q-bar_l is counted in `n_q` <= 1024 uniform bins over [0, 1], w_l
+        and w-bar_l in `n_w` <= 1024 bins over [-w_range, w_range]; a bond a-b is solid-like when the normalised product of
+        the vectors q_{solid_l, m} of a and b exceeds `solid_threshold` in (0, 1], and `connections` counts the atoms by
+        their number of such bonds.  `per_atom=True` adds `qbar_atoms`, `w_atoms`, `wbar_atoms`, `connections_atoms`,
+        `neighbours` and `mean`.
+
+        A centre with no neighbour, a coincident one, or a neighbour that is left out itself is counted in `isolated`,
+        `undefined` or `incomplete`; where a centre has more than 64 neighbours the call raises ValueError naming the
+        species: choose a smaller `r_cut` (`Engine.local_order` returns the numbers instead).  A sharded calculator
+        refuses (NotImplementedError).  Returns a `psa_amd.LocalOrder`."""
+        n_q = check_count("n_q", n_q, _hip.LOCAL_MAX_BINS)
+        n_w = check_count("n_w", n_w, _hip.LOCAL_MAX_BINS)
+        orders = np.asarray(ls)
+        if (orders.ndim != 1 or not 1 <= orders.size <= _hip.LOCAL_MAX_LS or orders.dtype.kind not in "iu"
+                or orders.min() < 2 or orders.max() > _hip.ORDER_MAX_L or np.any(np.diff(orders) <= 0)):
+            raise ValueError(f"ls must be 1 to {_hip.LOCAL_MAX_LS} strictly ascending even integers in [2, {_hip.ORDER_MAX_L}], got {ls!r}")
+        if np.any(orders % 2):
+            raise ValueError(f"ls must be even, got {ls!r}: for odd l the 3j symbol (l l l; m1 m2 m3) is antisymmetric under an "
+                             "exchange of two columns, so W_l vanishes identically")
+        if isinstance(solid_l, (bool, np.bool_)) or not isinstance(solid_l, (int, np.integer)) or int(solid_l) not in orders.tolist():
+            raise ValueError(f"solid_l = {solid_l!r} is not among ls = {orders.tolist()}")
+        thr, reach = float(solid_threshold), float(w_range)
+        if not 0.0 < thr <= 1.0:
+            raise ValueError(f"solid_threshold must lie in (0, 1], got {solid_threshold!r}")
+        if not (np.isfinite(reach) and reach > 0.0):
+            raise ValueError(f"w_range must be finite and positive, got {w_range!r}")
+        if not isinstance(per_atom, (bool, np.bool_)):
+            raise TypeError(f"per_atom must be a bool, got {type(per_atom).__name__}")
+        rc, step, groups = self._shell_inputs(r_cut, basis_atom_indices, basis_atom_types, origin_step, "the local order parameters")
+        if groups is None:
+            zero = np.zeros((1, local_order.row_words(orders.size, n_q, n_w)), np.uint64)
+            return local_order.result(zero, None, None, None, None, None, orders, n_q, n_w, reach, int(solid_l), thr, 0, [np.zeros(0, int)])
+        table = local_order.w3j_blocks(orders)
+        out = self._displacement_run(lambda eng, box: eng.local_order(box, rc, orders, n_q, n_w, table, groups, step, reach, int(solid_l),
+                                                                      thr, bool(per_atom)))
+        res = local_order.result(*out, orders, n_q, n_w, reach, int(solid_l), thr, (self.traj.n_frames - 1) // step + 1, groups)
+        self._refuse_truncated(res.truncated)
+        return res
 
     # ------------------------------------------------------------------ partial (species-resolved) spectra on that lattice
     def _partial_species(self, basis_atom_indices, basis_atom_types, weights):

@@ -1,4 +1,4 @@
-// psa_angle_histogram, psa_debug_neighbour_lists, psa_bond_order: the bond-angle distributions of species triplets, the
+// psa_angle_histogram, psa_debug_neighbour_lists, psa_bond_order, psa_local_order, psa_debug_qlm: the bond-angle distributions of species triplets, the
 // coordination statistics of species pairs and the Steinhardt order parameters of the neighbour shells over time origins
 // (definition: include/psa_hip.h; kernels: angle.hip, order.hip, and pair.hip's fraction pass).  Only the positions slot is read; atom weights and segments set on the context are ignored; nothing of
 // the other entry points' state is touched.
@@ -12,6 +12,10 @@
 // psa_bond_order (kernel: order.hip) is the same call with the order pass in place of the angle pass: the same checks, work
 // buffer, items and reduce; with per-atom output the block's X (8 n_l n_a bytes per origin) lies behind the counts, inside
 // the budget, and every block's X and counts are copied to the caller's arrays before the next block overwrites them.
+//
+// psa_local_order and psa_debug_qlm (kernels: qlm.hip) are the same call again with two passes in place of the angle pass:
+// the first leaves the table of the Q_lm (16 sum (l + 1) n_a bytes per origin) behind the counts, the second gathers from
+// it; the per-atom rows ((24 n_l + 8) n_a bytes per origin) lie behind the table, all inside the budget.
 #include "api_internal.h"
 
 namespace psa {
@@ -239,6 +243,144 @@ int order_run(psa_ctx* c, const double* box, const double* box_inverse, const in
     return PSA_OK;
 }
 
+// an item's samples of the local order pass, 64 centres x the origins of a block, fit 32 bits in every counter
+static_assert((uint64_t)ANGLE_ITEM_CENTRES * 65535 < (1ull << 32), "an item's samples fit 32 bits");
+
+// the orders of psa_local_order and psa_debug_qlm: at most four, even, in [2, 12], strictly ascending
+int local_orders(const int32_t* ls, int32_t n_ls, LocalLs* o) {
+    PSA_REQUIRE(ls != nullptr, "null ls");
+    PSA_REQUIRE(n_ls >= 1 && n_ls <= LOCAL_MAX_LS, "the number of orders is in [1, %d], got %d", LOCAL_MAX_LS, (int)n_ls);
+    *o = LocalLs{(int)n_ls, (int)ls[n_ls - 1], 0, 0, 0u};
+    for (int j = 0; j < n_ls; ++j) {
+        PSA_REQUIRE(ls[j] >= 2 && ls[j] <= ORDER_MAX_L, "ls[%d] = %d is outside [2, %d]", j, (int)ls[j], ORDER_MAX_L);
+        PSA_REQUIRE(ls[j] % 2 == 0, "ls[%d] = %d is odd: the 3j symbol (l l l; m1 m2 m3) is antisymmetric under an exchange of two "
+                    "columns for odd l, so W_l vanishes identically; only even orders are served", j, (int)ls[j]);
+        PSA_REQUIRE(j == 0 || ls[j] > ls[j - 1], "ls must be strictly ascending: ls[%d] = %d after %d", j, (int)ls[j], (int)ls[j ? j - 1 : 0]);
+        o->mask |= 1u << ls[j];
+        o->columns += ls[j] + 1;
+    }
+    return PSA_OK;
+}
+
+// N_lm = (-1)^m sqrt(1 / prod_{k = l-m+1 .. l+m} k), the product in float64 in ascending k, at [l * 13 + m]; behind it the
+// caller's 3j blocks, (2 l + 1)^2 each, one per LOCAL_W3J_WORDS
+int upload_local_tables(psa_ctx* c, const int32_t* ls, int32_t n_ls, const double* w3j) {
+    std::vector<double> tab((size_t)LOCAL_NORM_WORDS + (size_t)n_ls * LOCAL_W3J_WORDS, 0.0);
+    for (int l = 0; l <= ORDER_MAX_L; ++l)
+        for (int m = 0; m <= l; ++m) {
+            double prod = 1.0;
+            for (int k = l - m + 1; k <= l + m; ++k) prod *= (double)k;
+            tab[(size_t)(l * (ORDER_MAX_L + 1) + m)] = (m & 1 ? -1.0 : 1.0) * std::sqrt(1.0 / prod);
+        }
+    for (int j = 0; w3j != nullptr && j < n_ls; ++j) {
+        const size_t side = 2 * (size_t)ls[j] + 1;
+        std::memcpy(&tab[(size_t)LOCAL_NORM_WORDS + (size_t)j * LOCAL_W3J_WORDS], w3j, side * side * sizeof(double));
+        w3j += side * side;
+    }
+    StageTimer st(c, PSA_T_H2D);
+    return upload(c, c->d_local_tab, tab.data(), tab.size() * sizeof(double));
+}
+
+int local_order_run(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start, int32_t n_groups,
+                    const double* r_cut, int64_t origin_step, const int32_t* ls, int32_t n_ls, int32_t n_q, int32_t n_w, double w_range,
+                    int32_t solid_l, double solid_threshold, const double* w3j, int64_t w3j_count, uint64_t* hist, size_t hist_bytes,
+                    double* qbar2, double* w, double* wbar, int32_t* connections, int32_t* n) {
+    PSA_REQUIRE(hist != nullptr, "null output");
+    LocalLs o;
+    PSA_TRY(local_orders(ls, n_ls, &o));
+    o.solid_l = solid_l;
+    PSA_REQUIRE(o.mask >> (solid_l & 31) & 1u && solid_l >= 0 && solid_l < 32, "solid_l = %d is not among ls", (int)solid_l);
+    PSA_REQUIRE(solid_threshold > 0.0 && solid_threshold <= 1.0, "the solid-like threshold is in (0, 1], got %g", solid_threshold);
+    PSA_REQUIRE(std::isfinite(w_range) && w_range > 0.0, "w_range must be finite and positive, got %g", w_range);
+    int64_t want_3j = 0;
+    for (int j = 0; j < n_ls; ++j) want_3j += (2ll * ls[j] + 1) * (2ll * ls[j] + 1);
+    PSA_REQUIRE(w3j != nullptr && w3j_count == want_3j, "w3j holds %lld values, the blocks (2 l + 1)^2 of the orders have %lld",
+                (long long)w3j_count, (long long)want_3j);
+    for (int64_t i = 0; i < want_3j; ++i) PSA_REQUIRE(std::isfinite(w3j[i]) && std::fabs(w3j[i]) <= 1.0, "w3j[%lld] = %g is no 3j symbol", (long long)i, w3j[i]);
+    const bool    atoms = qbar2 != nullptr || w != nullptr || wbar != nullptr || connections != nullptr;
+    const int64_t q_bytes = 16 * (int64_t)o.columns, extra = q_bytes + (atoms ? 24 * (int64_t)n_ls + 8 : 0);
+    AtomGroups    p;
+    AngleSpecies  sp;
+    PSA_TRY(angle_check(c, "psa_local_order", box, box_inverse, idx, group_start, n_groups, r_cut, &p, &sp, extra));
+    PSA_REQUIRE(origin_step >= 1, "origin_step must be at least 1, got %lld", (long long)origin_step);
+    PSA_REQUIRE(n_q >= 1 && n_q <= LOCAL_MAX_BINS, "the number of q bins is in [1, %d], got %d", LOCAL_MAX_BINS, (int)n_q);
+    PSA_REQUIRE(n_w >= 1 && n_w <= LOCAL_MAX_BINS, "the number of w bins is in [1, %d], got %d", LOCAL_MAX_BINS, (int)n_w);
+    const int     S = p.G;
+    const int64_t row = local_row_words(n_ls, n_q, n_w);
+    const size_t  want = (size_t)S * (size_t)row * sizeof(uint64_t);
+    PSA_REQUIRE(hist_bytes == want, "hist_bytes is %zu, the (%d,%lld) uint64 result has %zu", hist_bytes, S, (long long)row, want);
+    std::memset(hist, 0, want);
+    if (p.n_a == 0) return PSA_OK;                           // every species empty: zeros
+    PSA_TRY(upload_local_tables(c, ls, n_ls, w3j));
+    const double*   d_norm = c->d_local_tab.as<double>();
+    const LocalBins bins{(int)n_q, (int)n_w, w_range, (double)n_w / (2.0 * w_range), solid_threshold * solid_threshold};
+    // behind the table of a block of B = min(n_o, Ab) origins: q-bar^2, w, w-bar (nb n_a, n_l) float64 each, one behind the
+    // other, of the nb origins a pass runs over; behind the room of 3 B of them the connections
+    const int64_t n_o = (p.T - 1) / origin_step + 1, rows = std::min<int64_t>({n_o, p.Ab, 65535}) * p.n_a;
+    struct Rows {
+        double* values;
+        int*    xi;
+    };
+    const auto rows_of = [&](const AngleWork& wk) {
+        char* at = reinterpret_cast<char*>(wk.x) + (size_t)rows * (size_t)q_bytes;
+        if (!atoms) return Rows{nullptr, nullptr};
+        return Rows{reinterpret_cast<double*>(at), reinterpret_cast<int*>(at + 3 * (size_t)rows * (size_t)n_ls * sizeof(double))};
+    };
+    std::vector<uint64_t> acc;
+    const ShellPass       passes = [&](const AngleWork& wk, int64_t n_items, int64_t, int64_t nb) -> int {
+        const Rows r = rows_of(wk);
+        PSA_TRY(launch_qlm_sum(c, wk.count, wk.list, c->d_rs_items.ptr, n_items, d_norm, wk.x, o, p.n_a, nb));
+        StageTimer second(c, PSA_T_PROJECT);                 // (inside the caller's PSA_T_PHASE, which spans both passes)
+        return launch_local_order(c, wk.count, wk.list, c->d_rs_items.ptr, n_items, wk.x, d_norm + LOCAL_NORM_WORDS, c->d_rs_part.as<unsigned>(),
+                                  r.values, r.xi, o, bins, p.n_a, nb);
+    };
+    // the block's per-atom rows to the caller's arrays
+    const ShellPass per_atom = [&](const AngleWork& wk, int64_t, int64_t k0, int64_t nb) -> int {
+        StageTimer   st(c, PSA_T_D2H);
+        const Rows   r = rows_of(wk);
+        const size_t at = (size_t)k0 * (size_t)p.n_a, cells = (size_t)nb * (size_t)p.n_a, bytes = cells * (size_t)n_ls * sizeof(double);
+        const size_t each = cells * (size_t)n_ls;
+        double*      host[3] = {qbar2, w, wbar};
+        for (int i = 0; i < 3; ++i)
+            if (host[i] != nullptr)
+                PSA_HIP_CHECK(hipMemcpyAsync(host[i] + at * (size_t)n_ls, r.values + (size_t)i * each, bytes, hipMemcpyDeviceToHost, c->stream));
+        if (connections != nullptr) PSA_HIP_CHECK(hipMemcpyAsync(connections + at, r.xi, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (n != nullptr) PSA_HIP_CHECK(hipMemcpyAsync(n + at, wk.count, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        return PSA_OK;
+    };
+    PSA_TRY(shell_run(c, p, sp, idx, box, box_inverse, origin_step, row, extra, passes, atoms || n != nullptr ? per_atom : ShellPass(), &acc));
+    std::memcpy(hist, acc.data(), want);
+    return PSA_OK;
+}
+
+// the fraction pass, the neighbour pass and the q_lm pass of one frame: Q (n_a, columns, 2) int64
+int debug_qlm_run(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start, int32_t n_groups,
+                  const double* r_cut, int64_t frame, const int32_t* ls, int32_t n_ls, int64_t* q) {
+    PSA_REQUIRE(q != nullptr, "null output");
+    LocalLs o;
+    PSA_TRY(local_orders(ls, n_ls, &o));
+    o.solid_l = ls[0];
+    const int64_t q_bytes = 16 * (int64_t)o.columns;
+    AtomGroups    p;
+    AngleSpecies  sp;
+    PSA_TRY(angle_check(c, "psa_debug_qlm", box, box_inverse, idx, group_start, n_groups, r_cut, &p, &sp, q_bytes));
+    PSA_REQUIRE(frame >= 0 && frame <= p.T - 1, "frame %lld is outside [0, T - 1 = %lld]", (long long)frame, (long long)(p.T - 1));
+    if (p.n_a == 0) return PSA_OK;
+    int32_t                      first[PAIR_MAX_SPECIES + 1];
+    const std::vector<AngleItem> items = angle_items(p, 1, 1, first);
+    PSA_TRY(upload_atom_list(c, &p, idx));
+    PSA_TRY(upload(c, c->d_rs_items, items.data(), items.size() * sizeof(AngleItem)));
+    PSA_TRY(upload_local_tables(c, ls, n_ls, nullptr));
+    AngleWork w;
+    PSA_TRY(angle_work(c, p.n_a, 1, &w, q_bytes));
+    PSA_TRY(launch_pair_frac(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), p.d_idx, p.n_a, box_inverse, w.c, frame, 0, 1, p.T, p.N));
+    PSA_TRY(launch_angle_neighbours(c, w.c, w.count, w.list, sp, box, p.n_a, 1));
+    PSA_TRY(launch_qlm_sum(c, w.count, w.list, c->d_rs_items.ptr, (int64_t)items.size(), c->d_local_tab.as<double>(), w.x, o, p.n_a, 1));
+    PSA_HIP_CHECK(hipMemcpyAsync(q, w.x, (size_t)p.n_a * (size_t)q_bytes, hipMemcpyDeviceToHost, c->stream));
+    PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return PSA_OK;
+}
+
 // the fraction pass and the neighbour pass of one frame: the true counts and the first 64 list positions of every centre
 int debug_lists_run(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start,
                     int32_t n_groups, const double* r_cut, int64_t frame, int32_t* count, int32_t* list) {
@@ -290,6 +432,24 @@ int psa_bond_order(psa_ctx* c, const double* box, const double* box_inverse, con
     Guard guard(c);
     return synchronised(c, order_run(c, box, box_inverse, idx, group_start, n_groups, r_cut, origin_step, ls, n_ls, n_q, hist, hist_bytes,
                                      truncated, isolated, undefined, x, n), "psa_bond_order");
+}
+
+int psa_local_order(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start,
+                    int32_t n_groups, const double* r_cut, int64_t origin_step, const int32_t* ls, int32_t n_ls, int32_t n_q, int32_t n_w,
+                    double w_range, int32_t solid_l, double solid_threshold, const double* w3j, int64_t w3j_count, uint64_t* hist,
+                    size_t hist_bytes, double* qbar2, double* w, double* wbar, int32_t* connections, int32_t* n) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    return synchronised(c, local_order_run(c, box, box_inverse, idx, group_start, n_groups, r_cut, origin_step, ls, n_ls, n_q, n_w, w_range,
+                                           solid_l, solid_threshold, w3j, w3j_count, hist, hist_bytes, qbar2, w, wbar, connections, n),
+                        "psa_local_order");
+}
+
+int psa_debug_qlm(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start, int32_t n_groups,
+                  const double* r_cut, int64_t frame, const int32_t* ls, int32_t n_ls, int64_t* q) {
+    PSA_TRY(enter(c));
+    Guard guard(c);
+    return synchronised(c, debug_qlm_run(c, box, box_inverse, idx, group_start, n_groups, r_cut, frame, ls, n_ls, q), "psa_debug_qlm");
 }
 
 int psa_debug_neighbour_lists(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start,

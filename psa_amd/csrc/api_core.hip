@@ -261,7 +261,7 @@ constexpr Scratch SCRATCH[] = {
     PSA_SCRATCH(d_msd_out, REAL),
     PSA_SCRATCH(d_pair_c, REAL),
     PSA_SCRATCH(d_angle_work, INDEX),                      // (the neighbour counts lie beside the lists)
-    PSA_SCRATCH(d_angle_edges, REAL),
+    PSA_SCRATCH(d_angle_edges, REAL), PSA_SCRATCH(d_local_tab, REAL),
     PSA_SCRATCH(d_sync, REAL),
 };
 #undef PSA_SCRATCH

@@ -374,6 +374,9 @@ struct psa_ctx {
     // (n_a, 64, 4) float32 -- 1040 n_a bytes, held to opt_dynamic_work_bytes; outside it the bin edges.  psa_bond_order
     // uses the same buffer, with its per-atom X (n_a, n_l) int64 behind the counts where the caller asks for them.
     psa::DevBuf  d_angle_work, d_angle_edges;
+    // psa_local_order, psa_debug_qlm: the same buffer again, the table of the Q_lm (n_a, columns, 2) int64 and the per-atom
+    // rows behind the counts; outside it the normalisations N_lm and the 3j symbols, float64, uploaded by every call
+    psa::DevBuf  d_local_tab;
 
     psa::TimingState timing;
     double oneoff_ms[4] = {0, 0, 0, 0};   // host wall clock of work done once: rocFFT plan builds, magnitude passes,
@@ -733,6 +736,38 @@ inline int64_t order_row_words(int n_l, int n_q) { return (int64_t)n_l * n_q + 3
 // null: per centre the clamped X_l, -1 where the centre is left out
 int launch_order_hist(psa_ctx* c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items, unsigned* d_part,
                       long long* d_x, const OrderLs& ls, int64_t n_a, int64_t n_ob, int32_t n_q);
+// --- qlm.hip (psa_local_order, psa_debug_qlm: the vectors q_lm of every atom's neighbour shell from the same lists, and from
+// them the neighbour-averaged q_l, the third-order invariants w_l and the solid-like bonds; the arithmetic and the tiling
+// are in its header)
+constexpr int LOCAL_MAX_LS = 4;            // most orders of a call, even ones in [2, ORDER_MAX_L]
+constexpr int LOCAL_MAX_BINS = 1024;       // most bins of a q-bar histogram and of a w histogram
+constexpr int LOCAL_SHIFT = 40;            // a harmonic is rounded to a multiple of 2^-40
+constexpr int LOCAL_MAX_COLUMNS = 40;      // sum of l + 1 over the orders of a call at most: 7 + 9 + 11 + 13
+constexpr int LOCAL_NORM_WORDS = (ORDER_MAX_L + 1) * (ORDER_MAX_L + 1);   // N_lm at [l * 13 + m]
+constexpr int LOCAL_W3J_WORDS = (2 * ORDER_MAX_L + 1) * (2 * ORDER_MAX_L + 1);   // a column's 3j block: (2 l + 1)^2 of them used
+// the orders of a call as the kernels take them: bit l of mask is set for every l asked for (ascending: the j-th set bit is
+// column j); columns = sum of l + 1; solid_l the order of the bond test
+struct LocalLs {
+    int      n_l, l_max, columns, solid_l;
+    unsigned mask;
+};
+// columns of a partial row and of a species' accumulator row: n_l n_q bins of q-bar, n_l n_w of w, n_l n_w of w-bar, the 65
+// connection counts, the truncated, isolated, undefined and incomplete centres, then per order w outside, w undefined, w-bar
+// outside, w-bar undefined
+inline int64_t local_row_words(int n_l, int n_q, int n_w) { return (int64_t)n_l * n_q + 2ll * n_l * n_w + ANGLE_MAX_NEIGHBOURS + 1 + 4 + 4ll * n_l; }
+// d_count, d_list, d_items as for launch_angle_hist; d_norm LOCAL_NORM_WORDS float64; d_q (n_ob, n_a, columns, 2) int64: Q_lm,
+// m = 0 .. l, of every centre; a centre that is truncated, isolated or undefined gets zeros with -1 in Im Q of its first column
+int launch_qlm_sum(psa_ctx* c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items, const double* d_norm,
+                   long long* d_q, const LocalLs& ls, int64_t n_a, int64_t n_ob);
+// after launch_qlm_sum over the same items.  d_w3j (n_l, LOCAL_W3J_WORDS) float64; d_part (n_items, local_row_words) uint32;
+// per atom d_atoms (3, n_ob, n_a, n_l) float64 or null: q-bar^2, w, w-bar (NaN: left out or undefined); d_xi (n_ob, n_a) int32 or null
+struct LocalBins {
+    int    n_q, n_w;
+    double w_range, w_scale, thr2;         // [-R, R], n_w / (2 R), the squared threshold of a solid-like bond
+};
+int launch_local_order(psa_ctx* c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items, const long long* d_q,
+                       const double* d_w3j, unsigned* d_part, double* d_atoms, int* d_xi, const LocalLs& ls, const LocalBins& bins,
+                       int64_t n_a, int64_t n_ob);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 

@@ -20,8 +20,9 @@ left out of the histograms, all or nothing, when it has more than 64 neighbours 
 
     sum_i counts[alpha, j, i] + truncated[alpha] + isolated[alpha] + undefined[alpha] = n_o N_alpha    for every j
 
-  * Not here: the third-order invariants w_l and the neighbour-averaged q_l of Lechner and Dellago (both need the q_lm
-    vectors themselves), Voronoi or solid-angle-weighted neighbours, sharding.
+  * Not here: the third-order invariants w_l, the neighbour-averaged q_l of Lechner and Dellago and the solid-like bonds
+    are in `psa_amd/local_order.py`, which forms the q_lm vectors.  Left out of both: odd l there, the q_lm of other
+    neighbour definitions, Voronoi or solid-angle weights, cluster analysis of the solid-like bonds, cell lists, sharding.
 
 This module is host code only: the result type.  `SEDCalculator.calculate_bond_order` runs the kernels
 (psa_amd/csrc/angle.hip's neighbour pass, psa_amd/csrc/order.hip).
