@@ -12,6 +12,7 @@ import os
 import threading
 import weakref
 from pathlib import Path
+from types import SimpleNamespace
 from typing import Optional, Sequence
 
 import numpy as np
@@ -1161,6 +1162,21 @@ class Engine:
             raise ValueError(f"r_cut must be a scalar or ({S}, {S}), got {rc.shape}")
         return rc
 
+    def _shell_args(self, box, box_inverse, groups, r_cut, origin_step=None, ls=None):
+        """What a shell entry point starts from, by name: head (its leading arguments: handle, box, inverse, atom list, offsets, S,
+        r_cut), G, n_a, n_o (with `origin_step`), orders as int32 and their pointer lp (with `ls`), alive (the arrays behind the
+        pointers, held as long as the result is)"""
+        T, N = self.shape(SLOT_POSITIONS)
+        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
+        rc = self._cutoffs(r_cut, G)
+        orders = None if ls is None else np.ascontiguousarray(ls, np.int32).ravel()
+        held = None if ls is None else orders if orders.size else np.zeros(1, np.int32)
+        n_a = N if groups is None else int(start[-1])
+        n_o = None if origin_step is None else (T - 1) // max(int(origin_step), 1) + 1 if T else 0
+        head = (self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G, rc.ctypes.data_as(_f64p))
+        return SimpleNamespace(head=head, G=G, n_a=n_a, n_o=n_o, orders=orders, lp=None if ls is None else held.ctypes.data_as(_i32p),
+                               alive=(H, inv, keep, start, rc, held))
+
     def angle_histogram(self, box, r_cut, n_theta: int, groups=None, origin_step: int = 1, box_inverse=None):
         """Bond angles and coordination as counts (psa_angle_histogram): (angles (S, P, n_theta + 1) uint64, coord (S, S,
         65) uint64, truncated (S,) uint64).  b is a neighbour of a when b != a and |mi(r_b - r_a)| < r_cut[alpha, beta]
@@ -1169,15 +1185,13 @@ class Engine:
         uniform bins of the angle at the centre, the last entry the undefined angles; coord[alpha, beta, n] the (centre,
         origin) with exactly n beta-neighbours; a centre with more than 64 neighbours is left out of both and counted in
         truncated[alpha].  `box`, `groups`, `origin_step` as for `pair_histogram`.  Only positions are read, as stored."""
-        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
-        rc = self._cutoffs(r_cut, G)
-        P, n1 = G * (G + 1) // 2, max(int(n_theta), 0) + 1
-        angles = np.empty((G, P, n1), np.uint64)
-        coord = np.empty((G, G, ANGLE_MAX_NEIGHBOURS + 1), np.uint64)
-        trunc = np.empty(G, np.uint64)
-        _check(self._lib.psa_angle_histogram(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G,
-                                             rc.ctypes.data_as(_f64p), int(origin_step), int(n_theta), angles.ctypes.data_as(_u64p),
-                                             angles.nbytes, coord.ctypes.data_as(_u64p), coord.nbytes, trunc.ctypes.data_as(_u64p)),
+        a = self._shell_args(box, box_inverse, groups, r_cut)
+        P, n1 = a.G * (a.G + 1) // 2, max(int(n_theta), 0) + 1
+        angles = np.empty((a.G, P, n1), np.uint64)
+        coord = np.empty((a.G, a.G, ANGLE_MAX_NEIGHBOURS + 1), np.uint64)
+        trunc = np.empty(a.G, np.uint64)
+        _check(self._lib.psa_angle_histogram(*a.head, int(origin_step), int(n_theta), angles.ctypes.data_as(_u64p), angles.nbytes,
+                                             coord.ctypes.data_as(_u64p), coord.nbytes, trunc.ctypes.data_as(_u64p)),
                "psa_angle_histogram")
         return angles, coord, trunc
 
@@ -1185,16 +1199,12 @@ class Engine:
         """The neighbour pass of `angle_histogram` alone at one frame (psa_debug_neighbour_lists): (count (n_a,) int32 the
         true numbers of neighbours, list (n_a, 64) int32 the positions in the concatenated atom list of the first 64,
         ascending, padded with -1)."""
-        T, N = self.shape(SLOT_POSITIONS)
-        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
-        rc = self._cutoffs(r_cut, G)
-        n_a = N if groups is None else int(start[-1])
-        count = np.zeros(max(n_a, 1), np.int32)
-        lst = np.full((max(n_a, 1), ANGLE_MAX_NEIGHBOURS), -1, np.int32)
-        _check(self._lib.psa_debug_neighbour_lists(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G,
-                                                   rc.ctypes.data_as(_f64p), int(frame), count.ctypes.data_as(_i32p),
-                                                   lst.ctypes.data_as(_i32p)), "psa_debug_neighbour_lists")
-        return count[:n_a], lst[:n_a]
+        a = self._shell_args(box, box_inverse, groups, r_cut)
+        count = np.zeros(max(a.n_a, 1), np.int32)
+        lst = np.full((max(a.n_a, 1), ANGLE_MAX_NEIGHBOURS), -1, np.int32)
+        _check(self._lib.psa_debug_neighbour_lists(*a.head, int(frame), count.ctypes.data_as(_i32p), lst.ctypes.data_as(_i32p)),
+               "psa_debug_neighbour_lists")
+        return count[:a.n_a], lst[:a.n_a]
 
     def bond_order(self, box, r_cut, ls, n_q: int, groups=None, origin_step: int = 1, per_atom: bool = False, box_inverse=None):
         """The Steinhardt order parameters q_l as counts (psa_bond_order): (hist (S, n_l, n_q) uint64, truncated, isolated,
@@ -1205,21 +1215,14 @@ class Engine:
         With `per_atom`: x (n_o, n_a, n_l) int64, q_l^2 = x / (n^2 2^24) exactly as binned, -1 where the centre is left out,
         and n (n_o, n_a) int32 the true neighbour counts, in list order; else None, None.  `box`, `groups`, `origin_step`
         as for `pair_histogram`.  Only positions are read, as stored."""
-        T, N = self.shape(SLOT_POSITIONS)
-        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
-        rc = self._cutoffs(r_cut, G)
-        orders = np.ascontiguousarray(ls, np.int32).ravel()
-        held = orders if orders.size else np.zeros(1, np.int32)
-        n_a = N if groups is None else int(start[-1])
-        n_o = (T - 1) // max(int(origin_step), 1) + 1 if T else 0
-        hist = np.empty((G, orders.size, max(int(n_q), 0)), np.uint64)
-        trunc, iso, undef = (np.empty(G, np.uint64) for _ in range(3))
-        x = pinned_empty((n_o, n_a, orders.size), np.int64) if per_atom else None       # (every cell is written by the call)
-        n = pinned_empty((n_o, n_a), np.int32) if per_atom else None
-        _check(self._lib.psa_bond_order(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G,
-                                        rc.ctypes.data_as(_f64p), int(origin_step), held.ctypes.data_as(_i32p), orders.size, int(n_q),
-                                        hist.ctypes.data_as(_u64p), hist.nbytes, trunc.ctypes.data_as(_u64p), iso.ctypes.data_as(_u64p),
-                                        undef.ctypes.data_as(_u64p), None if x is None else x.ctypes.data_as(_i64p),
+        a = self._shell_args(box, box_inverse, groups, r_cut, origin_step, ls)
+        hist = np.empty((a.G, a.orders.size, max(int(n_q), 0)), np.uint64)
+        trunc, iso, undef = (np.empty(a.G, np.uint64) for _ in range(3))
+        x = pinned_empty((a.n_o, a.n_a, a.orders.size), np.int64) if per_atom else None       # (every cell is written by the call)
+        n = pinned_empty((a.n_o, a.n_a), np.int32) if per_atom else None
+        _check(self._lib.psa_bond_order(*a.head, int(origin_step), a.lp, a.orders.size, int(n_q), hist.ctypes.data_as(_u64p), hist.nbytes,
+                                        trunc.ctypes.data_as(_u64p), iso.ctypes.data_as(_u64p), undef.ctypes.data_as(_u64p),
+                                        None if x is None else x.ctypes.data_as(_i64p),
                                         None if n is None else n.ctypes.data_as(_i32p)), "psa_bond_order")
         return hist, trunc, iso, undef, x, n
 
@@ -1234,44 +1237,30 @@ class Engine:
         `per_atom`: qbar2, w, wbar (n_o, n_a, n_l) float64 (NaN: left out or undefined), connections (n_o, n_a) int32 (-1: left
         out) and n (n_o, n_a) int32 the true neighbour counts, in list order; else None.  `box`, `groups`, `origin_step` as
         for `pair_histogram`.  Only positions are read, as stored."""
-        T, N = self.shape(SLOT_POSITIONS)
-        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
-        rc = self._cutoffs(r_cut, G)
-        orders = np.ascontiguousarray(ls, np.int32).ravel()
-        held = orders if orders.size else np.zeros(1, np.int32)
+        a = self._shell_args(box, box_inverse, groups, r_cut, origin_step, ls)
         table = np.ascontiguousarray(w3j, np.float64).ravel()
         held_3j = table if table.size else np.zeros(1, np.float64)
-        n_a = N if groups is None else int(start[-1])
-        n_o = (T - 1) // max(int(origin_step), 1) + 1 if T else 0
-        n_l = orders.size
+        n_l = a.orders.size
         row = n_l * max(int(n_q), 0) + 2 * n_l * max(int(n_w), 0) + ANGLE_MAX_NEIGHBOURS + 1 + 4 + 4 * n_l
-        hist = np.empty((G, row), np.uint64)
-        vals = [pinned_empty((n_o, n_a, n_l), np.float64) if per_atom else None for _ in range(3)]     # (every cell is written by the call)
-        xi, n = ((pinned_empty((n_o, n_a), np.int32) if per_atom else None) for _ in range(2))
+        hist = np.empty((a.G, row), np.uint64)
+        vals = [pinned_empty((a.n_o, a.n_a, n_l), np.float64) if per_atom else None for _ in range(3)]     # (every cell is written by the call)
+        xi, n = ((pinned_empty((a.n_o, a.n_a), np.int32) if per_atom else None) for _ in range(2))
         f64 = lambda a: None if a is None else a.ctypes.data_as(_f64p)                                 # noqa: E731
         i32 = lambda a: None if a is None else a.ctypes.data_as(_i32p)                                 # noqa: E731
-        _check(self._lib.psa_local_order(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G,
-                                         rc.ctypes.data_as(_f64p), int(origin_step), held.ctypes.data_as(_i32p), n_l, int(n_q), int(n_w),
-                                         float(w_range), int(solid_l), float(solid_threshold), held_3j.ctypes.data_as(_f64p), table.size,
-                                         hist.ctypes.data_as(_u64p), hist.nbytes, f64(vals[0]), f64(vals[1]), f64(vals[2]), i32(xi), i32(n)),
-               "psa_local_order")
+        _check(self._lib.psa_local_order(*a.head, int(origin_step), a.lp, n_l, int(n_q), int(n_w), float(w_range), int(solid_l),
+                                         float(solid_threshold), held_3j.ctypes.data_as(_f64p), table.size, hist.ctypes.data_as(_u64p),
+                                         hist.nbytes, f64(vals[0]), f64(vals[1]), f64(vals[2]), i32(xi), i32(n)), "psa_local_order")
         return hist, vals[0], vals[1], vals[2], xi, n
 
     def debug_qlm(self, box, r_cut, frame: int, ls, groups=None, box_inverse=None) -> np.ndarray:
         """The first pass of `local_order` alone at one frame (psa_debug_qlm): Q (n_a, sum (l + 1), 2) int64, the vectors
         Q_lm = sum_b round(Yt_lm(d_b) 2^40), m = 0 .. l, (re, im), of every listed atom; a centre that is truncated, isolated
         or undefined has zeros and -1 in Im Q of its first column."""
-        T, N = self.shape(SLOT_POSITIONS)
-        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
-        rc = self._cutoffs(r_cut, G)
-        orders = np.ascontiguousarray(ls, np.int32).ravel()
-        held = orders if orders.size else np.zeros(1, np.int32)
-        n_a = N if groups is None else int(start[-1])
-        cols = int((orders.astype(np.int64) + 1).sum())
-        q = np.zeros((max(n_a, 1), max(cols, 1), 2), np.int64)
-        _check(self._lib.psa_debug_qlm(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G, rc.ctypes.data_as(_f64p),
-                                       int(frame), held.ctypes.data_as(_i32p), orders.size, q.ctypes.data_as(_i64p)), "psa_debug_qlm")
-        return q[:n_a, :cols]
+        a = self._shell_args(box, box_inverse, groups, r_cut, ls=ls)
+        cols = int((a.orders.astype(np.int64) + 1).sum())
+        q = np.zeros((max(a.n_a, 1), max(cols, 1), 2), np.int64)
+        _check(self._lib.psa_debug_qlm(*a.head, int(frame), a.lp, a.orders.size, q.ctypes.data_as(_i64p)), "psa_debug_qlm")
+        return q[:a.n_a, :cols]
 
     def debug_correlation_transform(self, power, L: int, n_seg: int, n_lags: int, as_float32: bool = False) -> np.ndarray:
         """The back-transform of the time correlations alone (psa_debug_correlation_transform): `power` (fields, P, cols)

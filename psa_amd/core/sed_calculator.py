@@ -968,6 +968,23 @@ class SEDCalculator:
             raise ValueError(f"centres with more than {_hip.ANGLE_MAX_NEIGHBOURS} neighbours were left out ({bad} (centre, frame) "
                              "samples): r_cut reaches beyond the first shells, choose a smaller r_cut")
 
+    @staticmethod
+    def _check_orders(ls, most, lowest, even):
+        """`ls` as an array: 1 to `most` strictly ascending integers in [`lowest`, 12], with `even` none of them odd"""
+        orders = np.asarray(ls)
+        if (orders.ndim != 1 or not 1 <= orders.size <= most or orders.dtype.kind not in "iu"
+                or orders.min() < lowest or orders.max() > _hip.ORDER_MAX_L or np.any(np.diff(orders) <= 0)):
+            raise ValueError(f"ls must be 1 to {most} strictly ascending {'even ' if even else ''}integers in [{lowest}, {_hip.ORDER_MAX_L}], got {ls!r}")
+        if even and np.any(orders % 2):
+            raise ValueError(f"ls must be even, got {ls!r}: for odd l the 3j symbol (l l l; m1 m2 m3) is antisymmetric under an "
+                             "exchange of two columns, so W_l vanishes identically")
+        return orders
+
+    @staticmethod
+    def _check_per_atom(per_atom):
+        if not isinstance(per_atom, (bool, np.bool_)):
+            raise TypeError(f"per_atom must be a bool, got {type(per_atom).__name__}")
+
     # ------------------------------------------------------------------ Steinhardt bond-orientational order parameters
     def calculate_bond_order(self, r_cut, ls=(4, 6), n_q: int = 200,
                              basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
@@ -987,12 +1004,8 @@ class SEDCalculator:
         call raises ValueError naming the species: choose a smaller `r_cut` (`Engine.bond_order` returns the numbers
         instead).  A sharded calculator refuses (NotImplementedError).  Returns a `psa_amd.BondOrder`."""
         n_q = check_count("n_q", n_q, _hip.ORDER_MAX_BINS)
-        orders = np.asarray(ls)
-        if (orders.ndim != 1 or not 1 <= orders.size <= _hip.ORDER_MAX_LS or orders.dtype.kind not in "iu"
-                or orders.min() < 1 or orders.max() > _hip.ORDER_MAX_L or np.any(np.diff(orders) <= 0)):
-            raise ValueError(f"ls must be 1 to {_hip.ORDER_MAX_LS} strictly ascending integers in [1, {_hip.ORDER_MAX_L}], got {ls!r}")
-        if not isinstance(per_atom, (bool, np.bool_)):
-            raise TypeError(f"per_atom must be a bool, got {type(per_atom).__name__}")
+        orders = self._check_orders(ls, _hip.ORDER_MAX_LS, 1, False)
+        self._check_per_atom(per_atom)
         rc, step, groups = self._shell_inputs(r_cut, basis_atom_indices, basis_atom_types, origin_step, "the bond order parameters")
         if groups is None:
             zero = np.zeros(1, np.uint64)
@@ -1024,13 +1037,7 @@ class SEDCalculator:
         refuses (NotImplementedError).  Returns a `psa_amd.LocalOrder`."""
         n_q = check_count("n_q", n_q, _hip.LOCAL_MAX_BINS)
         n_w = check_count("n_w", n_w, _hip.LOCAL_MAX_BINS)
-        orders = np.asarray(ls)
-        if (orders.ndim != 1 or not 1 <= orders.size <= _hip.LOCAL_MAX_LS or orders.dtype.kind not in "iu"
-                or orders.min() < 2 or orders.max() > _hip.ORDER_MAX_L or np.any(np.diff(orders) <= 0)):
-            raise ValueError(f"ls must be 1 to {_hip.LOCAL_MAX_LS} strictly ascending even integers in [2, {_hip.ORDER_MAX_L}], got {ls!r}")
-        if np.any(orders % 2):
-            raise ValueError(f"ls must be even, got {ls!r}: for odd l the 3j symbol (l l l; m1 m2 m3) is antisymmetric under an "
-                             "exchange of two columns, so W_l vanishes identically")
+        orders = self._check_orders(ls, _hip.LOCAL_MAX_LS, 2, True)
         if isinstance(solid_l, (bool, np.bool_)) or not isinstance(solid_l, (int, np.integer)) or int(solid_l) not in orders.tolist():
             raise ValueError(f"solid_l = {solid_l!r} is not among ls = {orders.tolist()}")
         thr, reach = float(solid_threshold), float(w_range)
@@ -1038,8 +1045,7 @@ class SEDCalculator:
             raise ValueError(f"solid_threshold must lie in (0, 1], got {solid_threshold!r}")
         if not (np.isfinite(reach) and reach > 0.0):
             raise ValueError(f"w_range must be finite and positive, got {w_range!r}")
-        if not isinstance(per_atom, (bool, np.bool_)):
-            raise TypeError(f"per_atom must be a bool, got {type(per_atom).__name__}")
+        self._check_per_atom(per_atom)
         rc, step, groups = self._shell_inputs(r_cut, basis_atom_indices, basis_atom_types, origin_step, "the local order parameters")
         if groups is None:
             zero = np.zeros((1, local_order.row_words(orders.size, n_q, n_w)), np.uint64)

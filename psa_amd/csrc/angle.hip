@@ -12,9 +12,10 @@
 // (min_image.h: min_image, radial_x), with dr = r_cut[alpha,beta]:
 //     neighbour: x = __fmul_rn(__fsqrt_rn(r2), inv_rc) < 1                       inv_rc = float32(1 / r_cut)
 // so with one cut-off the neighbours are bit for bit what pair.hip counts in bin 0 of dr = r_cut, n_r = 1.  The angle at a
-// between the legs b and c, float32, every operation rounded once, from the stored d (r2 is formed again from d: the same
-// bits):
+// between the legs b and c, float32, every operation rounded once but the square root (v_sqrt_f32 behind __fsqrt_rn: within
+// one ulp), from the stored d (r2 is formed again from d: the same bits):
 //     dot = fma(d_z(b), d_z(c), fma(d_y(b), d_y(c), d_x(b) d_x(c)));   q = r2(b) r2(c);   cos = dot / sqrt(q)
+// (shell.h: shell_r2, shell_cos -- order.hip's cosine is this one by construction: it calls the same two functions)
 // clamped to [-1, 1]; every step is symmetric in b <-> c bit for bit.  The bin is the i with cedge[i + 1] < cos <=
 // cedge[i] of the host's table cedge[i] = float32(cos(i pi / n_theta)) (cedge[0] = 1, cedge[n_theta] = -1), found by
 // bisection of the table in LDS; cos = -1 is in the last bin; a cos that is not a number (r2 = 0, a coincident neighbour)
@@ -27,14 +28,14 @@
 // the list is in the order of the atom list.  Angle pass: a workgroup of four wavefronts takes an item of the host's table
 // (64 centres of one species, a slab of origins) and a chunk of species pairs whose histograms fit the LDS; a wavefront
 // takes a centre, its lanes load the list once (64 x 16 bytes, one coalesced read, issued while the centre before is
-// counted) and lane j takes the pairs (j, j + m
-// mod n), m = 1 .. n / 2, the partner's leg by cross-lane reads -- every unordered pair once.  Counts are 32-bit integer
-// adds in LDS (the host keeps an item's samples below 2^32), written to partials with plain stores and summed in uint64:
-// integer adds commute, so the counts are the same bits whatever the blocking and the order of the atoms in a species.
+// counted: shell.h's centre walk) and lane j takes the pairs (j, j + m mod n), m = 1 .. n / 2, the partner's leg by
+// cross-lane reads -- every unordered pair once (shell.h's leg-pair step).  Counts are 32-bit integer adds in LDS (the
+// host keeps an item's samples below 2^32), written to partials with plain stores and summed in uint64: integer adds
+// commute, so the counts are the same bits whatever the blocking and the order of the atoms in a species.
 #include <algorithm>
 
 #include "min_image.h"
-#include "psa_ctx.h"
+#include "shell.h"
 
 namespace psa {
 
@@ -132,22 +133,13 @@ angle_hist_kernel(const int* __restrict__ count, const float4* __restrict__ list
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64), lane = threadIdx.x % 64;
     // the wavefront's centres in turn, the next one's count and list on their way while this one is counted: every lane
     // loads a slot of the list whether it is filled or not (the slots are there; the lanes at and beyond n are masked)
-    int     k = it.slab, ci = wave;
-    bool    more = k < n_ob && ci < it.a_n;
-    int64_t row = (int64_t)k * n_a + it.a_lo + ci;
-    int     n_next = more ? count[row] : 0;
-    float4  e_next = more ? list[row * ANGLE_MAX_NEIGHBOURS + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+    SHELL_WALK_FIRST(it, wave, n_a, n_ob);
+    int    n_next = more ? count[row] : 0;
+    float4 e_next = more ? list[row * ANGLE_MAX_NEIGHBOURS + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
     while (more) {
-        const int n = __builtin_amdgcn_readfirstlane(n_next);
-        float4    e = e_next;
-        ci += ANGLE_CENTRES / 64;
-        if (ci >= it.a_n) ci = wave, k += it.n_os;
-        more = k < n_ob && ci < it.a_n;
-        if (more) {
-            row = (int64_t)k * n_a + it.a_lo + ci;
-            n_next = count[row];
-            e_next = list[row * ANGLE_MAX_NEIGHBOURS + lane];
-        }
+        const int    n = __builtin_amdgcn_readfirstlane(n_next);
+        const float4 e = e_next;
+        SHELL_WALK_NEXT(it, wave, n_a, n_ob, (n_next = count[row], e_next = list[row * ANGLE_MAX_NEIGHBOURS + lane]))
         if (n > ANGLE_MAX_NEIGHBOURS) {                                // truncated: all or nothing
             if (first && lane == 0) atomicAdd(&coord[n_coord - 1], 1u);
             continue;
@@ -158,18 +150,15 @@ angle_hist_kernel(const int* __restrict__ count, const float4* __restrict__ list
                 const int m = __popcll(__ballot(s == be));
                 if (lane == 0) atomicAdd(&coord[be * (ANGLE_MAX_NEIGHBOURS + 1) + m], 1u);
             }
-        const float r2 = __fmaf_rn(e.z, e.z, __fmaf_rn(e.y, e.y, __fmul_rn(e.x, e.x)));
+        const float r2 = shell_r2(e);
         for (int m = 1; 2 * m <= n; ++m) {
-            int src = lane + m;
-            src = src >= n ? src - n : src;
-            src = lane < n ? src : lane;
-            const float ox = __shfl(e.x, src), oy = __shfl(e.y, src), oz = __shfl(e.z, src), o2 = __shfl(r2, src);
-            const int   os = __shfl(s, src);
-            if (lane >= (2 * m == n ? m : n)) continue;                // n even, m = n / 2: each pair once
+            const int    src = shell_partner(lane, m, n);
+            const float4 o = shell_partner_leg(e, r2, src);
+            const int    os = __shfl(s, src);
+            if (!shell_has_pair(lane, m, n)) continue;
             const int lo = min(s, os), hi = max(s, os), p = lo * S - lo * (lo - 1) / 2 + hi - lo - p0;
             if (p < 0 || p >= np) continue;
-            const float dot = __fmaf_rn(e.z, oz, __fmaf_rn(e.y, oy, __fmul_rn(e.x, ox)));
-            float       cs = __fdiv_rn(dot, __fsqrt_rn(__fmul_rn(r2, o2)));
+            float cs = shell_cos(e, r2, o);
             int         bin = n_theta;                                 // not a number: undefined
             if (cs == cs) {
                 cs = fminf(1.f, fmaxf(-1.f, cs));
@@ -207,8 +196,8 @@ int launch_angle_neighbours(psa_ctx* c, const float* d_c, int* d_count, void* d_
 int launch_angle_hist(psa_ctx* c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items, const float* d_edges,
                       unsigned* d_part, int32_t S, int64_t n_a, int64_t n_ob, int32_t n_theta) {
     if (n_items == 0) return PSA_OK;
-    PSA_REQUIRE(n_items < (1ll << 31) && S >= 1 && S <= PAIR_MAX_SPECIES && n_a < (1ll << ANGLE_SPECIES_SHIFT) && n_ob >= 1 &&
-                    n_ob <= 65535 && n_theta >= 1 && n_theta <= ANGLE_MAX_BINS, "angle pass outside its grid");
+    PSA_REQUIRE(shell_grid_check(n_items, n_a, n_ob) && S >= 1 && S <= PAIR_MAX_SPECIES && n_theta >= 1 && n_theta <= ANGLE_MAX_BINS,
+                "angle pass outside its grid");
     const int P = S * (S + 1) / 2, per_chunk = std::min(P, ANGLE_HIST_WORDS / (n_theta + 1));
     hipLaunchKernelGGL(angle_hist_kernel, dim3((unsigned)n_items, (unsigned)((P + per_chunk - 1) / per_chunk)), dim3(ANGLE_CENTRES),
                        (size_t)per_chunk * (size_t)(n_theta + 1) * sizeof(unsigned), c->stream, d_count, static_cast<const float4*>(d_list), static_cast<const AngleItem*>(d_items), d_edges, d_part,

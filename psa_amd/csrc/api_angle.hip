@@ -1,7 +1,9 @@
-// psa_angle_histogram, psa_debug_neighbour_lists, psa_bond_order, psa_local_order, psa_debug_qlm: the bond-angle distributions of species triplets, the
-// coordination statistics of species pairs and the Steinhardt order parameters of the neighbour shells over time origins
-// (definition: include/psa_hip.h; kernels: angle.hip, order.hip, and pair.hip's fraction pass).  Only the positions slot is read; atom weights and segments set on the context are ignored; nothing of
-// the other entry points' state is touched.
+// psa_angle_histogram, psa_debug_neighbour_lists, psa_bond_order, psa_local_order, psa_debug_qlm: the bond-angle
+// distributions of species triplets, the coordination statistics of species pairs, the Steinhardt order parameters q_l and
+// the local order parameters (q-bar_l, w_l, solid-like bonds) of the neighbour shells over time origins (definition:
+// include/psa_hip.h; kernels: angle.hip, order.hip, qlm.hip -- their shared parts in shell.h -- and pair.hip's fraction
+// pass).  Only the positions slot is read; atom weights and segments set on the context are ignored; nothing of the other
+// entry points' state is touched.
 //
 // Budget (PSA_OPT_DYNAMIC_WORK_BYTES = W): per origin of a block the centred fractional coordinates of the listed atoms
 // (12 n_a bytes), their neighbour counts (4 n_a) and their neighbour lists (64 x 16 n_a): 1040 n_a bytes; a block is a
@@ -30,10 +32,12 @@ static_assert((uint64_t)ANGLE_ITEM_CENTRES * ANGLE_MAX_SLAB * (ANGLE_MAX_NEIGHBO
               "an item's samples fit 32 bits");
 constexpr int64_t ANGLE_ORIGIN_BYTES = 12 + 4 + 16 * ANGLE_MAX_NEIGHBOURS;   // per atom and origin
 
-// the shared checks, the cut-offs and the budget (extra: bytes per atom and origin behind the counts); fills p (Ab: origins
-// of a block) and sp
+// the shared checks, the cut-offs, the budget (extra: bytes per atom and origin behind the counts) and origin_step (1 for
+// the entries of one frame); fills p and sp.  p->Ab: the origins of a block, as many of the origins 0, origin_step, ... as
+// the budget and the fraction pass's grid (65535) hold -- the one place that decides it
 int angle_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
-                const int64_t* group_start, int32_t n_groups, const double* r_cut, AtomGroups* p, AngleSpecies* sp, int64_t extra = 0) {
+                const int64_t* group_start, int32_t n_groups, const double* r_cut, int64_t origin_step, AtomGroups* p, AngleSpecies* sp,
+                int64_t extra = 0) {
     PSA_TRY(group_list_check(c, entry, box, box_inverse, idx, group_start, n_groups, p));
     PSA_REQUIRE(r_cut != nullptr, "null r_cut");
     const int    S = p->G;
@@ -59,7 +63,8 @@ int angle_check(psa_ctx* c, const char* entry, const double* box, const double* 
     PSA_REQUIRE(W / per_origin >= 1, "the work budget of %lld bytes (PSA_OPT_DYNAMIC_WORK_BYTES) cannot hold the smallest block: the "
                 "fractional coordinates, neighbour counts and neighbour lists of %lld atoms at one origin need %lld bytes", (long long)W,
                 (long long)p->n_a, (long long)per_origin);
-    p->Ab = W / per_origin;
+    PSA_REQUIRE(origin_step >= 1, "origin_step must be at least 1, got %lld", (long long)origin_step);
+    p->Ab = std::min<int64_t>({(p->T - 1) / origin_step + 1, W / per_origin, 65535});
     return PSA_OK;
 }
 
@@ -110,7 +115,7 @@ using ShellPass = std::function<int(const AngleWork& w, int64_t n_items, int64_t
 int shell_run(psa_ctx* c, AtomGroups& p, const AngleSpecies& sp, const int32_t* idx, const double* box, const double* box_inverse,
               int64_t origin_step, int64_t row, int64_t extra, const ShellPass& pass, const ShellPass& after, std::vector<uint64_t>* acc) {
     const int     S = p.G;
-    const int64_t n_o = (p.T - 1) / origin_step + 1, B = std::min<int64_t>({n_o, p.Ab, 65535});
+    const int64_t n_o = (p.T - 1) / origin_step + 1, B = p.Ab;
     int32_t                      first[PAIR_MAX_SPECIES + 1];
     const std::vector<AngleItem> items = angle_items(p, B, row, first);
     AngleWork                    w;
@@ -153,14 +158,42 @@ int shell_run(psa_ctx* c, AtomGroups& p, const AngleSpecies& sp, const int32_t* 
     return PSA_OK;
 }
 
+// A block's per-atom rows to the caller's arrays: per output the caller's array over all origins (null: not asked for), the
+// block's rows on the device and the bytes of a cell, one per (origin, atom)
+struct AtomRows { void* host; const void* dev; size_t cell; };
+int copy_atom_rows(psa_ctx* c, int64_t n_a, int64_t k0, int64_t nb, std::initializer_list<AtomRows> rows) {
+    StageTimer   st(c, PSA_T_D2H);
+    const size_t at = (size_t)k0 * (size_t)n_a, cells = (size_t)nb * (size_t)n_a;
+    for (const AtomRows& r : rows)
+        if (r.host != nullptr)
+            PSA_HIP_CHECK(hipMemcpyAsync(static_cast<char*>(r.host) + at * r.cell, r.dev, cells * r.cell, hipMemcpyDeviceToHost, c->stream));
+    return PSA_OK;
+}
+
+// The orders of a call: 1 to `most` of them, each in [lowest, ORDER_MAX_L] and with `even` not odd, strictly ascending; fills
+// o but solid_l (mask: bit l set for every order, columns: the sum of l + 1)
+int ascending_orders(const int32_t* ls, int32_t n_ls, int most, int lowest, bool even, LocalLs* o) {
+    PSA_REQUIRE(ls != nullptr, "null ls");
+    PSA_REQUIRE(n_ls >= 1 && n_ls <= most, "the number of orders is in [1, %d], got %d", most, (int)n_ls);
+    *o = LocalLs{(int)n_ls, (int)ls[n_ls - 1], 0, 0, 0u};
+    for (int j = 0; j < n_ls; ++j) {
+        PSA_REQUIRE(ls[j] >= lowest && ls[j] <= ORDER_MAX_L, "ls[%d] = %d is outside [%d, %d]", j, (int)ls[j], lowest, ORDER_MAX_L);
+        PSA_REQUIRE(!even || ls[j] % 2 == 0, "ls[%d] = %d is odd: the 3j symbol (l l l; m1 m2 m3) is antisymmetric under an exchange of two "
+                    "columns for odd l, so W_l vanishes identically; only even orders are served", j, (int)ls[j]);
+        PSA_REQUIRE(j == 0 || ls[j] > ls[j - 1], "ls must be strictly ascending: ls[%d] = %d after %d", j, (int)ls[j], (int)ls[j ? j - 1 : 0]);
+        o->mask |= 1u << ls[j];
+        o->columns += ls[j] + 1;
+    }
+    return PSA_OK;
+}
+
 int angle_run(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start, int32_t n_groups,
               const double* r_cut, int64_t origin_step, int32_t n_theta, uint64_t* angles, size_t angles_bytes, uint64_t* coord,
               size_t coord_bytes, uint64_t* truncated) {
     PSA_REQUIRE(angles != nullptr && coord != nullptr && truncated != nullptr, "null output");
     AtomGroups   p;
     AngleSpecies sp;
-    PSA_TRY(angle_check(c, "psa_angle_histogram", box, box_inverse, idx, group_start, n_groups, r_cut, &p, &sp));
-    PSA_REQUIRE(origin_step >= 1, "origin_step must be at least 1, got %lld", (long long)origin_step);
+    PSA_TRY(angle_check(c, "psa_angle_histogram", box, box_inverse, idx, group_start, n_groups, r_cut, origin_step, &p, &sp));
     PSA_REQUIRE(n_theta >= 1 && n_theta <= ANGLE_MAX_BINS, "the number of bins is in [1, %d], got %d", ANGLE_MAX_BINS, (int)n_theta);
     const int    S = p.G, P = S * (S + 1) / 2, n1 = n_theta + 1, NC = ANGLE_MAX_NEIGHBOURS + 1;
     const size_t want_a = (size_t)S * (size_t)P * (size_t)n1 * sizeof(uint64_t), want_c = (size_t)S * (size_t)S * (size_t)NC * sizeof(uint64_t);
@@ -199,19 +232,13 @@ int order_run(psa_ctx* c, const double* box, const double* box_inverse, const in
               const double* r_cut, int64_t origin_step, const int32_t* ls, int32_t n_ls, int32_t n_q, uint64_t* hist, size_t hist_bytes,
               uint64_t* truncated, uint64_t* isolated, uint64_t* undefined, int64_t* x, int32_t* n) {
     PSA_REQUIRE(hist != nullptr && truncated != nullptr && isolated != nullptr && undefined != nullptr, "null output");
-    PSA_REQUIRE(ls != nullptr, "null ls");
-    PSA_REQUIRE(n_ls >= 1 && n_ls <= ORDER_MAX_LS, "the number of orders is in [1, %d], got %d", ORDER_MAX_LS, (int)n_ls);
-    OrderLs o{(int)n_ls, (int)ls[n_ls - 1], 0u};
-    for (int j = 0; j < n_ls; ++j) {
-        PSA_REQUIRE(ls[j] >= 1 && ls[j] <= ORDER_MAX_L, "ls[%d] = %d is outside [1, %d]", j, (int)ls[j], ORDER_MAX_L);
-        PSA_REQUIRE(j == 0 || ls[j] > ls[j - 1], "ls must be strictly ascending: ls[%d] = %d after %d", j, (int)ls[j], (int)ls[j ? j - 1 : 0]);
-        o.mask |= 1u << ls[j];
-    }
+    LocalLs all;
+    PSA_TRY(ascending_orders(ls, n_ls, ORDER_MAX_LS, 1, false, &all));
+    const OrderLs o{all.n_l, all.l_max, all.mask};
     const int64_t extra = x != nullptr ? 8 * (int64_t)n_ls : 0;
     AtomGroups    p;
     AngleSpecies  sp;
-    PSA_TRY(angle_check(c, "psa_bond_order", box, box_inverse, idx, group_start, n_groups, r_cut, &p, &sp, extra));
-    PSA_REQUIRE(origin_step >= 1, "origin_step must be at least 1, got %lld", (long long)origin_step);
+    PSA_TRY(angle_check(c, "psa_bond_order", box, box_inverse, idx, group_start, n_groups, r_cut, origin_step, &p, &sp, extra));
     PSA_REQUIRE(n_q >= 1 && n_q <= ORDER_MAX_BINS, "the number of bins is in [1, %d], got %d", ORDER_MAX_BINS, (int)n_q);
     const int    S = p.G;
     const size_t bins = (size_t)n_ls * (size_t)n_q, want = (size_t)S * bins * sizeof(uint64_t);
@@ -224,14 +251,8 @@ int order_run(psa_ctx* c, const double* box, const double* box_inverse, const in
     const ShellPass       order_pass = [&](const AngleWork& w, int64_t n_items, int64_t, int64_t nb) -> int {
         return launch_order_hist(c, w.count, w.list, c->d_rs_items.ptr, n_items, c->d_rs_part.as<unsigned>(), w.x, o, p.n_a, nb, n_q);
     };
-    // the block's per-atom rows to the caller's arrays
     const ShellPass per_atom = [&](const AngleWork& w, int64_t, int64_t k0, int64_t nb) -> int {
-        StageTimer   st(c, PSA_T_D2H);
-        const size_t at = (size_t)k0 * (size_t)p.n_a, cells = (size_t)nb * (size_t)p.n_a;
-        if (x != nullptr)
-            PSA_HIP_CHECK(hipMemcpyAsync(x + at * (size_t)n_ls, w.x, cells * (size_t)n_ls * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        if (n != nullptr) PSA_HIP_CHECK(hipMemcpyAsync(n + at, w.count, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        return PSA_OK;
+        return copy_atom_rows(c, p.n_a, k0, nb, {{x, w.x, (size_t)n_ls * sizeof(int64_t)}, {n, w.count, sizeof(int32_t)}});
     };
     PSA_TRY(shell_run(c, p, sp, idx, box, box_inverse, origin_step, row, extra, order_pass, x != nullptr || n != nullptr ? per_atom : ShellPass(),
                       &acc));
@@ -245,22 +266,6 @@ int order_run(psa_ctx* c, const double* box, const double* box_inverse, const in
 
 // an item's samples of the local order pass, 64 centres x the origins of a block, fit 32 bits in every counter
 static_assert((uint64_t)ANGLE_ITEM_CENTRES * 65535 < (1ull << 32), "an item's samples fit 32 bits");
-
-// the orders of psa_local_order and psa_debug_qlm: at most four, even, in [2, 12], strictly ascending
-int local_orders(const int32_t* ls, int32_t n_ls, LocalLs* o) {
-    PSA_REQUIRE(ls != nullptr, "null ls");
-    PSA_REQUIRE(n_ls >= 1 && n_ls <= LOCAL_MAX_LS, "the number of orders is in [1, %d], got %d", LOCAL_MAX_LS, (int)n_ls);
-    *o = LocalLs{(int)n_ls, (int)ls[n_ls - 1], 0, 0, 0u};
-    for (int j = 0; j < n_ls; ++j) {
-        PSA_REQUIRE(ls[j] >= 2 && ls[j] <= ORDER_MAX_L, "ls[%d] = %d is outside [2, %d]", j, (int)ls[j], ORDER_MAX_L);
-        PSA_REQUIRE(ls[j] % 2 == 0, "ls[%d] = %d is odd: the 3j symbol (l l l; m1 m2 m3) is antisymmetric under an exchange of two "
-                    "columns for odd l, so W_l vanishes identically; only even orders are served", j, (int)ls[j]);
-        PSA_REQUIRE(j == 0 || ls[j] > ls[j - 1], "ls must be strictly ascending: ls[%d] = %d after %d", j, (int)ls[j], (int)ls[j ? j - 1 : 0]);
-        o->mask |= 1u << ls[j];
-        o->columns += ls[j] + 1;
-    }
-    return PSA_OK;
-}
 
 // N_lm = (-1)^m sqrt(1 / prod_{k = l-m+1 .. l+m} k), the product in float64 in ascending k, at [l * 13 + m]; behind it the
 // caller's 3j blocks, (2 l + 1)^2 each, one per LOCAL_W3J_WORDS
@@ -287,7 +292,7 @@ int local_order_run(psa_ctx* c, const double* box, const double* box_inverse, co
                     double* qbar2, double* w, double* wbar, int32_t* connections, int32_t* n) {
     PSA_REQUIRE(hist != nullptr, "null output");
     LocalLs o;
-    PSA_TRY(local_orders(ls, n_ls, &o));
+    PSA_TRY(ascending_orders(ls, n_ls, LOCAL_MAX_LS, 2, true, &o));   // at most four, even, in [2, 12]
     o.solid_l = solid_l;
     PSA_REQUIRE(o.mask >> (solid_l & 31) & 1u && solid_l >= 0 && solid_l < 32, "solid_l = %d is not among ls", (int)solid_l);
     PSA_REQUIRE(solid_threshold > 0.0 && solid_threshold <= 1.0, "the solid-like threshold is in (0, 1], got %g", solid_threshold);
@@ -301,8 +306,7 @@ int local_order_run(psa_ctx* c, const double* box, const double* box_inverse, co
     const int64_t q_bytes = 16 * (int64_t)o.columns, extra = q_bytes + (atoms ? 24 * (int64_t)n_ls + 8 : 0);
     AtomGroups    p;
     AngleSpecies  sp;
-    PSA_TRY(angle_check(c, "psa_local_order", box, box_inverse, idx, group_start, n_groups, r_cut, &p, &sp, extra));
-    PSA_REQUIRE(origin_step >= 1, "origin_step must be at least 1, got %lld", (long long)origin_step);
+    PSA_TRY(angle_check(c, "psa_local_order", box, box_inverse, idx, group_start, n_groups, r_cut, origin_step, &p, &sp, extra));
     PSA_REQUIRE(n_q >= 1 && n_q <= LOCAL_MAX_BINS, "the number of q bins is in [1, %d], got %d", LOCAL_MAX_BINS, (int)n_q);
     PSA_REQUIRE(n_w >= 1 && n_w <= LOCAL_MAX_BINS, "the number of w bins is in [1, %d], got %d", LOCAL_MAX_BINS, (int)n_w);
     const int     S = p.G;
@@ -314,9 +318,9 @@ int local_order_run(psa_ctx* c, const double* box, const double* box_inverse, co
     PSA_TRY(upload_local_tables(c, ls, n_ls, w3j));
     const double*   d_norm = c->d_local_tab.as<double>();
     const LocalBins bins{(int)n_q, (int)n_w, w_range, (double)n_w / (2.0 * w_range), solid_threshold * solid_threshold};
-    // behind the table of a block of B = min(n_o, Ab) origins: q-bar^2, w, w-bar (nb n_a, n_l) float64 each, one behind the
-    // other, of the nb origins a pass runs over; behind the room of 3 B of them the connections
-    const int64_t n_o = (p.T - 1) / origin_step + 1, rows = std::min<int64_t>({n_o, p.Ab, 65535}) * p.n_a;
+    // behind the table of a block of p.Ab origins: q-bar^2, w, w-bar (nb n_a, n_l) float64 each, one behind the other, of
+    // the nb origins a pass runs over; behind the room of 3 p.Ab of them the connections
+    const int64_t rows = p.Ab * p.n_a;
     struct Rows {
         double* values;
         int*    xi;
@@ -334,23 +338,29 @@ int local_order_run(psa_ctx* c, const double* box, const double* box_inverse, co
         return launch_local_order(c, wk.count, wk.list, c->d_rs_items.ptr, n_items, wk.x, d_norm + LOCAL_NORM_WORDS, c->d_rs_part.as<unsigned>(),
                                   r.values, r.xi, o, bins, p.n_a, nb);
     };
-    // the block's per-atom rows to the caller's arrays
     const ShellPass per_atom = [&](const AngleWork& wk, int64_t, int64_t k0, int64_t nb) -> int {
-        StageTimer   st(c, PSA_T_D2H);
         const Rows   r = rows_of(wk);
-        const size_t at = (size_t)k0 * (size_t)p.n_a, cells = (size_t)nb * (size_t)p.n_a, bytes = cells * (size_t)n_ls * sizeof(double);
-        const size_t each = cells * (size_t)n_ls;
-        double*      host[3] = {qbar2, w, wbar};
-        for (int i = 0; i < 3; ++i)
-            if (host[i] != nullptr)
-                PSA_HIP_CHECK(hipMemcpyAsync(host[i] + at * (size_t)n_ls, r.values + (size_t)i * each, bytes, hipMemcpyDeviceToHost, c->stream));
-        if (connections != nullptr) PSA_HIP_CHECK(hipMemcpyAsync(connections + at, r.xi, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (n != nullptr) PSA_HIP_CHECK(hipMemcpyAsync(n + at, wk.count, cells * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        return PSA_OK;
+        const size_t each = atoms ? (size_t)nb * (size_t)p.n_a * (size_t)n_ls : 0, cell = (size_t)n_ls * sizeof(double);
+        return copy_atom_rows(c, p.n_a, k0, nb, {{qbar2, r.values, cell}, {w, r.values + each, cell}, {wbar, r.values + 2 * each, cell},
+                                                 {connections, r.xi, sizeof(int32_t)}, {n, wk.count, sizeof(int32_t)}});
     };
     PSA_TRY(shell_run(c, p, sp, idx, box, box_inverse, origin_step, row, extra, passes, atoms || n != nullptr ? per_atom : ShellPass(), &acc));
     std::memcpy(hist, acc.data(), want);
     return PSA_OK;
+}
+
+// What the two entries of one frame start with after angle_check: the frame refused outside [0, T - 1]; then, unless no atom
+// is listed (w->list stays null), the atom list uploaded, the work buffer of one origin (extra as for shell_run) and the
+// fraction pass and the neighbour pass of that frame into it
+int shell_one_frame(psa_ctx* c, AtomGroups& p, const AngleSpecies& sp, const int32_t* idx, const double* box, const double* box_inverse,
+                    int64_t frame, int64_t extra, AngleWork* w) {
+    PSA_REQUIRE(frame >= 0 && frame <= p.T - 1, "frame %lld is outside [0, T - 1 = %lld]", (long long)frame, (long long)(p.T - 1));
+    *w = AngleWork{};
+    if (p.n_a == 0) return PSA_OK;
+    PSA_TRY(upload_atom_list(c, &p, idx));
+    PSA_TRY(angle_work(c, p.n_a, 1, w, extra));
+    PSA_TRY(launch_pair_frac(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), p.d_idx, p.n_a, box_inverse, w->c, frame, 0, 1, p.T, p.N));
+    return launch_angle_neighbours(c, w->c, w->count, w->list, sp, box, p.n_a, 1);
 }
 
 // the fraction pass, the neighbour pass and the q_lm pass of one frame: Q (n_a, columns, 2) int64
@@ -358,23 +368,19 @@ int debug_qlm_run(psa_ctx* c, const double* box, const double* box_inverse, cons
                   const double* r_cut, int64_t frame, const int32_t* ls, int32_t n_ls, int64_t* q) {
     PSA_REQUIRE(q != nullptr, "null output");
     LocalLs o;
-    PSA_TRY(local_orders(ls, n_ls, &o));
+    PSA_TRY(ascending_orders(ls, n_ls, LOCAL_MAX_LS, 2, true, &o));   // at most four, even, in [2, 12]
     o.solid_l = ls[0];
     const int64_t q_bytes = 16 * (int64_t)o.columns;
     AtomGroups    p;
     AngleSpecies  sp;
-    PSA_TRY(angle_check(c, "psa_debug_qlm", box, box_inverse, idx, group_start, n_groups, r_cut, &p, &sp, q_bytes));
-    PSA_REQUIRE(frame >= 0 && frame <= p.T - 1, "frame %lld is outside [0, T - 1 = %lld]", (long long)frame, (long long)(p.T - 1));
+    AngleWork     w;
+    PSA_TRY(angle_check(c, "psa_debug_qlm", box, box_inverse, idx, group_start, n_groups, r_cut, 1, &p, &sp, q_bytes));
+    PSA_TRY(shell_one_frame(c, p, sp, idx, box, box_inverse, frame, q_bytes, &w));
     if (p.n_a == 0) return PSA_OK;
     int32_t                      first[PAIR_MAX_SPECIES + 1];
     const std::vector<AngleItem> items = angle_items(p, 1, 1, first);
-    PSA_TRY(upload_atom_list(c, &p, idx));
     PSA_TRY(upload(c, c->d_rs_items, items.data(), items.size() * sizeof(AngleItem)));
     PSA_TRY(upload_local_tables(c, ls, n_ls, nullptr));
-    AngleWork w;
-    PSA_TRY(angle_work(c, p.n_a, 1, &w, q_bytes));
-    PSA_TRY(launch_pair_frac(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), p.d_idx, p.n_a, box_inverse, w.c, frame, 0, 1, p.T, p.N));
-    PSA_TRY(launch_angle_neighbours(c, w.c, w.count, w.list, sp, box, p.n_a, 1));
     PSA_TRY(launch_qlm_sum(c, w.count, w.list, c->d_rs_items.ptr, (int64_t)items.size(), c->d_local_tab.as<double>(), w.x, o, p.n_a, 1));
     PSA_HIP_CHECK(hipMemcpyAsync(q, w.x, (size_t)p.n_a * (size_t)q_bytes, hipMemcpyDeviceToHost, c->stream));
     PSA_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -387,14 +393,10 @@ int debug_lists_run(psa_ctx* c, const double* box, const double* box_inverse, co
     PSA_REQUIRE(count != nullptr && list != nullptr, "null output");
     AtomGroups   p;
     AngleSpecies sp;
-    PSA_TRY(angle_check(c, "psa_debug_neighbour_lists", box, box_inverse, idx, group_start, n_groups, r_cut, &p, &sp));
-    PSA_REQUIRE(frame >= 0 && frame <= p.T - 1, "frame %lld is outside [0, T - 1 = %lld]", (long long)frame, (long long)(p.T - 1));
+    AngleWork    w;
+    PSA_TRY(angle_check(c, "psa_debug_neighbour_lists", box, box_inverse, idx, group_start, n_groups, r_cut, 1, &p, &sp));
+    PSA_TRY(shell_one_frame(c, p, sp, idx, box, box_inverse, frame, 0, &w));
     if (p.n_a == 0) return PSA_OK;
-    PSA_TRY(upload_atom_list(c, &p, idx));
-    AngleWork w;
-    PSA_TRY(angle_work(c, p.n_a, 1, &w));
-    PSA_TRY(launch_pair_frac(c, c->slot[PSA_SLOT_POSITIONS].buf.as<float>(), p.d_idx, p.n_a, box_inverse, w.c, frame, 0, 1, p.T, p.N));
-    PSA_TRY(launch_angle_neighbours(c, w.c, w.count, w.list, sp, box, p.n_a, 1));
     std::vector<float> h((size_t)p.n_a * ANGLE_MAX_NEIGHBOURS * 4);
     PSA_HIP_CHECK(hipMemcpyAsync(count, w.count, (size_t)p.n_a * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     PSA_HIP_CHECK(hipMemcpyAsync(h.data(), w.list, h.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));

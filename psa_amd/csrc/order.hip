@@ -7,7 +7,8 @@
 // so the pass needs no spherical harmonic and no frame: the pair loop of angle_hist_kernel with a Legendre recurrence on
 // the cosine in place of the bisection.
 //
-// Arithmetic.  Per pair of legs, float32, every operation rounded once; r2 and cos are exactly angle.hip's:
+// Arithmetic.  Per pair of legs, float32, every operation rounded once but the square root (v_sqrt_f32: within one ulp);
+// r2 and cos are angle.hip's by construction: both kernels call shell.h's shell_r2 and shell_cos:
 //     r2 = fma(d_z, d_z, fma(d_y, d_y, d_x d_x));  dot = fma(d_z(b), d_z(c), fma(d_y(b), d_y(c), d_x(b) d_x(c)))
 //     cos = dot / sqrt(r2(b) r2(c)), clamped to [-1, 1]; a cos that is not a number makes the centre undefined
 //     P_0 = 1;  P_1 = cos;  P_{k+1} = fma(A_k, cos P_k, -(B_k P_{k-1}))       k = 1 .. l_max - 1
@@ -20,13 +21,13 @@
 //
 // Tiling.  That of angle_hist_kernel: a workgroup of four wavefronts takes an item of the host's table (64 centres of one
 // species, a slab of origins); a wavefront takes a centre, its lanes load the list once (issued while the centre before
-// is processed) and lane j takes the pairs (j, j + m mod n), m = 1 .. n / 2, the partner's leg by cross-lane reads.  A
-// lane adds its t_l into one int64 accumulator per order asked for (a register per l = 1 .. 12, indexed statically; at
-// most eight are in use); a 64-bit wave reduction; the lanes 0 .. n_l - 1 clamp, bin and count one order each with a
-// 32-bit integer LDS add, and store X_l where the caller asks for it.  The histogram (n_l n_q <= 8192 words) and the three
-// counters of the centres left out go to partials with plain stores and through hist_reduce.hip.  No global atomics, no
-// float atomics.
-#include "psa_ctx.h"
+// is processed) and lane j takes the pairs (j, j + m mod n), m = 1 .. n / 2, the partner's leg by cross-lane reads: the
+// centre walk and the leg-pair step of shell.h, as in angle.hip.  A lane adds its t_l into one int64 accumulator per order
+// asked for (a register per l = 1 .. 12, indexed statically; at most eight are in use); a 64-bit wave reduction; the lanes
+// 0 .. n_l - 1 clamp, bin and count one order each with a 32-bit integer LDS add, and store X_l where the caller asks for
+// it.  The histogram (n_l n_q <= 8192 words) and the three counters of the centres left out go to partials with plain
+// stores and through hist_reduce.hip.  No global atomics, no float atomics.
+#include "shell.h"
 
 namespace psa {
 
@@ -46,37 +47,24 @@ order_hist_kernel(const int* __restrict__ count, const float4* __restrict__ list
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64), lane = threadIdx.x % 64;
     // the wavefront's centres in turn, the next one's count and list on their way while this one is processed
-    int     k = it.slab, ci = wave;
-    bool    more = k < n_ob && ci < it.a_n;
-    int64_t row = (int64_t)k * n_a + it.a_lo + ci;
-    int     n_next = more ? count[row] : 0;
-    float4  e_next = more ? list[row * ANGLE_MAX_NEIGHBOURS + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+    SHELL_WALK_FIRST(it, wave, n_a, n_ob);
+    int    n_next = more ? count[row] : 0;
+    float4 e_next = more ? list[row * ANGLE_MAX_NEIGHBOURS + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
     while (more) {
         const int     n = __builtin_amdgcn_readfirstlane(n_next);
         const float4  e = e_next;
         const int64_t cur = row;
-        ci += ANGLE_CENTRES / 64;
-        if (ci >= it.a_n) ci = wave, k += it.n_os;
-        more = k < n_ob && ci < it.a_n;
-        if (more) {
-            row = (int64_t)k * n_a + it.a_lo + ci;
-            n_next = count[row];
-            e_next = list[row * ANGLE_MAX_NEIGHBOURS + lane];
-        }
+        SHELL_WALK_NEXT(it, wave, n_a, n_ob, (n_next = count[row], e_next = list[row * ANGLE_MAX_NEIGHBOURS + lane]))
         int       out = n > ANGLE_MAX_NEIGHBOURS ? 0 : n == 0 ? 1 : -1;    // truncated, isolated: all or nothing
         long long acc[ORDER_MAX_L] = {};
         if (out < 0) {
-            const float r2 = __fmaf_rn(e.z, e.z, __fmaf_rn(e.y, e.y, __fmul_rn(e.x, e.x)));
+            const float r2 = shell_r2(e);
             bool        bad = false;
             for (int m = 1; 2 * m <= n; ++m) {
-                int src = lane + m;
-                src = src >= n ? src - n : src;
-                src = lane < n ? src : lane;
-                const float ox = __shfl(e.x, src), oy = __shfl(e.y, src), oz = __shfl(e.z, src), o2 = __shfl(r2, src);
-                // the lanes without a pair in this round (n even, m = n / 2: each pair once) go along and add nothing
-                const bool  mine = lane < (2 * m == n ? m : n);
-                const float dot = __fmaf_rn(e.z, oz, __fmaf_rn(e.y, oy, __fmul_rn(e.x, ox)));
-                float       cs = __fdiv_rn(dot, __fsqrt_rn(__fmul_rn(r2, o2)));
+                const float4 o = shell_partner_leg(e, r2, shell_partner(lane, m, n));
+                // the lanes without a pair in this round go along and add nothing
+                const bool   mine = shell_has_pair(lane, m, n);
+                float        cs = shell_cos(e, r2, o);
                 bad = bad || (mine && cs != cs);                           // a coincident neighbour: the sums are dropped below
                 cs = fminf(1.f, fmaxf(-1.f, cs));
                 float pm = 1.f, p = cs;                                    // P_{k-1}, P_k
@@ -100,7 +88,7 @@ order_hist_kernel(const int* __restrict__ count, const float4* __restrict__ list
 #pragma unroll
         for (int l = 1; l <= ORDER_MAX_L; ++l) {
             if (!(ls.mask >> l & 1u)) continue;
-            long long s = acc[l - 1];
+            long long s = acc[l - 1];                                      // (shell.h's wave_sum here costs 54 instructions: own loop)
             for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
             if (lane == col) X = s;
             ++col;
@@ -128,13 +116,10 @@ order_hist_kernel(const int* __restrict__ count, const float4* __restrict__ list
 int launch_order_hist(psa_ctx* c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items, unsigned* d_part,
                       long long* d_x, const OrderLs& ls, int64_t n_a, int64_t n_ob, int32_t n_q) {
     if (n_items == 0) return PSA_OK;
-    int n_l = 0, l_max = 0;
-    for (int l = 0; l < 32; ++l)
-        if (ls.mask >> l & 1u) ++n_l, l_max = l;
-    PSA_REQUIRE(n_items < (1ll << 31) && n_a < (1ll << ANGLE_SPECIES_SHIFT) && n_ob >= 1 && n_ob <= 65535 && n_q >= 1 &&
-                    n_q <= ORDER_MAX_BINS && n_l >= 1 && n_l <= ORDER_MAX_LS && n_l == ls.n_l && l_max == ls.l_max && l_max <= ORDER_MAX_L &&
-                    !(ls.mask & 1u), "order pass outside its grid");
-    hipLaunchKernelGGL(order_hist_kernel, dim3((unsigned)n_items), dim3(ANGLE_CENTRES), (size_t)order_row_words(n_l, n_q) * sizeof(unsigned),
+    const LocalLs o = shell_orders(ls.mask);
+    PSA_REQUIRE(shell_grid_check(n_items, n_a, n_ob) && n_q >= 1 && n_q <= ORDER_MAX_BINS && o.n_l >= 1 && o.n_l <= ORDER_MAX_LS &&
+                    o.n_l == ls.n_l && o.l_max == ls.l_max && o.l_max <= ORDER_MAX_L && !(ls.mask & 1u), "order pass outside its grid");
+    hipLaunchKernelGGL(order_hist_kernel, dim3((unsigned)n_items), dim3(ANGLE_CENTRES), (size_t)order_row_words(o.n_l, n_q) * sizeof(unsigned),
                        c->stream, d_count, static_cast<const float4*>(d_list), static_cast<const AngleItem*>(d_items), d_part, d_x, ls,
                        (int)n_a, (int)n_ob, (int)n_q);
     PSA_HIP_CHECK(hipGetLastError());

@@ -27,7 +27,7 @@
 // sum is fixed by the list and the table, so a centre's result does not depend on the item, the block or the wavefront.
 // The lanes 0, 1 and 2 count q-bar, w and w-bar with 32-bit integer LDS adds; the row leaves by plain stores and through hist_reduce.hip.  No global
 // atomics, no float atomics.
-#include "psa_ctx.h"
+#include "shell.h"
 
 namespace psa {
 
@@ -37,22 +37,6 @@ constexpr double LOCAL_ONE = (double)(1ll << LOCAL_SHIFT), LOCAL_EPS = 1.0 / LOC
 constexpr int    LOCAL_VALUES = 2 * LOCAL_MAX_COLUMNS;
 constexpr int    LOCAL_TAG_MASK = (1 << ANGLE_SPECIES_SHIFT) - 1;
 
-__device__ inline long long wave_sum(long long s) {
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
-
-__device__ inline double wave_dsum(double s) {
-    for (int o = 32; o >= 1; o >>= 1) s = __dadd_rn(s, __shfl_xor(s, o));
-    return s;
-}
-
-// what one wavefront wrote to LDS is there for its other lanes, and no access moves across
-__device__ inline void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // Grid (items).  q[(origin of the block, centre)][column][re, im]
 __global__ void __launch_bounds__(ANGLE_CENTRES)
 qlm_sum_kernel(const int* __restrict__ count, const float4* __restrict__ list, const AngleItem* __restrict__ items,
@@ -60,23 +44,14 @@ qlm_sum_kernel(const int* __restrict__ count, const float4* __restrict__ list, c
     const AngleItem it = items[blockIdx.x];
     const int       wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64), lane = threadIdx.x % 64;
     const int       V = 2 * ls.columns;
-    int     k = it.slab, ci = wave;
-    bool    more = k < n_ob && ci < it.a_n;
-    int64_t row = (int64_t)k * n_a + it.a_lo + ci;
-    int     n_next = more ? count[row] : 0;
-    float4  e_next = more ? list[row * ANGLE_MAX_NEIGHBOURS + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+    SHELL_WALK_FIRST(it, wave, n_a, n_ob);
+    int    n_next = more ? count[row] : 0;
+    float4 e_next = more ? list[row * ANGLE_MAX_NEIGHBOURS + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
     while (more) {
         const int     n = __builtin_amdgcn_readfirstlane(n_next);
         const float4  e = e_next;
         const int64_t cur = row;
-        ci += ANGLE_CENTRES / 64;
-        if (ci >= it.a_n) ci = wave, k += it.n_os;
-        more = k < n_ob && ci < it.a_n;
-        if (more) {
-            row = (int64_t)k * n_a + it.a_lo + ci;
-            n_next = count[row];
-            e_next = list[row * ANGLE_MAX_NEIGHBOURS + lane];
-        }
+        SHELL_WALK_NEXT(it, wave, n_a, n_ob, (n_next = count[row], e_next = list[row * ANGLE_MAX_NEIGHBOURS + lane]))
         long long*   out = q + cur * V;
         const bool   mine = lane < n;
         const double x = (double)e.x, y = (double)e.y, z = (double)e.z;
@@ -168,25 +143,15 @@ local_order_kernel(const int* __restrict__ count, const float4* __restrict__ lis
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
     // per atom (or null): q-bar^2, w, w-bar, each (n_ob, n_a, n_l), one behind the other
     const int64_t each = (int64_t)n_ob * n_a * n_l;
-    int     k = it.slab, ci = wave;
-    bool    more = k < n_ob && ci < it.a_n;
-    int64_t row = (int64_t)k * n_a + it.a_lo + ci;
-    int     k_row = k;
-    int     n_next = more ? count[row] : 0;
-    float   tag_next = more ? list[row * ANGLE_MAX_NEIGHBOURS + lane].w : 0.f;
+    SHELL_WALK_FIRST(it, wave, n_a, n_ob);
+    int   k_row = k;                                                       // the origin of the row on its way
+    int   n_next = more ? count[row] : 0;
+    float tag_next = more ? list[row * ANGLE_MAX_NEIGHBOURS + lane].w : 0.f;
     while (more) {
         const int     n = __builtin_amdgcn_readfirstlane(n_next);
         const int     tag = __float_as_int(tag_next);
         const int64_t cur = row, origin = (int64_t)k_row * n_a;
-        ci += ANGLE_CENTRES / 64;
-        if (ci >= it.a_n) ci = wave, k += it.n_os;
-        more = k < n_ob && ci < it.a_n;
-        if (more) {
-            k_row = k;
-            row = (int64_t)k * n_a + it.a_lo + ci;
-            n_next = count[row];
-            tag_next = list[row * ANGLE_MAX_NEIGHBOURS + lane].w;
-        }
+        SHELL_WALK_NEXT(it, wave, n_a, n_ob, (k_row = k, n_next = count[row], tag_next = list[row * ANGLE_MAX_NEIGHBOURS + lane].w))
         const bool    mine = lane < n && n <= ANGLE_MAX_NEIGHBOURS;
         const int64_t nrow = origin + (mine ? tag & LOCAL_TAG_MASK : 0);  // the neighbour's row, below (n_ob, n_a) by the neighbour pass
         int           out = n > ANGLE_MAX_NEIGHBOURS ? 0 : n == 0 ? 1 : -1;   // truncated, isolated: all or nothing
@@ -286,11 +251,10 @@ local_order_kernel(const int* __restrict__ count, const float4* __restrict__ lis
 }
 
 int local_ls_check(const LocalLs& ls) {
-    int n_l = 0, l_max = 0, columns = 0;
-    for (int l = 0; l < 32; ++l)
-        if (ls.mask >> l & 1u) ++n_l, l_max = l, columns += l + 1;
-    PSA_REQUIRE(n_l >= 1 && n_l <= LOCAL_MAX_LS && n_l == ls.n_l && l_max == ls.l_max && l_max <= ORDER_MAX_L && columns == ls.columns &&
-                    columns <= LOCAL_MAX_COLUMNS && !(ls.mask & 0xaaaaaaabu), "local order pass outside its orders");
+    const LocalLs o = shell_orders(ls.mask);
+    PSA_REQUIRE(o.n_l >= 1 && o.n_l <= LOCAL_MAX_LS && o.n_l == ls.n_l && o.l_max == ls.l_max && o.l_max <= ORDER_MAX_L &&
+                    o.columns == ls.columns && o.columns <= LOCAL_MAX_COLUMNS && !(ls.mask & 0xaaaaaaabu),
+                "local order pass outside its orders");
     return PSA_OK;
 }
 
@@ -300,7 +264,7 @@ int launch_qlm_sum(psa_ctx* c, const int* d_count, const void* d_list, const voi
                    long long* d_q, const LocalLs& ls, int64_t n_a, int64_t n_ob) {
     if (n_items == 0) return PSA_OK;
     PSA_TRY(local_ls_check(ls));
-    PSA_REQUIRE(n_items < (1ll << 31) && n_a < (1ll << ANGLE_SPECIES_SHIFT) && n_ob >= 1 && n_ob <= 65535, "q_lm pass outside its grid");
+    PSA_REQUIRE(shell_grid_check(n_items, n_a, n_ob), "q_lm pass outside its grid");
     hipLaunchKernelGGL(qlm_sum_kernel, dim3((unsigned)n_items), dim3(ANGLE_CENTRES), 0, c->stream, d_count, static_cast<const float4*>(d_list),
                        static_cast<const AngleItem*>(d_items), d_norm, d_q, ls, (int)n_a, (int)n_ob);
     PSA_HIP_CHECK(hipGetLastError());
@@ -312,8 +276,7 @@ int launch_local_order(psa_ctx* c, const int* d_count, const void* d_list, const
                        int64_t n_a, int64_t n_ob) {
     if (n_items == 0) return PSA_OK;
     PSA_TRY(local_ls_check(ls));
-    PSA_REQUIRE(n_items < (1ll << 31) && n_a < (1ll << ANGLE_SPECIES_SHIFT) && n_ob >= 1 && n_ob <= 65535 && bins.n_q >= 1 &&
-                    bins.n_q <= LOCAL_MAX_BINS && bins.n_w >= 1 && bins.n_w <= LOCAL_MAX_BINS && (ls.mask >> ls.solid_l & 1u),
+    PSA_REQUIRE(shell_grid_check(n_items, n_a, n_ob) && bins.n_q >= 1 && bins.n_q <= LOCAL_MAX_BINS && bins.n_w >= 1 && bins.n_w <= LOCAL_MAX_BINS && (ls.mask >> ls.solid_l & 1u),
                 "local order pass outside its grid");
     hipLaunchKernelGGL(local_order_kernel, dim3((unsigned)n_items), dim3(ANGLE_CENTRES),
                        (size_t)local_row_words(ls.n_l, bins.n_q, bins.n_w) * sizeof(unsigned), c->stream, d_count,

@@ -99,6 +99,38 @@ def diamond(n_frames):
     return np.ascontiguousarray(np.broadcast_to(pos, (n_frames, 512, 3))), [np.arange(256), np.arange(256, 512)]
 
 
+def walk_case():
+    """(positions (5, 70, 3) float32, box, the species of 67 and 3 atoms, r_cut): five frames that reach every branch of the
+    centre walk the passes over the neighbour lists share -- items of 64, 3 and 3 centres (the last wavefront of a short item
+    has no centre at all); centres with 0, 1, 2 (one round, counted once), an odd number, exactly 64 and 65 neighbours (atom 0
+    in its sphere, one atom of which leaves in the frames 1, 2 and 4); a coincident pair (67, 68), with a third atom in reach
+    (a leg of length 0 among two) and without (one leg).  `walk_counts` names the counts the frames hold"""
+    H = CUBIC.astype(np.float64)
+    centre = np.array([0.3, 0.3, 0.3]) @ H
+    ring = sphere(65, 3.0)[0, 1:].astype(np.float64) - sphere(65, 3.0)[0, 0].astype(np.float64)
+    rng = np.random.default_rng(21)
+    away = [np.array(f) @ H for f in ([0.8, 0.2, 0.2], [0.2, 0.8, 0.2], [0.8, 0.8, 0.2], [0.8, 0.8, 0.8])]   # 10 apart and more
+    frames = []
+    for f in range(5):
+        shell = centre[None] + ring + (0.0 if f == 0 else 0.02 * rng.standard_normal(ring.shape))
+        if f in (1, 2, 4):
+            shell[64] = away[0]                                               # 64 neighbours are left
+        pair = away[2] + (0.0 if f == 0 else 0.1 * f)
+        third = away[3] if f in (1, 2) else pair + np.array([1.0, 0.5, -0.25])
+        second = pair + np.array([0.0, 0.75, 0.0]) if f == 3 else pair    # frame 3: no two atoms at one place
+        frames.append(np.concatenate([centre[None], shell, away[1][None], pair[None], second[None], third[None]]))
+    return np.asarray(frames, np.float32), CUBIC, [np.arange(67), np.arange(67, 70)], 3.5
+
+
+def walk_counts(n):
+    """does `n` (5, 70), the true neighbour counts of `walk_case`, hold what its docstring names?"""
+    n = np.asarray(n)
+    odd = (n[:, 1:66] % 2 == 1) & (n[:, 1:66] > 2)
+    return (n[[0, 3], 0].tolist() == [65, 65] and n[[1, 2, 4], 0].tolist() == [64, 64, 64] and np.all(n[:, 66] == 0) and odd.any()
+            and np.all(n[[1, 2, 4], 65] == 0) and np.all(n[[1, 2], 67:69] == 1) and np.all(n[[1, 2], 69] == 0)
+            and np.all(n[[0, 3, 4], 67:70] == 2))
+
+
 # ---- the allowance ------------------------------------------------------------------------------------------------------
 def reference(positions, box, groups, r_cut, step, n_theta):
     """one pass of the brute force: dict of the reference counts `angles` (S, P, n_theta + 1), `coord` (S, S, 65),

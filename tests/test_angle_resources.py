@@ -21,6 +21,15 @@ def test_makefile_lists_the_sources():
     assert all((SRC / f).is_file() for f in srcs.split(":=")[1].split())
 
 
+def test_makefile_object_rule_names_every_header():
+    """an object is rebuilt when any header beside the sources changes: a header the rule leaves out gives stale objects"""
+    mk = (SRC / "Makefile").read_text()
+    rule = next(ln for ln in mk.splitlines() if ln.startswith("$(BUILD)/%.o:"))
+    named = set(rule.split(":", 1)[1].split("|")[0].split())
+    headers = sorted(p.name for p in SRC.glob("*.h"))
+    assert headers and [h for h in headers if h not in named] == []
+
+
 def test_exported_constants():
     head = (SRC / "psa_ctx.h").read_text()
     for name in ("ANGLE_MAX_NEIGHBOURS", "ANGLE_MAX_BINS"):

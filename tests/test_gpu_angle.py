@@ -260,6 +260,26 @@ def test_permutations_budgets_and_repeats(engine):
     assert np.array_equal(one[0][0, 0], two[0].sum(axis=(0, 1))) and one[2][0] == two[2].sum() == 0
 
 
+def test_walk_case_is_the_twin_exactly(engine):
+    """`angle_cases.walk_case`, every branch of the centre walk: its five origins in blocks of 2, 2 and 1, and the five frames
+    280 times over in one block -- 3 items x 1400 origins are more than the 4096 workgroups a launch aims at, so a slab holds
+    two origins and a wavefront walks on from one into the next.  Every count is the twin's (angle_cases.model), exactly"""
+    from psa_amd import _hip
+    pos, box, groups, rc = Q.walk_case()
+    listing = [np.asarray(g, np.int32) for g in groups]
+    want = Q.model(pos, box, groups, rc, 1, 1024)
+    assert want[2].tolist() == [2, 0] and want[0][..., 1024].sum() == 4 and want[1][0, 0, 64] == 3
+    _resident(engine, pos)
+    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, PER_ORIGIN * 70 * 2 + 5)
+    got = engine.angle_histogram(box, rc, 1024, listing)
+    assert all(np.array_equal(g.astype(np.int64), w) for g, w in zip(got, want))
+    reset(engine)
+    reps = 280
+    _resident(engine, np.tile(pos, (reps, 1, 1)))
+    got = engine.angle_histogram(box, rc, 1024, listing)
+    assert all(np.array_equal(g.astype(np.int64), reps * w) for g, w in zip(got, want))
+
+
 def test_species_pairs_in_chunks(engine):
     """eight species at 1024 bins: 36 species pairs, 11 of which fit a workgroup's histograms, so the angle pass runs four
     chunks of pairs; the sum over all is the one-species histogram"""

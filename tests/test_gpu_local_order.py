@@ -272,6 +272,35 @@ def test_budgets_blocks_and_repeats(engine):
         _call(engine, box, rc, ls, 200, 100, listing, solid_l=6, per_atom=False)
 
 
+def test_walk_case_is_the_twin_exactly(engine):
+    """`angle_cases.walk_case`, every branch of the centre walk of both passes: its five origins in blocks of 2, 2 and 1, and
+    the five frames 200 times over in one block -- 3 items x 1000 origins are more workgroups than the 2696 that rows of
+    6221 words leave the partials, so a slab holds two origins and a wavefront walks on from one into the next.  Q, q-bar^2,
+    w, w-bar, the connections and n are the twin's (qlm_cases.model), exactly; the histograms are the bin rules of them"""
+    from psa_amd import _hip
+    pos, box, groups, rc = Q.walk_case()
+    listing = [np.asarray(g, np.int32) for g in groups]
+    ls, n_a = (4, 6), 70
+    want = C.model(pos, box, groups, rc, 1, ls)
+    assert Q.walk_counts(want["n"]) and (want["xi"] >= 0).any()
+
+    rows = C.rows_of(want, [67, 3], 2, 1024, 1024, 0.2)                    # the bin rules of the twin's values, once
+
+    def same(got, reps):
+        return (all(np.array_equal(got[k], np.tile(want[k], (reps, 1, 1)), equal_nan=True) for k in ("qbar2", "w", "wbar"))
+                and all(np.array_equal(got[k], np.tile(want[k], (reps, 1))) for k in ("xi", "n"))
+                and np.array_equal(C.fold_left_out(got["hist"], 2, 1024, 1024), reps * rows))
+
+    _resident(engine, pos)
+    for f in range(5):
+        assert np.array_equal(engine.debug_qlm(box, rc, f, ls, listing), want["q"][f]), f
+    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, (PER_ORIGIN + 16 * 12 + 24 * 2 + 8) * n_a * 2 + 5)
+    assert same(_call(engine, box, rc, ls, 1024, 1024, listing), 1)
+    reset(engine)
+    _resident(engine, np.tile(pos, (200, 1, 1)))
+    assert same(_call(engine, box, rc, ls, 1024, 1024, listing), 200)
+
+
 def test_permutation_of_the_atoms(engine):
     """Q is the same bits after undoing the permutation, and so are n, xi and w; the gather of q-bar runs in another order:
     qbar2 moves by at most (n + 2) roundings of terms below 1, 2 (n + 2) 2^-53 (1 + qbar2), and w-bar = W / S^(3/2) by

@@ -231,6 +231,32 @@ def test_budgets_blocks_permutations_and_repeats(engine):
     assert whole[0].shape == (2, 8, 200) and T == 40
 
 
+def test_walk_case_is_the_twin_exactly(engine):
+    """`angle_cases.walk_case`, every branch of the centre walk: its five origins in blocks of 2, 2 and 1, and the five frames
+    150 times over in one block -- 3 items x 750 origins are more workgroups than the 2047 that rows of 8 x 1024 + 3 words
+    leave the partials, so a slab holds two origins and a wavefront walks on from one into the next.  The histogram, the
+    centres left out and n are the twin's (order_cases.model), exactly; X is held to the float64 reference and the bin rule
+    as everywhere else, and is the same bits in every blocking.
+
+    X is not compared with the twin bit for bit: the twin rounds the square root under the cosine once, the kernel's comes
+    from v_sqrt_f32 (within one ulp), and on this input 2577 of the 2800 X differ from the twin's, the first twenty by 10 to
+    268 units of 2^-24 on X near 10^9"""
+    from psa_amd import _hip
+    pos, box, groups, rc = Q.walk_case()
+    listing = [np.asarray(g, np.int32) for g in groups]
+    want = C.model(pos, box, groups, rc, 1, EIGHT, 1024)
+    assert Q.walk_counts(want[5]) and want[1].tolist() == [2, 0] and want[2].sum() == 10 and want[3].tolist() == [0, 4]
+    engine.set_option(_hip.OPT_DYNAMIC_WORK_BYTES, (PER_ORIGIN + 8 * len(EIGHT)) * 70 * 2 + 5)
+    first = _held(engine, pos, box, groups, listing, rc, 1, EIGHT, 1024, "walk case, blocks of 2, 2 and 1")
+    assert all(np.array_equal(first[i].astype(np.int64), want[i]) for i in (0, 1, 2, 3, 5))
+    reset(engine)
+    reps = 150
+    _resident(engine, np.tile(pos, (reps, 1, 1)))
+    got = engine.bond_order(box, rc, EIGHT, 1024, listing, per_atom=True)
+    assert all(np.array_equal(g.astype(np.int64), reps * w) for g, w in zip(got[:4], want[:4]))
+    assert np.array_equal(got[4], np.tile(first[4], (reps, 1, 1))) and np.array_equal(got[5], np.tile(want[5], (reps, 1)))
+
+
 # ---- the calculator -------------------------------------------------------------------------------------------------------
 def _calculator(engine, pos, box, types=None, dt=0.002):
     from psa_amd import SEDCalculator, Trajectory
