@@ -865,7 +865,8 @@ int psa_angle_histogram(psa_ctx* ctx, const double* box /* 9 */, const double* b
  * budget; ls null, n_ls outside [1, 8], an order outside [1, 12] or not strictly ascending; n_q outside [1, 1024];
  * hist_bytes not exact; a null hist, truncated, isolated or undefined.
  * Not here: odd l in psa_local_order, the q_lm of other neighbour definitions, Voronoi or solid-angle-weighted neighbours,
- * cluster analysis of the solid-like bonds, cell lists (w_l, the neighbour-averaged q_l and the bonds: psa_local_order).
+ * cell lists (w_l, the neighbour-averaged q_l and the bonds: psa_local_order; the clusters of the solid-like atoms:
+ * psa_solid_clusters).
  * Only the positions slot is read.  Atom weights and segments set on the context are ignored, not refused; every result
  * and plan of the other entry points is left as it is.  Stage times: [0] the table's upload, [5] the fraction pass,
  * [6] the neighbour pass, [1] the order pass, [4] reduce, [7] device->host. */
@@ -951,6 +952,65 @@ int psa_local_order(psa_ctx* ctx, const double* box /* 9 */, const double* box_i
 int psa_debug_qlm(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
                   const int64_t* group_start /* S+1 */, int32_t n_groups, const double* r_cut /* S*S */, int64_t frame,
                   const int32_t* ls /* n_ls */, int32_t n_ls, int64_t* q /* (n_a, sum (l + 1), 2) */);
+
+/* Solid-like clusters: the connected components of the solid atoms over the neighbour lists, per time origin -- the size
+ * of the largest is the order parameter of a nucleation study, the size distribution gives its free energy.
+ * Inputs.  The positions slot, H, the species, r_cut and origin_step exactly as for psa_local_order, under the same checks
+ * and refusals; solid_l an even order in [2, 12], 0 < solid_threshold <= 1, min_connections in [0, 64], link 0 or 1,
+ * n_sizes in [1, 4096].
+ * Definition.  The neighbours are those of psa_local_order (all species together, at most 64).  xi(a) is its number of
+ * solid-like bonds for the order solid_l, by its rule and its arithmetic, bit for bit; -1 for a centre that is truncated,
+ * isolated, undefined or incomplete.  a is solid when xi(a) >= min_connections.  Two solid atoms a != b are joined when b
+ * is in a's list or a is in b's (link 0, "neighbours": ten Wolde, Ruiz-Montero and Frenkel); with link 1 ("solid bonds")
+ * the bond, in whichever list holds it, must be solid-like as well.  A cluster is a connected component of solid atoms; its
+ * label is the smallest column of its members (a column: the position in the concatenated atom list); an atom that is not
+ * solid has label -1 and size 0.  Per origin, on positions as stored; the lists are minimum-image, so a cluster runs
+ * through the periodic boundary.
+ * Outputs.  species_rows (S, 69) uint64: connections[65], truncated, isolated, undefined, incomplete -- those 69 words of
+ * psa_local_order's row, the same bits.  size_counts (n_sizes + 2) uint64 over all origins: slot s in [1, n_sizes] the
+ * clusters of exactly s atoms, slot n_sizes + 1 the larger ones, slot 0 stays 0; *large_atoms the atoms in the larger ones:
+ * sum_s s size_counts[s] + large_atoms = sum n_solid, sum_s size_counts[s] = sum n_clusters.  Per origin (n_o) int32:
+ * n_solid, n_clusters, largest (0: none) and largest_label (the smallest label among the clusters of that size, -1: none).
+ * Optionally per atom, in list order (any may be NULL): labels, size_atoms (the size of the atom's cluster), connections
+ * (xi), n (the true neighbour count), int32 (n_o, n_a), and bond_masks uint64 (n_o, n_a): bit b set when the bond to the
+ * b-th neighbour of the list is solid-like (0 where the centre is left out).
+ * As evaluated (cluster.hip): the fraction pass and the neighbour pass of psa_angle_histogram, the q_lm pass of
+ * psa_local_order for the one order, then a bonds pass (xi, masks, every solid atom its own parent), a hook pass (lock-free
+ * union, the larger root under the smaller: compare-and-swap on parent, path halving, every loop bounded by n_a), a flatten
+ * pass (label = root; one integer add per distinct label of a wavefront on size) and a stats pass.  Integer global atomics
+ * on parent and size only; a minimum and integer sums do not depend on the order, so two identical calls and any budget
+ * give the same bits, and a permutation of the atoms gives the same partition.  No float atomics.
+ * Budget (PSA_OPT_DYNAMIC_WORK_BYTES): per origin of a block 1040 n_a bytes as for psa_angle_histogram, plus 16 (solid_l +
+ * 1) n_a for the table, plus 20 n_a (xi 4, mask 8, parent / label 4, size 4); a budget below one origin is refused and the
+ * refusal names the bytes needed.
+ * PSA_EINVAL: everything psa_angle_histogram refuses about the context (a sharded one among it), the box, the species,
+ * r_cut, origin_step and the budget; solid_l odd or outside [2, 12]; solid_threshold outside (0, 1]; min_connections
+ * outside [0, 64]; link not 0 or 1; n_sizes outside [1, 4096]; a null required output.  PSA_EHIP "cluster pass did not
+ * converge": a bounded loop of the hook or flatten pass ran out (a defect, never a hang).
+ * Only the positions slot is read; every result and plan of the other entry points is left as it is.  Stage times: [0] the
+ * tables' upload, [5] the fraction pass, [6] the neighbour pass, [1] the q_lm, bonds, hook and flatten passes, of these [2]
+ * the hook and [3] the flatten pass, [4] the species reduce, the stats pass and its reduce, [7] device->host. */
+int psa_solid_clusters(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                       const int64_t* group_start /* S+1 */, int32_t n_groups, const double* r_cut /* S*S */, int64_t origin_step,
+                       int32_t solid_l, double solid_threshold, int32_t min_connections, int32_t link, int32_t n_sizes,
+                       uint64_t* species_rows /* (S, 69) */, uint64_t* size_counts /* n_sizes + 2 */, uint64_t* large_atoms /* 1 */,
+                       int32_t* n_solid /* n_o */, int32_t* n_clusters /* n_o */, int32_t* largest /* n_o */,
+                       int32_t* largest_label /* n_o */, int32_t* labels /* (n_o, n_a) or NULL */, int32_t* size_atoms /* the same */,
+                       int32_t* connections /* the same */, int32_t* n /* the same */, uint64_t* bond_masks /* (n_o, n_a) or NULL */);
+
+/* The graph passes of psa_solid_clusters alone (hook, flatten, stats) on a graph of the caller's, all n_o <= 65535 origins
+ * in one block: count (n_o, n_a) int32 in [0, 64], list (n_o, n_a, 64) int32 the neighbours' columns (only the first count
+ * are read), solid (n_o, n_a) uint8, bond_masks (n_o, n_a) uint64 or NULL (all ones), link, n_sizes as above.  The list
+ * entries are built with the tags the neighbour pass would have written.  Lists that are not symmetric are legal: an edge
+ * that only one end lists joins.  Outputs as for psa_solid_clusters without the species rows; labels and size_atoms may be
+ * NULL.  PSA_EINVAL: a column outside [0, n_a), a count outside [0, 64], a self-loop, link, n_sizes, n_o or n_a out of
+ * range, a graph beyond the work budget, a sharded context, a null required argument. */
+int psa_debug_cluster_labels(psa_ctx* ctx, int64_t n_o, int64_t n_a, const int32_t* count /* (n_o, n_a) */,
+                             const int32_t* list /* (n_o, n_a, 64) */, const uint8_t* solid /* (n_o, n_a) */,
+                             const uint64_t* bond_masks /* (n_o, n_a) or NULL */, int32_t link, int32_t n_sizes,
+                             uint64_t* size_counts /* n_sizes + 2 */, uint64_t* large_atoms /* 1 */, int32_t* n_solid /* n_o */,
+                             int32_t* n_clusters /* n_o */, int32_t* largest /* n_o */, int32_t* largest_label /* n_o */,
+                             int32_t* labels /* (n_o, n_a) or NULL */, int32_t* size_atoms /* the same */);
 
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting

@@ -90,6 +90,10 @@ ORDER_SHIFT = 24        # X_l counts units of 2^-24: q_l^2 = X_l / (n^2 2^24)
 LOCAL_MAX_LS = 4        # most orders of a call, even ones in [2, ORDER_MAX_L]
 LOCAL_MAX_BINS = 1024   # most bins of a q-bar histogram and of a w histogram
 LOCAL_SHIFT = 40        # Q_lm counts units of 2^-40
+# the caps of the cluster kernels (psa_amd/csrc/cluster.hip)
+CLUSTER_MAX_SIZES = 4096    # most exact slots of the cluster-size histogram
+CLUSTER_ROW_WORDS = ANGLE_MAX_NEIGHBOURS + 1 + 4   # a species' row: connections[65], truncated, isolated, undefined, incomplete
+CLUSTER_LINKS = ("neighbours", "solid_bonds")      # link 0, 1
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -195,6 +199,11 @@ SIGNATURES = {
                                   _f64p, C.c_int64, _u64p, C.c_size_t, _f64p, _f64p, _f64p, _i32p, _i32p]),
     "psa_debug_qlm": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p, C.c_int64,
                                 _i32p, C.c_int32, _i64p]),
+    "psa_solid_clusters": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p, C.c_int64,
+                                     C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, _u64p, _u64p, _u64p,
+                                     _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _u64p]),
+    "psa_debug_cluster_labels": (C.c_int, [_ctx, C.c_int64, C.c_int64, _i32p, _i32p, C.POINTER(C.c_uint8), _u64p, C.c_int32,
+                                           C.c_int32, _u64p, _u64p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
     "psa_lowrank_plan": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, _i32p, _f64p,
                                    _f64p, _f32p, _f32p, _f32p]),
@@ -1251,6 +1260,61 @@ class Engine:
                                          float(solid_threshold), held_3j.ctypes.data_as(_f64p), table.size, hist.ctypes.data_as(_u64p),
                                          hist.nbytes, f64(vals[0]), f64(vals[1]), f64(vals[2]), i32(xi), i32(n)), "psa_local_order")
         return hist, vals[0], vals[1], vals[2], xi, n
+
+    def solid_clusters(self, box, r_cut, solid_l: int = 6, solid_threshold: float = 0.7, min_connections: int = 7, link: int = 0,
+                       n_sizes: int = 256, groups=None, origin_step: int = 1, per_atom: bool = False, box_inverse=None) -> dict:
+        """The clusters of the solid atoms per time origin (psa_solid_clusters).  The neighbours, xi and the left-out rules
+        are those of `local_order` with ls = (solid_l,), bit for bit; an atom is solid when xi >= `min_connections`; two
+        solid atoms are joined when one lists the other (`link` 0) and, with `link` 1, that bond is solid-like; a cluster's
+        label is the smallest column of its members, -1 and size 0 for an atom that is not solid.  Returns a dict:
+        species_rows (S, 69) uint64 (connections[65], truncated, isolated, undefined, incomplete), size_counts (n_sizes + 2)
+        uint64 (slot s: the clusters of exactly s atoms over all origins, the last the larger ones, slot 0 stays 0),
+        large_atoms int, n_solid, n_clusters, largest, largest_label (n_o,) int32; with `per_atom` labels, size_atoms,
+        connections, n (n_o, n_a) int32 and bond_masks (n_o, n_a) uint64 (bit b: the bond to the b-th neighbour of the list
+        is solid-like), else None.  `box`, `groups`, `origin_step` as for `pair_histogram`.  Only positions are read."""
+        a = self._shell_args(box, box_inverse, groups, r_cut, origin_step)
+        rows = np.empty((a.G, CLUSTER_ROW_WORDS), np.uint64)
+        counts = np.empty(min(max(int(n_sizes), 1), CLUSTER_MAX_SIZES) + 2, np.uint64)
+        large = np.zeros(1, np.uint64)
+        per_origin = [np.empty(max(a.n_o, 1), np.int32) for _ in range(4)]
+        atoms = [pinned_empty((a.n_o, a.n_a), np.int32) if per_atom else None for _ in range(4)]    # (every cell is written by the call)
+        masks = pinned_empty((a.n_o, a.n_a), np.uint64) if per_atom else None
+        i32 = lambda x: None if x is None else x.ctypes.data_as(_i32p)                                 # noqa: E731
+        _check(self._lib.psa_solid_clusters(*a.head, int(origin_step), int(solid_l), float(solid_threshold), int(min_connections),
+                                            int(link), int(n_sizes), rows.ctypes.data_as(_u64p), counts.ctypes.data_as(_u64p),
+                                            large.ctypes.data_as(_u64p), *(i32(x) for x in per_origin), *(i32(x) for x in atoms),
+                                            None if masks is None else masks.ctypes.data_as(_u64p)), "psa_solid_clusters")
+        return dict(species_rows=rows, size_counts=counts, large_atoms=int(large[0]), n_solid=per_origin[0][:a.n_o],
+                    n_clusters=per_origin[1][:a.n_o], largest=per_origin[2][:a.n_o], largest_label=per_origin[3][:a.n_o], labels=atoms[0],
+                    size_atoms=atoms[1], connections=atoms[2], n=atoms[3], bond_masks=masks)
+
+    def debug_cluster_labels(self, count, lists, solid, bond_masks=None, link: int = 0, n_sizes: int = 256) -> dict:
+        """The graph passes of `solid_clusters` alone on a graph of the caller's (psa_debug_cluster_labels): `count` (n_o, n_a)
+        in [0, 64], `lists` (n_o, n_a, 64) the neighbours' columns (-1 padding; only the first `count` are read), `solid`
+        (n_o, n_a) bool, `bond_masks` (n_o, n_a) uint64 or None (all ones).  Lists that are not symmetric are legal: an edge
+        that one end lists joins.  Returns the dict of `solid_clusters` without species_rows, connections, n, bond_masks."""
+        cnt = np.ascontiguousarray(count, np.int32)
+        if cnt.ndim != 2:
+            raise ValueError(f"count must be (n_o, n_a), got {cnt.shape}")
+        n_o, n_a = cnt.shape
+        lst = np.ascontiguousarray(lists, np.int32)
+        sol = np.ascontiguousarray(np.asarray(solid) != 0, np.uint8)
+        if lst.shape != (n_o, n_a, ANGLE_MAX_NEIGHBOURS) or sol.shape != (n_o, n_a):
+            raise ValueError(f"lists {lst.shape} and solid {sol.shape} do not fit count {cnt.shape} with {ANGLE_MAX_NEIGHBOURS} list positions")
+        msk = None if bond_masks is None else np.ascontiguousarray(bond_masks, np.uint64)
+        if msk is not None and msk.shape != (n_o, n_a):
+            raise ValueError(f"bond_masks {msk.shape} does not fit count {cnt.shape}")
+        counts = np.empty(min(max(int(n_sizes), 1), CLUSTER_MAX_SIZES) + 2, np.uint64)
+        large = np.zeros(1, np.uint64)
+        per_origin = [np.empty(max(n_o, 1), np.int32) for _ in range(4)]
+        labels, sizes = (np.empty((n_o, n_a), np.int32) for _ in range(2))
+        _check(self._lib.psa_debug_cluster_labels(self._h, n_o, n_a, cnt.ctypes.data_as(_i32p), lst.ctypes.data_as(_i32p),
+                                                  sol.ctypes.data_as(C.POINTER(C.c_uint8)), None if msk is None else msk.ctypes.data_as(_u64p),
+                                                  int(link), int(n_sizes), counts.ctypes.data_as(_u64p), large.ctypes.data_as(_u64p),
+                                                  *(x.ctypes.data_as(_i32p) for x in per_origin), labels.ctypes.data_as(_i32p),
+                                                  sizes.ctypes.data_as(_i32p)), "psa_debug_cluster_labels")
+        return dict(size_counts=counts, large_atoms=int(large[0]), n_solid=per_origin[0][:n_o], n_clusters=per_origin[1][:n_o],
+                    largest=per_origin[2][:n_o], largest_label=per_origin[3][:n_o], labels=labels, size_atoms=sizes)
 
     def debug_qlm(self, box, r_cut, frame: int, ls, groups=None, box_inverse=None) -> np.ndarray:
         """The first pass of `local_order` alone at one frame (psa_debug_qlm): Q (n_a, sum (l + 1), 2) int64, the vectors

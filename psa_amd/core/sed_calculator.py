@@ -37,9 +37,10 @@ from ..covariance import ModeVectors, mode_vectors, spectral_weights
 from ..displacements import (MeanSquareDisplacement, VanHoveSelf, alpha2, check_count, check_lag_frames, check_origin_step,
                              origin_counts, radial_bins)
 from ..dynamic import DynamicSpectra
-from .. import angles, local_order, order
+from .. import angles, clusters, local_order, order
 from ..angles import BondAngleDistribution
 from ..order import BondOrder
+from ..clusters import SolidClusters
 from ..local_order import LocalOrder
 from ..pairs import RadialDistribution, VanHoveDistinct, max_pair_radius
 from .. import lattice
@@ -1054,6 +1055,47 @@ class SEDCalculator:
         out = self._displacement_run(lambda eng, box: eng.local_order(box, rc, orders, n_q, n_w, table, groups, step, reach, int(solid_l),
                                                                       thr, bool(per_atom)))
         res = local_order.result(*out, orders, n_q, n_w, reach, int(solid_l), thr, (self.traj.n_frames - 1) // step + 1, groups)
+        self._refuse_truncated(res.truncated)
+        return res
+
+    # ------------------------------------------------------------------ solid-like clusters (the largest crystal nucleus)
+    def calculate_solid_clusters(self, r_cut, solid_l: int = 6, solid_threshold: float = 0.7, min_connections: int = 7,
+                                 link: str = "neighbours", n_sizes: int = 256,
+                                 basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                 basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                 origin_step: int = 1, per_atom: bool = False) -> SolidClusters:
+        """The clusters of the solid-like atoms at every time origin (not in the reference; definition in
+        psa_amd/clusters.py), computed on the GPU from the positions resident in HBM.  The neighbours, `r_cut`, the species
+        and `origin_step` are those of `calculate_local_order`, and so is the number of solid-like bonds of an atom for the
+        even order `solid_l` in [2, 12] and `solid_threshold` in (0, 1], bit for bit.  An atom with at least
+        `min_connections` (0 .. 64) such bonds is solid; two solid atoms are joined when one lists the other
+        (`link="neighbours"`) and, with `link="solid_bonds"`, that bond is solid-like too; a cluster is a connected component,
+        its label the smallest column of its members.  `largest` (n_o,) is n_max(t); `size_counts` counts the clusters by size
+        over all origins in `n_sizes` <= 4096 exact slots and one for the larger ones.  `per_atom=True` adds `labels`,
+        `size_atoms`, `connections_atoms`, `neighbours`, `bond_masks` and `atoms`, and with them `largest_atoms(origin)`.
+
+        Where a centre has more than 64 neighbours the call raises ValueError naming the species: choose a smaller `r_cut`
+        (`Engine.solid_clusters` returns the numbers instead).  A sharded calculator refuses (NotImplementedError).
+        Returns a `psa_amd.SolidClusters`."""
+        n_sizes = check_count("n_sizes", n_sizes, _hip.CLUSTER_MAX_SIZES)
+        if (isinstance(solid_l, (bool, np.bool_)) or not isinstance(solid_l, (int, np.integer)) or int(solid_l) % 2
+                or not 2 <= int(solid_l) <= _hip.ORDER_MAX_L):
+            raise ValueError(f"solid_l must be an even integer in [2, {_hip.ORDER_MAX_L}], got {solid_l!r}")
+        thr = float(solid_threshold)
+        if not 0.0 < thr <= 1.0:
+            raise ValueError(f"solid_threshold must lie in (0, 1], got {solid_threshold!r}")
+        if (isinstance(min_connections, (bool, np.bool_)) or not isinstance(min_connections, (int, np.integer))
+                or not 0 <= int(min_connections) <= _hip.ANGLE_MAX_NEIGHBOURS):
+            raise ValueError(f"min_connections must be an integer in [0, {_hip.ANGLE_MAX_NEIGHBOURS}], got {min_connections!r}")
+        code = clusters.link_code(link)
+        self._check_per_atom(per_atom)
+        rc, step, groups = self._shell_inputs(r_cut, basis_atom_indices, basis_atom_types, origin_step, "the solid-like clusters")
+        pars = (int(solid_l), thr, int(min_connections), link, n_sizes)
+        if groups is None:
+            return clusters.result(clusters.empty(1, n_sizes), *pars, 0, [np.zeros(0, int)])
+        out = self._displacement_run(lambda eng, box: eng.solid_clusters(box, rc, int(solid_l), thr, int(min_connections), code, n_sizes,
+                                                                         groups, step, bool(per_atom)))
+        res = clusters.result(out, *pars, (self.traj.n_frames - 1) // step + 1, groups)
         self._refuse_truncated(res.truncated)
         return res
 

@@ -375,7 +375,8 @@ struct psa_ctx {
     // uses the same buffer, with its per-atom X (n_a, n_l) int64 behind the counts where the caller asks for them.
     psa::DevBuf  d_angle_work, d_angle_edges;
     // psa_local_order, psa_debug_qlm: the same buffer again, the table of the Q_lm (n_a, columns, 2) int64 and the per-atom
-    // rows behind the counts; outside it the normalisations N_lm and the 3j symbols, float64, uploaded by every call
+    // rows behind the counts; outside it the normalisations N_lm and the 3j symbols, float64, uploaded by every call.
+    // psa_solid_clusters, psa_debug_cluster_labels: the same buffers, the masks, xi, parent and size behind the table
     psa::DevBuf  d_local_tab;
 
     psa::TimingState timing;
@@ -768,6 +769,34 @@ struct LocalBins {
 int launch_local_order(psa_ctx* c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items, const long long* d_q,
                        const double* d_w3j, unsigned* d_part, double* d_atoms, int* d_xi, const LocalLs& ls, const LocalBins& bins,
                        int64_t n_a, int64_t n_ob);
+// --- cluster.hip (psa_solid_clusters, psa_debug_cluster_labels: the connected components of the solid atoms over the same
+// lists; the definition and the passes are in its header)
+constexpr int CLUSTER_MAX_SIZES = 4096;    // most exact slots of the cluster-size histogram
+constexpr int CLUSTER_ROW_WORDS = ANGLE_MAX_NEIGHBOURS + 1 + 4;   // a species' row: connections[65], the four left-out kinds
+constexpr int CLUSTER_STATS_ORIGINS = 16;  // most origins of a workgroup of the stats pass
+// the words of a stats partial and of the accumulator behind the species rows: slots 0 .. n_sizes + 1, large_atoms
+inline int64_t cluster_stat_words(int n_sizes) { return (int64_t)n_sizes + 3; }
+// the workgroups of the stats pass over n_ob origins and the origins each takes (at most CLUSTER_STATS_ORIGINS)
+inline int64_t cluster_stat_each(int64_t n_ob) { return std::min<int64_t>(std::max<int64_t>((n_ob + 1023) / 1024, 1), CLUSTER_STATS_ORIGINS); }
+inline int64_t cluster_stat_groups(int64_t n_ob) { return (n_ob + cluster_stat_each(n_ob) - 1) / cluster_stat_each(n_ob); }
+// the four working arrays of the graph passes, each (n_ob, n_a): the ballot of solid bonds in list order, xi, parent (label
+// after the flatten pass) and size (size_atoms after the stats pass)
+struct ClusterWork {
+    unsigned long long* mask;
+    int *               xi, *parent, *size;
+};
+// after launch_qlm_sum with the single order ls.solid_l, over the same items: xi, mask, parent (own column where xi >=
+// min_connections, else -1) and size = 0 of every row; d_part (n_items, CLUSTER_ROW_WORDS) uint32
+int launch_cluster_bonds(psa_ctx* c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items, const long long* d_q,
+                         unsigned* d_part, const ClusterWork& w, const LocalLs& ls, double thr2, int min_connections, int64_t n_a,
+                         int64_t n_ob);
+// the union of the edges (link 1: those whose mask bit is set; both_ways: also the edges a centre lists towards a later
+// column, for lists that are not symmetric), then labels and sizes; d_err: set to 1 where a bounded loop ran out
+int launch_cluster_hook(psa_ctx* c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items, const ClusterWork& w,
+                        int link, bool both_ways, int* d_err, int64_t n_a, int64_t n_ob);
+int launch_cluster_flatten(psa_ctx* c, const ClusterWork& w, int* d_err, int64_t n_a, int64_t n_ob);
+// d_origin (n_ob, 4) int32: n_solid, n_clusters, largest, largest_label; d_part (cluster_stat_groups, cluster_stat_words) uint32
+int launch_cluster_stats(psa_ctx* c, const ClusterWork& w, int* d_origin, unsigned* d_part, int n_sizes, int64_t n_a, int64_t n_ob);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 

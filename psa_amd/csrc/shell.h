@@ -1,5 +1,5 @@
 // What the passes over the neighbour lists share (angle.hip: angle_hist_kernel; order.hip: order_hist_kernel; qlm.hip:
-// qlm_sum_kernel, local_order_kernel): the walk of a wavefront over the centres of its item, the round of leg pairs
+// qlm_sum_kernel, local_order_kernel; cluster.hip: cluster_bonds_kernel, cluster_hook_kernel): the walk of a wavefront over the centres of its item, the round of leg pairs
 // within a centre, the wave reductions and the launchers' shared guard.  The lists
 // are those the neighbour pass (angle.hip) leaves: per (origin, centre) the true neighbour count and up to 64 legs
 // {d_x, d_y, d_z, tag}.  A new pass over them uses the walk and the leg-pair step from here.
@@ -59,6 +59,34 @@ __device__ __forceinline__ float4 shell_partner_leg(const float4& e, float r2, i
 __device__ __forceinline__ float shell_cos(float4 e, float r2, float4 o) {
     const float dot = __fmaf_rn(e.z, o.z, __fmaf_rn(e.y, o.y, __fmul_rn(e.x, o.x)));
     return __fdiv_rn(dot, __fsqrt_rn(__fmul_rn(r2, o.w)));
+}
+
+// ---- the solid-like bond test (psa_local_order's definition).  v: a centre's vector of one order staged as float64, Q 2^-40,
+// (re, im) pairs for m = 0 .. l.  shell_norm2: sum_{m = -l .. l} |v_m|^2 = |v_0|^2 + 2 sum_{m > 0} |v_m|^2 in ascending m.
+// shell_solid_bond: o the neighbour's row of the table of that order (int64); D = Re sum_m Q_lm(a) conj Q_lm(b) and
+// B = sum_m |Q_lm(b)|^2 in ascending m, every operation rounded once, then D > 0 && D D > thr2 (A B), A = shell_norm2(v).
+// (cluster.hip uses them; qlm.hip keeps its own text of the same operations)
+constexpr double SHELL_Q_EPS = 1.0 / (double)(1ll << LOCAL_SHIFT);
+
+__device__ __forceinline__ double shell_norm2(const double* v, int l) {
+    double s = 0.0;
+    for (int m = 0; m <= l; ++m) {
+        const double t = __dadd_rn(__dmul_rn(v[2 * m], v[2 * m]), __dmul_rn(v[2 * m + 1], v[2 * m + 1]));
+        s = __dadd_rn(s, m ? __dmul_rn(2.0, t) : t);
+    }
+    return s;
+}
+
+__device__ __forceinline__ bool shell_solid_bond(const double* v, const long long* o, int l, double A, double thr2) {
+    double D = 0.0, B = 0.0;
+    for (int m = 0; m <= l; ++m) {
+        const double br = __dmul_rn((double)o[2 * m], SHELL_Q_EPS), bi = __dmul_rn((double)o[2 * m + 1], SHELL_Q_EPS);
+        const double d = __dadd_rn(__dmul_rn(v[2 * m], br), __dmul_rn(v[2 * m + 1], bi));
+        const double s = __dadd_rn(__dmul_rn(br, br), __dmul_rn(bi, bi));
+        D = __dadd_rn(D, m ? __dmul_rn(2.0, d) : d);
+        B = __dadd_rn(B, m ? __dmul_rn(2.0, s) : s);
+    }
+    return D > 0.0 && __dmul_rn(D, D) > __dmul_rn(thr2, __dmul_rn(A, B));
 }
 
 // ---- wave helpers

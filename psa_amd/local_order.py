@@ -31,8 +31,8 @@ none (`isolated`), a coincident one (`undefined`), or a neighbour that is trunca
     sum_i connections[alpha, i]    + the same four                                 = n_o N_alpha
     sum_i w_counts[alpha, j, i] + w_outside[alpha, j] + w_undefined[alpha, j] + the four = n_o N_alpha  (wbar alike)
 
-  * Left out: odd l, the q_lm of other neighbour definitions, Voronoi or solid-angle weights, the cluster analysis of the
-    solid-like bonds (`connections_atoms` and the neighbour lists are what it starts from), cell lists, sharding.
+  * Left out: odd l, the q_lm of other neighbour definitions, Voronoi or solid-angle weights, cell lists, sharding.  (The
+    clusters of the solid-like atoms: `psa_amd/clusters.py`.)
 
 This module is host code only: the 3j table, made in exact rational arithmetic, and the result type.
 `SEDCalculator.calculate_local_order` runs the kernels (psa_amd/csrc/angle.hip's neighbour pass, psa_amd/csrc/qlm.hip).
