@@ -89,18 +89,24 @@ def mode_tables(spec: SyntheticSpec, r0: np.ndarray):
     return amp, comp, ct, st, ca, sa
 
 
+def counter_noise(seed: int, i: np.ndarray) -> np.ndarray:
+    """The noise of the elements whose index in the whole (T, N, 3) array is `i` (uint64, any
+    shape), float32: what fill_synthetic_kernel writes there before it adds the planted modes."""
+    key = np.uint64((seed * _KEYMUL) & 0xFFFFFFFFFFFFFFFF)
+    h = _splitmix64(np.asarray(i, np.uint64) ^ key)
+    m16 = np.uint64(0xFFFF)
+    s = ((h & m16) + ((h >> np.uint64(16)) & m16) + ((h >> np.uint64(32)) & m16)
+         + (h >> np.uint64(48))).astype(np.int64) - 131070
+    return s.astype(np.float32) * _INV_SIGMA
+
+
 def velocities_block(spec: SyntheticSpec, tables, t0: int, nt: int) -> np.ndarray:
     """Frames [t0, t0+nt) of the synthetic velocity array, (nt, N, 3) float32 -- the NumPy
     twin of fill_synthetic_kernel."""
     amp, comp, ct, st, ca, sa = tables
     N = spec.n_atoms
-    key = np.uint64((spec.seed * _KEYMUL) & 0xFFFFFFFFFFFFFFFF)
     i = (np.arange(t0 * N * 3, (t0 + nt) * N * 3, dtype=np.uint64)).reshape(nt, N, 3)
-    h = _splitmix64(i ^ key)
-    m16 = np.uint64(0xFFFF)
-    s = ((h & m16) + ((h >> np.uint64(16)) & m16) + ((h >> np.uint64(32)) & m16)
-         + (h >> np.uint64(48))).astype(np.int64) - 131070
-    v = s.astype(np.float32) * _INV_SIGMA
+    v = counter_noise(spec.seed, i)
     for m in range(len(amp)):
         w = (ct[m, t0:t0 + nt, None] * ca[m][None, :]) + (st[m, t0:t0 + nt, None] * sa[m][None, :])
         v[:, :, comp[m]] = v[:, :, comp[m]] + amp[m] * w

@@ -9,7 +9,9 @@ the host), the FFT of the device's own q against numpy, Parseval, the planted pl
 groups (index lists: gather kernel on first use, compacted split planes afterwards).  C4 / C5
 run through the public API against the oracle at reduced T, and at FULL size through the same
 kind of properties (sampled frames, FFT, Parseval, k-subset / shard invariance, the k -> -k
-symmetry of a real trajectory, the planted modes' frequency, chiral phase)."""
+symmetry of a real trajectory, the planted modes' frequency, chiral phase).  C3 sits exactly at T N = 2^31, so t N + a
+peaks at 2^31 - 1 and no index wraps even there: the index-width cases (3 T N > 2^32, T N > 2^31) live in
+tests/test_gpu_bigslot.py."""
 import numpy as np
 import pytest
 
