@@ -1012,6 +1012,68 @@ int psa_debug_cluster_labels(psa_ctx* ctx, int64_t n_o, int64_t n_a, const int32
                              int32_t* n_clusters /* n_o */, int32_t* largest /* n_o */, int32_t* largest_label /* n_o */,
                              int32_t* labels /* (n_o, n_a) or NULL */, int32_t* size_atoms /* the same */);
 
+/* Bond persistence: how long a neighbour stays a neighbour.  The pairs listed at a time origin are tested again at later
+ * frames; the counts give the intermittent and the continuous bond correlation of every species pair and the cage
+ * correlation of every species, as integers.
+ * Inputs.  The positions slot as stored, H = box with its inverse, S <= 8 disjoint species (idx, group_start), r_cut (S, S)
+ * and origin_step exactly as for psa_angle_histogram, under the same checks and refusals.  r_break (S, S) double, symmetric
+ * and finite, every entry >= r_cut's and <= the served radius, 0 exactly where r_cut is 0: a bond forms below r_cut and
+ * counts as alive while it stays below r_break (hysteresis; r_break = r_cut: none).  lags: n_lags in [1, 1024] frame lags,
+ * strictly ascending, each in [0, T-1] and a multiple of sample_step >= 1.  continuous: 0 or 1.
+ * Origins and centres.  The origins of lag tau are O_tau = {o = 0, s, 2 s, ... : o + tau <= T-1}, s = origin_step, as for
+ * psa_pair_histogram; n_o(tau) = (T-1-tau) / s + 1 is their number.  The neighbours of centre a at origin o are bit for bit
+ * those of psa_angle_histogram (r_cut); n_beta(a, o) of them are of species beta.  A (centre, origin) with more than 64
+ * neighbours is left out whole -- never its first 64 -- and counted in truncated[j, alpha] for every lag j whose O_tau holds
+ * that origin.
+ * Alive.  A listed neighbour b of a at origin o is alive at frame o + f when x < 1, x being exactly the float32 chain
+ * stated at psa_angle_histogram evaluated on the centred fractions c_j of frame o + f, with float32(1 / r_break[alpha,beta])
+ * in place of the reciprocal of r_cut; every operation rounded once.  At f = 0 every listed neighbour is alive: the
+ * reciprocal of a larger radius is not larger, and the chain is otherwise the one that listed it.  The chain is odd in e bit
+ * for bit, so alive(a, b, o, f) = alive(b, a, o, f).
+ * Outputs, uint64.
+ *     bonds[j, alpha, beta]      sum over o in O_tau_j and the centres a in alpha that are not truncated of n_beta(a, o)
+ *     alive[j, alpha, beta]      those bonds alive at o + tau_j: the intermittent correlation is alive / bonds
+ *     unbroken[j, alpha, beta]   those bonds alive at every visited frame o + v, v in {sample_step, 2 sample_step, ...},
+ *                                v <= tau_j: the continuous correlation is unbroken / bonds; zeros when continuous = 0
+ *     lost[j, alpha, m]          m = 0 .. 64: the (a in alpha, o in O_tau_j), not truncated, with exactly m of their listed
+ *                                neighbours not alive at o + tau_j (the cage correlation: the share with m < c)
+ *     truncated[j, alpha]
+ * At lag 0 alive = unbroken = bonds = sum_n n coord[alpha, beta, n] of psa_angle_histogram, bit for bit;
+ * sum_m lost[j, alpha, m] + truncated[j, alpha] = n_o(tau_j) N_alpha;  sum_m m lost[j, alpha, m] = sum_beta (bonds -
+ * alive)[j, alpha, beta];  unbroken <= alive <= bonds (continuous = 1), exactly.
+ * Optionally per atom (NULL: not asked for): alive_masks and unbroken_masks, each (n_lags, n_o(0), n_a) uint64 in list
+ * order: bit i stands for the i-th neighbour in the order of psa_debug_neighbour_lists at the origin; 0 for a truncated
+ * centre and for an origin outside O_tau_j; unbroken_masks is zeros when continuous = 0.
+ * As evaluated (persist.hip): per block of origins the fraction pass and the neighbour pass of psa_angle_histogram; a tag
+ * pass that keeps of every list the 64 tag words and sets the centre's survivor mask to its n low bits; then per visited
+ * frame f -- with continuous = 1 every multiple of sample_step up to the last lag, else the listed lags alone -- the
+ * fraction pass of the frames o + f for the origins of the block with o + f <= T-1 and a step pass in which a wavefront
+ * takes a centre and lane i its i-th neighbour: it gathers the two atoms' fractions, runs the chain, the ballot is the alive
+ * mask, the survivor mask is ANDed with it.  At a listed lag the per-species popcounts and the centre's lost count go by
+ * 32-bit integer adds into counters in LDS -- the host keeps a workgroup's samples below 2^32 --, written to partials with
+ * plain stores and summed in 64-bit integers into that lag's rows.  No global atomics, no float atomics; two identical
+ * calls, any budget and any order of the atoms inside a species give the same bits.
+ * Budget (PSA_OPT_DYNAMIC_WORK_BYTES): per origin of a block 1040 n_a bytes as for psa_angle_histogram, plus 288 n_a (the
+ * tags 256, the lagged fractions 12, the survivor and the alive mask 8 each, 4 of padding); a budget below one origin is
+ * refused and the refusal names the bytes needed.
+ * PSA_EINVAL: everything psa_angle_histogram refuses about the context (a sharded one among it), the box, the species,
+ * r_cut, origin_step and the budget; r_break below r_cut, not symmetric, not finite, beyond the served radius, or 0 where
+ * r_cut is not (and the reverse); n_lags outside [1, 1024]; lags not strictly ascending, outside [0, T-1] or no multiple of
+ * sample_step; sample_step < 1; continuous not 0 or 1; pair_bytes, lost_bytes, truncated_bytes or (with a per-atom output)
+ * masks_bytes not exact; a null required argument.
+ * Only the positions slot is read.  Atom weights and segments set on the context are ignored, not refused; every result
+ * and plan of the other entry points is left as it is.  Stage times: [0] the tables' upload, [5] the origins' fraction
+ * pass, [6] the neighbour pass, [1] the tag pass and every visited frame's fraction pass, step pass and reduce,
+ * [7] device->host. */
+int psa_bond_persistence(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                         const int64_t* group_start /* S+1 */, int32_t n_groups, const double* r_cut /* S*S */,
+                         const double* r_break /* S*S */, int64_t origin_step, const int64_t* lags /* n_lags */, int32_t n_lags,
+                         int64_t sample_step, int32_t continuous, uint64_t* bonds /* (n_lags, S, S) */,
+                         uint64_t* alive /* the same */, uint64_t* unbroken /* the same */, size_t pair_bytes /* of each */,
+                         uint64_t* lost /* (n_lags, S, 65) */, size_t lost_bytes, uint64_t* truncated /* (n_lags, S) */,
+                         size_t truncated_bytes, uint64_t* alive_masks /* (n_lags, n_o(0), n_a) or NULL */,
+                         uint64_t* unbroken_masks /* the same */, size_t masks_bytes /* of each */);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is

@@ -94,6 +94,8 @@ LOCAL_SHIFT = 40        # Q_lm counts units of 2^-40
 CLUSTER_MAX_SIZES = 4096    # most exact slots of the cluster-size histogram
 CLUSTER_ROW_WORDS = ANGLE_MAX_NEIGHBOURS + 1 + 4   # a species' row: connections[65], truncated, isolated, undefined, incomplete
 CLUSTER_LINKS = ("neighbours", "solid_bonds")      # link 0, 1
+# the cap of the persistence kernels (psa_amd/csrc/persist.hip)
+PERSIST_MAX_LAGS = 1024     # most lags of a call
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -202,6 +204,9 @@ SIGNATURES = {
     "psa_solid_clusters": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p, C.c_int64,
                                      C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, _u64p, _u64p, _u64p,
                                      _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _u64p]),
+    "psa_bond_persistence": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p, _f64p, C.c_int64,
+                                       _i64p, C.c_int32, C.c_int64, C.c_int32, _u64p, _u64p, _u64p, C.c_size_t,
+                                       _u64p, C.c_size_t, _u64p, C.c_size_t, _u64p, _u64p, C.c_size_t]),
     "psa_debug_cluster_labels": (C.c_int, [_ctx, C.c_int64, C.c_int64, _i32p, _i32p, C.POINTER(C.c_uint8), _u64p, C.c_int32,
                                            C.c_int32, _u64p, _u64p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
@@ -1287,6 +1292,34 @@ class Engine:
         return dict(species_rows=rows, size_counts=counts, large_atoms=int(large[0]), n_solid=per_origin[0][:a.n_o],
                     n_clusters=per_origin[1][:a.n_o], largest=per_origin[2][:a.n_o], largest_label=per_origin[3][:a.n_o], labels=atoms[0],
                     size_atoms=atoms[1], connections=atoms[2], n=atoms[3], bond_masks=masks)
+
+    def bond_persistence(self, box, r_cut, lags, groups=None, step: int = 1, *, r_break=None, sample_step: int = 1,
+                         continuous: bool = True, per_atom: bool = False, box_inverse=None) -> dict:
+        """How long a neighbour stays a neighbour, as counts (psa_bond_persistence).  The pairs that `angle_histogram` lists
+        at the origins 0, `step`, ... (`r_cut` a scalar or symmetric (S, S), 0: no bond) are tested again `lags[j]` frames
+        later: a bond is alive while its distance stays below `r_break` (default: `r_cut`; >= `r_cut` entry by entry, 0
+        exactly where it is).  `lags` strictly ascending in [0, T - 1], multiples of `sample_step`.  Returns a dict: bonds,
+        alive, unbroken (n_lags, S, S) uint64 -- the bonds listed at the origins of lag j, those alive at o + lag, those
+        alive at every frame o + sample_step, o + 2 sample_step, ... up to o + lag (zeros unless `continuous`) --, lost
+        (n_lags, S, 65) uint64 the (centre, origin) by the number of listed neighbours that are not alive, truncated
+        (n_lags, S) uint64 the centres with more than 64 neighbours, left out whole; with `per_atom` alive_masks and
+        unbroken_masks (n_lags, n_o, n_a) uint64, bit i for the i-th neighbour of `debug_neighbour_lists`, else None.
+        `box`, `groups` as for `pair_histogram`.  Only positions are read, as stored."""
+        a = self._shell_args(box, box_inverse, groups, r_cut, step)
+        rb = a.alive[4] if r_break is None else self._cutoffs(r_break, a.G)
+        tau = np.ascontiguousarray(lags, np.int64).ravel()
+        held = tau if tau.size else np.zeros(1, np.int64)
+        pair = [np.empty((tau.size, a.G, a.G), np.uint64) for _ in range(3)]
+        lost = np.empty((tau.size, a.G, ANGLE_MAX_NEIGHBOURS + 1), np.uint64)
+        trunc = np.empty((tau.size, a.G), np.uint64)
+        masks = [pinned_empty((tau.size, a.n_o, a.n_a), np.uint64) if per_atom else None for _ in range(2)]   # (the call zeroes them)
+        u64 = lambda x: None if x is None else x.ctypes.data_as(_u64p)                                # noqa: E731
+        _check(self._lib.psa_bond_persistence(*a.head, rb.ctypes.data_as(_f64p), int(step), held.ctypes.data_as(_i64p), tau.size,
+                                              int(sample_step), 1 if continuous else 0, *(u64(x) for x in pair), pair[0].nbytes,
+                                              u64(lost), lost.nbytes, u64(trunc), trunc.nbytes, u64(masks[0]), u64(masks[1]),
+                                              masks[0].nbytes if per_atom else 0), "psa_bond_persistence")
+        return dict(bonds=pair[0], alive=pair[1], unbroken=pair[2], lost=lost, truncated=trunc, alive_masks=masks[0],
+                    unbroken_masks=masks[1])
 
     def debug_cluster_labels(self, count, lists, solid, bond_masks=None, link: int = 0, n_sizes: int = 256) -> dict:
         """The graph passes of `solid_clusters` alone on a graph of the caller's (psa_debug_cluster_labels): `count` (n_o, n_a)

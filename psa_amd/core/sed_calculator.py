@@ -37,10 +37,11 @@ from ..covariance import ModeVectors, mode_vectors, spectral_weights
 from ..displacements import (MeanSquareDisplacement, VanHoveSelf, alpha2, check_count, check_lag_frames, check_origin_step,
                              origin_counts, radial_bins)
 from ..dynamic import DynamicSpectra
-from .. import angles, clusters, local_order, order
+from .. import angles, clusters, local_order, order, persistence
 from ..angles import BondAngleDistribution
 from ..order import BondOrder
 from ..clusters import SolidClusters
+from ..persistence import BondPersistence
 from ..local_order import LocalOrder
 from ..pairs import RadialDistribution, VanHoveDistinct, max_pair_radius
 from .. import lattice
@@ -1097,6 +1098,51 @@ class SEDCalculator:
                                                                          groups, step, bool(per_atom)))
         res = clusters.result(out, *pars, (self.traj.n_frames - 1) // step + 1, groups)
         self._refuse_truncated(res.truncated)
+        return res
+
+    # ------------------------------------------------------------------ bond persistence (neighbour lifetimes, cages)
+    def calculate_bond_persistence(self, r_cut, lag_frames,
+                                   basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                   basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *, r_break=None,
+                                   origin_step: int = 1, sample_step: int = 1, continuous: bool = True,
+                                   per_atom: bool = False) -> BondPersistence:
+        """How long a neighbour stays a neighbour (not in the reference; definition in psa_amd/persistence.py), computed on
+        the GPU from the positions resident in HBM.  The neighbours, `r_cut`, the species and `origin_step` are those of
+        `calculate_bond_angles`, bit for bit.  The bonds listed at a time origin o are tested again at o + lag for every
+        lag of `lag_frames` (1 to 1024 strictly ascending frame lags in [0, T - 1], multiples of `sample_step`): a bond is
+        alive while its distance stays below `r_break` -- a scalar or a symmetric (S, S) matrix, at least `r_cut` entry by
+        entry, 0 exactly where `r_cut` is, nothing beyond `psa_amd.max_pair_radius(box)`; None: `r_cut`, no hysteresis.
+        `intermittent` is the share alive at the lag, `continuous` (unless `continuous=False`) the share alive at every
+        frame o + sample_step, o + 2 sample_step, ... up to the lag, `cage(c)` the share of the centres that lost fewer than
+        c neighbours, `lifetime()` the 1/e time.  Integer counts, the same bits for any budget and atom order; positions as
+        stored, nothing unwrapped.  `per_atom=True` adds `alive_masks`, `unbroken_masks` and `atoms`.
+
+        Where a centre has more than 64 neighbours the call raises ValueError naming the species: choose a smaller `r_cut`
+        (`Engine.bond_persistence` returns the numbers instead).  A sharded calculator refuses (NotImplementedError).
+        Returns a `psa_amd.BondPersistence`."""
+        if isinstance(sample_step, (bool, np.bool_)) or not isinstance(sample_step, (int, np.integer)) or int(sample_step) < 1:
+            raise ValueError(f"sample_step must be an integer of at least 1, got {sample_step!r}")
+        if not isinstance(continuous, (bool, np.bool_)):
+            raise TypeError(f"continuous must be a bool, got {type(continuous).__name__}")
+        self._check_per_atom(per_atom)
+        n_t = self.traj.n_frames
+        tau = persistence.check_lags(lag_frames, n_t, int(sample_step))
+        rc, step, groups = self._shell_inputs(r_cut, basis_atom_indices, basis_atom_types, origin_step, "the bond persistence")
+        rb = persistence.check_break(r_break, rc)
+        served = max_pair_radius(self.traj.box_matrix)
+        if rb.size and float(rb.max()) > served:
+            raise ValueError(f"r_break = {float(rb.max())!r} is beyond the served radius {served!r} (psa_amd.max_pair_radius): "
+                             "(1/2 - 2^-12) of the box's least perpendicular width")
+        if groups is None:
+            return persistence.result(persistence.empty(1, tau.size), tau, np.zeros(tau.size, np.int64), [np.zeros(0, int)], self.dt_ps,
+                                      bool(continuous))
+        if rb.ndim == 2 and rb.shape != (len(groups), len(groups)):
+            raise ValueError(f"r_break must be a scalar or a symmetric ({len(groups)}, {len(groups)}) matrix, got shape {rb.shape}")
+        out = self._displacement_run(lambda eng, box: eng.bond_persistence(box, rc, tau, groups, step, r_break=rb,
+                                                                           sample_step=int(sample_step), continuous=bool(continuous),
+                                                                           per_atom=bool(per_atom)))
+        res = persistence.result(out, tau, (n_t - 1 - tau) // step + 1, groups, self.dt_ps, bool(continuous))
+        self._refuse_truncated(res.truncated.sum(axis=0))
         return res
 
     # ------------------------------------------------------------------ partial (species-resolved) spectra on that lattice

@@ -797,6 +797,23 @@ int launch_cluster_hook(psa_ctx* c, const int* d_count, const void* d_list, cons
 int launch_cluster_flatten(psa_ctx* c, const ClusterWork& w, int* d_err, int64_t n_a, int64_t n_ob);
 // d_origin (n_ob, 4) int32: n_solid, n_clusters, largest, largest_label; d_part (cluster_stat_groups, cluster_stat_words) uint32
 int launch_cluster_stats(psa_ctx* c, const ClusterWork& w, int* d_origin, unsigned* d_part, int n_sizes, int64_t n_a, int64_t n_ob);
+// --- persist.hip (psa_bond_persistence: the pairs listed at an origin tested again at later frames; the arithmetic and the
+// tiling are in its header)
+constexpr int PERSIST_MAX_LAGS = 1024;     // most lags of a call
+// columns of a partial row and of a (lag, species) accumulator row: per beta the bonds, the alive and the unbroken ones (S
+// each), lost[65], the truncated centres
+inline int64_t persist_row_words(int S) { return 3ll * S + ANGLE_MAX_NEIGHBOURS + 2; }
+// d_count, d_list as the neighbour pass leaves them -> d_tags (n_ob, n_a, 64) int32, the tag words, and d_surv (n_ob, n_a):
+// a centre's n low bits, 0 where it is truncated
+int launch_persist_tags(psa_ctx* c, const int* d_count, const void* d_list, int* d_tags, unsigned long long* d_surv, int64_t n_a,
+                        int64_t n_ob);
+// one visited frame over the first n_ob origins of a block.  d_items as for launch_angle_hist; d_cl (n_ob, 3, n_a) the
+// fractions of the lagged frames; rb: the species with float32(1 / r_break) in inv_rc; keep: d_surv &= the alive mask;
+// d_part not null (a listed lag): d_alive (n_ob, n_a) and item i's persist_row_words counters at d_part + i part_stride
+// (uint32) are written -- an item's samples stay below 2^32 (the caller's rule)
+int launch_persist_step(psa_ctx* c, const int* d_count, const int* d_tags, const void* d_items, int64_t n_items, const float* d_cl,
+                        unsigned long long* d_surv, unsigned long long* d_alive, unsigned* d_part, int64_t part_stride,
+                        const AngleSpecies& rb, const double* box, int64_t n_a, int64_t n_ob, bool keep);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 
