@@ -1074,6 +1074,67 @@ int psa_bond_persistence(psa_ctx* ctx, const double* box /* 9 */, const double* 
                          size_t truncated_bytes, uint64_t* alive_masks /* (n_lags, n_o(0), n_a) or NULL */,
                          uint64_t* unbroken_masks /* the same */, size_t masks_bytes /* of each */);
 
+/* Common-neighbour analysis (Honeycutt and Andersen; Faken and Jonsson): the signature (j, k, l) of every bond of the
+ * neighbour lists and the structure type -- fcc, hcp, bcc, icosahedral, other -- of every atom at every time origin, as
+ * integers.
+ * Inputs.  The positions slot as stored, H = box with its inverse, S <= 8 disjoint species (idx, group_start), r_cut (S, S)
+ * and origin_step exactly as for psa_angle_histogram, under the same checks and refusals.  Origins o = 0, s, 2 s, ... <=
+ * T-1, n_o = (T-1) / s + 1.
+ * Neighbours and left-out centres.  The neighbours b_0, .., b_{n-1} of centre a at origin o are bit for bit those of
+ * psa_angle_histogram, of all species together, in the order of psa_debug_neighbour_lists.  A (centre, origin) with more
+ * than 64 neighbours is left out whole -- never its first 64 -- and counted in truncated[alpha].
+ * Adjacency.  Two listed neighbours b_i in beta, b_j in gamma of a are bonded when the float32 chain stated at
+ * psa_angle_histogram holds for them at that origin: min_image of their centred fractions, x = sqrt(r2) float32(1 /
+ * r_cut[beta,gamma]), x < 1, every operation rounded once; r_cut[beta,gamma] = 0: no bond.  The chain is odd in e bit for
+ * bit and r_cut is symmetric, so the adjacency is symmetric; it is "b_j is in b_i's list" wherever b_i's list is complete,
+ * and it asks for no list of b_i's: a neighbour that is truncated itself changes nothing.
+ * Signature of the bond a-b_i.  C_i: the listed neighbours of a that are bonded to b_i, the common neighbours.  j = |C_i|;
+ * k = the number of bonds among the members of C_i; l = the number of bonds of the largest connected component of that bond
+ * graph (the "longest chain" of the widely used implementations: a star of three bonds has l = 3, not 2).
+ * Type of a centre with n neighbours that is not truncated:
+ *     1 fcc    n = 12 and 12 x (4,2,1)
+ *     2 hcp    n = 12 and 6 x (4,2,1) + 6 x (4,2,2)
+ *     3 bcc    n = 14 and 8 x (6,6,6) + 6 x (4,4,4)
+ *     4 ico    n = 12 and 12 x (5,5,5)
+ *     0 other  anything else, n = 0 among it
+ * Outputs, uint64.  signature_counts (S, 8, 16, 16): per species of the centre the bonds with signature (j, k, l), j < 8, k <
+ * 16, l < 16, over all origins; signature_outside (S): the bonds whose signature does not fit.  type_counts (n_o, S, 5): the
+ * centres of every species by type at every origin.  truncated (S).  Exactly:
+ *     sum signature_counts[alpha] + signature_outside[alpha] = sum_beta sum_n n coord[alpha,beta,n] of psa_angle_histogram
+ *     sum_t type_counts[o,alpha,t] + the centres of alpha truncated at o = N_alpha
+ * Optionally per atom, in list order (NULL: not asked for): types (n_o, n_a) int32, -1 for a truncated centre; n (n_o, n_a)
+ * int32, the true neighbour count (beyond 64 too); bond_signatures (n_o, n_a, 64) uint32: j | k << 8 | l << 16 of the bond
+ * to the i-th neighbour in the order of psa_debug_neighbour_lists -- k and l clamped to 255 in this word (j <= 63 always;
+ * such a bond lies outside the table in any case) --, 0xFFFFFFFF at and beyond n and for a truncated centre.
+ * As evaluated (cna.hip): the fraction pass and the neighbour pass of psa_angle_histogram; a signature pass in which a
+ * wavefront takes a centre and lane i its i-th neighbour: the lane gathers the neighbour's fractions once, the n (n - 1) / 2
+ * pairs of neighbours go through rounds in which lane i tests (i, i + m mod n), m = 1 .. n / 2, each round's ballot sets both
+ * ends' bits, and lane i ends with row i of the 64 x 64 adjacency as one 64-bit word; the rows are parked in LDS and the lane
+ * derives its bond's signature with bit operations alone (a popcount, a flood over masks that pops every common neighbour
+ * once: at most 64 steps); the type is five ballots.  Counts go by 32-bit integer adds into counters in LDS -- the host
+ * keeps a workgroup's samples below 2^32 --, written to partials with plain stores and summed in 64-bit integers; a census
+ * pass counts the types per origin and species by integer sums.  No global atomics, no float atomics, and nothing after the
+ * adjacency is floating point: two identical calls, any budget, with or without the per-atom outputs and any order of the
+ * atoms inside a species give the same bits.
+ * Budget (PSA_OPT_DYNAMIC_WORK_BYTES): per origin of a block 1040 n_a bytes as for psa_angle_histogram, plus 8 n_a (the
+ * types 4, 4 of padding), plus 256 n_a where bond_signatures is asked for; a budget below one origin is refused and the
+ * refusal names the bytes needed.
+ * PSA_EINVAL: everything psa_angle_histogram refuses about the context (a sharded one among it), the box, the species,
+ * r_cut, origin_step and the budget; signature_bytes or type_bytes not exact; with types or n, atom_bytes not exact; with
+ * bond_signatures, bond_bytes not exact; a null required output.
+ * Only the positions slot is read.  Atom weights and segments set on the context are ignored, not refused; every result
+ * and plan of the other entry points is left as it is.  Stage times: [0] the tables' upload, [5] the fraction pass, [6] the
+ * neighbour pass, [1] the signature and the census pass, of these [2] the census pass, [4] reduce, [7] device->host.
+ * Not served: adaptive cut-offs per atom, diamond identification, signature tables resolved by the species pair of the
+ * bond (bond_signatures with the lists give them on the host), cell lists, sharding. */
+int psa_common_neighbours(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                          const int64_t* group_start /* S+1 */, int32_t n_groups, const double* r_cut /* S*S */,
+                          int64_t origin_step, uint64_t* signature_counts /* (S, 8, 16, 16) */, size_t signature_bytes,
+                          uint64_t* signature_outside /* S */, uint64_t* type_counts /* (n_o, S, 5) */, size_t type_bytes,
+                          uint64_t* truncated /* S */, int32_t* types /* (n_o, n_a) or NULL */, int32_t* n /* the same */,
+                          size_t atom_bytes /* of each */, uint32_t* bond_signatures /* (n_o, n_a, 64) or NULL */,
+                          size_t bond_bytes);
+
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting
  * (unique_idx[r] = position of row r's vector in the input list), with bit 31 set when vector i is

@@ -96,6 +96,9 @@ CLUSTER_ROW_WORDS = ANGLE_MAX_NEIGHBOURS + 1 + 4   # a species' row: connections
 CLUSTER_LINKS = ("neighbours", "solid_bonds")      # link 0, 1
 # the cap of the persistence kernels (psa_amd/csrc/persist.hip)
 PERSIST_MAX_LAGS = 1024     # most lags of a call
+# the table of the common-neighbour kernels (psa_amd/csrc/cna.hip)
+CNA_TABLE = (8, 16, 16)     # the signatures (j, k, l) the table holds: j < 8, k < 16, l < 16
+CNA_TYPES = ("other", "fcc", "hcp", "bcc", "ico")   # type 0 .. 4
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -207,6 +210,9 @@ SIGNATURES = {
     "psa_bond_persistence": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p, _f64p, C.c_int64,
                                        _i64p, C.c_int32, C.c_int64, C.c_int32, _u64p, _u64p, _u64p, C.c_size_t,
                                        _u64p, C.c_size_t, _u64p, C.c_size_t, _u64p, _u64p, C.c_size_t]),
+    "psa_common_neighbours": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p, C.c_int64, _u64p, C.c_size_t,
+                                        _u64p, _u64p, C.c_size_t, _u64p, _i32p, _i32p, C.c_size_t, C.POINTER(C.c_uint32),
+                                        C.c_size_t]),
     "psa_debug_cluster_labels": (C.c_int, [_ctx, C.c_int64, C.c_int64, _i32p, _i32p, C.POINTER(C.c_uint8), _u64p, C.c_int32,
                                            C.c_int32, _u64p, _u64p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
@@ -1320,6 +1326,31 @@ class Engine:
                                               masks[0].nbytes if per_atom else 0), "psa_bond_persistence")
         return dict(bonds=pair[0], alive=pair[1], unbroken=pair[2], lost=lost, truncated=trunc, alive_masks=masks[0],
                     unbroken_masks=masks[1])
+
+    def common_neighbours(self, box, r_cut, groups=None, origin_step: int = 1, per_atom: bool = False, box_inverse=None) -> dict:
+        """Common-neighbour analysis as counts (psa_common_neighbours).  The neighbours are those of `angle_histogram` (`r_cut`
+        a scalar or symmetric (S, S), 0: no bond); two neighbours of a centre are bonded by the same float32 chain.  The
+        bond a-b has the signature (j, k, l): its common neighbours, the bonds among them, the bonds of the largest connected
+        piece of those.  Returns a dict: signature_counts (S, 8, 16, 16) uint64 per species of the centre, signature_outside
+        (S,) uint64 the bonds beyond the table, type_counts (n_o, S, 5) uint64 the centres by type (`CNA_TYPES`: other, fcc,
+        hcp, bcc, ico) at every origin, truncated (S,) uint64 the centres with more than 64 neighbours, left out whole; with
+        `per_atom` types (n_o, n_a) int32 (-1: truncated), n (n_o, n_a) int32 the true neighbour counts and bond_signatures
+        (n_o, n_a, 64) uint32, j | k << 8 | l << 16 for the i-th neighbour of `debug_neighbour_lists` (0xFFFFFFFF: no bond),
+        else None.  `box`, `groups`, `origin_step` as for `pair_histogram`.  Only positions are read, as stored."""
+        a = self._shell_args(box, box_inverse, groups, r_cut, origin_step)
+        table = np.empty((a.G,) + CNA_TABLE, np.uint64)
+        outside, trunc = (np.empty(a.G, np.uint64) for _ in range(2))
+        census = np.empty((a.n_o, a.G, len(CNA_TYPES)), np.uint64)
+        types, n = ((pinned_empty((a.n_o, a.n_a), np.int32) if per_atom else None) for _ in range(2))   # (every cell is written by the call)
+        sigs = pinned_empty((a.n_o, a.n_a, ANGLE_MAX_NEIGHBOURS), np.uint32) if per_atom else None
+        u64 = lambda x: x.ctypes.data_as(_u64p)                                                        # noqa: E731
+        i32 = lambda x: None if x is None else x.ctypes.data_as(_i32p)                                 # noqa: E731
+        _check(self._lib.psa_common_neighbours(*a.head, int(origin_step), u64(table), table.nbytes, u64(outside), u64(census), census.nbytes,
+                                               u64(trunc), i32(types), i32(n), types.nbytes if per_atom else 0,
+                                               None if sigs is None else sigs.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                               sigs.nbytes if per_atom else 0), "psa_common_neighbours")
+        return dict(signature_counts=table, signature_outside=outside, type_counts=census, truncated=trunc, types=types, n=n,
+                    bond_signatures=sigs)
 
     def debug_cluster_labels(self, count, lists, solid, bond_masks=None, link: int = 0, n_sizes: int = 256) -> dict:
         """The graph passes of `solid_clusters` alone on a graph of the caller's (psa_debug_cluster_labels): `count` (n_o, n_a)

@@ -37,11 +37,12 @@ from ..covariance import ModeVectors, mode_vectors, spectral_weights
 from ..displacements import (MeanSquareDisplacement, VanHoveSelf, alpha2, check_count, check_lag_frames, check_origin_step,
                              origin_counts, radial_bins)
 from ..dynamic import DynamicSpectra
-from .. import angles, clusters, local_order, order, persistence
+from .. import angles, clusters, cna, local_order, order, persistence
 from ..angles import BondAngleDistribution
 from ..order import BondOrder
 from ..clusters import SolidClusters
 from ..persistence import BondPersistence
+from ..cna import CommonNeighbours
 from ..local_order import LocalOrder
 from ..pairs import RadialDistribution, VanHoveDistinct, max_pair_radius
 from .. import lattice
@@ -1143,6 +1144,33 @@ class SEDCalculator:
                                                                            per_atom=bool(per_atom)))
         res = persistence.result(out, tau, (n_t - 1 - tau) // step + 1, groups, self.dt_ps, bool(continuous))
         self._refuse_truncated(res.truncated.sum(axis=0))
+        return res
+
+    # ------------------------------------------------------------------ common-neighbour analysis (fcc / hcp / bcc / ico)
+    def calculate_common_neighbours(self, r_cut,
+                                    basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                    basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                    origin_step: int = 1, per_atom: bool = False) -> CommonNeighbours:
+        """Common-neighbour analysis (not in the reference; definition in psa_amd/cna.py), computed on the GPU from the
+        positions resident in HBM.  The neighbours, `r_cut`, the species and `origin_step` are those of
+        `calculate_bond_angles`, bit for bit, and two neighbours of a centre are bonded by the same test.  Every bond gets
+        its signature (j, k, l) -- the common neighbours of its two ends, the bonds among them, the bonds of the largest
+        connected piece of those -- and every atom its type at every origin: fcc (12 x 421), hcp (6 x 421 + 6 x 422), bcc
+        (8 x 666 + 6 x 444 among 14 neighbours), ico (12 x 555) or other.  `signature_counts`, `type_counts` and with them
+        `fraction(type)`, `signature(j, k, l)` and `share(j, k, l)` are integer counts, the same bits for any budget and atom
+        order; positions as stored, nothing unwrapped.  `per_atom=True` adds `types`, `neighbours`, `bond_signatures`, `atoms`
+        and `atoms_of(origin, type)`.
+
+        Where a centre has more than 64 neighbours the call raises ValueError naming the species: choose a smaller `r_cut`
+        (`Engine.common_neighbours` returns the numbers instead).  A sharded calculator refuses (NotImplementedError).
+        Returns a `psa_amd.CommonNeighbours`."""
+        self._check_per_atom(per_atom)
+        rc, step, groups = self._shell_inputs(r_cut, basis_atom_indices, basis_atom_types, origin_step, "the common-neighbour analysis")
+        if groups is None:
+            return cna.result(cna.empty(1), 0, [np.zeros(0, int)])
+        out = self._displacement_run(lambda eng, box: eng.common_neighbours(box, rc, groups, step, bool(per_atom)))
+        res = cna.result(out, (self.traj.n_frames - 1) // step + 1, groups)
+        self._refuse_truncated(res.truncated)
         return res
 
     # ------------------------------------------------------------------ partial (species-resolved) spectra on that lattice

@@ -814,6 +814,21 @@ int launch_persist_tags(psa_ctx* c, const int* d_count, const void* d_list, int*
 int launch_persist_step(psa_ctx* c, const int* d_count, const int* d_tags, const void* d_items, int64_t n_items, const float* d_cl,
                         unsigned long long* d_surv, unsigned long long* d_alive, unsigned* d_part, int64_t part_stride,
                         const AngleSpecies& rb, const double* box, int64_t n_a, int64_t n_ob, bool keep);
+// --- cna.hip (psa_common_neighbours: the signature (j, k, l) of every bond of the lists and the structure type of every
+// centre; the arithmetic and the tiling are in its header)
+constexpr int CNA_MAX_J = 8, CNA_MAX_K = 16, CNA_MAX_L = 16;   // the signature table holds j < 8, k < 16, l < 16
+constexpr int CNA_TYPES = 5;               // other, fcc, hcp, bcc, ico
+// columns of a partial row and of a species' accumulator row: the table, the bonds outside it, the truncated centres
+constexpr int CNA_ROW_WORDS = CNA_MAX_J * CNA_MAX_K * CNA_MAX_L + 2;
+// d_c (n_ob, 3, n_a) the fractions the neighbour pass read; d_count, d_list, d_items as for launch_angle_hist; d_types (n_ob,
+// n_a) int32: the type, -1 where the centre is truncated; d_sigs (n_ob, n_a, 64) uint32 or null: j | k << 8 | l << 16 in list
+// order, 0xffffffff at and beyond n and for a truncated centre; d_part (n_items, CNA_ROW_WORDS) uint32 -- an item's samples
+// stay below 2^32 (the caller's rule)
+int launch_cna_signature(psa_ctx* c, const float* d_c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items,
+                         int* d_types, unsigned* d_sigs, unsigned* d_part, const AngleSpecies& sp, const double* box, int64_t n_a,
+                         int64_t n_ob);
+// d_types as above -> d_out (n_ob, S, CNA_TYPES) uint64, the centres of every species by type (a truncated one in none)
+int launch_cna_census(psa_ctx* c, const int* d_types, unsigned long long* d_out, const AngleSpecies& sp, int64_t n_a, int64_t n_ob);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 
