@@ -88,6 +88,13 @@ int         psa_set_k1(psa_ctx* ctx, int selector);     /* PSA_K1_* */
  * per-element bound; on = 0: the route as it was, bit for bit.  A switch of its own like psa_set_k1, not a row of the option
  * table below. */
 int         psa_set_k1_lowrank_fold(psa_ctx* ctx, int on);
+/* The folded route's node count, 48 (a new context) or 64.  64 Chebyshev nodes interpolate the line's phases to fp64
+ * rounding; 48 leave a residual of at most 4.6e-7, which the folded D image absorbs with everything else the node rows' hi
+ * piece does not carry: D' = P_ref w - phi L W_hi, taken in fp64 and rounded once to float16.  Node rows fall from 128 to 96
+ * (k1_lowrank_n48.hip for lists the pair launch serves, else the two-product node pass on the 48-node table and the D pass on
+ * that image).  Effective only while the fold is on: with the fold off the route has 64 nodes.  Results move within the
+ * route's per-element bound; 64: the folded route as it was, bit for bit.  A switch of its own, like the fold. */
+int         psa_set_k1_lowrank_nodes(psa_ctx* ctx, int nodes);
 /* Tunables of the product path (defaults in brackets):
  *   PSA_OPT_PLANES        [1] keep, per atom group, the group's data scaled, split into its two
  *                             float16 pieces and laid out in MFMA-fragment order ("split planes",
@@ -1155,6 +1162,12 @@ int psa_sed_set_kmap(psa_ctx* ctx, const int32_t* kmap, int64_t K_out);
  * factors are checked against, which no kernel reads (any may be null).  No context, no GPU. */
 int psa_lowrank_plan(const float* k_vectors, int64_t K, const float* mean_pos_all, int64_t N, const int32_t* idx,
                      int64_t n_g, int32_t* ok, double* geo, double* kappa, float* C, float* L, float* phi);
+/* The same for a plan of `nodes` = 48 or 64 nodes (psa_set_k1_lowrank_nodes): kappa[nodes], L[K * nodes], C[K * nodes * 2];
+ * geo[15], the 14 values above -- e_bound from this plan's L; with 48 nodes the scale of the image from d_bound + e_bound +
+ * 1e-6, the cap on r_bound a launch uses -- and r_bound, with 48 nodes the fp64 maximum over the rows and the group's atoms
+ * of |P_line - phi L W| (W the node rows in fp64, L and phi the float32 tables), 0 with 64. */
+int psa_lowrank_plan_nodes(const float* k_vectors, int64_t K, const float* mean_pos_all, int64_t N, const int32_t* idx,
+                           int64_t n_g, int32_t nodes, int32_t* ok, double* geo, double* kappa, float* C, float* L, float* phi);
 
 /* One (k, omega) bin: S[c] = FFT_t(q)[i_w] / T for ONE k-vector and one atom group, as 3
  * complex64 -- what iSED consumes of a group's spectrum (sed_calculator.py:483, :494-499: only
@@ -1196,6 +1209,9 @@ int psa_lowrank_pair_image(int32_t n_stage, int64_t* index, int64_t* bytes);
 /* The same for the folded D image of the folded pair launch (k1_lowrank_fold.h, psa_set_k1_lowrank_fold): rows 0..127 in
  * role A's part, rows 128..511 in role B's.  No context, no GPU. */
 int psa_lowrank_fold_image(int32_t n_stage, int64_t* index, int64_t* bytes);
+/* ... and for the D image of the 48-node pair launch (k1_lowrank_n48.h, psa_set_k1_lowrank_nodes): rows 0..159 in role A's
+ * part, rows 160..511 in role B's.  No context, no GPU. */
+int psa_lowrank_n48_image(int32_t n_stage, int64_t* index, int64_t* bytes);
 /* Device allocations the library's contexts hold at this moment, process-wide: how many and their bytes.  A destroyed
  * context leaves none behind.  No context, no GPU. */
 int psa_debug_device_buffers(int64_t* count, int64_t* bytes);

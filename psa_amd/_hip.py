@@ -121,6 +121,7 @@ SIGNATURES = {
     "psa_synchronize": (C.c_int, [_ctx]),
     "psa_set_k1": (C.c_int, [_ctx, C.c_int]),
     "psa_set_k1_lowrank_fold": (C.c_int, [_ctx, C.c_int]),
+    "psa_set_k1_lowrank_nodes": (C.c_int, [_ctx, C.c_int]),
     "psa_set_option": (C.c_int, [_ctx, C.c_int, C.c_int64]),
     "psa_device_info": (C.c_int, [_ctx, C.c_char_p, C.c_int, C.POINTER(C.c_int), _i64p]),
     "psa_data_upload": (C.c_int, [_ctx, C.c_int, _f32p, C.c_int64, C.c_int64]),
@@ -230,6 +231,9 @@ SIGNATURES = {
     "psa_k1_lowrank_pair_launches": (C.c_int, [_ctx, _i64p]),
     "psa_lowrank_pair_image": (C.c_int, [C.c_int32, _i64p, _i64p]),
     "psa_lowrank_fold_image": (C.c_int, [C.c_int32, _i64p, _i64p]),
+    "psa_lowrank_n48_image": (C.c_int, [C.c_int32, _i64p, _i64p]),
+    "psa_lowrank_plan_nodes": (C.c_int, [_f32p, C.c_int64, _f32p, C.c_int64, _i32p, C.c_int64, C.c_int32, _i32p, _f64p, _f64p, _f32p,
+                                         _f32p, _f32p]),
     "psa_oneoff_stats": (C.c_int, [_ctx, _f64p]),
     "psa_option_info": (C.c_int, [C.c_int, C.POINTER(C.c_int32), _i64p, C.POINTER(C.c_char_p)]),
     "psa_debug_device_buffers": (C.c_int, [_i64p, _i64p]),
@@ -390,6 +394,38 @@ def lowrank_plan(k_vectors, mean_pos_all, idx=None):
     return {"u": geo[0:3].copy(), "k0": geo[3:6].copy(), "x_c": geo[6], "h_x": geo[7], "width": geo[8],
             "interval": int(geo[9]), "d_bound": geo[10], "dscale": geo[11], "e_bound": geo[12],
             "dscale_fold": geo[13], "kappa": kappa, "C": cm, "L": lw, "phi": phi}
+
+
+def lowrank_plan_nodes(k_vectors, mean_pos_all, idx=None, nodes=48):
+    """lowrank_plan for a plan of `nodes` = 48 or 64 Chebyshev nodes (psa_lowrank_plan_nodes; host only;
+    Engine.set_k1_lowrank_nodes): kappa (nodes,), C and L (K, nodes), and beside lowrank_plan's keys r_bound -- with 48 nodes
+    the largest |P_line - phi L W| over the rows and the group's atoms, which the D image absorbs; dscale_fold then comes
+    from d_bound + e_bound + 1e-6, the cap on r_bound."""
+    kv = _as_f32(k_vectors, (3,))
+    mean = _as_f32(mean_pos_all, (3,))
+    K, N, nodes = kv.shape[0], mean.shape[0], int(nodes)
+    ix = None if idx is None else np.ascontiguousarray(idx, np.int32)
+    n_g = N if ix is None else ix.size
+    ok, geo = C.c_int32(0), np.zeros(15, np.float64)
+    kappa, cm = np.zeros(nodes, np.float64), np.zeros((K, nodes), np.complex64)
+    lw, phi = np.zeros((K, nodes), np.float32), np.zeros(K, np.complex64)
+    _check(load_library().psa_lowrank_plan_nodes(_f32(kv), K, _f32(mean), N, None if ix is None else ix.ctypes.data_as(_i32p), n_g,
+                                                 nodes, C.byref(ok), geo.ctypes.data_as(_f64p), kappa.ctypes.data_as(_f64p),
+                                                 cm.ctypes.data_as(_f32p), _f32(lw), phi.ctypes.data_as(_f32p)),
+           "psa_lowrank_plan_nodes")
+    if not ok.value:
+        return None
+    return {"u": geo[0:3].copy(), "k0": geo[3:6].copy(), "x_c": geo[6], "h_x": geo[7], "width": geo[8],
+            "interval": int(geo[9]), "d_bound": geo[10], "dscale": geo[11], "e_bound": geo[12],
+            "dscale_fold": geo[13], "r_bound": geo[14], "nodes": nodes, "kappa": kappa, "C": cm, "L": lw, "phi": phi}
+
+
+def lowrank_n48_image(n_stage: int):
+    """The D image of the low-rank route's 48-node pair launch (psa_lowrank_n48_image; host only) for n_stage 32-atom
+    stages: (index, nbytes) as lowrank_pair_image, rows 0..159 in role A's part and rows 160..511 in role B's."""
+    index, nbytes = np.zeros((512, 32 * int(n_stage)), np.int64), C.c_int64(0)
+    _check(load_library().psa_lowrank_n48_image(int(n_stage), index.ctypes.data_as(_i64p), C.byref(nbytes)), "psa_lowrank_n48_image")
+    return index, nbytes.value
 
 
 def lowrank_pair_image(n_stage: int):
@@ -571,6 +607,12 @@ class Engine:
         """The low-rank k-path route with the node table's lo piece folded into the D image (psa_set_k1_lowrank_fold; on in a
         new context).  False: the route as it was, bit for bit."""
         _check(self._lib.psa_set_k1_lowrank_fold(self._h, int(bool(on))), "psa_set_k1_lowrank_fold")
+
+    def set_k1_lowrank_nodes(self, nodes: int):
+        """Chebyshev nodes of the folded low-rank k-path route (psa_set_k1_lowrank_nodes): 48 (a new context) or 64.  With 48
+        the folded D image also absorbs the interpolation residual and the node rows are 96.  Effective only while the fold
+        is on; 64: the folded route as it was, bit for bit."""
+        _check(self._lib.psa_set_k1_lowrank_nodes(self._h, int(nodes)), "psa_set_k1_lowrank_nodes")
 
     def device_info(self) -> dict:
         name = C.create_string_buffer(256)

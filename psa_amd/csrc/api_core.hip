@@ -433,6 +433,14 @@ int psa_set_k1_lowrank_fold(psa_ctx* c, int on) {
     return PSA_OK;
 }
 
+int psa_set_k1_lowrank_nodes(psa_ctx* c, int nodes) {
+    PSA_TRY(enter(c));
+    PSA_REQUIRE(nodes == 48 || nodes == 64, "the low-rank route has 48 or 64 nodes, not %d", nodes);
+    Guard g(c);
+    c->k1_lowrank_nodes = nodes;
+    return PSA_OK;
+}
+
 int psa_set_option(psa_ctx* c, int option, int64_t value) {
     PSA_TRY(enter(c));
     Guard g(c);

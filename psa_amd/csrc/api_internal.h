@@ -173,20 +173,25 @@ struct LowRankPlan {
     double              u[3] = {0, 0, 0}, k0[3] = {0, 0, 0};   // the line: k0 + kappa u
     double              x_c = 0, h_x = 0, width = 0;          // the group's centre / half-width along u; node interval width
     int64_t             interval = 0;                         // node interval [interval * width, + width)
-    double              kappa[LOWRANK_NODES] = {};            // the nodes
+    int                 nodes = LOWRANK_NODES;                // Chebyshev nodes: 64, or 48 (psa_set_k1_lowrank_nodes)
+    double              kappa[LOWRANK_NODES] = {};            // the nodes (the first `nodes` entries)
     double              d_bound = 0;                          // bound on |P_ref - P_line|
     float               dscale = 0.f;                         // power of two the D image carries
     double              e_bound = 0;                          // bound on |E|, the node table's lo piece through the combine:
                                                               // max_j rot_j Lam_j 2^-12 from the float32 L and phi
-    float               dscale_fold = 0.f;                    // power of two the folded image D + E carries
+    float               dscale_fold = 0.f;                    // power of two the folded image D + E carries (48 nodes: from
+                                                              // d_bound + e_bound + LR48_R_MAX, the cap on any r_bound)
+    double              r_bound = 0;                          // 48 nodes, on request: max over rows and atoms of |P_line - phi L W|
     std::vector<double> kline;                               // (K, 3) the k-vectors projected on the line
-    std::vector<float>  L;                                    // (K, 64) the combine's real Lagrange weights L_l(kappa_j)
+    std::vector<float>  L;                                    // (K, nodes) the combine's real Lagrange weights L_l(kappa_j)
     std::vector<float>  phi;                                  // (K) complex64, the combine's row phases exp(i kappa_j x_c)
 };
 // C (may be null; written only when the plan is ok): (K, 64) complex64, the product phi L rounded once from fp64 -- what
 // psa_lowrank_plan reports beside the two factors.  No kernel reads it, so a launch asks for none.
+// nodes: 64 or 48.  want_r (48 nodes): also r_bound, K x n_g x 48 complex products on the host -- the entry that reports the
+// plan asks for it, a launch does not (its image scale takes the cap LR48_R_MAX instead).
 int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, const int32_t* h_idx, int64_t n_g, LowRankPlan* p,
-                 float* C = nullptr);
+                 float* C = nullptr, int nodes = LOWRANK_NODES, bool want_r = false);
 int prepare_lowrank(psa_ctx* c, const GroupView& v, const ProjectArgs& list, int64_t k_first, int64_t nk, ProjGeom* g);
 // api_modes.hip: what psa_sed_modes, psa_sed_modes_welch and their fits were called with, and their one body.  The result,
 // (T, K, M) or with segments (L, K, M), is left in c->d_modes_out.  `segments`: the context's segments are honoured or

@@ -26,6 +26,7 @@
 // for such lists splitting can move rows by the ~1e-7 that separates the two routes.
 #include "api_internal.h"
 #include "k1_lowrank_fold.h"
+#include "k1_lowrank_n48.h"
 #include "k1_lowrank_pair.h"
 
 namespace psa {
@@ -33,11 +34,19 @@ namespace psa {
 namespace {
 constexpr double LR_OMEGA = 30.0;                 // half-width product h_k h_x of a node interval
 constexpr double LR_D_MAX = 1.0 / 8192.0;         // 2^-13
+// Cap on the 48-node plan's r_bound (plan_lowrank).  The largest residual of 48-node interpolation over a whole node interval
+// is a function of LR_OMEGA and the node count alone: 4.6e-7 at 30 and 48 (1.0e-3 with 40 nodes, 2.7e-5 with 44), plus the
+// float32 rounding of phi and L, at most (1 + 3.5) 2^-24 = 2.7e-7.  No launch checks it -- tests/test_lowrank_n48_host.py
+// holds every r_bound to it --, so a change of LR_OMEGA or of the node count has to work this number out again.
+constexpr double LR48_R_MAX = 1e-6;
+static_assert(LR_OMEGA == 30.0 && LOWRANK_NODES_48 == 48, "LR48_R_MAX was worked out for 48 nodes on h_k h_x = 30");
 }  // namespace
 
 int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, const int32_t* h_idx, int64_t n_g, LowRankPlan* p,
-                 float* C) {
+                 float* C, int nodes, bool want_r) {
     *p = LowRankPlan{};
+    PSA_REQUIRE(nodes == LOWRANK_NODES || nodes == LOWRANK_NODES_48, "the plan has 48 or 64 nodes");
+    p->nodes = nodes;
     auto fail = [&](const char* why) {
         p->why = why;
         return PSA_OK;
@@ -153,39 +162,39 @@ int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, co
         if (std::floor(std::fabs(kap[(size_t)j]) / p->width) != n0) return fail("k-path longer than one node interval");
     p->interval = side ? (int64_t)n0 : -(int64_t)n0 - 1;
     const double mid = (p->interval + 0.5) * p->width, half = 0.5 * p->width;
-    double       bw[LOWRANK_NODES];
-    for (int l = 0; l < LOWRANK_NODES; ++l) {
-        const double th = M_PI * (2 * l + 1) / (2.0 * LOWRANK_NODES);
+    double       bw[LOWRANK_NODES];                               // (the first `nodes` entries)
+    for (int l = 0; l < nodes; ++l) {
+        const double th = M_PI * (2 * l + 1) / (2.0 * nodes);
         p->kappa[l] = mid + half * std::cos(th);
         bw[l] = ((l & 1) ? -1.0 : 1.0) * std::sin(th);           // barycentric weights of Chebyshev points of the first kind
     }
     // ---- L[j, l] and phi[j], each rounded from fp64 on its own; for a caller that asks, C[j, l] = exp(i kappa_j x_c)
     // L_l(kappa_j), complex64, their product rounded once
-    p->L.assign((size_t)K * LOWRANK_NODES, 0.f);
+    p->L.assign((size_t)K * nodes, 0.f);
     p->phi.assign((size_t)K * 2, 0.f);
     for (int64_t j = 0; j < K; ++j) {
         const double kj = kap[(size_t)j];
-        double       L[LOWRANK_NODES], den = 0.0;
+        double       L[LOWRANK_NODES], den = 0.0;                     // (the first `nodes` entries)
         int          hit = -1;
-        for (int l = 0; l < LOWRANK_NODES; ++l)
+        for (int l = 0; l < nodes; ++l)
             if (kj == p->kappa[l]) hit = l;
         if (hit >= 0) {
-            for (int l = 0; l < LOWRANK_NODES; ++l) L[l] = l == hit;
+            for (int l = 0; l < nodes; ++l) L[l] = l == hit;
         } else {
-            for (int l = 0; l < LOWRANK_NODES; ++l) {
+            for (int l = 0; l < nodes; ++l) {
                 L[l] = bw[l] / (kj - p->kappa[l]);
                 den += L[l];
             }
-            for (double& v : L) v /= den;
+            for (int l = 0; l < nodes; ++l) L[l] /= den;
         }
         const double cr = std::cos(kj * p->x_c), ci = std::sin(kj * p->x_c);
         p->phi[(size_t)j * 2 + 0] = (float)cr;
         p->phi[(size_t)j * 2 + 1] = (float)ci;
-        for (int l = 0; l < LOWRANK_NODES; ++l) {
-            p->L[(size_t)j * LOWRANK_NODES + l] = (float)L[l];
+        for (int l = 0; l < nodes; ++l) {
+            p->L[(size_t)j * nodes + l] = (float)L[l];
             if (C) {
-                C[((size_t)j * LOWRANK_NODES + l) * 2 + 0] = (float)(cr * L[l]);
-                C[((size_t)j * LOWRANK_NODES + l) * 2 + 1] = (float)(ci * L[l]);
+                C[((size_t)j * nodes + l) * 2 + 0] = (float)(cr * L[l]);
+                C[((size_t)j * nodes + l) * 2 + 1] = (float)(ci * L[l]);
             }
         }
     }
@@ -196,17 +205,47 @@ int plan_lowrank(const float* k, int64_t K, const float* mean_all, int64_t N, co
     // rot_j = |Re phi_j| + |Im phi_j|, Lam_j = sum_l |L[j, l]| of the float32 tables the device reads
     for (int64_t j = 0; j < K; ++j) {
         double lam = 0.0;
-        for (int l = 0; l < LOWRANK_NODES; ++l) lam += std::fabs((double)p->L[(size_t)j * LOWRANK_NODES + l]);
+        for (int l = 0; l < nodes; ++l) lam += std::fabs((double)p->L[(size_t)j * nodes + l]);
         const double rot = std::fabs((double)p->phi[(size_t)j * 2]) + std::fabs((double)p->phi[(size_t)j * 2 + 1]);
         p->e_bound = std::max(p->e_bound, rot * lam * 0x1p-12);
     }
     p->dscale_fold = std::ldexp(1.0f, 14 - (int)std::ceil(std::log2(p->d_bound + p->e_bound)));
+    // ---- 48 nodes: the image also holds the interpolation residual R = P_line - phi L W.  |R| depends on (kappa - mid) h_x
+    // and (x - x_c) / h_x alone, so its largest value over a whole node interval is one number for every plan: 4.6e-7
+    // at h_k h_x = 30, plus the float32 rounding of phi and L, (1 + Lam) 2^-24 <= 2.7e-7.  A launch scales the image
+    // by the cap LR48_R_MAX = 1e-6 on that; r_bound itself, the largest |R| over the launch's rows and the group's atoms,
+    // costs K x n_g x 48 complex products on the host and is worked out for psa_lowrank_plan_nodes alone.
+    if (nodes == LOWRANK_NODES_48) {
+        p->dscale_fold = std::ldexp(1.0f, 14 - (int)std::ceil(std::log2(p->d_bound + p->e_bound + LR48_R_MAX)));
+        if (want_r) {
+            std::vector<double> wr((size_t)nodes), wi((size_t)nodes);
+            for (int64_t a = 0; a < n_g; ++a) {
+                const float* r = mean_all + 3 * (h_idx ? h_idx[a] : a);
+                const double y = (u[0] * r[0] + u[1] * r[1] + u[2] * r[2]) - p->x_c;
+                const double t0 = p->k0[0] * r[0] + p->k0[1] * r[1] + p->k0[2] * r[2];
+                for (int l = 0; l < nodes; ++l) {
+                    wr[(size_t)l] = std::cos(t0 + p->kappa[l] * y);
+                    wi[(size_t)l] = std::sin(t0 + p->kappa[l] * y);
+                }
+                for (int64_t j = 0; j < K; ++j) {
+                    double sr = 0.0, si = 0.0;
+                    for (int l = 0; l < nodes; ++l) {
+                        sr += (double)p->L[(size_t)j * nodes + l] * wr[(size_t)l];
+                        si += (double)p->L[(size_t)j * nodes + l] * wi[(size_t)l];
+                    }
+                    const double pr = p->phi[(size_t)j * 2], pi = p->phi[(size_t)j * 2 + 1];
+                    const double th = p->kline[3 * j] * r[0] + p->kline[3 * j + 1] * r[1] + p->kline[3 * j + 2] * r[2];
+                    p->r_bound = std::max(p->r_bound, std::hypot(std::cos(th) - (pr * sr - pi * si), std::sin(th) - (pr * si + pi * sr)));
+                }
+            }
+        }
+    }
     p->ok = true;
     return PSA_OK;
 }
 
 // Decide the route of one projection launch (a group's planes, nk k-vectors from k_first of the list) and, when the
-// low-rank route serves, upload what it needs: fp64 [k0 (3), u (3), x_c, kappa (64), kline (nk x 3)] and the
+// low-rank route serves, upload what it needs: fp64 [k0 (3), u (3), x_c, kappa (64 or 48), with 64 nodes kline (nk x 3)] and the
 // combine's weights L and phases phi.
 // The decision depends on the list, the group and the options only -- never on how the list is split over
 // calls -- as long as every part keeps PSA_OPT_K1_LOWRANK_MIN_LOCAL vectors (default 128: a 512-row D block at
@@ -216,25 +255,30 @@ int prepare_lowrank(psa_ctx* c, const GroupView& v, const ProjectArgs& list, int
     if (!c->opt_k1_lowrank || g->split != K1Family::f16_planes || !v.ps || list.K_total < c->opt_k1_lowrank_min_k ||
         nk < c->opt_k1_lowrank_min_local)
         return PSA_OK;
+    // 48 nodes only while the fold is on: with it off the route is the 64-node route on its own kernels
+    const int   nodes = c->k1_lowrank_fold && c->k1_lowrank_nodes == LOWRANK_NODES_48 ? LOWRANK_NODES_48 : LOWRANK_NODES;
     LowRankPlan p;
-    PSA_TRY(plan_lowrank(list.k_vectors + 3 * k_first, nk, list.mean_pos_all, c->slot[v.slot].N, v.h_idx, g->n_g, &p));
+    PSA_TRY(plan_lowrank(list.k_vectors + 3 * k_first, nk, list.mean_pos_all, c->slot[v.slot].N, v.h_idx, g->n_g, &p, nullptr, nodes));
     if (!p.ok) return PSA_OK;
-    std::vector<double> f64((size_t)7 + LOWRANK_NODES + 3 * (size_t)nk);
+    // (kline feeds the 64-node tables' P_line; the 48-node image is built from the node table and needs none)
+    const bool          kline = nodes == LOWRANK_NODES;
+    std::vector<double> f64((size_t)7 + nodes + (kline ? 3 * (size_t)nk : 0));
     std::memcpy(f64.data(), p.k0, 3 * sizeof(double));
     std::memcpy(f64.data() + 3, p.u, 3 * sizeof(double));
     f64[6] = p.x_c;
-    std::memcpy(f64.data() + 7, p.kappa, sizeof(p.kappa));
-    std::memcpy(f64.data() + 7 + LOWRANK_NODES, p.kline.data(), p.kline.size() * sizeof(double));
+    std::memcpy(f64.data() + 7, p.kappa, (size_t)nodes * sizeof(double));
+    if (kline) std::memcpy(f64.data() + 7 + nodes, p.kline.data(), p.kline.size() * sizeof(double));
     PSA_TRY(upload(c, c->d_lr_f64, f64.data(), f64.size() * sizeof(double)));
     PSA_TRY(upload(c, c->d_lr_L, p.L.data(), p.L.size() * sizeof(float)));
     PSA_TRY(upload(c, c->d_lr_phi, p.phi.data(), p.phi.size() * sizeof(float)));
-    PSA_TRY(c->d_lr_qn.reserve((size_t)LOWRANK_NODES * 3 * (size_t)c->slot[v.slot].T * sizeof(float2)));
+    PSA_TRY(c->d_lr_qn.reserve((size_t)nodes * 3 * (size_t)c->slot[v.slot].T * sizeof(float2)));
     g->lowrank = true;
+    g->lr_nodes = nodes;
     g->lr_fold = c->k1_lowrank_fold;                                   // D' = D + E in the image, two products per node row
     g->dscale = g->lr_fold ? p.dscale_fold : p.dscale;
     g->M_pad_d = (int)((2 * nk + 511) / 512 * 512);
     g->lr_pair = c->opt_k1_lowrank_pair && g->M_pad_d == LRP_ROWS;     // one D block: node rows and D rows in one launch
-    static_assert(LRF_ROWS == LRP_ROWS, "the folded pair launch serves the lists the pair launch serves");
+    static_assert(LRF_ROWS == LRP_ROWS && LRN_ROWS == LRP_ROWS, "the folded pair launches serve the lists the pair launch serves");
     return PSA_OK;
 }
 
@@ -258,6 +302,32 @@ int psa_lowrank_plan(const float* k_vectors, int64_t K, const float* mean_pos_al
     if (p.ok && kappa) std::memcpy(kappa, p.kappa, sizeof(p.kappa));
     if (p.ok && L) std::memcpy(L, p.L.data(), p.L.size() * sizeof(float));
     if (p.ok && phi) std::memcpy(phi, p.phi.data(), p.phi.size() * sizeof(float));
+    return PSA_OK;
+}
+
+int psa_lowrank_plan_nodes(const float* k_vectors, int64_t K, const float* mean_pos_all, int64_t N, const int32_t* idx, int64_t n_g,
+                           int32_t nodes, int32_t* ok, double* geo, double* kappa, float* C, float* L, float* phi) {
+    PSA_REQUIRE(K >= 0 && K < (1ll << 29) && N >= 1 && n_g >= 0 && n_g <= (idx ? (int64_t)1 << 30 : N) && ok && geo &&
+                    (K == 0 || k_vectors) && mean_pos_all && (nodes == LOWRANK_NODES || nodes == LOWRANK_NODES_48),
+                "bad argument");
+    LowRankPlan p;
+    PSA_TRY(plan_lowrank(k_vectors, K, mean_pos_all, N, idx, n_g, &p, C, nodes, true));
+    *ok = p.ok;
+    const double g[15] = {p.u[0],  p.u[1],  p.u[2],  p.k0[0], p.k0[1], p.k0[2], p.x_c, p.h_x, p.width, (double)p.interval,
+                          p.d_bound, p.dscale, p.e_bound, p.dscale_fold, p.r_bound};
+    std::memcpy(geo, g, sizeof(g));
+    if (p.ok && kappa) std::memcpy(kappa, p.kappa, (size_t)nodes * sizeof(double));
+    if (p.ok && L) std::memcpy(L, p.L.data(), p.L.size() * sizeof(float));
+    if (p.ok && phi) std::memcpy(phi, p.phi.data(), p.phi.size() * sizeof(float));
+    return PSA_OK;
+}
+
+int psa_lowrank_n48_image(int32_t n_stage, int64_t* index, int64_t* bytes) {
+    PSA_REQUIRE(n_stage >= 1 && n_stage < (1 << 20) && bytes, "bad argument");
+    *bytes = (int64_t)pd16_n48_table_bytes(n_stage);
+    if (index)
+        for (int m = 0; m < LRN_ROWS; ++m)
+            for (int a = 0; a < n_stage * K1_BA; ++a) index[(size_t)m * n_stage * K1_BA + a] = (int64_t)pd16_n48_index(m, a, n_stage);
     return PSA_OK;
 }
 

@@ -275,6 +275,9 @@ int prepare_phase(psa_ctx* c, const GroupView& v, const ProjGeom& g, int64_t k_f
         PSA_TRY(c->d_phase.reserve(pf16_table_bytes(128, g.A_pad)));
         StageTimer    st(c, PSA_T_PHASE);
         const double* f64 = c->d_lr_f64.as<double>();
+        if (g.lr_nodes == 48)     // the 48-node table, and the image of everything its hi piece does not carry
+            return launch_lowrank_tables_n48(c, d_kvec, f64, f64 + 7, c->d_mean_all.as<float>(), d_idx, c->d_lr_L.as<float>(),
+                                             c->d_lr_phi.as<float2>(), c->d_lr_diff.ptr, c->d_phase.ptr, g, g.M_pad_d, g.dscale, g.lr_pair);
         if (g.lr_fold)     // the folded image is built from the node table and the combine's L and phi
             return launch_lowrank_tables_fold(c, d_kvec, f64 + 7 + LOWRANK_NODES, f64, f64 + 7, c->d_mean_all.as<float>(), d_idx,
                                               c->d_lr_L.as<float>(), c->d_lr_phi.as<float2>(), c->d_lr_diff.ptr, c->d_phase.ptr, g,
@@ -336,13 +339,16 @@ static int launch_projection_once(psa_ctx* c, const GroupView& v, ProjGeom g, fl
         if (g.lowrank) {
             // node rows (the 128-row planes kernel on the node table in d_phase) -> d_lr_qn; D pass -> q; q += C Qn (C = phi L)
             ProjGeom gn = g;
-            gn.K = LOWRANK_NODES;
+            gn.K = g.lr_nodes;                                             // (48 nodes: rows 96..127 of the block are padding)
             gn.m_blk = gn.M_pad = 2 * LOWRANK_NODES;
             gn.q_stride = t_count;
-            PSA_REQUIRE(c->d_lr_qn.cap >= (size_t)LOWRANK_NODES * 3 * t_count * sizeof(float2), "node projections not reserved");
+            PSA_REQUIRE(g.lr_nodes == LOWRANK_NODES || (g.lr_nodes == 48 && g.lr_fold), "48 nodes only with the fold");
+            PSA_REQUIRE(c->d_lr_qn.cap >= (size_t)g.lr_nodes * 3 * t_count * sizeof(float2), "node projections not reserved");
             if (g.lr_pair) {      // one 512-row D block: both in one launch of balanced row pairs (the D image is in its layout)
-                PSA_TRY((g.lr_fold ? launch_k1_lowrank_fold : launch_k1_lowrank_pair)(c, pl, c->d_phase.ptr, c->d_lr_diff.ptr,
-                                                                                      c->d_lr_qn.as<float2>(), d_q, g, n_fg, g.dscale));
+                PSA_TRY((g.lr_nodes == 48 ? launch_k1_lowrank_n48
+                         : g.lr_fold      ? launch_k1_lowrank_fold
+                                          : launch_k1_lowrank_pair)(c, pl, c->d_phase.ptr, c->d_lr_diff.ptr, c->d_lr_qn.as<float2>(), d_q,
+                                                                    g, n_fg, g.dscale));
                 ++c->lowrank_pair_launches;
             } else {
                 PSA_TRY((g.lr_fold ? launch_k1_planes_lw2 : launch_k1_planes_lw)(c, pl, c->d_phase.ptr, c->d_lr_qn.as<float2>(), gn, n_fg));

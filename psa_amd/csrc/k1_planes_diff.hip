@@ -26,6 +26,7 @@
 
 #include "k1_f16.h"
 #include "k1_lowrank_fold.h"
+#include "k1_lowrank_n48.h"
 #include "k1_lowrank_pair.h"
 
 namespace psa {
@@ -375,6 +376,138 @@ int launch_lowrank_tables(psa_ctx* c, const float* d_kvec, const double* d_kline
     hipLaunchKernelGGL(node_table_kernel, dim3(LOWRANK_NODES, (g.A_pad + 255) / 256), dim3(256), 0, c->stream, d_geo, d_kappa, d_mean_all,
                        d_idx, g.weights, 1.f / g.wscale, (_Float16*)d_nodes, g.n_g, g.A_pad);
     PSA_HIP_CHECK(hipGetLastError());
+    return PSA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Tables of the 48-node route (psa_set_k1_lowrank_nodes, k1_lowrank_n48.hip)
+// ---------------------------------------------------------------------------------------------
+// node_table_kernel for 48 nodes in the same 128-row block: rows 2 l, 2 l + 1 of node l < 48 with node_table_kernel's
+// arithmetic, rows 96..127 zero in both pieces (the two-product node pass multiplies them and stores nothing of them)
+__global__ void __launch_bounds__(256)
+node_table_n48_kernel(const double* __restrict__ geo, const double* __restrict__ kappa, const float* __restrict__ mean_all,
+                      const int* __restrict__ idx, const float* __restrict__ w, float wnorm, _Float16* __restrict__ Pb, int n_g,
+                      int A_pad) {
+    const int a = blockIdx.y * 256 + threadIdx.x;
+    const int l = blockIdx.x;
+    if (a >= A_pad) return;
+    double cs[2] = {0.0, 0.0};
+    if (a < n_g && l < LOWRANK_NODES_48) {
+        const int    src = idx ? idx[a] : a;
+        const double rx = mean_all[3 * (size_t)src + 0], ry = mean_all[3 * (size_t)src + 1], rz = mean_all[3 * (size_t)src + 2];
+        const double th = (geo[0] * rx + geo[1] * ry + geo[2] * rz) + kappa[l] * ((geo[3] * rx + geo[4] * ry + geo[5] * rz) - geo[6]);
+        sincos(th, &cs[1], &cs[0]);
+        if (w) {
+            const double wa = (double)(w[src] * wnorm);
+            cs[0] *= wa;
+            cs[1] *= wa;
+        }
+    }
+    const int n_stage = A_pad / K1_BA;
+#pragma unroll
+    for (int ri = 0; ri < 2; ++ri) {
+        const double   x = cs[ri] * (double)F16x2::P_SCALE;
+        const _Float16 lead = (_Float16)(float)x;
+        Pb[pf16_tile_index(0, 2 * l + ri, a, 128, n_stage)] = lead;
+        Pb[pf16_tile_index(1, 2 * l + ri, a, 128, n_stage)] = (_Float16)(float)(x - (double)lead);
+    }
+}
+
+// fp64 to float16 with ONE rounding: to float32 rounded to odd (an inexact result takes the neighbour whose last bit is
+// set), which float16's rounding to nearest even then sees as it would see x itself (24 bits >= 11 + 2)
+__device__ __forceinline__ _Float16 f64_to_f16(double x) {
+    float        f = (float)x;
+    const double e = x - (double)f;                                       // exact
+    if (e != 0.0 && f != 0.f) {
+        unsigned b = __float_as_uint(f);
+        if (!(b & 1u)) {
+            const bool grow = (e > 0.0) == !(b >> 31);                    // x lies past f in magnitude
+            f = __uint_as_float(grow ? b + 1u : b - 1u);
+        }
+    }
+    return (_Float16)f;
+}
+
+// The D image of the 48-node route: what the node rows' hi piece does not carry,
+//     D'[j, a] = (P_ref[j, a] w_a - phi_j sum_l L[j, l] W_hi[l, a] / 2^14) dscale,
+// taken in fp64 and rounded ONCE to float16.  P_ref and w_a as in diff_table_kernel; W_hi the float16 hi pieces AS THEY
+// STAND in the node table image Pn (node_table_n48_kernel, which therefore runs first; they carry the weights), exact in
+// fp64; L and phi the plan's float32 tables that the combine reads.  The one expression holds D = (P_ref - P_line) w,
+// E = phi L W_lo, the residual of 48-node interpolation (<= 4.6e-7) and the float32 rounding of phi and L on the v_hi
+// term.  One fixed order per element: fp64 FMAs over l = 0..47 from zero, real and imaginary sums on their own, then
+// phi_r s_r, fma(-phi_i, s_i, .) and phi_r s_i, fma(phi_i, s_r, .) -- a row's bits depend on k_j, the node interval and
+// the group alone, however rows and atoms are tiled.  |D'| <= d_bound + e_bound + r_bound: dscale is the 48-node plan's
+// dscale_fold.  A thread holds one atom's 96 hi pieces as doubles and walks FOLD_JB rows; L and phi are uniform reads.
+// N48: the 48-node pair launch's image (pd16_n48_index, k1_lowrank_n48.h) instead of the D pass's.
+template <bool N48>
+__global__ void __launch_bounds__(256)
+diff_n48_table_kernel(const float* __restrict__ kvec, const float* __restrict__ mean_all, const int* __restrict__ idx,
+                      const float* __restrict__ w, float wnorm, const _Float16* __restrict__ Pn, const float* __restrict__ L,
+                      const float2* __restrict__ phi, _Float16* __restrict__ Db, int K, int n_g, int A_pad, float dscale) {
+    constexpr int NN = LOWRANK_NODES_48;
+    const int     a = blockIdx.y * 256 + threadIdx.x;
+    const int     k0 = blockIdx.x * FOLD_JB;
+    if (a >= A_pad) return;
+    const int n_stage = A_pad / K1_BA;
+    double    wh[2 * NN];
+#pragma unroll
+    for (int m = 0; m < 2 * NN; ++m) wh[m] = (double)(float)Pn[pf16_tile_index(0, m, a, 128, n_stage)];
+    float  rx = 0.f, ry = 0.f, rz = 0.f;
+    double wa = 0.0;
+    if (a < n_g) {
+        const int src = idx ? idx[a] : a;
+        rx = mean_all[3 * (size_t)src + 0], ry = mean_all[3 * (size_t)src + 1], rz = mean_all[3 * (size_t)src + 2];
+        wa = w ? (double)(w[src] * wnorm) : 1.0;
+    }
+    for (int k = k0; k < k0 + FOLD_JB; ++k) {
+        double d[2] = {0.0, 0.0};
+        if (k < K && a < n_g) {
+            const float* Lk = L + (size_t)k * NN;
+            double       sr = 0.0, si = 0.0;
+#pragma unroll
+            for (int l = 0; l < NN; ++l) {
+                const double ll = (double)Lk[l];
+                sr = fma(ll, wh[2 * l], sr);
+                si = fma(ll, wh[2 * l + 1], si);
+            }
+            const float2 ph = phi[k];
+            const double pr = (double)ph.x, pi = (double)ph.y;
+            const double er = fma(-pi, si, pr * sr), ei = fma(pi, sr, pr * si);
+            const float  kx = kvec[3 * k + 0], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
+            const float  arg = __fmaf_rn(kz, rz, __fmaf_rn(ky, ry, __fmul_rn(kx, rx)));
+            float        cs[2];
+            sincosf(arg, &cs[1], &cs[0]);
+            constexpr double inv_p = 1.0 / (double)F16x2::P_SCALE;
+            d[0] = ((double)cs[0] * wa - er * inv_p) * (double)dscale;
+            d[1] = ((double)cs[1] * wa - ei * inv_p) * (double)dscale;
+        }
+        Db[N48 ? pd16_n48_index(2 * k, a, n_stage) : pd16_index(2 * k, a, n_stage)] = f64_to_f16(d[0]);
+        Db[N48 ? pd16_n48_index(2 * k + 1, a, n_stage) : pd16_index(2 * k + 1, a, n_stage)] = f64_to_f16(d[1]);
+    }
+}
+
+// the tables of the 48-node route: the node table first, then the D image from its hi pieces (d_L, d_phi: the 48-node plan's)
+int launch_lowrank_tables_n48(psa_ctx* c, const float* d_kvec, const double* d_geo, const double* d_kappa, const float* d_mean_all,
+                              const int* d_idx, const float* d_L, const float2* d_phi, void* d_diff, void* d_nodes, const ProjGeom& g,
+                              int M_pad_d, float dscale, bool pair) {
+    PSA_REQUIRE(M_pad_d % D_M_BLK == 0 && M_pad_d >= 2 * g.K && g.A_pad % K1_BA == 0, "bad low-rank table geometry");
+    PSA_REQUIRE(!pair || M_pad_d == LRN_ROWS, "the 48-node pair launch's image is one 512-row block");
+    hipLaunchKernelGGL(node_table_n48_kernel, dim3(64, (g.A_pad + 255) / 256), dim3(256), 0, c->stream, d_geo, d_kappa, d_mean_all,
+                       d_idx, g.weights, 1.f / g.wscale, (_Float16*)d_nodes, g.n_g, g.A_pad);
+    PSA_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(pair ? diff_n48_table_kernel<true> : diff_n48_table_kernel<false>,
+                       dim3(M_pad_d / 2 / FOLD_JB, (g.A_pad + 255) / 256), dim3(256), 0, c->stream, d_kvec, d_mean_all, d_idx, g.weights,
+                       1.f / g.wscale, (const _Float16*)d_nodes, d_L, d_phi, (_Float16*)d_diff, g.K, g.n_g, g.A_pad, dscale);
+    PSA_HIP_CHECK(hipGetLastError());
+    if (pair) {      // each role's part ends with its own padding stages
+        const size_t n_stage = (size_t)g.A_pad / K1_BA, a_pad = LRN_PAD_STAGES * LRN_A_UNITS * 1024, b_pad = LRN_PAD_STAGES * LRN_B_UNITS * 1024;
+        static_assert(LRN_ROWS == D_M_BLK, "the 48-node image has the size of one D block");
+        PSA_HIP_CHECK(hipMemsetAsync((char*)d_diff + n_stage * LRN_A_UNITS * 1024, 0, a_pad, c->stream));
+        PSA_HIP_CHECK(hipMemsetAsync((char*)d_diff + pd16_n48_table_bytes((int)n_stage) - b_pad, 0, b_pad, c->stream));
+    } else {
+        PSA_HIP_CHECK(hipMemsetAsync((char*)d_diff + (size_t)M_pad_d * g.A_pad * 2, 0,
+                                     pd16_table_bytes(M_pad_d, g.A_pad) - (size_t)M_pad_d * g.A_pad * 2, c->stream));
+    }
     return PSA_OK;
 }
 

@@ -16,6 +16,7 @@ namespace psa {
 // -- one packed FMA and four bytes of LDS per node and element, where a complex weight would take two and eight.  It is
 // the arithmetic of every row whatever the launch holds besides it, so a list split over calls keeps its bits.  It is
 // not a sum over (float)(phi L): (float)phi and (float)L are rounded apart.
+// NODES = 64 or 48 (psa_set_k1_lowrank_nodes): the same chain over l = 0..NODES-1.
 // A thread holds the 64 node values of one (c, t) in registers and walks every row j; the block stages L 64 rows at a
 // time in LDS (16 KiB, and the 64 phases) and reads it back as broadcasts, one ds_read_b128 = four nodes of a row for
 // the whole wavefront.  Rows go four at a time, four independent chains of one dependent packed FMA per node; the q
@@ -48,10 +49,11 @@ __device__ __forceinline__ float2 phase_add(float2 o, float2 ph, f32x2 s) {
 
 constexpr int COMBINE_R_JB = 64;
 constexpr int COMBINE_R_PF = 2;            // groups of four rows whose q values are in flight ahead of the sums
+template <int NODES>
 __global__ void __launch_bounds__(256)
 lowrank_combine_r_kernel(const float2* __restrict__ Qn, const float* __restrict__ Lm, const float2* __restrict__ phi,
                          float2* __restrict__ q, int64_t T, int64_t q_stride, int64_t qn_stride, int K) {
-    __shared__ __attribute__((aligned(16))) f32x4 ls[COMBINE_R_JB * LOWRANK_NODES / 4];   // 16 KiB: rows j0.., four nodes per entry
+    __shared__ __attribute__((aligned(16))) f32x4 ls[COMBINE_R_JB * NODES / 4];   // 16 KiB at 64 nodes: rows j0.., four nodes per entry
     __shared__ float2 ps[COMBINE_R_JB];
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int     c = blockIdx.y;
@@ -66,9 +68,9 @@ lowrank_combine_r_kernel(const float2* __restrict__ Qn, const float* __restrict_
     for (int d = 0; d < PF; ++d)
 #pragma unroll
         for (int r = 0; r < 4; ++r) nx[d][r] = at(row(4 * d + r));
-    f32x2 v[LOWRANK_NODES];
+    f32x2 v[NODES];
 #pragma unroll
-    for (int l = 0; l < LOWRANK_NODES; ++l) {
+    for (int l = 0; l < NODES; ++l) {
         const float2 x = Qn[((int64_t)l * 3 + c) * qn_stride + tl];
         v[l] = f32x2{x.x, x.y};
     }
@@ -76,7 +78,7 @@ lowrank_combine_r_kernel(const float2* __restrict__ Qn, const float* __restrict_
     for (int j0 = 0; j0 < K; j0 += COMBINE_R_JB) {
         const int nj = K - j0 < COMBINE_R_JB ? K - j0 : COMBINE_R_JB;
         __syncthreads();                                                 // the previous rows are read
-        for (int i = threadIdx.x; i < nj * LOWRANK_NODES / 4; i += 256) ls[i] = l4[(size_t)j0 * (LOWRANK_NODES / 4) + i];
+        for (int i = threadIdx.x; i < nj * NODES / 4; i += 256) ls[i] = l4[(size_t)j0 * (NODES / 4) + i];
         if (threadIdx.x < nj) ps[threadIdx.x] = phi[j0 + threadIdx.x];
         __syncthreads();
         if (!live) continue;                                             // (frames past the end only stage and meet the barriers)
@@ -97,9 +99,9 @@ lowrank_combine_r_kernel(const float2* __restrict__ Qn, const float* __restrict_
             f32x2 s0 = {0.f, 0.f}, s1 = {0.f, 0.f}, s2 = {0.f, 0.f}, s3 = {0.f, 0.f};
             asm volatile("s_nop 0" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3));   // the zeros are VALU results read by a packed FMA
 #pragma unroll
-            for (int i = 0; i < LOWRANK_NODES / 4; ++i) {
-                const f32x4 w0 = ls[jr[0] * (LOWRANK_NODES / 4) + i], w1 = ls[jr[1] * (LOWRANK_NODES / 4) + i];
-                const f32x4 w2 = ls[jr[2] * (LOWRANK_NODES / 4) + i], w3 = ls[jr[3] * (LOWRANK_NODES / 4) + i];
+            for (int i = 0; i < NODES / 4; ++i) {
+                const f32x4 w0 = ls[jr[0] * (NODES / 4) + i], w1 = ls[jr[1] * (NODES / 4) + i];
+                const f32x4 w2 = ls[jr[2] * (NODES / 4) + i], w3 = ls[jr[3] * (NODES / 4) + i];
                 rmac4(s0, s1, s2, s3, f32x2{w0[0], w0[1]}, f32x2{w1[0], w1[1]}, f32x2{w2[0], w2[1]}, f32x2{w3[0], w3[1]}, v[4 * i],
                       v[4 * i + 1]);
                 rmac4(s0, s1, s2, s3, f32x2{w0[2], w0[3]}, f32x2{w1[2], w1[3]}, f32x2{w2[2], w2[3]}, f32x2{w3[2], w3[3]}, v[4 * i + 2],
@@ -114,12 +116,17 @@ lowrank_combine_r_kernel(const float2* __restrict__ Qn, const float* __restrict_
     }
 }
 
+// (the 64-node instantiation first: it stays the file's first kernel)
+template __global__ void lowrank_combine_r_kernel<LOWRANK_NODES>(const float2*, const float*, const float2*, float2*, int64_t, int64_t, int64_t, int);
+template __global__ void lowrank_combine_r_kernel<48>(const float2*, const float*, const float2*, float2*, int64_t, int64_t, int64_t, int);
+
 int launch_lowrank_combine_r(psa_ctx* c, const float2* d_qn, const float* d_L, const float2* d_phi, float2* d_q, const ProjGeom& g,
                              int64_t qn_stride) {
     const int64_t nb = (g.T + 255) / 256;
     PSA_REQUIRE(nb < (1ll << 31) && g.K > 0, "combine grid too large");
-    hipLaunchKernelGGL(lowrank_combine_r_kernel, dim3((unsigned)nb, 3), dim3(256), 0, c->stream, d_qn, d_L, d_phi, d_q, g.T, g.q_stride,
-                       qn_stride, g.K);
+    PSA_REQUIRE(g.lr_nodes == LOWRANK_NODES || g.lr_nodes == 48, "combine: 48 or 64 nodes");
+    hipLaunchKernelGGL(g.lr_nodes == LOWRANK_NODES ? lowrank_combine_r_kernel<LOWRANK_NODES> : lowrank_combine_r_kernel<48>, dim3((unsigned)nb, 3),
+                       dim3(256), 0, c->stream, d_qn, d_L, d_phi, d_q, g.T, g.q_stride, qn_stride, g.K);
     PSA_HIP_CHECK(hipGetLastError());
     return PSA_OK;
 }

@@ -171,6 +171,8 @@ struct ProjGeom {
     bool    lr_pair = false;  // lowrank: node rows and D rows in one launch (k1_lowrank_pair.hip; PSA_OPT_K1_LOWRANK_PAIR)
     bool    lr_fold = false;  // lowrank: the node table's lo piece folded into the D image, two-product node rows (psa_set_k1_lowrank_fold;
                               // dscale is then the plan's dscale_fold)
+    int     lr_nodes = 64;    // lowrank: Chebyshev nodes of the plan, 64 or -- only with lr_fold -- 48 (psa_set_k1_lowrank_nodes:
+                              // the 48-node tables and k1_lowrank_n48.hip)
     // per-atom weights (psa_set_atom_weights), folded into the phase table: (N_tot) float32 on the device, indexed like
     // the mean positions; nullptr = none.  The float16 tables hold w 2^-e and their launches multiply qscale by
     // wscale = 2^e (the float32 and bf16 tables hold w itself)
@@ -288,6 +290,7 @@ struct psa_ctx {
     int64_t      lowrank_launches = 0;          // projection launches that took the route (psa_k1_lowrank_launches)
     int64_t      opt_k1_lowrank_pair;           // PSA_OPT_K1_LOWRANK_PAIR: lists with one 512-row D block through k1_lowrank_pair.hip
     int64_t      lowrank_pair_launches = 0;     // ... of which the pair launch served (psa_k1_lowrank_pair_launches)
+    int          k1_lowrank_nodes = 48;         // psa_set_k1_lowrank_nodes: 48 or 64 Chebyshev nodes; 48 only while the fold is on (k1_lowrank_n48.hip)
     bool         k1_lowrank_fold = true;        // psa_set_k1_lowrank_fold: D' = D + E in the D image, two products per node row (k1_lowrank_fold.hip)
     // its D image, node projections, the combine's L and phi, fp64 inputs (the node table goes into d_phase);
     // released when the route is switched off
@@ -471,6 +474,14 @@ int    launch_lowrank_tables_fold(psa_ctx* c, const float* d_kvec, const double*
 int    launch_k1_lowrank_pair(psa_ctx* c, const void* d_planes, const void* d_nodes, const void* d_diff, float2* d_qn, float2* d_q,
                               const ProjGeom& g, int64_t n_fg, float dscale);
 
+// (psa_set_k1_lowrank_nodes = 48: the 48-node table in the same 128-row block, then the D image from its hi pieces; pair: in
+// the layout of k1_lowrank_n48.h)
+int    launch_lowrank_tables_n48(psa_ctx* c, const float* d_kvec, const double* d_geo, const double* d_kappa, const float* d_mean_all,
+                                 const int* d_idx, const float* d_L, const float2* d_phi, void* d_diff, void* d_nodes, const ProjGeom& g,
+                                 int M_pad_d, float dscale, bool pair);
+// --- k1_lowrank_n48.hip (the folded launch with 48 nodes: 96 node rows + D' rows 0..159 / D' rows 160..511)
+int    launch_k1_lowrank_n48(psa_ctx* c, const void* d_planes, const void* d_nodes, const void* d_diff, float2* d_qn, float2* d_q,
+                             const ProjGeom& g, int64_t n_fg, float dscale);
 // --- k1_lowrank_fold.hip (the same launch on the folded tables: two-product node rows + D' rows 0..127 / D' rows 128..511)
 int    launch_k1_lowrank_fold(psa_ctx* c, const void* d_planes, const void* d_nodes, const void* d_diff, float2* d_qn, float2* d_q,
                               const ProjGeom& g, int64_t n_fg, float dscale);
