@@ -734,6 +734,36 @@ int psa_van_hove_self(psa_ctx* ctx, const double* box /* 9 */, const double* box
                       int64_t origin_step, int32_t unwrap, double dr, int32_t n_r, uint64_t* out_host /* (n_vh, G, n_r + 1) */,
                       size_t out_bytes);
 
+/* The self-overlap per time origin and its two moments over the origins (dynamic heterogeneity): for the lags tau_j
+ * (1 <= n_lags <= 256 of them, each in [0, T-1], duplicates allowed), the cut-off a > 0 and the origins o_k = k s,
+ * k < n_o(tau_j) = (T-1-tau_j) / s + 1,
+ *     Q[j,g,k] = #{ a in g : overlap(a, o_k, tau_j) }                       (uint32)
+ *     S1[j,g]  = sum_k Q[j,g,k],   S2[j,g] = sum_k Q[j,g,k]^2               (uint64)
+ * so that q(t) = S1 / (n_o N_g) and the four-point susceptibility chi_4(t) = (n_o S2 - S1^2) / (n_o^2 N_g), the variance
+ * of Q over the origins used, per atom.  Groups, unwrapping, origins and the budget's blocks of atoms are those of
+ * psa_van_hove_self.  overlap is the van Hove sample with one bin of width a: a_c = float32(u_c[o] - u_c[o_0]) and
+ * b_c = float32(u_c[o+tau] - u_c[o_0]), o_0 the first origin of the origin tile of at most 1024 origins that holds o
+ * (float64 subtraction, one rounding), D and r2 as in psa_displacement_moments, and the sample overlaps iff
+ *     sqrt(r2) (rounded once) times inv_a (rounded once) < 1,   inv_a the float32 nearest to 1/a
+ * -- a strict inequality, the bin 0 of psa_van_hove_self(dr = a, n_r = 1): S1[j,g] equals that count bit for bit.
+ * out_sums (n_lags, G, 2) uint64: S1, S2.  out_origins, unless NULL, (n_lags, G, n_o_max) uint32 with n_o_max = n_o(the
+ * smallest lag): Q, the entries at k >= n_o(tau_j) zero; origins_bytes is its size, 0 with NULL.  An empty group gives
+ * zeros; every group empty gives zeros without a launch.
+ * The count kernel (overlap.hip) takes a lane per origin, eight lags per workgroup and a chunk of atoms, keeps its counts
+ * in registers and writes them with plain stores; an integer reduce adds a group's chunks into Q, which lives in device
+ * memory across the blocks of a call; the last pass forms S1 and S2 in uint64.  No atomics anywhere: the counts are
+ * bit-identical whatever the blocking.  Budget (PSA_OPT_DYNAMIC_WORK_BYTES): the table Q, 4 n_lags G n_o_max bytes, and
+ * beside it u of a block, 24 T bytes per atom; a table that leaves no room for one atom is refused, and the refusal advises
+ * a larger origin_step or fewer lags.
+ * PSA_EINVAL: everything psa_van_hove_self refuses about the context, the box, the groups, the lags, origin_step, unwrap
+ * and the budget; n_lags outside [1, 256]; a cut-off that is not positive and finite or has no float32 reciprocal;
+ * out_bytes or origins_bytes not exact; N_g^2 n_o >= 2^63 (S2 could overflow); a sharded context (psa_comm_init).
+ * Stage times: [5] unwrap, [6] the count kernel, [4] reduce and moments, [7] device->host. */
+int psa_self_overlap(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                     const int64_t* group_start /* G+1 */, int32_t n_groups, const int64_t* lags /* n_lags */, int64_t n_lags,
+                     int64_t origin_step, int32_t unwrap, double cutoff, uint64_t* out_sums /* (n_lags, G, 2): S1, S2 */,
+                     size_t out_bytes, uint32_t* out_origins /* (n_lags, G, n_o_max) or NULL */, size_t origins_bytes);
+
 /* Pair distributions: the radial distribution function g(r), its species-resolved partials and the distinct van Hove
  * function G_d(r,t), as integer counts, from the positions resident in PSA_SLOT_POSITIONS as stored, wrapped or not.
  * H = box (rows = box vectors, r = s H), Hinv = box_inverse.  Species alpha = 0 .. S-1, S <= 8, are listed like the

@@ -25,6 +25,7 @@ from .partial import PartialSpectra, PowderPartialSpectra
 from .self_spectra import draw_atoms
 from .correlations import PowderTimeCorrelations, TimeCorrelations, relaxation_time
 from .displacements import MeanSquareDisplacement, VanHoveSelf
+from .overlap import DynamicOverlap
 from .pairs import RadialDistribution, VanHoveDistinct, max_pair_radius
 from .angles import BondAngleDistribution
 from .order import BondOrder
@@ -36,5 +37,5 @@ from .weights import mass_weights
 
 __version__ = "0.2.0"
 __all__ = ["Trajectory", "SED", "SEDCalculator", "parse_direction", "fast_intensity", "mass_weights", "Segments",
-           "VDOS", "DynamicSpectra", "PowderSpectra", "PartialSpectra", "PowderPartialSpectra", "commensurate_vectors", "shell_bins", "draw_atoms", "TimeCorrelations", "PowderTimeCorrelations", "relaxation_time", "MeanSquareDisplacement", "VanHoveSelf", "RadialDistribution", "VanHoveDistinct", "max_pair_radius", "BondAngleDistribution", "BondOrder", "LocalOrder", "wigner_3j_table", "SolidClusters", "BondPersistence", "CommonNeighbours", "ModeSED", "site_groups", "PeakFit", "fit_peaks", "ModeVectors",
+           "VDOS", "DynamicSpectra", "PowderSpectra", "PartialSpectra", "PowderPartialSpectra", "commensurate_vectors", "shell_bins", "draw_atoms", "TimeCorrelations", "PowderTimeCorrelations", "relaxation_time", "MeanSquareDisplacement", "VanHoveSelf", "DynamicOverlap", "RadialDistribution", "VanHoveDistinct", "max_pair_radius", "BondAngleDistribution", "BondOrder", "LocalOrder", "wigner_3j_table", "SolidClusters", "BondPersistence", "CommonNeighbours", "ModeSED", "site_groups", "PeakFit", "fit_peaks", "ModeVectors",
            "mode_vectors", "spectral_weights", "__version__"]

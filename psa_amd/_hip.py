@@ -73,6 +73,8 @@ MSD_MAX_BINS = 1024    # most bins of a van Hove histogram
 MSD_MAX_VH_LAGS = 64   # most lags of a van Hove call
 MSD_UNWRAP_FRAMES = 64  # frames of an unwrap tile
 MSD_UNWRAP_ATOMS = 16   # atoms of an unwrap tile
+# the caps of the self-overlap kernels (psa_amd/csrc/overlap.hip)
+OVERLAP_MAX_LAGS = 256  # most lags of a self-overlap call
 # the tile and caps of the pair kernels (psa_amd/csrc/pair.hip)
 PAIR_TILE = 256        # alpha-atoms of a workgroup and beta-atoms of a staged tile
 PAIR_MAX_BINS = 1024   # most bins of a pair histogram
@@ -107,6 +109,7 @@ _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
 _f64p = C.POINTER(C.c_double)
 _u64p = C.POINTER(C.c_uint64)
+_u32p = C.POINTER(C.c_uint32)
 _ctx = C.c_void_p
 
 # name -> (restype, argtypes); must list every symbol include/psa_hip.h declares
@@ -186,6 +189,8 @@ SIGNATURES = {
                                            C.c_int64, C.c_int32, _f64p, C.c_size_t]),
     "psa_van_hove_self": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _i64p, C.c_int64,
                                     C.c_int64, C.c_int32, C.c_double, C.c_int32, _u64p, C.c_size_t]),
+    "psa_self_overlap": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _i64p, C.c_int64,
+                                   C.c_int64, C.c_int32, C.c_double, _u64p, C.c_size_t, _u32p, C.c_size_t]),
     "psa_debug_unwrap": (C.c_int, [_ctx, _f64p, _f64p, _i32p, C.c_int64, C.c_int32,
                                    _f64p, _i32p]),
     "psa_pair_histogram": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _i64p, C.c_int64,
@@ -1164,6 +1169,31 @@ class Engine:
                                            held.ctypes.data_as(_i64p), tau.size, int(origin_step), 1 if unwrap else 0, float(dr),
                                            int(n_r), out.ctypes.data_as(_u64p), out.nbytes), "psa_van_hove_self")
         return out
+
+    def self_overlap(self, box, lags, cutoff: float, groups=None, origin_step: int = 1, unwrap: bool = True,
+                     per_origin: bool = False, box_inverse=None):
+        """The self-overlap per time origin and its moments over the origins (psa_self_overlap): (sums (n_lags, G, 2)
+        uint64 -- S1 = sum_k Q and S2 = sum_k Q^2 of Q[j,g,k], the atoms of group g within `cutoff` of where they were
+        `lags[j]` frames before, at the origin k origin_step --, and with `per_origin` Q itself, (n_lags, G, n_o_max)
+        uint32, zero beyond a lag's origins, else None).  Everything else as for `van_hove_self`."""
+        H, inv, keep, ip, start, sp, G = self._displacement_args(box, box_inverse, groups)
+        tau = np.ascontiguousarray(lags, np.int64).ravel()
+        held = tau if tau.size else np.zeros(1, np.int64)
+        out = np.empty((tau.size, G, 2), np.uint64)
+        table = None
+        if per_origin:
+            try:
+                T = self.shape(SLOT_POSITIONS)[0]
+            except PsaHipError:                                  # nothing resident: the call below says so
+                T = 0
+            n_o_max = (T - 1 - int(tau.min())) // max(int(origin_step), 1) + 1 if tau.size and T else 0
+            table = np.empty((tau.size, G, max(n_o_max, 0)), np.uint32)
+        _check(self._lib.psa_self_overlap(self._h, H.ctypes.data_as(_f64p), inv.ctypes.data_as(_f64p), ip, sp, G,
+                                          held.ctypes.data_as(_i64p), tau.size, int(origin_step), 1 if unwrap else 0, float(cutoff),
+                                          out.ctypes.data_as(_u64p), out.nbytes,
+                                          None if table is None else table.ctypes.data_as(_u32p),
+                                          0 if table is None else table.nbytes), "psa_self_overlap")
+        return out, table
 
     def debug_unwrap(self, box, idx=None, unwrap: bool = True, images: bool = True, box_inverse=None):
         """The unwrap pass alone (psa_debug_unwrap): (u (T, n_g, 3) float64, image counts (T, n_g, 3) int32 or None)."""

@@ -37,6 +37,7 @@ from ..covariance import ModeVectors, mode_vectors, spectral_weights
 from ..displacements import (MeanSquareDisplacement, VanHoveSelf, alpha2, check_count, check_lag_frames, check_origin_step,
                              origin_counts, radial_bins)
 from ..dynamic import DynamicSpectra
+from ..overlap import DynamicOverlap
 from .. import angles, clusters, cna, local_order, order, persistence
 from ..angles import BondAngleDistribution
 from ..order import BondOrder
@@ -840,6 +841,39 @@ class SEDCalculator:
         n_o = (n_t - 1 - tau) // step + 1
         samples = n_o[:, None] * np.array([g.size for g in groups], np.int64)[None, :]
         return VanHoveSelf(out[:, :, :n_r].copy(), out[:, :, n_r].copy(), edges, centres, samples, tau, times, groups, self.dt_ps)
+
+    def calculate_overlap(self, lag_frames, cutoff: float,
+                          basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                          basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *, origin_step: int = 1,
+                          unwrap: bool = True, max_atoms: Optional[int] = None, seed: int = 0,
+                          per_origin: bool = False) -> DynamicOverlap:
+        """The self-overlap function and the four-point susceptibility chi_4(t) of atom groups at the lags `lag_frames`
+        (frames, at most 256, each in [0, T - 1]) (not in the reference; definition in psa_amd/overlap.py): per lag and
+        time origin the number Q of atoms of the group with |u[o+t,a] - u[o,a]| < `cutoff`, and its sum and sum of squares
+        over the origins, as exact integers computed on the GPU.  `.q` is the mean overlap, `.chi4` the variance of Q over
+        the origins per atom, `.peak()` its largest value and the time t* of it -- the lifetime of the dynamic
+        heterogeneity.  `per_origin=True` also returns Q per origin.  Unwrapping, groups, `origin_step`, `max_atoms` and
+        the sharded refusal are those of `calculate_van_hove`.  Returns a `psa_amd.DynamicOverlap`."""
+        n_t = self.traj.n_frames
+        tau = check_lag_frames(lag_frames, _hip.OVERLAP_MAX_LAGS, n_t)
+        if isinstance(cutoff, (bool, np.bool_)) or not isinstance(cutoff, (int, float, np.integer, np.floating)) \
+                or not (np.isfinite(cutoff) and float(cutoff) > 0.0):
+            raise ValueError(f"cutoff must be positive and finite, got {cutoff!r}")
+        if not isinstance(per_origin, (bool, np.bool_)):
+            raise TypeError(f"per_origin must be a bool, got {type(per_origin).__name__}")
+        step, groups = self._displacement_groups(basis_atom_indices, basis_atom_types, origin_step, unwrap, max_atoms, seed,
+                                                 "the self-overlap")
+        times = tau.astype(np.float64) * (self.dt_ps if self.dt_ps is not None else 1.0)
+        if groups is None:
+            logger.warning("Cannot calculate the self-overlap: 0 frames or 0 atoms.")
+            n_o = np.zeros(tau.size, np.int64) if n_t == 0 else (n_t - 1 - tau) // step + 1
+            table = np.zeros((tau.size, 1, int(n_o.max(initial=0))), np.uint32) if per_origin else None
+            return DynamicOverlap(np.zeros((tau.size, 1), np.uint64), np.zeros((tau.size, 1), np.uint64), n_o,
+                                  np.zeros(1, np.int64), float(cutoff), tau, times, [np.zeros(0, int)], table, self.dt_ps)
+        out, table = self._displacement_run(lambda eng, box: eng.self_overlap(box, tau, float(cutoff), groups, step, bool(unwrap),
+                                                                              bool(per_origin)))
+        return DynamicOverlap(out[:, :, 0].copy(), out[:, :, 1].copy(), (n_t - 1 - tau) // step + 1,
+                              np.array([g.size for g in groups], np.int64), float(cutoff), tau, times, groups, table, self.dt_ps)
 
     # ------------------------------------------------------------------ pair distributions in real space
     def _pair_call(self, tau, r_max, n_r, basis_atom_indices, basis_atom_types, origin_step, max_atoms, seed, what):

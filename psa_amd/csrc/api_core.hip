@@ -259,6 +259,7 @@ constexpr Scratch SCRATCH[] = {
     PSA_SCRATCH(d_msd_sizes, REAL),
     PSA_SCRATCH(d_msd_lags, INDEX),                        // (a lag is a frame offset)
     PSA_SCRATCH(d_msd_out, REAL),
+    PSA_SCRATCH(d_ov_q, REAL), PSA_SCRATCH(d_ov_sums, REAL),
     PSA_SCRATCH(d_pair_c, REAL),
     PSA_SCRATCH(d_angle_work, INDEX),                      // (the neighbour counts lie beside the lists)
     PSA_SCRATCH(d_angle_edges, REAL), PSA_SCRATCH(d_local_tab, REAL),

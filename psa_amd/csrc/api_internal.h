@@ -25,6 +25,7 @@
 //                    and served radius, the histogram arguments, the atom-list upload, the rows of the integer reduce
 //                    (hist_reduce.hip; the device side of the geometry: min_image.h)
 //   api_msd.hip      MSD moments and the self van Hove function from unwrapped displacements
+//   api_overlap.hip  the self-overlap Q(o, t) per time origin and its two moments over the origins (q(t), chi_4(t))
 //   api_pair.hip     g(r), its partials and the distinct van Hove function
 //   api_angle.hip    bond-angle distributions, coordination statistics and the Steinhardt order parameters q_l
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
@@ -446,6 +447,21 @@ int upload_atom_list(psa_ctx* c, AtomGroups* p, const int32_t* idx);
 // the rows of a table listed group by group -- group g's entries are first[g] .. first[g + 1] - 1, `per` rows each -- as the
 // integer reduce takes them
 int rows_of_groups(const int32_t* first, int n, int64_t per, HistRows* rows);
+// ---- api_msd.hip: what the entries on unwrapped displacements (api_msd.hip, api_overlap.hip) share.
+// group_list_check, unwrap in {0, 1}, and the block rule: p->Ab atoms of 24 T bytes each within the work budget (a budget
+// below one atom is refused)
+int msd_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
+              const int64_t* group_start, int32_t n_groups, int32_t unwrap, AtomGroups* p);
+// the unwrap pass of atoms [a0, a0 + na) of the list into d_msd_u (and, with `images`, d_msd_img)
+int msd_unwrap(psa_ctx* c, const AtomGroups& p, const double* box, const double* box_inverse, int64_t a0, int64_t na, bool unwrap,
+               bool images);
+// the chunk table of the block [a0, a0 + na): every group's part of it in runs of at most `ca` atoms, {first atom of the
+// block, one past the last, group, 0}, group by group; first (G + 1): where each group's chunks begin
+std::vector<int32_t> msd_chunks(const AtomGroups& p, int64_t a0, int64_t na, int64_t ca, int32_t* first);
+// origin slabs and atoms per chunk of a launch with `rows` workgroups per (slab, chunk); a chunk holds at most ca_max atoms
+void msd_split(const AtomGroups& p, int64_t rows, int64_t step, int64_t ca_max, int64_t* n_os, int64_t* ca);
+// the atom list (d_rs_idx) and the groups' sizes (d_msd_sizes)
+int msd_upload_list(psa_ctx* c, AtomGroups* p, const int32_t* idx);
 int    check_weights(psa_ctx* c, int64_t N);            // the context's atom weights fit a slot of N atoms
 void   set_geom_weights(const psa_ctx* c, ProjGeom* g);  // ... and go into a launch's geometry
 int    begin_result(psa_ctx* c, int64_t T, int64_t K_total, int64_t k_offset, bool intensity, char** rows);

@@ -12,8 +12,7 @@
 
 namespace psa {
 
-namespace {
-
+// (msd_check, msd_unwrap, msd_chunks, msd_split and msd_upload_list are shared with api_overlap.hip: api_internal.h)
 int msd_check(psa_ctx* c, const char* entry, const double* box, const double* box_inverse, const int32_t* idx,
               const int64_t* group_start, int32_t n_groups, int32_t unwrap, AtomGroups* p) {
     PSA_TRY(group_list_check(c, entry, box, box_inverse, idx, group_start, n_groups, p));
@@ -76,6 +75,8 @@ int msd_upload_list(psa_ctx* c, AtomGroups* p, const int32_t* idx) {
     StageTimer st(c, PSA_T_H2D);
     return upload(c, c->d_msd_sizes, p->size.data(), p->size.size() * sizeof(int64_t));
 }
+
+namespace {
 
 int moments_run(psa_ctx* c, const double* box, const double* box_inverse, const int32_t* idx, const int64_t* group_start,
                 int32_t n_groups, int64_t n_lags, int64_t origin_step, int32_t unwrap, double* out_host, size_t out_bytes) {

@@ -49,6 +49,7 @@
 #include <algorithm>
 
 #include "min_image.h"
+#include "msd_unit.h"
 #include "psa_ctx.h"
 
 namespace psa {
@@ -151,22 +152,7 @@ msd_unwrap_write_kernel(const float* __restrict__ pos, const int* __restrict__ i
     }
 }
 
-// One (lag, origin) unit of the moments and of the histogram: D, the squares and r2 in the stated order
-struct MsdUnit {
-    float qx, qy, qz, r2;
-};
-__device__ inline MsdUnit msd_unit(float bx, float by, float bz, float ax, float ay, float az) {
-    const float dx = __fsub_rn(bx, ax), dy = __fsub_rn(by, ay), dz = __fsub_rn(bz, az);
-    MsdUnit     q;
-    q.qx = __fmul_rn(dx, dx), q.qy = __fmul_rn(dy, dy), q.qz = __fmul_rn(dz, dz);
-    q.r2 = __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, q.qx));
-    return q;
-}
-
-// chunk table: per chunk its first atom of the block, one past its last, its group
-struct MsdChunk {
-    int a_lo, a_hi, group, pad;
-};
+// (MsdUnit, msd_unit and MsdChunk -- the (lag, origin) unit and the chunk table's entry: msd_unit.h, shared with overlap.hip)
 
 // Grid (lag tiles x origin slabs, chunks).  Origin tile j holds the origins (j NO + k) step, k < NO; slab s of n_os takes
 // the tiles j = s, s + n_os, ...  part[(chunk n_os + slab)][lag][4]

@@ -368,6 +368,11 @@ struct psa_ctx {
     // image counts, the unwrap pass's tile sums and offsets, the groups' sizes, the van Hove lags and the scaled moments.
     psa::DevBuf  d_msd_u, d_msd_img, d_msd_sums, d_msd_offs, d_msd_sizes, d_msd_lags, d_msd_out;
 
+    // the self-overlap (psa_self_overlap; api_overlap.hip): the per-origin counts Q (n_lags, G, n_o_max) uint32, which live
+    // across the blocks of a call (zeroed by the call) and count against opt_dynamic_work_bytes beside u64, and the two
+    // sums over origins (n_lags, G, 2) uint64.  The lags go through d_msd_lags, the chunk partials through d_rs_part.
+    psa::DevBuf  d_ov_q, d_ov_sums;
+
     // pair distributions (psa_pair_histogram, psa_debug_pair_fractions; api_pair.hip): the centred fractional coordinates
     // of a block of origin frames and of their partner frames (2, origins, 3, n_a) float32, held to opt_dynamic_work_bytes.
     psa::DevBuf  d_pair_c;
@@ -669,6 +674,21 @@ int launch_msd_moments_finish(psa_ctx* c, const double* d_acc, const int64_t* d_
 // below 2^32 (the caller's chunk rule) --, launch_hist_reduce adds them to acc (n_vh, G, n_r + 1) uint64
 int launch_msd_hist(psa_ctx* c, const double* d_u, const void* d_chunks, int64_t n_chunks, const int64_t* d_lags, int64_t n_vh,
                     unsigned* d_part, int64_t T, int64_t step, int64_t n_os, float inv_dr, int32_t n_r);
+// --- overlap.hip (psa_self_overlap: per (lag, group, origin) the number of atoms still within the cut-off of where they
+// were, and the first two moments of that count over the origins; the arithmetic and the layouts are in its header)
+constexpr int OVERLAP_MAX_LAGS = 256;  // most lags of a call
+constexpr int OVERLAP_RUN = 8;         // lags of a count workgroup: the origin side of u64 is read once for all of them
+constexpr int OVERLAP_LANES = 256;     // origins of a count workgroup, one per lane: a piece of an origin tile
+// d_chunks as for the moments kernel; d_lags (n_lags) the call's lags; n_o_max the origins of the smallest lag.  The count
+// kernel writes d_part (n_chunks, n_lags, n_o_max) uint32 at the origins k < n_o(lag) and nowhere else; the reduce adds a
+// group's chunks to q (n_lags, G, n_o_max) uint32 at those origins -- group_first as for launch_msd_moments_reduce
+int launch_overlap_count(psa_ctx* c, const double* d_u, const void* d_chunks, int64_t n_chunks, const int64_t* d_lags, int64_t n_lags,
+                         unsigned* d_part, int64_t T, int64_t step, int64_t n_o_max, float inv_a);
+int launch_overlap_reduce(psa_ctx* c, const unsigned* d_part, const int32_t* group_first, const int64_t* d_lags, unsigned* d_q, int64_t T,
+                          int64_t n_lags, int32_t G, int64_t step, int64_t n_o_max);
+// sums (n_lags, G, 2) uint64 = the sums over k < n_o(lag) of q and of q^2
+int launch_overlap_moments(psa_ctx* c, const unsigned* d_q, const int64_t* d_lags, unsigned long long* d_sums, int64_t T, int64_t n_lags,
+                           int32_t G, int64_t step, int64_t n_o_max);
 // --- hist_reduce.hip (the integer reduce of the three histogram families).  The rows of the partials that output row g
 // sums, [lo[g], hi[g]), and what it multiplies the sum by: resolved by the host, passed by value
 constexpr int HIST_REDUCE_MAX_ROWS = 64;   // most output rows of a launch: the ordered pairs of PAIR_MAX_SPECIES species

@@ -24,7 +24,9 @@ o + t <= T - 1} (s = `origin_step`, n_o(t) = (T - 1 - t) // s + 1) and the atoms
   * `radial_density` = counts / (samples dr) is 4 pi r^2 G_s(r,t), which integrates to 1 - overflow / samples;
     `g_s` = counts / (samples x shell volume) is G_s(r,t) itself.
   * Not here: centre-of-mass drift removal, the velocity autocorrelation in time, per-atom output, sharding.  The
-    distinct part G_d and g(r) are in `psa_amd.pairs` (`SEDCalculator.calculate_distinct_van_hove`, `calculate_rdf`).
+    distinct part G_d and g(r) are in `psa_amd.pairs` (`SEDCalculator.calculate_distinct_van_hove`, `calculate_rdf`);
+    the self-overlap per time origin and chi_4(t), its variance over the origins, in `psa_amd.overlap`
+    (`SEDCalculator.calculate_overlap`).
 
 This module is host code only: the result types.  `SEDCalculator.calculate_msd` and `SEDCalculator.calculate_van_hove`
 run the kernels (psa_amd/csrc/msd.hip).
