@@ -27,7 +27,13 @@
 //   api_msd.hip      MSD moments and the self van Hove function from unwrapped displacements
 //   api_overlap.hip  the self-overlap Q(o, t) per time origin and its two moments over the origins (q(t), chi_4(t))
 //   api_pair.hip     g(r), its partials and the distinct van Hove function
-//   api_angle.hip    bond-angle distributions, coordination statistics and the Steinhardt order parameters q_l
+//   api_shell.hip    what the entries on the neighbour shells below share (api_shell.h): the call and its checks, the block
+//                    rule, the layout of the work buffer, the items, the one run body over the blocks of origins
+//   api_angle.hip    bond-angle distributions and coordination statistics
+//   api_order.hip    the Steinhardt order parameters q_l and the local order (q-bar_l, w_l, solid-like bonds)
+//   api_cluster.hip  solid-like clusters: the connected components of the solid atoms
+//   api_persist.hip  bond persistence: neighbour-lifetime and cage correlations
+//   api_cna.hip      common-neighbour analysis: the bonds' signatures and the atoms' structure types
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
 // k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
 #pragma once
@@ -417,10 +423,11 @@ int self_power_run(psa_ctx* c, const SelfPower& w, const SelfFill& fill);
 // work buffer of one block with rows of d.P frames reserved, and everything of w but mirror and finish
 int self_blocks(psa_ctx* c, const SelfCall& p, std::vector<int64_t>* vcut, SelfPower* w);
 
-// ---- api_realspace.hip: what the real-space entries (api_msd.hip, api_pair.hip, api_angle.hip) share.
+// ---- api_realspace.hip: what the real-space entries (api_msd.hip, api_pair.hip and, through api_shell.h, the entries on the
+// neighbour shells) share.
 // The atom groups (species) of a real-space call
 struct AtomGroups {
-    int64_t              T = 0, N = 0, n_a = 0, Ab = 0;   // Ab: atoms (msd) or origins (pair, angle) of a block
+    int64_t              T = 0, N = 0, n_a = 0, Ab = 0;   // Ab: atoms (msd) or origins (pair, shell) of a block
     int32_t              G = 1;
     bool                 listed = false;        // false: all N atoms in order, one group
     const int*           d_idx = nullptr;       // the atom list on the device once upload_atom_list has run (null: not listed)

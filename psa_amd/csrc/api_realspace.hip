@@ -1,5 +1,5 @@
 // What the real-space entries share on the host (api_msd.hip: MSD and the self van Hove function; api_pair.hip: g(r) and
-// the distinct van Hove function; api_angle.hip: bond angles and coordination): the atom groups of a call and their checks,
+// the distinct van Hove function; api_shell.hip: the entries on the neighbour shells): the atom groups of a call and their checks,
 // the box's determinant, inverse and served radius, the arguments of a histogram over lags, the atom-list upload and the
 // row ranges of the integer reduce (hist_reduce.hip).  Every refusal of these entries that does not concern one family
 // alone is worded here, once.

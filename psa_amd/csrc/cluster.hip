@@ -1,5 +1,5 @@
 // Kernels of the solid-like cluster analysis (psa_solid_clusters, psa_debug_cluster_labels; definition: include/psa_hip.h,
-// host side: api_angle.hip): the connected components of the solid atoms over the neighbour lists that the neighbour pass
+// host side: api_cluster.hip): the connected components of the solid atoms over the neighbour lists that the neighbour pass
 // (angle.hip) leaves, from the table of the Q_lm of the order solid_l that qlm_sum_kernel (qlm.hip) leaves.  Four passes on
 // one stream, all integer but the bond test, which is psa_local_order's operation for operation (shell.h).
 //

@@ -1,4 +1,4 @@
-// Kernels of the common-neighbour analysis (psa_common_neighbours; definition: include/psa_hip.h, host side: api_angle.hip):
+// Kernels of the common-neighbour analysis (psa_common_neighbours; definition: include/psa_hip.h, host side: api_cna.hip):
 // per bond a-b_i of the neighbour pass's lists the signature (j, k, l) of Honeycutt-Andersen and Faken-Jonsson -- the common
 // neighbours of a and b_i, the bonds among them, the bonds of the largest connected piece of those --, and per centre the
 // structure type its bonds' signatures add up to (fcc, hcp, bcc, ico, other).

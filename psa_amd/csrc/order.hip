@@ -1,5 +1,5 @@
 // Kernel of the Steinhardt bond-orientational order parameters (psa_bond_order; definition: include/psa_hip.h, host side:
-// api_angle.hip): q_l of the neighbour shell of every atom at every origin, from the lists that the fraction pass
+// api_order.hip): q_l of the neighbour shell of every atom at every origin, from the lists that the fraction pass
 // (pair.hip) and the neighbour pass (angle.hip) leave -- per (origin, centre) the true neighbour count and up to 64 legs
 // {d_x, d_y, d_z, tag}.  By the addition theorem of the spherical harmonics, with n legs and theta_bc the angle between
 // the legs b and c,

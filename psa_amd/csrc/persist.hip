@@ -1,4 +1,4 @@
-// Kernels of the bond persistence (psa_bond_persistence; definition: include/psa_hip.h, host side: api_angle.hip): the pairs
+// Kernels of the bond persistence (psa_bond_persistence; definition: include/psa_hip.h, host side: api_persist.hip): the pairs
 // that the neighbour pass (angle.hip) lists at an origin o, tested again at the later frames o + f -- is the bond still
 // alive (intermittent), has it been alive at every visited frame so far (continuous), how many of its bonds has a centre
 // lost (the cage).

@@ -357,7 +357,7 @@ struct psa_ctx {
     // and the float32 result (1 or 3, n_lags, K or n_bins).  All kept between calls.
     psa::DevBuf  d_corr_tab, d_corr_factor, d_corr_scale, d_corr_in, d_corr_out;
 
-    // real-space structure (api_realspace.hip: what api_msd.hip, api_pair.hip and api_angle.hip share).  One set that every
+    // real-space structure (api_realspace.hip: what api_msd.hip, api_pair.hip and api_shell.hip share).  One set that every
     // call of the three families fills before it reads it and none keeps for the next: the atom list, the item or chunk
     // table, the workgroups' partials (uint32 histograms; float64 moments) and the accumulator that lives across the
     // blocks and lags of a call (zeroed by the call).
@@ -377,14 +377,14 @@ struct psa_ctx {
     // of a block of origin frames and of their partner frames (2, origins, 3, n_a) float32, held to opt_dynamic_work_bytes.
     psa::DevBuf  d_pair_c;
 
-    // bond angles and coordination (psa_angle_histogram, psa_debug_neighbour_lists; api_angle.hip): per origin of a block
-    // the centred fractional coordinates (3, n_a) float32, the neighbour counts (n_a) int32 and the neighbour lists
-    // (n_a, 64, 4) float32 -- 1040 n_a bytes, held to opt_dynamic_work_bytes; outside it the bin edges.  psa_bond_order
-    // uses the same buffer, with its per-atom X (n_a, n_l) int64 behind the counts where the caller asks for them.
+    // the neighbour shells (api_shell.hip's angle_work, for the entries of api_angle, api_order, api_cluster, api_persist and
+    // api_cna.hip): per origin of a block the centred fractional coordinates (3, n_a) float32, the neighbour counts (n_a)
+    // int32 and the neighbour lists (n_a, 64, 4) float32 -- 1040 n_a bytes -- and behind the counts what the entry's
+    // ShellLayout states, all held to opt_dynamic_work_bytes; outside it the bin edges of psa_angle_histogram.
     psa::DevBuf  d_angle_work, d_angle_edges;
-    // psa_local_order, psa_debug_qlm: the same buffer again, the table of the Q_lm (n_a, columns, 2) int64 and the per-atom
-    // rows behind the counts; outside it the normalisations N_lm and the 3j symbols, float64, uploaded by every call.
-    // psa_solid_clusters, psa_debug_cluster_labels: the same buffers, the masks, xi, parent and size behind the table
+    // psa_local_order, psa_debug_qlm (api_order.hip): behind the counts the table of the Q_lm (n_a, columns, 2) int64 and the
+    // per-atom rows; outside the buffer the normalisations N_lm and the 3j symbols, float64, uploaded by every call.
+    // psa_solid_clusters, psa_debug_cluster_labels (api_cluster.hip): the masks, xi, parent and size behind the table
     psa::DevBuf  d_local_tab;
 
     psa::TimingState timing;

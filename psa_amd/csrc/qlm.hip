@@ -1,5 +1,5 @@
 // Kernels of the local order parameters that need the vectors q_lm themselves (psa_local_order, psa_debug_qlm; definition:
-// include/psa_hip.h, host side: api_angle.hip): the neighbour-averaged q-bar_l of Lechner and Dellago, the third-order
+// include/psa_hip.h, host side: api_order.hip): the neighbour-averaged q-bar_l of Lechner and Dellago, the third-order
 // invariants w_l and w-bar_l, and the solid-like bonds of ten Wolde, Ruiz-Montero and Frenkel, from the lists that the
 // fraction pass (pair.hip) and the neighbour pass (angle.hip) leave -- per (origin, centre) the true neighbour count and up
 // to 64 legs {d_x, d_y, d_z, tag}, the tag's low 28 bits the neighbour's row in the atom list.

@@ -12,7 +12,7 @@ from kernel_build import SRC, device_compile
 def test_makefile_lists_the_sources():
     mk = (SRC / "Makefile").read_text()
     srcs = next(ln for ln in mk.splitlines() if ln.startswith("SRCS"))
-    assert " order.hip" in srcs and " api_angle.hip" in srcs              # the host entry stands beside angle_run
+    assert " order.hip" in srcs and " api_order.hip" in srcs              # the file of the host entry
     assert re.search(r"for f in [^;]*\border\b[^;]*; do", mk)                 # the asm list
     assert all((SRC / f).is_file() for f in srcs.split(":=")[1].split())
     assert (SRC / "order.hip").read_text().count("__global__") == 1
