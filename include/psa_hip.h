@@ -1162,8 +1162,8 @@ int psa_bond_persistence(psa_ctx* ctx, const double* box /* 9 */, const double* 
  * Only the positions slot is read.  Atom weights and segments set on the context are ignored, not refused; every result
  * and plan of the other entry points is left as it is.  Stage times: [0] the tables' upload, [5] the fraction pass, [6] the
  * neighbour pass, [1] the signature and the census pass, of these [2] the census pass, [4] reduce, [7] device->host.
- * Not served: adaptive cut-offs per atom, diamond identification, signature tables resolved by the species pair of the
- * bond (bond_signatures with the lists give them on the host), cell lists, sharding. */
+ * Not served: diamond identification, signature tables resolved by the species pair of the bond (bond_signatures with the
+ * lists give them on the host), cell lists, sharding.  Adaptive cut-offs per atom: psa_adaptive_common_neighbours. */
 int psa_common_neighbours(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
                           const int64_t* group_start /* S+1 */, int32_t n_groups, const double* r_cut /* S*S */,
                           int64_t origin_step, uint64_t* signature_counts /* (S, 8, 16, 16) */, size_t signature_bytes,
@@ -1171,6 +1171,72 @@ int psa_common_neighbours(psa_ctx* ctx, const double* box /* 9 */, const double*
                           uint64_t* truncated /* S */, int32_t* types /* (n_o, n_a) or NULL */, int32_t* n /* the same */,
                           size_t atom_bytes /* of each */, uint32_t* bond_signatures /* (n_o, n_a, 64) or NULL */,
                           size_t bond_bytes);
+
+/* Adaptive common-neighbour analysis (Stukowski, Modelling Simul. Mater. Sci. Eng. 20, 045021, 2012): the structure type of
+ * every atom at every time origin with a cut-off of the atom's own, derived from its nearest candidates, so that r_cut is no
+ * longer a radius to tune but a generous candidate radius: it must only contain the 14 nearest atoms (up to the third shell,
+ * usually).
+ * Inputs.  Exactly those of psa_common_neighbours, under the same checks and refusals; origins o = 0, s, 2 s, ... <= T-1.
+ * Candidates.  The candidates of centre a at an origin are the list the neighbour pass of psa_angle_histogram leaves for
+ * r_cut (a scalar or a symmetric (S, S) matrix, 0: not a candidate, nothing beyond max_pair_radius(box)), in the order of
+ * psa_debug_neighbour_lists; n is the true count, at most 64 candidates are held.  Species play no part after this list.
+ *   Truncated.  n > 64: the centre is left out whole: type -1, counted in truncated[alpha].
+ *   Short.  n < 12: type other, no bonds, counted in short_centres[alpha].
+ * Rank.  s_i = d_x^2 + d_y^2 + d_z^2 of leg i, float32, fma(d_z, d_z, fma(d_y, d_y, d_x d_x)): the same bits as the neighbour
+ * pass's r2.  rank(i) = #{j : s_j < s_i} + #{j < i : s_j = s_i}: exact float compares on r2, no root; a tie goes to the earlier
+ * list position (the lower atom column).  rho_k = sqrt(s), float32, of the candidate with rank k.
+ * Test A (n >= 12).  The members are the ranks 0 .. 11.  L = rho_0 + .. + rho_11 added in ascending rank, each add rounded
+ * once; r_A = L * float32(K / 12), K = (1 + sqrt 2) / 2; inv_A = 1.f / r_A, each rounded once.  Two members u, v are bonded
+ * when the float32 chain stated at psa_angle_histogram gives x < 1 for them with inv_A: min_image of their centred
+ * fractions, x = sqrt(r2) inv_A -- the chain of psa_common_neighbours on the same fractions, not a difference of legs (wrong
+ * beyond half a box); a value that is not a number: no bond.  The signature (j, k, l) of each of the 12 bonds a-member is
+ * psa_common_neighbours' own: the common neighbours among the members, the bonds among them, the bonds of the largest
+ * connected component.  Type: fcc 12 x (4,2,1); hcp 6 x (4,2,1) + 6 x (4,2,2); ico 12 x (5,5,5); else other.
+ * Test B (only where test A gave other and n >= 14).  The members are the ranks 0 .. 13.  P = rho_0 + .. + rho_7 and Q = rho_8
+ * + .. + rho_13, each in ascending rank; L = P * float32(2 / sqrt 3) + Q, the product and the sum rounded once each (no fma);
+ * r_B = L * float32(K / 14); inv_B = 1.f / r_B.  Type: bcc 8 x (6,6,6) + 6 x (4,4,4); else other.
+ * Which bonds are counted.  A centre's counted bonds, and its per-atom rows, are those of the test that ran last: the 12 of A
+ * or the 14 of B; its cut-off is that test's r.  Bonds and per-atom rows are indexed by rank, not by list position.
+ * Everything after the adjacency is integers.  (Where rho_11 = rho_12 exactly -- the perfect bcc lattice -- test A's members
+ * are decided by the tie rule; such a centre cannot come out fcc, hcp or ico there, and test B decides.)
+ * Outputs, uint64.  signature_counts (S, 8, 16, 16) per species of the centre, over all origins; signature_outside (S): the
+ * counted bonds whose signature does not fit (k up to 78 among 14 members); type_counts (n_o, S, 5): other, fcc, hcp, bcc,
+ * ico; truncated (S); short_centres (S).  Exactly:
+ *     sum_t type_counts[o,alpha,t] + the centres of alpha truncated at o = N_alpha
+ *     sum signature_counts[alpha] + signature_outside[alpha] = 12 #(centres of alpha whose last test is A) + 14 #(B)
+ * Optionally per atom, in list order (NULL: not asked for): types (n_o, n_a) int32, -1 for a truncated centre; n (n_o, n_a)
+ * int32, the true candidate count (beyond 64 too); cutoffs (n_o, n_a) float32, the r of the test that ran last, NaN where no
+ * test ran (truncated, short); nearest (n_o, n_a, 14) int32, the members' atom columns by rank, -1 beyond the members of the
+ * last test; bond_signatures (n_o, n_a, 14) uint32, j | k << 8 | l << 16 of the bond to the member of that rank, 0xFFFFFFFF
+ * where there is no bond.
+ * As evaluated (acna.hip): the fraction pass and the neighbour pass of psa_angle_histogram; a pass in which a wavefront takes
+ * a centre and lane i its i-th candidate, loaded as one float4: the 64 s_i are parked in LDS and every lane counts its rank
+ * from same-address broadcast reads; a lane with a rank below 14 writes the candidate's fractions, column and rho to LDS slot
+ * `rank`, lanes 0 .. 13 then are the members; the pairs of members go through the leg-pair rounds of psa_common_neighbours
+ * with 12 members, then where test B runs with 14 (the branch is uniform over the wavefront); rows of the adjacency as 32-bit
+ * words in LDS, the flood over masks and the type ballots as there; counts by 32-bit integer adds in LDS, partials with plain
+ * stores, summed in 64-bit integers; psa_common_neighbours' census pass on the types.  No global atomics, no float atomics:
+ * two identical calls, any budget, with or without the per-atom outputs give the same bits; so does any order of the atoms
+ * inside a species on the counts and the types, and on the bonds as sets of (centre, member, word) -- the rank labels of
+ * candidates whose r2 are exactly tied follow the list order.
+ * Budget (PSA_OPT_DYNAMIC_WORK_BYTES): per origin of a block 1040 n_a bytes as for psa_angle_histogram, plus 12 n_a (the
+ * types 4, 4 of padding, the cut-offs 4), plus 112 n_a where nearest or bond_signatures is asked for; a budget below one origin
+ * is refused and the refusal names the bytes needed.
+ * PSA_EINVAL: everything psa_common_neighbours refuses about the context (a sharded one among it), the box, the species,
+ * r_cut, origin_step and the budget; signature_bytes or type_bytes not exact; with types, n or cutoffs, atom_bytes not exact
+ * (4 n_o n_a); with nearest or bond_signatures, bond_bytes not exact (56 n_o n_a); a null required output.  Byte counts of
+ * outputs not asked for are not read.
+ * Only the positions slot is read; every result and plan of the other entry points is left as it is.  Stage times as for
+ * psa_common_neighbours.
+ * Not served: diamond identification, signature tables per species pair, cell lists, sharding. */
+int psa_adaptive_common_neighbours(psa_ctx* ctx, const double* box /* 9 */, const double* box_inverse /* 9 */, const int32_t* idx,
+                                   const int64_t* group_start /* S+1 */, int32_t n_groups, const double* r_cut /* S*S */,
+                                   int64_t origin_step, uint64_t* signature_counts /* (S, 8, 16, 16) */, size_t signature_bytes,
+                                   uint64_t* signature_outside /* S */, uint64_t* type_counts /* (n_o, S, 5) */, size_t type_bytes,
+                                   uint64_t* truncated /* S */, uint64_t* short_centres /* S */,
+                                   int32_t* types /* (n_o, n_a) or NULL */, int32_t* n /* the same */, float* cutoffs /* the same */,
+                                   size_t atom_bytes /* of each */, int32_t* nearest /* (n_o, n_a, 14) or NULL */,
+                                   uint32_t* bond_signatures /* the same */, size_t bond_bytes /* of each */);
 
 /* Pair folding (PSA_OPT_FOLD_PAIRS) as a service for callers that split a k-list themselves
  * (psa_amd/dist.py): kmap[i] = row of k-vector i among the n_unique vectors that need projecting

@@ -32,10 +32,11 @@ from .order import BondOrder
 from .clusters import SolidClusters
 from .persistence import BondPersistence
 from .cna import CommonNeighbours
+from .acna import AdaptiveCommonNeighbours
 from .local_order import LocalOrder, wigner_3j_table
 from .weights import mass_weights
 
 __version__ = "0.2.0"
 __all__ = ["Trajectory", "SED", "SEDCalculator", "parse_direction", "fast_intensity", "mass_weights", "Segments",
-           "VDOS", "DynamicSpectra", "PowderSpectra", "PartialSpectra", "PowderPartialSpectra", "commensurate_vectors", "shell_bins", "draw_atoms", "TimeCorrelations", "PowderTimeCorrelations", "relaxation_time", "MeanSquareDisplacement", "VanHoveSelf", "DynamicOverlap", "RadialDistribution", "VanHoveDistinct", "max_pair_radius", "BondAngleDistribution", "BondOrder", "LocalOrder", "wigner_3j_table", "SolidClusters", "BondPersistence", "CommonNeighbours", "ModeSED", "site_groups", "PeakFit", "fit_peaks", "ModeVectors",
+           "VDOS", "DynamicSpectra", "PowderSpectra", "PartialSpectra", "PowderPartialSpectra", "commensurate_vectors", "shell_bins", "draw_atoms", "TimeCorrelations", "PowderTimeCorrelations", "relaxation_time", "MeanSquareDisplacement", "VanHoveSelf", "DynamicOverlap", "RadialDistribution", "VanHoveDistinct", "max_pair_radius", "BondAngleDistribution", "BondOrder", "LocalOrder", "wigner_3j_table", "SolidClusters", "BondPersistence", "CommonNeighbours", "AdaptiveCommonNeighbours", "ModeSED", "site_groups", "PeakFit", "fit_peaks", "ModeVectors",
            "mode_vectors", "spectral_weights", "__version__"]

@@ -101,6 +101,8 @@ PERSIST_MAX_LAGS = 1024     # most lags of a call
 # the table of the common-neighbour kernels (psa_amd/csrc/cna.hip)
 CNA_TABLE = (8, 16, 16)     # the signatures (j, k, l) the table holds: j < 8, k < 16, l < 16
 CNA_TYPES = ("other", "fcc", "hcp", "bcc", "ico")   # type 0 .. 4
+# the members of the adaptive common-neighbour kernel (psa_amd/csrc/acna.hip)
+ACNA_MEMBERS = 14           # the nearest candidates a centre's per-bond rows hold: 12 of test A, 14 of test B
 UNIQUE_ID_BYTES = 128
 TIMING_NAMES = ("h2d", "phase", "project", "fft", "epilogue", "gather", "transpose", "d2h")
 
@@ -219,6 +221,9 @@ SIGNATURES = {
     "psa_common_neighbours": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p, C.c_int64, _u64p, C.c_size_t,
                                         _u64p, _u64p, C.c_size_t, _u64p, _i32p, _i32p, C.c_size_t, C.POINTER(C.c_uint32),
                                         C.c_size_t]),
+    "psa_adaptive_common_neighbours": (C.c_int, [_ctx, _f64p, _f64p, _i32p, _i64p, C.c_int32, _f64p, C.c_int64, _u64p, C.c_size_t,
+                                                 _u64p, _u64p, C.c_size_t, _u64p, _u64p, _i32p, _i32p, _f32p, C.c_size_t, _i32p,
+                                                 C.POINTER(C.c_uint32), C.c_size_t]),
     "psa_debug_cluster_labels": (C.c_int, [_ctx, C.c_int64, C.c_int64, _i32p, _i32p, C.POINTER(C.c_uint8), _u64p, C.c_int32,
                                            C.c_int32, _u64p, _u64p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
     "psa_k_pairs": (C.c_int, [_f32p, C.c_int64, _i32p, _i32p, _i64p]),
@@ -1423,6 +1428,37 @@ class Engine:
                                                sigs.nbytes if per_atom else 0), "psa_common_neighbours")
         return dict(signature_counts=table, signature_outside=outside, type_counts=census, truncated=trunc, types=types, n=n,
                     bond_signatures=sigs)
+
+    def adaptive_common_neighbours(self, box, r_cut, groups=None, origin_step: int = 1, per_atom: bool = False, box_inverse=None) -> dict:
+        """Adaptive common-neighbour analysis as counts (psa_adaptive_common_neighbours).  `r_cut` (a scalar or symmetric
+        (S, S), 0: not a candidate) is a generous candidate radius: it must only contain the 14 nearest atoms.  The candidates
+        are the neighbours of `angle_histogram`; a centre ranks them by distance, takes the cut-off (1 + sqrt 2) / 2 of the
+        mean distance of its 12 nearest, and the signatures of `common_neighbours` among those 12 make it fcc, hcp or ico;
+        otherwise, with 14 candidates or more, the 14 nearest with the cut-off of the bcc shells make it bcc or other.
+        Returns a dict: signature_counts (S, 8, 16, 16), signature_outside (S,), type_counts (n_o, S, 5), truncated (S,) the
+        centres with more than 64 candidates, left out whole, short (S,) those with fewer than 12 (other, no bonds), all
+        uint64; with `per_atom` types (n_o, n_a) int32 (-1: truncated), n (n_o, n_a) int32 the true candidate counts, cutoffs
+        (n_o, n_a) float32 the cut-off of the test that ran last (NaN: none ran), nearest (n_o, n_a, 14) int32 the members'
+        columns of the atom list by rank (-1 beyond the last test's members) and bond_signatures (n_o, n_a, 14) uint32, j |
+        k << 8 | l << 16 of the bond to that member (0xFFFFFFFF: no bond), else None.  `box`, `groups`, `origin_step` as for
+        `pair_histogram`.  Only positions are read, as stored."""
+        a = self._shell_args(box, box_inverse, groups, r_cut, origin_step)
+        table = np.empty((a.G,) + CNA_TABLE, np.uint64)
+        outside, trunc, short = (np.empty(a.G, np.uint64) for _ in range(3))
+        census = np.empty((a.n_o, a.G, len(CNA_TYPES)), np.uint64)
+        types, n = ((pinned_empty((a.n_o, a.n_a), np.int32) if per_atom else None) for _ in range(2))   # (every cell is written by the call)
+        cuts = pinned_empty((a.n_o, a.n_a), np.float32) if per_atom else None
+        near = pinned_empty((a.n_o, a.n_a, ACNA_MEMBERS), np.int32) if per_atom else None
+        sigs = pinned_empty((a.n_o, a.n_a, ACNA_MEMBERS), np.uint32) if per_atom else None
+        u64 = lambda x: x.ctypes.data_as(_u64p)                                                        # noqa: E731
+        ptr = lambda x, t: None if x is None else x.ctypes.data_as(t)                                  # noqa: E731
+        _check(self._lib.psa_adaptive_common_neighbours(*a.head, int(origin_step), u64(table), table.nbytes, u64(outside), u64(census),
+                                                        census.nbytes, u64(trunc), u64(short), ptr(types, _i32p), ptr(n, _i32p),
+                                                        ptr(cuts, _f32p), types.nbytes if per_atom else 0, ptr(near, _i32p),
+                                                        ptr(sigs, C.POINTER(C.c_uint32)), sigs.nbytes if per_atom else 0),
+               "psa_adaptive_common_neighbours")
+        return dict(signature_counts=table, signature_outside=outside, type_counts=census, truncated=trunc, short=short, types=types,
+                    n=n, cutoffs=cuts, nearest=near, bond_signatures=sigs)
 
     def debug_cluster_labels(self, count, lists, solid, bond_masks=None, link: int = 0, n_sizes: int = 256) -> dict:
         """The graph passes of `solid_clusters` alone on a graph of the caller's (psa_debug_cluster_labels): `count` (n_o, n_a)

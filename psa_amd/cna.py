@@ -29,9 +29,9 @@ identical calls and any order of the atoms inside a species.
     sum signature_counts[alpha] + signature_outside[alpha] = sum_n n coordination_counts[alpha, :, n] of calculate_bond_angles
     sum_t type_counts[o, alpha, t] + the centres of alpha truncated at o = N_alpha
 
-  * Left out: adaptive CNA (a cut-off per atom from its sorted neighbours), diamond identification, signature tables
-    resolved by the species pair of the bond (`bond_signatures` with the neighbour lists give them on the host), cell lists,
-    sharding.
+  * Left out: diamond identification, signature tables resolved by the species pair of the bond (`bond_signatures` with the
+    neighbour lists give them on the host), cell lists, sharding.  Adaptive CNA (a cut-off per atom from its sorted
+    neighbours): psa_amd/acna.py.
 
 This module is host code only: the result type.  `SEDCalculator.calculate_common_neighbours` runs the kernels
 (psa_amd/csrc/angle.hip's neighbour pass, psa_amd/csrc/cna.hip).

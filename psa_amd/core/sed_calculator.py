@@ -38,12 +38,13 @@ from ..displacements import (MeanSquareDisplacement, VanHoveSelf, alpha2, check_
                              origin_counts, radial_bins)
 from ..dynamic import DynamicSpectra
 from ..overlap import DynamicOverlap
-from .. import angles, clusters, cna, local_order, order, persistence
+from .. import acna, angles, clusters, cna, local_order, order, persistence
 from ..angles import BondAngleDistribution
 from ..order import BondOrder
 from ..clusters import SolidClusters
 from ..persistence import BondPersistence
 from ..cna import CommonNeighbours
+from ..acna import AdaptiveCommonNeighbours
 from ..local_order import LocalOrder
 from ..pairs import RadialDistribution, VanHoveDistinct, max_pair_radius
 from .. import lattice
@@ -1204,6 +1205,35 @@ class SEDCalculator:
             return cna.result(cna.empty(1), 0, [np.zeros(0, int)])
         out = self._displacement_run(lambda eng, box: eng.common_neighbours(box, rc, groups, step, bool(per_atom)))
         res = cna.result(out, (self.traj.n_frames - 1) // step + 1, groups)
+        self._refuse_truncated(res.truncated)
+        return res
+
+    # ------------------------------------------------------------------ adaptive common-neighbour analysis (no radius to tune)
+    def calculate_adaptive_common_neighbours(self, r_cut,
+                                             basis_atom_indices: Optional[Union[List[int], List[List[int]], np.ndarray]] = None,
+                                             basis_atom_types: Optional[Union[List[int], List[List[int]]]] = None, *,
+                                             origin_step: int = 1, per_atom: bool = False) -> AdaptiveCommonNeighbours:
+        """Adaptive common-neighbour analysis (not in the reference; definition in psa_amd/acna.py), computed on the GPU from
+        the positions resident in HBM.  `r_cut`, the species and `origin_step` are those of `calculate_common_neighbours`,
+        but `r_cut` is only a generous candidate radius: it must contain the 14 nearest atoms of every centre (up to the
+        third shell, usually) and no more than 64.  Every centre ranks its candidates by distance and takes a cut-off of its
+        own: (1 + sqrt 2) / 2 of the mean distance of its 12 nearest, among which the signatures of
+        `calculate_common_neighbours` make it fcc, hcp or ico; otherwise the 14 nearest with the cut-off of the two bcc
+        shells make it bcc or other.  A strained, expanded or two-phase sample needs no radius tuned by hand.
+        `signature_counts`, `type_counts`, `fraction(type)`, `signature(j, k, l)` and `share(j, k, l)` are integer counts, the
+        same bits for any budget.  `per_atom=True` adds `types`, `neighbours`, `cutoffs`, `nearest`, `bond_signatures`, `atoms`
+        and `atoms_of(origin, type)`.
+
+        Where a centre has more than 64 candidates the call raises ValueError naming the species: choose a smaller `r_cut`
+        (`Engine.adaptive_common_neighbours` returns the numbers instead).  A sharded calculator refuses
+        (NotImplementedError).  Returns a `psa_amd.AdaptiveCommonNeighbours`."""
+        self._check_per_atom(per_atom)
+        rc, step, groups = self._shell_inputs(r_cut, basis_atom_indices, basis_atom_types, origin_step,
+                                              "the adaptive common-neighbour analysis")
+        if groups is None:
+            return acna.result(acna.empty(1), 0, [np.zeros(0, int)])
+        out = self._displacement_run(lambda eng, box: eng.adaptive_common_neighbours(box, rc, groups, step, bool(per_atom)))
+        res = acna.result(out, (self.traj.n_frames - 1) // step + 1, groups)
         self._refuse_truncated(res.truncated)
         return res
 

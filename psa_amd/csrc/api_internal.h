@@ -34,6 +34,7 @@
 //   api_cluster.hip  solid-like clusters: the connected components of the solid atoms
 //   api_persist.hip  bond persistence: neighbour-lifetime and cage correlations
 //   api_cna.hip      common-neighbour analysis: the bonds' signatures and the atoms' structure types
+//   api_acna.hip     adaptive common-neighbour analysis: a cut-off per atom from its nearest candidates
 // What the K1 kernels and their launchers share: k1_tile.h (block map and grid, swizzles: every K1 kernel) and
 // k1_f16.h (the "2 x f16" family: split, images, LDS-DMA, unit ring, fold, chain loop, epilogue, planes-family launch).
 #pragma once

@@ -1,7 +1,8 @@
 // What the entries on the neighbour shells share on the host (api_shell.hip): api_angle.hip (bond angles, coordination),
-// api_order.hip (q_l, the local order), api_cluster.hip (solid clusters), api_persist.hip (bond persistence) and api_cna.hip
-// (common neighbours).  Each of them is one call description (ShellCall), one layout of what it keeps behind the counts
-// (ShellLayout), a pass over the items and, where it has something to take out of a block, an `after`, run by shell_run.
+// api_order.hip (q_l, the local order), api_cluster.hip (solid clusters), api_persist.hip (bond persistence), api_cna.hip
+// (common neighbours) and api_acna.hip (adaptive common neighbours).  Each of them is one call description (ShellCall), one
+// layout of what it keeps behind the counts (ShellLayout), a pass over the items and, where it has something to take out of
+// a block, an `after`, run by shell_run.
 //
 // Budget (PSA_OPT_DYNAMIC_WORK_BYTES = W): per origin of a block the centred fractional coordinates of the listed atoms
 // (12 n_a bytes), their neighbour counts (4 n_a), their neighbour lists (64 x 16 n_a) and what the entry's layout adds per

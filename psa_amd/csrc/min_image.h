@@ -1,8 +1,9 @@
 // What the real-space kernels share (pair.hip: psa_pair_histogram; angle.hip: psa_angle_histogram; msd.hip:
-// psa_van_hove_self; persist.hip: psa_bond_persistence; cna.hip: psa_common_neighbours): the box as float32, the minimum-image displacement of two centred fractional coordinates and the
-// radial bin of a squared length.  The chain, operation for operation, and its error bound are derived in the header of
-// pair.hip; every caller goes through these functions, so what one of them counts below a radius is bit for bit what
-// another one does.
+// psa_van_hove_self; persist.hip: psa_bond_persistence; cna.hip: psa_common_neighbours; acna.hip:
+// psa_adaptive_common_neighbours): the box as float32, the minimum-image displacement of two centred fractional coordinates
+// and the radial bin of a squared length.  The chain, operation for operation, and its error bound are derived in the
+// header of pair.hip; every caller goes through these functions, so what one of them counts below a radius is bit for bit
+// what another one does.
 #pragma once
 #include <hip/hip_runtime.h>
 

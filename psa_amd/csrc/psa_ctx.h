@@ -377,10 +377,10 @@ struct psa_ctx {
     // of a block of origin frames and of their partner frames (2, origins, 3, n_a) float32, held to opt_dynamic_work_bytes.
     psa::DevBuf  d_pair_c;
 
-    // the neighbour shells (api_shell.hip's angle_work, for the entries of api_angle, api_order, api_cluster, api_persist and
-    // api_cna.hip): per origin of a block the centred fractional coordinates (3, n_a) float32, the neighbour counts (n_a)
-    // int32 and the neighbour lists (n_a, 64, 4) float32 -- 1040 n_a bytes -- and behind the counts what the entry's
-    // ShellLayout states, all held to opt_dynamic_work_bytes; outside it the bin edges of psa_angle_histogram.
+    // the neighbour shells (api_shell.hip's angle_work, for the entries of api_angle, api_order, api_cluster, api_persist,
+    // api_cna and api_acna.hip): per origin of a block the centred fractional coordinates (3, n_a) float32, the neighbour
+    // counts (n_a) int32 and the neighbour lists (n_a, 64, 4) float32 -- 1040 n_a bytes -- and behind the counts what the
+    // entry's ShellLayout states, all held to opt_dynamic_work_bytes; outside it the bin edges of psa_angle_histogram.
     psa::DevBuf  d_angle_work, d_angle_edges;
     // psa_local_order, psa_debug_qlm (api_order.hip): behind the counts the table of the Q_lm (n_a, columns, 2) int64 and the
     // per-atom rows; outside the buffer the normalisations N_lm and the 3j symbols, float64, uploaded by every call.
@@ -860,6 +860,18 @@ int launch_cna_signature(psa_ctx* c, const float* d_c, const int* d_count, const
                          int64_t n_ob);
 // d_types as above -> d_out (n_ob, S, CNA_TYPES) uint64, the centres of every species by type (a truncated one in none)
 int launch_cna_census(psa_ctx* c, const int* d_types, unsigned long long* d_out, const AngleSpecies& sp, int64_t n_a, int64_t n_ob);
+// --- acna.hip (psa_adaptive_common_neighbours: a cut-off per centre from its nearest candidates, the signatures on its 12
+// nearest and, where that gives nothing, on its 14 nearest; the arithmetic and the tiling are in its header)
+constexpr int ACNA_MEMBERS_A = 12, ACNA_MEMBERS = 14;   // the members of test A (fcc, hcp, ico) and of test B (bcc)
+// columns of a partial row and of a species' accumulator row: the table, the bonds outside it, the truncated, the short centres
+constexpr int ACNA_ROW_WORDS = CNA_MAX_J * CNA_MAX_K * CNA_MAX_L + 3;
+// d_c, d_count, d_list, d_items, d_types as for launch_cna_signature; d_cut (n_ob, n_a) float32: the cut-off of the test that
+// ran last, not a number where none ran; d_near (n_ob, n_a, 14) int32 and d_sigs (n_ob, n_a, 14) uint32, both or neither: by
+// rank the members' columns (-1 beyond the last test's) and their bonds' words (0xffffffff there); d_part (n_items,
+// ACNA_ROW_WORDS) uint32
+int launch_acna_signature(psa_ctx* c, const float* d_c, const int* d_count, const void* d_list, const void* d_items, int64_t n_items,
+                          int* d_types, float* d_cut, int* d_near, unsigned* d_sigs, unsigned* d_part, const double* box, int64_t n_a,
+                          int64_t n_ob);
 int launch_result_intensity(psa_ctx* c, const float2* d_out, float* d_int, int64_t n_tk);
 int launch_result_chiral_c(psa_ctx* c, const float2* d_out, float* d_phase, int64_t n_tk, int c1, int c2);
 

@@ -1,7 +1,8 @@
 // What the passes over the neighbour lists share (angle.hip: angle_hist_kernel; order.hip: order_hist_kernel; qlm.hip:
-// qlm_sum_kernel, local_order_kernel; cluster.hip: cluster_bonds_kernel, cluster_hook_kernel; persist.hip: persist_step_kernel; cna.hip: cna_signature_kernel): the walk of a wavefront over the centres of its item, the round of leg pairs
-// within a centre, the wave reductions and the launchers' shared guard.  The lists
-// are those the neighbour pass (angle.hip) leaves: per (origin, centre) the true neighbour count and up to 64 legs
+// qlm_sum_kernel, local_order_kernel; cluster.hip: cluster_bonds_kernel, cluster_hook_kernel; persist.hip:
+// persist_step_kernel; cna.hip: cna_signature_kernel; acna.hip: acna_signature_kernel): the walk of a wavefront over the
+// centres of its item, the round of leg pairs within a centre, the wave reductions and the launchers' shared guard.  The
+// lists are those the neighbour pass (angle.hip) leaves: per (origin, centre) the true neighbour count and up to 64 legs
 // {d_x, d_y, d_z, tag}.  A new pass over them uses the walk and the leg-pair step from here.
 #pragma once
 #include "psa_ctx.h"
